@@ -2,6 +2,7 @@
 """Headline benchmark: signature images/sec for one G+D train step (n_critic = 1).
 
     python bench.py --gpus N --steps K --warmup W [--dtype f32|bf16|f16] [--size 64|128] [--batch B] [--latent Z]
+                    [--dump-outputs DIR] [--full]
     python -m torch.distributed.run --nnodes=1 --nproc-per-node N ... bench.py --gpus N ...
 
 Default workload (BASELINE.json configs[1], the configuration the metric is quoted on): reference conv G/D, 64x64x1,
@@ -16,18 +17,25 @@ A "step" = siggan_step_begin / d_apply / g_grads / g_apply through the C ABI.  W
 own shard (weak scaling, per-replica BatchNorm) and the two flat gradient buckets are sum-all-reduced over RCCL INSIDE the
 library (siggan_comm_init; torch.distributed only carries the 128-byte id and the timing barrier).
 
-Timing: W warm-up steps, then `--blocks` (default 10) blocks of EXACTLY K steps, each bracketed by a barrier +
-torch.cuda.synchronize() on both sides and reduced with MAX over ranks; `ms_per_step` / `value` are the MEDIAN block, p10 / p90
-and the first block are reported beside it.
+Timing: W warm-up steps, then ONE block of EXACTLY K timed steps, bracketed by a barrier + torch.cuda.synchronize() on both
+sides and reduced with MAX over ranks; `ms_per_step` / `value` are that block.  A plain run does nothing else: set up, warm
+up, time the K steps, write the outputs (--dump-outputs) and print the line.
 
-Prints ONE JSON line on rank 0 (contract in the task statement) with:
+--dump-outputs DIR: after the timed block, rank 0 writes what a caller of the step holds after its last step -- the 16
+training metrics and the updated G / D weights and G BatchNorm buffers -- as DIR/<name>.npy in float32 (under 64 MB; a
+larger set is cut to a fixed, seeded sample).  Inputs are seeded: the same arguments give the same inputs in every run.
+
+--full adds, after the dump, everything the headline does not need (each leg can still be skipped by its --no-* flag):
+  timing       -- `--blocks` - 1 (default 10 - 1) further blocks of K steps: median / p10 / p90 over all blocks
   roofline     -- the dominant MFMA kernel: algorithmic FLOPs per launch / its mean launch duration, measured live with HIP
                   events stamped by the launch itself (hipExtLaunchKernelGGL) over a second, instrumented pass of K steps run
                   one kernel at a time; `peak` is derived from the device (compute units x clock x FLOP/clk/CU of the dtype's
                   MFMA); `hbm` gives the same kernel's algorithmic bytes / duration against 8 TB/s.  `traffic` (HBM bytes per
                   launch from PMC counters) comes from a committed rocprofv3 pass and is labelled with its file
+  secondary    -- generation throughput (G eval forward) on the same engine and batch
   cpu_baseline -- the oracle's same step (torch CPU, fp32) timed on the host cores of the same box in the same run (rank 0, at
                   every N); `cores` = the threads used, `host` = the box's physical cores / logical CPUs / this job's share
+Without --full these objects are null.
 
 Parity contract of what is measured here (tests/test_engine_gpu.py through the C ABI; numbers of the round's final binary in
 profiles/r04_parity_margins.json, the attribution in profiles/r03_flip_attribution.txt): against the reference run's fixtures
@@ -120,6 +128,33 @@ def cpu_baseline(threads, size, latent, batch, budget_s=12.0):
     return batch * n / dt, n
 
 
+DUMP_LIMIT_BYTES = 60_000_000                     # --dump-outputs: under 64 MB in all, .npy headers included
+
+
+def dump_outputs(out_dir, arrays):
+    """arrays: name -> tensor.  Written as out_dir/<name>.npy in float32.  If they hold more than DUMP_LIMIT_BYTES in all,
+    every array above 64 K elements is cut to the same fraction of its (flattened) elements, at sorted indices drawn from
+    a fixed seed, so that two builds still compare element for element."""
+    import numpy as np
+    small = 1 << 16
+    host = {k: v.detach().float().cpu().numpy().reshape(-1) for k, v in arrays.items()}
+    fixed = sum(a.nbytes for a in host.values() if a.size <= small)
+    large = sum(a.nbytes for a in host.values() if a.size > small)
+    frac = min(1.0, (DUMP_LIMIT_BYTES - fixed) / large) if large else 1.0
+    os.makedirs(out_dir, exist_ok=True)
+    for k, a in host.items():
+        if frac < 1.0 and a.size > small:
+            keep = max(1, int(a.size * frac))
+            a = a[np.sort(np.random.default_rng(1234).choice(a.size, keep, replace=False))]
+        np.save(os.path.join(out_dir, f"{k}.npy"), np.ascontiguousarray(a, dtype=np.float32))
+
+
+def step_outputs(m):
+    """What a caller of the train step holds after it: metrics, updated weights, G BatchNorm running statistics."""
+    return {"metrics": m.metrics, "g_params": m.g_params, "d_params": m.d_params,
+            "g_bn_running_mean": m.g_bn_mean, "g_bn_running_var": m.g_bn_var}
+
+
 def bench_mlp(args):
     """BASELINE.json configs[0] as worded (fully-connected G/D, 28x28, batch 32): a BUILD-DEFINED extension with no reference
     model -- parity unpinned (include/siggan_mlp.h).  Same timing protocol; the CPU leg times the extension's own oracle."""
@@ -132,22 +167,28 @@ def bench_mlp(args):
     real = (torch.rand(batch, 1, size, size, generator=torch.Generator().manual_seed(1)) * 2 - 1).cuda()
     for _ in range(args.warmup):
         m.train_step(real, sync=False)
-    blocks = []
-    for _ in range(max(1, args.blocks)):
+
+    def timed_block():
         torch.cuda.synchronize()
         t0 = time.perf_counter()
         for _ in range(args.steps):
             m.train_step(real, sync=False)
         torch.cuda.synchronize()
-        blocks.append(time.perf_counter() - t0)
-    dt = statistics.median(blocks)
+        return time.perf_counter() - t0
+
+    dt = timed_block()
     met = m.metrics.cpu()
     assert torch.isfinite(met).all()
+    if args.dump_outputs:
+        dump_outputs(args.dump_outputs, step_outputs(m))
+    blocks = [dt]
+    if args.full:
+        blocks += [timed_block() for _ in range(max(1, args.blocks) - 1)]
     dims = [100, *hidden, size * size]
     fwd = sum(2 * a * b for a, b in zip(dims[:-1], dims[1:]))            # G forward = D forward (mirror) FLOP per image, + the 1-wide head
     flop_img = 8 * (fwd - 2 * 100 * hidden[0] + 2 * hidden[0]) + 4 * fwd   # 8 x D_fwd + 4 x G_fwd, as for the conv model
     cpu = None
-    if not args.no_cpu:
+    if args.full and not args.no_cpu:
         from oracle import mlp_oracle as M
         from oracle.siggan_oracle import AdamState
         torch.set_num_threads(min(16, os.cpu_count() or 1))
@@ -171,8 +212,7 @@ def bench_mlp(args):
         "scaling": "weak", "vs_baseline": None, "dtype": "f32", "data": "synthetic",
         "config": {"workload": f"configs[0] as worded: fully-connected G 100-256-512-{size * size} / mirror D, {size}x{size}x1, batch {batch}, fp32 -- "
                                "BUILD-DEFINED extension, the reference has no such model: PARITY UNPINNED", "global_batch": batch, "parallelism": "dp1"},
-        "timing": {"blocks": len(blocks), "stat": "median", "ms_per_step_p10": round(1e3 * pct(blocks, 0.1) / args.steps, 4),
-                   "ms_per_step_p90": round(1e3 * pct(blocks, 0.9) / args.steps, 4)},
+        "timing": timing_summary(blocks, args.steps),
         "achieved_tflops_whole_step": round(imgs / dt * flop_img / 1e12, 4),
         "frac_of_mfma_peak_whole_step": round(imgs / dt * flop_img / 1e12 / peak, 6),
         "roofline": None, "note": "launch-bound: ~0.4 GFLOP per step spread over ~45 launches; no kernel of this path is near any roofline",
@@ -221,22 +261,38 @@ def pct(xs, q):
     return xs[min(len(xs) - 1, max(0, int(round(q * (len(xs) - 1)))))]
 
 
+def timing_summary(block_s, steps):
+    """block_s[0] is the headline block (`ms_per_step`); --full adds the spread over all blocks."""
+    out = {"blocks": len(block_s), "steps_per_block": steps, "headline": "block 1"}
+    if len(block_s) > 1:
+        out.update({"ms_per_step_median": round(1e3 * statistics.median(block_s) / steps, 4),
+                    "ms_per_step_p10": round(1e3 * pct(block_s, 0.1) / steps, 4),
+                    "ms_per_step_p90": round(1e3 * pct(block_s, 0.9) / steps, 4)})
+    return out
+
+
 def main(argv=None):
     argv = sys.argv[1:] if argv is None else list(argv)
     ap = argparse.ArgumentParser()
     ap.add_argument("--gpus", type=int, default=1)
     ap.add_argument("--steps", type=int, default=200)
     ap.add_argument("--warmup", type=int, default=20)
-    ap.add_argument("--blocks", type=int, default=10, help="timed blocks of --steps steps (median / p10 / p90 over them)")
+    ap.add_argument("--blocks", type=int, default=10,
+                    help="with --full: blocks of --steps steps in all, the headline block included (median / p10 / p90 over them)")
+    ap.add_argument("--full", action="store_true",
+                    help="after the headline: further timing blocks, the roofline pass, generation throughput and the CPU "
+                         "baseline (each still skippable by its --no-* flag)")
+    ap.add_argument("--dump-outputs", metavar="DIR", default=None,
+                    help="write the last timed step's metrics, weights and BatchNorm buffers to DIR/<name>.npy (float32)")
     ap.add_argument("--dtype", default="f32", choices=["f32", "bf16", "f16"])
     ap.add_argument("--model", default="conv", choices=["conv", "mlp"],
                     help="conv: the reference's G/D (default, the headline). mlp: the fully-connected extension (configs[0], parity unpinned)")
     ap.add_argument("--size", type=int, default=None, help="64 | 128 (conv); any (mlp, default 28)")
     ap.add_argument("--latent", type=int, default=None)
     ap.add_argument("--batch", type=int, default=64, help="batch PER GPU")
-    ap.add_argument("--no-cpu", action="store_true", help="skip the CPU baseline leg")
-    ap.add_argument("--no-roofline", action="store_true", help="skip the instrumented pass")
-    ap.add_argument("--no-secondary", action="store_true", help="skip the generation-throughput pass (the `secondary` object)")
+    ap.add_argument("--no-cpu", action="store_true", help="--full: skip the CPU baseline leg")
+    ap.add_argument("--no-roofline", action="store_true", help="--full: skip the instrumented pass")
+    ap.add_argument("--no-secondary", action="store_true", help="--full: skip the generation-throughput pass (the `secondary` object)")
     ap.add_argument("--serialize", action="store_true",
                     help="run every pass with side-lane overlap OFF (one kernel at a time): the mode the roofline "
                          "pass always uses, and the one to profile with rocprofv3 so per-kernel durations agree")
@@ -342,10 +398,7 @@ def main(argv=None):
                 host_ev[(i - 1) & 1].synchronize()
                 seen["n"] += 1; seen["d_loss"] += float(host_m[(i - 1) & 1][0]); seen["g_loss"] += float(host_m[(i - 1) & 1][8])
 
-    for i in range(args.warmup):
-        step(i)
-    block_s = []
-    for _ in range(max(1, args.blocks)):
+    def timed_block():
         barrier()
         t0 = time.perf_counter()
         for i in range(args.steps):
@@ -356,17 +409,25 @@ def main(argv=None):
             t = torch.tensor([dt], dtype=torch.float64, device=dev)
             dist.all_reduce(t, op=dist.ReduceOp.MAX)
             dt = float(t.item())
-        block_s.append(dt)
-    dt = statistics.median(block_s)
+        return dt
+
+    for i in range(args.warmup):
+        step(i)
+    dt = timed_block()                                          # the headline: exactly --steps timed steps
     m = eng.metrics.cpu()
     assert torch.isfinite(m).all(), "non-finite training metrics"
+    if rank == 0 and args.dump_outputs:
+        dump_outputs(args.dump_outputs, step_outputs(eng))
+    block_s = [dt]
+    if args.full:
+        block_s += [timed_block() for _ in range(max(1, args.blocks) - 1)]
 
     cus, khz, hbm_bytes = Engine.device_info(local)
     peak = cus * khz * 1e3 * FLOP_PER_CLK_PER_CU[dtype] / 1e12          # TFLOP/s, dense, for this dtype's MFMA
     fpi = flop_per_image(size, latent)
 
     roofline = None
-    if rank == 0 and not args.no_roofline:
+    if rank == 0 and args.full and not args.no_roofline:
         # one kernel at a time: a launch's event-bracketed time is then the kernel's own duration
         # (with overlap on, two MFMA kernels share the chip and each looks proportionally longer)
         eng.set_mode(graph=False, overlap=False)
@@ -418,7 +479,7 @@ def main(argv=None):
                                                     "algorithmic_gbps": round(r["bytes"] / (r["ms"] * 1e-3) / 1e9, 1)} for r in recs}},
         }
     secondary = None
-    if rank == 0 and not args.no_roofline and not args.no_secondary:
+    if rank == 0 and args.full and not args.no_roofline and not args.no_secondary:
         # generation throughput (Generator.forward in eval mode, vanilla_gan_model.py:338-371) beside the headline,
         # same engine / weights / batch; MFMA kernels stamped one at a time as above (profiles/secondary.py has the wider table)
         gflop = {64: 87.06e6, 128: 414.19e6}[size] + 2 * (4096 if size == 64 else 8192) * (latent - (100 if size == 64 else 128))
@@ -443,7 +504,7 @@ def main(argv=None):
                                                                            "tflops": round(r["flops"] / (r["ms"] * 1e-3) / 1e12, 1)} for r in grecs},
                                     "mfma_us_per_batch": round(sum(1e3 * r["ms"] for r in grecs) / 50, 1)}}
     cpu = None
-    if rank == 0 and not args.no_cpu:
+    if rank == 0 and args.full and not args.no_cpu:
         # At every N, on rank 0, while the other ranks wait in the barrier below (their GPUs are idle: nothing is timed any
         # more).  Two thread counts -- this job's CPU share (16 per GPU on the pool's boxes) and 8, the survey container's
         # count; torch's oneDNN convs do not always scale past 8: the faster one is the baseline, the other is quoted in `sample`
@@ -477,10 +538,7 @@ def main(argv=None):
                        "gradient_allreduce": None if world == 1 and not grouped else
                        ("library RCCL (siggan_comm_init)" if transport == "lib" else "torch.distributed between the step halves"
                         + (f" (fallback: {comm_note})" if comm_note else ""))},
-            "timing": {"blocks": len(block_s), "steps_per_block": args.steps, "stat": "median",
-                       "ms_per_step_p10": round(1e3 * pct(block_s, 0.1) / args.steps, 4),
-                       "ms_per_step_p90": round(1e3 * pct(block_s, 0.9) / args.steps, 4),
-                       "ms_per_step_first_block": round(1e3 * block_s[0] / args.steps, 4)},
+            "timing": timing_summary(block_s, args.steps),
             "achieved_tflops_whole_step": round(imgs / dt * fpi / 1e12, 3),
             "frac_of_mfma_peak_whole_step": round(imgs / dt * fpi / 1e12 / (peak * world), 4),
             "final_metrics": {"d_loss": round(float(m[0]), 4), "g_loss": round(float(m[8]), 4)},

@@ -290,3 +290,36 @@ def test_bench_states_the_host_core_count():
     phys, logical, share = bench.host_cores()
     assert logical >= 1 and 1 <= share <= logical
     assert phys is None or 1 <= phys <= logical
+
+
+def test_bench_dump_outputs_is_bounded_and_seeded(tmp_path, monkeypatch):
+    """bench.py --dump-outputs: float32 .npy per array; above the size limit every large array is cut to the same seeded
+    sample (identical from run to run), small ones stay whole, and the files stay under the limit."""
+    import bench
+    gen = torch.Generator().manual_seed(0)
+    arrays = {"metrics": torch.arange(16, dtype=torch.float32), "g_params": torch.randn(300_000, generator=gen),
+              "d_params": torch.randn(500_000, generator=gen, dtype=torch.float64)}
+    bench.dump_outputs(str(tmp_path / "whole"), arrays)
+    for k, v in arrays.items():
+        got = np.load(tmp_path / "whole" / f"{k}.npy")
+        assert got.dtype == np.float32 and np.array_equal(got, v.float().numpy())
+    monkeypatch.setattr(bench, "DUMP_LIMIT_BYTES", 1_000_000)
+    bench.dump_outputs(str(tmp_path / "a"), arrays)
+    bench.dump_outputs(str(tmp_path / "b"), arrays)
+    assert sum(os.path.getsize(tmp_path / "a" / f"{k}.npy") for k in arrays) <= 1_000_000 + 3 * 128
+    assert np.array_equal(np.load(tmp_path / "a" / "metrics.npy"), arrays["metrics"].numpy())
+    for k in arrays:
+        a, b = np.load(tmp_path / "a" / f"{k}.npy"), np.load(tmp_path / "b" / f"{k}.npy")
+        assert a.dtype == np.float32 and np.array_equal(a, b)
+    assert np.isin(np.load(tmp_path / "a" / "g_params.npy"), arrays["g_params"].numpy()).all()
+
+
+def test_fixtures_record_the_thread_count_the_oracle_tests_pin():
+    """test_oracle_golden runs the oracle with FIXTURE_THREADS CPU threads: every fixture made by a reference run says so."""
+    import glob
+    from test_oracle_golden import FIXTURE_THREADS
+    for p in glob.glob(os.path.join(GOLDEN, "golden_*.npz")):
+        f = np.load(p)
+        for k in (k for k in f.files if k.endswith("meta")):
+            threads = json.loads(str(f[k])).get("threads")
+            assert threads in (None, FIXTURE_THREADS), (p, k, threads)

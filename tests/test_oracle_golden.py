@@ -12,6 +12,17 @@ from common import (CASES, I, O, SEED, ablation_groups, assert_close, census_sig
 
 RT, AT = 1e-4, 1e-6
 SEQ3_RT, SEQ3_AT = 1e-4, 1e-5     # chained metrics of the three-step sequence (losses / mean predictions, O(0.1 .. 1))
+FIXTURE_THREADS = 8               # torch CPU threads of the reference run that made the fixtures (their meta 'threads')
+
+
+@pytest.fixture(autouse=True)
+def _fixture_thread_count():
+    """torch's CPU kernels split their work (and so their fp32 summation order) by the thread count: the oracle runs with
+    the count the fixtures were made with, whatever count the host would give it."""
+    n = torch.get_num_threads()
+    torch.set_num_threads(FIXTURE_THREADS)
+    yield
+    torch.set_num_threads(n)
 
 
 @pytest.mark.parametrize("size,latent,batch", CASES)
