@@ -307,7 +307,12 @@ int siggan_prof_read(siggan_ctx *ctx, int32_t idx, char *name, int32_t name_cap,
 
 /* test hook: copy the first n elements of a library-owned workspace tensor (NHWC), converted to fp32, into out_dev:
  * "g_y"/"g_a"/"g_da" (layer 0..Lg), "d_a"/"d_dv" (block 1..Ld), "img", "dpre", "logits",
- * "probs", "dlogit".  Used by tests that localise a parity failure. */
+ * "probs", "dlogit"; "d_noise" (block 1..Ld): the dropout multipliers (0 or 1/keep) of the last D step, [2B][C_l] -- rows
+ * [0, B) the D(real) pass, [B, 2B) the D(fake) pass.  Scalars (n = 1, index 0; the call synchronises the stream):
+ * "rode" -- the batch whose first Discriminator block the last siggan_g_grads took from the riders of the preceding D
+ * update (0: it ran the block itself); "pre_real" -- the batch whose D(real) forward that call started ahead beside the
+ * Generator backward (siggan_stage_real; 0: none); "ride_late" -- 1 once an update's riders did not report in time (sticky:
+ * every later step call returns SIGGAN_E_STATE).  Used by tests that localise a parity failure. */
 int siggan_debug_tensor(siggan_ctx *ctx, const char *name, int32_t index, float *out_dev, int64_t n, void *stream);
 
 #ifdef __cplusplus

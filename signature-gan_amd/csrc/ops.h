@@ -216,8 +216,10 @@ struct ApTable {
 void ap_add(ApTable& t, const ApJob& j);
 // Riders: further workgroups of the same launch run the first Discriminator block's forward of B images with the block's
 // UPDATED weights, which each of them derives for itself from the arena (1088 values); the workgroup that owns those ranges
-// writes them only after every rider has read them (`counter`: one zero-initialised word, left at zero).
-struct ApRide { const float* x; void* out; int B, S, dt; float slope; long long w_off, b_off; unsigned* counter; };
+// writes them only after every rider has read them (`counter`: one zero-initialised word, left at zero).  If the owner's wait
+// is bounded out before every rider has reported, it still takes the whole launch's count off `counter` (the late riders bring
+// it back to zero) and sets `late` (a sticky word of host-visible memory: the step's caller is told, siggan.hip lane_check).
+struct ApRide { const float* x; void* out; int B, S, dt; float slope; long long w_off, b_off; unsigned* counter; unsigned* late; };
 bool launch_adam_pack(const ApTable& t, float* p, float* g, float* m, float* v, DevState* st, float* steps, int ntensors,
                       double tstep, double lr, double beta1, double beta2, double eps, float grad_scale, float clip_max_norm,
                       float* metric_norm, const float* sumsq_partial, float* metric_skipped, float bn_eps,

@@ -1607,7 +1607,8 @@ __device__ __forceinline__ float4 ap_upd4(const ApArena& a, const AdamK& k, size
     return pp;
 }
 static constexpr int AP_TS = 273;          // LDS tile of a CONV unit: [a][b][tap] at a * 273 + b * 17 + tap (odd strides: conflict-free both ways)
-__device__ __forceinline__ void ap_unit(const ApTable& t, const ApArena& a, const AdamK& k, float bn_eps, unsigned bid, unsigned* counter) {
+__device__ __forceinline__ void ap_unit(const ApTable& t, const ApArena& a, const AdamK& k, float bn_eps, unsigned bid, unsigned* counter,
+                                        unsigned* late) {
     extern __shared__ float tile[];
     int j = 0;
     while ((long long)bid >= t.prefix[j + 1]) ++j;
@@ -1661,12 +1662,17 @@ __device__ __forceinline__ void ap_unit(const ApTable& t, const ApArena& a, cons
         if (tid < q.n2) { pb = a.p[q.off2 + tid]; gb = a.g[q.off2 + tid]; mb = a.m[q.off2 + tid]; vb = a.v[q.off2 + tid]; adam_upd(k, pb, gb, mb, vb); }
         if (q.wait > 0) {
             // the riders form these values from the ranges as they are NOW: nothing is written until all of them have read
-            // (bounded: a rider never waits, so the count is reached as soon as the last one has been dispatched)
+            // (bounded: a rider never waits, so the count is reached as soon as the last one has been dispatched).  The count
+            // is taken off, not reset: a rider that reports after the bound ran out brings the word back to zero instead of
+            // releasing the next launch's owner early -- and that rider has formed its values from the updated ranges, so
+            // the bound running out is an error the caller sees (`late`, sticky), not a silently different G step
             if (tid == 0) {
+                int seen = 0;
                 unsigned it = 0;
-                while (__hip_atomic_load(counter, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT) < (unsigned)q.wait && ++it < (1u << 20))
+                while ((seen = (int)__hip_atomic_load(counter, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT)) < q.wait && ++it < (1u << 20))
                     __builtin_amdgcn_s_sleep(16);
-                __hip_atomic_store(counter, 0u, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT);
+                if (seen < q.wait) __hip_atomic_store(late, 1u, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_SYSTEM);
+                __hip_atomic_fetch_sub(counter, (unsigned)q.wait, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT);
             }
             __syncthreads();
         }
@@ -1694,14 +1700,14 @@ __device__ __forceinline__ void ap_unit(const ApTable& t, const ApArena& a, cons
         }
     }
 }
-struct ApRideDev { const float* x; void* out; int B, S; float slope; long long w_off, b_off; };
+struct ApRideDev { const float* x; void* out; int B, S; float slope; long long w_off, b_off; unsigned* late; };
 template <class T, bool RIDE>
 __global__ __launch_bounds__(256) void k_adam_pack(const ApTable t, const ApArena a, DevState* __restrict__ st, float w1, float beta2,
                                                    float w2, float eps, const AdamHost h, float bn_eps, unsigned nprep,
                                                    const ApRideDev r, unsigned* counter) {
     AdamK k; k.w1 = w1; k.beta2 = beta2; k.w2 = w2; k.eps = eps;
     adam_fused_scalars(h, st, k);
-    if (blockIdx.x < nprep) { ap_unit(t, a, k, bn_eps, blockIdx.x, counter); return; }
+    if (blockIdx.x < nprep) { ap_unit(t, a, k, bn_eps, blockIdx.x, counter, r.late); return; }
     if (RIDE) {
         Conv1Ride rd;
         rd.pw = a.p + r.w_off; rd.gw = a.g + r.w_off; rd.mw = a.m + r.w_off; rd.vw = a.v + r.w_off;
@@ -1726,6 +1732,7 @@ bool launch_adam_pack(const ApTable& t, float* p, float* g, float* m, float* v, 
         return true;
     }
     ApRideDev r; r.x = ride->x; r.out = ride->out; r.B = ride->B; r.S = ride->S; r.slope = ride->slope; r.w_off = ride->w_off; r.b_off = ride->b_off;
+    r.late = ride->late;
     const unsigned nride = (unsigned)(ride->B * (ride->S / 4));
     SIGGAN_DT_SWITCH(ride->dt, T, hipLaunchKernelGGL((k_adam_pack<T, true>), dim3(nprep + nride), dim3(256), lds, s, t, a, st, fw1, fb2, fw2, fe,
                                                       h, bn_eps, nprep, r, ride->counter));

@@ -197,6 +197,10 @@ struct siggan_ctx {
     int g_fwd_pending;   // batch of a Generator training forward already enqueued by siggan_step_begin (0: none)
     int conv1_rode;      // batch whose first-Discriminator-block forward (workspace rows [B, 2B), updated weights) the last D apply ran
     float* ride_ctr;     // k_adam_pack's rider count (one word, zero between launches)
+    unsigned* ride_late; // host-visible, sticky: a k_adam_pack owner stopped waiting for its riders (lane_check reports it)
+    unsigned* ride_late_dev;   // (the same word as the device addresses it)
+    int g_rode, g_pre_real;    // what the last siggan_g_grads did (test hook "rode" / "pre_real"): batch whose first-block rows
+                               // the riders had run (0: none), batch whose D(real) it started ahead (0: none)
     double adam_t[2];    // step count of the network's Adam state as the HOST knows it ([0] G, [1] D); valid while adam_t_known
     bool adam_t_known[2];// (reset by siggan_bind / siggan_params_changed: the caller may have written the step tensors)
     int g_r0;            // first workspace row of the Discriminator pass of the last G step (0, or B: beside an early D(real))
@@ -396,6 +400,10 @@ extern "C" int siggan_create(const siggan_config* cfg, siggan_ctx** out) {
     c->dreal_orphan = false; c->lane_err = hipSuccess;
     c->comm = nullptr; c->comm_rank = 0; c->comm_world = 1; c->comm_err = 0;
     c->g_fwd_pending = 0; c->conv1_rode = 0;
+    c->g_rode = c->g_pre_real = 0;
+    HIPCHK(hipHostMalloc((void**)&c->ride_late, sizeof(unsigned), hipHostMallocCoherent | hipHostMallocMapped));
+    *c->ride_late = 0u;
+    HIPCHK(hipHostGetDevicePointer((void**)&c->ride_late_dev, c->ride_late, 0));
     c->zg_stash = 0;
     c->ga_last_B = 0; c->g_r0 = 0;
     c->adam_t_known[0] = c->adam_t_known[1] = false;
@@ -425,6 +433,7 @@ extern "C" int siggan_destroy(siggan_ctx* c) {
     if (c->ev_gfwd) (void)hipEventDestroy(c->ev_gfwd);
     if (c->ev_dreal) (void)hipEventDestroy(c->ev_dreal);
     if (c->ws) (void)hipFree(c->ws);
+    if (c->ride_late) (void)hipHostFree(c->ride_late);
     delete c;
     return SIGGAN_OK;
 }
@@ -689,6 +698,11 @@ static int lane_check(siggan_ctx* c) {
     if (c->comm_err)      // sticky: the communicator is unusable and the replicas have diverged; cleared by siggan_comm_destroy
         return fail(SIGGAN_E_HIP, "ncclAllReduce of the gradient bucket failed (the optimiser update was skipped): %s",
                     rccl()->GetErrorString(c->comm_err));
+    // sticky: set by the device (k_adam_pack) when its owner of the block-1 ranges stopped waiting for the riders -- a late
+    // rider then ran the G step's first Discriminator block on weights updated twice.  Seen once that launch has run.
+    if (c->ride_late && __atomic_load_n(c->ride_late, __ATOMIC_ACQUIRE))
+        return fail(SIGGAN_E_STATE, "riders did not report: the optimiser update's owner of the first Discriminator block stopped "
+                                    "waiting for them (a G step's first block may have used twice-updated weights)");
     if (c->lane_err == hipSuccess) return SIGGAN_OK;
     const hipError_t e = c->lane_err; c->lane_err = hipSuccess;
     return fail(SIGGAN_E_HIP, "an event record / stream wait / prepare table of the step failed: %s", hipGetErrorString(e));
@@ -1222,7 +1236,7 @@ static void phase_apply(siggan_ctx* c, Lanes& L, const PhaseKey& k) {
             const int64_t H = c->S >> 1;
             rd.x = c->img_g; rd.out = c->d_a[1] + (size_t)((int64_t)k.ride * H * H * c->dC[1]) * c->es; rd.B = k.ride; rd.S = c->S;
             rd.dt = c->dt; rd.slope = c->cfg.leaky_slope; rd.w_off = c->d_off[di_w(1)]; rd.b_off = c->d_off[di_b(1)];
-            rd.counter = (unsigned*)c->ride_ctr;
+            rd.counter = (unsigned*)c->ride_ctr; rd.late = c->ride_late_dev;
         }
         const bool ok = (which == 0 ? ap_table_g(c, t) : ap_table_d(c, t, k.ride ? k.ride * (c->S / 4) : 0)) &&
             launch_adam_pack(t, p, g, m, v, c->dev, steps, nt, k.fused_t, k.lr, k.beta1, k.beta2, k.eps, gs, k.clip,
@@ -1538,6 +1552,7 @@ extern "C" int siggan_g_grads(siggan_ctx* c, int32_t batch, const float* z_dev, 
     k.pre_real = c->staged_B == B && c->dreal_B == 0 && (c->mode & SIGGAN_MODE_OVERLAP) != 0 && (c->mode & SIGGAN_MODE_GRAPH) == 0 &&
                  g_prof == nullptr && c->pending == 0 && !c->sn;
     if ((rc = run_phase(c, k, s))) return rc;
+    c->g_rode = k.rode ? B : 0; c->g_pre_real = k.pre_real ? B : 0;
     if (k.pre_real) c->dreal_B = B;
     c->g_fwd_pending = 0;
     c->d_dirty = false;
@@ -1732,6 +1747,17 @@ extern "C" int siggan_debug_tensor(siggan_ctx* c, const char* name, int32_t idx,
     else if (!strcmp(name, "logits")) { *ptr = c->logits; *cap = Bd; typed = false; }
     else if (!strcmp(name, "probs")) { *ptr = c->probs; *cap = Bd; typed = false; }
     else if (!strcmp(name, "dlogit")) { *ptr = c->dlogit; *cap = Bd; typed = false; }
+    else if (!strcmp(name, "d_noise") && dl) { *ptr = c->d_noise[idx]; *cap = Bd * c->dC[idx]; typed = false; }
+    else if (!strcmp(name, "rode") || !strcmp(name, "pre_real") || !strcmp(name, "ride_late")) {
+        // host-side scalars (as floats), read once the stream has run (ride_late is written by the device): synchronous
+        if (n != 1) return fail(SIGGAN_E_INVALID, "debug scalar %s holds 1 float, %lld asked", name, (long long)n);
+        DevGuard dg_(c->cfg.device); HIPCHK(dg_.err);
+        HIPCHK(hipStreamSynchronize((hipStream_t)stream));
+        const float v = !strcmp(name, "rode") ? (float)c->g_rode : !strcmp(name, "pre_real") ? (float)c->g_pre_real
+                                                                                               : (float)__atomic_load_n(c->ride_late, __ATOMIC_ACQUIRE);
+        HIPCHK(hipMemcpy(out_dev, &v, sizeof v, hipMemcpyHostToDevice));
+        return SIGGAN_OK;
+    }
     else return fail(SIGGAN_E_INVALID, "unknown debug tensor %s[%d]", name, idx);
     if (n > capv) return fail(SIGGAN_E_INVALID, "debug tensor %s[%d] holds %lld floats, %lld asked", name, idx, (long long)capv, (long long)n);
     DevGuard dg_(c->cfg.device); HIPCHK(dg_.err);

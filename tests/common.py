@@ -21,6 +21,10 @@ CASES = [(64, 100, 4), (64, 100, 64), (128, 128, 4), (128, 128, 32), (64, 100, 1
          (64, 100, 5),      # an odd batch: ragged row tiles in every GEMM, five samples per BatchNorm statistic
          (128, 128, 5),     # the same at 128x128 (five blocks per network, the 64-channel patch kernel)
          (64, 50, 8)]       # latent_dim % 4 != 0 (the ablation grid's z = 50): the Generator fc's generic (non-MFMA) kernels
+# The workloads bench.py times (profiles/r04_bench_*.json): (dtype, size, latent, batch per GPU) -- the headline, BASELINE
+# configs[3], and the 128x128 fp32 / bf16 / fp16 shards.  The timed path (DataParallelStep.step(real, next_real=real)) is
+# held to the oracle and to the split steps at exactly these shapes.
+TIMED = [("f32", 64, 100, 64), ("f32", 64, 100, 128), ("f32", 128, 128, 32), ("bf16", 64, 100, 64), ("f16", 128, 128, 32)]
 SEED = dict(state_g=101, state_d=202, adam_g=303, adam_d=404, z=11, real=22)
 
 

@@ -42,6 +42,61 @@ def cuda(a):
     return torch.as_tensor(a).to("cuda:0")
 
 
+def oracle_state_of(eng, size, latent):
+    """The engine's complete training state as oracle dicts (copies on the CPU): g_sd (parameters + BatchNorm buffers), d_sd,
+    and both Adam states."""
+    gs, ds = O.g_state_specs(latent, size), O.d_state_specs(size)
+    cp = lambda d: {k: t.detach().float().cpu().clone() for k, t in d.items()}
+    g_par, d_par, bn = cp(eng.views("g")), cp(eng.views("d")), eng.bn_views()
+    g_sd = {}
+    for k, (_, kind) in gs.items():
+        g_sd[k] = g_par[k] if kind == "param" else (bn[k].detach().cpu().clone() if kind == "counter" else bn[k].detach().float().cpu().clone())
+    opts = []
+    for which, specs, sd in (("g", gs, g_sd), ("d", ds, d_par)):
+        o = O.AdamState(O.param_names(specs), sd)
+        o.m, o.v = cp(eng.views(which, "exp_avg")), cp(eng.views(which, "exp_avg_sq"))
+        o.step = int(float(getattr(eng, f"{which}_adam_steps")[0]))
+        opts.append(o)
+    return g_sd, d_par, opts[0], opts[1]
+
+
+# ---- the benchmark's loop (bench.py, --gpus 1) ----------------------------------------------------------------
+def bench_setup(dtype, size, latent, batch):
+    """Engine, DataParallelStep and real batch exactly as bench.py builds them for one GPU: context seed 2 (library RNG),
+    init_reference(seed=0) with fresh Adam state, default execution mode (overlap, no graph), no process group."""
+    from signature_gan_amd.dp import DataParallelStep
+    eng = Engine(latent_dim=latent, image_size=size, max_batch=batch, device="cuda:0", seed=2, dtype=dtype)
+    eng.init_reference(seed=0)
+    dp = DataParallelStep(eng, transport="host")
+    dp.sync_initial_state()
+    gen = torch.Generator(device="cpu").manual_seed(1)
+    real = (torch.rand(batch, 1, size, size, generator=gen) * 2 - 1).to("cuda:0")
+    return eng, dp, real
+
+
+def full_state(eng):
+    """Copies of everything a step changes: both networks' parameters and Adam moments / step counts, the BatchNorm
+    buffers and the 16 metrics."""
+    return {n: getattr(eng, n).clone() for n in ("g_params", "d_params", "g_exp_avg", "g_exp_avg_sq", "d_exp_avg", "d_exp_avg_sq",
+                                                 "g_adam_steps", "d_adam_steps", "g_bn_mean", "g_bn_var", "g_bn_batches", "metrics")}
+
+
+def assert_same_state(a, b, what):
+    for n in a:
+        assert torch.equal(a[n], b[n]), f"{what}: {n} differs"
+
+
+def hip_d_masks(eng, size, batch):
+    """The dropout keep masks the last D step used (debug 'd_noise' > 0): D(real) blocks then D(fake) blocks, (B, C_l) each,
+    in the order the oracle's d_step takes them."""
+    noise = [eng.debug_tensor("d_noise", l, (2 * batch, c)).cpu() for l, c in enumerate(O.D_CHAIN[size], start=1)]
+    return [(t[:batch] > 0).float() for t in noise] + [(t[batch:] > 0).float() for t in noise]
+
+
+def debug_scalar(eng, name):
+    return float(eng.debug_tensor(name, 0, (1,)).item())
+
+
 # ---- sign decisions of the HIP path (DESIGN.md 3: borderline activations) -------------------------------------
 def _nchw(t):
     return t.permute(0, 3, 1, 2).contiguous().cpu()

@@ -6,7 +6,7 @@ import numpy as np
 import pytest
 import torch
 
-from common import (CASES, I, O, SEED, assert_close, census_signs, d_chans, flips_vs_census, load_golden, masks_from, oracle_states,
+from common import (CASES, TIMED, I, O, SEED, assert_close, census_signs, d_chans, flips_vs_census, load_golden, masks_from, oracle_states,
                     probe)
 
 pytestmark = pytest.mark.gpu
@@ -288,22 +288,7 @@ def test_single_steps_in_a_context_for_320_images(tag):
     _single_steps(64, 100, 64, tag, max_batch=BIG_CTX)
 
 
-def _oracle_state_of(eng, size, latent):
-    """The engine's complete training state as oracle dicts (copies on the CPU): g_sd (parameters + BatchNorm buffers), d_sd,
-    and both Adam states."""
-    gs, ds = O.g_state_specs(latent, size), O.d_state_specs(size)
-    cp = lambda d: {k: t.detach().float().cpu().clone() for k, t in d.items()}
-    g_par, d_par, bn = cp(eng.views("g")), cp(eng.views("d")), eng.bn_views()
-    g_sd = {}
-    for k, (_, kind) in gs.items():
-        g_sd[k] = g_par[k] if kind == "param" else (bn[k].detach().cpu().clone() if kind == "counter" else bn[k].detach().float().cpu().clone())
-    opts = []
-    for which, specs, sd in (("g", gs, g_sd), ("d", ds, d_par)):
-        o = O.AdamState(O.param_names(specs), sd)
-        o.m, o.v = cp(eng.views(which, "exp_avg")), cp(eng.views(which, "exp_avg_sq"))
-        o.step = int(float(getattr(eng, f"{which}_adam_steps")[0]))
-        opts.append(o)
-    return g_sd, d_par, opts[0], opts[1]
+from hipcommon import oracle_state_of as _oracle_state_of  # noqa: E402  (shared with test_timed_step_gpu)
 
 
 def _grads_close(eng, which, o_grads, what, tol=1e-4):
@@ -393,18 +378,17 @@ def test_three_step_sequence(size, latent, batch):
     eng.close()
 
 
-def test_execution_modes_are_bitwise_identical():
+def test_execution_modes_are_bitwise_identical(dtype="f32", size=64, latent=100, batch=16):
     """hipGraph replay and side-stream overlap only change scheduling: with injected noise and
     masks the four mode combinations must give bit-identical parameters, moments and metrics,
     also on the replayed (second and third) steps."""
     from hipcommon import cuda, make_engine
-    size, latent, batch = 64, 100, 16
     real = cuda(torch.from_numpy(I.gen_real(batch, size, SEED["real"])))
     masks = [torch.from_numpy(m) for m in I.gen_masks(batch, d_chans(size) * 2, 3)]
     ref = None
     for graph, overlap, pipelined in ((False, False, False), (True, True, False), (True, False, False), (False, True, False),
                                       (False, True, True), (False, False, True)):
-        eng = make_engine(size, latent, batch, warm=True)
+        eng = make_engine(size, latent, batch, warm=True, dtype=dtype)
         eng.set_mode(graph=graph, overlap=overlap)
         mets = []
         for s in range(3):
@@ -428,7 +412,14 @@ def test_execution_modes_are_bitwise_identical():
             assert mets == ref[1]
 
 
-@pytest.mark.parametrize("dtype,size,latent,batch", [("f32", 64, 100, 16), ("bf16", 64, 100, 16), ("f32", 128, 128, 4)])
+@pytest.mark.parametrize("dtype,size,latent,batch", [t for t in TIMED if t[0] == "f32"])
+def test_execution_modes_are_bitwise_identical_at_timed_shapes(dtype, size, latent, batch):
+    """The same at the fp32 workloads bench.py times: tile / split-K choice, the classifier in the split-K epilogue and the
+    number of k_adam_pack's riders (B * S/4: 1024 and 2048 here) all depend on the batch."""
+    test_execution_modes_are_bitwise_identical(dtype, size, latent, batch)
+
+
+@pytest.mark.parametrize("dtype,size,latent,batch", [("f32", 64, 100, 16), ("bf16", 64, 100, 16), ("f32", 128, 128, 4)] + TIMED)
 def test_update_launch_leaves_the_packs_the_prepare_pass_would(dtype, size, latent, batch):
     """k_adam_pack (the optimiser update that also writes the MFMA weight packs, the permuted one-channel weights and the
     BatchNorm eval tables) against k_prepare: after pipelined steps -- whose updates wrote them, the D one with the next
@@ -458,17 +449,16 @@ def test_update_launch_leaves_the_packs_the_prepare_pass_would(dtype, size, late
         assert torch.equal(x, y), f"{name}: the packs written by the update launch differ from the prepare pass'"
 
 
-def test_staged_next_batch_is_bitwise_identical():
+def test_staged_next_batch_is_bitwise_identical(dtype="f32", size=64, latent=100, batch=16):
     """siggan_stage_real: D(real) of step t+1 runs beside the Generator backward of step t.  With the
     library's own RNG (z and dropout drawn on the device) the staged sequence must reproduce the
     un-staged one bit for bit -- parameters, Adam moments, BatchNorm statistics and every metric --
     including when a staged batch is dropped (different tensor passed) or the weights are touched."""
     from hipcommon import cuda, make_engine
-    size, latent, batch = 64, 100, 16
     reals = [cuda(torch.from_numpy(I.gen_real(batch, size, SEED["real"] + 7 * t))) for t in range(5)]
 
     def run(kind):
-        eng = make_engine(size, latent, batch, warm=True)
+        eng = make_engine(size, latent, batch, warm=True, dtype=dtype)
         eng.seed(1234)
         mets = []
         for t in range(4):
@@ -488,6 +478,56 @@ def test_staged_next_batch_is_bitwise_identical():
         assert mets == ref_mets, kind
         for a, b in zip(ref_state, state):
             assert torch.equal(a, b), f"{kind}: staging the next batch changed the result"
+
+
+@pytest.mark.parametrize("dtype,size,latent,batch", TIMED)
+def test_staged_next_batch_is_bitwise_identical_at_timed_shapes(dtype, size, latent, batch):
+    test_staged_next_batch_is_bitwise_identical(dtype, size, latent, batch)
+
+
+@pytest.mark.parametrize("dtype,size,latent,batch", TIMED)
+def test_timed_loop_is_bitwise_the_pipelined_and_the_split_steps(dtype, size, latent, batch):
+    """bench.py's loop as it is written -- DataParallelStep(eng) at world 1 with no process group, step(real, next_real=real),
+    sync=False, library RNG, bench.py's engine and starting state -- bit for bit against the same engine and seed run
+    (a) as the unstaged pipelined step (step_begin / d_apply / g_compute_grads / g_apply, no next batch) and
+    (b) as split steps, d_step(real) + g_step(batch, z_g), over four steps: parameters, both Adam moments and step counts,
+    BatchNorm buffers and all 16 metrics after every step.
+
+    (b) draws its own z and dropout tables but is handed the Generator step's z_g that (a) drew: split and pipelined steps
+    do not draw the same latent batch, by design.  The fc kernel draws z at the RNG counter in force when the Generator's
+    training forward runs, and the counter ticks once per optimiser update; the pipelined step runs that forward in
+    siggan_step_begin, before the D update (counter t), g_step after it (t + 1).  Everything else is drawn at the same
+    counter on both paths -- including the dropout tables of a staged D(real) pass, which the previous G step draws one
+    update ahead (make_noise's ctr_add = 1) -- and that is what (a) against the timed loop checks."""
+    from hipcommon import bench_setup, debug_scalar, full_state, assert_same_state
+    steps = 4
+    eng, dp, real = bench_setup(dtype, size, latent, batch)
+    timed = []
+    for _ in range(steps):
+        dp.step(real, next_real=real)
+        timed.append(full_state(eng))
+    assert debug_scalar(eng, "pre_real") == batch              # the loop staged: it is not the unstaged one below
+    eng.close()
+
+    hp = dp.hp
+    eng, dp, real = bench_setup(dtype, size, latent, batch)
+    z_g = []
+    for s in range(steps):
+        eng.step_begin(real, label_smoothing=hp["ls"])
+        eng.d_apply(hp["lr_d"], hp["beta1"], hp["beta2"], sync=False)
+        eng.g_compute_grads(batch)
+        z_g.append(eng.debug_tensor("z_g", 0, (batch, latent)).clone())
+        eng.g_apply(hp["lr_g"], hp["beta1"], hp["beta2"], sync=False)
+        assert debug_scalar(eng, "pre_real") == 0
+        assert_same_state(timed[s], full_state(eng), f"step {s}: the timed loop vs the unstaged pipelined step")
+    eng.close()
+
+    eng, dp, real = bench_setup(dtype, size, latent, batch)
+    for s in range(steps):
+        eng.d_step(real, sync=False)
+        eng.g_step(batch, z_g[s], sync=False)
+        assert_same_state(timed[s], full_state(eng), f"step {s}: the timed loop vs split steps")
+    eng.close()
 
 
 def test_latent_drawn_inside_the_fc_kernel():
@@ -538,17 +578,16 @@ def test_one_sample_is_refused_where_torch_refuses_it():
     eng.close()
 
 
-def test_abandoned_staged_forward_is_ordered():
+def test_abandoned_staged_forward_is_ordered(dtype="f32", size=64, latent=100, batch=16):
     """A D(real) forward started ahead of time (siggan_stage_real) that no D step consumes must not race with what
     follows: a Discriminator forward on other images right behind the step, then a step on a DIFFERENT batch, give
     exactly what the un-staged sequence gives (the abandoned lane is waited for before its rows / packs are reused)."""
     from hipcommon import cuda, make_engine
-    size, latent, batch = 64, 100, 16
     reals = [cuda(torch.from_numpy(I.gen_real(batch, size, SEED["real"] + 3 * t))) for t in range(3)]
     probe_x = cuda(torch.from_numpy(I.gen_real(batch, size, SEED["real"] + 99)))
 
     def run(staged):
-        eng = make_engine(size, latent, batch, warm=True)
+        eng = make_engine(size, latent, batch, warm=True, dtype=dtype)
         eng.seed(77)
         out = [eng.train_step(reals[0], clip=0.5, next_real=reals[1] if staged else None)]
         out.append(eng.d_forward(probe_x, training=False).clone())       # abandons the forward of reals[1]
@@ -565,6 +604,11 @@ def test_abandoned_staged_forward_is_ordered():
     assert torch.equal(p0, q0)
     for a, b in zip(s0, s1):
         assert torch.equal(a, b)
+
+
+@pytest.mark.parametrize("dtype,size,latent,batch", TIMED)
+def test_abandoned_staged_forward_is_ordered_at_timed_shapes(dtype, size, latent, batch):
+    test_abandoned_staged_forward_is_ordered(dtype, size, latent, batch)
 
 
 def test_rng_position_survives_a_larger_batch_and_is_readable():
