@@ -47,7 +47,8 @@
 extern "C" {
 #endif
 
-#define SIGGAN_ABI_VERSION 3   /* 2: siggan_stage_real, siggan_augment_batch; 3: siggan_config.dtype, siggan_rng_state, siggan_comm_* */
+#define SIGGAN_ABI_VERSION 4   /* 2: siggan_stage_real, siggan_augment_batch; 3: siggan_config.dtype, siggan_rng_state, siggan_comm_*;
+                                * 4: siggan_config.g_leaky_slope (appended) */
 
 enum {
     SIGGAN_OK = 0,
@@ -88,6 +89,12 @@ typedef struct siggan_config {
                              * arena then holds weight_orig, siggan_storage.d_sn_u / d_sn_v the weight_u / weight_v buffers; every
                              * training-mode Discriminator forward runs one power iteration (u, v updated in place), every forward
                              * divides the weights by sigma = u . (W v), and the D step's gradients flow through sigma. */
+    float   g_leaky_slope;  /* the Generator's activation after every BatchNorm (fc block and upsample blocks).  0: ReLU, the
+                             * reference Generator (generator_vanilla_gan.py:107-176).  > 0: LeakyReLU with this negative slope,
+                             * the ablation study's ConfigurableGenerator(activation="leaky_relu", leaky_slope)
+                             * (ablation_vanilla_gan_signatures.py:159-213 UpsampleBlockConfigurable, 216-328
+                             * ConfigurableGenerator); the Discriminator's own LeakyReLU (leaky_slope above) is unaffected.  Must be
+                             * finite and >= 0, else SIGGAN_E_INVALID.  Every mode, dtype, size and step variant supports it. */
 } siggan_config;
 enum { SIGGAN_DTYPE_F32 = 0, SIGGAN_DTYPE_BF16 = 1, SIGGAN_DTYPE_F16 = 2 };
 

@@ -13,7 +13,7 @@ _HERE = os.path.dirname(os.path.abspath(__file__))
 # SIGGAN_LIB_PATH: load another build of the same ABI (A/B measurements of kernel variants); it must exist -- a missing
 # library raises either way, there is nothing to fall back to
 LIB_PATH = os.environ.get("SIGGAN_LIB_PATH") or os.path.join(_HERE, "libsiggan_hip.so")
-ABI_VERSION = 3
+ABI_VERSION = 4
 M_COUNT = 16
 METRIC_INDEX = {"d_loss": 0, "d_loss_real": 1, "d_loss_fake": 2, "d_real_mean": 3, "d_fake_mean": 4,
                 "d_real_acc": 5, "d_fake_acc": 6, "d_grad_norm": 7, "g_loss": 8, "g_fake_mean": 9,
@@ -24,7 +24,7 @@ class Config(C.Structure):
     _fields_ = [("device", C.c_int32), ("latent_dim", C.c_int32), ("image_size", C.c_int32),
                 ("image_channels", C.c_int32), ("max_batch", C.c_int32), ("dropout", C.c_float),
                 ("leaky_slope", C.c_float), ("seed", C.c_uint64), ("dtype", C.c_int32), ("f16_grad_scale", C.c_float),
-                ("spectral_norm", C.c_int32)]
+                ("spectral_norm", C.c_int32), ("g_leaky_slope", C.c_float)]
 
 
 DTYPES = {"f32": 0, "fp32": 0, "float32": 0, "bf16": 1, "bfloat16": 1, "f16": 2, "fp16": 2, "float16": 2}

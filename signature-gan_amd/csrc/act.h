@@ -62,6 +62,21 @@ template <> __device__ __forceinline__ void st4<f16_t>(f16_t* p, f32x4 v) {
 template <class T> __device__ __forceinline__ float ld1(const T* p) { return (float)*p; }
 template <class T> __device__ __forceinline__ void st1(T* p, float v) { *p = (T)v; }
 
+// The Generator's activation: ReLU when the context's slope gs is 0 (the reference Generator), else LeakyReLU(gs) (the ablation
+// study's ConfigurableGenerator).  LK selects at compile time (the launchers instantiate both and pick by gs != 0), so a ReLU
+// kernel is the former ReLU code: fmaxf gives +0 for a negative input where x * 0 would give -0, and the masked gradient is
+// +0, not g * 0.  g_act: the activation of a post-BatchNorm value x.  g_dact: the gradient g through it, the mask re-derived
+// from x.
+template <bool LK> __device__ __forceinline__ float g_act(float x, float gs) { return LK ? (x > 0.f ? x : x * gs) : fmaxf(x, 0.f); }
+template <bool LK> __device__ __forceinline__ float g_dact(float x, float g, float gs) { return x > 0.f ? g : (LK ? g * gs : 0.f); }
+
+// run BODY with the constexpr bool `LK` bound to gs != 0 (the Generator activation's variant, see g_act)
+#define SIGGAN_GS_SWITCH(GS, LK, ...)                                                   \
+    do {                                                                         \
+        if ((GS) != 0.f) { constexpr bool LK = true; __VA_ARGS__; }              \
+        else { constexpr bool LK = false; __VA_ARGS__; }                         \
+    } while (0)
+
 // run BODY with `T` bound to the element type of dtype code DT
 #define SIGGAN_DT_SWITCH(DT, T, ...)                                     \
     do {                                                                 \

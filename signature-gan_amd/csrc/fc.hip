@@ -28,7 +28,7 @@ struct FcFwdArgs {
     const float* W;        // [F][K] torch layout, f = c*16 + hw
     const float* bias;     // [F] torch order
     void* y;               // training: pre-BN output [B][F] (NHWC feature order), element type T
-    void* a;               // relu(BN(y)) [B][F], element type T
+    void* a;               // act(BN(y)) [B][F], element type T (g_act, act.h)
     const float* gamma; const float* beta;       // training: BN affine (torch order)
     float* rmean; float* rvar; int64_t* batches; // training: running statistics (torch order), num_batches_tracked
     float* bn;             // training: out [6*F]: scale | shift | mean | rstd | (2 slots the backward fills)
@@ -37,10 +37,11 @@ struct FcFwdArgs {
     const DevState* st; uint32_t sid;
     int B, K, C0;
     float momentum, eps;
+    float gslope;          // Generator activation slope (0 = ReLU)
 };
 
 // one workgroup = 32 features x all B rows (B <= 32*MT); wave w takes the k-chunks c = w, w+4, ... of 8
-template <class T, int MT>
+template <class T, int MT, bool LK>
 __global__ __launch_bounds__(256) void k_fc_fwd_mfma(const FcFwdArgs p) {
     __shared__ __attribute__((aligned(16))) float red[3][MT][16][64];      // partial accumulators of waves 1..3
     const int tid = threadIdx.x, lane = tid & 63, wave = tid >> 6, li = lane & 31, lh = lane >> 5;
@@ -155,19 +156,23 @@ __global__ __launch_bounds__(256) void k_fc_fwd_mfma(const FcFwdArgs p) {
             if (n >= B) continue;
             const float v = acc[m][r];
             if (!p.bne) st1<T>(yo + (size_t)n * F + fpl, v);
-            st1<T>(ao + (size_t)n * F + fpl, fmaxf(fmaf(v, sc, sf), 0.f));
+            st1<T>(ao + (size_t)n * F + fpl, g_act<LK>(fmaf(v, sc, sf), p.gslope));
         }
 }
 
 bool launch_fc_fwd_fused(int dt, const float* z, const float* W, const float* bias, void* y, void* a, const float* gamma,
                          const float* beta, float* rmean, float* rvar, int64_t* batches, float* bn, const float* bne,
                          float* z_out, const DevState* st, uint32_t sid, int B, int K, int C0, float momentum, float eps,
-                         hipStream_t s) {
+                         float gslope, hipStream_t s) {
     if (B > 256 || (C0 * 16) % 32 != 0 || (!z && (K & 3) != 0)) return false;       // caller falls back to the generic kernels
-    FcFwdArgs p{z, W, bias, y, a, gamma, beta, rmean, rvar, batches, bn, bne, z_out, st, sid, B, K, C0, momentum, eps};
+    FcFwdArgs p{z, W, bias, y, a, gamma, beta, rmean, rvar, batches, bn, bne, z_out, st, sid, B, K, C0, momentum, eps, gslope};
     const dim3 grid(C0 * 16 / 32), blk(256);
     const int mt = (B + 31) / 32;
-#define FCF(T, MT) hipLaunchKernelGGL((k_fc_fwd_mfma<T, MT>), grid, blk, 0, s, p)
+#define FCF(T, MT)                                                                               \
+    do {                                                                                         \
+        if (gslope != 0.f) hipLaunchKernelGGL((k_fc_fwd_mfma<T, MT, true>), grid, blk, 0, s, p); \
+        else hipLaunchKernelGGL((k_fc_fwd_mfma<T, MT, false>), grid, blk, 0, s, p);             \
+    } while (0)
     SIGGAN_DT_SWITCH(dt, T, {
         if (mt <= 1) FCF(T, 1); else if (mt <= 2) FCF(T, 2); else if (mt <= 4) FCF(T, 4); else FCF(T, 8);
     });
@@ -176,19 +181,20 @@ bool launch_fc_fwd_fused(int dt, const float* z, const float* W, const float* bi
 }
 
 // ------------------------------------------------------------------------------------------
-// backward: relu mask + BatchNorm1d backward + dW = dy^T z + db, one workgroup per 32 features
+// backward: activation mask + BatchNorm1d backward + dW = dy^T z + db, one workgroup per 32 features
 // ------------------------------------------------------------------------------------------
 struct FcBwdArgs {
-    const void* da;        // d(relu output) [B][F], element type T
+    const void* da;        // d(activation output) [B][F], element type T
     const void* y;         // pre-BN [B][F], T
     const float* z;        // [B][K]
     float* bn;             // [6F]: scale | shift | mean | rstd (from the forward)
     float* dW; float* db;  // [F][K], [F] torch order
     float* dgamma; float* dbeta;
     int B, K, C0;
+    float gslope;          // Generator activation slope (0 = ReLU)
 };
 
-template <class T>
+template <class T, bool LK>
 __global__ __launch_bounds__(256) void k_fc_bwd_mfma(const FcBwdArgs p) {
     extern __shared__ float sdy[];                 // [Bpad][33] dy of the tile (rows >= B zero), then [Bpad][33] xhat
     __shared__ float s0[8][32], s1[8][32];
@@ -216,7 +222,7 @@ __global__ __launch_bounds__(256) void k_fc_bwd_mfma(const FcBwdArgs p) {
         for (int u = 0; u < 4; ++u) {
             const int n = nb + 8 * u;
             if (n >= Bp) continue;
-            const float g = (n < B && fmaf(yy[u], sc, sf) > 0.f) ? gg[u] : 0.f;
+            const float g = n < B ? g_dact<LK>(fmaf(yy[u], sc, sf), gg[u], p.gslope) : 0.f;
             const float xh = n < B ? (yy[u] - mu) * rs : 0.f;
             sdy[n * 33 + fl] = g; sxh[n * 33 + fl] = xh;
             a0 += g; a1 = fmaf(g, xh, a1);
@@ -280,12 +286,15 @@ __global__ __launch_bounds__(256) void k_fc_bwd_mfma(const FcBwdArgs p) {
 }
 
 bool launch_fc_bwd_fused(int dt, const void* da, const void* y, const float* z, float* bn, float* dW, float* db, float* dgamma,
-                         float* dbeta, int B, int K, int C0, hipStream_t s) {
+                         float* dbeta, int B, int K, int C0, float gslope, hipStream_t s) {
     const int Bp = (B + 1) & ~1;
     const size_t lds = (size_t)2 * Bp * 33 * sizeof(float);      // dy and xhat of the tile
     if (lds > 96 * 1024 || (C0 * 16) % 32 != 0) return false;
-    FcBwdArgs p{da, y, z, bn, dW, db, dgamma, dbeta, B, K, C0};
-    SIGGAN_DT_SWITCH(dt, T, hipLaunchKernelGGL(k_fc_bwd_mfma<T>, dim3(C0 * 16 / 32), dim3(256), lds, s, p));
+    FcBwdArgs p{da, y, z, bn, dW, db, dgamma, dbeta, B, K, C0, gslope};
+    SIGGAN_DT_SWITCH(dt, T, {
+        if (gslope != 0.f) hipLaunchKernelGGL((k_fc_bwd_mfma<T, true>), dim3(C0 * 16 / 32), dim3(256), lds, s, p);
+        else hipLaunchKernelGGL((k_fc_bwd_mfma<T, false>), dim3(C0 * 16 / 32), dim3(256), lds, s, p);
+    });
     return true;
 }
 

@@ -13,10 +13,10 @@ namespace siggan {
 enum Epilogue : int {
     EPI_RAW = 0,          // store the accumulator
     EPI_BIAS_LRELU_DROP,  // leaky(acc + bias[c]) * noise[n,c]         (Discriminator block forward)
-    EPI_AFFINE_RELU,      // relu(acc * scale[c] + shift[c])           (Generator block, BN eval folded)
+    EPI_AFFINE_RELU,      // g_act(acc * scale[c] + shift[c], gslope)  (Generator block, BN eval folded)
     EPI_LRELU_BWD,        // acc * leaky'(aref) * noise[n,c]           (Discriminator input-gradient)
     EPI_BN_BWD_STATS,     // store the accumulator AND the BatchNorm-backward sums of the tensor it is the gradient of (Generator
-                          // input-gradient): per workgroup one partial row of sum(dr) and sum(dr * xhat), dr = relu'(.) * acc with
+                          // input-gradient): per workgroup one partial row of sum(dr) and sum(dr * xhat), dr = g_act'(.) * acc with
                           // the mask re-derived from aref = the pre-BatchNorm tensor y (fma(y, scale, shift) > 0, k_bn_relu's own
                           // expression) and xhat = (y - mean) * rstd -- what k_colreduce<FBnBwd> computes in a pass of its own
 };
@@ -48,7 +48,8 @@ struct GConvArgs {
                           //   dot product of its 1024 stored output values with cls_w to cls_part[workgroup] (P = Ho*Wo*Co / 1024
                           //   consecutive partials per image); launch_gconv returns P, or 0 when the epilogue ran elsewhere (the
                           //   caller then runs k_cls_fwd)
-    float slope;
+    float slope;          // the Discriminator's LeakyReLU slope (EPI_BIAS_LRELU_DROP, EPI_LRELU_BWD)
+    float gslope;         // the Generator's activation slope (EPI_AFFINE_RELU, EPI_BN_BWD_STATS; 0 = ReLU, see g_act in act.h)
     // split-K scratch (optional): nsplit fp32 slabs of the whole output, summed by k_splitk_epilogue
     float* slab;
     int64_t slab_floats;
@@ -65,15 +66,20 @@ __device__ __forceinline__ BnBwdParams bn_bwd_params(const float* __restrict__ b
     q.mu = *reinterpret_cast<const f32x4*>(bnp + 2 * Co + co); q.rs = *reinterpret_cast<const f32x4*>(bnp + 3 * Co + co);
     return q;
 }
-template <class T>
-__device__ __forceinline__ void bn_bwd_stat_terms(const f32x4 v, const f32x4 y, const BnBwdParams& q, f32x4& s0, f32x4& s1) {
+template <class T, bool LK>
+__device__ __forceinline__ void bn_bwd_stat_terms(const f32x4 v, const f32x4 y, const BnBwdParams& q, float gs, f32x4& s0, f32x4& s1) {
 #pragma unroll
     for (int e = 0; e < 4; ++e) {
         const float vq = (float)(T)v[e];
-        const float d = fmaf(y[e], q.sc[e], q.sf[e]) > 0.f ? vq : 0.f;
+        const float d = g_dact<LK>(fmaf(y[e], q.sc[e], q.sf[e]), vq, gs);
         s0[e] += d;
         s1[e] = fmaf(d, (y[e] - q.mu[e]) * q.rs[e], s1[e]);
     }
+}
+// the Generator activation's variant matters only to the epilogues that form it or its mask: a launch takes the LeakyReLU
+// instantiation (LK = true) of its kernel exactly when this holds (g_act, act.h)
+__host__ __device__ inline bool gen_lk(const GConvArgs& a) {
+    return a.gslope != 0.f && (a.epi == EPI_AFFINE_RELU || a.epi == EPI_BN_BWD_STATS);
 }
 
 // slab[z][i][tap*Cl + l] = sum_{pix in split z} S[pix][i] * L[n, 2p-1+kh, 2q-1+kw][l]

@@ -35,7 +35,7 @@ __device__ __forceinline__ int xcd_remap(int bid, int nwg) {
 // own LDS buffers; the second quad's accumulators are added to the first's through LDS before the epilogue.  This is a
 // two-way K split WITHOUT slabs or a second kernel (sum order quad 0 + quad 1 = slab 0 + slab 1 of the split-K protocol:
 // bit-identical); used for the launches that would otherwise be split in two.
-template <int BM, int BN, int WM, int WN, int BK = 32, int DEEP = 0, int KQ = 1>
+template <int BM, int BN, int WM, int WN, int BK = 32, int DEEP = 0, int KQ = 1, bool LK = false>   // LK: g_act's variant
 __global__ __launch_bounds__(256 * KQ) void k_gconv(const GConvArgs a) {
     constexpr int TM = BM / (32 * WM), TN = BN / (32 * WN);
     constexpr int PA = BM / 32, PB = BN / 32;
@@ -309,7 +309,7 @@ __global__ __launch_bounds__(256 * KQ) void k_gconv(const GConvArgs a) {
         const size_t o = opix * a.Co + co;
         f32x4 v = *reinterpret_cast<const f32x4*>(sT + row * LDT + c4 * 4);
         if (epi == EPI_BN_BWD_STATS) {
-            bn_bwd_stat_terms<float>(v, *reinterpret_cast<const f32x4*>(static_cast<const float*>(a.aref) + o), bq, st0, st1);
+            bn_bwd_stat_terms<float, LK>(v, *reinterpret_cast<const f32x4*>(static_cast<const float*>(a.aref) + o), bq, a.gslope, st0, st1);
         } else if (epi == EPI_BIAS_LRELU_DROP) {
 #pragma unroll
             for (int e = 0; e < 4; ++e) { float t = v[e] + bias4[e]; v[e] = t > 0.f ? t : t * a.slope; }
@@ -320,7 +320,7 @@ __global__ __launch_bounds__(256 * KQ) void k_gconv(const GConvArgs a) {
             }
         } else if (epi == EPI_AFFINE_RELU) {
 #pragma unroll
-            for (int e = 0; e < 4; ++e) v[e] = fmaxf(fmaf(v[e], sc4[e], sh4[e]), 0.f);
+            for (int e = 0; e < 4; ++e) v[e] = g_act<LK>(fmaf(v[e], sc4[e], sh4[e]), a.gslope);
         } else if (epi == EPI_LRELU_BWD) {
             const f32x4 ar = *reinterpret_cast<const f32x4*>(static_cast<const float*>(a.aref) + o);
 #pragma unroll
@@ -367,7 +367,7 @@ __global__ __launch_bounds__(256 * KQ) void k_gconv(const GConvArgs a) {
 // weight tiles.  Four accumulators per wave; the 2x2 output pixels of the 128 input pixels form one contiguous 64 KB
 // range of the NHWC output, assembled in LDS and stored with 16-byte lanes.
 // ------------------------------------------------------------------------------------------
-template <int CI>
+template <int CI, bool LK>
 __global__ __launch_bounds__(256) void k_gconv_up4(const GConvArgs a) {
     constexpr int BM = 128, BN = 32, LD = BK + 4, LP = CI + 4, NCC = CI / BK;
     constexpr int PATCH_PIX = 264;                   // (128 / Wr + 2) * (Wr + 2) for Wr = 16, 32, 64: 180, 204, 264
@@ -491,7 +491,7 @@ __global__ __launch_bounds__(256) void k_gconv_up4(const GConvArgs a) {
 #pragma unroll
         for (int cls = 0; cls < 4; ++cls) {
             float v = acc[cls][r];
-            if (a.epi == EPI_AFFINE_RELU) v = fmaxf(fmaf(v, sc, sf), 0.f);
+            if (a.epi == EPI_AFFINE_RELU) v = g_act<LK>(fmaf(v, sc, sf), a.gslope);
             so[(((2 * rl + (cls >> 1)) * Wo) + 2 * rw + (cls & 1)) * BN + li] = v;
         }
     }
@@ -503,7 +503,7 @@ __global__ __launch_bounds__(256) void k_gconv_up4(const GConvArgs a) {
 }
 
 // split-K tail: out = epilogue(sum_z slab[z]) over the NHWC output (4 channels per thread)
-template <class T>
+template <class T, bool LK>
 __global__ __launch_bounds__(256) void k_splitk_epilogue(const GConvArgs a, int nsplit, int64_t total4) {
     const int64_t i = (int64_t)blockIdx.x * 256 + threadIdx.x;
     if (a.epi == EPI_BN_BWD_STATS) {
@@ -517,7 +517,7 @@ __global__ __launch_bounds__(256) void k_splitk_epilogue(const GConvArgs a, int 
             const size_t stride4 = a.slab_stride / 4;
             f32x4 v = sl[i];
             for (int z = 1; z < nsplit; ++z) v += sl[(size_t)z * stride4 + i];
-            bn_bwd_stat_terms<T>(v, ld4<T>(static_cast<const T*>(a.aref) + i * 4), bn_bwd_params(a.bnp, a.Co, c4 * 4), s0, s1);
+            bn_bwd_stat_terms<T, LK>(v, ld4<T>(static_cast<const T*>(a.aref) + i * 4), bn_bwd_params(a.bnp, a.Co, c4 * 4), a.gslope, s0, s1);
             st4<T>(static_cast<T*>(a.out) + i * 4, v);
         }
         *reinterpret_cast<f32x4*>(sh + threadIdx.x * 8) = s0;
@@ -557,7 +557,7 @@ __global__ __launch_bounds__(256) void k_splitk_epilogue(const GConvArgs a, int 
         }
     } else if (a.epi == EPI_AFFINE_RELU) {
 #pragma unroll
-        for (int k = 0; k < 4; ++k) e[k] = fmaxf(fmaf(e[k], a.scale[c + k], a.shift[c + k]), 0.f);
+        for (int k = 0; k < 4; ++k) e[k] = g_act<LK>(fmaf(e[k], a.scale[c + k], a.shift[c + k]), a.gslope);
     } else if (a.epi == EPI_LRELU_BWD) {
         const f32x4 ar = ld4<T>(static_cast<const T*>(a.aref) + i * 4);
         const float* r = reinterpret_cast<const float*>(&ar);
@@ -642,13 +642,16 @@ static int launch_cfg(const GConvArgs& a_in, hipStream_t st, int id, int nsplit)
     hipEvent_t e0 = g_prof ? g_prof->recs.back().e0 : nullptr, e1 = g_prof ? g_prof->recs.back().e1 : nullptr;
     if (a.dt != DT_F32) {
         launch_gconv16(id, a, grid, st, e0, e1, KQ);
+    } else if (gen_lk(a)) {
+        hipExtLaunchKernelGGL((k_gconv<BM, BN, WM, WN, BKT, DEEP, KQ, true>), grid, dim3(256 * KQ), 0, st, e0, e1, 0, a);
     } else if (g_prof) {
         hipExtLaunchKernelGGL((k_gconv<BM, BN, WM, WN, BKT, DEEP, KQ>), grid, dim3(256 * KQ), 0, st, e0, e1, 0, a);
     } else {
         hipLaunchKernelGGL((k_gconv<BM, BN, WM, WN, BKT, DEEP, KQ>), grid, dim3(256 * KQ), 0, st, a);
     }
     if (nsplit > 1)
-        SIGGAN_DT_SWITCH(a.dt, T, hipLaunchKernelGGL(k_splitk_epilogue<T>, dim3((unsigned)((total4 + 255) / 256)), dim3(256), 0, st, a, nsplit, total4));
+        SIGGAN_GS_SWITCH(gen_lk(a) ? 1.f : 0.f, LK, SIGGAN_DT_SWITCH(a.dt, T, hipLaunchKernelGGL((k_splitk_epilogue<T, LK>),
+            dim3((unsigned)((total4 + 255) / 256)), dim3(256), 0, st, a, nsplit, total4)));
     return rows;
 }
 
@@ -695,8 +698,13 @@ int launch_gconv(const GConvArgs& a_in, hipStream_t st) {
         dim3 grid(a.M / 128);
         if (g_prof) g_prof->begin(5, 2.0 * a.M * a.Co * (double)(4 * a.Ci) * 4, gconv_bytes(a), st);
         hipEvent_t e0 = g_prof ? g_prof->recs.back().e0 : nullptr, e1 = g_prof ? g_prof->recs.back().e1 : nullptr;
-        if (a.Ci == 32) hipExtLaunchKernelGGL(k_gconv_up4<32>, grid, dim3(256), 0, st, e0, e1, 0, a);
-        else hipExtLaunchKernelGGL(k_gconv_up4<64>, grid, dim3(256), 0, st, e0, e1, 0, a);
+        if (gen_lk(a)) {
+            if (a.Ci == 32) hipExtLaunchKernelGGL((k_gconv_up4<32, true>), grid, dim3(256), 0, st, e0, e1, 0, a);
+            else hipExtLaunchKernelGGL((k_gconv_up4<64, true>), grid, dim3(256), 0, st, e0, e1, 0, a);
+        } else {
+            if (a.Ci == 32) hipExtLaunchKernelGGL((k_gconv_up4<32, false>), grid, dim3(256), 0, st, e0, e1, 0, a);
+            else hipExtLaunchKernelGGL((k_gconv_up4<64, false>), grid, dim3(256), 0, st, e0, e1, 0, a);
+        }
         return 0;
     }
     const int ns = splits(blocks(128, 32));

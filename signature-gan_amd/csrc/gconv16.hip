@@ -37,7 +37,7 @@ template <> struct Mma<f16_t> {
 
 // KQ = 2: two wave quads per workgroup, each on its own half of the K range with its own LDS buffers, accumulators added
 // through LDS before the epilogue -- a two-way K split without slabs or a second kernel (see k_gconv in gconv.hip)
-template <class T, int BM, int BN, int WM, int WN, int NSET = 2, int KQ = 1>
+template <class T, int BM, int BN, int WM, int WN, int NSET = 2, int KQ = 1, bool LK = false>   // LK: a.gslope != 0 (g_act)
 __global__ __launch_bounds__(256 * KQ) void k_gconv16(const GConvArgs a) {
     typedef typename Mma<T>::V Frag;
     constexpr int TM = BM / (32 * WM), TN = BN / (32 * WN);
@@ -259,7 +259,7 @@ __global__ __launch_bounds__(256 * KQ) void k_gconv16(const GConvArgs a) {
             const size_t o = opix * a.Co + co;
             f32x4 v = *reinterpret_cast<const f32x4*>(sT + row * LDT + c4 * 4);
             if (epi == EPI_BN_BWD_STATS) {
-                bn_bwd_stat_terms<T>(v, ld4<T>(aref + o), bq, st0, st1);      // (v as it is stored: rounded to T)
+                bn_bwd_stat_terms<T, LK>(v, ld4<T>(aref + o), bq, a.gslope, st0, st1);      // (v as it is stored: rounded to T)
             } else if (epi == EPI_BIAS_LRELU_DROP) {
 #pragma unroll
                 for (int e = 0; e < 4; ++e) { float t = v[e] + bias4[e]; v[e] = t > 0.f ? t : t * a.slope; }
@@ -270,7 +270,7 @@ __global__ __launch_bounds__(256 * KQ) void k_gconv16(const GConvArgs a) {
                 }
             } else if (epi == EPI_AFFINE_RELU) {
 #pragma unroll
-                for (int e = 0; e < 4; ++e) v[e] = fmaxf(fmaf(v[e], sc4[e], sh4[e]), 0.f);
+                for (int e = 0; e < 4; ++e) v[e] = g_act<LK>(fmaf(v[e], sc4[e], sh4[e]), a.gslope);
             } else if (epi == EPI_LRELU_BWD) {
                 const f32x4 ar = ld4<T>(aref + o);
 #pragma unroll
@@ -304,19 +304,24 @@ __global__ __launch_bounds__(256 * KQ) void k_gconv16(const GConvArgs a) {
     }
 }
 
-void launch_gconv16(int cfg, const GConvArgs& a, dim3 grid, hipStream_t st, hipEvent_t e0, hipEvent_t e1, int kq) {
+template <bool LK>
+static void launch_gconv16_v(int cfg, const GConvArgs& a, dim3 grid, hipStream_t st, hipEvent_t e0, hipEvent_t e1, int kq) {
     if (kq == 2) {          // 64x64 tiles, two-way K split inside the workgroup
-        if (a.dt == DT_BF16) hipExtLaunchKernelGGL((k_gconv16<bf16_t, 64, 64, 2, 2, 2, 2>), grid, dim3(512), 0, st, e0, e1, 0, a);
-        else hipExtLaunchKernelGGL((k_gconv16<f16_t, 64, 64, 2, 2, 2, 2>), grid, dim3(512), 0, st, e0, e1, 0, a);
+        if (a.dt == DT_BF16) hipExtLaunchKernelGGL((k_gconv16<bf16_t, 64, 64, 2, 2, 2, 2, LK>), grid, dim3(512), 0, st, e0, e1, 0, a);
+        else hipExtLaunchKernelGGL((k_gconv16<f16_t, 64, 64, 2, 2, 2, 2, LK>), grid, dim3(512), 0, st, e0, e1, 0, a);
         return;
     }
-#define GC16(T, BM, BN, WM, WN) hipExtLaunchKernelGGL((k_gconv16<T, BM, BN, WM, WN>), grid, dim3(256), 0, st, e0, e1, 0, a)
+#define GC16(T, BM, BN, WM, WN) hipExtLaunchKernelGGL((k_gconv16<T, BM, BN, WM, WN, 2, 1, LK>), grid, dim3(256), 0, st, e0, e1, 0, a)
     if (a.dt == DT_BF16) {
         if (cfg == 0) GC16(bf16_t, 128, 128, 2, 2); else if (cfg == 2) GC16(bf16_t, 64, 64, 2, 2); else GC16(bf16_t, 128, 32, 4, 1);
     } else {
         if (cfg == 0) GC16(f16_t, 128, 128, 2, 2); else if (cfg == 2) GC16(f16_t, 64, 64, 2, 2); else GC16(f16_t, 128, 32, 4, 1);
     }
 #undef GC16
+}
+void launch_gconv16(int cfg, const GConvArgs& a, dim3 grid, hipStream_t st, hipEvent_t e0, hipEvent_t e1, int kq) {
+    if (gen_lk(a)) launch_gconv16_v<true>(cfg, a, grid, st, e0, e1, kq);
+    else launch_gconv16_v<false>(cfg, a, grid, st, e0, e1, kq);
 }
 
 // ------------------------------------------------------------------------------------------

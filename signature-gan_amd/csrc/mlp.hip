@@ -258,7 +258,7 @@ static void g_fwd(mlpgan_ctx* c, const float* z, int B, bool training, float* im
             launch_bn_train_stats(DT_F32, c->gy[i], B, N, MGP(c, 4 * i + 2), MGP(c, 4 * i + 3), c->st.g_bn_running_mean + c->bn_off[i],
                                   c->st.g_bn_running_var + c->bn_off[i], c->st.g_bn_batches ? c->st.g_bn_batches + i : nullptr, c->gbn[i],
                                   c->partial, 0, MLP_BN_MOM, MLP_BN_EPS, s);
-            launch_bn_relu(DT_F32, c->gy[i], c->ga[i], B, N, c->gbn[i], s);
+            launch_bn_relu(DT_F32, c->gy[i], c->ga[i], B, N, c->gbn[i], 0.f, s);
         } else {
             hipLaunchKernelGGL(k_bn_eval_relu, dim3(blocks((int64_t)B * N)), dim3(256), 0, s, c->gy[i], c->ga[i], (int64_t)B * N, N,
                                MGP(c, 4 * i + 2), MGP(c, 4 * i + 3), c->st.g_bn_running_mean + c->bn_off[i],
@@ -368,7 +368,7 @@ extern "C" int mlpgan_g_step(mlpgan_ctx* c, int32_t B, const float* z, const sig
     gemm(1, dpre, MGP(c, 4 * nh), c->gda[nh - 1], B, c->gdim[nh], c->P, nullptr, ACT_NONE, 0.f, s);
     for (int i = nh - 1; i >= 0; --i) {
         const int N = c->gdim[i + 1], K = c->gdim[i];
-        launch_bn_bwd(DT_F32, c->gda[i], c->gy[i], B, N, c->gbn[i], c->partial, MGG(c, 4 * i + 2), MGG(c, 4 * i + 3), 0, s);   // gda[i] <- d(y_i)
+        launch_bn_bwd(DT_F32, c->gda[i], c->gy[i], B, N, c->gbn[i], c->partial, MGG(c, 4 * i + 2), MGG(c, 4 * i + 3), 0, 0.f, s);   // gda[i] <- d(y_i)
         gemm(2, c->gda[i], i == 0 ? c->z : c->ga[i - 1], MGG(c, 4 * i), N, K, B, nullptr, ACT_NONE, 0.f, s);
         hipLaunchKernelGGL(k_colsum, dim3(blocks(N)), dim3(256), 0, s, c->gda[i], MGG(c, 4 * i + 1), B, N);
         if (i > 0) gemm(1, c->gda[i], MGP(c, 4 * i), c->gda[i - 1], B, K, N, nullptr, ACT_NONE, 0.f, s);

@@ -59,24 +59,25 @@ bool launch_prepare_conv1(const PrepTable& t, float bn_eps, int dt, const float*
 
 // ---- Generator pieces ---------------------------------------------------------------------
 // y[n][f'] = z[n,:] . W[f,:] + b[f],  f' = hw*C0 + c  <->  f = c*16 + hw   (NHWC feature order)
-// bn_affine_relu != nullptr (eval): y = relu((z.Wt + b) * scale + shift) with [scale | shift] of the folded BatchNorm1d.
+// bn_affine_relu != nullptr (eval): y = g_act((z.Wt + b) * scale + shift, gslope) with [scale | shift] of the folded BatchNorm1d.
+// gslope (here and below): the Generator's activation slope, 0 = ReLU, > 0 = LeakyReLU (g_act / g_dact, act.h).
 // z == nullptr: z ~ N(0,1) is drawn inside the kernel (the values launch_randn(z_out, B*K, st, stream_id) would write) and
 // also stored to z_out
 // (dt: element type of the activation / gradient tensors passed as void*, see act.h)
-void launch_fc_fwd(int dt, const float* z, const float* Wt, const float* b, void* y, int B, int K, int C0, hipStream_t s,
-                   const float* bn_affine_relu = nullptr, const DevState* st = nullptr, uint32_t stream_id = 0,
+void launch_fc_fwd(int dt, const float* z, const float* Wt, const float* b, void* y, int B, int K, int C0, float gslope,
+                   hipStream_t s, const float* bn_affine_relu = nullptr, const DevState* st = nullptr, uint32_t stream_id = 0,
                    float* z_out = nullptr);
-// fc.hip: Linear + BatchNorm1d + ReLU in ONE launch on the fp32 matrix cores.  bne != nullptr: eval mode (folded [scale | shift]
+// fc.hip: Linear + BatchNorm1d + activation in ONE launch on the fp32 matrix cores.  bne != nullptr: eval mode (folded [scale | shift]
 // table, only `a` is written); else training: y (pre-BN), a, the bn table [scale | shift | mean | rstd | . | .] the backward
 // reuses, and the running statistics / batch counter are written.  W is the torch-layout weight (no transposed copy).
 // Returns false (nothing launched) when the shape is outside what the kernel covers (B > 256, or RNG draw with K % 4 != 0).
 bool launch_fc_fwd_fused(int dt, const float* z, const float* W, const float* bias, void* y, void* a, const float* gamma,
                          const float* beta, float* rmean, float* rvar, int64_t* batches, float* bn, const float* bne,
                          float* z_out, const DevState* st, uint32_t sid, int B, int K, int C0, float momentum, float eps,
-                         hipStream_t s);
-// ReLU mask + BatchNorm1d backward + dW / db of the Linear in ONE launch: da, y element type dt; dW, db, dgamma, dbeta fp32 (torch order)
+                         float gslope, hipStream_t s);
+// activation mask + BatchNorm1d backward + dW / db of the Linear in ONE launch: da, y element type dt; dW, db, dgamma, dbeta fp32 (torch order)
 bool launch_fc_bwd_fused(int dt, const void* da, const void* y, const float* z, float* bn, float* dW, float* db, float* dgamma,
-                         float* dbeta, int B, int K, int C0, hipStream_t s);
+                         float* dbeta, int B, int K, int C0, float gslope, hipStream_t s);
 // dW[f][k] = sum_n dy[n][f'] z[n][k];  db[f] = sum_n dy[n][f']
 void launch_fc_wgrad(int dt, const void* dy, const float* z, float* dW, float* db, int B, int K, int C0, hipStream_t s);
 
@@ -84,27 +85,27 @@ void launch_fc_wgrad(int dt, const void* dy, const float* z, float* dW, float* d
 void launch_bn_train_stats(int dt, const void* y, int64_t R, int C, const float* gamma, const float* beta,
                            float* rmean, float* rvar, int64_t* batches, float* bn, float* partial,
                            int perm_c0, float momentum, float eps, hipStream_t s);
-// a = relu(y*scale + shift)
-void launch_bn_relu(int dt, const void* y, void* a, int64_t R, int C, const float* bn, hipStream_t s);
-// backward through relu(BN(y)): da (in) -> dy (in place); dgamma/dbeta (torch order) written.  The relu mask is
+// a = g_act(y*scale + shift, gslope)
+void launch_bn_relu(int dt, const void* y, void* a, int64_t R, int C, const float* bn, float gslope, hipStream_t s);
+// backward through g_act(BN(y)): da (in) -> dy (in place); dgamma/dbeta (torch order) written.  The activation mask is
 // re-derived from y and the layer's scale/shift (the forward's own expression), so the activation is not read.
 void launch_bn_bwd(int dt, void* da, const void* y, int64_t R, int C, float* bn, float* partial,
-                   float* dgamma, float* dbeta, int perm_c0, hipStream_t s, int pre_rows = 0, hipEvent_t done = nullptr);
+                   float* dgamma, float* dbeta, int perm_c0, float gslope, hipStream_t s, int pre_rows = 0, hipEvent_t done = nullptr);
 
 // final 3x3 conv (C->1) + tanh, and its backward pieces.  act: [B][S][S][C] NHWC, img [B][S][S].
 // bn != nullptr (training): `act` is the last block's PRE-BatchNorm tensor y and bn its [scale | shift] table -- the
-// activation relu(fma(y, scale, shift)) is formed on load and never stored
-void launch_final_fwd(int dt, const void* act, const float* Wt, const float* b, float* img, int B, int S, int C, hipStream_t s,
-                      const float* bn = nullptr, hipEvent_t done = nullptr);
+// activation g_act(fma(y, scale, shift), gslope) is formed on load and never stored
+void launch_final_fwd(int dt, const void* act, const float* Wt, const float* b, float* img, int B, int S, int C, float gslope,
+                      hipStream_t s, const float* bn = nullptr, hipEvent_t done = nullptr);
 // backward of the last Generator block from dpre.  (1) launch_final_bwd_reduce: ONE read of y gives the BatchNorm-backward sums
-// (d(act) of the final conv recomputed from dpre, never stored; relu mask re-derived from y) into `partial` AND the partial
+// (d(act) of the final conv recomputed from dpre, never stored; activation mask re-derived from y) into `partial` AND the partial
 // rows of the final conv's weight / bias gradient (activation re-derived from y) into `partial_w`;  (2) launch_final_bn_bwd_apply:
 // ONE finalizer launch (dW / db from partial_w, dgamma / dbeta and the two means from `partial`), then dy
 void launch_final_bwd_reduce(int dt, const float* dpre, const float* Wt, const void* y, int B, int S, int C, const float* bn,
-                             float* partial, float* partial_w, hipStream_t s);
+                             float* partial, float* partial_w, float gslope, hipStream_t s);
 void launch_final_bn_bwd_apply(int dt, const float* dpre, const float* Wt, const void* y, void* dy, int B, int S, int C, float* bn,
                                const float* partial, const float* partial_w, float* dW, float* db, float* dgamma, float* dbeta,
-                               hipStream_t s, hipEvent_t done = nullptr);
+                               float gslope, hipStream_t s, hipEvent_t done = nullptr);
 
 // ---- Discriminator pieces -----------------------------------------------------------------
 // first block (Cin = 1): x = two segments (x0: n < n0, x1: the rest), out [B][S/2][S/2][C]

@@ -267,14 +267,14 @@ struct FStats {   // shifted sums around the first row: robust single-pass varia
         s1.x = fmaf(d.x, d.x, s1.x); s1.y = fmaf(d.y, d.y, s1.y); s1.z = fmaf(d.z, d.z, s1.z); s1.w = fmaf(d.w, d.w, s1.w);
     }
 };
-template <class T>
-struct FBnBwd {   // relu mask re-derived from y (a > 0 <=> fma(y, scale, shift) > 0, k_bn_relu's own expression): a is not read
-    const T* da; const T* y; const float4* bn;
+template <class T, bool LK>
+struct FBnBwd {   // activation mask re-derived from y (a > 0 <=> fma(y, scale, shift) > 0, k_bn_relu's own expression): a is not read
+    const T* da; const T* y; const float4* bn; float gs;
     __device__ void operator()(int64_t r, int c4, int C4, float4& s0, float4& s1) const {
         const size_t i = (size_t)r * C4 + c4;
         const float4 g = f4(ld4<T>(da + i * 4)), yy = f4(ld4<T>(y + i * 4)), sc = bn[c4], sf = bn[C4 + c4], mu = bn[2 * C4 + c4], rs = bn[3 * C4 + c4];
-        const float4 d = make_float4(fmaf(yy.x, sc.x, sf.x) > 0.f ? g.x : 0.f, fmaf(yy.y, sc.y, sf.y) > 0.f ? g.y : 0.f,
-                                     fmaf(yy.z, sc.z, sf.z) > 0.f ? g.z : 0.f, fmaf(yy.w, sc.w, sf.w) > 0.f ? g.w : 0.f);
+        const float4 d = make_float4(g_dact<LK>(fmaf(yy.x, sc.x, sf.x), g.x, gs), g_dact<LK>(fmaf(yy.y, sc.y, sf.y), g.y, gs),
+                                     g_dact<LK>(fmaf(yy.z, sc.z, sf.z), g.z, gs), g_dact<LK>(fmaf(yy.w, sc.w, sf.w), g.w, gs));
         add4(s0, d);
         s1.x = fmaf(d.x, (yy.x - mu.x) * rs.x, s1.x); s1.y = fmaf(d.y, (yy.y - mu.y) * rs.y, s1.y);
         s1.z = fmaf(d.z, (yy.z - mu.z) * rs.z, s1.z); s1.w = fmaf(d.w, (yy.w - mu.w) * rs.w, s1.w);
@@ -327,20 +327,24 @@ void launch_bn_train_stats(int dt, const void* yv, int64_t R, int C, const float
     });
 }
 
-template <class T>
+template <class T, bool LK>
 __global__ void k_bn_relu(const T* __restrict__ y, T* __restrict__ a, int64_t n4, int C4,
-                          const float4* __restrict__ bn) {
+                          const float4* __restrict__ bn, float gs) {
     const int64_t i = (int64_t)blockIdx.x * blockDim.x + threadIdx.x;
     if (i >= n4) return;
     const int c = (C4 & (C4 - 1)) == 0 ? (int)(i & (C4 - 1)) : (int)(i % C4);      // (channel counts are powers of two)
     const float4 v = f4(ld4<T>(y + i * 4)), sc = bn[c], sh = bn[C4 + c];
-    st4<T>(a + i * 4, f32x4{fmaxf(fmaf(v.x, sc.x, sh.x), 0.f), fmaxf(fmaf(v.y, sc.y, sh.y), 0.f),
-                            fmaxf(fmaf(v.z, sc.z, sh.z), 0.f), fmaxf(fmaf(v.w, sc.w, sh.w), 0.f)});
+    st4<T>(a + i * 4, f32x4{g_act<LK>(fmaf(v.x, sc.x, sh.x), gs), g_act<LK>(fmaf(v.y, sc.y, sh.y), gs),
+                            g_act<LK>(fmaf(v.z, sc.z, sh.z), gs), g_act<LK>(fmaf(v.w, sc.w, sh.w), gs)});
 }
-void launch_bn_relu(int dt, const void* y, void* a, int64_t R, int C, const float* bn, hipStream_t s) {
+void launch_bn_relu(int dt, const void* y, void* a, int64_t R, int C, const float* bn, float gslope, hipStream_t s) {
     const int64_t n4 = R * C / 4;
-    SIGGAN_DT_SWITCH(dt, T, hipLaunchKernelGGL(k_bn_relu<T>, dim3(cdiv(n4, 256)), dim3(256), 0, s, (const T*)y, (T*)a, n4, C / 4,
-                                                (const float4*)bn));
+    SIGGAN_DT_SWITCH(dt, T, {
+        if (gslope != 0.f) hipLaunchKernelGGL((k_bn_relu<T, true>), dim3(cdiv(n4, 256)), dim3(256), 0, s, (const T*)y, (T*)a, n4, C / 4,
+                                               (const float4*)bn, gslope);
+        else hipLaunchKernelGGL((k_bn_relu<T, false>), dim3(cdiv(n4, 256)), dim3(256), 0, s, (const T*)y, (T*)a, n4, C / 4,
+                                (const float4*)bn, gslope);
+    });
 }
 
 template <int W>
@@ -361,19 +365,19 @@ static void launch_bn_bwd_fin(const float* p0, const float* p1, int nch, int64_t
     if (C <= 32) hipLaunchKernelGGL(k_bn_bwd_fin<32>, dim3(cdiv(C, 32)), dim3(1024), 0, s, p0, p1, nch, R, C, bn, dgamma, dbeta, perm_c0);
     else hipLaunchKernelGGL(k_bn_bwd_fin<64>, dim3(cdiv(C, 64)), dim3(1024), 0, s, p0, p1, nch, R, C, bn, dgamma, dbeta, perm_c0);
 }
-template <class T>
+template <class T, bool LK>
 __global__ void k_bn_bwd_apply(T* __restrict__ da, const T* __restrict__ y, int64_t n4, int C4,
-                               const float4* __restrict__ bn) {
+                               const float4* __restrict__ bn, float gs) {
     const int64_t i = (int64_t)blockIdx.x * blockDim.x + threadIdx.x;
     if (i >= n4) return;
     const int c = (C4 & (C4 - 1)) == 0 ? (int)(i & (C4 - 1)) : (int)(i % C4);      // (channel counts are powers of two)
     const float4 g = f4(ld4<T>(da + i * 4)), yy = f4(ld4<T>(y + i * 4));
     const float4 sc = bn[c], sf = bn[C4 + c], mu = bn[2 * C4 + c], rs = bn[3 * C4 + c], c1 = bn[4 * C4 + c], c2 = bn[5 * C4 + c];
     float4 o;
-    o.x = sc.x * ((fmaf(yy.x, sc.x, sf.x) > 0.f ? g.x : 0.f) - c1.x - (yy.x - mu.x) * rs.x * c2.x);
-    o.y = sc.y * ((fmaf(yy.y, sc.y, sf.y) > 0.f ? g.y : 0.f) - c1.y - (yy.y - mu.y) * rs.y * c2.y);
-    o.z = sc.z * ((fmaf(yy.z, sc.z, sf.z) > 0.f ? g.z : 0.f) - c1.z - (yy.z - mu.z) * rs.z * c2.z);
-    o.w = sc.w * ((fmaf(yy.w, sc.w, sf.w) > 0.f ? g.w : 0.f) - c1.w - (yy.w - mu.w) * rs.w * c2.w);
+    o.x = sc.x * (g_dact<LK>(fmaf(yy.x, sc.x, sf.x), g.x, gs) - c1.x - (yy.x - mu.x) * rs.x * c2.x);
+    o.y = sc.y * (g_dact<LK>(fmaf(yy.y, sc.y, sf.y), g.y, gs) - c1.y - (yy.y - mu.y) * rs.y * c2.y);
+    o.z = sc.z * (g_dact<LK>(fmaf(yy.z, sc.z, sf.z), g.z, gs) - c1.z - (yy.z - mu.z) * rs.z * c2.z);
+    o.w = sc.w * (g_dact<LK>(fmaf(yy.w, sc.w, sf.w), g.w, gs) - c1.w - (yy.w - mu.w) * rs.w * c2.w);
     st4<T>(da + i * 4, f32x4{o.x, o.y, o.z, o.w});
 }
 // k_bn_bwd_fin folded into k_bn_bwd_apply (round 4; used when the producing GEMM left partial rows): a workgroup owns a
@@ -381,10 +385,11 @@ __global__ void k_bn_bwd_apply(T* __restrict__ da, const T* __restrict__ y, int6
 // rows rl, rl + 32, ...; the 32 lanes are then added in order: a fixed order, so every workgroup of a slice forms the same
 // bits).  64-128 KB of L2-resident rows per workgroup instead of a 1-4 workgroup finalize launch on the Generator backward's
 // critical lane: same-box A/B 1.4192 -> 1.4130 ms at fp32, 0.6400 -> 0.6304 at bf16, three launches fewer.
-template <class T>
+template <class T, bool LK>
 __global__ __launch_bounds__(256) void k_bn_bwd_fin_apply(T* __restrict__ da, const T* __restrict__ y, int64_t R, int C, float* __restrict__ bn,
                                                           const float* __restrict__ p0, const float* __restrict__ p1, int nrows,
-                                                          float* __restrict__ dgamma, float* __restrict__ dbeta, int rows_per_chunk) {
+                                                          float* __restrict__ dgamma, float* __restrict__ dbeta, int rows_per_chunk,
+                                                          float gs) {
     __shared__ f32x4 sh[2][32][8];
     const int c4 = threadIdx.x & 7, rl = threadIdx.x >> 3;
     const int ch = blockIdx.x * 32 + c4 * 4;
@@ -415,12 +420,12 @@ __global__ __launch_bounds__(256) void k_bn_bwd_fin_apply(T* __restrict__ da, co
         f32x4 o;
 #pragma unroll
         for (int e = 0; e < 4; ++e)
-            o[e] = sc[e] * ((fmaf(yy[e], sc[e], sf[e]) > 0.f ? g[e] : 0.f) - c1[e] - (yy[e] - mu[e]) * rs[e] * c2[e]);
+            o[e] = sc[e] * (g_dact<LK>(fmaf(yy[e], sc[e], sf[e]), g[e], gs) - c1[e] - (yy[e] - mu[e]) * rs[e] * c2[e]);
         st4<T>(da + i, o);
     }
 }
 void launch_bn_bwd(int dt, void* dav, const void* yv, int64_t R, int C, float* bn, float* partial,
-                   float* dgamma, float* dbeta, int perm_c0, hipStream_t s, int pre_rows, hipEvent_t done) {
+                   float* dgamma, float* dbeta, int perm_c0, float gslope, hipStream_t s, int pre_rows, hipEvent_t done) {
     // pre_rows > 0: the kernel that produced da left that many partial rows of both sums in `partial` (gconv's
     // EPI_BN_BWD_STATS): no reduction pass over da and y
     const ColPlan pl = col_plan(R, C);
@@ -433,18 +438,19 @@ void launch_bn_bwd(int dt, void* dav, const void* yv, int64_t R, int C, float* b
         if (chunks > (R + 63) / 64) chunks = (R + 63) / 64;
         int rpc = (int)((R + chunks - 1) / chunks); rpc = ((rpc + 31) / 32) * 32;
         chunks = (R + rpc - 1) / rpc;
-        SIGGAN_DT_SWITCH(dt, T, SIGGAN_LAUNCH_EV(done, k_bn_bwd_fin_apply<T>, dim3(slices, (unsigned)chunks), dim3(256), 0, s, (T*)dav, (const T*)yv, R, C,
-                                                  bn, p0, p1, nch, dgamma, dbeta, rpc));
+        SIGGAN_GS_SWITCH(gslope, LK, SIGGAN_DT_SWITCH(dt, T, SIGGAN_LAUNCH_EV(done, (k_bn_bwd_fin_apply<T, LK>), dim3(slices, (unsigned)chunks),
+                                                                      dim3(256), 0, s, (T*)dav, (const T*)yv, R, C, bn, p0, p1, nch,
+                                                                      dgamma, dbeta, rpc, gslope)));
         return;
     }
-    SIGGAN_DT_SWITCH(dt, T, {
+    SIGGAN_GS_SWITCH(gslope, LK, SIGGAN_DT_SWITCH(dt, T, {
         T* da = (T*)dav; const T* y = (const T*)yv;
         if (pre_rows <= 0)
-            hipLaunchKernelGGL((k_colreduce<FBnBwd<T>>), dim3(pl.cbx, pl.nch), dim3(256), 0, s,
-                               FBnBwd<T>{da, y, (const float4*)bn}, R, C, pl.cg, pl.rows, p0, p1);
+            hipLaunchKernelGGL((k_colreduce<FBnBwd<T, LK>>), dim3(pl.cbx, pl.nch), dim3(256), 0, s,
+                               FBnBwd<T, LK>{da, y, (const float4*)bn, gslope}, R, C, pl.cg, pl.rows, p0, p1);
         launch_bn_bwd_fin(p0, p1, nch, R, C, bn, dgamma, dbeta, perm_c0, s);
-        SIGGAN_LAUNCH_EV(done, k_bn_bwd_apply<T>, dim3(cdiv(n4, 256)), dim3(256), 0, s, da, y, n4, C / 4, (const float4*)bn);
-    });
+        SIGGAN_LAUNCH_EV(done, (k_bn_bwd_apply<T, LK>), dim3(cdiv(n4, 256)), dim3(256), 0, s, da, y, n4, C / 4, (const float4*)bn, gslope);
+    }));
 }
 
 // =========================================================================================
@@ -452,11 +458,11 @@ void launch_bn_bwd(int dt, void* dav, const void* yv, int64_t R, int C, float* b
 // =========================================================================================
 // (Wt[k][f'] = W[f][k] is the k-major copy k_prepare keeps in the NHWC feature order, so lanes walk f' coalesced)
 // one thread = one feature f' x 8 batch rows; z rows broadcast from LDS; 50 weight loads in flight
-template <class T>
+template <class T, bool LK>
 __global__ __launch_bounds__(256) void k_fc_fwd(const float* __restrict__ z, const float* __restrict__ Wt,
                                                 const float* __restrict__ b, T* __restrict__ y, int B, int K, int C0,
                                                 const float* __restrict__ bn, const DevState* __restrict__ st, uint32_t sid,
-                                                float* __restrict__ z_out) {
+                                                float* __restrict__ z_out, float gs) {
     extern __shared__ float sz[];   // [8][K]
     const int F = C0 * 16;
     const int fp = blockIdx.x * 256 + threadIdx.x, nb = blockIdx.y * 8;
@@ -516,21 +522,22 @@ __global__ __launch_bounds__(256) void k_fc_fwd(const float* __restrict__ z, con
         for (int j = 0; j < 8; ++j) acc[j] = fmaf(sz[j * K + k], w, acc[j]);
     }
     const float bias = b[(fp % C0) * 16 + fp / C0];
-    if (bn) {            // eval mode: BatchNorm1d folded to scale/shift + ReLU, the pre-BN tensor is not kept
+    if (bn) {            // eval mode: BatchNorm1d folded to scale/shift + activation, the pre-BN tensor is not kept
         const float sc = bn[fp], sf = bn[F + fp];
 #pragma unroll
         for (int j = 0; j < 8; ++j)
-            if (nb + j < B) st1<T>(y + (size_t)(nb + j) * F + fp, fmaxf(fmaf(acc[j] + bias, sc, sf), 0.f));
+            if (nb + j < B) st1<T>(y + (size_t)(nb + j) * F + fp, g_act<LK>(fmaf(acc[j] + bias, sc, sf), gs));
         return;
     }
 #pragma unroll
     for (int j = 0; j < 8; ++j)
         if (nb + j < B) st1<T>(y + (size_t)(nb + j) * F + fp, acc[j] + bias);
 }
-void launch_fc_fwd(int dt, const float* z, const float* Wt, const float* b, void* y, int B, int K, int C0, hipStream_t s,
-                   const float* bn_affine_relu, const DevState* st, uint32_t stream_id, float* z_out) {
-    SIGGAN_DT_SWITCH(dt, T, hipLaunchKernelGGL(k_fc_fwd<T>, dim3(cdiv(C0 * 16, 256), cdiv(B, 8)), dim3(256), 8 * K * sizeof(float), s, z, Wt,
-                                                b, (T*)y, B, K, C0, bn_affine_relu, st, stream_id, z_out));
+void launch_fc_fwd(int dt, const float* z, const float* Wt, const float* b, void* y, int B, int K, int C0, float gslope,
+                   hipStream_t s, const float* bn_affine_relu, const DevState* st, uint32_t stream_id, float* z_out) {
+    SIGGAN_GS_SWITCH(gslope, LK, SIGGAN_DT_SWITCH(dt, T, hipLaunchKernelGGL((k_fc_fwd<T, LK>), dim3(cdiv(C0 * 16, 256), cdiv(B, 8)), dim3(256),
+                                                                     8 * K * sizeof(float), s, z, Wt, b, (T*)y, B, K, C0, bn_affine_relu,
+                                                                     st, stream_id, z_out, gslope)));
 }
 // dW[f][k] = sum_n dy[n][f'] * z[n][k],  db[f] = sum_n dy[n][f'].  A thread owns feature f' and a group of
 // FK latent columns: every dy value it loads feeds FK FMAs (z rows broadcast from LDS, 64 batch rows per
@@ -607,13 +614,13 @@ __device__ __forceinline__ StripId strip_of(int sid, int S, int xi) {
     return r;
 }
 
-// BN: `act` is the last block's PRE-BatchNorm tensor y and bn = [scale | shift]: the activation relu(fma(y, scale, shift))
+// BN: `act` is the last block's PRE-BatchNorm tensor y and bn = [scale | shift]: the activation g_act(fma(y, scale, shift))
 // (k_bn_relu's own expression) is formed on load and never stored -- in training mode nothing else reads it in the
 // forward pass, and the backward pass re-derives it from y as well (k_final_bwd_reduce).
-template <class T, bool BN>
+template <class T, bool BN, bool LK>
 __global__ __launch_bounds__(256) void k_final_fwd(const T* __restrict__ act, const float* __restrict__ Wt,
                                                    const float* __restrict__ b, float* __restrict__ img, int S,
-                                                   const float* __restrict__ bn) {
+                                                   const float* __restrict__ bn, float gs) {
     constexpr int RY = 4, C = 32;
     const int c4 = threadIdx.x & 7;
     const StripId t = strip_of<RY>(blockIdx.x, S, threadIdx.x >> 3);
@@ -632,8 +639,8 @@ __global__ __launch_bounds__(256) void k_final_fwd(const T* __restrict__ act, co
         for (int d = 0; d < 3; ++d) {
             const int xx = t.x + d - 1, xc = clampi(xx, S - 1);
             f4v q = ld4<T>(base + ((size_t)yc * S + xc) * C);
-            if (BN) q = f4v{fmaxf(fmaf(q.x, sc.x, sf.x), 0.f), fmaxf(fmaf(q.y, sc.y, sf.y), 0.f),
-                            fmaxf(fmaf(q.z, sc.z, sf.z), 0.f), fmaxf(fmaf(q.w, sc.w, sf.w), 0.f)};
+            if (BN) q = f4v{g_act<LK>(fmaf(q.x, sc.x, sf.x), gs), g_act<LK>(fmaf(q.y, sc.y, sf.y), gs),
+                            g_act<LK>(fmaf(q.z, sc.z, sf.z), gs), g_act<LK>(fmaf(q.w, sc.w, sf.w), gs)};
             v[r][d] = (yy == yc && xx == xc) ? q : f4v{0.f, 0.f, 0.f, 0.f};
         }
     }
@@ -651,13 +658,14 @@ __global__ __launch_bounds__(256) void k_final_fwd(const T* __restrict__ act, co
         if (c4 == 0) img[((size_t)t.n * S + t.y0 + r) * S + t.x] = tanhf(acc + bias);
     }
 }
-void launch_final_fwd(int dt, const void* act, const float* Wt, const float* b, float* img, int B, int S, int C, hipStream_t s,
-                      const float* bn, hipEvent_t done) {
+void launch_final_fwd(int dt, const void* act, const float* Wt, const float* b, float* img, int B, int S, int C, float gslope,
+                      hipStream_t s, const float* bn, hipEvent_t done) {
     (void)C;                                            // host checks C == 32, S % 32 == 0
     const dim3 grid(B * (S / 4) * (S / 32));
     SIGGAN_DT_SWITCH(dt, T, {
-        if (bn) SIGGAN_LAUNCH_EV(done, (k_final_fwd<T, true>), grid, dim3(256), 0, s, (const T*)act, Wt, b, img, S, bn);
-        else SIGGAN_LAUNCH_EV(done, (k_final_fwd<T, false>), grid, dim3(256), 0, s, (const T*)act, Wt, b, img, S, bn);
+        if (bn && gslope != 0.f) SIGGAN_LAUNCH_EV(done, (k_final_fwd<T, true, true>), grid, dim3(256), 0, s, (const T*)act, Wt, b, img, S, bn, gslope);
+        else if (bn) SIGGAN_LAUNCH_EV(done, (k_final_fwd<T, true, false>), grid, dim3(256), 0, s, (const T*)act, Wt, b, img, S, bn, gslope);
+        else SIGGAN_LAUNCH_EV(done, (k_final_fwd<T, false, false>), grid, dim3(256), 0, s, (const T*)act, Wt, b, img, S, bn, gslope);
     });
 }
 
@@ -707,11 +715,11 @@ __device__ __forceinline__ f4v final_dact(const float (&d)[RY + 2][3], const f4v
 //     with act = relu(fma(y, scale, shift)) re-derived the same way (the activation tensor is not materialised in training).
 // A block walks 8-row strips (grid-stride), folds the 32 pixel lanes (shuffles inside a wave, LDS across the 4 waves, fixed
 // order) and writes one partial row per output family; k_bn_bwd_fin / k_rows_sum add the rows.
-template <class T, int RY>
+template <class T, int RY, bool LK>
 __global__ __launch_bounds__(256) void k_final_bwd_reduce(const float* __restrict__ dpre, const float* __restrict__ Wt,
                                                           const T* __restrict__ y, const float* __restrict__ bn,
                                                           float* __restrict__ p0, float* __restrict__ p1,
-                                                          float* __restrict__ pw, int S, int nstrips) {
+                                                          float* __restrict__ pw, int S, int nstrips, float gs) {
     constexpr int C = 32;
     __shared__ f4v sh[2][4][8];
     __shared__ float shw[4][8][37];
@@ -760,11 +768,11 @@ __global__ __launch_bounds__(256) void k_final_bwd_reduce(const float* __restric
             const f4v g = final_dact<RY>(d, w, r);
             const f4v v = yv[r];
             const f4v pre = {fmaf(v.x, sc.x, sf.x), fmaf(v.y, sc.y, sf.y), fmaf(v.z, sc.z, sf.z), fmaf(v.w, sc.w, sf.w)};
-            const f4v m = {pre.x > 0.f ? g.x : 0.f, pre.y > 0.f ? g.y : 0.f, pre.z > 0.f ? g.z : 0.f, pre.w > 0.f ? g.w : 0.f};
+            const f4v m = {g_dact<LK>(pre.x, g.x, gs), g_dact<LK>(pre.y, g.y, gs), g_dact<LK>(pre.z, g.z, gs), g_dact<LK>(pre.w, g.w, gs)};
             s0 += m;
             s1.x = fmaf(m.x, (v.x - mu.x) * rs.x, s1.x); s1.y = fmaf(m.y, (v.y - mu.y) * rs.y, s1.y);
             s1.z = fmaf(m.z, (v.z - mu.z) * rs.z, s1.z); s1.w = fmaf(m.w, (v.w - mu.w) * rs.w, s1.w);
-            const f4v a = {fmaxf(pre.x, 0.f), fmaxf(pre.y, 0.f), fmaxf(pre.z, 0.f), fmaxf(pre.w, 0.f)};
+            const f4v a = {g_act<LK>(pre.x, gs), g_act<LK>(pre.y, gs), g_act<LK>(pre.z, gs), g_act<LK>(pre.w, gs)};
             sdb += d[r + 1][1];
 #pragma unroll
             for (int kh = 0; kh < 3; ++kh)
@@ -810,10 +818,10 @@ __global__ __launch_bounds__(256) void k_final_bwd_reduce(const float* __restric
     }
 }
 // stage 2 (after k_bn_bwd_fin): dy = scale * (dy_relu - c1 - xhat * c2), written to dy[B][S][S][C]
-template <class T>
+template <class T, bool LK>
 __global__ __launch_bounds__(256) void k_final_bnbwd_apply(const float* __restrict__ dpre, const float* __restrict__ Wt,
                                                            const T* __restrict__ y, const float* __restrict__ bn,
-                                                           T* __restrict__ dy, int S) {
+                                                           T* __restrict__ dy, int S, float gs) {
     constexpr int RY = 4, C = 32;
     const int c4 = threadIdx.x & 7;
     const StripId t = strip_of<RY>(blockIdx.x, S, threadIdx.x >> 3);
@@ -838,10 +846,10 @@ __global__ __launch_bounds__(256) void k_final_bnbwd_apply(const float* __restri
         const f4v g = final_dact<RY>(d, w, r);
         const f4v v = yv[r];
         f4v o;
-        o.x = sc.x * ((fmaf(v.x, sc.x, sf.x) > 0.f ? g.x : 0.f) - c1.x - (v.x - mu.x) * rs.x * c2.x);
-        o.y = sc.y * ((fmaf(v.y, sc.y, sf.y) > 0.f ? g.y : 0.f) - c1.y - (v.y - mu.y) * rs.y * c2.y);
-        o.z = sc.z * ((fmaf(v.z, sc.z, sf.z) > 0.f ? g.z : 0.f) - c1.z - (v.z - mu.z) * rs.z * c2.z);
-        o.w = sc.w * ((fmaf(v.w, sc.w, sf.w) > 0.f ? g.w : 0.f) - c1.w - (v.w - mu.w) * rs.w * c2.w);
+        o.x = sc.x * (g_dact<LK>(fmaf(v.x, sc.x, sf.x), g.x, gs) - c1.x - (v.x - mu.x) * rs.x * c2.x);
+        o.y = sc.y * (g_dact<LK>(fmaf(v.y, sc.y, sf.y), g.y, gs) - c1.y - (v.y - mu.y) * rs.y * c2.y);
+        o.z = sc.z * (g_dact<LK>(fmaf(v.z, sc.z, sf.z), g.z, gs) - c1.z - (v.z - mu.z) * rs.z * c2.z);
+        o.w = sc.w * (g_dact<LK>(fmaf(v.w, sc.w, sf.w), g.w, gs) - c1.w - (v.w - mu.w) * rs.w * c2.w);
         st4<T>(dy + o0 + (size_t)r * S * C, o);
     }
 }
@@ -887,21 +895,22 @@ static int final_reduce_rows(int B, int S) {
     const int n = B * (S / FINAL_RY) * (S / 32); return n < 512 ? n : 512;
 }
 void launch_final_bwd_reduce(int dt, const float* dpre, const float* Wt, const void* y, int B, int S, int C, const float* bn,
-                             float* partial, float* partial_w, hipStream_t s) {
+                             float* partial, float* partial_w, float gslope, hipStream_t s) {
     const int nstrips = B * (S / FINAL_RY) * (S / 32), nch = final_reduce_rows(B, S);
     float* p0 = partial; float* p1 = partial + (size_t)nch * C;
-    SIGGAN_DT_SWITCH(dt, T, hipLaunchKernelGGL((k_final_bwd_reduce<T, FINAL_RY>), dim3(nch), dim3(256), 0, s, dpre, Wt, (const T*)y, bn, p0, p1,
-                                                partial_w, S, nstrips));
+    SIGGAN_GS_SWITCH(gslope, LK, SIGGAN_DT_SWITCH(dt, T, hipLaunchKernelGGL((k_final_bwd_reduce<T, FINAL_RY, LK>), dim3(nch), dim3(256), 0, s, dpre, Wt,
+                                                                     (const T*)y, bn, p0, p1, partial_w, S, nstrips, gslope)));
 }
 void launch_final_bn_bwd_apply(int dt, const float* dpre, const float* Wt, const void* y, void* dy, int B, int S, int C, float* bn,
                                const float* partial, const float* partial_w, float* dW, float* db, float* dgamma, float* dbeta,
-                               hipStream_t s, hipEvent_t done) {
+                               float gslope, hipStream_t s, hipEvent_t done) {
     const int nstrips = B * (S / 4) * (S / 32), nch = final_reduce_rows(B, S);
     const float* p0 = partial; const float* p1 = partial + (size_t)nch * C;
     const int nbw = cdiv(C * 9 + 1, 64);
     hipLaunchKernelGGL(k_final_fin, dim3(nbw + cdiv(C, 32)), dim3(1024), 0, s, partial_w, nch, C * 9 + 1, dW, C * 9, db, nbw, p0, p1, nch,
                        (int64_t)B * S * S, C, bn, dgamma, dbeta);
-    SIGGAN_DT_SWITCH(dt, T, SIGGAN_LAUNCH_EV(done, k_final_bnbwd_apply<T>, dim3(nstrips), dim3(256), 0, s, dpre, Wt, (const T*)y, bn, (T*)dy, S));
+    SIGGAN_GS_SWITCH(gslope, LK, SIGGAN_DT_SWITCH(dt, T, SIGGAN_LAUNCH_EV(done, (k_final_bnbwd_apply<T, LK>), dim3(nstrips), dim3(256), 0, s, dpre, Wt,
+                                                                   (const T*)y, bn, (T*)dy, S, gslope)));
 }
 
 // =========================================================================================

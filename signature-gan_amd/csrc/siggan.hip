@@ -6,6 +6,7 @@
 // packed weight copies, split-K slabs, reduction partials, device-side step state).
 #include <hip/hip_runtime.h>
 #include <dlfcn.h>
+#include <math.h>
 #include <stdarg.h>
 #include <stdio.h>
 #include <stdlib.h>
@@ -279,6 +280,8 @@ extern "C" int siggan_create(const siggan_config* cfg, siggan_ctx** out) {
         return fail(SIGGAN_E_INVALID, "dtype must be SIGGAN_DTYPE_F32, _BF16 or _F16, got %d", cfg->dtype);
     if (!(cfg->f16_grad_scale >= 0.f) || cfg->f16_grad_scale > 65536.f)
         return fail(SIGGAN_E_INVALID, "f16_grad_scale must be in [0, 65536] (0 = default)");
+    if (!(cfg->g_leaky_slope >= 0.f) || !isfinite(cfg->g_leaky_slope))
+        return fail(SIGGAN_E_INVALID, "g_leaky_slope must be finite and >= 0 (0 = ReLU), got %g", (double)cfg->g_leaky_slope);
     DevGuard dg(cfg->device);
     HIPCHK(dg.err);
     siggan_ctx* c = new (std::nothrow) siggan_ctx();
@@ -740,7 +743,7 @@ struct Lanes {
 
 static GConvArgs gconv_args(siggan_ctx* c) {
     GConvArgs a; memset(&a, 0, sizeof a);
-    a.dt = c->dt;
+    a.dt = c->dt; a.gslope = c->cfg.g_leaky_slope;
     a.slab = c->slab_k; a.slab_floats = c->slab_k_floats; a.zeros = c->zeros;
     return a;
 }
@@ -753,19 +756,20 @@ static void g_forward_pass(siggan_ctx* c, const float* z, int B, bool training, 
                            hipEvent_t done = nullptr) {     // done: completion event of the pass' last launch
     if (!partial) partial = c->partial;
     char* const* const A = training ? c->g_a : c->g_ae;     // (fp32: the same buffers)
-    // fc + BatchNorm1d + ReLU: one MFMA launch (fc.hip) whenever the shape allows, else the generic kernels
+    const float gs = c->cfg.g_leaky_slope;                   // the Generator's activation: 0 = ReLU, else LeakyReLU(gs)
+    // fc + BatchNorm1d + activation: one MFMA launch (fc.hip) whenever the shape allows, else the generic kernels
     if (c->fc_fused && launch_fc_fwd_fused(c->dt, z, GP(c, gi_fc_w()), GP(c, gi_fc_b()), c->fc_y, A[0], GP(c, gi_bn0_w()),
                                           GP(c, gi_bn0_b()), c->st.g_bn_running_mean, c->st.g_bn_running_var, c->st.g_bn_batches,
                                           c->g_bn[0], training ? nullptr : c->g_bne[0], z_out, c->dev, rng_sid, B, c->latent,
-                                          c->gC[0], BN_MOMENTUM, BN_EPS, s)) {
-    } else if (!training) {     // eval: BatchNorm1d + ReLU folded into the fc epilogue
-        launch_fc_fwd(c->dt, z, c->wfc_t, GP(c, gi_fc_b()), A[0], B, c->latent, c->gC[0], s, c->g_bne[0], c->dev, rng_sid, z_out);
+                                          c->gC[0], BN_MOMENTUM, BN_EPS, gs, s)) {
+    } else if (!training) {     // eval: BatchNorm1d + activation folded into the fc epilogue
+        launch_fc_fwd(c->dt, z, c->wfc_t, GP(c, gi_fc_b()), A[0], B, c->latent, c->gC[0], gs, s, c->g_bne[0], c->dev, rng_sid, z_out);
     } else {
-        launch_fc_fwd(c->dt, z, c->wfc_t, GP(c, gi_fc_b()), c->fc_y, B, c->latent, c->gC[0], s, nullptr, c->dev, rng_sid, z_out);
+        launch_fc_fwd(c->dt, z, c->wfc_t, GP(c, gi_fc_b()), c->fc_y, B, c->latent, c->gC[0], gs, s, nullptr, c->dev, rng_sid, z_out);
         launch_bn_train_stats(c->dt, c->fc_y, B, c->F, GP(c, gi_bn0_w()), GP(c, gi_bn0_b()), c->st.g_bn_running_mean,
                               c->st.g_bn_running_var, c->st.g_bn_batches, c->g_bn[0], partial, c->gC[0], BN_MOMENTUM,
                               BN_EPS, s);
-        launch_bn_relu(c->dt, c->fc_y, A[0], B, c->F, c->g_bn[0], s);
+        launch_bn_relu(c->dt, c->fc_y, A[0], B, c->F, c->g_bn[0], gs, s);
     }
     for (int l = 1; l <= c->Lg; ++l) {
         const int Hi = 4 << (l - 1), Ci = c->gC[l - 1], Co = c->gC[l];
@@ -784,16 +788,16 @@ static void g_forward_pass(siggan_ctx* c, const float* z, int B, bool training, 
             launch_bn_train_stats(c->dt, c->g_y[l], R, C, GP(c, gi_bn_w(l)), GP(c, gi_bn_b(l)), c->st.g_bn_running_mean + off,
                                   c->st.g_bn_running_var + off, c->st.g_bn_batches + l, c->g_bn[l], partial, 0,
                                   BN_MOMENTUM, BN_EPS, s);
-            if (l < c->Lg) launch_bn_relu(c->dt, c->g_y[l], A[l], R, C, c->g_bn[l], s);
+            if (l < c->Lg) launch_bn_relu(c->dt, c->g_y[l], A[l], R, C, c->g_bn[l], gs, s);
         } else {
             a.out = A[l]; a.epi = EPI_AFFINE_RELU; a.scale = c->g_bne[l]; a.shift = c->g_bne[l] + C;
             launch_gconv(a, s);
         }
     }
     if (training)
-        launch_final_fwd(c->dt, c->g_y[c->Lg], c->wfin_t, GP(c, gi_fin_b(c)), img, B, c->S, c->gC[c->Lg], s, c->g_bn[c->Lg], done);
+        launch_final_fwd(c->dt, c->g_y[c->Lg], c->wfin_t, GP(c, gi_fin_b(c)), img, B, c->S, c->gC[c->Lg], gs, s, c->g_bn[c->Lg], done);
     else
-        launch_final_fwd(c->dt, A[c->Lg], c->wfin_t, GP(c, gi_fin_b(c)), img, B, c->S, c->gC[c->Lg], s, nullptr, done);
+        launch_final_fwd(c->dt, A[c->Lg], c->wfin_t, GP(c, gi_fin_b(c)), img, B, c->S, c->gC[c->Lg], gs, s, nullptr, done);
     c->ga_last_B = training ? B : 0;
 }
 
@@ -931,6 +935,7 @@ static void d_backward_pass(siggan_ctx* c, Lanes& L, const float* x0, int n0, co
 // Backward through the Generator from d(pre-tanh) in c->dpre; fills the G gradient arena.  Lane m:
 // BatchNorm backward and the input-gradient chain; lane a: the weight gradients.
 static void g_backward_pass(siggan_ctx* c, Lanes& L, const float* z, int B) {
+    const float gs = c->cfg.g_leaky_slope;                   // the Generator's activation slope (g_dact, act.h)
     const int Lg = c->Lg, S = c->S;
     int pre_rows = 0;              // partial rows of block l's BatchNorm-backward sums left by the input-gradient GEMM of block l+1
     for (int l = Lg; l >= 1; --l) {
@@ -941,11 +946,11 @@ static void g_backward_pass(siggan_ctx* c, Lanes& L, const float* z, int B) {
         hipEvent_t const ef = L.fork_event(L.a);
         if (l == Lg) {   // final conv's input-gradient folded into this block's BatchNorm backward; its weight gradient rides in
                          // the same pass over y and its row sums stay on this lane (a 5 us kernel does not pay for a fork + join)
-            launch_final_bwd_reduce(c->dt, c->dpre, c->wfin_t, c->g_y[l], B, S, Co, c->g_bn[l], c->partial, c->partial_b, L.m);
+            launch_final_bwd_reduce(c->dt, c->dpre, c->wfin_t, c->g_y[l], B, S, Co, c->g_bn[l], c->partial, c->partial_b, gs, L.m);
             launch_final_bn_bwd_apply(c->dt, c->dpre, c->wfin_t, c->g_y[l], c->g_da[l], B, S, Co, c->g_bn[l], c->partial, c->partial_b,
-                                      GG(c, gi_fin_w(c)), GG(c, gi_fin_b(c)), GG(c, gi_bn_w(l)), GG(c, gi_bn_b(l)), L.m, ef);
+                                      GG(c, gi_fin_w(c)), GG(c, gi_fin_b(c)), GG(c, gi_bn_w(l)), GG(c, gi_bn_b(l)), gs, L.m, ef);
         } else
-            launch_bn_bwd(c->dt, c->g_da[l], c->g_y[l], R, Co, c->g_bn[l], c->partial, GG(c, gi_bn_w(l)), GG(c, gi_bn_b(l)), 0, L.m, pre_rows, ef);
+            launch_bn_bwd(c->dt, c->g_da[l], c->g_y[l], R, Co, c->g_bn[l], c->partial, GG(c, gi_bn_w(l)), GG(c, gi_bn_b(l)), 0, gs, L.m, pre_rows, ef);
         L.fork_after(L.a, ef);
         // weight gradient: small = block input a[l-1] (Hi), large = dy[l] (Ho)
         // (one fork per block; per two blocks measured the same, weight gradients on the main lane 2.5 % slower: DESIGN 4)
@@ -959,15 +964,15 @@ static void g_backward_pass(siggan_ctx* c, Lanes& L, const float* z, int B) {
         a.in = c->g_da[l]; a.wp = c->g_dn[l]; a.out = c->g_da[l - 1];
         a.B = B; a.Hi = Ho; a.Wi = Ho; a.Ci = Co; a.Co = Ci;
         a.lgHr = ilog2i(Hi); a.lgWr = a.lgHr; a.Ho = Hi; a.Wo = Hi; a.form = 0; a.M = B * Hi * Hi; a.epi = EPI_RAW;
-        if (l >= 2) {              // its output is d(relu output) of block l-1: that block's BatchNorm-backward sums ride in the epilogue
+        if (l >= 2) {              // its output is d(activation output) of block l-1: that block's BatchNorm-backward sums ride in the epilogue
             a.epi = EPI_BN_BWD_STATS; a.aref = c->g_y[l - 1]; a.bnp = c->g_bn[l - 1]; a.stat0 = c->partial; a.stat_cap = PARTIAL_FLOATS;
         }
         pre_rows = launch_gconv(a, L.m);
     }
     if (!(c->fc_fused && launch_fc_bwd_fused(c->dt, c->g_da[0], c->fc_y, z, c->g_bn[0], GG(c, gi_fc_w()), GG(c, gi_fc_b()),
-                                             GG(c, gi_bn0_w()), GG(c, gi_bn0_b()), B, c->latent, c->gC[0], L.m))) {
+                                             GG(c, gi_bn0_w()), GG(c, gi_bn0_b()), B, c->latent, c->gC[0], gs, L.m))) {
         launch_bn_bwd(c->dt, c->g_da[0], c->fc_y, B, c->F, c->g_bn[0], c->partial, GG(c, gi_bn0_w()), GG(c, gi_bn0_b()),
-                      c->gC[0], L.m);
+                      c->gC[0], gs, L.m);
         launch_fc_wgrad(c->dt, c->g_da[0], z, GG(c, gi_fc_w()), GG(c, gi_fc_b()), B, c->latent, c->gC[0], L.m);
     }
     L.join(L.a);
@@ -1765,7 +1770,8 @@ extern "C" int siggan_debug_tensor(siggan_ctx* c, const char* name, int32_t idx,
         // after a training forward the last block's activation exists only as y + the BatchNorm table: form it now
         const int64_t H = c->S;
         HIPCHK(hipDeviceSynchronize());
-        launch_bn_relu(c->dt, c->g_y[idx], c->g_a[idx], (int64_t)c->ga_last_B * H * H, c->gC[idx], c->g_bn[idx], (hipStream_t)stream);
+        launch_bn_relu(c->dt, c->g_y[idx], c->g_a[idx], (int64_t)c->ga_last_B * H * H, c->gC[idx], c->g_bn[idx], c->cfg.g_leaky_slope,
+                       (hipStream_t)stream);
         LAUNCHCHK();
     }
     if (typed && c->dt != DT_F32) { launch_to_f32(c->dt, src, out_dev, n, (hipStream_t)stream); LAUNCHCHK(); }

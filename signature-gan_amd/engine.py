@@ -30,8 +30,11 @@ class Engine:
     no conversion)."""
 
     def __init__(self, latent_dim=100, image_size=64, max_batch=64, device="cuda:0", seed=0,
-                 dropout=0.25, leaky_slope=0.2, image_channels=1, dtype="f32", f16_grad_scale=0.0, spectral_norm=False):
+                 dropout=0.25, leaky_slope=0.2, image_channels=1, dtype="f32", f16_grad_scale=0.0, spectral_norm=False,
+                 g_activation="relu", g_leaky_slope=0.2):
         layout.check_size(image_size)
+        if g_activation not in ("relu", "leaky_relu"):
+            raise ValueError(f"g_activation must be 'relu' or 'leaky_relu', got {g_activation!r}")
         if image_channels != 1:
             raise ValueError(f"only image_channels == 1 is built, got {image_channels}")
         self.device = torch.device(device)
@@ -52,6 +55,10 @@ class Engine:
         # torch.nn.utils.spectral_norm on every Discriminator conv + the classifier (discriminator_vanilla_gan.py:60-62,200-202):
         # d_params then holds weight_orig, d_sn_u / d_sn_v the weight_u / weight_v buffers
         self.spectral_norm = bool(spectral_norm)
+        # the Generator's activation after every BatchNorm: ReLU (the reference Generator) or LeakyReLU(g_leaky_slope) (the
+        # ablation study's ConfigurableGenerator, ablation_vanilla_gan_signatures.py:159-328); the library takes slope 0 as ReLU
+        self.g_activation = g_activation
+        self.g_slope = float(g_leaky_slope) if g_activation == "leaky_relu" else 0.0
         self._h = None
         self._staged = None
         self._comm = None
@@ -99,7 +106,7 @@ class Engine:
     def _create_context(self):
         cfg = _lib.Config(self.device.index, self.latent_dim, self.image_size, 1, self.max_batch,
                           self.dropout, self.leaky_slope, self._seed, _lib.DTYPES[self.dtype], self.f16_grad_scale,
-                          int(self.spectral_norm))
+                          int(self.spectral_norm), self.g_slope)
         h = C.c_void_p()
         with torch.cuda.device(self.device):
             _lib.check(self.lib.siggan_create(C.byref(cfg), C.byref(h)))
