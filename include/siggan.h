@@ -48,12 +48,12 @@ extern "C" {
 #endif
 
 #define SIGGAN_ABI_VERSION 4   /* 2: siggan_stage_real, siggan_augment_batch; 3: siggan_config.dtype, siggan_rng_state, siggan_comm_*;
-                                * 4: siggan_config.g_leaky_slope (appended) */
+                                * 4: siggan_config.g_leaky_slope (appended); siggan_prof_launch (a test hook, added) */
 
 enum {
     SIGGAN_OK = 0,
     SIGGAN_E_INVALID = -1,     /* bad argument (maps to ValueError in the Python shim) */
-    SIGGAN_E_STATE = -2,       /* call sequence / binding missing                      */
+    SIGGAN_E_STATE = -2,       /* call sequence / binding missing; a launch the library refused (sticky) */
     SIGGAN_E_HIP = -3,         /* HIP runtime error                                    */
     SIGGAN_E_NOMEM = -4
 };
@@ -311,6 +311,10 @@ int siggan_prof_enable(siggan_ctx *ctx, int32_t on);
 int32_t siggan_prof_slots(void);
 int siggan_prof_read(siggan_ctx *ctx, int32_t idx, char *name, int32_t name_cap, int64_t *launches,
                      double *ms, double *flops, double *bytes);
+/* test hook: *count = the launches recorded since siggan_prof_enable; for launch idx (in launch order) the first n of
+ * {kernel slot, form (0 down / 1 up), epilogue asked for, epilogue run, rows per class M, Ci, Co} (gconv.h: GConvArgs,
+ * enum Epilogue; -1 where a launch is no implicit GEMM).  Does not synchronise. */
+int siggan_prof_launch(siggan_ctx *ctx, int64_t idx, int32_t *fields, int32_t n, int64_t *count);
 
 /* test hook: copy the first n elements of a library-owned workspace tensor (NHWC), converted to fp32, into out_dev:
  * "g_y"/"g_a"/"g_da" (layer 0..Lg), "d_a"/"d_dv" (block 1..Ld), "img", "dpre", "logits",

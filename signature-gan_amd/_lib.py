@@ -15,6 +15,8 @@ _HERE = os.path.dirname(os.path.abspath(__file__))
 LIB_PATH = os.environ.get("SIGGAN_LIB_PATH") or os.path.join(_HERE, "libsiggan_hip.so")
 ABI_VERSION = 4
 M_COUNT = 16
+# the implicit-GEMM epilogues in gconv.h's enum Epilogue order (siggan_prof_launch reports them by number)
+EPILOGUES = ("raw", "bias_lrelu_drop", "affine_relu", "lrelu_bwd", "bn_bwd_stats")
 METRIC_INDEX = {"d_loss": 0, "d_loss_real": 1, "d_loss_fake": 2, "d_real_mean": 3, "d_fake_mean": 4,
                 "d_real_acc": 5, "d_fake_acc": 6, "d_grad_norm": 7, "g_loss": 8, "g_fake_mean": 9,
                 "g_grad_norm": 10, "d_skipped": 11, "g_skipped": 12}
@@ -95,6 +97,7 @@ _SIGNATURES = {
     "siggan_device_info": (C.c_int, [_I32, C.POINTER(_I32), C.POINTER(_I32), C.POINTER(_I64)]),
     "siggan_prof_enable": (C.c_int, [_P, _I32]),
     "siggan_prof_slots": (_I32, []),
+    "siggan_prof_launch": (C.c_int, [_P, _I64, C.POINTER(_I32), _I32, C.POINTER(_I64)]),
     "siggan_prof_read": (C.c_int, [_P, _I32, C.c_char_p, _I32, C.POINTER(_I64), C.POINTER(C.c_double), C.POINTER(C.c_double),
                                    C.POINTER(C.c_double)]),
     "siggan_debug_tensor": (C.c_int, [_P, C.c_char_p, _I32, _P, _I64, _P]),

@@ -101,16 +101,23 @@ struct WgradArgs {
 // Optional per-kernel timing (bench.py's roofline leg): when a profiler is installed every MFMA
 // launch is bracketed by HIP events on its own stream and tagged with its algorithmic FLOPs.
 struct Prof {
-    struct Rec { int id; double flops, bytes; hipEvent_t e0, e1; };   // algorithmic FLOPs and HBM bytes (operands read once + result written once)
+    struct Rec {
+        int id; double flops, bytes; hipEvent_t e0, e1;   // algorithmic FLOPs and HBM bytes (operands read once + result written once)
+        // implicit-GEMM launches (else -1): form, the epilogue the caller asked for and the one that ran (they differ where
+        // EPI_BN_BWD_STATS fell back to EPI_RAW: the stat_cap carve was too small), rows per class, Ci, Co
+        int form, epi_req, epi, M, Ci, Co;
+    };
     static constexpr int NID = 8;
     std::vector<Rec> recs;
     static const char* name(int id);
     void begin(int id, double flops, double bytes, hipStream_t st);
+    void shape(const GConvArgs& a, int epi_req);      // tags the last record with the GEMM it launched
     void clear();
 };
 extern Prof* g_prof;
 
-// returns the number of partial rows written to stat0 / stat1 (EPI_BN_BWD_STATS), 0 otherwise
+// returns the number of partial rows written to stat0 / stat1 (EPI_BN_BWD_STATS), 0 otherwise; -1, with nothing enqueued,
+// for an EPI_BN_BWD_STATS launch without a carve (stat0 null or stat_cap <= 0)
 int launch_gconv(const GConvArgs& a, hipStream_t st);
 // 16-bit operand kernels (gconv16.hip); cfg: 0 = 128x128, 2 = 64x64, 3 = 128x32 tiles; e0 / e1: optional timing events
 void launch_gconv16(int cfg, const GConvArgs& a, dim3 grid, hipStream_t st, hipEvent_t e0, hipEvent_t e1, int kq = 1);

@@ -597,8 +597,13 @@ const char* Prof::name(int id) {
 // hipEventRecord pair would include.
 void Prof::begin(int id, double flops, double bytes, hipStream_t) {
     Rec r; r.id = id; r.flops = flops; r.bytes = bytes;
+    r.form = r.epi_req = r.epi = r.M = r.Ci = r.Co = -1;
     (void)hipEventCreate(&r.e0); (void)hipEventCreate(&r.e1);
     recs.push_back(r);
+}
+void Prof::shape(const GConvArgs& a, int epi_req) {
+    Rec& r = recs.back();
+    r.form = a.form; r.epi_req = epi_req; r.epi = a.epi; r.M = a.M; r.Ci = a.Ci; r.Co = a.Co;
 }
 void Prof::clear() {
     for (auto& r : recs) { (void)hipEventDestroy(r.e0); (void)hipEventDestroy(r.e1); }
@@ -638,7 +643,10 @@ static int launch_cfg(const GConvArgs& a_in, hipStream_t st, int id, int nsplit)
     }
     dim3 grid(tiles, nsplit, ncls);
     // algorithmic FLOPs = 2 * M * Co * (taps * Ci) per class (== 2 * conv MACs, padding taps included)
-    if (g_prof) g_prof->begin(id, 2.0 * a.M * a.Co * (double)((a.form == 0 ? 16 : 4) * a.Ci) * ncls, gconv_bytes(a), st);
+    if (g_prof) {
+        g_prof->begin(id, 2.0 * a.M * a.Co * (double)((a.form == 0 ? 16 : 4) * a.Ci) * ncls, gconv_bytes(a), st);
+        g_prof->shape(a, a_in.epi);
+    }
     hipEvent_t e0 = g_prof ? g_prof->recs.back().e0 : nullptr, e1 = g_prof ? g_prof->recs.back().e1 : nullptr;
     if (a.dt != DT_F32) {
         launch_gconv16(id, a, grid, st, e0, e1, KQ);
@@ -661,6 +669,11 @@ int launch_gconv(const GConvArgs& a_in, hipStream_t st) {
     // to cover each other's barrier / first-fragment bubbles.  Take the largest tile that still
     // gives that; when even 64x64 tiles cannot, split K into slabs (summed by k_splitk_epilogue).
     GConvArgs a = a_in;
+    // The BatchNorm-backward sums need a carve to land in.  A launch without one (a caller that did not set stat0 /
+    // stat_cap) is refused before anything is enqueued: with stat_cap <= 0 it would quietly take the raw-store fallback
+    // below (meant for a batch that outgrows a real carve) on every launch, and with a null stat0 and a positive cap the
+    // epilogue would store its partial rows through a null pointer.
+    if (a.epi == EPI_BN_BWD_STATS && (a.stat0 == nullptr || a.stat_cap <= 0)) return -1;
     const int ncls = a.form == 0 ? 1 : 4;
     auto blocks = [&](int bm, int bn) { return ((a.M + bm - 1) / bm) * (a.Co / bn) * ncls; };
     const int nk = (a.form == 0 ? 16 : 4) * (a.Ci / BK);
@@ -696,7 +709,10 @@ int launch_gconv(const GConvArgs& a_in, hipStream_t st) {
         ((1 << (a.lgHr + a.lgWr)) % 128) == 0 && a.lgWr >= 4 && a.lgWr <= 6) {
         // all four parity classes per workgroup, input patch resident in LDS (k_gconv_up4): the short-K Generator blocks
         dim3 grid(a.M / 128);
-        if (g_prof) g_prof->begin(5, 2.0 * a.M * a.Co * (double)(4 * a.Ci) * 4, gconv_bytes(a), st);
+        if (g_prof) {
+            g_prof->begin(5, 2.0 * a.M * a.Co * (double)(4 * a.Ci) * 4, gconv_bytes(a), st);
+            g_prof->shape(a, a.epi);
+        }
         hipEvent_t e0 = g_prof ? g_prof->recs.back().e0 : nullptr, e1 = g_prof ? g_prof->recs.back().e1 : nullptr;
         if (gen_lk(a)) {
             if (a.Ci == 32) hipExtLaunchKernelGGL((k_gconv_up4<32, true>), grid, dim3(256), 0, st, e0, e1, 0, a);

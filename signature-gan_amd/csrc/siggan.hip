@@ -185,6 +185,7 @@ struct siggan_ctx {
     bool early_ar;       // the last D block's weight gradient is already being all-reduced on s_n (ev_ar marks its end)
     bool dreal_orphan;   // a D(real) forward enqueued on lane c was abandoned: the next enqueue waits for ev_dreal first
     hipError_t lane_err; // first failed event record / wait of a fork or join (checked after every phase)
+    const char* refused; // sticky: a launcher refused a launch of a step (nothing was enqueued for it; lane_check reports it)
     // data-parallel communicator (siggan_comm_init): world 1 = none
     ncclComm_t comm; int comm_rank, comm_world; int comm_err;
     int staged_B;        // batch of a real batch staged for the NEXT D step by siggan_stage_real (0: none)
@@ -706,6 +707,7 @@ static int lane_check(siggan_ctx* c) {
     if (c->ride_late && __atomic_load_n(c->ride_late, __ATOMIC_ACQUIRE))
         return fail(SIGGAN_E_STATE, "riders did not report: the optimiser update's owner of the first Discriminator block stopped "
                                     "waiting for them (a G step's first block may have used twice-updated weights)");
+    if (c->refused) return fail(SIGGAN_E_STATE, "%s", c->refused);
     if (c->lane_err == hipSuccess) return SIGGAN_OK;
     const hipError_t e = c->lane_err; c->lane_err = hipSuccess;
     return fail(SIGGAN_E_HIP, "an event record / stream wait / prepare table of the step failed: %s", hipGetErrorString(e));
@@ -968,6 +970,10 @@ static void g_backward_pass(siggan_ctx* c, Lanes& L, const float* z, int B) {
             a.epi = EPI_BN_BWD_STATS; a.aref = c->g_y[l - 1]; a.bnp = c->g_bn[l - 1]; a.stat0 = c->partial; a.stat_cap = PARTIAL_FLOATS;
         }
         pre_rows = launch_gconv(a, L.m);
+        if (pre_rows < 0) {        // (the pass goes on, so the lanes still join; the step's call returns SIGGAN_E_STATE)
+            c->refused = "the Generator's input-gradient GEMM was refused: its BatchNorm-backward sums had no carve (stat_cap)";
+            pre_rows = 0;
+        }
     }
     if (!(c->fc_fused && launch_fc_bwd_fused(c->dt, c->g_da[0], c->fc_y, z, c->g_bn[0], GG(c, gi_fc_w()), GG(c, gi_fc_b()),
                                              GG(c, gi_bn0_w()), GG(c, gi_bn0_b()), B, c->latent, c->gC[0], gs, L.m))) {
@@ -1274,6 +1280,7 @@ static void run_phase_body(siggan_ctx* c, Lanes& L, const PhaseKey& k) {
 // forked from it).  Graph mode: the phase is captured once per distinct key on the library's own
 // main lane (a caller stream may be the legacy default stream, which cannot be captured) and replayed.
 static int run_phase(siggan_ctx* c, const PhaseKey& k, hipStream_t u) {
+    if (c->refused) return lane_check(c);           // a step's launch was refused: nothing more is enqueued on this context
     const bool overlap = (c->mode & SIGGAN_MODE_OVERLAP) != 0;
     const bool graph = (c->mode & SIGGAN_MODE_GRAPH) != 0 && g_prof == nullptr;
     if (graph && c->comm && k.phase >= 2) return fail(SIGGAN_E_STATE, "SIGGAN_MODE_GRAPH is not available with a communicator");
@@ -1295,6 +1302,7 @@ static int run_phase(siggan_ctx* c, const PhaseKey& k, hipStream_t u) {
         run_phase_body(c, L, k);
         hipError_t e1 = hipStreamEndCapture(c->s_m, &g);
         if (e1 != hipSuccess || !g) return fail(SIGGAN_E_HIP, "stream capture failed: %s", hipGetErrorString(e1));
+        if (c->refused) { (void)hipGraphDestroy(g); return lane_check(c); }     // (a refused launch: not cached, never replayed)
         hipError_t e2 = hipGraphInstantiate(&exec, g, nullptr, nullptr, 0);
         (void)hipGraphDestroy(g);
         if (e2 != hipSuccess) return fail(SIGGAN_E_HIP, "hipGraphInstantiate: %s", hipGetErrorString(e2));
@@ -1724,6 +1732,17 @@ extern "C" int siggan_prof_read(siggan_ctx* c, int32_t idx, char* name, int32_t 
         HIPCHK(hipEventElapsedTime(&t, r.e0, r.e1));
         *launches += 1; *ms += t; *flops += r.flops; *bytes += r.bytes;
     }
+    return SIGGAN_OK;
+}
+
+extern "C" int siggan_prof_launch(siggan_ctx* c, int64_t idx, int32_t* fields, int32_t n, int64_t* count) {
+    if (!c || !count || (n > 0 && !fields)) return fail(SIGGAN_E_INVALID, "bad argument");
+    *count = (int64_t)g_prof_store.recs.size();
+    if (n <= 0) return SIGGAN_OK;
+    if (idx < 0 || idx >= *count) return fail(SIGGAN_E_INVALID, "launch %lld of %lld", (long long)idx, (long long)*count);
+    const Prof::Rec& r = g_prof_store.recs[(size_t)idx];
+    const int32_t v[7] = {r.id, r.form, r.epi_req, r.epi, r.M, r.Ci, r.Co};
+    for (int i = 0; i < n && i < 7; ++i) fields[i] = v[i];
     return SIGGAN_OK;
 }
 

@@ -463,6 +463,26 @@ class Engine:
                             "bytes": by.value})
         return out
 
+    def prof_launches(self):
+        """[{kernel, form, epi_req, epi, M, Ci, Co}] for every launch recorded since prof_enable, in launch order (test hook:
+        which GEMM ran on which tile; epilogue names as _lib.EPILOGUES, None where a launch is no implicit GEMM)."""
+        names = {}
+        for i in range(self.lib.siggan_prof_slots()):
+            buf = C.create_string_buffer(64)
+            n, ms, fl, by = C.c_int64(), C.c_double(), C.c_double(), C.c_double()
+            _lib.check(self.lib.siggan_prof_read(self._h, i, buf, 64, C.byref(n), C.byref(ms), C.byref(fl), C.byref(by)))
+            names[i] = buf.value.decode()
+        count = C.c_int64()
+        _lib.check(self.lib.siggan_prof_launch(self._h, 0, None, 0, C.byref(count)))
+        f = (C.c_int32 * 7)()
+        out = []
+        for i in range(count.value):
+            _lib.check(self.lib.siggan_prof_launch(self._h, i, f, 7, C.byref(count)))
+            epi = lambda e: _lib.EPILOGUES[e] if 0 <= e < len(_lib.EPILOGUES) else None
+            out.append({"kernel": names.get(f[0], "?"), "form": f[1], "epi_req": epi(f[2]), "epi": epi(f[3]), "M": f[4],
+                        "Ci": f[5], "Co": f[6]})
+        return out
+
     def debug_tensor(self, name, index, shape):
         """Copy of a workspace tensor (test hook): first prod(shape) floats, reshaped."""
         n = 1

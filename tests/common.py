@@ -22,9 +22,38 @@ CASES = [(64, 100, 4), (64, 100, 64), (128, 128, 4), (128, 128, 32), (64, 100, 1
          (128, 128, 5),     # the same at 128x128 (five blocks per network, the 64-channel patch kernel)
          (64, 50, 8)]       # latent_dim % 4 != 0 (the ablation grid's z = 50): the Generator fc's generic (non-MFMA) kernels
 # The workloads bench.py times (profiles/r04_bench_*.json): (dtype, size, latent, batch per GPU) -- the headline, BASELINE
-# configs[3], and the 128x128 fp32 / bf16 / fp16 shards.  The timed path (DataParallelStep.step(real, next_real=real)) is
-# held to the oracle and to the split steps at exactly these shapes.
-TIMED = [("f32", 64, 100, 64), ("f32", 64, 100, 128), ("f32", 128, 128, 32), ("bf16", 64, 100, 64), ("f16", 128, 128, 32)]
+# configs[3], the 128x128 fp32 / bf16 / fp16 shards, and the larger batches of the same records (fp32 and bf16 64x64 at 256,
+# bf16 64x64 at 128, fp16 128x128 at 64).  The timed path (DataParallelStep.step(real, next_real=real)) is held to the oracle
+# and to the split steps at exactly these shapes.
+TIMED = [("f32", 64, 100, 64), ("f32", 64, 100, 128), ("f32", 128, 128, 32), ("bf16", 64, 100, 64), ("f16", 128, 128, 32),
+         ("f32", 64, 100, 256), ("bf16", 64, 100, 128), ("bf16", 64, 100, 256), ("f16", 128, 128, 64)]
+# Batches no benchmark record reaches, each there for a path the launchers (launch_gconv, launch_fc_*_fused, launch_bn_bwd)
+# select from the batch size alone; run through the timed step against the oracle (test_timed_step_gpu).  (..., steps):
+BATCH_EDGES = [
+    # the 128x128 GEMM tile on ragged rows (M % 128 != 0: the G step's D backward); the fused fc kernels at MT = 8
+    # (129 <= B <= 256) on an odd batch; k_adam_pack with an odd rider count (255 x 16)
+    ("f32", 64, 100, 255, 4),
+    # the stat_cap fallback: the G input gradients of blocks 5 and 4 outgrow the partial-row carve, store raw values, and
+    # that BatchNorm backward runs k_colreduce + k_bn_bwd_fin + k_bn_bwd_apply; the generic fc kernels at a batch > 256.
+    # One step: the oracle's four would take minutes of CPU time
+    ("f32", 128, 128, 1025, 1),
+]
+# The launches each added workload exists for, pinned by test_timed_step_gpu's coverage test against the library's per-launch
+# profile (Engine.prof_launches): every pattern must match one launch of a timed step -- kernel tile, form (0 down / 1 up),
+# epilogue asked for / run, rows per class M, Ci, Co.  A retuned threshold then names the row that no longer reaches its
+# path.  (bf16 b128 is a benchmark record with no launch of its own: it is not listed.)
+_T128 = "k_gconv<128,128>"
+COVERS = {
+    # D forward block 2 of a B-row pass: down form, bias + LeakyReLU + dropout epilogue, B*16*16 rows = 512 tiles
+    ("f32", 64, 100, 256): [dict(kernel=_T128, form=0, epi="bias_lrelu_drop", M=256 * 16 * 16, Ci=64, Co=128)],
+    ("bf16", 64, 100, 256): [dict(kernel=_T128, form=0, epi="bias_lrelu_drop", M=256 * 16 * 16, Ci=64, Co=128)],
+    ("f16", 128, 128, 64): [dict(kernel=_T128, form=0, epi="bias_lrelu_drop", M=64 * 32 * 32, Ci=64, Co=128)],
+    # the G step's D backward (B rows): block 3's input gradient, up form, 255*8*8 = 127.5 row tiles x 4 classes
+    ("f32", 64, 100, 255): [dict(kernel=_T128, form=1, epi="lrelu_bwd", M=255 * 8 * 8, Ci=256, Co=128)],
+    # the stat_cap fallback: the G input gradients of blocks 5 and 4 ask for the BatchNorm-backward sums and store raw values
+    ("f32", 128, 128, 1025): [dict(form=0, epi_req="bn_bwd_stats", epi="raw", M=1025 * 64 * 64, Ci=32, Co=32),
+                              dict(form=0, epi_req="bn_bwd_stats", epi="raw", M=1025 * 32 * 32, Ci=32, Co=64)],
+}
 SEED = dict(state_g=101, state_d=202, adam_g=303, adam_d=404, z=11, real=22)
 
 

@@ -415,7 +415,7 @@ def test_execution_modes_are_bitwise_identical(dtype="f32", size=64, latent=100,
 @pytest.mark.parametrize("dtype,size,latent,batch", [t for t in TIMED if t[0] == "f32"])
 def test_execution_modes_are_bitwise_identical_at_timed_shapes(dtype, size, latent, batch):
     """The same at the fp32 workloads bench.py times: tile / split-K choice, the classifier in the split-K epilogue and the
-    number of k_adam_pack's riders (B * S/4: 1024 and 2048 here) all depend on the batch."""
+    number of k_adam_pack's riders (B * S/4: 1024, 2048 and 4096 here) all depend on the batch."""
     test_execution_modes_are_bitwise_identical(dtype, size, latent, batch)
 
 

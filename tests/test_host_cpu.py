@@ -323,3 +323,42 @@ def test_fixtures_record_the_thread_count_the_oracle_tests_pin():
         for k in (k for k in f.files if k.endswith("meta")):
             threads = json.loads(str(f[k])).get("threads")
             assert threads in (None, FIXTURE_THREADS), (p, k, threads)
+
+
+_REFUSAL_DRIVER = r"""
+#include <stdio.h>
+#include <string.h>
+#include "gconv.h"
+int main() {
+    int n = 0;
+    if (hipGetDeviceCount(&n) == hipSuccess && n > 0) { puts("device"); return 0; }   // (below, a regression would launch)
+    siggan::GConvArgs a; memset(&a, 0, sizeof a);
+    a.dt = siggan::DT_F32; a.form = 0; a.B = 2; a.Hi = a.Wi = 16; a.Ci = 64; a.Co = 32; a.Ho = a.Wo = 8;
+    a.lgHr = a.lgWr = 3; a.M = 2 * 8 * 8; a.epi = siggan::EPI_BN_BWD_STATS;
+    const int no_carve = siggan::launch_gconv(a, nullptr);
+    float carve[4];
+    a.stat0 = carve;                          // a carve whose size the caller did not set
+    const int no_cap = siggan::launch_gconv(a, nullptr);
+    printf("%d %d\n", no_carve, no_cap);
+    return 0;
+}
+"""
+
+
+def test_gconv_refuses_a_statistics_epilogue_without_a_carve(tmp_path):
+    """launch_gconv refuses an EPI_BN_BWD_STATS launch whose caller did not set stat0 / stat_cap (-1, nothing enqueued)
+    instead of storing raw values that the caller's BatchNorm backward would then read as partial sums; siggan.hip turns
+    the refusal into SIGGAN_E_STATE.  A host-only program calls the library's launcher on a box without a GPU."""
+    import subprocess
+    src, exe = tmp_path / "refuse.cpp", tmp_path / "refuse"
+    src.write_text(_REFUSAL_DRIVER)
+    pkg = os.path.join(ROOT, "signature-gan_amd")
+    lib = os.path.join(pkg, "libsiggan_hip.so")
+    assert os.path.exists(lib), "build() first"
+    hipcc = os.environ.get("HIPCC", "/opt/rocm/bin/hipcc")
+    subprocess.run([hipcc, "-x", "hip", "--cuda-host-only", "--offload-arch=gfx950", "-std=c++17", "-I", os.path.join(pkg, "csrc"),
+                    str(src), "-x", "none", "-o", str(exe), lib, f"-Wl,-rpath,{pkg}"], check=True, capture_output=True, timeout=300)
+    out = subprocess.run([str(exe)], check=True, capture_output=True, text=True, timeout=60).stdout.split()
+    if out == ["device"]:
+        pytest.skip("a GPU is visible: this check runs where a regression cannot launch the refused kernel")
+    assert out == ["-1", "-1"], out

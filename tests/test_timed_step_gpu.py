@@ -9,13 +9,18 @@ contexts), and the next step's D(real) forward with its dropout tables drawn ahe
 already-updated network -- making DataParallelStep.step's ABI calls with read points between them, and every half-step is
 compared with the oracle run from the engine's own state before it (as test_three_step_sequence does), given the noise the
 library drew and the HIP path's sign decisions.  One assertion shows the read points did not change the path: the final state
-equals an uninstrumented dp.step loop's, bit for bit."""
+equals an uninstrumented dp.step loop's, bit for bit.
+
+The same check runs at common.BATCH_EDGES, batches that reach launcher paths no benchmark record does (one step at the
+largest), and one test pins the GEMM tile each added workload exists for (common.COVERS) through the library's profiler."""
 import copy
+import resource
+import time
 
 import pytest
 import torch
 
-from common import TIMED, O, assert_close
+from common import BATCH_EDGES, COVERS, TIMED, O, assert_close
 from hipcommon import (assert_same_state, bench_setup, count_sign_flips, debug_scalar, full_state, hip_d_masks, hip_signs_d,
                        hip_signs_g, oracle_state_of)
 from signature_gan_amd import _lib
@@ -42,6 +47,11 @@ def _scale_of(o_grads, names):
     return {k: max(float(o_grads[k].abs().max()), (1e-2 if k == "fc.0.bias" else 1e-3) * gscale) for k in names}
 
 
+def _worst_tensor(got, want, names, scale):
+    """name of the gradient tensor furthest from the oracle's, relative to its comparison scale (for the margins record)"""
+    return max(names, key=lambda k: float((got[k] - want[k]).abs().max()) / scale[k])
+
+
 def _metric_frac(got, want, keys, rt=2e-4, at=2e-6):
     """largest |got - want| as a fraction of assert_close's tolerance"""
     return max(abs(got[k] - want[k]) / (at + rt * abs(want[k])) for k in keys)
@@ -58,9 +68,11 @@ def _fp32_d_half(eng, size, real, z, masks, signs, state, m):
         assert_close(met[k], om[k], 2e-4, 2e-6, f"D metric {k} vs oracle(HIP signs) from the engine's state")
     m["metric_frac"] = max(m["metric_frac"], _metric_frac(met, om, DK))
     names = list(eng.views("d", "grads"))
-    worst = _close_halves(_Half.of_engine(eng, "d", met), _Half.of_oracle(om, og, d_sd, d_opt), names, _scale_of(og, names),
-                          init_d, init_opt, 1e-4, "D half vs oracle(HIP signs)")
-    m["d_grad"] = max(m["d_grad"], worst)
+    mine, scale = _Half.of_engine(eng, "d", met), _scale_of(og, names)
+    worst = _close_halves(mine, _Half.of_oracle(om, og, d_sd, d_opt), names, scale, init_d, init_opt, 1e-4,
+                          "D half vs oracle(HIP signs)")
+    if worst >= m["d_grad"]:
+        m["d_grad"], m["d_grad_worst_tensor"] = worst, _worst_tensor(mine.g, og, names, scale)
 
 
 def _fp32_g_half(eng, size, z, signs, state, m):
@@ -74,9 +86,11 @@ def _fp32_g_half(eng, size, z, signs, state, m):
         assert_close(met[k], om[k], 2e-4, 2e-6, f"G metric {k} vs oracle(HIP signs) from the engine's state")
     m["metric_frac"] = max(m["metric_frac"], _metric_frac(met, om, GK))
     names = list(eng.views("g", "grads"))
-    worst = _close_halves(_Half.of_engine(eng, "g", met), _Half.of_oracle(om, og, g_sd, g_opt), names, _scale_of(og, names),
-                          init_g, init_opt, 1e-4, "G half vs oracle(HIP signs)")
-    m["g_grad"] = max(m["g_grad"], worst)
+    mine, scale = _Half.of_engine(eng, "g", met), _scale_of(og, names)
+    worst = _close_halves(mine, _Half.of_oracle(om, og, g_sd, g_opt), names, scale, init_g, init_opt, 1e-4,
+                          "G half vs oracle(HIP signs)")
+    if worst >= m["g_grad"]:
+        m["g_grad"], m["g_grad_worst_tensor"] = worst, _worst_tensor(mine.g, og, names, scale)
     for k, t in eng.bn_views().items():
         if "num_batches" in k:
             assert int(t) == int(g_sd[k]), k
@@ -108,6 +122,23 @@ TIMED_SIGN_BOUNDS = (SIGN_FRAC["bf16"], SIGN_DIST["bf16"])
 
 @pytest.mark.parametrize("dtype,size,latent,batch", TIMED)
 def test_timed_step_vs_oracle(dtype, size, latent, batch):
+    _timed_vs_oracle(dtype, size, latent, batch, STEPS)
+
+
+@pytest.mark.parametrize("dtype,size,latent,batch,steps", BATCH_EDGES)
+def test_batch_edge_step_vs_oracle(dtype, size, latent, batch, steps):
+    """The same check at the batches of common.BATCH_EDGES, whose paths (tile, fallback, fc kernel, rider count) no benchmark
+    record reaches; records the row's wall time with its margins, and the peak host memory of the whole test process so far
+    (ru_maxrss: an upper bound for the row's own, which depends on what ran before it in the process)."""
+    t0 = time.perf_counter()
+    m = _timed_vs_oracle(dtype, size, latent, batch, steps)
+    m["wall_s"] = round(time.perf_counter() - t0, 1)
+    m["process_peak_rss_gb"] = round(resource.getrusage(resource.RUSAGE_SELF).ru_maxrss / 2 ** 20, 2)
+    MARGINS[f"timed_step/{dtype}/s{size}_b{batch}"] = m
+    _dump_margins()
+
+
+def _timed_vs_oracle(dtype, size, latent, batch, steps):
     eng, dp, real = bench_setup(dtype, size, latent, batch)
     hp, real_c = dp.hp, real.cpu()
     assert eng._mode == 2 and dp.transport == "host"       # overlap on, no graph (pre_real is off under graph mode)
@@ -116,7 +147,7 @@ def test_timed_step_vs_oracle(dtype, size, latent, batch):
     ride = batch if dtype == "f32" else 0
     m = dict(rode=ride, riders=ride * (size // 4))
     m.update(dict(sign_flips=0, metric_frac=0.0, d_grad=0.0, g_grad=0.0, bn=0.0) if dtype == "f32" else dict(narrow=[]))
-    for s in range(STEPS):
+    for s in range(steps):
         where = f"{dtype} s{size} b{batch} step {s}"
         before = oracle_state_of(eng, size, latent)
         # ---- D half: DataParallelStep.step's calls, world 1 (the all-reduce of the host transport is a no-op) ----
@@ -164,7 +195,7 @@ def test_timed_step_vs_oracle(dtype, size, latent, batch):
     eng.close()
 
     eng, dp, real = bench_setup(dtype, size, latent, batch)
-    for _ in range(STEPS):
+    for _ in range(steps):
         dp.step(real, next_real=real)
     torch.cuda.synchronize()
     assert debug_scalar(eng, "ride_late") == 0.0
@@ -186,3 +217,28 @@ def test_timed_step_vs_oracle(dtype, size, latent, batch):
         m["worst_fraction_of_tolerance_fp32_bn_at_TOL_FP32"] = max(r["bn_vs_fp32"] / TOL_FP32[dtype]["bn"] for r in m["narrow"])
     MARGINS[f"timed_step/{dtype}/s{size}_b{batch}"] = m
     _dump_margins()
+    return m
+
+
+@pytest.mark.parametrize("dtype,size,latent,batch", list(COVERS))
+def test_added_workloads_reach_their_launches(dtype, size, latent, batch):
+    """Each workload added to TIMED / BATCH_EDGES for a launcher path makes, in one timed step, the launches common.COVERS
+    lists for it: the tile, form, epilogue and GEMM shape, read per launch from the library's profile.  Profiling is
+    process-wide and turns the riders off: this engine is its own, and the profiler is off again before the next test."""
+    eng, dp, real = bench_setup(dtype, size, latent, batch)
+    eng.prof_enable(True)
+    try:
+        dp.step(real, next_real=real)
+        torch.cuda.synchronize()
+        launches = eng.prof_launches()
+    finally:
+        eng.prof_enable(False)
+        eng.close()
+    seen = sorted({tuple(sorted(l.items())) for l in launches if l["M"] >= 0})
+    for want in COVERS[(dtype, size, latent, batch)]:
+        hit = [l for l in launches if all(l[k] == v for k, v in want.items())]
+        assert hit, (f"{dtype} s{size} b{batch} no longer makes the launch it exists for: {want}; "
+                     f"its GEMM launches were {[dict(t) for t in seen]}")
+    if batch <= 256:
+        # (the fallback belongs to the b1025 row alone: below it every statistics epilogue fits its carve)
+        assert not [l for l in launches if l["epi_req"] == "bn_bwd_stats" and l["epi"] != "bn_bwd_stats"]
