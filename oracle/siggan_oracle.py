@@ -17,6 +17,8 @@ Reference lines followed (all under /root/reference/src):
   * BCE / labels / D step / G step: vanilla_gan_model.py:107, :152-178, :180-252, :254-306
   * clipping + trainer variants of the steps: train_vanilla_gan_signatures.py:262-376
   * Adam hyper-parameters: vanilla_gan_model.py:110-120 (torch.optim.Adam defaults otherwise)
+  * the ablation harness: ablation_vanilla_gan_signatures.py:159-328 (ConfigurableGenerator), :311-328 (its forward),
+    :361-366 (the slope AblationGANTrainer builds it with), :397-467 (one train_epoch iteration)
 
 State is held in plain dicts keyed exactly like the reference's ``state_dict()``.
 """
@@ -189,11 +191,13 @@ _NOQ = _NoQuant()
 
 def g_forward(sd: Dict[str, Tensor], z: Tensor, training: bool, size: int,
               signs: Optional[Sequence[Tensor]] = None, record: Optional[list] = None,
-              q: Optional[Quant] = None) -> Tensor:
+              q: Optional[Quant] = None, slope: float = 0.0) -> Tensor:
     """Generator.forward (generator_vanilla_gan.py:189-209).  ``training`` selects the
     BatchNorm mode; in training mode running stats / num_batches_tracked in ``sd`` are
     updated in place exactly as nn.BatchNorm does (momentum 0.1, unbiased running var).
-    ``signs`` / ``record``: see _ActWithGivenSign (one entry per ReLU, NCHW bool)."""
+    ``signs`` / ``record``: see _ActWithGivenSign (one entry per activation, NCHW bool).
+    ``slope`` > 0: ConfigurableGenerator.forward (ablation_vanilla_gan_signatures.py:311-328), the same layers with
+    LeakyReLU(slope) for every ReLU."""
     chain = G_CHAIN[size]
     sg = (lambda i: None) if signs is None else (lambda i: signs[i])
     q = q or _NOQ
@@ -210,12 +214,12 @@ def g_forward(sd: Dict[str, Tensor], z: Tensor, training: bool, size: int,
                             training, BN_MOMENTUM, BN_EPS)
 
     x = qy(F.linear(z, sd["fc.0.weight"], sd["fc.0.bias"]))
-    x = q.g(q.a(_act(bn(x, "fc.1."), 0.0, sg(0), record)))
+    x = q.g(q.a(_act(bn(x, "fc.1."), slope, sg(0), record)))
     x = x.view(-1, chain[0], 4, 4)
     for i in range(n_blocks):
         p = f"upsample_blocks.{i}.block."
         x = qy(F.conv_transpose2d(x, q.w(sd[p + "0.weight"]), None, stride=2, padding=1))
-        x = _act(bn(x, p + "1."), 0.0, sg(i + 1), record)
+        x = _act(bn(x, p + "1."), slope, sg(i + 1), record)
         if i + 1 < n_blocks or not training:
             x = q.a(x)                  # (training: the last block's activation is re-derived from y by both of its readers, never stored)
         if i + 1 < n_blocks:            # the last block's activation gradient is consumed where it is formed, never stored
@@ -303,82 +307,6 @@ class AdamState:
 
 
 # --------------------------------------------------------------------------------------
-# the two training steps
-# --------------------------------------------------------------------------------------
-def _leafs(sd, names):
-    return {k: sd[k].detach().clone().requires_grad_(True) for k in names}
-
-
-def d_grads(g_sd, d_sd, real: Tensor, z: Tensor, masks_real, masks_fake, size: int,
-            label_smoothing: float = 0.9, dropout: float = 0.25, signs=None, record=None, q=None):
-    """Forward/backward half of the D step (vanilla_gan_model.py:204-233 ==
-    train_vanilla_gan_signatures.py:294-323): returns (metrics, grads, real_preds, fake_preds,
-    fake_images).  G runs in eval mode under no_grad; only D parameters receive gradients."""
-    names = param_names(d_state_specs(size, real.shape[1]))
-    leaf = _leafs(d_sd, names)
-    with torch.no_grad():
-        fake = g_forward(g_sd, z, training=False, size=size, q=q)
-    nb = len(D_CHAIN[size])
-    s_real, s_fake = (None, None) if signs is None else (signs[:nb], signs[nb:])
-    real_preds = d_forward(leaf, real, size, masks_real, dropout, signs=s_real, record=record, q=q)
-    loss_real = bce(real_preds, label_smoothing)
-    fake_preds = d_forward(leaf, fake, size, masks_fake, dropout, signs=s_fake, record=record, q=q)
-    loss_fake = bce(fake_preds, 0.0)
-    loss = loss_real + loss_fake
-    gl = torch.autograd.grad(loss, [leaf[k] for k in names])
-    grads = {k: g.detach() for k, g in zip(names, gl)}
-    loss, loss_real, loss_fake = loss.detach(), loss_real.detach(), loss_fake.detach()
-    real_preds, fake_preds = real_preds.detach(), fake_preds.detach()
-    metrics = {
-        "d_loss": float(loss), "d_loss_real": float(loss_real), "d_loss_fake": float(loss_fake),
-        "d_real_mean": float(real_preds.mean()), "d_fake_mean": float(fake_preds.mean()),
-        "d_real_acc": float((real_preds > 0.5).float().mean()),
-        "d_fake_acc": float((fake_preds < 0.5).float().mean()),
-    }
-    return metrics, grads, real_preds.detach(), fake_preds.detach(), fake
-
-
-def g_grads(g_sd, d_sd, z: Tensor, size: int, signs=None, record=None, q=None):
-    """Forward/backward half of the G step (vanilla_gan_model.py:274-297 ==
-    train_vanilla_gan_signatures.py:349-365): G in train mode (BN batch statistics, running
-    stats updated in ``g_sd``), D in eval mode (dropout off), BCE against 1.0 (no smoothing)."""
-    names = param_names(g_state_specs(z.shape[1], size))
-    leaf = dict(g_sd)
-    leaf.update(_leafs(g_sd, names))
-    ng = len(G_CHAIN[size])
-    s_g, s_d = (None, None) if signs is None else (signs[:ng], signs[ng:])
-    fake = g_forward(leaf, z, training=True, size=size, signs=s_g, record=record, q=q)
-    for k in g_sd:                      # running stats / counters were updated on the copies
-        if k not in names:
-            g_sd[k] = leaf[k]
-    fake_preds = d_forward(d_sd, fake, size, None, signs=s_d, record=record, q=q)
-    loss = bce(fake_preds, 1.0)
-    gl = torch.autograd.grad(loss, [leaf[k] for k in names])
-    grads = {k: g.detach() for k, g in zip(names, gl)}
-    loss, fake_preds = loss.detach(), fake_preds.detach()
-    metrics = {"g_loss": float(loss), "g_fake_mean": float(fake_preds.mean())}
-    return metrics, grads, fake_preds.detach(), fake.detach()
-
-
-def d_step(g_sd, d_sd, d_opt: AdamState, real, z, masks_real, masks_fake, size,
-           lr=2e-4, beta1=0.5, beta2=0.999, label_smoothing=0.9, clip: Optional[float] = None,
-           dropout: float = 0.25, signs=None, record=None, q=None):
-    metrics, grads, rp, fp, fake = d_grads(g_sd, d_sd, real, z, masks_real, masks_fake, size,
-                                           label_smoothing, dropout, signs, record, q)
-    metrics["d_grad_norm"] = clip_grad_norm(list(grads.values()), clip) if clip is not None else None
-    d_opt.apply(d_sd, grads, lr, beta1, beta2)
-    return metrics, grads
-
-
-def g_step(g_sd, d_sd, g_opt: AdamState, z, size, lr=2e-4, beta1=0.5, beta2=0.999,
-           clip: Optional[float] = None, signs=None, record=None, q=None):
-    metrics, grads, fp, fake = g_grads(g_sd, d_sd, z, size, signs, record, q)
-    metrics["g_grad_norm"] = clip_grad_norm(list(grads.values()), clip) if clip is not None else None
-    g_opt.apply(g_sd, grads, lr, beta1, beta2)
-    return metrics, grads
-
-
-# --------------------------------------------------------------------------------------
 # spectral normalisation (torch.nn.utils.spectral_norm on every D conv + the classifier,
 # discriminator_vanilla_gan.py:60-62,200-202)
 # --------------------------------------------------------------------------------------
@@ -408,86 +336,147 @@ def sn_weights(d_sd, sn: Dict[str, Tensor], size: int, training: bool) -> Dict[s
     return out
 
 
-def d_step_sn(g_sd, d_sd, sn, d_opt: AdamState, real, z, masks_real, masks_fake, size,
-              lr=2e-4, beta1=0.5, beta2=0.999, label_smoothing=0.9, dropout: float = 0.25, signs=None, record=None):
-    """train_discriminator_step with Discriminator(use_spectral_norm=True) (vanilla_gan_model.py:180-252): D.train(), so the real
-    and the fake forward each run a power iteration and see different effective weights; the gradient w.r.t. weight_orig goes
-    through both sigmas."""
-    names = param_names(d_state_specs(size, real.shape[1]))
-    leaf = _leafs(d_sd, names)
-    with torch.no_grad():
-        fake = g_forward(g_sd, z, training=False, size=size)
-    nb = len(D_CHAIN[size])
-    s_real, s_fake = (None, None) if signs is None else (signs[:nb], signs[nb:])       # D(real) blocks, then D(fake) blocks
-    real_preds = d_forward(sn_weights(leaf, sn, size, True), real, size, masks_real, dropout, signs=s_real, record=record)
-    fake_preds = d_forward(sn_weights(leaf, sn, size, True), fake, size, masks_fake, dropout, signs=s_fake, record=record)
-    loss_real, loss_fake = bce(real_preds, label_smoothing), bce(fake_preds, 0.0)
-    loss = loss_real + loss_fake
+# --------------------------------------------------------------------------------------
+# the training steps.  Keyword-only in every one of them: ``g_slope`` -- the Generator's activation slope (0: the ReLU
+# Generator; > 0: ConfigurableGenerator(activation='leaky_relu')); ``sn`` -- the weight_u / weight_v dict of a
+# Discriminator(use_spectral_norm=True), updated in place (None: plain weights)
+# --------------------------------------------------------------------------------------
+def _leafs(sd, names):
+    return {k: sd[k].detach().clone().requires_grad_(True) for k in names}
+
+
+def _grads(loss, leaf, names):
     gl = torch.autograd.grad(loss, [leaf[k] for k in names])
-    grads = {k: g.detach() for k, g in zip(names, gl)}
-    d_opt.apply(d_sd, grads, lr, beta1, beta2)
-    metrics = {"d_loss": float(loss.detach()), "d_loss_real": float(loss_real.detach()), "d_loss_fake": float(loss_fake.detach()),
-               "d_real_mean": float(real_preds.detach().mean()), "d_fake_mean": float(fake_preds.detach().mean())}
-    return metrics, grads
+    return {k: g.detach() for k, g in zip(names, gl)}
 
 
-def g_step_sn(g_sd, d_sd, sn, g_opt: AdamState, z, size, lr=2e-4, beta1=0.5, beta2=0.999, signs=None, record=None):
-    """train_generator_step against a spectral-norm Discriminator (vanilla_gan_model.py:254-306): D.eval() -- no power
-    iteration, sigma from the stored (u, v)."""
+def _d_weights(d_sd, sn, size: int, training: bool):
+    """The dict ONE Discriminator forward runs with: ``d_sd`` itself, or what the spectral-norm hook makes of it
+    (sn_weights).  Called once per forward and never shared between two: every train-mode forward runs a power iteration
+    of its own, so the real and the fake pass of a D step see different effective weights."""
+    return d_sd if sn is None else sn_weights(d_sd, sn, size, training)
+
+
+def _g_train_forward(g_sd, z, size, g_slope, signs, record, q):
+    """The Generator's train-mode forward through leaf copies of its parameters; the running stats / counters, which were
+    updated on the copies, are written back into ``g_sd``.  Returns (parameter names, leaf dict, image)."""
     names = param_names(g_state_specs(z.shape[1], size))
     leaf = dict(g_sd)
     leaf.update(_leafs(g_sd, names))
-    ng = len(G_CHAIN[size])
-    s_g, s_d = (None, None) if signs is None else (signs[:ng], signs[ng:])             # fc, G blocks, then D blocks
-    fake = g_forward(leaf, z, training=True, size=size, signs=s_g, record=record)
+    fake = g_forward(leaf, z, training=True, size=size, signs=signs, record=record, q=q, slope=g_slope)
     for k in g_sd:
         if k not in names:
             g_sd[k] = leaf[k]
-    fake_preds = d_forward(sn_weights(d_sd, sn, size, False), fake, size, None, signs=s_d, record=record)
+    return names, leaf, fake
+
+
+def _d_half(d_sd, real, fake, masks_real, masks_fake, size, label_smoothing, dropout, signs, records, q, sn):
+    """The Discriminator's train-mode forward on ``real`` and on ``fake`` (an image without a graph) through leaf copies of
+    its parameters, BCE against the smoothed label resp. 0, and the backward pass (vanilla_gan_model.py:204-233 ==
+    train_vanilla_gan_signatures.py:294-323 == ablation_vanilla_gan_signatures.py:414-430).  With ``sn`` the gradient
+    w.r.t. weight_orig goes through both passes' sigmas.  ``signs`` / ``records``: (real pass, fake pass).
+    Returns (five-key metrics, grads, real_preds, fake_preds), all detached."""
+    names = param_names(d_state_specs(size, real.shape[1]))
+    leaf = _leafs(d_sd, names)
+    real_preds = d_forward(_d_weights(leaf, sn, size, True), real, size, masks_real, dropout,
+                           signs=signs[0], record=records[0], q=q)
+    fake_preds = d_forward(_d_weights(leaf, sn, size, True), fake, size, masks_fake, dropout,
+                           signs=signs[1], record=records[1], q=q)
+    loss_real, loss_fake = bce(real_preds, label_smoothing), bce(fake_preds, 0.0)
+    loss = loss_real + loss_fake
+    grads = _grads(loss, leaf, names)
+    real_preds, fake_preds = real_preds.detach(), fake_preds.detach()
+    metrics = {"d_loss": float(loss.detach()), "d_loss_real": float(loss_real.detach()), "d_loss_fake": float(loss_fake.detach()),
+               "d_real_mean": float(real_preds.mean()), "d_fake_mean": float(fake_preds.mean())}
+    return metrics, grads, real_preds, fake_preds
+
+
+def d_grads(g_sd, d_sd, real: Tensor, z: Tensor, masks_real, masks_fake, size: int,
+            label_smoothing: float = 0.9, dropout: float = 0.25, signs=None, record=None, q=None, *,
+            g_slope: float = 0.0, sn=None):
+    """Forward/backward half of the D step (vanilla_gan_model.py:204-233 ==
+    train_vanilla_gan_signatures.py:294-323): returns (metrics, grads, real_preds, fake_preds,
+    fake_images).  G runs in eval mode under no_grad; only D parameters receive gradients.
+    ``sn``: train_discriminator_step with Discriminator(use_spectral_norm=True) (vanilla_gan_model.py:180-252): D.train(),
+    so the real and the fake forward each run a power iteration (see _d_weights).
+    ``signs`` / ``record``: D(real) blocks, then D(fake) blocks."""
+    with torch.no_grad():
+        fake = g_forward(g_sd, z, training=False, size=size, q=q, slope=g_slope)
+    nb = len(D_CHAIN[size])
+    s_real, s_fake = (None, None) if signs is None else (signs[:nb], signs[nb:])
+    metrics, grads, real_preds, fake_preds = _d_half(d_sd, real, fake, masks_real, masks_fake, size, label_smoothing, dropout,
+                                                     (s_real, s_fake), (record, record), q, sn)
+    metrics["d_real_acc"] = float((real_preds > 0.5).float().mean())
+    metrics["d_fake_acc"] = float((fake_preds < 0.5).float().mean())
+    return metrics, grads, real_preds, fake_preds, fake
+
+
+def g_grads(g_sd, d_sd, z: Tensor, size: int, signs=None, record=None, q=None, *, g_slope: float = 0.0, sn=None):
+    """Forward/backward half of the G step (vanilla_gan_model.py:274-297 ==
+    train_vanilla_gan_signatures.py:349-365): G in train mode (BN batch statistics, running
+    stats updated in ``g_sd``), D in eval mode (dropout off), BCE against 1.0 (no smoothing).
+    ``sn``: train_generator_step against a spectral-norm Discriminator (vanilla_gan_model.py:254-306): D.eval() -- no power
+    iteration, sigma from the stored (u, v).
+    ``signs`` / ``record``: fc, G blocks, then D blocks."""
+    ng = len(G_CHAIN[size])
+    s_g, s_d = (None, None) if signs is None else (signs[:ng], signs[ng:])
+    names, leaf, fake = _g_train_forward(g_sd, z, size, g_slope, s_g, record, q)
+    fake_preds = d_forward(_d_weights(d_sd, sn, size, False), fake, size, None, signs=s_d, record=record, q=q)
     loss = bce(fake_preds, 1.0)
-    gl = torch.autograd.grad(loss, [leaf[k] for k in names])
-    grads = {k: g.detach() for k, g in zip(names, gl)}
+    grads = _grads(loss, leaf, names)
+    fake_preds = fake_preds.detach()
+    metrics = {"g_loss": float(loss.detach()), "g_fake_mean": float(fake_preds.mean())}
+    return metrics, grads, fake_preds, fake.detach()
+
+
+def d_step(g_sd, d_sd, d_opt: AdamState, real, z, masks_real, masks_fake, size,
+           lr=2e-4, beta1=0.5, beta2=0.999, label_smoothing=0.9, clip: Optional[float] = None,
+           dropout: float = 0.25, signs=None, record=None, q=None, *, g_slope: float = 0.0, sn=None):
+    """d_grads, clipping (``d_grad_norm``: the pre-clip norm, None without ``clip``), Adam on ``d_sd``.  In front of a
+    LeakyReLU Generator (``g_slope``) the reference never trains this step: that pins the engine's arithmetic only."""
+    metrics, grads, rp, fp, fake = d_grads(g_sd, d_sd, real, z, masks_real, masks_fake, size,
+                                           label_smoothing, dropout, signs, record, q, g_slope=g_slope, sn=sn)
+    metrics["d_grad_norm"] = clip_grad_norm(list(grads.values()), clip) if clip is not None else None
+    d_opt.apply(d_sd, grads, lr, beta1, beta2)
+    return metrics, grads
+
+
+def g_step(g_sd, d_sd, g_opt: AdamState, z, size, lr=2e-4, beta1=0.5, beta2=0.999,
+           clip: Optional[float] = None, signs=None, record=None, q=None, *, g_slope: float = 0.0, sn=None):
+    """g_grads, clipping (``g_grad_norm`` as in d_step), Adam on ``g_sd``."""
+    metrics, grads, fp, fake = g_grads(g_sd, d_sd, z, size, signs, record, q, g_slope=g_slope, sn=sn)
+    metrics["g_grad_norm"] = clip_grad_norm(list(grads.values()), clip) if clip is not None else None
     g_opt.apply(g_sd, grads, lr, beta1, beta2)
-    return {"g_loss": float(loss.detach()), "g_fake_mean": float(fake_preds.detach().mean())}, grads
+    return metrics, grads
 
 
 def ablation_step(g_sd, d_sd, g_opt: AdamState, d_opt: AdamState, real, z, masks_real, masks_fake, masks_g, size,
                   lr_g=2e-4, lr_d=2e-4, beta1=0.5, beta2=0.999, label_smoothing=0.9, dropout: float = 0.25, q=None,
-                  signs=None, record=None):
+                  signs=None, record=None, *, g_slope: float = 0.0, sn=None, preds=None):
     """One iteration of AblationGANTrainer.train_epoch (ablation_vanilla_gan_signatures.py:397-467), for the standard
-    (ReLU) Generator: both networks in train mode for the whole iteration; ONE Generator forward (BatchNorm batch
+    (ReLU) Generator or, with ``g_slope``, the configurable one (:159-328; the harness builds it with slope 0.2, :361-366):
+    both networks in train mode for the whole iteration; ONE Generator forward (BatchNorm batch
     statistics, running stats updated) whose detached image feeds the D update (:414-430) and through which the G update
     back-propagates (:432-441); the G update runs the UPDATED Discriminator, still in train mode (a third set of dropout
-    masks), against the smoothed real label.  Returns (metrics, d_grads, g_grads).
+    masks and, with ``sn``, a third power iteration), against the smoothed real label.  Returns (metrics, d_grads, g_grads).
     ``signs`` / ``record`` (see _act): dicts keyed 'g' (fc + Generator blocks), 'd_real', 'd_fake', 'd_g' (the Discriminator
     pass of the G update), each a per-layer list -- the harness calls D(real) BEFORE the Generator, this restatement after it,
-    so the groups are named rather than positional."""
-    g_names = param_names(g_state_specs(z.shape[1], size))
-    d_names = param_names(d_state_specs(size, real.shape[1]))
-    g_leaf = dict(g_sd)
-    g_leaf.update(_leafs(g_sd, g_names))
+    so the groups are named rather than positional.
+    ``preds`` (a list, optional) receives the three Discriminator outputs: real, fake.detach(), fake (the G update's)."""
     sg = (lambda key: None) if signs is None else (lambda key: signs[key])
     rc = (lambda key: None) if record is None else (lambda key: record.setdefault(key, []))
-    fake = g_forward(g_leaf, z, training=True, size=size, q=q, signs=sg("g"), record=rc("g"))
-    for k in g_sd:
-        if k not in g_names:
-            g_sd[k] = g_leaf[k]
-    d_leaf = _leafs(d_sd, d_names)
-    real_preds = d_forward(d_leaf, real, size, masks_real, dropout, q=q, signs=sg("d_real"), record=rc("d_real"))
-    fake_preds = d_forward(d_leaf, fake.detach(), size, masks_fake, dropout, q=q, signs=sg("d_fake"), record=rc("d_fake"))
-    loss_real, loss_fake = bce(real_preds, label_smoothing), bce(fake_preds, 0.0)
-    d_loss = loss_real + loss_fake
-    gl = torch.autograd.grad(d_loss, [d_leaf[k] for k in d_names])
-    d_grads = {k: g.detach() for k, g in zip(d_names, gl)}
+    g_names, g_leaf, fake = _g_train_forward(g_sd, z, size, g_slope, sg("g"), rc("g"), q)
+    metrics, d_grads, real_preds, fake_preds = _d_half(d_sd, real, fake.detach(), masks_real, masks_fake, size, label_smoothing,
+                                                       dropout, (sg("d_real"), sg("d_fake")), (rc("d_real"), rc("d_fake")), q, sn)
     d_opt.apply(d_sd, d_grads, lr_d, beta1, beta2)
-    preds_g = d_forward(d_sd, fake, size, masks_g, dropout, q=q, signs=sg("d_g"), record=rc("d_g"))   # the updated D, dropout still active
+    preds_g = d_forward(_d_weights(d_sd, sn, size, True), fake, size, masks_g, dropout, q=q,
+                        signs=sg("d_g"), record=rc("d_g"))                # the updated D, dropout still active
     g_loss = bce(preds_g, label_smoothing)
-    gl = torch.autograd.grad(g_loss, [g_leaf[k] for k in g_names])
-    g_grads = {k: g.detach() for k, g in zip(g_names, gl)}
+    g_grads = _grads(g_loss, g_leaf, g_names)
     g_opt.apply(g_sd, g_grads, lr_g, beta1, beta2)
-    metrics = {"d_loss": float(d_loss.detach()), "d_loss_real": float(loss_real.detach()), "d_loss_fake": float(loss_fake.detach()),
-               "d_real_mean": float(real_preds.detach().mean()), "d_fake_mean": float(fake_preds.detach().mean()),
-               "g_loss": float(g_loss.detach()), "g_fake_mean": float(preds_g.detach().mean())}
+    if preds is not None:
+        preds += [p.detach().reshape(-1) for p in (real_preds, fake_preds, preds_g)]
+    metrics.update(g_loss=float(g_loss.detach()), g_fake_mean=float(preds_g.detach().mean()))
     return metrics, d_grads, g_grads
 
 

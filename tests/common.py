@@ -55,6 +55,10 @@ COVERS = {
                               dict(form=0, epi_req="bn_bwd_stats", epi="raw", M=1025 * 32 * 32, Ci=32, Co=64)],
 }
 SEED = dict(state_g=101, state_d=202, adam_g=303, adam_d=404, z=11, real=22)
+# the loss / mean-prediction metrics of a D and of a G step: what the parity tests compare by name
+DK = ("d_loss", "d_loss_real", "d_loss_fake", "d_real_mean", "d_fake_mean")
+GK = ("g_loss", "g_fake_mean")
+SLOPE = 0.2          # ConfigurableGenerator's default leaky_slope, the one AblationGANTrainer uses (ablation...py:361-366)
 
 
 def load_golden(size, batch, latent=None):
@@ -80,6 +84,16 @@ def oracle_states(size, latent, warm):
             opt.v = {k: torch.from_numpy(a).clone() for k, a in v.items()}
             opt.step = step
     return g_sd, d_sd, g_opt, d_opt
+
+
+def oracle_states_sn(size, latent, sn=True):
+    """Warm oracle_states plus the spectral-norm case's (u, v) dict (weight_orig stays under the plain names in d_sd), or
+    None where ``sn`` is false: (g_sd, d_sd, g_opt, d_opt, sn dict or None)."""
+    uv = None
+    if sn:
+        full = I.gen_sn_state(O.d_state_specs(size), SEED["state_d"])
+        uv = {k: torch.from_numpy(v).clone() for k, v in full.items() if k.endswith(("weight_u", "weight_v"))}
+    return (*oracle_states(size, latent, warm=True), uv)
 
 
 def masks_from(f, key, batch, size, passes):

@@ -126,6 +126,35 @@ def hip_signs_g(eng, size, batch):
     return out
 
 
+def hip_ablation_iteration(eng, real, z, masks, size, batch):
+    """One iteration of the 'ablation' step variant phase by phase (what Engine.ablation_step does), reading the sign decisions
+    where they still stand.  ``masks``: the three passes' dropout masks.  Returns (metrics, signs, keep, d_grads, g_grads,
+    probs): ``signs`` in the named groups oracle.ablation_step takes, ``keep`` the dropout masks of the same groups (for
+    count_sign_flips), the two gradient arenas as CPU copies, and the per-sample Discriminator outputs of the three passes,
+    (3, batch)."""
+    nb = len(masks) // 3
+    eng.d_compute_grads(cuda(real), cuda(z), masks, 0.9, mask_passes=3)
+    s_g, s_d = hip_signs_g(eng, size, batch), hip_signs_d(eng, size, batch, 2)
+    d_grads = {k: v.cpu().clone() for k, v in eng.views("d", "grads").items()}
+    probs = [eng.debug_tensor("probs", 0, (2 * batch,)).cpu().clone()]
+    met = eng.d_apply()
+    eng.g_compute_grads(batch, label_smoothing=0.9)
+    s_dg = hip_signs_d(eng, size, batch, 1)
+    probs.append(eng.debug_tensor("probs", 0, (batch,)).cpu().clone())
+    met.update(eng.g_apply())
+    g_grads = {k: v.cpu().clone() for k, v in eng.views("g", "grads").items()}
+    signs = {"g": s_g, "d_real": s_d[:nb], "d_fake": s_d[nb:], "d_g": s_dg}
+    keep = {"g": None, "d_real": masks[:nb], "d_fake": masks[nb:2 * nb], "d_g": masks[2 * nb:]}
+    return met, signs, keep, d_grads, g_grads, torch.cat(probs).reshape(3, batch)
+
+
+def grad_scales(o_grads, names):
+    """Per-tensor comparison scale of a gradient arena against an oracle's: the tensor's largest gradient, floored at 1e-3 of
+    the network's (1e-2 for the Linear bias in front of BatchNorm1d, whose true gradient is zero)."""
+    gscale = max(float(o_grads[k].abs().max()) for k in names)
+    return {k: max(float(o_grads[k].abs().max()), (1e-2 if k == "fc.0.bias" else 1e-3) * gscale) for k in names}
+
+
 def count_sign_flips(signs, recorded, keep=None):
     """Disagreements between the HIP sign decisions and the oracle's own; every one must be a
     pre-activation within rounding of zero (|x| <= 1e-5 of the layer's scale).  Their NUMBER is bounded too, in proportion to

@@ -1,6 +1,6 @@
-"""The ablation study's LeakyReLU Generator on the host: the test-side restatement (tests/leaky_ref.py) against the fixtures
-the reference's own AblationGANTrainer.train_epoch wrote (tests/golden/make_golden_ablation_leaky.py), and host checks of the
-drop-in module.  CPU only."""
+"""The ablation study's LeakyReLU Generator on the host: the oracle's restatement (oracle.siggan_oracle with g_slope /
+slope = common.SLOPE) against the fixtures the reference's own AblationGANTrainer.train_epoch wrote
+(tests/golden/make_golden_ablation_leaky.py), and host checks of the drop-in module.  CPU only."""
 import json
 import os
 
@@ -8,22 +8,14 @@ import numpy as np
 import pytest
 import torch
 
-import leaky_ref as L
-from common import GOLDEN, I, O, SEED, ablation_groups, assert_close, census_signs, d_chans, oracle_states, probe
+from common import (GOLDEN, SLOPE, I, O, SEED, ablation_groups, assert_close, census_signs, d_chans, oracle_states,
+                    oracle_states_sn, probe)
 from test_oracle_golden import _check_step
 
 import signature_gan_amd  # noqa: F401  (import shim for signature-gan_amd/)
 
 # (size, latent, batch, spectral norm): z = 50 (latent % 4 != 0) runs the Generator fc's generic kernels
 LEAKY_CASES = [(64, 200, 8, False), (64, 50, 8, True), (128, 128, 4, False)]
-
-
-def leaky_states(size, latent, sn):
-    """Oracle-side states of a fixture case: (g_sd, d_sd, g_opt, d_opt, sn dict or None)."""
-    if sn:
-        from test_oracle_golden import _sn_states
-        return _sn_states(size, latent)
-    return (*oracle_states(size, latent, warm=True), None)
 
 
 @pytest.fixture(autouse=True)
@@ -47,10 +39,11 @@ def test_restatement_reproduces_reference_iteration(size, latent, batch, sn):
     nb = len(masks) // 3
     z = torch.from_numpy(f[f"{tag}/z"])
     real = torch.from_numpy(I.gen_real(batch, size, SEED["real"]))
-    g_sd, d_sd, g_opt, d_opt, sn_uv = leaky_states(size, latent, sn)
+    g_sd, d_sd, g_opt, d_opt, sn_uv = oracle_states_sn(size, latent, sn)
     preds = []
-    met, d_grads, g_grads = L.ablation_step(g_sd, d_sd, g_opt, d_opt, real, z, masks[:nb], masks[nb:2 * nb], masks[2 * nb:],
-                                            size, sn=sn_uv, signs=ablation_groups(size, census_signs(f, tag)), preds=preds)
+    met, d_grads, g_grads = O.ablation_step(g_sd, d_sd, g_opt, d_opt, real, z, masks[:nb], masks[nb:2 * nb], masks[2 * nb:],
+                                            size, signs=ablation_groups(size, census_signs(f, tag)), g_slope=SLOPE, sn=sn_uv,
+                                            preds=preds)
     assert_close(torch.stack(preds).numpy(), f[f"{tag}/preds"], 1e-4, 1e-6, f"{tag} D predictions")
     if sn:
         for k, v in sn_uv.items():                     # three power iterations later
@@ -60,7 +53,7 @@ def test_restatement_reproduces_reference_iteration(size, latent, batch, sn):
     _check_step(f, f"{tag}/g", g_opt.names, {"g_loss": met["g_loss"]}, g_grads, g_sd, g_opt, bufs)
     # generate_samples after the iteration: eval mode on the updated weights and running statistics
     with torch.no_grad():
-        img = L.g_forward(g_sd, torch.from_numpy(f[f"{tag}/eval/z"]), False, size)
+        img = O.g_forward(g_sd, torch.from_numpy(f[f"{tag}/eval/z"]), False, size, slope=SLOPE)
     want = f[f"{tag}/eval/img"]
     assert_close(img.numpy(), want, 0, 1e-4 * float(np.abs(want).max()), f"{tag} eval image")
 
@@ -77,8 +70,8 @@ def test_restatement_reproduces_reference_epoch_means():
     for k in range(n):
         real = torch.from_numpy(I.gen_real(batch, size, SEED["real"] + k))
         ms = masks[k * per:(k + 1) * per]
-        met, _, _ = L.ablation_step(g_sd, d_sd, g_opt, d_opt, real, torch.from_numpy(f["epoch/z"][k]), ms[:nb], ms[nb:2 * nb],
-                                    ms[2 * nb:], size)
+        met, _, _ = O.ablation_step(g_sd, d_sd, g_opt, d_opt, real, torch.from_numpy(f["epoch/z"][k]), ms[:nb], ms[nb:2 * nb],
+                                    ms[2 * nb:], size, g_slope=SLOPE)
         sums += [met["g_loss"], met["d_loss"], met["d_real_mean"], met["d_fake_mean"]]
     # own sign decisions here (no census for iterations 2-3): a borderline flip moves a chained mean by far less than 1e-4
     assert_close(sums / n, f["epoch/means"], 1e-4, 1e-6, "epoch means")
@@ -86,14 +79,15 @@ def test_restatement_reproduces_reference_epoch_means():
 
 
 def test_slope_zero_is_the_relu_oracle():
-    """slope 0 in the restatement is the oracle's ReLU Generator, bit for bit (the restatement changes nothing else)."""
+    """The oracle's Generator with its default slope is the ReLU network -- slope=0.0 bit for bit -- and slope=SLOPE is another
+    one."""
     size, latent, batch = 64, 100, 4
     g_sd, *_ = oracle_states(size, latent, warm=False)
     z = torch.from_numpy(I.gen_z(batch, latent, SEED["z"]))
-    a = L.g_forward({k: v.clone() for k, v in g_sd.items()}, z, True, size, slope=0.0)
+    a = O.g_forward({k: v.clone() for k, v in g_sd.items()}, z, True, size, slope=0.0)
     b = O.g_forward({k: v.clone() for k, v in g_sd.items()}, z, True, size)
     assert torch.equal(a, b)
-    c = L.g_forward({k: v.clone() for k, v in g_sd.items()}, z, True, size)
+    c = O.g_forward({k: v.clone() for k, v in g_sd.items()}, z, True, size, slope=SLOPE)
     assert not torch.equal(a, c)
 
 

@@ -1,22 +1,22 @@
 """The ablation study's LeakyReLU Generator (siggan_config.g_leaky_slope, Engine(g_activation='leaky_relu'),
 signature_gan_amd.ablation_vanilla_gan_signatures) on the MI355X.
 
-Chain of the fp32 parity tests (test_engine_gpu.test_ablation_step_variant): the HIP path against the test-side restatement
-(tests/leaky_ref.py) given the HIP path's own activation-sign decisions (arithmetic, 1e-4 of scale), the restatement given
-the reference run's decisions (fixture census) against the fixture, and the HIP decisions that differ from the reference's
-counted against the census."""
+Chain of the fp32 parity tests (test_engine_gpu.test_ablation_step_variant): the HIP path against the oracle's restatement
+(oracle.siggan_oracle with g_slope / slope = common.SLOPE) given the HIP path's own activation-sign decisions (arithmetic,
+1e-4 of scale), the restatement given the reference run's decisions (fixture census) against the fixture, and the HIP
+decisions that differ from the reference's counted against the census."""
 import os
 
 import numpy as np
 import pytest
 import torch
 
-import leaky_ref as L
-from common import GOLDEN, I, O, SEED, ablation_groups, assert_close, census_signs, d_chans, flips_vs_census, oracle_states, probe
+from common import (GOLDEN, SLOPE, I, O, SEED, ablation_groups, assert_close, census_signs, d_chans, flips_vs_census, oracle_states,
+                    oracle_states_sn, probe)
 
 pytestmark = pytest.mark.gpu
 
-from test_ablation_leaky_cpu import LEAKY_CASES, leaky_states      # noqa: E402  (size, latent, batch, spectral norm)
+from test_ablation_leaky_cpu import LEAKY_CASES      # noqa: E402  (size, latent, batch, spectral norm)
 
 
 def _fixture():
@@ -27,7 +27,7 @@ def _engine(size, latent, batch, warm=True, dtype="f32", spectral_norm=False, se
     from hipcommon import load_engine_state
     from signature_gan_amd.engine import Engine
     eng = Engine(latent_dim=latent, image_size=size, max_batch=batch, device="cuda:0", seed=seed, dtype=dtype,
-                 spectral_norm=spectral_norm, g_activation="leaky_relu", g_leaky_slope=L.SLOPE)
+                 spectral_norm=spectral_norm, g_activation="leaky_relu", g_leaky_slope=SLOPE)
     return load_engine_state(eng, size, latent, warm)
 
 
@@ -49,7 +49,7 @@ def test_leaky_ablation_iteration_vs_restatement_and_reference(size, latent, bat
     """Each fixture case; (64, 50, 8) runs the Generator fc's generic kernels (latent % 4 != 0: k_fc_fwd, k_bn_relu,
     k_colreduce<FBnBwd> + k_bn_bwd_apply) against a spectral-norm Discriminator (a power iteration in each of the three
     train-mode D passes)."""
-    from hipcommon import count_sign_flips, cuda, hip_signs_d, hip_signs_g
+    from hipcommon import count_sign_flips, cuda, hip_ablation_iteration
     f = _fixture()
     tag = f"s{size}_z{latent}_b{batch}" + ("_sn" if sn else "")
     masks = [torch.from_numpy(m) for m in I.unpack_masks(f[f"{tag}/masks"], batch, d_chans(size) * 3)]
@@ -59,26 +59,14 @@ def test_leaky_ablation_iteration_vs_restatement_and_reference(size, latent, bat
     eng = _engine(size, latent, batch, spectral_norm=sn)
     if sn:
         for k, v in eng.sn_views().items():
-            v.copy_(leaky_states(size, latent, sn)[4][k])
+            v.copy_(oracle_states_sn(size, latent)[4][k])
     eng.set_step_variant("ablation")
-    eng.d_compute_grads(cuda(real), cuda(z), masks, 0.9, mask_passes=3)
-    s_g, s_d = hip_signs_g(eng, size, batch), hip_signs_d(eng, size, batch, 2)
-    d_hip = {k: v.cpu().clone() for k, v in eng.views("d", "grads").items()}
-    p_hip = [eng.debug_tensor("probs", 0, (2 * batch,)).cpu().clone()]
-    met = eng.d_apply()
-    eng.g_compute_grads(batch, label_smoothing=0.9)
-    s_dg = hip_signs_d(eng, size, batch, 1)
-    p_hip.append(eng.debug_tensor("probs", 0, (batch,)).cpu().clone())
-    p_hip = torch.cat(p_hip).reshape(3, batch)
-    met.update(eng.g_apply())
-    g_hip = {k: v.cpu().clone() for k, v in eng.views("g", "grads").items()}
-    hip = {"g": s_g, "d_real": s_d[:nb], "d_fake": s_d[nb:], "d_g": s_dg}
-    keep = {"g": None, "d_real": masks[:nb], "d_fake": masks[nb:2 * nb], "d_g": masks[2 * nb:]}
+    met, hip, keep, d_hip, g_hip, p_hip = hip_ablation_iteration(eng, real, z, masks, size, batch)
 
     def run(signs, rec, preds=None):
-        g_sd, d_sd, g_opt, d_opt, sn_uv = leaky_states(size, latent, sn)
-        o = L.ablation_step(g_sd, d_sd, g_opt, d_opt, real, z, masks[:nb], masks[nb:2 * nb], masks[2 * nb:], size, sn=sn_uv,
-                            signs=signs, record=rec, preds=preds)
+        g_sd, d_sd, g_opt, d_opt, sn_uv = oracle_states_sn(size, latent, sn)
+        o = O.ablation_step(g_sd, d_sd, g_opt, d_opt, real, z, masks[:nb], masks[nb:2 * nb], masks[2 * nb:], size,
+                            signs=signs, record=rec, g_slope=SLOPE, sn=sn_uv, preds=preds)
         return o, sn_uv
     rec, o_preds = {}, []
     (o_met, o_dg, o_gg), o_sn = run(hip, rec, o_preds)
@@ -122,7 +110,7 @@ def test_leaky_ablation_iteration_vs_restatement_and_reference(size, latent, bat
     ez = torch.from_numpy(f[f"{tag}/eval/z"])
     img = eng.g_forward(cuda(ez), training=False).cpu()
     with torch.no_grad():
-        oimg = L.g_forward(oracle_state_of(eng, size, latent)[0], ez, False, size)
+        oimg = O.g_forward(oracle_state_of(eng, size, latent)[0], ez, False, size, slope=SLOPE)
     assert float((img - oimg).abs().max()) <= 1e-4 * float(oimg.abs().max()), "eval image vs restatement"
     want = f[f"{tag}/eval/img"]
     assert float(np.abs(img.numpy() - want).max()) <= 5e-3 * float(np.abs(want).max()), "eval image vs reference"
@@ -162,7 +150,7 @@ def test_leaky_trainer_variant_vs_restatement():
     g_sd, d_sd, g_opt, d_opt = oracle_states(size, latent, warm=True)
     dm = eng.d_step(cuda(real), cuda(z1), masks)
     signs, rec = hip_signs_d(eng, size, batch, 2), []
-    odm, odg = L.d_step(g_sd, d_sd, d_opt, real, z1, masks[:nb], masks[nb:], size, signs=signs, record=rec)
+    odm, odg = O.d_step(g_sd, d_sd, d_opt, real, z1, masks[:nb], masks[nb:], size, signs=signs, record=rec, g_slope=SLOPE)
     count_sign_flips(signs, rec, keep=masks)
     dv = eng.views("d", "grads")
     assert _worst(dv, odg, _scale(odg, list(odg))) <= 1e-4
@@ -170,14 +158,14 @@ def test_leaky_trainer_variant_vs_restatement():
         assert_close(dm[k], odm[k], 2e-4, 2e-6, k)
     gm = eng.g_step(batch, cuda(z2))
     signs, rec = hip_signs_g(eng, size, batch) + hip_signs_d(eng, size, batch, 1), []
-    ogm, ogg = L.g_step(g_sd, d_sd, g_opt, z2, size, signs=signs, record=rec)
+    ogm, ogg = O.g_step(g_sd, d_sd, g_opt, z2, size, signs=signs, record=rec, g_slope=SLOPE)
     count_sign_flips(signs, rec)
     assert _worst(eng.views("g", "grads"), ogg, _scale(ogg, list(ogg))) <= 1e-4
     for k in ("g_loss", "g_fake_mean"):
         assert_close(gm[k], ogm[k], 2e-4, 2e-6, k)
     img = eng.g_forward(cuda(z1), training=False).cpu()
     with torch.no_grad():
-        oimg = L.g_forward(g_sd, z1, False, size)
+        oimg = O.g_forward(g_sd, z1, False, size, slope=SLOPE)
     assert float((img - oimg).abs().max()) <= 1e-4 * float(oimg.abs().max())
     eng.close()
 
@@ -198,15 +186,15 @@ def test_leaky_narrow_vs_fp32_restatement(dtype):
     g_sd, d_sd, g_opt, d_opt = oracle_states(size, latent, warm=True)
     img = eng.g_forward(cuda(z1), training=False).cpu()
     with torch.no_grad():
-        oimg = L.g_forward({k: v.clone() for k, v in g_sd.items()}, z1, False, size)
+        oimg = O.g_forward({k: v.clone() for k, v in g_sd.items()}, z1, False, size, slope=SLOPE)
     assert float((img - oimg).abs().max()) <= tol["image"]
     dm = eng.d_step(cuda(real), cuda(z1), masks)
-    odm, odg = L.d_step(g_sd, d_sd, d_opt, real, z1, masks[:nb], masks[nb:], size)
+    odm, odg = O.d_step(g_sd, d_sd, d_opt, real, z1, masks[:nb], masks[nb:], size, g_slope=SLOPE)
     gm = eng.g_step(batch, cuda(z2))
-    ogm, ogg = L.g_step(g_sd, d_sd, g_opt, z2, size)
-    for got, want in ((dm, odm), (gm, ogm)):
-        for k, v in want.items():
-            assert abs(got[k] - v) <= tol["metric"] * max(abs(v), 1e-3), (dtype, k, got[k], v)
+    ogm, ogg = O.g_step(g_sd, d_sd, g_opt, z2, size, g_slope=SLOPE)
+    for got, want, keys in ((dm, odm, ("d_loss", "d_real_mean", "d_fake_mean")), (gm, ogm, ("g_loss", "g_fake_mean"))):
+        for k in keys:
+            assert abs(got[k] - want[k]) <= tol["metric"] * max(abs(want[k]), 1e-3), (dtype, k, got[k], want[k])
     hip = torch.cat([t.reshape(-1).cpu() for t in eng.views("g", "grads").values()])
     ref = torch.cat([ogg[k].reshape(-1) for k in eng.views("g", "grads")])
     assert float((hip - ref).norm() / ref.norm()) <= tol["grad_all"], dtype
@@ -323,6 +311,6 @@ def test_leaky_eval_forward_at_batch_64_vs_restatement():
     eng.prof_enable(False)
     assert launched.get("k_gconv_up4", 0) >= 1, launched
     with torch.no_grad():
-        oimg = L.g_forward(oracle_state_of(eng, size, latent)[0], z, False, size)
+        oimg = O.g_forward(oracle_state_of(eng, size, latent)[0], z, False, size, slope=SLOPE)
     assert float((img - oimg).abs().max()) <= 1e-4 * float(oimg.abs().max())
     eng.close()

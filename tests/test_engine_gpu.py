@@ -6,8 +6,8 @@ import numpy as np
 import pytest
 import torch
 
-from common import (CASES, TIMED, I, O, SEED, assert_close, census_signs, d_chans, flips_vs_census, load_golden, masks_from, oracle_states,
-                    probe)
+from common import (CASES, DK, GK, TIMED, I, O, SEED, assert_close, census_signs, d_chans, flips_vs_census, load_golden, masks_from,
+                    oracle_states, oracle_states_sn, probe)
 
 pytestmark = pytest.mark.gpu
 RT = 2e-4
@@ -86,7 +86,7 @@ def test_forward_in_a_context_for_320_images():
     _forward_case(64, 100, 64, max_batch=BIG_CTX)
 
 
-from hipcommon import count_sign_flips, hip_signs_d, hip_signs_g  # noqa: E402  (sign decisions of the HIP path, shared with smoke())
+from hipcommon import count_sign_flips, grad_scales, hip_signs_d, hip_signs_g  # noqa: E402  (sign decisions of the HIP path, shared with smoke())
 
 LR = 2e-4
 
@@ -292,16 +292,14 @@ from hipcommon import oracle_state_of as _oracle_state_of  # noqa: E402  (shared
 
 
 def _grads_close(eng, which, o_grads, what, tol=1e-4):
-    """HIP gradient arena vs an oracle's, each tensor relative to its own scale (floored at 1e-3 of the network's; the Linear
-    bias in front of BatchNorm1d, whose true gradient is zero, at 1e-2)."""
+    """HIP gradient arena vs an oracle's, each tensor relative to its own scale (hipcommon.grad_scales)."""
     gv = eng.views(which, "grads")
-    gscale = max(float(o_grads[k].abs().max()) for k in gv)
+    scale = grad_scales(o_grads, list(gv))
     worst = 0.0
     for k, t in gv.items():
-        sc = max(float(o_grads[k].abs().max()), (1e-2 if k == "fc.0.bias" else 1e-3) * gscale)
-        err = float((t.cpu() - o_grads[k]).abs().max()) / sc
+        err = float((t.cpu() - o_grads[k]).abs().max()) / scale[k]
         worst = max(worst, err)
-        assert err <= tol, f"{what} grad {k}: {err:.3e} of scale {sc:.3e}"
+        assert err <= tol, f"{what} grad {k}: {err:.3e} of scale {scale[k]:.3e}"
     return worst
 
 
@@ -662,7 +660,7 @@ def test_ablation_step_variant(size, latent, batch):
     decisions that differ from the replay's counted against the census."""
     import os
     from common import GOLDEN, ablation_groups
-    from hipcommon import cuda, make_engine
+    from hipcommon import cuda, hip_ablation_iteration, make_engine
     f = np.load(os.path.join(GOLDEN, "golden_ablation_step.npz"))
     tag = f"s{size}_b{batch}"
     masks = [torch.from_numpy(m) for m in I.unpack_masks(f[f"{tag}/masks"], batch, d_chans(size) * 3)]
@@ -671,16 +669,7 @@ def test_ablation_step_variant(size, latent, batch):
     real = torch.from_numpy(I.gen_real(batch, size, SEED["real"]))
     eng = make_engine(size, latent, batch, warm=True)
     eng.set_step_variant("ablation")
-    # the iteration phase by phase (what Engine.ablation_step does), reading the sign decisions where they still stand
-    eng.d_compute_grads(cuda(real), cuda(z), masks, 0.9, mask_passes=3)
-    s_g, s_d = hip_signs_g(eng, size, batch), hip_signs_d(eng, size, batch, 2)
-    d_grads_hip = {k: v.cpu().clone() for k, v in eng.views("d", "grads").items()}
-    met = eng.d_apply()
-    eng.g_compute_grads(batch, label_smoothing=0.9)
-    s_dg = hip_signs_d(eng, size, batch, 1)
-    met.update(eng.g_apply())
-    hip = {"g": s_g, "d_real": s_d[:nb], "d_fake": s_d[nb:], "d_g": s_dg}
-    keep = {"g": None, "d_real": masks[:nb], "d_fake": masks[nb:2 * nb], "d_g": masks[2 * nb:]}
+    met, hip, keep, d_grads_hip, _, _ = hip_ablation_iteration(eng, real, z, masks, size, batch)
 
     def run(signs, rec):
         g_sd, d_sd, g_opt, d_opt = oracle_states(size, latent, warm=True)
@@ -745,7 +734,6 @@ def test_spectral_norm_training(size, latent, batch):
     from common import GOLDEN
     from hipcommon import cuda, load_engine_state
     from signature_gan_amd.engine import Engine
-    from test_oracle_golden import _sn_states
     f = np.load(os.path.join(GOLDEN, "golden_sn_steps.npz"))
     tag = f"s{size}_b{batch}"
     masks = [torch.from_numpy(m) for m in I.unpack_masks(f[f"{tag}/masks"], batch, d_chans(size) * 2)]
@@ -755,7 +743,7 @@ def test_spectral_norm_training(size, latent, batch):
     real = torch.from_numpy(I.gen_real(batch, size, SEED["real"]))
     eng = load_engine_state(Engine(latent_dim=latent, image_size=size, max_batch=batch, device="cuda:0", spectral_norm=True),
                             size, latent, warm=True)
-    _, _, _, _, sn0 = _sn_states(size, latent)
+    _, _, _, _, sn0 = oracle_states_sn(size, latent)
     for k, v in eng.sn_views().items():
         v.copy_(sn0[k])
     ren = lambda k: k + "_orig" if k.endswith(".weight") else k
@@ -772,20 +760,20 @@ def test_spectral_norm_training(size, latent, batch):
     g_hip = {k: v.cpu().clone() for k, v in eng.views("g", "grads").items()}
 
     def run(signs_d, signs_g, rec_d=None, rec_g=None):
-        g_sd, d_sd, g_opt, d_opt, sn = _sn_states(size, latent)
-        dm, dg = O.d_step_sn(g_sd, d_sd, sn, d_opt, real, z, masks[:nb], masks[nb:], size, signs=signs_d, record=rec_d)
+        g_sd, d_sd, g_opt, d_opt, sn = oracle_states_sn(size, latent)
+        dm, dg = O.d_step(g_sd, d_sd, d_opt, real, z, masks[:nb], masks[nb:], size, signs=signs_d, record=rec_d, sn=sn)
         sn_after_d = {k: v.clone() for k, v in sn.items()}
-        gm, gg = O.g_step_sn(g_sd, d_sd, sn, g_opt, z2, size, signs=signs_g, record=rec_g)
+        gm, gg = O.g_step(g_sd, d_sd, g_opt, z2, size, signs=signs_g, record=rec_g, sn=sn)
         return dm, dg, gm, gg, sn_after_d, g_sd, d_sd, g_opt, d_opt
     rec_d, rec_g = [], []
     dm, dg, gm, gg, sn_b, g_sd, d_sd, g_opt, d_opt = run(s_d, s_g, rec_d, rec_g)
     count_sign_flips(s_d, rec_d, keep=masks)
     count_sign_flips(s_g, rec_g)
-    for k, v in dm.items():
-        assert_close(met[k], v, 2e-4, 2e-6, f"SN d metric {k} vs oracle")
+    for k in DK:
+        assert_close(met[k], dm[k], 2e-4, 2e-6, f"SN d metric {k} vs oracle")
         assert_close(met[k], f[f"{tag}/d/metric/{k}"], 2e-4, 2e-6, f"SN d metric {k} vs golden")
-    for k, v in gm.items():
-        assert_close(gmet[k], v, 2e-4, 2e-6, f"SN g metric {k} vs oracle")
+    for k in GK:
+        assert_close(gmet[k], gm[k], 2e-4, 2e-6, f"SN g metric {k} vs oracle")
         assert_close(gmet[k], f[f"{tag}/g/metric/{k}"], 2e-4, 2e-6, f"SN g metric {k} vs golden")
     sc_d, _ = _scales(dg, list(dg), np.array([float(dg[k].norm()) for k in dg]))
     sc_g, _ = _scales(gg, list(gg), f[f"{tag}/g/grad_norm"])
@@ -799,7 +787,7 @@ def test_spectral_norm_training(size, latent, batch):
         _scale_close(probe(v, k), f[f"{tag}/d/buf/{k}"], f"SN buffer {k} vs golden", 1e-4)
     for k, v in eng.sn_views().items():                        # D.eval(): untouched by the G step
         _scale_close(probe(v.cpu(), k), f[f"{tag}/g/dbuf/{k}"], f"SN buffer {k} after the G step", 1e-5)
-    i_g, i_d, i_gopt, i_dopt, _ = _sn_states(size, latent)
+    i_g, i_d, i_gopt, i_dopt, _ = oracle_states_sn(size, latent)
     for which, og, oopt, sc, isd, iopt in (("d", dg, d_opt, sc_d, i_d, i_dopt), ("g", gg, g_opt, sc_g, i_g, i_gopt)):
         mv = eng.views(which, "exp_avg")
         for k in mv:
@@ -833,12 +821,11 @@ def test_spectral_norm_pipelined_step_equals_split_steps(size, latent, batch):
     (the running statistics MUST move), u / v and every metric."""
     from hipcommon import cuda, load_engine_state
     from signature_gan_amd.engine import Engine
-    from test_oracle_golden import _sn_states
     masks = [torch.from_numpy(m) for m in I.gen_masks(batch, d_chans(size) * 2, 9)]
     z = cuda(torch.from_numpy(I.gen_z(batch, latent, SEED["z"])))
     z2 = cuda(torch.from_numpy(I.gen_z(batch, latent, SEED["z"] + 1)))
     real = cuda(torch.from_numpy(I.gen_real(batch, size, SEED["real"])))
-    _, _, _, _, sn = _sn_states(size, latent)
+    _, _, _, _, sn = oracle_states_sn(size, latent)
 
     def engine():
         e = load_engine_state(Engine(latent_dim=latent, image_size=size, max_batch=batch, device="cuda:0", spectral_norm=True),

@@ -7,8 +7,8 @@ import numpy as np
 import pytest
 import torch
 
-from common import (CASES, I, O, SEED, ablation_groups, assert_close, census_signs, flips_vs_census, load_golden, masks_from,
-                    oracle_states, probe)
+from common import (CASES, DK, GK, I, O, SEED, ablation_groups, assert_close, census_signs, flips_vs_census, load_golden, masks_from,
+                    oracle_states, oracle_states_sn, probe)
 
 RT, AT = 1e-4, 1e-6
 SEQ3_RT, SEQ3_AT = 1e-4, 1e-5     # chained metrics of the three-step sequence (losses / mean predictions, O(0.1 .. 1))
@@ -193,21 +193,13 @@ def test_ablation_step(size, latent, batch):
     _check_step(f, f"{tag}/g", g_opt.names, {k: v for k, v in met.items() if k.startswith("g_")}, g_grads, g_sd, g_opt, bufs)
 
 
-def _sn_states(size, latent):
-    """Oracle-side states of the spectral-norm case: weight_orig under the plain names, (u, v) in their own dict."""
-    g_sd, d_sd, g_opt, d_opt = oracle_states(size, latent, warm=True)
-    full = I.gen_sn_state(O.d_state_specs(size), SEED["state_d"])
-    sn = {k: torch.from_numpy(v).clone() for k, v in full.items() if k.endswith(("weight_u", "weight_v"))}
-    return g_sd, d_sd, g_opt, d_opt, sn
-
-
-def _sn_check(f, tag, names_plain, met, grads, sd, opt, sn=None):
+def _sn_check(f, tag, names_plain, keys, met, grads, sd, opt, sn=None):
     """_check_step against a fixture whose parameter names carry weight_orig (and whose parameter ORDER is the SN module's:
     bias before weight_orig) -- compared by name.  The oracle is given the reference run's near-zero sign decisions (census),
     the chained G step included, so both steps are held to 1e-4 of the network's gradient scale."""
     ren = lambda k: k.replace(".weight", ".weight_orig") if (k.endswith(".weight") and f"{tag}/grad/{k}_orig" in f) else k
-    for k, v in met.items():
-        assert_close(v, f[f"{tag}/metric/{k}"], 1e-4, 1e-6, f"{tag} metric {k}")
+    for k in keys:
+        assert_close(met[k], f[f"{tag}/metric/{k}"], 1e-4, 1e-6, f"{tag} metric {k}")
     gscale = max(float(g.abs().max()) for g in grads.values())
     ga = 1e-4 * gscale + 1e-9
     for k in names_plain:
@@ -222,7 +214,7 @@ def _sn_check(f, tag, names_plain, met, grads, sd, opt, sn=None):
 
 @pytest.mark.parametrize("size,latent,batch", [(64, 100, 8), (128, 128, 4)])
 def test_spectral_norm_steps(size, latent, batch):
-    """oracle.d_step_sn / g_step_sn (power iteration per training forward, gradient through sigma) against
+    """oracle.d_step / g_step with ``sn`` (power iteration per training forward, gradient through sigma) against
     VanillaGAN(use_spectral_norm=True) run on the reference itself (make_golden.py::make_spectral_norm_steps)."""
     import os
     from common import GOLDEN, d_chans
@@ -233,10 +225,10 @@ def test_spectral_norm_steps(size, latent, batch):
     z = torch.from_numpy(I.gen_z(batch, latent, SEED["z"]))
     z2 = torch.from_numpy(I.gen_z(batch, latent, SEED["z"] + 1))
     real = torch.from_numpy(I.gen_real(batch, size, SEED["real"]))
-    g_sd, d_sd, g_opt, d_opt, sn = _sn_states(size, latent)
-    met, grads = O.d_step_sn(g_sd, d_sd, sn, d_opt, real, z, masks[:nb], masks[nb:], size, signs=census_signs(f, f"{tag}/d"))
-    _sn_check(f, f"{tag}/d", d_opt.names, met, grads, d_sd, d_opt, sn)
-    met, grads = O.g_step_sn(g_sd, d_sd, sn, g_opt, z2, size, signs=census_signs(f, f"{tag}/g"))   # on the state the D step left (as the fixture)
-    _sn_check(f, f"{tag}/g", g_opt.names, met, grads, g_sd, g_opt)
+    g_sd, d_sd, g_opt, d_opt, sn = oracle_states_sn(size, latent)
+    met, grads = O.d_step(g_sd, d_sd, d_opt, real, z, masks[:nb], masks[nb:], size, signs=census_signs(f, f"{tag}/d"), sn=sn)
+    _sn_check(f, f"{tag}/d", d_opt.names, DK + ("d_real_acc", "d_fake_acc"), met, grads, d_sd, d_opt, sn)
+    met, grads = O.g_step(g_sd, d_sd, g_opt, z2, size, signs=census_signs(f, f"{tag}/g"), sn=sn)   # on the state the D step left (as the fixture)
+    _sn_check(f, f"{tag}/g", g_opt.names, GK, met, grads, g_sd, g_opt)
     for k, t in sn.items():                                        # D.eval(): the buffers did not move
         assert_close(probe(t, k), f[f"{tag}/g/dbuf/{k}"], 1e-6, 1e-7, f"G step leaves {k} alone")

@@ -20,17 +20,15 @@ import time
 import pytest
 import torch
 
-from common import BATCH_EDGES, COVERS, TIMED, O, assert_close
-from hipcommon import (assert_same_state, bench_setup, count_sign_flips, debug_scalar, full_state, hip_d_masks, hip_signs_d,
-                       hip_signs_g, oracle_state_of)
+from common import BATCH_EDGES, COVERS, DK, GK, TIMED, O, assert_close
+from hipcommon import (assert_same_state, bench_setup, count_sign_flips, debug_scalar, full_state, grad_scales, hip_d_masks,
+                       hip_signs_d, hip_signs_g, oracle_state_of)
 from signature_gan_amd import _lib
 from test_engine_gpu import MARGINS, _Half, _close_halves, _dump_margins, _scale_close
 from test_narrow_gpu import SIGN_DIST, SIGN_FRAC, TOL_FP32, TOL_Q, assert_narrow_row, compare_d_half, compare_g_half
 
 pytestmark = pytest.mark.gpu
 STEPS = 4
-DK = ("d_loss", "d_loss_real", "d_loss_fake", "d_real_mean", "d_fake_mean")
-GK = ("g_loss", "g_fake_mean")
 # per workload: the worst deviation of each kind over the four steps, and the largest fraction of its tolerance any check
 # used -- recorded with the other parity margins (test_engine_gpu.MARGINS, under "timed_step/...") for the measurement record
 
@@ -38,13 +36,6 @@ GK = ("g_loss", "g_fake_mean")
 def _metrics(eng, keys):
     m = eng.metrics.cpu()
     return {k: float(m[_lib.METRIC_INDEX[k]]) for k in keys}
-
-
-def _scale_of(o_grads, names):
-    """per-tensor comparison scale of _grads_close: the tensor's largest gradient, floored at 1e-3 of the network's (1e-2 for
-    the Linear bias in front of BatchNorm1d, whose true gradient is zero)"""
-    gscale = max(float(o_grads[k].abs().max()) for k in names)
-    return {k: max(float(o_grads[k].abs().max()), (1e-2 if k == "fc.0.bias" else 1e-3) * gscale) for k in names}
 
 
 def _worst_tensor(got, want, names, scale):
@@ -68,7 +59,7 @@ def _fp32_d_half(eng, size, real, z, masks, signs, state, m):
         assert_close(met[k], om[k], 2e-4, 2e-6, f"D metric {k} vs oracle(HIP signs) from the engine's state")
     m["metric_frac"] = max(m["metric_frac"], _metric_frac(met, om, DK))
     names = list(eng.views("d", "grads"))
-    mine, scale = _Half.of_engine(eng, "d", met), _scale_of(og, names)
+    mine, scale = _Half.of_engine(eng, "d", met), grad_scales(og, names)
     worst = _close_halves(mine, _Half.of_oracle(om, og, d_sd, d_opt), names, scale, init_d, init_opt, 1e-4,
                           "D half vs oracle(HIP signs)")
     if worst >= m["d_grad"]:
@@ -86,7 +77,7 @@ def _fp32_g_half(eng, size, z, signs, state, m):
         assert_close(met[k], om[k], 2e-4, 2e-6, f"G metric {k} vs oracle(HIP signs) from the engine's state")
     m["metric_frac"] = max(m["metric_frac"], _metric_frac(met, om, GK))
     names = list(eng.views("g", "grads"))
-    mine, scale = _Half.of_engine(eng, "g", met), _scale_of(og, names)
+    mine, scale = _Half.of_engine(eng, "g", met), grad_scales(og, names)
     worst = _close_halves(mine, _Half.of_oracle(om, og, g_sd, g_opt), names, scale, init_g, init_opt, 1e-4,
                           "G half vs oracle(HIP signs)")
     if worst >= m["g_grad"]:
