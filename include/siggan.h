@@ -48,7 +48,8 @@ extern "C" {
 #endif
 
 #define SIGGAN_ABI_VERSION 4   /* 2: siggan_stage_real, siggan_augment_batch; 3: siggan_config.dtype, siggan_rng_state, siggan_comm_*;
-                                * 4: siggan_config.g_leaky_slope (appended); siggan_prof_launch (a test hook, added) */
+                                * 4: siggan_config.g_leaky_slope (appended); siggan_prof_launch (a test hook, added);
+                                *    siggan_g_generate_u8, siggan_image_stats (added: no existing call or struct changes) */
 
 enum {
     SIGGAN_OK = 0,
@@ -188,6 +189,20 @@ int siggan_set_step_variant(siggan_ctx *ctx, int32_t variant);
 int siggan_g_forward(siggan_ctx *ctx, const float *z_dev, int32_t batch, int32_t training,
                      float *images_dev, void *stream);
 
+/* per-image stroke counters (int32 each): what the reference's calculate_stroke_density / calculate_foreground_ratio
+ * (utils/metrics.py:118-174) count, for a pixel value t and a threshold thr, all in fp32:
+ *   NEG         #{t < 0}                     -- summed over a batch it tells which branch the reference takes (images.min() < 0)
+ *   INK_SIGNED  #{(t + 1.0f) * 0.5f < thr}   -- the branch for images in [-1, 1]
+ *   INK_UNIT    #{t < thr}                   -- the branch for images in [0, 1]
+ * A NaN pixel is not part of the contract. */
+enum { SIGGAN_IS_NEG = 0, SIGGAN_IS_INK_SIGNED = 1, SIGGAN_IS_INK_UNIT = 2, SIGGAN_IS_COUNT = 3 };
+/* Generator eval forward ending in what the callers of generation consume.  u8_dev (B,S,S) required (4-byte aligned): the
+ * bytes of utils/inference.py:129, (t + 1) * 127.5 in fp32, clamped to [0, 255] and truncated;
+ * images_dev (B,1,S,S) fp32 optional: bit-identical to siggan_g_forward(training = 0);
+ * stats_dev (B, SIGGAN_IS_COUNT) int32 optional, zeroed by the call (threshold must then be finite). */
+int siggan_g_generate_u8(siggan_ctx *ctx, const float *z_dev, int32_t batch, uint8_t *u8_dev,
+                         float *images_dev, int32_t *stats_dev, float threshold, void *stream);
+
 /* x_dev (B,1,S,S) -> probs_dev (B) probabilities.  features_dev (B,512*4*4, reference
  * flatten order c,h,w) optional.  training!=0 enables Dropout2d: masks_dev, if given, holds the
  * keep masks (1 keep / 0 drop) of all blocks concatenated [(B,C_1),(B,C_2),...]; NULL draws
@@ -300,6 +315,10 @@ int siggan_augment_batch(int32_t device, const uint8_t *cache_dev, int64_t n_ima
                          const int32_t *params_dev, const int16_t *tables_dev, const float *lut_dev,
                          float *out_dev, int32_t batch, int32_t size, int32_t augment, int32_t fill,
                          void *stream);
+/* the same counters for any fp32 image tensor x_dev (batch, pixels) on `device`, pixels any positive count; stats_dev
+ * (batch, SIGGAN_IS_COUNT) int32 is zeroed by the call.  Needs no context. */
+int siggan_image_stats(int32_t device, const float *x_dev, int32_t batch, int64_t pixels,
+                       float threshold, int32_t *stats_dev, void *stream);
 /* what the roofline peaks are derived from (bench.py): compute units x shader clock (kHz) of the device, and its HBM size */
 int siggan_device_info(int32_t device, int32_t *compute_units, int32_t *clock_khz, int64_t *hbm_bytes);
 /* measurement hook (bench.py roofline leg): while enabled, every MFMA implicit-GEMM launch is

@@ -20,6 +20,8 @@ EPILOGUES = ("raw", "bias_lrelu_drop", "affine_relu", "lrelu_bwd", "bn_bwd_stats
 METRIC_INDEX = {"d_loss": 0, "d_loss_real": 1, "d_loss_fake": 2, "d_real_mean": 3, "d_fake_mean": 4,
                 "d_real_acc": 5, "d_fake_acc": 6, "d_grad_norm": 7, "g_loss": 8, "g_fake_mean": 9,
                 "g_grad_norm": 10, "d_skipped": 11, "g_skipped": 12}
+# columns of the per-image stroke counters (SIGGAN_IS_*): #{t < 0}, #{(t + 1) / 2 < thr}, #{t < thr}
+IS_NEG, IS_INK_SIGNED, IS_INK_UNIT, IS_COUNT = 0, 1, 2, 3
 
 
 class Config(C.Structure):
@@ -75,6 +77,7 @@ _SIGNATURES = {
     "siggan_set_mode": (C.c_int, [_P, _I32]),
     "siggan_set_step_variant": (C.c_int, [_P, _I32]),
     "siggan_g_forward": (C.c_int, [_P, _P, _I32, _I32, _P, _P]),
+    "siggan_g_generate_u8": (C.c_int, [_P, _P, _I32, _P, _P, _P, C.c_float, _P]),
     "siggan_d_forward": (C.c_int, [_P, _P, _I32, _I32, _P, _P, _P, _P]),
     "siggan_d_step": (C.c_int, [_P, _P, _I32, _P, _P, C.POINTER(Hyper), _P, _P, _P]),
     "siggan_g_step": (C.c_int, [_P, _I32, _P, C.POINTER(Hyper), _P, _P, _P]),
@@ -89,6 +92,7 @@ _SIGNATURES = {
     "siggan_op_adam": (C.c_int, [_P, _P, _P, _P, _P, _I64, _I32, C.POINTER(Hyper), _P]),
     "siggan_op_randn": (C.c_int, [_P, _P, _I64, _P]),
     "siggan_augment_batch": (C.c_int, [_I32, _P, _I64, _P, _P, _P, _P, _P, _I32, _I32, _I32, _I32, _P]),
+    "siggan_image_stats": (C.c_int, [_I32, _P, _I32, _I64, C.c_float, _P, _P]),
     "siggan_comm_unique_id": (C.c_int, [_P]),
     "siggan_comm_init": (C.c_int, [_P, _I32, _I32, _P]),
     "siggan_comm_destroy": (C.c_int, [_P]),

@@ -95,8 +95,11 @@ void launch_bn_bwd(int dt, void* da, const void* y, int64_t R, int C, float* bn,
 // final 3x3 conv (C->1) + tanh, and its backward pieces.  act: [B][S][S][C] NHWC, img [B][S][S].
 // bn != nullptr (training): `act` is the last block's PRE-BatchNorm tensor y and bn its [scale | shift] table -- the
 // activation g_act(fma(y, scale, shift), gslope) is formed on load and never stored
+// u8 != nullptr (eval only, bn == nullptr): the pass ends in k_final_fwd_u8 -- u8 [B][S][S] bytes by the reference's
+// quantisation rule, stats [B][SIGGAN_IS_COUNT] int32 stroke counters against thr (optional, zeroed here), img optional
 void launch_final_fwd(int dt, const void* act, const float* Wt, const float* b, float* img, int B, int S, int C, float gslope,
-                      hipStream_t s, const float* bn = nullptr, hipEvent_t done = nullptr);
+                      hipStream_t s, const float* bn = nullptr, hipEvent_t done = nullptr, uint8_t* u8 = nullptr,
+                      int32_t* stats = nullptr, float thr = 0.f);
 // backward of the last Generator block from dpre.  (1) launch_final_bwd_reduce: ONE read of y gives the BatchNorm-backward sums
 // (d(act) of the final conv recomputed from dpre, never stored; activation mask re-derived from y) into `partial` AND the partial
 // rows of the final conv's weight / bias gradient (activation re-derived from y) into `partial_w`;  (2) launch_final_bn_bwd_apply:
@@ -229,5 +232,9 @@ bool launch_adam_pack(const ApTable& t, float* p, float* g, float* m, float* v, 
 // input pipeline: out[b] = lut[ resample(cache[index[b]]) ], (B,1,S,S) fp32 from an (N,S,S) uint8 cache (see k_augment)
 void launch_augment(const uint8_t* cache, int64_t n_images, const int32_t* index, const int32_t* prm, const int16_t* tabs,
                     const float* lut, float* out, int B, int S, int augment, int fill, hipStream_t s);
+
+// stats [B][SIGGAN_IS_COUNT] int32 (zeroed here): per-image stroke counters of x [B][P] fp32 against thr (see k_image_stats)
+int image_stats_chunks(int64_t P);
+void launch_image_stats(const float* x, int B, int64_t P, float thr, int32_t* stats, hipStream_t s);
 
 }  // namespace siggan

@@ -4,6 +4,7 @@
 // segments) and per-channel reductions are two-stage (per-chunk partials, then a finalize
 // kernel that adds the partials in chunk order), so results are bitwise reproducible.
 #include "ops.h"
+#include "../../include/siggan.h"
 #include "rng.h"
 
 namespace siggan {
@@ -658,10 +659,91 @@ __global__ __launch_bounds__(256) void k_final_fwd(const T* __restrict__ act, co
         if (c4 == 0) img[((size_t)t.n * S + t.y0 + r) * S + t.x] = tanhf(acc + bias);
     }
 }
+// The eval forward that ends in what the callers of generation consume (siggan_g_generate_u8).  A sibling of
+// k_final_fwd<T, false, false>, whose loads and arithmetic up to the tanh value tv it repeats statement by statement (kept
+// apart so that the training step's kernel stays the code it was); from tv:
+//   u8 (B,S,S): (tv + 1) * 127.5 as two separately rounded fp32 operations, clamped to [0, 255], truncated -- the rule of
+//     utils/inference.py:129 (tensor_to_uint8).  A lane keeps its pixel's four rows in one dword; the four pixels of a row
+//     segment (lanes 8 apart) exchange them with three lane shuffles, and pixel j of the segment stores row j's four bytes
+//     as ONE dword: 8 dword stores per wave, not 32 byte stores.
+//   stats (B,3) int32, optional (zeroed by the launcher): #{tv < 0}, #{(tv + 1) * 0.5 < thr}, #{tv < thr} per image.  All
+//     eight lanes of a pixel vote alike, so a row's count is popcount(ballot) / 8; the four waves meet in LDS and three
+//     threads issue one integer atomic add each per block (32 / 128 blocks per image; integer sums do not depend on order).
+//   img (B,1,S,S) fp32, optional: tv itself, as k_final_fwd stores it.
+template <class T>
+__global__ __launch_bounds__(256) void k_final_fwd_u8(const T* __restrict__ act, const float* __restrict__ Wt,
+                                                      const float* __restrict__ b, float* __restrict__ img,
+                                                      uint8_t* __restrict__ u8, int32_t* __restrict__ stats, float thr, int S) {
+    constexpr int RY = 4, C = 32;
+    __shared__ int sh[4][SIGGAN_IS_COUNT];
+    const int c4 = threadIdx.x & 7;
+    const StripId t = strip_of<RY>(blockIdx.x, S, threadIdx.x >> 3);
+    f4v w[9];
+#pragma unroll
+    for (int k = 0; k < 9; ++k) w[k] = ldg4(Wt + k * 32 + c4 * 4);
+    const float bias = b[0];
+    const T* base = act + (size_t)t.n * S * S * C + c4 * 4;
+    f4v v[RY + 2][3];
+#pragma unroll
+    for (int r = 0; r < RY + 2; ++r) {
+        const int yy = t.y0 + r - 1, yc = clampi(yy, S - 1);
+#pragma unroll
+        for (int d = 0; d < 3; ++d) {
+            const int xx = t.x + d - 1, xc = clampi(xx, S - 1);
+            const f4v q = ld4<T>(base + ((size_t)yc * S + xc) * C);
+            v[r][d] = (yy == yc && xx == xc) ? q : f4v{0.f, 0.f, 0.f, 0.f};
+        }
+    }
+    uint32_t rows = 0;                                  // byte r: this pixel in row y0 + r
+    int n_neg = 0, n_sig = 0, n_uni = 0;                // wave-uniform
+#pragma unroll
+    for (int r = 0; r < RY; ++r) {
+        float acc = 0.f;
+#pragma unroll
+        for (int kh = 0; kh < 3; ++kh)
+#pragma unroll
+            for (int kw = 0; kw < 3; ++kw) {
+                const f4v a = v[r + kh][kw], ww = w[kh * 3 + kw];
+                acc = fmaf(a.x, ww.x, acc); acc = fmaf(a.y, ww.y, acc); acc = fmaf(a.z, ww.z, acc); acc = fmaf(a.w, ww.w, acc);
+            }
+        acc += __shfl_xor(acc, 4, 8); acc += __shfl_xor(acc, 2, 8); acc += __shfl_xor(acc, 1, 8);
+        const float tv = tanhf(acc + bias);             // the butterfly leaves the same sum (fp32 addition commutes) in all eight lanes of the pixel
+        if (img && c4 == 0) img[((size_t)t.n * S + t.y0 + r) * S + t.x] = tv;
+        const float u = tv + 1.0f;
+        const float q = fminf(fmaxf(u * 127.5f, 0.f), 255.f);
+        rows |= (uint32_t)(int)q << (8 * r);
+        if (stats) {                                    // (uniform)
+            n_neg += __popcll(__ballot(tv < 0.f));
+            n_sig += __popcll(__ballot(u * 0.5f < thr));
+            n_uni += __popcll(__ballot(tv < thr));
+        }
+    }
+    const int j = (threadIdx.x >> 3) & 3, sft = 8 * j;  // pixel j of its 4-pixel row segment
+    uint32_t out = ((rows >> sft) & 255u) << sft;       // row j: own byte at position j, pixel j ^ k's at position j ^ k
+#pragma unroll
+    for (int k = 1; k < 4; ++k) out |= ((__shfl_xor(rows, 8 * k) >> sft) & 255u) << (8 * (j ^ k));
+    if (c4 == 0) *reinterpret_cast<uint32_t*>(u8 + ((size_t)t.n * S + t.y0 + j) * S + (t.x & ~3)) = out;
+    if (stats) {
+        if ((threadIdx.x & 63) == 0) {
+            int* cnt = sh[threadIdx.x >> 6];
+            cnt[SIGGAN_IS_NEG] = n_neg >> 3; cnt[SIGGAN_IS_INK_SIGNED] = n_sig >> 3; cnt[SIGGAN_IS_INK_UNIT] = n_uni >> 3;
+        }
+        __syncthreads();
+        if (threadIdx.x < SIGGAN_IS_COUNT) {
+            const int k = threadIdx.x, sum = sh[0][k] + sh[1][k] + sh[2][k] + sh[3][k];
+            if (sum) atomicAdd(stats + (size_t)t.n * SIGGAN_IS_COUNT + k, sum);
+        }
+    }
+}
 void launch_final_fwd(int dt, const void* act, const float* Wt, const float* b, float* img, int B, int S, int C, float gslope,
-                      hipStream_t s, const float* bn, hipEvent_t done) {
+                      hipStream_t s, const float* bn, hipEvent_t done, uint8_t* u8, int32_t* stats, float thr) {
     (void)C;                                            // host checks C == 32, S % 32 == 0
     const dim3 grid(B * (S / 4) * (S / 32));
+    if (u8) {                                           // eval only (the caller passes no bn table): bytes, optional counters, optional img
+        if (stats) (void)hipMemsetAsync(stats, 0, (size_t)B * SIGGAN_IS_COUNT * sizeof(int32_t), s);
+        SIGGAN_DT_SWITCH(dt, T, SIGGAN_LAUNCH_EV(done, (k_final_fwd_u8<T>), grid, dim3(256), 0, s, (const T*)act, Wt, b, img, u8, stats, thr, S));
+        return;
+    }
     SIGGAN_DT_SWITCH(dt, T, {
         if (bn && gslope != 0.f) SIGGAN_LAUNCH_EV(done, (k_final_fwd<T, true, true>), grid, dim3(256), 0, s, (const T*)act, Wt, b, img, S, bn, gslope);
         else if (bn) SIGGAN_LAUNCH_EV(done, (k_final_fwd<T, true, false>), grid, dim3(256), 0, s, (const T*)act, Wt, b, img, S, bn, gslope);
@@ -1415,6 +1497,56 @@ void launch_augment(const uint8_t* cache, int64_t n_images, const int32_t* index
                     const float* lut, float* out, int B, int S, int augment, int fill, hipStream_t s) {
     hipLaunchKernelGGL(k_augment, dim3(cdiv((int64_t)S * S, 256), B), dim3(256), 0, s, cache, index, prm, tabs, lut, out, S,
                        augment, fill, n_images);
+}
+
+// =========================================================================================
+// per-image stroke counters of any fp32 image tensor (siggan_image_stats): the three counts k_final_fwd_u8 takes
+// =========================================================================================
+// x[B][P], P any positive count: block (chunk, image) strides over the image's 16-byte-aligned middle with float4 loads;
+// the up-to-three scalars in front of it and behind it go to chunk 0.  Counts meet per wave (shuffles), per block (LDS) and
+// then in one integer atomic add per block and counter.
+__device__ __forceinline__ void stats_vote(float v, float thr, int& n_neg, int& n_sig, int& n_uni) {
+    n_neg += v < 0.f; n_sig += (v + 1.0f) * 0.5f < thr; n_uni += v < thr;
+}
+__global__ __launch_bounds__(256) void k_image_stats(const float* __restrict__ x, int64_t P, float thr, int32_t* __restrict__ stats,
+                                                     int chunks) {
+    __shared__ int sh[4][SIGGAN_IS_COUNT];
+    const int64_t img = blockIdx.x / chunks;
+    const int chunk = blockIdx.x % chunks;
+    const float* row = x + (size_t)img * P;
+    int64_t head = (int64_t)((16 - (reinterpret_cast<uintptr_t>(row) & 15)) & 15) >> 2;   // scalars up to the first aligned float4
+    if (head > P) head = P;
+    const int64_t n4 = (P - head) >> 2, tail0 = head + 4 * n4;
+    int c[SIGGAN_IS_COUNT] = {0, 0, 0};
+    for (int64_t i = (int64_t)chunk * 256 + threadIdx.x; i < n4; i += (int64_t)chunks * 256) {
+        const f4v q = ldg4(row + head + 4 * i);
+        stats_vote(q.x, thr, c[0], c[1], c[2]); stats_vote(q.y, thr, c[0], c[1], c[2]);
+        stats_vote(q.z, thr, c[0], c[1], c[2]); stats_vote(q.w, thr, c[0], c[1], c[2]);
+    }
+    if (chunk == 0) {
+        if ((int64_t)threadIdx.x < head) stats_vote(row[threadIdx.x], thr, c[0], c[1], c[2]);
+        if (tail0 + threadIdx.x < P) stats_vote(row[tail0 + threadIdx.x], thr, c[0], c[1], c[2]);
+    }
+#pragma unroll
+    for (int k = 0; k < SIGGAN_IS_COUNT; ++k) {
+#pragma unroll
+        for (int o = 32; o > 0; o >>= 1) c[k] += __shfl_xor(c[k], o);
+        if ((threadIdx.x & 63) == 0) sh[threadIdx.x >> 6][k] = c[k];
+    }
+    __syncthreads();
+    if (threadIdx.x < SIGGAN_IS_COUNT) {
+        const int k = threadIdx.x, sum = sh[0][k] + sh[1][k] + sh[2][k] + sh[3][k];
+        if (sum) atomicAdd(stats + (size_t)img * SIGGAN_IS_COUNT + k, sum);
+    }
+}
+int image_stats_chunks(int64_t P) {                      // blocks per image: eight float4 per thread, at most 64 blocks
+    const int64_t c = cdiv(P, 256 * 4 * 8);
+    return (int)(c < 1 ? 1 : (c > 64 ? 64 : c));
+}
+void launch_image_stats(const float* x, int B, int64_t P, float thr, int32_t* stats, hipStream_t s) {
+    (void)hipMemsetAsync(stats, 0, (size_t)B * SIGGAN_IS_COUNT * sizeof(int32_t), s);
+    const int chunks = image_stats_chunks(P);
+    hipLaunchKernelGGL(k_image_stats, dim3((unsigned)((int64_t)B * chunks)), dim3(256), 0, s, x, P, thr, stats, chunks);
 }
 
 // =========================================================================================

@@ -755,7 +755,8 @@ static GConvArgs gconv_args(siggan_ctx* c) {
 // z == nullptr: the latent batch is drawn inside the fc kernel from RNG stream rng_sid and left in z_out.
 static void g_forward_pass(siggan_ctx* c, const float* z, int B, bool training, float* img, hipStream_t s,
                            float* partial = nullptr, float* slab_k = nullptr, uint32_t rng_sid = 0, float* z_out = nullptr,
-                           hipEvent_t done = nullptr) {     // done: completion event of the pass' last launch
+                           hipEvent_t done = nullptr,       // done: completion event of the pass' last launch
+                           uint8_t* u8 = nullptr, int32_t* stats = nullptr, float thr = 0.f) {   // eval only: see launch_final_fwd
     if (!partial) partial = c->partial;
     char* const* const A = training ? c->g_a : c->g_ae;     // (fp32: the same buffers)
     const float gs = c->cfg.g_leaky_slope;                   // the Generator's activation: 0 = ReLU, else LeakyReLU(gs)
@@ -799,7 +800,7 @@ static void g_forward_pass(siggan_ctx* c, const float* z, int B, bool training, 
     if (training)
         launch_final_fwd(c->dt, c->g_y[c->Lg], c->wfin_t, GP(c, gi_fin_b(c)), img, B, c->S, c->gC[c->Lg], gs, s, c->g_bn[c->Lg], done);
     else
-        launch_final_fwd(c->dt, A[c->Lg], c->wfin_t, GP(c, gi_fin_b(c)), img, B, c->S, c->gC[c->Lg], gs, s, nullptr, done);
+        launch_final_fwd(c->dt, A[c->Lg], c->wfin_t, GP(c, gi_fin_b(c)), img, B, c->S, c->gC[c->Lg], gs, s, nullptr, done, u8, stats, thr);
     c->ga_last_B = training ? B : 0;
 }
 
@@ -1375,6 +1376,23 @@ extern "C" int siggan_g_forward(siggan_ctx* c, const float* z_dev, int32_t batch
     return lane_check(c);
 }
 
+extern "C" int siggan_g_generate_u8(siggan_ctx* c, const float* z_dev, int32_t batch, uint8_t* u8_dev, float* images_dev,
+                                    int32_t* stats_dev, float threshold, void* stream) {
+    ENTER(c);
+    int rc = check_call(c, batch);
+    if (rc) return rc;
+    if (!z_dev || !u8_dev) return fail(SIGGAN_E_INVALID, "null tensor");
+    if (reinterpret_cast<uintptr_t>(u8_dev) & 3) return fail(SIGGAN_E_INVALID, "u8_dev must be 4-byte aligned");
+    if (stats_dev && !isfinite(threshold)) return fail(SIGGAN_E_INVALID, "threshold must be finite");
+    hipStream_t s = (hipStream_t)stream;
+    if ((rc = settle(c, s))) return rc;
+    repack(c, s, s, c->g_dirty, !c->sn && c->d_dirty);
+    c->g_dirty = false; if (!c->sn) c->d_dirty = false;
+    g_forward_pass(c, z_dev, batch, false, images_dev, s, nullptr, nullptr, 0, nullptr, nullptr, u8_dev, stats_dev, threshold);
+    LAUNCHCHK();
+    return lane_check(c);
+}
+
 extern "C" int siggan_d_forward(siggan_ctx* c, const float* x_dev, int32_t batch, int32_t training, const float* masks_dev,
                                 float* probs_dev, float* features_dev, void* stream) {
     ENTER(c);
@@ -1807,6 +1825,19 @@ extern "C" int siggan_augment_batch(int32_t device, const uint8_t* cache_dev, in
     if (fill < 0 || fill > 255) return fail(SIGGAN_E_INVALID, "fill must be a byte value");
     DevGuard dg_(device); HIPCHK(dg_.err);
     launch_augment(cache_dev, n_images, index_dev, params_dev, tables_dev, lut_dev, out_dev, batch, size, augment != 0, fill, (hipStream_t)stream);
+    LAUNCHCHK();
+    return SIGGAN_OK;
+}
+
+extern "C" int siggan_image_stats(int32_t device, const float* x_dev, int32_t batch, int64_t pixels, float threshold,
+                                  int32_t* stats_dev, void* stream) {
+    if (!x_dev || !stats_dev) return fail(SIGGAN_E_INVALID, "null tensor");
+    if (batch < 1 || pixels < 1) return fail(SIGGAN_E_INVALID, "bad batch / pixel count");
+    if (!isfinite(threshold)) return fail(SIGGAN_E_INVALID, "threshold must be finite");
+    if (reinterpret_cast<uintptr_t>(x_dev) & 3) return fail(SIGGAN_E_INVALID, "x_dev must be 4-byte aligned");
+    if ((int64_t)batch * image_stats_chunks(pixels) > INT32_MAX) return fail(SIGGAN_E_INVALID, "batch too large for one launch");
+    DevGuard dg_(device); HIPCHK(dg_.err);
+    launch_image_stats(x_dev, batch, pixels, threshold, stats_dev, (hipStream_t)stream);
     LAUNCHCHK();
     return SIGGAN_OK;
 }

@@ -281,6 +281,42 @@ class Engine:
         _lib.check(self.lib.siggan_g_forward(self._h, _ptr(z), b, int(training), _ptr(out), self._stream()))
         return out
 
+    def g_generate_u8(self, z, threshold=None, want_f32=False):
+        """Eval-mode Generator forward ending in bytes (siggan_g_generate_u8): uint8 (B, S, S) by the reference's rule
+        ((x + 1) * 127.5, clip, truncate -- utils/inference.tensor_to_uint8), written by the final-conv kernel itself.
+        ``threshold``: also return the int32 (B, 3) per-image stroke counters (_lib.IS_NEG / IS_INK_SIGNED / IS_INK_UNIT)
+        against it.  ``want_f32``: also return the fp32 (B, 1, S, S) images, bit-identical to g_forward(z).
+        Returns u8, or the tuple (u8[, stats][, images])."""
+        b = 1
+        if z is not None:                                 # (a null z goes to the library, which refuses it: ValueError)
+            z = _f32(z, self.device, "z")
+            if z.dim() != 2 or z.shape[1] != self.latent_dim:
+                raise ValueError(f"z must be (B, {self.latent_dim}), got {tuple(z.shape)}")
+            b = z.shape[0]
+        self._check_batch(b)
+        s = self.image_size
+        u8 = torch.empty(b, s, s, dtype=torch.uint8, device=self.device)
+        stats = torch.empty(b, _lib.IS_COUNT, dtype=torch.int32, device=self.device) if threshold is not None else None
+        img = torch.empty(b, 1, s, s, dtype=torch.float32, device=self.device) if want_f32 else None
+        _lib.check(self.lib.siggan_g_generate_u8(self._h, _ptr(z), b, _ptr(u8), _ptr(img), _ptr(stats),
+                                                 float(threshold) if threshold is not None else 0.0, self._stream()))
+        out = (u8,) + ((stats,) if stats is not None else ()) + ((img,) if img is not None else ())
+        return out[0] if len(out) == 1 else out
+
+    @staticmethod
+    def image_stats(x, threshold):
+        """int32 (B, 3) per-image stroke counters of a contiguous fp32 (B, ...) device tensor against ``threshold``
+        (siggan_image_stats; columns as g_generate_u8's).  Needs no context."""
+        if x.device.type != "cuda":
+            raise RuntimeError("image_stats runs on a ROCm device ('cuda:N'); there is no CPU path")
+        if x.dtype != torch.float32 or not x.is_contiguous() or x.dim() < 1:
+            raise ValueError("image_stats needs a contiguous float32 (B, ...) tensor")
+        b = x.shape[0]
+        stats = torch.empty(b, _lib.IS_COUNT, dtype=torch.int32, device=x.device)
+        _lib.check(_lib.load().siggan_image_stats(x.device.index, _ptr(x), b, x.numel() // b if b else 0, float(threshold),
+                                                  _ptr(stats), C.c_void_p(torch.cuda.current_stream(x.device).cuda_stream)))
+        return stats
+
     def _masks(self, masks, b, passes):
         if masks is None:
             return None

@@ -1,0 +1,333 @@
+"""Drop-in for the reference's ``evaluate_vanilla_gan_signatures.py`` CLI on the MI355X HIP engine: checkpoint in ->
+generated samples -> sample grids, stroke / foreground statistics (against a folder of real images when one is given)
+and a JSON report.  Flags, function names, stdout lines, report keys and exit codes follow
+evaluate_vanilla_gan_signatures.py:44-612.
+
+What differs is where the work happens.  Generation goes through ``Engine.g_generate_u8`` with the stroke counters: the
+Generator's last kernel counts the pixels itself, so evaluating N samples brings 12 bytes per image to the host, plus the
+fp32 images of the samples the grids show -- not 4 * S * S bytes for every sample.  Real images are decoded and resized by
+the loader's helper, normalised on the device and counted by ``siggan_image_stats``.  FID / LPIPS are reported as not
+computed (utils/metrics.py of this package)."""
+import argparse
+import json
+import sys
+from datetime import datetime
+from pathlib import Path
+from typing import Any, Dict, List, Optional, Tuple
+
+import numpy as np
+import torch
+
+from .data_loader_signatures import FILL, SignatureDataset, normalize_lut
+from .generator_vanilla_gan import Generator
+from .train_vanilla_gan_signatures import save_sample_grid
+from .utils.inference import load_generator_and_config
+from .utils.metrics import (INCEPTION_AVAILABLE, LPIPS_AVAILABLE, calculate_fid, calculate_foreground_ratio,
+                            calculate_lpips_diversity, calculate_stroke_density, foreground_ratio_from_counts,
+                            stroke_density_from_counts)
+
+THRESHOLD = 0.5          # the threshold compute_metrics passes to both statistics (evaluate_vanilla_gan_signatures.py:306,318)
+
+
+class GeneratedSamples:
+    """What generate_samples hands on: the per-image stroke counters of all N samples (``counts``, int (N, 3) against
+    ``threshold``) and the fp32 images of the first ``len(images)`` of them (CPU, (K, 1, S, S) in [-1, 1])."""
+
+    def __init__(self, n: int, image_shape: Tuple[int, int, int], counts: np.ndarray, images: torch.Tensor, threshold: float):
+        self.n, self.image_shape, self.counts, self.images, self.threshold = n, tuple(image_shape), counts, images, threshold
+
+    def __len__(self) -> int:
+        return self.n
+
+    @property
+    def shape(self) -> Tuple[int, ...]:
+        return (self.n,) + self.image_shape
+
+
+def load_generator_from_checkpoint(checkpoint_path: Path, device: torch.device) -> Tuple[Generator, Dict[str, Any]]:
+    """(Generator in eval mode, the checkpoint's config dict).  Safe loader only (utils.inference)."""
+    checkpoint_path = Path(checkpoint_path)
+    if not checkpoint_path.exists():
+        raise FileNotFoundError(f"Checkpoint not found: {checkpoint_path}")
+    print(f"Loading checkpoint from: {checkpoint_path}")
+    generator, latent_dim, config = load_generator_and_config(str(checkpoint_path), device)
+    print("Generator loaded successfully:")
+    print(f"  - Latent dim: {latent_dim}")
+    print(f"  - Image size: {generator.output_size}x{generator.output_size}")
+    print(f"  - Epoch trained: {config.get('current_epoch', 'N/A')}")
+    return generator, config
+
+
+@torch.no_grad()
+def generate_samples(generator: Generator, n_samples: int, latent_dim: int, device: torch.device, batch_size: int = 64,
+                     keep_images: Optional[int] = None, threshold: float = THRESHOLD) -> GeneratedSamples:
+    """N samples, z = torch.randn per batch as the reference draws it (so a seed means the same).  ``keep_images``: how
+    many leading samples to bring back as fp32 images (None: all, what the reference returns)."""
+    generator.eval()
+    eng = generator._require_engine()
+    keep = n_samples if keep_images is None else max(0, min(int(keep_images), n_samples))
+    n_batches = (n_samples + batch_size - 1) // batch_size
+    counts, images = [], []
+    print(f"Generating {n_samples} samples...")
+    for i in range(n_batches):
+        b = min(batch_size, n_samples - i * batch_size)
+        z = torch.randn(b, latent_dim, device=device)
+        want = min(b, keep - i * batch_size)
+        if want > 0:
+            _, st, img = eng.g_generate_u8(z, threshold=threshold, want_f32=True)
+            images.append(img[:want].cpu())
+        else:
+            _, st = eng.g_generate_u8(z, threshold=threshold)
+        counts.append(st)
+        if (i + 1) % 10 == 0 or i == n_batches - 1:
+            print(f"  Generated {min((i + 1) * batch_size, n_samples)}/{n_samples} samples")
+    s = generator.output_size
+    kept = torch.cat(images, dim=0) if images else torch.empty(0, 1, s, s)
+    all_counts = torch.cat(counts, dim=0).cpu().numpy() if counts else np.zeros((0, 3), np.int32)
+    return GeneratedSamples(n_samples, (1, s, s), all_counts, kept, threshold)
+
+
+def load_real_images(real_dir: Path, n_images: int, image_size: int, device: torch.device) -> torch.Tensor:
+    """Up to ``n_images`` files of ``real_dir`` as (N, 1, S, S) fp32 in [-1, 1] ON THE DEVICE: decoded and resized by the
+    loader's helper (PIL -> 'L' -> bilinear), normalised by its byte table in the input-pipeline kernel."""
+    from . import _lib
+    real_dir = Path(real_dir)
+    if not real_dir.exists():
+        raise FileNotFoundError(f"Real images directory not found: {real_dir}")
+    ds = SignatureDataset(real_dir)
+    if len(ds) == 0:
+        raise ValueError(f"No images found in {real_dir}")
+    picks = list(range(len(ds)))
+    if len(picks) > n_images:
+        picks = [int(i) for i in np.random.choice(len(picks), n_images, replace=False)]
+    print(f"Loading {len(picks)} real images from {real_dir}")
+    decoded = []
+    for i in picks:
+        arr = ds.decode(i, image_size)
+        if arr is None:
+            print(f"  Warning: Failed to load {ds.get_image_path(i)}: unreadable image")
+        else:
+            decoded.append(arr)
+    if not decoded:
+        raise ValueError("No images could be loaded successfully")
+    dev = torch.device(device)
+    if dev.type != "cuda":
+        raise RuntimeError("real images are normalised and counted on a ROCm device ('cuda:N'); there is no CPU path")
+    if dev.index is None:
+        dev = torch.device("cuda", torch.cuda.current_device())
+    n = len(decoded)
+    cache = torch.from_numpy(np.stack(decoded)).to(dev)
+    index = torch.arange(n, dtype=torch.int32, device=dev)
+    lut = normalize_lut((-1.0, 1.0)).to(dev)
+    out = torch.empty(n, 1, image_size, image_size, dtype=torch.float32, device=dev)
+    _lib.check(_lib.load().siggan_augment_batch(dev.index, cache.data_ptr(), n, index.data_ptr(), None, None, lut.data_ptr(),
+                                                out.data_ptr(), n, image_size, 0, FILL,
+                                                torch.cuda.current_stream(dev).cuda_stream))
+    return out
+
+
+def create_sample_grids(samples, output_dir: Path, n_grids: int = 3, grid_size: int = 64) -> List[Path]:
+    """Up to ``n_grids`` PNG grids of ``grid_size`` samples each (the trainer's grid writer); ``samples``: an (N, C, H, W)
+    tensor or a GeneratedSamples (its kept images)."""
+    images = samples.images if isinstance(samples, GeneratedSamples) else samples
+    output_dir = Path(output_dir)
+    output_dir.mkdir(parents=True, exist_ok=True)
+    stamp = datetime.now().strftime("%Y%m%d_%H%M%S")
+    saved: List[Path] = []
+    for i in range(n_grids):
+        lo = i * grid_size
+        if lo >= len(images):
+            break
+        chunk = images[lo:min(lo + grid_size, len(images))]
+        path = output_dir / f"sample_grid_{stamp}_{i + 1}.png"
+        save_sample_grid(chunk, path, nrow=int(np.sqrt(len(chunk))))
+        saved.append(path)
+        print(f"  Saved grid: {path}")
+    return saved
+
+
+def _stroke(images) -> Dict[str, float]:
+    if isinstance(images, GeneratedSamples):
+        return stroke_density_from_counts(images.counts, int(np.prod(images.image_shape)))
+    return calculate_stroke_density(images, threshold=THRESHOLD)
+
+
+def _foreground(images) -> Dict[str, Any]:
+    if isinstance(images, GeneratedSamples):
+        return foreground_ratio_from_counts(images.counts, int(np.prod(images.image_shape)))
+    return calculate_foreground_ratio(images, threshold=THRESHOLD)
+
+
+def compute_metrics(fake_images, real_images: Optional[torch.Tensor], device: torch.device) -> Dict[str, Any]:
+    """The report's ``metrics`` dictionary.  ``fake_images``: a GeneratedSamples (its counters are used) or a tensor."""
+    metrics: Dict[str, Any] = {"n_samples": len(fake_images), "image_shape": list(fake_images.shape[1:]),
+                               "metrics_computed_at": datetime.now().isoformat()}
+    if real_images is not None and INCEPTION_AVAILABLE:
+        print("Computing FID score...")
+        try:
+            metrics["fid_score"] = calculate_fid(real_images, getattr(fake_images, "images", fake_images), device)
+            print(f"  FID Score: {metrics['fid_score']:.4f}")
+        except Exception as e:                                  # noqa: BLE001 -- the report records any failure
+            print(f"  Warning: FID computation failed: {e}")
+            metrics["fid_score"], metrics["fid_error"] = None, str(e)
+    elif not INCEPTION_AVAILABLE:
+        print("  Skipping FID: torchvision not available")
+        metrics["fid_score"], metrics["fid_error"] = None, "torchvision not available"
+    else:
+        print("  Skipping FID: no real images provided")
+        metrics["fid_score"], metrics["fid_error"] = None, "no real images provided"
+
+    if LPIPS_AVAILABLE:
+        print("Computing LPIPS diversity...")
+        try:
+            pool = getattr(fake_images, "images", fake_images)
+            metrics["lpips_diversity"] = calculate_lpips_diversity([pool[i] for i in range(min(100, len(pool)))], device)
+            print(f"  LPIPS Diversity: {metrics['lpips_diversity']:.4f}")
+        except Exception as e:                                  # noqa: BLE001
+            print(f"  Warning: LPIPS computation failed: {e}")
+            metrics["lpips_diversity"], metrics["lpips_error"] = None, str(e)
+    else:
+        print("  Skipping LPIPS: lpips package not available")
+        metrics["lpips_diversity"], metrics["lpips_error"] = None, "lpips package not available"
+
+    print("Computing stroke density distribution...")
+    try:
+        sd = metrics["stroke_density"] = _stroke(fake_images)
+        print(f"  Stroke Density - Mean: {sd['mean']:.4f}, Std: {sd['std']:.4f}")
+    except Exception as e:                                      # noqa: BLE001
+        print(f"  Warning: Stroke density computation failed: {e}")
+        metrics["stroke_density"], metrics["stroke_density_error"] = None, str(e)
+    print("Computing foreground ratio statistics...")
+    try:
+        fr = metrics["foreground_ratio"] = _foreground(fake_images)
+        print(f"  Foreground Ratio - Mean: {fr['mean']:.4f}, Std: {fr['std']:.4f}")
+    except Exception as e:                                      # noqa: BLE001
+        print(f"  Warning: Foreground ratio computation failed: {e}")
+        metrics["foreground_ratio"], metrics["foreground_ratio_error"] = None, str(e)
+
+    if real_images is not None:
+        print("Computing real image statistics for comparison...")
+        try:
+            rs, rf = _stroke(real_images), _foreground(real_images)
+            metrics["real_stroke_density"], metrics["real_foreground_ratio"] = rs, rf
+            print(f"  Real Stroke Density - Mean: {rs['mean']:.4f}")
+            print(f"  Real Foreground Ratio - Mean: {rf['mean']:.4f}")
+        except Exception as e:                                  # noqa: BLE001
+            print(f"  Warning: Real image statistics failed: {e}")
+    return metrics
+
+
+def save_evaluation_report(metrics: Dict[str, Any], config: Dict[str, Any], output_dir: Path, checkpoint_path: Path,
+                           grid_paths: List[Path]) -> Path:
+    output_dir = Path(output_dir)
+    output_dir.mkdir(parents=True, exist_ok=True)
+    report = {
+        "evaluation_info": {"checkpoint": str(checkpoint_path), "evaluation_timestamp": datetime.now().isoformat(),
+                            "sample_grids": [str(p) for p in grid_paths]},
+        "model_config": config,
+        "metrics": metrics,
+        "summary": {"fid_score": metrics.get("fid_score"), "lpips_diversity": metrics.get("lpips_diversity"),
+                    "stroke_density_mean": (metrics.get("stroke_density") or {}).get("mean"),
+                    "foreground_ratio_mean": (metrics.get("foreground_ratio") or {}).get("mean"),
+                    "n_samples_evaluated": metrics.get("n_samples")},
+    }
+    path = output_dir / f"evaluation_report_{datetime.now().strftime('%Y%m%d_%H%M%S')}.json"
+    with open(path, "w") as f:
+        json.dump(report, f, indent=2, default=str)
+    print(f"\nEvaluation report saved to: {path}")
+    return path
+
+
+def print_summary(metrics: Dict[str, Any]) -> None:
+    bar = "=" * 60
+    print("\n" + bar + "\nEVALUATION SUMMARY\n" + bar)
+    print(f"\nSamples Evaluated: {metrics.get('n_samples', 'N/A')}")
+    print(f"Image Shape: {metrics.get('image_shape', 'N/A')}")
+    print("\n--- Quality Metrics ---")
+    fid, lp = metrics.get("fid_score"), metrics.get("lpips_diversity")
+    print(f"FID Score: {fid:.4f} (lower is better)" if fid is not None
+          else f"FID Score: Not computed - {metrics.get('fid_error', 'unknown reason')}")
+    print(f"LPIPS Diversity: {lp:.4f} (higher = more diverse)" if lp is not None
+          else f"LPIPS Diversity: Not computed - {metrics.get('lpips_error', 'unknown reason')}")
+    print("\n--- Stroke Analysis ---")
+    stroke = metrics.get("stroke_density")
+    if stroke:
+        print("Stroke Density:")
+        print(f"  Mean: {stroke['mean']:.4f}")
+        print(f"  Std:  {stroke['std']:.4f}")
+        print(f"  Range: [{stroke['min']:.4f}, {stroke['max']:.4f}]")
+    print("\n--- Foreground Analysis ---")
+    fg = metrics.get("foreground_ratio")
+    if fg:
+        print("Foreground Ratio:")
+        print(f"  Mean: {fg['mean']:.4f}")
+        print(f"  Std:  {fg['std']:.4f}")
+        if "percentiles" in fg:
+            pc = fg["percentiles"]
+            print(f"  Percentiles: 25%={pc['25']:.4f}, 50%={pc['50']:.4f}, 75%={pc['75']:.4f}")
+    if "real_stroke_density" in metrics:
+        print("\n--- Comparison with Real Images ---")
+        rs, rf = metrics["real_stroke_density"], metrics.get("real_foreground_ratio", {})
+        print(f"Real Stroke Density Mean: {rs['mean']:.4f} (Generated: {stroke['mean']:.4f})")
+        if rf:
+            print(f"Real Foreground Ratio Mean: {rf['mean']:.4f} (Generated: {fg['mean']:.4f})")
+    print("\n" + bar)
+
+
+def parse_args(argv=None) -> argparse.Namespace:
+    p = argparse.ArgumentParser(description="Evaluate trained Vanilla GAN for signature generation (MI355X HIP engine)",
+                                formatter_class=argparse.ArgumentDefaultsHelpFormatter)
+    p.add_argument("--checkpoint", type=str, required=True, help="Path to model checkpoint (.pt file)")
+    p.add_argument("--n_samples", type=int, default=500, help="Number of samples to generate for evaluation")
+    p.add_argument("--real_dir", type=str, default=None, help="Directory of real signature images to compare with")
+    p.add_argument("--output_dir", type=str, default="figures/evaluation", help="Directory for grids and reports")
+    p.add_argument("--batch_size", type=int, default=64, help="Batch size for sample generation")
+    p.add_argument("--n_grids", type=int, default=3, help="Number of sample grids to generate")
+    p.add_argument("--grid_size", type=int, default=64, help="Number of samples per grid")
+    p.add_argument("--device", type=str, default=None, help="Device to use. Auto-detected if not specified.")
+    p.add_argument("--seed", type=int, default=None, help="Random seed for reproducibility")
+    return p.parse_args(argv)
+
+
+def main(argv=None) -> int:
+    a = parse_args(argv)
+    if a.seed is not None:
+        torch.manual_seed(a.seed)
+        np.random.seed(a.seed)
+        print(f"Random seed set to: {a.seed}")
+    device = torch.device(a.device) if a.device else torch.device("cuda" if torch.cuda.is_available() else "cpu")
+    print(f"Using device: {device}")
+    checkpoint_path, output_dir = Path(a.checkpoint), Path(a.output_dir)
+    real_dir = Path(a.real_dir) if a.real_dir else None
+    try:
+        generator, config = load_generator_from_checkpoint(checkpoint_path, device)
+        fake = generate_samples(generator, a.n_samples, generator.latent_dim, device, a.batch_size,
+                                keep_images=max(0, a.n_grids) * a.grid_size)
+        print("\nCreating sample grids...")
+        grid_paths = create_sample_grids(fake, output_dir, a.n_grids, a.grid_size)
+        real = None
+        if real_dir:
+            try:
+                real = load_real_images(real_dir, a.n_samples, generator.output_size, device)
+            except Exception as e:                              # noqa: BLE001 -- the evaluation goes on without them
+                print(f"Warning: Could not load real images: {e}")
+        print("\nComputing evaluation metrics...")
+        metrics = compute_metrics(fake, real, device)
+        report_path = save_evaluation_report(metrics, config, output_dir, checkpoint_path, grid_paths)
+        print_summary(metrics)
+        print("\nEvaluation complete!")
+        print(f"  Sample grids saved to: {output_dir}")
+        print(f"  Report saved to: {report_path}")
+        return 0
+    except FileNotFoundError as e:
+        print(f"Error: {e}")
+        return 1
+    except Exception as e:                                      # noqa: BLE001
+        print(f"Evaluation failed: {e}")
+        import traceback
+        traceback.print_exc()
+        return 1
+
+
+if __name__ == "__main__":
+    sys.exit(main())

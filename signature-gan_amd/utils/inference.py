@@ -32,8 +32,15 @@ def infer_architecture_from_state_dict(state_dict: Dict[str, Any]) -> Tuple[int,
 
 def load_generator(checkpoint_path: str, device: torch.device) -> Tuple[Generator, int]:
     """(Generator in eval mode on ``device``, latent_dim).  Only the safe loader is used."""
+    g, latent_dim, _ = load_generator_and_config(checkpoint_path, device)
+    return g, latent_dim
+
+
+def load_generator_and_config(checkpoint_path: str, device: torch.device) -> Tuple[Generator, int, Dict[str, Any]]:
+    """load_generator plus the checkpoint's ``config`` dict ({} where the file has none): what the evaluation report records."""
     ck = torch.load(checkpoint_path, map_location="cpu", weights_only=True)
     channels = DEFAULT_IMAGE_CHANNELS
+    cfg: Dict[str, Any] = {}
     if isinstance(ck, dict) and ("generator_state_dict" in ck or "state_dict" in ck):
         cfg = ck.get("config", {}) or {}
         latent_dim = cfg.get("latent_dim", DEFAULT_LATENT_DIM)
@@ -47,13 +54,36 @@ def load_generator(checkpoint_path: str, device: torch.device) -> Tuple[Generato
     g.load_state_dict(sd)
     g.to(device)
     g.eval()
-    return g, latent_dim
+    return g, latent_dim, dict(cfg)
 
 
 def tensor_to_uint8(images: torch.Tensor) -> np.ndarray:
     """(B,1,H,W) in [-1,1] -> (B,H,W) uint8 with the reference's rule ((x+1)*127.5, clip, TRUNCATE)."""
     x = images.detach().float().cpu().numpy()
     return ((x[:, 0] + 1) * 127.5).clip(0, 255).astype(np.uint8)
+
+
+_pinned: Dict[Any, torch.Tensor] = {}       # one reused page-locked staging buffer per device (grown, never shrunk)
+
+
+def _to_host_u8(u8: torch.Tensor) -> np.ndarray:
+    """Device uint8 tensor -> numpy array of the same shape: one byte per pixel through the pinned buffer."""
+    n = u8.numel()
+    buf = _pinned.get(u8.device)
+    if buf is None or buf.numel() < n:
+        buf = _pinned[u8.device] = torch.empty(max(n, 1), dtype=torch.uint8, pin_memory=True)
+    buf[:n].copy_(u8.reshape(-1), non_blocking=True)
+    torch.cuda.current_stream(u8.device).synchronize()
+    return buf[:n].numpy().reshape(tuple(u8.shape)).copy()       # (the buffer is reused by the next call)
+
+
+def generate_uint8(generator: Generator, z: torch.Tensor) -> np.ndarray:
+    """z (B, latent) -> (B, H, W) uint8, the bytes of ``tensor_to_uint8(generator(z))``.  In eval mode the Generator's last
+    kernel writes them itself (Engine.g_generate_u8) and one byte per pixel crosses to the host; a Generator left in train()
+    mode (BatchNorm batch statistics) has no such kernel and takes the fp32 route."""
+    if generator.training:
+        return tensor_to_uint8(generator(z))
+    return _to_host_u8(generator._require_engine().g_generate_u8(z))
 
 
 def tensor_to_pil_image(tensor: torch.Tensor):
@@ -77,7 +107,7 @@ def generate_signatures_batch(generator: Generator, n_samples: int, latent_dim: 
     while done < n_samples:
         b = min(batch_size, n_samples - done)
         z = torch.randn(b, latent_dim, device=device) * noise_scale
-        for arr in tensor_to_uint8(generator(z)):
+        for arr in generate_uint8(generator, z):
             out.append(Image.fromarray(arr, mode="L"))
         done += b
         if progress_callback is not None:

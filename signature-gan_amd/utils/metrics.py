@@ -1,0 +1,136 @@
+"""Drop-in for the reference's ``utils/metrics.py`` on the MI355X HIP engine.
+
+The stroke statistics (utils/metrics.py:118-174) are per-image pixel counts below a threshold.  Here the counting is done
+on the device -- by the Generator's last kernel for generated batches (Engine.g_generate_u8) or by ``siggan_image_stats``
+for any other tensor -- and only three int32 per image reach the host; the dictionaries are then formed from the counts
+with the numpy calls the reference makes on its per-image densities.  A per-image density is count / P in fp32: exact for
+the image sizes built here (P a power of two, count < 2**24), so it equals the reference's mean over 0/1 floats bit for bit;
+for another P the two may differ in the last bit.
+
+FID and LPIPS need downloaded network weights; computing them is not built.  The availability flags and the ImportError
+texts are the reference's, so callers (the evaluation CLI) report them the same way."""
+from collections import defaultdict
+from typing import Dict, List, Optional, Union
+
+import numpy as np
+import torch
+
+from .._lib import IS_INK_SIGNED, IS_INK_UNIT, IS_NEG
+
+try:
+    from torchvision.models import inception_v3  # noqa: F401
+    INCEPTION_AVAILABLE = True
+except ImportError:
+    INCEPTION_AVAILABLE = False
+
+try:
+    import lpips  # noqa: F401
+    LPIPS_AVAILABLE = True
+except ImportError:
+    LPIPS_AVAILABLE = False
+
+
+def calculate_fid(real_images: torch.Tensor, fake_images: torch.Tensor, device: Optional[torch.device] = None) -> float:
+    if not INCEPTION_AVAILABLE:
+        raise ImportError("torchvision required for FID calculation")
+    raise NotImplementedError("FID needs InceptionV3 weights, which this build does not ship or download")
+
+
+def calculate_lpips_diversity(images_list: List[torch.Tensor], device: Optional[torch.device] = None) -> float:
+    if not LPIPS_AVAILABLE:
+        raise ImportError("lpips package required: pip install lpips")
+    raise NotImplementedError("LPIPS needs AlexNet weights, which this build does not ship or download")
+
+
+# ---- counters -> dictionaries (pure numpy) ---------------------------------------------------------------------------
+def densities_from_counts(counts, pixels: int, signed: Optional[bool] = None) -> np.ndarray:
+    """Per-image fraction of pixels below the threshold, float32 (N,), from (N, 3) counters (columns _lib.IS_*).
+    ``signed`` None: the reference's test ``images.min() < 0`` over the whole batch, i.e. any NEG count non-zero; True /
+    False pick the [-1, 1] / [0, 1] branch outright."""
+    counts = np.asarray(counts).reshape(-1, 3)
+    if signed is None:
+        signed = bool(counts[:, IS_NEG].sum() > 0)
+    ink = counts[:, IS_INK_SIGNED if signed else IS_INK_UNIT]
+    return ink.astype(np.float32) / np.float32(pixels)
+
+
+def _stroke_dict(d: np.ndarray) -> Dict[str, float]:
+    return {"mean": float(np.mean(d)), "std": float(np.std(d)), "min": float(np.min(d)), "max": float(np.max(d))}
+
+
+def _foreground_dict(d: np.ndarray) -> Dict[str, object]:
+    return {"mean": float(np.mean(d)), "std": float(np.std(d)),
+            "percentiles": {q: float(np.percentile(d, int(q))) for q in ("25", "50", "75")}}
+
+
+def stroke_density_from_counts(counts, pixels: int, signed: Optional[bool] = None) -> Dict[str, float]:
+    """calculate_stroke_density's dictionary from ready counters (what the evaluation CLI holds after generation)."""
+    return _stroke_dict(densities_from_counts(counts, pixels, signed))
+
+
+def foreground_ratio_from_counts(counts, pixels: int, signed: Optional[bool] = None) -> Dict[str, object]:
+    """calculate_foreground_ratio's dictionary from ready counters."""
+    return _foreground_dict(densities_from_counts(counts, pixels, signed))
+
+
+# ---- tensors -> counters (device) ------------------------------------------------------------------------------------
+def _densities(images: torch.Tensor, threshold: float) -> np.ndarray:
+    from ..engine import Engine
+    if images.device.type != "cuda":
+        if not torch.cuda.is_available():
+            raise RuntimeError("the stroke statistics are counted on a ROCm device ('cuda:N'); there is no CPU path")
+        images = images.cuda()
+    x = images.detach().to(torch.float32)
+    signed = None
+    if x.dim() == 4 and x.shape[1] > 1:
+        # more than one channel: the reference maps to [0, 1] first (when any value is negative) and averages the
+        # channels (utils/metrics.py:129-133); torch does both, the kernel counts the one-channel result's unit branch
+        if bool(x.min() < 0):
+            x = (x + 1) / 2
+        x = x.mean(dim=1, keepdim=True)
+        signed = False
+    x = x.contiguous()
+    counts = Engine.image_stats(x, threshold).cpu().numpy()
+    return densities_from_counts(counts, x.numel() // x.shape[0], signed)
+
+
+def calculate_stroke_density(images: torch.Tensor, threshold: float = 0.5) -> Dict[str, float]:
+    """images (N, C, H, W) in [0, 1] or [-1, 1] -> {'mean', 'std', 'min', 'max'} of the per-image stroke density."""
+    return _stroke_dict(_densities(images, threshold))
+
+
+def calculate_foreground_ratio(images: torch.Tensor, threshold: float = 0.5) -> Dict[str, object]:
+    """images (N, C, H, W) in [0, 1] or [-1, 1] -> {'mean', 'std', 'percentiles': {'25', '50', '75'}}."""
+    return _foreground_dict(_densities(images, threshold))
+
+
+class MetricsTracker:
+    """Per-epoch running values and the history of their epoch averages (utils/metrics.py:177-213)."""
+
+    def __init__(self) -> None:
+        self.metrics: Dict[str, List[float]] = defaultdict(list)
+        self.epoch_metrics: Dict[str, List[float]] = defaultdict(list)
+
+    def add(self, name: str, value: Union[float, torch.Tensor]) -> None:
+        self.epoch_metrics[name].append(value.item() if isinstance(value, torch.Tensor) else value)
+
+    def get_average(self, name: str) -> float:
+        values = self.epoch_metrics.get(name, [])
+        return float(np.mean(values)) if values else 0.0
+
+    def get_all_averages(self) -> Dict[str, float]:
+        return {name: self.get_average(name) for name in self.epoch_metrics}
+
+    def reset(self) -> None:
+        """Close the epoch: every metric's average joins its history, the running values are dropped."""
+        for name, values in self.epoch_metrics.items():
+            if values:
+                self.metrics[name].append(float(np.mean(values)))
+        self.epoch_metrics.clear()
+
+    def get_history(self, name: str) -> List[float]:
+        return self.metrics.get(name, [])
+
+    def get_last(self, name: str, default: float = 0.0) -> float:
+        history = self.metrics.get(name, [])
+        return history[-1] if history else default
