@@ -1,4 +1,4 @@
-"""ctypes binding of the C ABI in include/siggan.h.
+"""ctypes binding of the C ABI in include/siggan.h (and siggan_mlp.h, siggan_verifier.h).
 
 The shared library is built in-tree by ``__graft_entry__.build()`` / ``csrc/Makefile`` and must be
 present: there is no CPU or PyTorch fallback for this path -- a missing or stale library raises.
@@ -55,6 +55,19 @@ class MlpStorage(C.Structure):
     _fields_ = [(n, C.c_void_p) for n in (
         "g_params", "g_grads", "g_exp_avg", "g_exp_avg_sq", "g_adam_steps", "g_bn_running_mean",
         "g_bn_running_var", "g_bn_batches", "d_params", "d_grads", "d_exp_avg", "d_exp_avg_sq", "d_adam_steps")]
+
+
+VERIFIER_WEIGHT_FIELDS = (                 # include/siggan_verifier.h, state_dict() order
+    "conv1_weight", "conv1_bias", "bn1_weight", "bn1_bias", "bn1_running_mean", "bn1_running_var",
+    "conv2_weight", "conv2_bias", "bn2_weight", "bn2_bias", "bn2_running_mean", "bn2_running_var",
+    "conv3_weight", "conv3_bias", "bn3_weight", "bn3_bias", "bn3_running_mean", "bn3_running_var",
+    "fc1_weight", "fc1_bias", "fc2_weight", "fc2_bias", "cls0_weight", "cls0_bias", "cls3_weight", "cls3_bias")
+VFMT_F32, VFMT_U8 = 0, 1
+E_ARG = -1                                 # SIGGAN_E_ARG (= SIGGAN_E_INVALID)
+
+
+class VerifierWeights(C.Structure):
+    _fields_ = [(n, C.c_void_p) for n in VERIFIER_WEIGHT_FIELDS] + [("bn_eps", C.c_float)]
 
 
 _P, _I32, _I64 = C.c_void_p, C.c_int32, C.c_int64
@@ -120,6 +133,17 @@ _SIGNATURES = {
     "mlpgan_op_gemm": (C.c_int, [_I32, _I32, _P, _P, _P, _I32, _I32, _I32, _P]),
 }
 EXPORTS = tuple(_SIGNATURES)
+# Siamese signature verifier, eval-mode forward (include/siggan_verifier.h): new symbols beside ABI 4, listed on their own
+_VERIFIER_SIGNATURES = {
+    "siggan_verifier_create": (C.c_int, [_I32, _I32, _I32, C.POINTER(_P)]),
+    "siggan_verifier_destroy": (C.c_int, [_P]),
+    "siggan_verifier_bind": (C.c_int, [_P, C.POINTER(VerifierWeights), _P]),
+    "siggan_verifier_embed": (C.c_int, [_P, _P, _I32, _I32, _P, _P]),
+    "siggan_verifier_compare": (C.c_int, [_P, _P, _P, _I32, _P, _P]),
+    "siggan_verifier_score": (C.c_int, [_P, _P, _P, _I32, _I32, _P, _P, _P, _P]),
+    "siggan_verifier_debug_tensor": (C.c_int, [_P, C.c_char_p, _P, _I64, _P]),
+}
+VERIFIER_EXPORTS = tuple(_VERIFIER_SIGNATURES)
 
 _lib = None
 
@@ -134,7 +158,7 @@ def load():
             f"{LIB_PATH} is missing: build it with `python -c 'import __graft_entry__ as g; g.build()'` "
             "(or `make -C signature-gan_amd/csrc`). This path has no CPU/PyTorch fallback.")
     lib = C.CDLL(LIB_PATH)
-    for name, (res, args) in _SIGNATURES.items():
+    for name, (res, args) in {**_SIGNATURES, **_VERIFIER_SIGNATURES}.items():
         fn = getattr(lib, name)          # AttributeError if the library does not export the symbol
         fn.restype, fn.argtypes = res, args
     if lib.siggan_abi_version() != ABI_VERSION:

@@ -1,0 +1,969 @@
+"""Signature verification model evaluation on the MI355X HIP path.
+
+Drop-in for the reference's ``signature_verifier_eval`` module: the Siamese CNN (``CNNEncoder`` / ``SiameseNetwork``,
+reference :39-179) with the reference's attribute names, ``state_dict()`` and checkpoint dictionary, its test dataset and
+pair generation, its metrics, report and CLI.  The eval-mode forward runs in HIP (include/siggan_verifier.h,
+csrc/verifier.hip); the modules here only hold the parameters.  There is no PyTorch fallback: a forward in training mode
+or on CPU tensors raises.  Training the verifier is not part of this package.
+
+Beyond the reference: ``embed_u8`` / ``score_u8`` take uint8 (N, 64, 64) images (what ``Engine.g_generate_u8`` writes and
+what a PNG holds) and normalise them on load exactly as ToTensor + Normalize([0.5], [0.5]) would; ``compare`` scores
+embeddings that were computed earlier (one query against an enrolled gallery).
+
+The metrics are numpy only (this package imports neither scikit-learn nor matplotlib at module level); the ROC points are
+those of ``sklearn.metrics.roc_curve`` with its defaults.  The plots are written when matplotlib can be imported.
+"""
+import argparse
+import ctypes as C
+import json
+from datetime import datetime
+from pathlib import Path
+from typing import Any, Dict, List, Optional, Tuple, Union
+
+import numpy as np
+import torch
+import torch.nn as nn
+from PIL import Image
+from torch.utils.data import DataLoader, Dataset
+
+from . import _lib
+
+IMAGE_SIZE = 64
+DEFAULT_MAX_IMAGES = 512
+_NO_CPU = "runs on the MI355X HIP path only: move the model and its inputs to a ROCm device (.to('cuda')); there is no CPU path"
+
+
+def _ptr(t):
+    return C.c_void_p(t.data_ptr()) if t is not None else C.c_void_p(0)
+
+
+# =============================================================================
+# HIP context
+# =============================================================================
+
+
+class _Context:
+    """One siggan_verifier handle: the packed weights and the workspace for up to ``max_images`` images per call."""
+
+    def __init__(self, device, embedding_dim, max_images):
+        self.lib = _lib.load()
+        self.device = torch.device(device)
+        if self.device.index is None:
+            self.device = torch.device("cuda", torch.cuda.current_device())
+        self.E, self.max_images = int(embedding_dim), int(max_images)
+        h = C.c_void_p()
+        _lib.check(self.lib.siggan_verifier_create(self.device.index, self.E, self.max_images, C.byref(h)))
+        self._h = h
+
+    def _stream(self):
+        return C.c_void_p(torch.cuda.current_stream(self.device).cuda_stream)
+
+    def bind(self, tensors, bn_eps):
+        """tensors: the 26 fp32 device tensors in _lib.VERIFIER_WEIGHT_FIELDS order (copied / packed by the library)."""
+        w = _lib.VerifierWeights()
+        keep = []
+        for name, t in zip(_lib.VERIFIER_WEIGHT_FIELDS, tensors):
+            t = t.detach()
+            if t.device != self.device or t.dtype != torch.float32:
+                raise ValueError(f"{name} must be float32 on {self.device}, got {t.dtype} on {t.device}")
+            t = t.contiguous()
+            keep.append(t)
+            setattr(w, name, t.data_ptr())
+        w.bn_eps = float(bn_eps)
+        _lib.check(self.lib.siggan_verifier_bind(self._h, C.byref(w), self._stream()))
+
+    def _images(self, x, what):
+        """-> (contiguous tensor, fmt, n)"""
+        if x.device != self.device:
+            raise ValueError(f"{what} must live on {self.device}, got {x.device}")
+        if x.dim() == 4 and x.shape[1] == 1:
+            x = x[:, 0]
+        if x.dim() != 3 or x.shape[1] != IMAGE_SIZE or x.shape[2] != IMAGE_SIZE:
+            raise ValueError(f"{what} must be (N, 1, {IMAGE_SIZE}, {IMAGE_SIZE}) or (N, {IMAGE_SIZE}, {IMAGE_SIZE}), got {tuple(x.shape)}")
+        if x.dtype == torch.uint8:
+            fmt = _lib.VFMT_U8
+        elif x.dtype == torch.float32:
+            fmt = _lib.VFMT_F32
+        else:
+            raise ValueError(f"{what} must be float32 or uint8, got {x.dtype}")
+        return x.contiguous(), fmt, x.shape[0]
+
+    def embed(self, x):
+        x, fmt, n = self._images(x, "x")
+        out = torch.empty(n, self.E, dtype=torch.float32, device=self.device)
+        for i in range(0, n, self.max_images):
+            c = x[i:i + self.max_images]
+            _lib.check(self.lib.siggan_verifier_embed(self._h, _ptr(c), fmt, c.shape[0], _ptr(out[i:]), self._stream()))
+        return out
+
+    def score(self, x1, x2):
+        x1, fmt, n = self._images(x1, "x1")
+        x2, fmt2, n2 = self._images(x2, "x2")
+        if fmt != fmt2 or n != n2:
+            raise ValueError("x1 and x2 must have the same dtype and batch size")
+        if self.max_images < 2:
+            raise ValueError("scoring pairs needs a context of at least 2 images")
+        e1 = torch.empty(n, self.E, dtype=torch.float32, device=self.device)
+        e2 = torch.empty_like(e1)
+        s = torch.empty(n, 1, dtype=torch.float32, device=self.device)
+        step = self.max_images // 2
+        for i in range(0, n, step):
+            a, b = x1[i:i + step], x2[i:i + step]
+            _lib.check(self.lib.siggan_verifier_score(self._h, _ptr(a), _ptr(b), fmt, a.shape[0], _ptr(e1[i:]), _ptr(e2[i:]),
+                                                      _ptr(s[i:]), self._stream()))
+        return e1, e2, s
+
+    def compare(self, e1, e2):
+        for e in (e1, e2):
+            if e.device != self.device or e.dtype != torch.float32 or e.dim() != 2 or e.shape[1] != self.E:
+                raise ValueError(f"embeddings must be float32 (N, {self.E}) on {self.device}")
+        if e1.shape != e2.shape:
+            raise ValueError("e1 and e2 must have the same shape")
+        e1, e2 = e1.contiguous(), e2.contiguous()
+        s = torch.empty(e1.shape[0], 1, dtype=torch.float32, device=self.device)
+        if e1.shape[0]:
+            _lib.check(self.lib.siggan_verifier_compare(self._h, _ptr(e1), _ptr(e2), e1.shape[0], _ptr(s), self._stream()))
+        return s
+
+    def debug_tensor(self, name, shape):
+        """Stage 'pool1' | 'pool2' | 'pool3' | 'fc1' of the last call in torch's layout (test hook)."""
+        n = int(np.prod(shape))
+        out = torch.empty(n, dtype=torch.float32, device=self.device)
+        _lib.check(self.lib.siggan_verifier_debug_tensor(self._h, name.encode(), _ptr(out), n, self._stream()))
+        return out.view(*shape)
+
+    def close(self):
+        if getattr(self, "_h", None):
+            self.lib.siggan_verifier_destroy(self._h)
+            self._h = None
+
+    def __del__(self):
+        try:
+            self.close()
+        except Exception:                                   # interpreter shutdown
+            pass
+
+
+class _HipModule(nn.Module):
+    """Shared plumbing: a lazily created context whose packs are refreshed after the weights change."""
+
+    def _init_hip(self, max_images):
+        self.max_images = int(max_images)
+        self._ctx = None
+        self._stale = True
+
+    def params_changed(self):
+        """Tell the HIP path that parameters or buffers were written in place (the packs are rebuilt on the next call)."""
+        self._stale = True
+        for m in self.children():
+            if isinstance(m, _HipModule):
+                m.params_changed()
+
+    def _apply(self, fn, recurse=True):
+        out = super()._apply(fn, recurse)
+        if self._ctx is not None:
+            self._ctx.close()
+        self._ctx, self._stale = None, True
+        return out
+
+    def load_state_dict(self, state_dict, strict=True, assign=False):
+        out = super().load_state_dict(state_dict, strict=strict, assign=assign)
+        self.params_changed()
+        return out
+
+    def _weights(self):
+        raise NotImplementedError
+
+    def _context(self):
+        dev = next(self.parameters()).device
+        if dev.type != "cuda":
+            raise RuntimeError(f"{type(self).__name__} {_NO_CPU}")
+        if self._ctx is None or self._ctx.max_images != self.max_images:
+            if self._ctx is not None:
+                self._ctx.close()
+            self._ctx = _Context(dev, self.embedding_dim, self.max_images)
+            self._stale = True
+        if self._stale:
+            tensors, eps = self._weights()
+            self._ctx.bind(tensors, eps)
+            self._stale = False
+        return self._ctx
+
+    def _on_device(self, *xs):
+        if self.training:
+            raise RuntimeError(f"{type(self).__name__}: only the eval-mode forward is built (call .eval()); "
+                               "training the verifier is not part of this package")
+        for x in xs:
+            if not isinstance(x, torch.Tensor) or x.device.type != "cuda":
+                raise RuntimeError(f"{type(self).__name__} {_NO_CPU}")
+
+
+# =============================================================================
+# Model Architecture (must match training)
+# =============================================================================
+
+
+class CNNEncoder(_HipModule):
+    """
+    CNN encoder for extracting features from 64x64 signature images.
+
+    Architecture:
+        Conv2d(1,32) -> Conv2d(32,64) -> Conv2d(64,128) -> FC -> embedding
+    """
+
+    def __init__(self, embedding_dim: int = 128, max_images: int = DEFAULT_MAX_IMAGES) -> None:
+        super().__init__()
+        self.conv1 = nn.Conv2d(1, 32, kernel_size=5, stride=1, padding=2)
+        self.bn1 = nn.BatchNorm2d(32)
+        self.pool1 = nn.MaxPool2d(kernel_size=2, stride=2)
+
+        self.conv2 = nn.Conv2d(32, 64, kernel_size=5, stride=1, padding=2)
+        self.bn2 = nn.BatchNorm2d(64)
+        self.pool2 = nn.MaxPool2d(kernel_size=2, stride=2)
+
+        self.conv3 = nn.Conv2d(64, 128, kernel_size=3, stride=1, padding=1)
+        self.bn3 = nn.BatchNorm2d(128)
+        self.pool3 = nn.MaxPool2d(kernel_size=2, stride=2)
+
+        # After 3 pooling layers: 64 -> 32 -> 16 -> 8
+        self.fc1 = nn.Linear(128 * 8 * 8, 512)
+        self.dropout = nn.Dropout(0.5)
+        self.fc2 = nn.Linear(512, embedding_dim)
+        self.embedding_dim = int(embedding_dim)
+        self._init_hip(max_images)
+
+    def _encoder_tensors(self):
+        out = []
+        for conv, bn in ((self.conv1, self.bn1), (self.conv2, self.bn2), (self.conv3, self.bn3)):
+            out += [conv.weight, conv.bias, bn.weight, bn.bias, bn.running_mean, bn.running_var]
+        out += [self.fc1.weight, self.fc1.bias, self.fc2.weight, self.fc2.bias]
+        if not (self.bn1.eps == self.bn2.eps == self.bn3.eps):
+            raise ValueError("the three BatchNorm layers must share one eps")
+        return out, self.bn1.eps
+
+    def _weights(self):
+        enc, eps = self._encoder_tensors()
+        dev, e = self.fc2.weight.device, self.embedding_dim
+        z = lambda *s: torch.zeros(*s, dtype=torch.float32, device=dev)   # a bare encoder has no pair head
+        return enc + [z(64, e), z(64), z(1, 64), z(1)], eps
+
+    def forward(self, x: torch.Tensor) -> torch.Tensor:
+        """(batch_size, 1, 64, 64) in [-1, 1] -> L2-normalised (batch_size, embedding_dim)."""
+        self._on_device(x)
+        return self._context().embed(x)
+
+    def embed_u8(self, images: torch.Tensor) -> torch.Tensor:
+        """uint8 (N, 64, 64) -> embeddings; bit-identical to forward() on ((b / 255) - 0.5) / 0.5."""
+        self._on_device(images)
+        if images.dtype != torch.uint8:
+            raise ValueError(f"embed_u8 takes uint8 images, got {images.dtype}")
+        return self._context().embed(images)
+
+
+class SiameseNetwork(_HipModule):
+    """
+    Siamese Network for signature verification.
+
+    Uses twin CNN encoders with shared weights to compare two signatures
+    and determine if they belong to the same person.
+    """
+
+    def __init__(self, embedding_dim: int = 128, max_images: int = DEFAULT_MAX_IMAGES) -> None:
+        super().__init__()
+        self.encoder = CNNEncoder(embedding_dim=embedding_dim, max_images=max_images)
+        self.embedding_dim = embedding_dim
+
+        # Classifier for BCE loss approach
+        self.classifier = nn.Sequential(
+            nn.Linear(embedding_dim, 64),
+            nn.ReLU(),
+            nn.Dropout(0.3),
+            nn.Linear(64, 1),
+            nn.Sigmoid()
+        )
+        self._init_hip(max_images)
+
+    def _weights(self):
+        enc, eps = self.encoder._encoder_tensors()
+        c0, c3 = self.classifier[0], self.classifier[3]
+        return enc + [c0.weight, c0.bias, c3.weight, c3.bias], eps
+
+    def forward_one(self, x: torch.Tensor) -> torch.Tensor:
+        """Embedding of a batch of images (one encoder pass)."""
+        self._on_device(x)
+        return self._context().embed(x)
+
+    def forward(self, x1: torch.Tensor, x2: torch.Tensor) -> Tuple[torch.Tensor, torch.Tensor, torch.Tensor]:
+        """(embedding1, embedding2, similarity (B, 1)); both images of every pair go through the encoder as one batch.
+        Batches larger than the context (``max_images`` images, i.e. max_images // 2 pairs) are chunked."""
+        self._on_device(x1, x2)
+        return self._context().score(x1, x2)
+
+    def embed_u8(self, images: torch.Tensor) -> torch.Tensor:
+        self._on_device(images)
+        if images.dtype != torch.uint8:
+            raise ValueError(f"embed_u8 takes uint8 images, got {images.dtype}")
+        return self._context().embed(images)
+
+    def score_u8(self, images1: torch.Tensor, images2: torch.Tensor) -> Tuple[torch.Tensor, torch.Tensor, torch.Tensor]:
+        """forward() on uint8 (B, 64, 64) images, normalised on load."""
+        self._on_device(images1, images2)
+        if images1.dtype != torch.uint8 or images2.dtype != torch.uint8:
+            raise ValueError("score_u8 takes uint8 images")
+        return self._context().score(images1, images2)
+
+    def compare(self, e1: torch.Tensor, e2: torch.Tensor) -> torch.Tensor:
+        """Similarity (B, 1) of embeddings computed earlier (forward_one / embed_u8)."""
+        self._on_device(e1, e2)
+        return self._context().compare(e1, e2)
+
+    def debug_tensor(self, name, shape):
+        return self._context().debug_tensor(name, shape)
+
+
+# =============================================================================
+# Test Dataset
+# =============================================================================
+
+
+def load_uint8(path: Union[str, Path]) -> np.ndarray:
+    """PIL 'L' + bilinear resize to 64x64 (what torchvision's Resize does on a PIL image) -> uint8 (64, 64)."""
+    img = Image.open(path).convert('L').resize((IMAGE_SIZE, IMAGE_SIZE), Image.BILINEAR)
+    return np.asarray(img, dtype=np.uint8)
+
+
+def normalize_uint8(a: np.ndarray) -> np.ndarray:
+    """ToTensor then Normalize([0.5], [0.5]): two fp32 operations, in this order."""
+    v = a.astype(np.float32) / np.float32(255.0)
+    return (v - np.float32(0.5)) / np.float32(0.5)
+
+
+def default_transform(img: Image.Image) -> torch.Tensor:
+    """Resize((64, 64)) -> Grayscale(1) -> ToTensor -> Normalize([0.5], [0.5]) with PIL + numpy: (1, 64, 64) fp32."""
+    a = np.asarray(img.convert('L').resize((IMAGE_SIZE, IMAGE_SIZE), Image.BILINEAR), dtype=np.uint8)
+    return torch.from_numpy(normalize_uint8(a)[None])
+
+
+class SignatureTestDataset(Dataset):
+    """
+    Test dataset for signature verification evaluation.
+
+    Supports two directory structures:
+        1. Organized by user: test_dir/user_id/*.png
+        2. Flat with naming convention: test_dir/userID_sigNum.png
+
+    Generates genuine (same user) and forgery (different user) pairs with the reference's np.random calls.
+    ``uint8=True`` hands out the resized uint8 (64, 64) images instead of normalised fp32 (the byte route).
+    """
+
+    def __init__(self, test_dir: str, transform=None, pairs_per_user: int = 20, seed: int = 42, uint8: bool = False) -> None:
+        self.test_dir = Path(test_dir)
+        self.pairs_per_user = pairs_per_user
+        self.transform = transform or default_transform
+        self.uint8 = bool(uint8)
+
+        np.random.seed(seed)
+
+        self.user_signatures: Dict[str, List[Path]] = {}
+        self._load_signatures()
+
+        self.pairs: List[Tuple[Path, Path, int]] = []
+        self._generate_pairs()
+
+    def _load_signatures(self) -> None:
+        image_extensions = {'.png', '.jpg', '.jpeg', '.bmp', '.tiff'}
+        subdirs = [d for d in self.test_dir.iterdir() if d.is_dir()]
+        if subdirs:
+            for user_dir in subdirs:
+                user_id = user_dir.name
+                user_images = [f for f in user_dir.iterdir() if f.suffix.lower() in image_extensions]
+                if len(user_images) >= 2:
+                    self.user_signatures[user_id] = user_images
+        else:
+            all_images = [f for f in self.test_dir.iterdir() if f.suffix.lower() in image_extensions]
+            for img_path in all_images:
+                filename = img_path.stem
+                parts = filename.split('_')
+                user_id = parts[0] if parts else filename
+                if user_id not in self.user_signatures:
+                    self.user_signatures[user_id] = []
+                self.user_signatures[user_id].append(img_path)
+            self.user_signatures = {k: v for k, v in self.user_signatures.items() if len(v) >= 2}
+        print(f"[Test Dataset] Loaded {len(self.user_signatures)} users")
+
+    def _generate_pairs(self) -> None:
+        user_ids = list(self.user_signatures.keys())
+        if len(user_ids) < 2:
+            print("WARNING: Need at least 2 users to generate forgery pairs")
+            return
+        for user_id in user_ids:
+            user_sigs = self.user_signatures[user_id]
+            # genuine pairs (same user), label 1
+            num_genuine = min(self.pairs_per_user, len(user_sigs) * (len(user_sigs) - 1) // 2)
+            for _ in range(num_genuine):
+                if len(user_sigs) >= 2:
+                    indices = np.random.choice(len(user_sigs), 2, replace=False)
+                    self.pairs.append((user_sigs[indices[0]], user_sigs[indices[1]], 1))
+            # forgery pairs (different users), label 0
+            other_users = [u for u in user_ids if u != user_id]
+            for _ in range(self.pairs_per_user):
+                other_user = np.random.choice(other_users)
+                sig1 = user_sigs[np.random.randint(len(user_sigs))]
+                other_sigs = self.user_signatures[other_user]
+                sig2 = other_sigs[np.random.randint(len(other_sigs))]
+                self.pairs.append((sig1, sig2, 0))
+        np.random.shuffle(self.pairs)
+        genuine_count = sum(1 for _, _, label in self.pairs if label == 1)
+        forgery_count = len(self.pairs) - genuine_count
+        print(f"[Test Dataset] Generated {len(self.pairs)} pairs: "
+              f"{genuine_count} genuine, {forgery_count} forgery")
+
+    def __len__(self) -> int:
+        return len(self.pairs)
+
+    def get_uint8(self, idx: int) -> Tuple[torch.Tensor, torch.Tensor, torch.Tensor]:
+        """The pair as resized uint8 (64, 64) tensors; normalize_uint8 of them is the default transform bit for bit."""
+        sig1_path, sig2_path, label = self.pairs[idx]
+        return (torch.from_numpy(load_uint8(sig1_path).copy()), torch.from_numpy(load_uint8(sig2_path).copy()),
+                torch.tensor(label, dtype=torch.float32))
+
+    def __getitem__(self, idx: int) -> Tuple[torch.Tensor, torch.Tensor, torch.Tensor]:
+        if self.uint8:
+            return self.get_uint8(idx)
+        sig1_path, sig2_path, label = self.pairs[idx]
+        img1 = Image.open(sig1_path).convert('L')
+        img2 = Image.open(sig2_path).convert('L')
+        if self.transform:
+            img1 = self.transform(img1)
+            img2 = self.transform(img2)
+        return img1, img2, torch.tensor(label, dtype=torch.float32)
+
+
+# =============================================================================
+# Model Loading
+# =============================================================================
+
+
+def load_model(checkpoint_path: str, device: torch.device, embedding_dim: Optional[int] = None
+               ) -> Tuple[SiameseNetwork, Dict[str, Any]]:
+    """Load a trained Siamese model from the reference's checkpoint dictionary; returns (model, metadata)."""
+    checkpoint_path = Path(checkpoint_path)
+    if not checkpoint_path.exists():
+        raise FileNotFoundError(f"Checkpoint not found: {checkpoint_path}")
+    device = torch.device(device)
+    if device.type != "cuda":
+        raise RuntimeError(f"load_model: the verifier {_NO_CPU}")
+
+    checkpoint = torch.load(checkpoint_path, map_location=device, weights_only=False)
+    emb_dim = embedding_dim or checkpoint.get('embedding_dim', 128)
+
+    model = SiameseNetwork(embedding_dim=emb_dim)
+    model.load_state_dict(checkpoint['model_state_dict'])
+    model.to(device)
+    model.eval()
+
+    metadata = {
+        'embedding_dim': emb_dim,
+        'val_accuracy': checkpoint.get('val_accuracy', None),
+        'epoch': checkpoint.get('epoch', None),
+        'includes_synthetic': checkpoint.get('includes_synthetic', False),
+        'checkpoint_path': str(checkpoint_path)
+    }
+    acc = f"{metadata['val_accuracy']:.4f}" if metadata['val_accuracy'] else 'N/A'
+    print(f"[Model] Loaded from: {checkpoint_path}")
+    print(f"[Model] Embedding dim: {emb_dim}, Val accuracy: {acc}")
+    return model, metadata
+
+
+# =============================================================================
+# Metrics Computation (numpy; the points of sklearn.metrics.roc_curve / det_curve)
+# =============================================================================
+
+
+def _binary_clf_curve(y_true: np.ndarray, y_scores: np.ndarray):
+    """False / true positive counts at every distinct score, decreasing (positive label 1)."""
+    y_true = np.asarray(y_true).ravel() == 1
+    y_scores = np.asarray(y_scores, dtype=np.float64).ravel()
+    order = np.argsort(y_scores, kind="mergesort")[::-1]
+    y_scores, y_true = y_scores[order], y_true[order]
+    idx = np.r_[np.where(np.diff(y_scores))[0], y_true.size - 1]
+    tps = np.cumsum(y_true, dtype=np.float64)[idx]
+    fps = 1 + idx - tps
+    return fps, tps, y_scores[idx]
+
+
+def roc_curve(y_true: np.ndarray, y_scores: np.ndarray) -> Tuple[np.ndarray, np.ndarray, np.ndarray]:
+    """(fpr, tpr, thresholds) as sklearn.metrics.roc_curve with its defaults: collinear intermediate points dropped, a
+    leading (0, 0) point at threshold inf; a class with no samples gives NaN rates."""
+    fps, tps, thr = _binary_clf_curve(y_true, y_scores)
+    if len(fps) > 2:
+        keep = np.where(np.r_[True, np.logical_or(np.diff(fps, 2), np.diff(tps, 2)), True])[0]
+        fps, tps, thr = fps[keep], tps[keep], thr[keep]
+    tps, fps, thr = np.r_[0, tps], np.r_[0, fps], np.r_[np.inf, thr]
+    fpr = np.repeat(np.nan, fps.shape) if fps[-1] <= 0 else fps / fps[-1]
+    tpr = np.repeat(np.nan, tps.shape) if tps[-1] <= 0 else tps / tps[-1]
+    return fpr, tpr, thr
+
+
+def det_curve(y_true: np.ndarray, y_scores: np.ndarray) -> Tuple[np.ndarray, np.ndarray, np.ndarray]:
+    """(fpr, fnr, thresholds) as sklearn.metrics.det_curve."""
+    fps, tps, thr = _binary_clf_curve(y_true, y_scores)
+    fns = tps[-1] - tps
+    p_count, n_count = tps[-1], fps[-1]
+    first = fps.searchsorted(fps[0], side="right") - 1 if fps.searchsorted(fps[0], side="right") > 0 else None
+    last = tps.searchsorted(tps[-1]) + 1
+    sl = slice(first, last)
+    return fps[sl][::-1] / n_count, fns[sl][::-1] / p_count, thr[sl][::-1]
+
+
+def auc(x: np.ndarray, y: np.ndarray) -> float:
+    """Trapezoidal area (x monotonic), as sklearn.metrics.auc."""
+    x, y = np.asarray(x, dtype=np.float64), np.asarray(y, dtype=np.float64)
+    dx = np.diff(x)
+    direction = -1.0 if np.any(dx < 0) and np.all(dx <= 0) else 1.0
+    return float(direction * np.sum(dx * (y[1:] + y[:-1]) / 2.0))
+
+
+def compute_verification_metrics(y_true: np.ndarray, y_scores: np.ndarray, y_pred: np.ndarray, threshold: float = 0.5
+                                 ) -> Dict[str, float]:
+    """The reference's metrics dictionary (FAR, FRR, EER, ROC-AUC, ...) for labels 1 = genuine, 0 = forgery."""
+    y_true, y_pred = np.asarray(y_true), np.asarray(y_pred)
+    accuracy = np.mean(y_true == y_pred) if y_true.size else float('nan')
+    tn = int(np.sum((y_true == 0) & (y_pred == 0)))
+    fp = int(np.sum((y_true == 0) & (y_pred == 1)))
+    fn = int(np.sum((y_true == 1) & (y_pred == 0)))
+    tp = int(np.sum((y_true == 1) & (y_pred == 1)))
+
+    # FAR: forgeries accepted as genuine; FRR: genuine signatures rejected
+    total_forgeries = fp + tn
+    far = fp / total_forgeries if total_forgeries > 0 else 0.0
+    total_genuine = fn + tp
+    frr = fn / total_genuine if total_genuine > 0 else 0.0
+
+    precision = tp / (tp + fp) if (tp + fp) > 0 else 0.0
+    recall = tp / (tp + fn) if (tp + fn) > 0 else 0.0
+    f1 = 2 * precision * recall / (precision + recall) if (precision + recall) > 0 else 0.0
+    specificity = tn / (tn + fp) if (tn + fp) > 0 else 0.0
+
+    fpr, tpr, roc_thresholds = roc_curve(y_true, y_scores)
+    roc_auc = auc(fpr, tpr)
+
+    # EER: the ROC point where FAR = FRR (an all-NaN curve, i.e. a class without samples, raises as np.nanargmin does)
+    fnr = 1 - tpr
+    eer_threshold_idx = np.nanargmin(np.abs(fpr - fnr))
+    eer = (fpr[eer_threshold_idx] + fnr[eer_threshold_idx]) / 2
+    eer_threshold = roc_thresholds[eer_threshold_idx] if len(roc_thresholds) > eer_threshold_idx else threshold
+
+    return {
+        'accuracy': float(accuracy),
+        'far': float(far),
+        'frr': float(frr),
+        'eer': float(eer),
+        'eer_threshold': float(eer_threshold),
+        'precision': float(precision),
+        'recall': float(recall),
+        'f1_score': float(f1),
+        'specificity': float(specificity),
+        'roc_auc': float(roc_auc),
+        'true_positives': int(tp),
+        'true_negatives': int(tn),
+        'false_positives': int(fp),
+        'false_negatives': int(fn),
+        'total_genuine': int(total_genuine),
+        'total_forgeries': int(total_forgeries),
+        'threshold': float(threshold)
+    }
+
+
+def compute_eer_from_scores(y_true: np.ndarray, y_scores: np.ndarray) -> Tuple[float, float]:
+    """(EER value, EER threshold) from scores."""
+    fpr, tpr, thresholds = roc_curve(y_true, y_scores)
+    fnr = 1 - tpr
+    eer_idx = np.nanargmin(np.abs(fpr - fnr))
+    eer = (fpr[eer_idx] + fnr[eer_idx]) / 2
+    eer_threshold = thresholds[eer_idx] if len(thresholds) > eer_idx else 0.5
+    return float(eer), float(eer_threshold)
+
+
+# =============================================================================
+# Model Evaluation
+# =============================================================================
+
+
+def evaluate_model(model: SiameseNetwork, dataloader: DataLoader, device: torch.device, threshold: float = 0.5
+                   ) -> Tuple[Dict[str, float], np.ndarray, np.ndarray, np.ndarray]:
+    """Evaluate a Siamese model on test data: (metrics_dict, y_true, y_scores, y_pred).  The loader may hand out fp32
+    (B, 1, 64, 64) or uint8 (B, 64, 64) images (SignatureTestDataset(uint8=True))."""
+    model.eval()
+    all_labels: List[float] = []
+    all_scores: List[float] = []
+    with torch.no_grad():
+        for img1, img2, labels in dataloader:
+            img1 = img1.to(device)
+            img2 = img2.to(device)
+            _, _, similarity = model(img1, img2)
+            all_labels.extend(labels.cpu().numpy().reshape(-1).tolist())
+            all_scores.extend(similarity.reshape(-1).cpu().numpy().tolist())
+    y_true = np.array(all_labels)
+    y_scores = np.array(all_scores)
+    y_pred = (y_scores >= threshold).astype(int)
+    metrics = compute_verification_metrics(y_true, y_scores, y_pred, threshold)
+    return metrics, y_true, y_scores, y_pred
+
+
+# =============================================================================
+# Visualization (written when matplotlib can be imported)
+# =============================================================================
+
+_COLORS = ['#2ecc71', '#e74c3c', '#3498db', '#9b59b6']
+_LINESTYLES = ['-', '--', '-.', ':']
+
+
+def _pyplot():
+    try:
+        import matplotlib
+        matplotlib.use("Agg")
+        import matplotlib.pyplot as plt
+        return plt
+    except ImportError:
+        return None
+
+
+def _save(plt, save_path, what):
+    save_path = Path(save_path)
+    save_path.parent.mkdir(parents=True, exist_ok=True)
+    plt.savefig(save_path, dpi=150, bbox_inches='tight')
+    plt.close()
+    print(f"[Plot] {what} saved to: {save_path}")
+
+
+def plot_roc_curve(results: Dict[str, Dict[str, Any]], save_path: Union[str, Path], figsize: Tuple[int, int] = (10, 8)) -> bool:
+    """ROC curves of all evaluated models; False (nothing written) without matplotlib."""
+    plt = _pyplot()
+    if plt is None:
+        return False
+    plt.figure(figsize=figsize)
+    for idx, (model_name, data) in enumerate(results.items()):
+        fpr, tpr, _ = roc_curve(data['y_true'], data['y_scores'])
+        plt.plot(fpr, tpr, color=_COLORS[idx % 4], linestyle=_LINESTYLES[idx % 4], linewidth=2,
+                 label=f"{model_name} (AUC = {data['metrics']['roc_auc']:.4f})")
+    plt.plot([0, 1], [0, 1], 'k--', linewidth=1, label='Random Classifier')
+    plt.xlim([0.0, 1.0])
+    plt.ylim([0.0, 1.05])
+    plt.xlabel('False Positive Rate (FAR)', fontsize=12)
+    plt.ylabel('True Positive Rate (1 - FRR)', fontsize=12)
+    plt.title('ROC Curve - Signature Verification', fontsize=14)
+    plt.legend(loc='lower right', fontsize=10)
+    plt.grid(True, alpha=0.3)
+    _save(plt, save_path, "ROC curve")
+    return True
+
+
+def plot_det_curve(results: Dict[str, Dict[str, Any]], save_path: Union[str, Path], figsize: Tuple[int, int] = (10, 8)) -> bool:
+    """DET curves (FRR vs FAR, log scale) of all evaluated models."""
+    plt = _pyplot()
+    if plt is None:
+        return False
+    plt.figure(figsize=figsize)
+    for idx, (model_name, data) in enumerate(results.items()):
+        fpr, fnr, _ = det_curve(data['y_true'], data['y_scores'])
+        plt.plot(fpr, fnr, color=_COLORS[idx % 4], linestyle=_LINESTYLES[idx % 4], linewidth=2,
+                 label=f"{model_name} (EER = {data['metrics']['eer']:.4f})")
+    plt.plot([0.001, 1], [0.001, 1], 'k--', linewidth=1, label='EER Line')
+    plt.xscale('log')
+    plt.yscale('log')
+    plt.xlim([0.001, 1])
+    plt.ylim([0.001, 1])
+    plt.xlabel('False Acceptance Rate (FAR)', fontsize=12)
+    plt.ylabel('False Rejection Rate (FRR)', fontsize=12)
+    plt.title('DET Curve - Signature Verification', fontsize=14)
+    plt.legend(loc='upper right', fontsize=10)
+    plt.grid(True, alpha=0.3, which='both')
+    _save(plt, save_path, "DET curve")
+    return True
+
+
+def plot_score_distribution(results: Dict[str, Dict[str, Any]], save_path: Union[str, Path],
+                            figsize: Tuple[int, int] = (12, 5)) -> bool:
+    """Score histograms of genuine and forgery pairs per model."""
+    plt = _pyplot()
+    if plt is None:
+        return False
+    num_models = len(results)
+    fig, axes = plt.subplots(1, num_models, figsize=(figsize[0], figsize[1]))
+    if num_models == 1:
+        axes = [axes]
+    for idx, (model_name, data) in enumerate(results.items()):
+        ax = axes[idx]
+        y_true, y_scores, metrics = data['y_true'], data['y_scores'], data['metrics']
+        ax.hist(y_scores[y_true == 1], bins=30, alpha=0.7, color='#2ecc71', label='Genuine', density=True,
+                edgecolor='black', linewidth=0.5)
+        ax.hist(y_scores[y_true == 0], bins=30, alpha=0.7, color='#e74c3c', label='Forgery', density=True,
+                edgecolor='black', linewidth=0.5)
+        threshold = metrics.get('eer_threshold', 0.5)
+        ax.axvline(x=threshold, color='#3498db', linestyle='--', linewidth=2, label=f'EER Threshold ({threshold:.3f})')
+        ax.set_xlabel('Similarity Score', fontsize=11)
+        ax.set_ylabel('Density', fontsize=11)
+        ax.set_title(f'{model_name}\nEER: {metrics["eer"]:.4f}', fontsize=12)
+        ax.legend(loc='upper right', fontsize=9)
+        ax.grid(True, alpha=0.3)
+    plt.tight_layout()
+    _save(plt, save_path, "Score distribution")
+    return True
+
+
+def plot_comparison_bar_chart(results: Dict[str, Dict[str, Any]], save_path: Union[str, Path],
+                              figsize: Tuple[int, int] = (12, 6)) -> bool:
+    """Bar chart of the key metrics across models."""
+    plt = _pyplot()
+    if plt is None:
+        return False
+    metrics_to_plot = ['accuracy', 'far', 'frr', 'eer', 'roc_auc', 'f1_score']
+    metric_labels = ['Accuracy', 'FAR', 'FRR', 'EER', 'ROC-AUC', 'F1 Score']
+    model_names = list(results.keys())
+    num_models = len(model_names)
+    x = np.arange(len(metrics_to_plot))
+    width = 0.35 if num_models == 2 else 0.25
+    fig, ax = plt.subplots(figsize=figsize)
+    for idx, model_name in enumerate(model_names):
+        values = [results[model_name]['metrics'][m] for m in metrics_to_plot]
+        offset = (idx - (num_models - 1) / 2) * width
+        bars = ax.bar(x + offset, values, width, label=model_name, color=_COLORS[idx % 4], edgecolor='black', linewidth=0.5)
+        for bar, val in zip(bars, values):
+            ax.annotate(f'{val:.3f}', xy=(bar.get_x() + bar.get_width() / 2, bar.get_height()), xytext=(0, 3),
+                        textcoords="offset points", ha='center', va='bottom', fontsize=8)
+    ax.set_xlabel('Metric', fontsize=12)
+    ax.set_ylabel('Value', fontsize=12)
+    ax.set_title('Model Comparison - Signature Verification Metrics', fontsize=14)
+    ax.set_xticks(x)
+    ax.set_xticklabels(metric_labels, fontsize=10)
+    ax.legend(loc='upper right', fontsize=10)
+    ax.set_ylim(0, 1.15)
+    ax.grid(True, alpha=0.3, axis='y')
+    plt.tight_layout()
+    _save(plt, save_path, "Comparison bar chart")
+    return True
+
+
+# =============================================================================
+# Report Generation
+# =============================================================================
+
+
+def generate_evaluation_report(results: Dict[str, Dict[str, Any]], output_path: Union[str, Path]) -> Dict[str, Any]:
+    """Write the evaluation report (JSON) and return it."""
+    report = {
+        'evaluation_timestamp': datetime.now().isoformat(),
+        'num_models_evaluated': len(results),
+        'models': {}
+    }
+    for model_name, data in results.items():
+        report['models'][model_name] = {
+            'model_metadata': data.get('metadata', {}),
+            'metrics': data['metrics'],
+            'num_test_samples': len(data['y_true']),
+            'genuine_samples': int(np.sum(data['y_true'] == 1)),
+            'forgery_samples': int(np.sum(data['y_true'] == 0)),
+        }
+
+    if len(results) > 1:
+        comparison = {}
+        higher_is_better = ['accuracy', 'roc_auc', 'f1_score']
+        for metric in ['accuracy', 'far', 'frr', 'eer', 'roc_auc', 'f1_score']:
+            values = {name: data['metrics'][metric] for name, data in results.items()}
+            pick = max if metric in higher_is_better else min
+            comparison[metric] = {'values': values, 'best_model': pick(values.keys(), key=lambda k: values[k]),
+                                  'improvement': None}
+            if 'Baseline' in values and 'Augmented' in values:
+                baseline_val, augmented_val = values['Baseline'], values['Augmented']
+                if metric in higher_is_better:
+                    improvement = ((augmented_val - baseline_val) / baseline_val * 100) if baseline_val != 0 else 0
+                else:
+                    improvement = ((baseline_val - augmented_val) / baseline_val * 100) if baseline_val != 0 else 0
+                comparison[metric]['improvement'] = f"{improvement:+.2f}%"
+        report['comparison_summary'] = comparison
+
+    output_path = Path(output_path)
+    output_path.parent.mkdir(parents=True, exist_ok=True)
+    with open(output_path, 'w', encoding='utf-8') as f:
+        json.dump(report, f, indent=2, ensure_ascii=False)
+    print(f"[Report] Evaluation report saved to: {output_path}")
+    return report
+
+
+def print_evaluation_summary(results: Dict[str, Dict[str, Any]]) -> None:
+    """Print a formatted summary of evaluation results to console."""
+    print("\n" + "=" * 70)
+    print("SIGNATURE VERIFICATION EVALUATION SUMMARY")
+    print("=" * 70)
+
+    for model_name, data in results.items():
+        metrics = data['metrics']
+        print(f"\n{model_name.upper()}")
+        print("-" * 40)
+        print(f"  Accuracy:     {metrics['accuracy']:.4f}")
+        print(f"  FAR:          {metrics['far']:.4f}")
+        print(f"  FRR:          {metrics['frr']:.4f}")
+        print(f"  EER:          {metrics['eer']:.4f}")
+        print(f"  ROC-AUC:      {metrics['roc_auc']:.4f}")
+        print(f"  F1 Score:     {metrics['f1_score']:.4f}")
+        print(f"  Precision:    {metrics['precision']:.4f}")
+        print(f"  Recall:       {metrics['recall']:.4f}")
+        print(f"  Specificity:  {metrics['specificity']:.4f}")
+        print(f"  EER Threshold:{metrics['eer_threshold']:.4f}")
+        print(f"  Confusion Matrix:")
+        print(f"    TP: {metrics['true_positives']}, TN: {metrics['true_negatives']}")
+        print(f"    FP: {metrics['false_positives']}, FN: {metrics['false_negatives']}")
+
+    if len(results) > 1:
+        print("\n" + "-" * 70)
+        print("MODEL COMPARISON")
+        print("-" * 70)
+        model_names = list(results.keys())
+        header = f"{'Metric':<15}"
+        for name in model_names:
+            header += f"{name:<15}"
+        header += "Winner"
+        print(header)
+        print("-" * len(header))
+        for metric in ['accuracy', 'far', 'frr', 'eer', 'roc_auc']:
+            row = f"{metric.upper():<15}"
+            values = []
+            for name in model_names:
+                val = results[name]['metrics'][metric]
+                values.append(val)
+                row += f"{val:<15.4f}"
+            winner_idx = np.argmax(values) if metric in ['accuracy', 'roc_auc'] else np.argmin(values)
+            row += model_names[winner_idx]
+            print(row)
+
+    print("\n" + "=" * 70)
+
+
+# =============================================================================
+# Main Evaluation Pipeline
+# =============================================================================
+
+
+def evaluate_signature_verifier(
+    baseline_model_path: Optional[str],
+    augmented_model_path: Optional[str],
+    test_dir: str,
+    output_dir: str,
+    batch_size: int = 32,
+    pairs_per_user: int = 20,
+    threshold: float = 0.5,
+    device: Optional[str] = None
+) -> Dict[str, Any]:
+    """Run the complete signature verification evaluation pipeline; returns the report dictionary."""
+    if device is None:
+        device = 'cuda' if torch.cuda.is_available() else 'cpu'
+    device = torch.device(device)
+    if device.type != "cuda":
+        raise RuntimeError(f"evaluate_signature_verifier: the verifier {_NO_CPU}")
+    print(f"[Setup] Using device: {device}")
+
+    output_path = Path(output_dir)
+    output_path.mkdir(parents=True, exist_ok=True)
+
+    print("\n[Setup] Loading test dataset...")
+    test_dataset = SignatureTestDataset(test_dir=test_dir, pairs_per_user=pairs_per_user)
+    if len(test_dataset) == 0:
+        raise ValueError(f"No test pairs generated from: {test_dir}")
+    test_loader = DataLoader(test_dataset, batch_size=batch_size, shuffle=False, num_workers=0)
+
+    results: Dict[str, Dict[str, Any]] = {}
+    for name, path in (('Baseline', baseline_model_path), ('Augmented', augmented_model_path)):
+        if not path:
+            continue
+        print("\n" + "=" * 50)
+        print(f"Evaluating {name.upper()} Model")
+        print("=" * 50)
+        model, metadata = load_model(path, device)
+        metrics, y_true, y_scores, y_pred = evaluate_model(model, test_loader, device, threshold)
+        results[name] = {'metrics': metrics, 'y_true': y_true, 'y_scores': y_scores, 'y_pred': y_pred, 'metadata': metadata}
+
+    if not results:
+        raise ValueError("At least one model path must be provided for evaluation.")
+
+    print_evaluation_summary(results)
+
+    print("\n[Plots] Generating visualizations...")
+    plotted = plot_roc_curve(results, output_path / 'roc_curve.png')
+    if plotted:
+        plot_det_curve(results, output_path / 'det_curve.png')
+        plot_score_distribution(results, output_path / 'score_distribution.png')
+        if len(results) > 1:
+            plot_comparison_bar_chart(results, output_path / 'comparison_metrics.png')
+    else:
+        print("[Plot] skipped (matplotlib not available)")
+
+    report = generate_evaluation_report(results, output_path / 'evaluation_report.json')
+
+    print("\n" + "=" * 50)
+    print("EVALUATION COMPLETE")
+    print("=" * 50)
+    print(f"Output directory: {output_path}")
+    if plotted:
+        print(f"  - ROC curve: roc_curve.png")
+        print(f"  - DET curve: det_curve.png")
+        print(f"  - Score distribution: score_distribution.png")
+        if len(results) > 1:
+            print(f"  - Comparison chart: comparison_metrics.png")
+    print(f"  - Report: evaluation_report.json")
+    return report
+
+
+def main() -> None:
+    """Main entry point with CLI argument parsing."""
+    parser = argparse.ArgumentParser(
+        description='Evaluate trained Siamese network models for signature verification',
+        formatter_class=argparse.ArgumentDefaultsHelpFormatter
+    )
+    parser.add_argument('--baseline_model', type=str, default=None,
+                        help='Path to baseline Siamese model checkpoint (.pth file)')
+    parser.add_argument('--augmented_model', type=str, default=None,
+                        help='Path to augmented (GAN-enhanced) Siamese model checkpoint (.pth file)')
+    parser.add_argument('--test_dir', type=str, required=True,
+                        help='Directory containing test signature images (organized by user)')
+    parser.add_argument('--output_dir', type=str, default='./evaluation_results',
+                        help='Directory to save evaluation outputs (plots, report)')
+    parser.add_argument('--batch_size', type=int, default=32, help='Batch size for evaluation')
+    parser.add_argument('--pairs_per_user', type=int, default=20,
+                        help='Number of genuine/forgery pairs to generate per user')
+    parser.add_argument('--threshold', type=float, default=0.5, help='Decision threshold for binary classification')
+    parser.add_argument('--device', type=str, default=None, choices=['cuda', 'cpu'],
+                        help='Device to run evaluation on (default: auto-detect)')
+    args = parser.parse_args()
+
+    if not args.baseline_model and not args.augmented_model:
+        parser.error("At least one of --baseline_model or --augmented_model must be provided")
+    if args.device == 'cpu':
+        parser.error(f"--device cpu: the verifier {_NO_CPU}")
+
+    print("=" * 70)
+    print("SIGNATURE VERIFICATION MODEL EVALUATION")
+    print("=" * 70)
+    print(f"Baseline model:  {args.baseline_model or 'Not provided'}")
+    print(f"Augmented model: {args.augmented_model or 'Not provided'}")
+    print(f"Test directory:  {args.test_dir}")
+    print(f"Output directory:{args.output_dir}")
+    print(f"Batch size:      {args.batch_size}")
+    print(f"Pairs per user:  {args.pairs_per_user}")
+    print(f"Threshold:       {args.threshold}")
+    print("=" * 70)
+
+    evaluate_signature_verifier(
+        baseline_model_path=args.baseline_model,
+        augmented_model_path=args.augmented_model,
+        test_dir=args.test_dir,
+        output_dir=args.output_dir,
+        batch_size=args.batch_size,
+        pairs_per_user=args.pairs_per_user,
+        threshold=args.threshold,
+        device=args.device
+    )
+
+
+if __name__ == '__main__':
+    main()
