@@ -127,12 +127,71 @@ struct PhaseKey {
     int ride;         // D apply: ... and runs the first Discriminator block of the pending G step's `ride` images (its riders)
     int rode;         // G grads: the preceding D apply did
     float ls, clip, gs;
+    // what an earlier call left in flight, as far as THIS phase reads it (Carried, below; 0 where the phase does not look)
+    int dreal_joined, dreal_noise2, lP0;   // pre_real == 2: the staged D(real) forward's lane state and its classifier form
+    int gfwd_joined;                       // G grads after step_begin / D apply with riders: ev_gfwd was already waited for
+    int early_ar;                          // D apply: the tail of the bucket is already being reduced
+    const float* staged_src;               // pre_real: where the staged real batch lies
     bool operator==(const PhaseKey& o) const {
         return phase == o.phase && B == o.B && has_z == o.has_z && has_masks == o.has_masks && g_dirty == o.g_dirty &&
                d_dirty == o.d_dirty && spec_g == o.spec_g && has_zg == o.has_zg && pre_real == o.pre_real && variant == o.variant && coll == o.coll && mt == o.mt && lr == o.lr && beta1 == o.beta1 && beta2 == o.beta2 && eps == o.eps && ls == o.ls &&
-               clip == o.clip && gs == o.gs && fused_t == o.fused_t && pack == o.pack && ride == o.ride && rode == o.rode;
+               clip == o.clip && gs == o.gs && fused_t == o.fused_t && pack == o.pack && ride == o.ride && rode == o.rode &&
+               dreal_joined == o.dreal_joined && dreal_noise2 == o.dreal_noise2 && lP0 == o.lP0 && gfwd_joined == o.gfwd_joined &&
+               early_ar == o.early_ar && staged_src == o.staged_src;
     }
 };
+
+// What one training step leaves in flight for the next C-ABI call.  Three kinds of code write it and no other: the entry
+// points (their own bookkeeping), run_phase (commits a phase's PhaseResult -- eagerly after the enqueue, on every replay in
+// graph mode) and invalidate() (whatever makes work in flight worthless).  The phase bodies only enqueue: they see the context
+// as const, read carried state through their PhaseKey and report what they left behind in their PhaseResult.
+//
+//   field          set by                                    consumed by                              invalidated by
+//   pending        *_grads (1 D, 2 G)                        *_apply (-> 0), set_step_variant         rebind
+//   metrics_last   *_grads                                   *_apply (the step's one metrics buffer)  --
+//   staged_B/_src  stage_real                                d_grads (-> 0), g_grads (pre_real)       rebind (src: with B)
+//   dreal_B        g_grads that ran D(real) ahead            d_grads (pre_real 2, -> 0)               drop_dreal: every reason but comm
+//   dreal_orphan   drop_dreal                                settle (next enqueue waits for ev_dreal) --
+//   dreal_joined   phase G grads (16-bit: lane c joined)     phase D grads (-> 0)                     --
+//   dreal_noise2   phase G grads (drew D(fake)'s tables)     phase D grads (-> 0)                     --
+//   g_fwd_pending  step_begin (G forward enqueued)           g_grads (-> 0), D apply (riders)         --
+//   gfwd_joined    phase D grads, phase D apply (riders)     phase G grads (-> 0)                     --
+//   zg_stash       step_begin that could not pipeline        g_grads (-> 0)                           --
+//   conv1_rode     D apply (riders ran block 1)              g_grads (-> 0)                           weights, rows, rebind
+//   abl_masks      d_grads (ablation, explicit masks)        g_grads (-> 0)                           --
+//   early_ar       phase D grads (tail all-reduce started)   phase D apply (-> 0)                     weights, rebind, comm
+//   lP[2]          every d_forward_rows (phases, d_forward)  the next phase D grads (lP[0], pre_real 2)  --
+//   g_r0           phase G grads                             debug_tensor("d_a_g")                    --
+//   ga_last_B      every Generator forward                   debug_tensor("g_a", Lg)                  --
+//   g_rode, g_pre_real  g_grads                              debug_tensor("rode" / "pre_real")        --
+struct Carried {
+    int pending;         // last *_grads call (for *_apply): 0 none, 1 D, 2 G
+    float* metrics_last; // metrics target of the last *_grads call
+    int staged_B;        // batch of a real batch staged for the NEXT D step by siggan_stage_real (0: none)
+    const float* staged_src;   // where that batch lies: the caller's own tensor (borrowed until the D step that consumes it)
+    int dreal_B;         // batch whose D(real) forward siggan_g_grads already enqueued on lane c (0: none)
+    bool dreal_orphan;   // a D(real) forward enqueued on lane c was abandoned: the next enqueue waits for ev_dreal first
+    bool dreal_joined;   // the lane of that early forward was already joined into the caller's stream (end of the G step)
+    bool dreal_noise2;   // its launch also drew the dropout tables of the D(fake) pass
+    int g_fwd_pending;   // batch of a Generator training forward already enqueued by siggan_step_begin (0: none)
+    bool gfwd_joined;    // the pipelined Generator forward's lane was already joined into the caller's stream (end of the D grads phase)
+    int zg_stash;        // batch of an explicit G-step z handed to siggan_step_begin when the forward was not pipelined
+    int conv1_rode;      // batch whose first-Discriminator-block forward (workspace rows [B, 2B), updated weights) the last D apply ran
+    bool abl_masks;      // ablation step: the D half was given explicit masks, the third set waits in mask_stage for the G half
+    bool early_ar;       // the last D block's weight gradient is already being all-reduced on s_n (ev_ar marks its end)
+    int lP[2];           // partial classifier dot products per image of workspace half h, left in lparts by the last block's
+                         //   split-K epilogue (0: that half's logits are in `logits`, written by k_cls_fwd)
+    int g_r0;            // first workspace row of the Discriminator pass of the last G step (0, or B: beside an early D(real))
+    int ga_last_B;       // batch of the last TRAINING Generator forward: the last block's activation was not materialised
+                         // (siggan_debug_tensor("g_a", Lg) forms it on demand)
+    int g_rode, g_pre_real;    // what the last siggan_g_grads did (test hook "rode" / "pre_real"): batch whose first-block rows
+                               // the riders had run (0: none), batch whose D(real) it started ahead (0: none)
+};
+// The carried fields a phase body produces; < 0: the phase left that one as it was.
+struct PhaseResult {
+    int early_ar = -1, dreal_joined = -1, dreal_noise2 = -1, gfwd_joined = -1, g_r0 = -1, ga_last_B = -1, lP[2] = {-1, -1};
+};
+struct CachedPhase { PhaseKey key; hipGraphExec_t exec; PhaseResult res; };
 
 struct siggan_ctx {
     siggan_config cfg;
@@ -143,7 +202,6 @@ struct siggan_ctx {
     SnTable snt;        // its layer table (pointers into the bound arenas are refreshed by siggan_bind)
     float *sn_tbuf, *sn_wbuf, *sn_sig, *sn_us, *sn_vs, *sn_dots, *sn_g[2], *d_w1s;
     int variant;        // SIGGAN_STEP_TRAINER / SIGGAN_STEP_ABLATION (siggan_set_step_variant)
-    bool abl_masks;     // ablation step: the D half was given explicit masks, the third set waits in mask_stage for the G half
     bool fc_fused;      // Generator.fc runs as the one-launch MFMA kernels of fc.hip (max_batch <= 256, latent % 4 == 0)
     float gscale;       // gradient scale of the backward chains (fp16: keeps small gradients out of the subnormals; else 1)
     int gC[MAXL + 1];   // generator channel chain gC[0..Lg]  (generator_vanilla_gan.py:131-149)
@@ -166,51 +224,32 @@ struct siggan_ctx {
     char *d_a[MAXL + 1], *d_dv[MAXL + 1];
     float *d_noise[MAXL + 1];
     float *logits, *probs, *dlogit;
-    float* lparts;       // partial classifier dot products left by the last block's split-K epilogue: lP[h] per image of workspace half h
-    int lP[2];           //   (0: that half's logits are in `logits`, written by k_cls_fwd)
+    float* lparts;       // partial classifier dot products left by the last block's split-K epilogue (Carried::lP per image)
     char *g_up[MAXL + 1], *g_dn[MAXL + 1], *d_dn[MAXL + 1], *d_up[MAXL + 1];
     float *wcp;
     float *slab, *slab_k, *slab_k2, *slab_k3, *partial, *partial_b, *partial_c, *z_g, *img_g, *metrics, *zeros, *wfc_t, *wfin_t, *d_w1t, *real_stage, *mask_stage;
     char *op_pack;
     int64_t slab_floats, slab_k_floats;
     DevState* dev;
-    // last *_grads call (for *_apply)
-    int pending;   // 0 none, 1 D, 2 G
-    float* metrics_last;   // metrics target of the last *_grads call
+    Carried cs;          // what is in flight between two calls (the table above)
     // lanes / graphs
     static constexpr int NEV = 96;
     int mode;
     hipStream_t s_m, s_a, s_b, s_c, s_n;      // s_n: the lane of an all-reduce issued while the backward pass is still running
     hipEvent_t ev_gfwd, ev_dreal, ev_ar, ev_sys[2];
-    bool early_ar;       // the last D block's weight gradient is already being all-reduced on s_n (ev_ar marks its end)
-    bool dreal_orphan;   // a D(real) forward enqueued on lane c was abandoned: the next enqueue waits for ev_dreal first
     hipError_t lane_err; // first failed event record / wait of a fork or join (checked after every phase)
     const char* refused; // sticky: a launcher refused a launch of a step (nothing was enqueued for it; lane_check reports it)
     // data-parallel communicator (siggan_comm_init): world 1 = none
     ncclComm_t comm; int comm_rank, comm_world; int comm_err;
-    int staged_B;        // batch of a real batch staged for the NEXT D step by siggan_stage_real (0: none)
-    bool gfwd_joined;    // the pipelined Generator forward's lane was already joined into the caller's stream (end of the D grads phase)
-    bool dreal_joined;   // the lane of that early forward was already joined into the caller's stream (end of the G step)
-    bool dreal_noise2;   // its launch also drew the dropout tables of the D(fake) pass
     float* slab_b;       // second weight-gradient slab region (a weight gradient on the main lane beside lane a's)
-    const float* staged_src;   // where that batch lies: the caller's own tensor (borrowed until the D step that consumes it)
-    int dreal_B;         // batch whose D(real) forward siggan_g_grads already enqueued on lane c (0: none)
-    int zg_stash;        // batch of an explicit G-step z handed to siggan_step_begin when the forward was not pipelined
-    int g_fwd_pending;   // batch of a Generator training forward already enqueued by siggan_step_begin (0: none)
-    int conv1_rode;      // batch whose first-Discriminator-block forward (workspace rows [B, 2B), updated weights) the last D apply ran
     float* ride_ctr;     // k_adam_pack's rider count (one word, zero between launches)
     unsigned* ride_late; // host-visible, sticky: a k_adam_pack owner stopped waiting for its riders (lane_check reports it)
     unsigned* ride_late_dev;   // (the same word as the device addresses it)
-    int g_rode, g_pre_real;    // what the last siggan_g_grads did (test hook "rode" / "pre_real"): batch whose first-block rows
-                               // the riders had run (0: none), batch whose D(real) it started ahead (0: none)
     double adam_t[2];    // step count of the network's Adam state as the HOST knows it ([0] G, [1] D); valid while adam_t_known
     bool adam_t_known[2];// (reset by siggan_bind / siggan_params_changed: the caller may have written the step tensors)
-    int g_r0;            // first workspace row of the Discriminator pass of the last G step (0, or B: beside an early D(real))
-    int ga_last_B;       // batch of the last TRAINING Generator forward: the last block's activation was not materialised
-                         // (siggan_debug_tensor("g_a", Lg) forms it on demand)
     hipEvent_t ev[NEV], ev_fenced[NEV], ev_bridge[2];   // ev_fenced: the same ring with the system-scope fence (used while a communicator exists)
     int evi;
-    std::vector<std::pair<PhaseKey, hipGraphExec_t>> graphs;
+    std::vector<CachedPhase> graphs;
 };
 
 // parameter tensor indices
@@ -269,6 +308,44 @@ static void build_layout(siggan_ctx* c) {
     for (int l = 1; l <= c->Lg; ++l) { c->g_bn_off[l] = c->bn_total; c->bn_total += c->gC[l]; }
 }
 
+// A D(real) forward that siggan_g_grads started ahead of time on lane c (siggan_stage_real) and that no D step will
+// consume still reads the staged batch, the D weight packs and slab_k2 and writes activation rows [0,B): whoever
+// abandons it marks it orphaned, and the next call that enqueues anything first makes its stream wait for that lane.
+static void drop_dreal(siggan_ctx* c) {
+    if (c->cs.dreal_B) { c->cs.dreal_orphan = true; c->cs.dreal_B = 0; }
+}
+static int settle(siggan_ctx* c, hipStream_t s) {
+    if (c->cs.dreal_orphan) {
+        HIPCHK(hipStreamWaitEvent(s, c->ev_dreal, 0));
+        c->cs.dreal_orphan = false;
+    }
+    return SIGGAN_OK;
+}
+// The ONE place that says what an outside event makes worthless.  The ORDER matters: each reason down to INV_STREAM also
+// drops everything the reasons below it drop (the switch falls through), so a field added to one reason is dropped by every
+// reason above it as well -- put it at the lowest reason that must drop it.
+enum Inval {
+    INV_INIT,      // siggan_create: nothing in flight, nothing derived from the arenas yet
+    INV_REBIND,    // siggan_bind: ... a pending *_apply and a staged batch belonged to the old arenas
+    INV_WEIGHTS,   // siggan_params_changed: ... packs / eval tables are stale, the caller may have written the Adam step tensors,
+                   //   an early all-reduce whose apply never ran is abandoned with the gradients it covered
+    INV_ROWS,      // siggan_d_forward: ... the rows of a first-block forward the last D apply ran ahead are overwritten (or used old weights)
+    INV_STREAM,    // siggan_seed (dropout tables drawn from the old RNG stream) / siggan_stage_real (the staged batch is replaced):
+                   //   a D(real) forward started ahead of time is abandoned
+    INV_COMM,      // siggan_comm_destroy: only the early all-reduce
+};
+static void invalidate(siggan_ctx* c, Inval why) {
+    Carried& cs = c->cs;
+    switch (why) {
+    case INV_INIT:    cs = Carried{};                                                  [[fallthrough]];
+    case INV_REBIND:  cs.pending = 0; cs.staged_B = 0;                                 [[fallthrough]];
+    case INV_WEIGHTS: c->g_dirty = c->d_dirty = true; c->adam_t_known[0] = c->adam_t_known[1] = false; cs.early_ar = false; [[fallthrough]];
+    case INV_ROWS:    cs.conv1_rode = 0;                                               [[fallthrough]];
+    case INV_STREAM:  drop_dreal(c); break;
+    case INV_COMM:    cs.early_ar = false; break;
+    }
+}
+
 extern "C" int siggan_create(const siggan_config* cfg, siggan_ctx** out) {
     if (!cfg || !out) return fail(SIGGAN_E_INVALID, "null argument");
     if (cfg->image_size != 64 && cfg->image_size != 128)
@@ -290,12 +367,13 @@ extern "C" int siggan_create(const siggan_config* cfg, siggan_ctx** out) {
     c->cfg = *cfg; c->S = cfg->image_size; c->latent = cfg->latent_dim; c->Bm = cfg->max_batch;
     c->dt = cfg->dtype; c->es = dt_size(c->dt);
     c->fc_fused = cfg->max_batch <= 256 && (cfg->latent_dim & 3) == 0;
-    c->variant = SIGGAN_STEP_TRAINER; c->abl_masks = false;
+    c->variant = SIGGAN_STEP_TRAINER;
     c->sn = cfg->spectral_norm != 0;
     // fp16 stores activation gradients of order 1e-7..1e-3: a power-of-two scale (exact to apply and to remove) lifts
     // them clear of the fp16 subnormals; bf16 has fp32's exponent range and needs none
     c->gscale = c->dt == DT_F16 ? (cfg->f16_grad_scale > 0.f ? cfg->f16_grad_scale : 1024.f) : 1.0f;
-    c->bound = false; c->g_dirty = c->d_dirty = true; c->pending = 0; c->metrics_last = nullptr;
+    c->bound = false;
+    invalidate(c, INV_INIT);
     build_layout(c);
 
     // ---- workspace carve (two passes: size, then assign) ----------------------------------
@@ -399,18 +477,11 @@ extern "C" int siggan_create(const siggan_config* cfg, siggan_ctx** out) {
     HIPCHK(hipEventCreateWithFlags(&c->ev_dreal, EV_FLAGS));
     HIPCHK(hipEventCreateWithFlags(&c->ev_ar, hipEventDisableTiming));
     for (int i = 0; i < 2; ++i) HIPCHK(hipEventCreateWithFlags(&c->ev_sys[i], hipEventDisableTiming));
-    c->early_ar = false;
-    c->staged_B = c->dreal_B = 0; c->staged_src = nullptr; c->dreal_joined = c->dreal_noise2 = c->gfwd_joined = false;
-    c->dreal_orphan = false; c->lane_err = hipSuccess;
+    c->lane_err = hipSuccess;
     c->comm = nullptr; c->comm_rank = 0; c->comm_world = 1; c->comm_err = 0;
-    c->g_fwd_pending = 0; c->conv1_rode = 0;
-    c->g_rode = c->g_pre_real = 0;
     HIPCHK(hipHostMalloc((void**)&c->ride_late, sizeof(unsigned), hipHostMallocCoherent | hipHostMallocMapped));
     *c->ride_late = 0u;
     HIPCHK(hipHostGetDevicePointer((void**)&c->ride_late_dev, c->ride_late, 0));
-    c->zg_stash = 0;
-    c->ga_last_B = 0; c->g_r0 = 0;
-    c->adam_t_known[0] = c->adam_t_known[1] = false;
     for (int i = 0; i < siggan_ctx::NEV; ++i) HIPCHK(hipEventCreateWithFlags(&c->ev[i], EV_FLAGS));
     for (int i = 0; i < siggan_ctx::NEV; ++i) HIPCHK(hipEventCreateWithFlags(&c->ev_fenced[i], hipEventDisableTiming));
     for (int i = 0; i < 2; ++i) HIPCHK(hipEventCreateWithFlags(&c->ev_bridge[i], hipEventDisableTiming));
@@ -423,7 +494,7 @@ extern "C" int siggan_destroy(siggan_ctx* c) {
     DevGuard dg(c->cfg.device);
     (void)hipDeviceSynchronize();
     if (c->comm) { (void)rccl()->CommDestroy(c->comm); c->comm = nullptr; }
-    for (auto& e : c->graphs) (void)hipGraphExecDestroy(e.second);
+    for (auto& e : c->graphs) (void)hipGraphExecDestroy(e.exec);
     for (int i = 0; i < siggan_ctx::NEV; ++i) if (c->ev[i]) (void)hipEventDestroy(c->ev[i]);
     for (int i = 0; i < siggan_ctx::NEV; ++i) if (c->ev_fenced[i]) (void)hipEventDestroy(c->ev_fenced[i]);
     for (int i = 0; i < 2; ++i) if (c->ev_bridge[i]) (void)hipEventDestroy(c->ev_bridge[i]);
@@ -464,20 +535,6 @@ extern "C" int64_t siggan_sn_count(const siggan_ctx* c, int which) {
 extern "C" int32_t siggan_bn_layers(const siggan_ctx* c) { return c ? c->Lg + 1 : -1; }
 extern "C" int64_t siggan_workspace_bytes(const siggan_ctx* c) { return c ? (int64_t)c->ws_bytes : -1; }
 
-// A D(real) forward that siggan_g_grads started ahead of time on lane c (siggan_stage_real) and that no D step will
-// consume still reads the staged batch, the D weight packs and slab_k2 and writes activation rows [0,B): whoever
-// abandons it marks it orphaned, and the next call that enqueues anything first makes its stream wait for that lane.
-static void drop_dreal(siggan_ctx* c) {
-    if (c->dreal_B) { c->dreal_orphan = true; c->dreal_B = 0; }
-}
-static int settle(siggan_ctx* c, hipStream_t s) {
-    if (c->dreal_orphan) {
-        HIPCHK(hipStreamWaitEvent(s, c->ev_dreal, 0));
-        c->dreal_orphan = false;
-    }
-    return SIGGAN_OK;
-}
-
 extern "C" int siggan_bind(siggan_ctx* c, const siggan_storage* st) {
     if (!c || !st) return fail(SIGGAN_E_INVALID, "null argument");
     const void* need[] = {st->g_params, st->g_bn_running_mean, st->g_bn_running_var, st->d_params};
@@ -507,19 +564,13 @@ extern "C" int siggan_bind(siggan_ctx* c, const siggan_storage* st) {
         t.u = st->d_sn_u; t.v = st->d_sn_v; t.tbuf = c->sn_tbuf; t.wbuf = c->sn_wbuf; t.sig = c->sn_sig;
         t.u_saved = c->sn_us; t.v_saved = c->sn_vs; t.dots = c->sn_dots; t.u_total = uo; t.v_total = vo;
     }
-    c->bound = true; c->g_dirty = c->d_dirty = true; c->pending = 0; c->staged_B = 0; c->conv1_rode = 0;
-    c->adam_t_known[0] = c->adam_t_known[1] = false;
-    c->early_ar = false;               // (an early all-reduce whose apply never ran is abandoned with the gradients it covered)
-    drop_dreal(c);
+    c->bound = true;
+    invalidate(c, INV_REBIND);
     return SIGGAN_OK;
 }
 extern "C" int siggan_params_changed(siggan_ctx* c) {
     if (!c) return fail(SIGGAN_E_INVALID, "null context");
-    c->g_dirty = c->d_dirty = true;
-    c->conv1_rode = 0;                 // (a first-block forward the last D apply ran ahead used the old weights too)
-    c->adam_t_known[0] = c->adam_t_known[1] = false;      // (optimizer.load_state_dict writes the step tensors)
-    c->early_ar = false;
-    drop_dreal(c);                     // a D(real) forward started ahead of time used the old weights
+    invalidate(c, INV_WEIGHTS);        // (optimizer.load_state_dict writes the step tensors too)
     return SIGGAN_OK;
 }
 extern "C" int siggan_seed(siggan_ctx* c, uint64_t seed, uint64_t offset) {
@@ -527,7 +578,7 @@ extern "C" int siggan_seed(siggan_ctx* c, uint64_t seed, uint64_t offset) {
     DevGuard dg_(c->cfg.device); HIPCHK(dg_.err);
     unsigned long long v[2] = {seed, offset};
     HIPCHK(hipMemcpy(c->dev, v, sizeof v, hipMemcpyHostToDevice));   // seed, rng_ctr are the first two fields
-    drop_dreal(c);                     // its dropout tables were drawn from the old stream
+    invalidate(c, INV_STREAM);
     return SIGGAN_OK;
 }
 
@@ -559,11 +610,69 @@ static int check_call(siggan_ctx* c, int batch, bool need_bound = true) {
     return SIGGAN_OK;
 }
 
+// ------------------------------------------------------------------------------------------
+// lanes: where a phase enqueues its kernels.  m is the main lane; a and b are side lanes that run
+// independent work (weight gradients, bias / BatchNorm reductions) beside the main chain.  With
+// overlap off all three are the same stream and fork/join are no-ops.  Forks and joins are plain
+// event record / wait pairs, so the same code runs eagerly and under stream capture (hipGraph).
+// ------------------------------------------------------------------------------------------
+static int lane_check(siggan_ctx* c) {
+    if (c->comm_err)      // sticky: the communicator is unusable and the replicas have diverged; cleared by siggan_comm_destroy
+        return fail(SIGGAN_E_HIP, "ncclAllReduce of the gradient bucket failed (the optimiser update was skipped): %s",
+                    rccl()->GetErrorString(c->comm_err));
+    // sticky: set by the device (k_adam_pack) when its owner of the block-1 ranges stopped waiting for the riders -- a late
+    // rider then ran the G step's first Discriminator block on weights updated twice.  Seen once that launch has run.
+    if (c->ride_late && __atomic_load_n(c->ride_late, __ATOMIC_ACQUIRE))
+        return fail(SIGGAN_E_STATE, "riders did not report: the optimiser update's owner of the first Discriminator block stopped "
+                                    "waiting for them (a G step's first block may have used twice-updated weights)");
+    if (c->refused) return fail(SIGGAN_E_STATE, "%s", c->refused);
+    if (c->lane_err == hipSuccess) return SIGGAN_OK;
+    const hipError_t e = c->lane_err; c->lane_err = hipSuccess;
+    return fail(SIGGAN_E_HIP, "an event record / stream wait / prepare table of the step failed: %s", hipGetErrorString(e));
+}
+// Lanes is also the one door through which an enqueue writes the context -- the event ring's index and the sticky
+// diagnostics lane_err / refused / comm_err; the passes see everything else as const.
+class Lanes {
+    siggan_ctx* c;
+public:
+    Lanes(siggan_ctx* c_, hipStream_t m_, hipStream_t a_, hipStream_t b_, bool ext_) : c(c_), m(m_), a(a_), b(b_), ext(ext_), tail_wait(nullptr) {}
+    Lanes(siggan_ctx* c_, hipStream_t s) : Lanes(c_, s, s, s, false) {}       // one stream: the entry points outside a step
+    hipStream_t m, a, b;
+    // ext: a fork may ride on the producing kernel's own completion signal (ops.h, SIGGAN_LAUNCH_EV) instead of a marker packet
+    // behind it -- eager launches only (not under stream capture, not with the profiler's own events on the launch)
+    bool ext;
+    hipEvent_t tail_wait;        // d_backward_pass: one more event the main lane waits for where it is idle anyway (before its last join)
+    // the event to hand the producing launch as `done` (nullptr: fork_after records one the classic way)
+    hipEvent_t fork_event(hipStream_t to) { return (ext && to != m) ? next() : nullptr; }
+    void fork_after(hipStream_t to, hipEvent_t done) {      // `to` waits for the launch that was given `done` (and all before it on m)
+        if (to == m) return;
+        if (done) note(hipStreamWaitEvent(to, done, 0)); else fork(to);
+    }
+    // with a communicator every lane event keeps its system-scope fence: peers read this device's gradient arena over xGMI
+    hipEvent_t next() { hipEvent_t e = (c->comm ? c->ev_fenced : c->ev)[c->evi]; c->evi = (c->evi + 1) % siggan_ctx::NEV; return e; }
+    void fork(hipStream_t to) {          // `to` waits for everything enqueued on m so far
+        if (to == m) return;
+        hipEvent_t e = next();
+        note(hipEventRecord(e, m)); note(hipStreamWaitEvent(to, e, 0));
+    }
+    void join(hipStream_t from) {        // m waits for everything enqueued on `from`
+        if (from == m) return;
+        hipEvent_t e = next();
+        note(hipEventRecord(e, from)); note(hipStreamWaitEvent(m, e, 0));
+    }
+    // a failed record / wait would silently drop an ordering edge: remember the first one, run_phase reports it
+    void note(hipError_t e) { if (e != hipSuccess && c->lane_err == hipSuccess) c->lane_err = e; }
+    void refuse(const char* why) { c->refused = why; }       // a launcher refused a launch (sticky, lane_check)
+    void comm_fail(int rc) { c->comm_err = rc; }             // a collective failed (sticky until siggan_comm_destroy)
+    void record(hipEvent_t e, hipStream_t s) { note(hipEventRecord(e, s)); }
+    void wait(hipStream_t s, hipEvent_t e) { note(hipStreamWaitEvent(s, e, 0)); }
+};
+
 // One launch per network rebuilds everything derived from its arena: GEMM-friendly weight copies and
 // (for G) the BatchNorm eval-mode scale/shift tables.  sg / sd: the lanes the two launches go to.
 // conv1_x != nullptr (G step, no spectral norm): the D table's launch also runs the first-block forward of conv1_B images at
 // conv1_x into workspace rows [conv1_r0, ...) -- it reads the raw block-1 weights, not a pack (launch_prepare_conv1)
-static void repack(siggan_ctx* c, hipStream_t sg, hipStream_t sd, bool do_g, bool do_d, int sn_slot = 0, const float* conv1_x = nullptr,
+static void repack(const siggan_ctx* c, Lanes& L, hipStream_t sg, hipStream_t sd, bool do_g, bool do_d, int sn_slot = 0, const float* conv1_x = nullptr,
                    int conv1_r0 = 0, int conv1_B = 0) {
     if (do_g) {
         PrepTable t; t.njobs = 0; t.overflow = 0;
@@ -593,7 +702,7 @@ static void repack(siggan_ctx* c, hipStream_t sg, hipStream_t sd, bool do_g, boo
         memset(&j, 0, sizeof j);                                       // final conv: [tap][c] for the strip kernels
         j.type = PREP_TAPS; j.I = 9; j.O = c->gC[c->Lg]; j.src = GP(c, gi_fin_w(c)); j.dst = c->wfin_t;
         prep_add(t, j, 9 * j.O);
-        if (!launch_prepare(t, BN_EPS, sg)) c->lane_err = hipErrorInvalidValue;   // table overflow: reported by the caller
+        if (!launch_prepare(t, BN_EPS, sg)) L.note(hipErrorInvalidValue);          // table overflow: reported by the caller
     }
     if (do_d) {
         PrepTable t; t.njobs = 0; t.overflow = 0;
@@ -630,14 +739,14 @@ static void repack(siggan_ctx* c, hipStream_t sg, hipStream_t sd, bool do_g, boo
         } else {
             ok = launch_prepare(t, BN_EPS, sd);
         }
-        if (!ok) c->lane_err = hipErrorInvalidValue;
+        if (!ok) L.note(hipErrorInvalidValue);
     }
 }
 
 // The job tables of the one-launch update (launch_adam_pack): the whole arena, tensor by tensor, with what launch_prepare
 // would derive from each.  false: this context keeps the two-launch path (the generic fc kernel's k-major copy, channel
 // counts the 16 x 16 tiles do not divide).
-static bool ap_table_g(siggan_ctx* c, ApTable& t) {
+static bool ap_table_g(const siggan_ctx* c, ApTable& t) {
     if (!c->fc_fused || c->gC[c->Lg] * 9 > 1024) return false;
     for (int l = 0; l <= c->Lg; ++l) if (c->gC[l] % 16) return false;
     t.njobs = 0; t.overflow = 0;
@@ -665,7 +774,7 @@ static bool ap_table_g(siggan_ctx* c, ApTable& t) {
     ap_add(t, j);
     return !t.overflow;
 }
-static bool ap_table_d(siggan_ctx* c, ApTable& t, int nride) {
+static bool ap_table_d(const siggan_ctx* c, ApTable& t, int nride) {
     if (c->sn || c->dC[1] * 16 > 1024 || c->dC[1] > 256) return false;     // (spectral norm: the packs follow sigma, not the update)
     for (int l = 1; l <= c->Ld; ++l) if (c->dC[l] % 16) return false;
     t.njobs = 0; t.overflow = 0;
@@ -692,58 +801,7 @@ static bool ap_table_d(siggan_ctx* c, ApTable& t, int nride) {
     return !t.overflow;
 }
 
-// ------------------------------------------------------------------------------------------
-// lanes: where a phase enqueues its kernels.  m is the main lane; a and b are side lanes that run
-// independent work (weight gradients, bias / BatchNorm reductions) beside the main chain.  With
-// overlap off all three are the same stream and fork/join are no-ops.  Forks and joins are plain
-// event record / wait pairs, so the same code runs eagerly and under stream capture (hipGraph).
-// ------------------------------------------------------------------------------------------
-static int lane_check(siggan_ctx* c) {
-    if (c->comm_err)      // sticky: the communicator is unusable and the replicas have diverged; cleared by siggan_comm_destroy
-        return fail(SIGGAN_E_HIP, "ncclAllReduce of the gradient bucket failed (the optimiser update was skipped): %s",
-                    rccl()->GetErrorString(c->comm_err));
-    // sticky: set by the device (k_adam_pack) when its owner of the block-1 ranges stopped waiting for the riders -- a late
-    // rider then ran the G step's first Discriminator block on weights updated twice.  Seen once that launch has run.
-    if (c->ride_late && __atomic_load_n(c->ride_late, __ATOMIC_ACQUIRE))
-        return fail(SIGGAN_E_STATE, "riders did not report: the optimiser update's owner of the first Discriminator block stopped "
-                                    "waiting for them (a G step's first block may have used twice-updated weights)");
-    if (c->refused) return fail(SIGGAN_E_STATE, "%s", c->refused);
-    if (c->lane_err == hipSuccess) return SIGGAN_OK;
-    const hipError_t e = c->lane_err; c->lane_err = hipSuccess;
-    return fail(SIGGAN_E_HIP, "an event record / stream wait / prepare table of the step failed: %s", hipGetErrorString(e));
-}
-struct Lanes {
-    siggan_ctx* c;
-    hipStream_t m, a, b;
-    // ext: a fork may ride on the producing kernel's own completion signal (ops.h, SIGGAN_LAUNCH_EV) instead of a marker packet
-    // behind it -- eager launches only (not under stream capture, not with the profiler's own events on the launch)
-    bool ext;
-    hipEvent_t tail_wait;        // d_backward_pass: one more event the main lane waits for where it is idle anyway (before its last join)
-    // the event to hand the producing launch as `done` (nullptr: fork_after records one the classic way)
-    hipEvent_t fork_event(hipStream_t to) { return (ext && to != m) ? next() : nullptr; }
-    void fork_after(hipStream_t to, hipEvent_t done) {      // `to` waits for the launch that was given `done` (and all before it on m)
-        if (to == m) return;
-        if (done) note(hipStreamWaitEvent(to, done, 0)); else fork(to);
-    }
-    // with a communicator every lane event keeps its system-scope fence: peers read this device's gradient arena over xGMI
-    hipEvent_t next() { hipEvent_t e = (c->comm ? c->ev_fenced : c->ev)[c->evi]; c->evi = (c->evi + 1) % siggan_ctx::NEV; return e; }
-    void fork(hipStream_t to) {          // `to` waits for everything enqueued on m so far
-        if (to == m) return;
-        hipEvent_t e = next();
-        note(hipEventRecord(e, m)); note(hipStreamWaitEvent(to, e, 0));
-    }
-    void join(hipStream_t from) {        // m waits for everything enqueued on `from`
-        if (from == m) return;
-        hipEvent_t e = next();
-        note(hipEventRecord(e, from)); note(hipStreamWaitEvent(m, e, 0));
-    }
-    // a failed record / wait would silently drop an ordering edge: remember the first one, run_phase reports it
-    void note(hipError_t e) { if (e != hipSuccess && c->lane_err == hipSuccess) c->lane_err = e; }
-    void record(hipEvent_t e, hipStream_t s) { note(hipEventRecord(e, s)); }
-    void wait(hipStream_t s, hipEvent_t e) { note(hipStreamWaitEvent(s, e, 0)); }
-};
-
-static GConvArgs gconv_args(siggan_ctx* c) {
+static GConvArgs gconv_args(const siggan_ctx* c) {
     GConvArgs a; memset(&a, 0, sizeof a);
     a.dt = c->dt; a.gslope = c->cfg.g_leaky_slope;
     a.slab = c->slab_k; a.slab_floats = c->slab_k_floats; a.zeros = c->zeros;
@@ -753,7 +811,8 @@ static GConvArgs gconv_args(siggan_ctx* c) {
 // Generator.forward (generator_vanilla_gan.py:189-209).  training: BN batch stats (+ running
 // update) and raw pre-BN outputs kept for the backward pass; eval: BN folded into the epilogue.
 // z == nullptr: the latent batch is drawn inside the fc kernel from RNG stream rng_sid and left in z_out.
-static void g_forward_pass(siggan_ctx* c, const float* z, int B, bool training, float* img, hipStream_t s,
+// Returns what Carried::ga_last_B becomes: B after a training forward (its last activation was not written), else 0.
+static int g_forward_pass(const siggan_ctx* c, const float* z, int B, bool training, float* img, hipStream_t s,
                            float* partial = nullptr, float* slab_k = nullptr, uint32_t rng_sid = 0, float* z_out = nullptr,
                            hipEvent_t done = nullptr,       // done: completion event of the pass' last launch
                            uint8_t* u8 = nullptr, int32_t* stats = nullptr, float thr = 0.f) {   // eval only: see launch_final_fwd
@@ -801,15 +860,17 @@ static void g_forward_pass(siggan_ctx* c, const float* z, int B, bool training, 
         launch_final_fwd(c->dt, c->g_y[c->Lg], c->wfin_t, GP(c, gi_fin_b(c)), img, B, c->S, c->gC[c->Lg], gs, s, c->g_bn[c->Lg], done);
     else
         launch_final_fwd(c->dt, A[c->Lg], c->wfin_t, GP(c, gi_fin_b(c)), img, B, c->S, c->gC[c->Lg], gs, s, nullptr, done, u8, stats, thr);
-    c->ga_last_B = training ? B : 0;
+    return training ? B : 0;
 }
 
 // Discriminator conv blocks + classifier logits for nB images written to workspace rows
 // [r0, r0 + nB) (the D step runs D(real) into rows [0,B) on a side lane while the Generator
 // produces the fakes, then D(fake) into rows [B,2B); backward treats the 2B rows as one batch).
-static void d_forward_rows(siggan_ctx* c, const float* x, int r0, int nB, bool dropout, hipStream_t s, float* slab_k,
+// Returns the form the logits were left in: P > 0 partial dot products per image in lparts, 0: stored in `logits`.
+static int d_forward_rows(const siggan_ctx* c, const float* x, int r0, int nB, bool dropout, hipStream_t s, float* slab_k,
                            bool fuse_cls = false, bool conv1_done = false) {
     const float slope = c->cfg.leaky_slope;
+    int P = 0;
     auto act = [&](int l) { const int64_t H = c->S >> l; return c->d_a[l] + (size_t)((int64_t)r0 * H * H * c->dC[l]) * c->es; };
     auto nz = [&](int l) { return dropout ? c->d_noise[l] + (int64_t)r0 * c->dC[l] : nullptr; };
     if (!conv1_done)          // (done: it rode in the launch that re-packed D's weights, see repack)
@@ -826,11 +887,12 @@ static void d_forward_rows(siggan_ctx* c, const float* x, int r0, int nB, bool d
         // the classifier's dot product rides there as P partials per image and k_cls_fwd is not launched
         const int P_max = c->dC[c->Ld] * 16 / 1024;
         if (l == c->Ld && fuse_cls && P_max >= 1 && P_max <= 16) { a.cls_w = c->wcp; a.cls_part = c->lparts + (size_t)r0 * P_max; }
-        const int P = launch_gconv(a, s);
-        if (l == c->Ld) c->lP[r0 == 0 ? 0 : 1] = a.cls_w ? P : 0;
+        const int splits = launch_gconv(a, s);
+        if (l == c->Ld && a.cls_w) P = splits;
     }
-    if (c->lP[r0 == 0 ? 0 : 1] == 0)
+    if (P == 0)
         launch_cls_fwd(c->dt, act(c->Ld), c->wcp, DP(c, di_cls_b(c)), c->logits + r0, nB, c->dC[c->Ld] * 16, s);
+    return P;
 }
 
 // Backward through the Discriminator from d(logit).  want_wgrad: fill the D gradient arena
@@ -840,10 +902,12 @@ static void d_forward_rows(siggan_ctx* c, const float* x, int r0, int nB, bool d
 struct BceSpec { int n0; float y0, y1; float* mt; int is_g; };   // rows < n0: target y0, the rest y1 (each segment's mean)
 
 // r0 / garena (spectral norm: one pass at a time): the Bd rows start at workspace row r0 and the gradients go to garena
-// (an arena-shaped temporary) instead of the bound arena.
-static void d_backward_pass(siggan_ctx* c, Lanes& L, const float* x0, int n0, const float* x1, int Bd, bool dropout,
-                            bool want_wgrad, bool want_dimage, const BceSpec& bce, int r0 = 0, float* garena = nullptr,
+// (an arena-shaped temporary) instead of the bound arena.  P: the form d_forward_rows left these rows' logits in (< 0: the
+// two halves of a 2B-row pass disagree).  Returns whether the tail's all-reduce was started (Carried::early_ar).
+static bool d_backward_pass(const siggan_ctx* c, Lanes& L, const float* x0, int n0, const float* x1, int Bd, bool dropout,
+                            bool want_wgrad, bool want_dimage, const BceSpec& bce, int P, int r0 = 0, float* garena = nullptr,
                             bool early_allreduce = false) {
+    bool early_ar = false;
     const float slope = c->cfg.leaky_slope;
     const int Ld = c->Ld;
     float* const ga = garena ? garena : c->st.d_grads;
@@ -860,9 +924,7 @@ static void d_backward_pass(siggan_ctx* c, Lanes& L, const float* x0, int n0, co
     hipStream_t const sb = want_wgrad ? L.b : L.m;
     // the logits of the rows this pass covers: stored, or P partial dot products per image (d_forward_rows).  Both halves of a
     // 2B-row pass were produced with the same batch size, hence in the same form
-    const int hP = c->lP[r0 == 0 ? 0 : 1];
-    const int P = (r0 == 0 && Bd > bce.n0 && bce.n0 > 0 && c->lP[1] != hP) ? -1 : hP;
-    if (P < 0) { c->lane_err = hipErrorInvalidValue; return; }       // (cannot happen: reported, not computed wrongly)
+    if (P < 0) { L.note(hipErrorInvalidValue); return false; }       // (cannot happen: reported, not computed wrongly)
     const float* const parts = P ? c->lparts + (size_t)r0 * P : nullptr;
     const float* const bc = DP(c, di_cls_b(c));
     if (sb != L.m) {
@@ -901,8 +963,8 @@ static void d_backward_pass(siggan_ctx* c, Lanes& L, const float* x0, int n0, co
                 L.wait(c->s_n, ea); L.wait(c->s_n, eb);
                 const int64_t o = c->d_off[di_w(l)];
                 const int rc = rccl()->AllReduce(ga + o, ga + o, (size_t)(c->d_total - o), NCCL_FLOAT32, NCCL_SUM, c->comm, c->s_n);
-                if (rc != NCCL_SUCCESS) c->comm_err = rc;
-                else { L.record(c->ev_ar, c->s_n); c->early_ar = true; }
+                if (rc != NCCL_SUCCESS) L.comm_fail(rc);
+                else { L.record(c->ev_ar, c->s_n); early_ar = true; }
             }
         }
         // input gradient ("up" form): contract Cout, produce Cin at (Hi x Hi); fused leaky'/dropout of block l-1
@@ -933,11 +995,12 @@ static void d_backward_pass(siggan_ctx* c, Lanes& L, const float* x0, int n0, co
     }
     if (want_dimage)
         launch_conv1_dgrad_tanh(c->dt, dvp(1), c->d_w1t, x0, c->dpre, Bd, c->S, c->dC[1], L.m);
+    return early_ar;
 }
 
 // Backward through the Generator from d(pre-tanh) in c->dpre; fills the G gradient arena.  Lane m:
 // BatchNorm backward and the input-gradient chain; lane a: the weight gradients.
-static void g_backward_pass(siggan_ctx* c, Lanes& L, const float* z, int B) {
+static void g_backward_pass(const siggan_ctx* c, Lanes& L, const float* z, int B) {
     const float gs = c->cfg.g_leaky_slope;                   // the Generator's activation slope (g_dact, act.h)
     const int Lg = c->Lg, S = c->S;
     int pre_rows = 0;              // partial rows of block l's BatchNorm-backward sums left by the input-gradient GEMM of block l+1
@@ -972,7 +1035,7 @@ static void g_backward_pass(siggan_ctx* c, Lanes& L, const float* z, int B) {
         }
         pre_rows = launch_gconv(a, L.m);
         if (pre_rows < 0) {        // (the pass goes on, so the lanes still join; the step's call returns SIGGAN_E_STATE)
-            c->refused = "the Generator's input-gradient GEMM was refused: its BatchNorm-backward sums had no carve (stat_cap)";
+            L.refuse("the Generator's input-gradient GEMM was refused: its BatchNorm-backward sums had no carve (stat_cap)");
             pre_rows = 0;
         }
     }
@@ -987,7 +1050,7 @@ static void g_backward_pass(siggan_ctx* c, Lanes& L, const float* z, int B) {
 
 // dropout multiplier tables of passes [p0, p1) (pass 0 = rows [0,B) = D(real), pass 1 = rows [B,2B) = D(fake)).
 // ctr_add: draw as if the step counter were that much further (a pass generated ahead of its step).
-static void make_noise(siggan_ctx* c, const float* masks, int B, int p0, int p1, hipStream_t s, uint32_t ctr_add = 0) {
+static void make_noise(const siggan_ctx* c, const float* masks, int B, int p0, int p1, hipStream_t s, uint32_t ctr_add = 0) {
     const float keep = 1.0f - c->cfg.dropout;
     int64_t sumC = 0;
     for (int l = 1; l <= c->Ld; ++l) sumC += c->dC[l];
@@ -1025,58 +1088,60 @@ static const float SN_EPS = 1e-12f;        // torch.nn.utils.spectral_norm's eps
 // fake pass see different effective weights W / sigma_p.  The passes therefore run one after the other on the main lane
 // (sigma -> weight packs -> forward), the backward is done per pass with that pass's packs into two arena-shaped
 // temporaries, and k_sn_combine forms the gradient w.r.t. weight_orig through both sigmas.
-static void phase_d_grads_sn(siggan_ctx* c, Lanes& L, const PhaseKey& k) {
+static void phase_d_grads_sn(const siggan_ctx* c, Lanes& L, const PhaseKey& k, PhaseResult& r) {
     const int B = k.B;
     const bool drop = c->cfg.dropout > 0.f;
-    repack(c, L.m, L.m, k.g_dirty != 0, false);
+    repack(c, L, L.m, L.m, k.g_dirty != 0, false);
     if (k.pre_real)
-        L.note(hipMemcpyAsync(c->real_stage, c->staged_src, (size_t)B * c->S * c->S * sizeof(float), hipMemcpyDeviceToDevice, L.m));
+        L.note(hipMemcpyAsync(c->real_stage, k.staged_src, (size_t)B * c->S * c->S * sizeof(float), hipMemcpyDeviceToDevice, L.m));
     if (drop) make_noise(c, k.has_masks ? c->mask_stage : nullptr, B, 0, 2, L.m);
     const float* fake = c->img;
     if (k.variant == SIGGAN_STEP_ABLATION) {
-        g_forward_pass(c, k.has_zg ? c->z_g : nullptr, B, true, c->img_g, L.m, nullptr, nullptr, 2, c->z_g);
+        r.ga_last_B = g_forward_pass(c, k.has_zg ? c->z_g : nullptr, B, true, c->img_g, L.m, nullptr, nullptr, 2, c->z_g);
         L.record(c->ev_gfwd, L.m);
         fake = c->img_g;
     } else {
-        g_forward_pass(c, k.has_z ? c->z : nullptr, B, false, c->img, L.m, nullptr, nullptr, 1, c->z);
+        r.ga_last_B = g_forward_pass(c, k.has_z ? c->z : nullptr, B, false, c->img, L.m, nullptr, nullptr, 1, c->z);
     }
     launch_sn_sigma(c->snt, 1, 0, SN_EPS, L.m);                       // D(real): power iteration 1
-    repack(c, L.m, L.m, false, true, 0);
-    d_forward_rows(c, c->real_stage, 0, B, drop, L.m, c->slab_k);
+    repack(c, L, L.m, L.m, false, true, 0);
+    r.lP[0] = d_forward_rows(c, c->real_stage, 0, B, drop, L.m, c->slab_k);
     launch_sn_sigma(c->snt, 1, 1, SN_EPS, L.m);                       // D(fake): power iteration 2
-    repack(c, L.m, L.m, false, true, 1);
-    d_forward_rows(c, fake, B, B, drop, L.m, c->slab_k);
+    repack(c, L, L.m, L.m, false, true, 1);
+    r.lP[1] = d_forward_rows(c, fake, B, B, drop, L.m, c->slab_k);
     launch_bce(c->logits, 2 * B, B, k.ls, 0.f, c->probs, c->dlogit, k.mt, 0, L.m, c->gscale);     // the step's metrics
-    d_backward_pass(c, L, fake, B, fake, B, drop, true, false, BceSpec{B, 0.f, 0.f, nullptr, 0}, B, c->sn_g[1]);
-    repack(c, L.m, L.m, false, true, 0);
-    d_backward_pass(c, L, c->real_stage, B, c->real_stage, B, drop, true, false, BceSpec{B, k.ls, k.ls, nullptr, 0}, 0, c->sn_g[0]);
-    c->snt.slot[0] = 0; c->snt.slot[1] = 1;
-    launch_sn_combine(c->snt, c->sn_g[0], c->sn_g[1], c->st.d_grads, c->d_total, 2, L.m);
+    d_backward_pass(c, L, fake, B, fake, B, drop, true, false, BceSpec{B, 0.f, 0.f, nullptr, 0}, r.lP[1], B, c->sn_g[1]);
+    repack(c, L, L.m, L.m, false, true, 0);
+    d_backward_pass(c, L, c->real_stage, B, c->real_stage, B, drop, true, false, BceSpec{B, k.ls, k.ls, nullptr, 0}, r.lP[0], 0, c->sn_g[0]);
+    SnTable t = c->snt;                                               // (a launch-argument table: the slots are this launch's)
+    t.slot[0] = 0; t.slot[1] = 1;
+    launch_sn_combine(t, c->sn_g[0], c->sn_g[1], c->st.d_grads, c->d_total, 2, L.m);
 }
 
-static void phase_d_grads(siggan_ctx* c, Lanes& L, const PhaseKey& k) {
-    c->early_ar = false;             // set again by this pass when (and only when) it starts the tail's all-reduce itself
-    if (c->sn) return phase_d_grads_sn(c, L, k);
+static void phase_d_grads(const siggan_ctx* c, Lanes& L, const PhaseKey& k, PhaseResult& r) {
+    r.early_ar = 0;                  // set again by this pass when (and only when) it starts the tail's all-reduce itself
+    if (c->sn) return phase_d_grads_sn(c, L, k, r);
     const int B = k.B;
     const bool drop = c->cfg.dropout > 0.f;
     // A staged step whose D(real) forward already ran has nothing for lane a: the real batch is read where it lies (no copy:
     // the borrowed tensor is valid until this call returns), the dropout tables of BOTH passes were drawn when that forward
     // was launched -- no fork, no join, two launches fewer in the step's first 100 us (+0.4 %)
-    const bool nolane = k.pre_real == 2 && !k.d_dirty && (!drop || c->dreal_noise2);
+    const bool nolane = k.pre_real == 2 && !k.d_dirty && (!drop || k.dreal_noise2);
     const float* xreal = c->real_stage;
+    int P_real = k.lP0;                                               // (pre_real == 2: as the staged forward left it)
     if (nolane) {
-        repack(c, L.m, L.m, k.g_dirty != 0, false);
-        xreal = c->staged_src;
+        repack(c, L, L.m, L.m, k.g_dirty != 0, false);
+        xreal = k.staged_src;
     } else {
     L.fork(L.a);                                                     // lane a: D's packs, dropout tables, D(real)
-    repack(c, L.m, L.a, k.g_dirty != 0, k.d_dirty != 0);
+    repack(c, L, L.m, L.a, k.g_dirty != 0, k.d_dirty != 0);
     if (k.pre_real)      // staged batch -> this step's real batch (the D backward reads it again)
-        L.note(hipMemcpyAsync(c->real_stage, c->staged_src, (size_t)B * c->S * c->S * sizeof(float), hipMemcpyDeviceToDevice, L.a));
-    if (drop && !(k.pre_real == 2 && c->dreal_noise2))
+        L.note(hipMemcpyAsync(c->real_stage, k.staged_src, (size_t)B * c->S * c->S * sizeof(float), hipMemcpyDeviceToDevice, L.a));
+    if (drop && !(k.pre_real == 2 && k.dreal_noise2))
         make_noise(c, k.has_masks ? c->mask_stage : nullptr, B, k.pre_real == 2 ? 1 : 0, 2, L.a);
     // D(real) beside the Generator (train...py:309) -- unless the previous siggan_g_grads already ran it
     // (siggan_stage_real) beside its Generator backward; then bce only has to wait for that lane
-    if (k.pre_real != 2) d_forward_rows(c, c->real_stage, 0, B, drop, L.a, c->slab_k2, true);
+    if (k.pre_real != 2) r.lP[0] = P_real = d_forward_rows(c, c->real_stage, 0, B, drop, L.a, c->slab_k2, true);
     }
     const float* fake = c->img;
     const bool spec_fwd = k.spec_g && k.variant != SIGGAN_STEP_ABLATION;
@@ -1092,17 +1157,17 @@ static void phase_d_grads(siggan_ctx* c, Lanes& L, const PhaseKey& k) {
         // ablation_vanilla_gan_signatures.py:397-448: both nets in train mode and ONE Generator forward per iteration --
         // BatchNorm batch statistics (+ running update), activations kept: the D half sees fake.detach(), the G half
         // back-propagates through the very same forward
-        g_forward_pass(c, k.has_zg ? c->z_g : nullptr, B, true, c->img_g, L.m, nullptr, nullptr, 2, c->z_g);
+        r.ga_last_B = g_forward_pass(c, k.has_zg ? c->z_g : nullptr, B, true, c->img_g, L.m, nullptr, nullptr, 2, c->z_g);
         L.record(c->ev_gfwd, L.m);
         fake = c->img_g;
     } else {
         // (nolane: the pipelined forward below needs nothing but this pass -- its fork rides on the last kernel here)
         if (spec_fwd && !spec_early && nolane) e_eval = L.fork_event(c->s_c);
-        g_forward_pass(c, k.has_z ? c->z : nullptr, B, false, c->img, L.m, nullptr, nullptr, 1, c->z, e_eval);   // G.eval(), no grad (train...py:314-315)
+        r.ga_last_B = g_forward_pass(c, k.has_z ? c->z : nullptr, B, false, c->img, L.m, nullptr, nullptr, 1, c->z, e_eval);   // G.eval(), no grad (train...py:314-315)
     }
     if (spec_early) {       // (enqueued behind the eval forward: the critical lane's kernels reach the dispatcher first)
         L.wait(c->s_c, e_early);
-        g_forward_pass(c, k.has_zg ? c->z_g : nullptr, B, true, c->img_g, c->s_c, c->partial_c, c->slab_k3, 2, c->z_g);
+        r.ga_last_B = g_forward_pass(c, k.has_zg ? c->z_g : nullptr, B, true, c->img_g, c->s_c, c->partial_c, c->slab_k3, 2, c->z_g);
         L.record(c->ev_gfwd, c->s_c);
     }
     if (!nolane) L.join(L.a);
@@ -1114,43 +1179,44 @@ static void phase_d_grads(siggan_ctx* c, Lanes& L, const PhaseKey& k) {
     if (spec_fwd && !spec_early) { e_spec = e_eval; if (!e_spec) { e_spec = L.next(); L.record(e_spec, L.m); } }
     // the staged D(real) launch (lane c, previous G step) also drew THIS pass' dropout tables (dreal_noise2): the main lane
     // must be behind that lane before D(fake) reads them, not only before the backward pass reads the rows
-    const bool join_early = k.pre_real == 2 && !c->dreal_joined && drop && c->dreal_noise2;
+    const bool join_early = k.pre_real == 2 && !k.dreal_joined && drop && k.dreal_noise2;
     if (join_early) L.wait(L.m, c->ev_dreal);
-    d_forward_rows(c, fake, B, B, drop, L.m, c->slab_k, true);       // D(fake) into rows [B, 2B)
-    if (k.pre_real == 2 && !c->dreal_joined && !join_early) L.wait(L.m, c->ev_dreal);
-    c->dreal_joined = c->dreal_noise2 = false;
+    r.lP[1] = d_forward_rows(c, fake, B, B, drop, L.m, c->slab_k, true);   // D(fake) into rows [B, 2B)
+    if (k.pre_real == 2 && !k.dreal_joined && !join_early) L.wait(L.m, c->ev_dreal);
+    r.dreal_joined = r.dreal_noise2 = 0;
     if (spec_fwd && !spec_early) {
         L.wait(c->s_c, e_spec);
-        g_forward_pass(c, k.has_zg ? c->z_g : nullptr, B, true, c->img_g, c->s_c, c->partial_c, c->slab_k2, 2, c->z_g);
+        r.ga_last_B = g_forward_pass(c, k.has_zg ? c->z_g : nullptr, B, true, c->img_g, c->s_c, c->partial_c, c->slab_k2, 2, c->z_g);
         L.record(c->ev_gfwd, c->s_c);
     }
     // the pipelined forward has ended by the time the weight gradients have: the main lane waits for it inside the backward
     // pass' tail (fp32) / next to the two joins of this phase (16-bit), not between the optimiser and the G step's first kernel
-    c->gfwd_joined = false;
-    if (spec_fwd && c->dt == DT_F32) { L.tail_wait = c->ev_gfwd; c->gfwd_joined = true; }
-    d_backward_pass(c, L, xreal, B, fake, 2 * B, drop, true, false, BceSpec{B, k.ls, 0.f, k.mt, 0}, 0, nullptr, k.coll != 0);
+    if (spec_fwd && c->dt == DT_F32) L.tail_wait = c->ev_gfwd;
+    r.early_ar = d_backward_pass(c, L, xreal, B, fake, 2 * B, drop, true, false, BceSpec{B, k.ls, 0.f, k.mt, 0},
+                                 P_real == r.lP[1] ? P_real : -1, 0, nullptr, k.coll != 0);
     L.tail_wait = nullptr;
-    if (spec_fwd && c->dt != DT_F32) { L.wait(L.m, c->ev_gfwd); c->gfwd_joined = true; }
+    if (spec_fwd && c->dt != DT_F32) L.wait(L.m, c->ev_gfwd);
+    r.gfwd_joined = spec_fwd;
 }
 
-static void phase_g_grads(siggan_ctx* c, Lanes& L, const PhaseKey& k) {
+static void phase_g_grads(const siggan_ctx* c, Lanes& L, const PhaseKey& k, PhaseResult& r) {
     const int B = k.B;
     const float* zg; float* img;
     const bool d_pack = !c->sn && k.d_dirty != 0;                    // (spectral norm: the packs follow sigma, below)
     bool conv1_done = false;
     if (k.spec_g) {                                                  // forward already enqueued by siggan_step_begin
-        if (!c->gfwd_joined) L.wait(L.m, c->ev_gfwd);
-        c->gfwd_joined = false;
+        if (!k.gfwd_joined) L.wait(L.m, c->ev_gfwd);
+        r.gfwd_joined = 0;
         // trainer step: the first-block forward of the new images (rows [B, 2B), no dropout in this pass) rides in the launch
         // that re-packs D's weights -- it reads the raw block-1 weights, and the two would stand back to back on this lane
         // (k.rode: both already happened in the D update's launch, k_adam_pack)
         conv1_done = k.rode || (d_pack && k.variant != SIGGAN_STEP_ABLATION);
-        repack(c, L.m, L.m, false, d_pack, 0, (conv1_done && !k.rode) ? c->img_g : nullptr, B, B);
+        repack(c, L, L.m, L.m, false, d_pack, 0, (conv1_done && !k.rode) ? c->img_g : nullptr, B, B);
         zg = c->z_g; img = c->img_g;
     } else {
         L.fork(L.a);
-        repack(c, L.m, L.a, k.g_dirty != 0, d_pack);
-        g_forward_pass(c, k.has_z ? c->z : nullptr, B, true, c->img, L.m, nullptr, nullptr, 2, c->z);   // G.train(): BN batch stats (train...py:349)
+        repack(c, L, L.m, L.a, k.g_dirty != 0, d_pack);
+        r.ga_last_B = g_forward_pass(c, k.has_z ? c->z : nullptr, B, true, c->img, L.m, nullptr, nullptr, 2, c->z);   // G.train(): BN batch stats (train...py:349)
         L.join(L.a);
         zg = c->z; img = c->img;
     }
@@ -1160,7 +1226,7 @@ static void phase_g_grads(siggan_ctx* c, Lanes& L, const PhaseKey& k) {
     const bool gdrop = abl && c->cfg.dropout > 0.f;
     if (c->sn) {        // D.eval() (trainer step): sigma from the stored u, v; D.train() (ablation step): a third power iteration
         launch_sn_sigma(c->snt, abl ? 1 : 0, 2, SN_EPS, L.m);
-        repack(c, L.m, L.m, false, true, 2);
+        repack(c, L, L.m, L.m, false, true, 2);
     }
     if (gdrop) {
         int64_t sumC = 0;
@@ -1173,18 +1239,18 @@ static void phase_g_grads(siggan_ctx* c, Lanes& L, const PhaseKey& k) {
     // input-gradient chain (one B-sized GEMM at a time leaves half the chip's wave slots idle), not only beside the Generator
     // backward: +1.3 % (round 3).  (ablation step: its dropout tables are drawn for rows [0, B); spectral norm: no staging)
     const int r0g = (!abl && !c->sn) ? B : 0;
-    c->g_r0 = r0g;
+    r.g_r0 = r0g;
     const bool real_early = k.pre_real && r0g != 0;
     if (real_early) {
         const bool drop = c->cfg.dropout > 0.f;
         L.fork(c->s_c);                                               // D's packs are complete on m here
         if (drop) make_noise(c, nullptr, B, 0, 2, c->s_c, 1);       // the D(fake) pass' tables too (this G step's pass has no dropout)
-        c->dreal_noise2 = drop;
-        d_forward_rows(c, c->staged_src, 0, B, drop, c->s_c, c->slab_k2, true);
+        r.dreal_noise2 = drop;
+        r.lP[0] = d_forward_rows(c, k.staged_src, 0, B, drop, c->s_c, c->slab_k2, true);
         L.record(c->ev_dreal, c->s_c);
     }
-    d_forward_rows(c, img, r0g, B, gdrop, L.m, c->slab_k, true, conv1_done);
-    d_backward_pass(c, L, img, B, img, B, gdrop, false, true, BceSpec{B, gy, gy, k.mt, 1}, r0g);   // through D into the image; no D weight grads
+    const int P = r.lP[r0g ? 1 : 0] = d_forward_rows(c, img, r0g, B, gdrop, L.m, c->slab_k, true, conv1_done);
+    d_backward_pass(c, L, img, B, img, B, gdrop, false, true, BceSpec{B, gy, gy, k.mt, 1}, P, r0g);   // through D into the image; no D weight grads
     if (k.pre_real && !real_early) {
         // siggan_stage_real: the NEXT D step's D(real) forward needs the Discriminator as it is now (its
         // update is behind us) and the activation rows this step is done with: run it on lane c beside the
@@ -1193,16 +1259,16 @@ static void phase_g_grads(siggan_ctx* c, Lanes& L, const PhaseKey& k) {
         const bool drop = c->cfg.dropout > 0.f;
         L.fork(c->s_c);
         if (drop) make_noise(c, nullptr, B, 0, 1, c->s_c, 1);
-        d_forward_rows(c, c->staged_src, 0, B, drop, c->s_c, c->slab_k2, true);
+        r.lP[0] = d_forward_rows(c, k.staged_src, 0, B, drop, c->s_c, c->slab_k2, true);
         L.record(c->ev_dreal, c->s_c);
     }
     g_backward_pass(c, L, zg, B);
     // 16-bit contexts: join the early D(real) lane HERE, next to the join of the weight-gradient lane, so that the next D step
     // does not stop for it behind D(fake)
-    if (real_early && c->dt != DT_F32) { L.wait(L.m, c->ev_dreal); c->dreal_joined = true; }
+    if (real_early && c->dt != DT_F32) { L.wait(L.m, c->ev_dreal); r.dreal_joined = 1; }
 }
 
-static void phase_apply(siggan_ctx* c, Lanes& L, const PhaseKey& k) {
+static void phase_apply(const siggan_ctx* c, Lanes& L, const PhaseKey& k, PhaseResult& r) {
     const int which = k.phase == 2 ? 1 : 0;                          // phase 2 = D apply, 3 = G apply
     float* p = which == 0 ? c->st.g_params : c->st.d_params;
     float* g = which == 0 ? c->st.g_grads : c->st.d_grads;
@@ -1223,16 +1289,16 @@ static void phase_apply(siggan_ctx* c, Lanes& L, const PhaseKey& k) {
         // the update is skipped and lane_check hands the error to the caller (sticky: every later call returns it until
         // siggan_comm_destroy)
         if (c->comm_err) return;
-        if (which == 1 && c->early_ar) {
+        if (which == 1 && k.early_ar) {
             // the tail of the arena (last block + classifier) went ahead (d_backward_pass): the head now
             const int64_t o = c->d_off[di_w(c->Ld)];
             const int e = rccl()->AllReduce(g, g, (size_t)o, NCCL_FLOAT32, NCCL_SUM, c->comm, L.m);
-            c->early_ar = false;
-            if (e != NCCL_SUCCESS) { c->comm_err = e; return; }
+            r.early_ar = 0;
+            if (e != NCCL_SUCCESS) { L.comm_fail(e); return; }
             L.wait(L.m, c->ev_ar);
         } else {
         const int e = rccl()->AllReduce(g, g, (size_t)n, NCCL_FLOAT32, NCCL_SUM, c->comm, L.m);
-        if (e != NCCL_SUCCESS) { c->comm_err = e; return; }
+        if (e != NCCL_SUCCESS) { L.comm_fail(e); return; }
         }
         gs *= 1.0f / (float)c->comm_world;
     }
@@ -1244,7 +1310,7 @@ static void phase_apply(siggan_ctx* c, Lanes& L, const PhaseKey& k) {
         ApTable t;
         ApRide rd; memset(&rd, 0, sizeof rd);
         if (k.ride) {      // the pending G step's first Discriminator block (siggan_step_begin's images; rows [B, 2B)) rides along
-            if (!c->gfwd_joined) { L.wait(L.m, c->ev_gfwd); c->gfwd_joined = true; }
+            if (!k.gfwd_joined) { L.wait(L.m, c->ev_gfwd); r.gfwd_joined = 1; }
             const int64_t H = c->S >> 1;
             rd.x = c->img_g; rd.out = c->d_a[1] + (size_t)((int64_t)k.ride * H * H * c->dC[1]) * c->es; rd.B = k.ride; rd.S = c->S;
             rd.dt = c->dt; rd.slope = c->cfg.leaky_slope; rd.w_off = c->d_off[di_w(1)]; rd.b_off = c->d_off[di_b(1)];
@@ -1254,7 +1320,7 @@ static void phase_apply(siggan_ctx* c, Lanes& L, const PhaseKey& k) {
             launch_adam_pack(t, p, g, m, v, c->dev, steps, nt, k.fused_t, k.lr, k.beta1, k.beta2, k.eps, gs, k.clip,
                              k.mt + (which == 0 ? SIGGAN_M_G_GRAD_NORM : SIGGAN_M_D_GRAD_NORM), clip ? c->partial : nullptr,
                              k.mt + (which == 0 ? SIGGAN_M_G_SKIPPED : SIGGAN_M_D_SKIPPED), BN_EPS, k.ride ? &rd : nullptr, L.m);
-        if (!ok) c->lane_err = hipErrorInvalidValue;                    // (apply_common checked the table: not reached)
+        if (!ok) L.note(hipErrorInvalidValue);                          // (apply_common checked the table: not reached)
         return;
     }
     if (k.fused_t > 0.0) {
@@ -1271,16 +1337,19 @@ static void phase_apply(siggan_ctx* c, Lanes& L, const PhaseKey& k) {
     launch_adam(p, g, m, v, n, c->dev, k.beta1, k.beta2, k.eps, (clip || gs != 1.0f) ? 1 : 0, L.m);
 }
 
-static void run_phase_body(siggan_ctx* c, Lanes& L, const PhaseKey& k) {
-    if (k.phase == 0) phase_d_grads(c, L, k);
-    else if (k.phase == 1) phase_g_grads(c, L, k);
-    else phase_apply(c, L, k);
+static PhaseResult run_phase_body(const siggan_ctx* c, Lanes& L, const PhaseKey& k) {
+    PhaseResult r;
+    if (k.phase == 0) phase_d_grads(c, L, k, r);
+    else if (k.phase == 1) phase_g_grads(c, L, k, r);
+    else phase_apply(c, L, k, r);
+    return r;
 }
 
 // Enqueue one phase behind everything on the caller's stream u.  Eager: directly on u (side lanes
 // forked from it).  Graph mode: the phase is captured once per distinct key on the library's own
 // main lane (a caller stream may be the legacy default stream, which cannot be captured) and replayed.
-static int run_phase(siggan_ctx* c, const PhaseKey& k, hipStream_t u) {
+// r: what the phase leaves behind -- of the enqueue just made, or (replay) of the capture, kept beside the graph.
+static int enqueue_phase(siggan_ctx* c, const PhaseKey& k, hipStream_t u, PhaseResult& r) {
     if (c->refused) return lane_check(c);           // a step's launch was refused: nothing more is enqueued on this context
     const bool overlap = (c->mode & SIGGAN_MODE_OVERLAP) != 0;
     const bool graph = (c->mode & SIGGAN_MODE_GRAPH) != 0 && g_prof == nullptr;
@@ -1288,27 +1357,27 @@ static int run_phase(siggan_ctx* c, const PhaseKey& k, hipStream_t u) {
     if (graph && c->sn) return fail(SIGGAN_E_STATE, "SIGGAN_MODE_GRAPH is not available with spectral normalisation");
     if (!graph) {
         const bool ext = overlap && g_prof == nullptr;
-        Lanes L{c, u, overlap ? c->s_a : u, overlap ? c->s_b : u, ext, nullptr};
-        run_phase_body(c, L, k);
+        Lanes L(c, u, overlap ? c->s_a : u, overlap ? c->s_b : u, ext);
+        r = run_phase_body(c, L, k);
         LAUNCHCHK();
         return lane_check(c);
     }
     hipGraphExec_t exec = nullptr;
     for (auto& e : c->graphs)
-        if (e.first == k) { exec = e.second; break; }
+        if (e.key == k) { exec = e.exec; r = e.res; break; }
     if (!exec) {
-        Lanes L{c, c->s_m, overlap ? c->s_a : c->s_m, overlap ? c->s_b : c->s_m, false, nullptr};
+        Lanes L(c, c->s_m, overlap ? c->s_a : c->s_m, overlap ? c->s_b : c->s_m, false);
         hipGraph_t g = nullptr;
         HIPCHK(hipStreamBeginCapture(c->s_m, hipStreamCaptureModeRelaxed));
-        run_phase_body(c, L, k);
+        r = run_phase_body(c, L, k);
         hipError_t e1 = hipStreamEndCapture(c->s_m, &g);
         if (e1 != hipSuccess || !g) return fail(SIGGAN_E_HIP, "stream capture failed: %s", hipGetErrorString(e1));
         if (c->refused) { (void)hipGraphDestroy(g); return lane_check(c); }     // (a refused launch: not cached, never replayed)
         hipError_t e2 = hipGraphInstantiate(&exec, g, nullptr, nullptr, 0);
         (void)hipGraphDestroy(g);
         if (e2 != hipSuccess) return fail(SIGGAN_E_HIP, "hipGraphInstantiate: %s", hipGetErrorString(e2));
-        if (c->graphs.size() >= 64) { (void)hipGraphExecDestroy(c->graphs.front().second); c->graphs.erase(c->graphs.begin()); }
-        c->graphs.emplace_back(k, exec);
+        if (c->graphs.size() >= 64) { (void)hipGraphExecDestroy(c->graphs.front().exec); c->graphs.erase(c->graphs.begin()); }
+        c->graphs.push_back(CachedPhase{k, exec, r});
     }
     hipEvent_t e_in = c->ev_bridge[0], e_out = c->ev_bridge[1];
     HIPCHK(hipEventRecord(e_in, u));
@@ -1317,6 +1386,17 @@ static int run_phase(siggan_ctx* c, const PhaseKey& k, hipStream_t u) {
     HIPCHK(hipEventRecord(e_out, c->s_m));
     HIPCHK(hipStreamWaitEvent(u, e_out, 0));
     return SIGGAN_OK;
+}
+static int run_phase(siggan_ctx* c, const PhaseKey& k, hipStream_t u) {
+    PhaseResult r;
+    const int rc = enqueue_phase(c, k, u, r);
+    // the ONE place a phase's results reach the context (also when a check after the enqueue failed: the work is in flight)
+    Carried& cs = c->cs;
+    auto put = [](auto& field, int v) { if (v >= 0) field = v; };
+    put(cs.early_ar, r.early_ar); put(cs.dreal_joined, r.dreal_joined); put(cs.dreal_noise2, r.dreal_noise2);
+    put(cs.gfwd_joined, r.gfwd_joined); put(cs.g_r0, r.g_r0); put(cs.ga_last_B, r.ga_last_B);
+    put(cs.lP[0], r.lP[0]); put(cs.lP[1], r.lP[1]);
+    return rc;
 }
 
 static PhaseKey make_key(siggan_ctx* c, int phase, int B, bool has_z, bool has_masks, const siggan_hyper* hp,
@@ -1348,7 +1428,7 @@ static int finish_metrics(siggan_ctx* c, float* metrics_dev, float* metrics_host
 extern "C" int siggan_set_step_variant(siggan_ctx* c, int32_t variant) {
     if (!c) return fail(SIGGAN_E_INVALID, "null context");
     if (variant != SIGGAN_STEP_TRAINER && variant != SIGGAN_STEP_ABLATION) return fail(SIGGAN_E_INVALID, "unknown step variant %d", variant);
-    if (c->g_fwd_pending || c->pending) return fail(SIGGAN_E_STATE, "a step is in flight");
+    if (c->cs.g_fwd_pending || c->cs.pending) return fail(SIGGAN_E_STATE, "a step is in flight");
     c->variant = variant;
     return SIGGAN_OK;
 }
@@ -1368,9 +1448,10 @@ extern "C" int siggan_g_forward(siggan_ctx* c, const float* z_dev, int32_t batch
     if (!z_dev || !images_dev) return fail(SIGGAN_E_INVALID, "null tensor");
     hipStream_t s = (hipStream_t)stream;
     if ((rc = settle(c, s))) return rc;
-    repack(c, s, s, c->g_dirty, !c->sn && c->d_dirty);
+    Lanes L(c, s);
+    repack(c, L, s, s, c->g_dirty, !c->sn && c->d_dirty);
     c->g_dirty = false; if (!c->sn) c->d_dirty = false;
-    g_forward_pass(c, z_dev, batch, training != 0, images_dev, s);
+    c->cs.ga_last_B = g_forward_pass(c, z_dev, batch, training != 0, images_dev, s);
     if (training) c->g_dirty = true;   // running statistics moved: the eval-mode tables are stale
     LAUNCHCHK();
     return lane_check(c);
@@ -1386,9 +1467,10 @@ extern "C" int siggan_g_generate_u8(siggan_ctx* c, const float* z_dev, int32_t b
     if (stats_dev && !isfinite(threshold)) return fail(SIGGAN_E_INVALID, "threshold must be finite");
     hipStream_t s = (hipStream_t)stream;
     if ((rc = settle(c, s))) return rc;
-    repack(c, s, s, c->g_dirty, !c->sn && c->d_dirty);
+    Lanes L(c, s);
+    repack(c, L, s, s, c->g_dirty, !c->sn && c->d_dirty);
     c->g_dirty = false; if (!c->sn) c->d_dirty = false;
-    g_forward_pass(c, z_dev, batch, false, images_dev, s, nullptr, nullptr, 0, nullptr, nullptr, u8_dev, stats_dev, threshold);
+    c->cs.ga_last_B = g_forward_pass(c, z_dev, batch, false, images_dev, s, nullptr, nullptr, 0, nullptr, nullptr, u8_dev, stats_dev, threshold);
     LAUNCHCHK();
     return lane_check(c);
 }
@@ -1400,15 +1482,15 @@ extern "C" int siggan_d_forward(siggan_ctx* c, const float* x_dev, int32_t batch
     if (rc) return rc;
     if (!x_dev || (!probs_dev && !features_dev)) return fail(SIGGAN_E_INVALID, "null tensor");
     hipStream_t s = (hipStream_t)stream;
-    drop_dreal(c);                     // the activation rows of a D(real) forward started ahead of time are overwritten
-    c->conv1_rode = 0;                 // ... and those of a first-block forward the last D apply ran ahead
+    invalidate(c, INV_ROWS);           // rows [0, batch) are overwritten
     if ((rc = settle(c, s))) return rc;
+    Lanes L(c, s);
     if (c->sn) launch_sn_sigma(c->snt, training != 0, 2, SN_EPS, s);   // train(): one power iteration (u, v move), as torch's hook
-    repack(c, s, s, c->g_dirty, c->sn || c->d_dirty, 2);
+    repack(c, L, s, s, c->g_dirty, c->sn || c->d_dirty, 2);
     c->g_dirty = c->d_dirty = false;
     const bool drop = training != 0 && c->cfg.dropout > 0.f;
     if (drop) { if (!masks_dev) launch_tick(c->dev, s); make_noise(c, masks_dev, batch, 0, 1, s); }
-    d_forward_rows(c, x_dev, 0, batch, drop, s, c->slab_k);
+    c->cs.lP[0] = d_forward_rows(c, x_dev, 0, batch, drop, s, c->slab_k);
     if (probs_dev) launch_bce(c->logits, batch, batch, 0.f, 0.f, probs_dev, nullptr, nullptr, 0, s);
     if (features_dev) launch_cls_features(c->dt, c->d_a[c->Ld], features_dev, batch, c->dC[c->Ld], s);
     LAUNCHCHK();
@@ -1419,13 +1501,14 @@ static int d_grads_common(siggan_ctx* c, const float* real_dev, int32_t batch, c
                           const siggan_hyper* hp, float* metrics_dev, void* stream, bool spec_g, const float* zg_dev,
                           bool apply_follows = false) {
     ENTER(c);
+    Carried& cs = c->cs;
     int rc = check_call(c, batch);
     if (rc) return rc;
     if ((rc = check_hyper(hp))) return rc;
-    if (!real_dev && c->staged_B != batch)
+    if (!real_dev && cs.staged_B != batch)
         return fail(SIGGAN_E_INVALID, "null real batch (and no batch of %d images staged by siggan_stage_real)", batch);
     if (!c->st.d_grads) return fail(SIGGAN_E_STATE, "gradient arena was not bound");
-    if (c->g_fwd_pending) return fail(SIGGAN_E_STATE, "siggan_step_begin must be followed by siggan_g_grads before the next D step");
+    if (cs.g_fwd_pending) return fail(SIGGAN_E_STATE, "siggan_step_begin must be followed by siggan_g_grads before the next D step");
     // the speculative forward needs its own lane: without overlap (or under graph replay) it is skipped
     if (spec_g && ((c->mode & SIGGAN_MODE_OVERLAP) == 0 || (c->mode & SIGGAN_MODE_GRAPH) != 0 || g_prof != nullptr)) spec_g = false;
     const bool abl = c->variant == SIGGAN_STEP_ABLATION;
@@ -1445,27 +1528,29 @@ static int d_grads_common(siggan_ctx* c, const float* real_dev, int32_t batch, c
     const size_t img_bytes = (size_t)B * c->S * c->S * sizeof(float);
     // stage the caller's tensors into fixed workspace slots (captured phases must see fixed addresses)
     int pre_real = 0;                          // 1: the staged batch is this step's real batch; 2: and its D(real) forward is done
-    if (!real_dev) pre_real = (c->dreal_B == B && !masks_dev) ? 2 : 1;
-    if (pre_real == 2) c->dreal_B = 0;         // consumed: the phase waits for ev_dreal where it needs the rows
+    if (!real_dev) pre_real = (cs.dreal_B == B && !masks_dev) ? 2 : 1;
+    if (pre_real == 2) cs.dreal_B = 0;         // consumed: the phase waits for ev_dreal where it needs the rows
     else drop_dreal(c);                        // D(real) is redone (explicit batch / masks): the early one is abandoned
     if ((rc = settle(c, s))) return rc;
     if (real_dev && real_dev != c->real_stage) HIPCHK(hipMemcpyAsync(c->real_stage, real_dev, img_bytes, hipMemcpyDeviceToDevice, s));
-    c->staged_B = 0;
+    cs.staged_B = 0;
     if (z_dev && z_dev != c->z) HIPCHK(hipMemcpyAsync(c->z, z_dev, (size_t)B * c->latent * sizeof(float), hipMemcpyDeviceToDevice, s));
     int64_t sumC = 0;
     for (int l = 1; l <= c->Ld; ++l) sumC += c->dC[l];
     if (masks_dev) HIPCHK(hipMemcpyAsync(c->mask_stage, masks_dev, (size_t)(abl ? 3 : 2) * B * sumC * sizeof(float), hipMemcpyDeviceToDevice, s));
-    c->abl_masks = abl && masks_dev != nullptr;
+    cs.abl_masks = abl && masks_dev != nullptr;
     if (zg_dev) HIPCHK(hipMemcpyAsync(c->z_g, zg_dev, (size_t)B * c->latent * sizeof(float), hipMemcpyDeviceToDevice, s));
-    c->zg_stash = (!spec_g && zg_dev) ? B : 0;
+    cs.zg_stash = (!spec_g && zg_dev) ? B : 0;
     PhaseKey k = make_key(c, 0, B, z_dev != nullptr, masks_dev != nullptr, hp, metrics_dev);
-    c->metrics_last = k.mt;
+    cs.metrics_last = k.mt;
     k.spec_g = spec_g; k.has_zg = spec_g && zg_dev != nullptr; k.pre_real = pre_real; k.variant = c->variant;
+    if (pre_real) k.staged_src = cs.staged_src;
+    if (pre_real == 2) { k.dreal_joined = cs.dreal_joined; k.dreal_noise2 = cs.dreal_noise2; k.lP0 = cs.lP[0]; }
     k.coll = apply_follows && c->comm != nullptr && (c->mode & SIGGAN_MODE_GRAPH) == 0;   // (no collective inside a captured phase)
     if ((rc = run_phase(c, k, s))) return rc;
     c->g_dirty = c->d_dirty = false;
-    if (spec_g) { c->g_fwd_pending = B; c->g_dirty = true; }   // running statistics moved
-    c->pending = 1;
+    if (spec_g) { cs.g_fwd_pending = B; c->g_dirty = true; }   // running statistics moved
+    cs.pending = 1;
     return SIGGAN_OK;
 }
 
@@ -1474,12 +1559,12 @@ extern "C" int siggan_stage_real(siggan_ctx* c, const float* real_dev, int32_t b
     int rc = check_call(c, batch);
     if (rc) return rc;
     if (!real_dev) return fail(SIGGAN_E_INVALID, "null real batch");
-    drop_dreal(c);                     // an early D(real) forward of a previously staged batch may still be reading that batch
+    invalidate(c, INV_STREAM);         // an early D(real) forward of a previously staged batch may still be reading that batch
     if ((rc = settle(c, (hipStream_t)stream))) return rc;
     // borrowed, not copied (a 1 MB copy on the step's critical lane): the caller keeps the tensor alive and unmodified until the
     // D step that consumes it has returned (include/siggan.h); that step copies it into the workspace on a side lane
-    c->staged_src = real_dev;
-    c->staged_B = batch;
+    c->cs.staged_src = real_dev;
+    c->cs.staged_B = batch;
     return SIGGAN_OK;
 }
 
@@ -1495,10 +1580,11 @@ extern "C" int siggan_step_begin(siggan_ctx* c, const float* real_dev, int32_t b
 
 static int apply_common(siggan_ctx* c, int which, const siggan_hyper* hp, float* metrics_dev, float* metrics_host, void* stream) {
     ENTER(c);
+    Carried& cs = c->cs;
     int rc = check_call(c, 1);
     if (rc) return rc;
     if ((rc = check_hyper(hp))) return rc;
-    if (c->pending != (which == 1 ? 1 : 2))
+    if (cs.pending != (which == 1 ? 1 : 2))
         return fail(SIGGAN_E_STATE, "siggan_%c_apply without a preceding siggan_%c_grads", which ? 'd' : 'g', which ? 'd' : 'g');
     const float* need[] = {which ? c->st.d_grads : c->st.g_grads, which ? c->st.d_exp_avg : c->st.g_exp_avg,
                            which ? c->st.d_exp_avg_sq : c->st.g_exp_avg_sq, which ? c->st.d_adam_steps : c->st.g_adam_steps};
@@ -1507,10 +1593,11 @@ static int apply_common(siggan_ctx* c, int which, const siggan_hyper* hp, float*
     hipStream_t s = (hipStream_t)stream;
     if ((rc = settle(c, s))) return rc;
     // metrics of a step live in ONE buffer: the one the *_grads call named (its losses are already there)
-    if (!metrics_dev) metrics_dev = c->metrics_last != c->metrics ? c->metrics_last : nullptr;
-    else if (c->metrics_last && metrics_dev != c->metrics_last)
-        HIPCHK(hipMemcpyAsync(metrics_dev, c->metrics_last, SIGGAN_M_COUNT * sizeof(float), hipMemcpyDeviceToDevice, (hipStream_t)stream));
+    if (!metrics_dev) metrics_dev = cs.metrics_last != c->metrics ? cs.metrics_last : nullptr;
+    else if (cs.metrics_last && metrics_dev != cs.metrics_last)
+        HIPCHK(hipMemcpyAsync(metrics_dev, cs.metrics_last, SIGGAN_M_COUNT * sizeof(float), hipMemcpyDeviceToDevice, (hipStream_t)stream));
     PhaseKey k = make_key(c, which == 1 ? 2 : 3, 0, false, false, hp, metrics_dev);
+    if (which == 1) k.early_ar = cs.early_ar;
     // One-launch update whenever the step count can live on the host: not under graph replay (arguments are baked into the
     // captured launch) and not with the fp16 overflow guard (a skipped update leaves the device-side count behind).  The count
     // is read back once after siggan_bind / siggan_params_changed and tracked from then on.
@@ -1528,8 +1615,9 @@ static int apply_common(siggan_ctx* c, int which, const siggan_hyper* hp, float*
         // trainer step with the G step's training forward already enqueued (siggan_step_begin): its first Discriminator block
         // needs nothing but the updated block-1 weights -- it rides in the update's launch (phase_g_grads then skips it).
         // fp32 only: 1.4201 -> 1.4105 ms; at bf16 the separate launch measured better (0.6216 vs 0.6245 ms)
-        if (which == 1 && k.pack && c->g_fwd_pending && c->variant != SIGGAN_STEP_ABLATION && g_prof == nullptr && c->dt == DT_F32)
-            k.ride = c->g_fwd_pending;
+        if (which == 1 && k.pack && cs.g_fwd_pending && c->variant != SIGGAN_STEP_ABLATION && g_prof == nullptr && c->dt == DT_F32) {
+            k.ride = cs.g_fwd_pending; k.gfwd_joined = cs.gfwd_joined;
+        }
     } else {
         c->adam_t_known[wi] = false;
     }
@@ -1538,8 +1626,8 @@ static int apply_common(siggan_ctx* c, int which, const siggan_hyper* hp, float*
     // (k.pack: the launch that updated the arena also rebuilt what is derived from it, with the running statistics as the
     // G step's training forward left them)
     if (which == 0) c->g_dirty = !k.pack; else c->d_dirty = !k.pack;
-    if (which == 1) c->conv1_rode = k.ride;
-    c->pending = 0;
+    if (which == 1) cs.conv1_rode = k.ride;
+    cs.pending = 0;
     return finish_metrics(c, metrics_dev, metrics_host, s);
 }
 
@@ -1557,6 +1645,7 @@ extern "C" int siggan_d_step(siggan_ctx* c, const float* real_dev, int32_t batch
 extern "C" int siggan_g_grads(siggan_ctx* c, int32_t batch, const float* z_dev, const siggan_hyper* hp, float* metrics_dev,
                               void* stream) {
     ENTER(c);
+    Carried& cs = c->cs;
     int rc = check_call(c, batch);
     if (rc) return rc;
     if ((rc = check_bn_batch(c, batch))) return rc;
@@ -1565,30 +1654,32 @@ extern "C" int siggan_g_grads(siggan_ctx* c, int32_t batch, const float* z_dev, 
     hipStream_t s = (hipStream_t)stream;
     if ((rc = settle(c, s))) return rc;
     const int B = batch;
-    const bool spec = c->g_fwd_pending != 0;
+    const bool spec = cs.g_fwd_pending != 0;
     if (c->variant == SIGGAN_STEP_ABLATION && !spec)
         return fail(SIGGAN_E_STATE, "ablation step: siggan_g_grads follows the siggan_d_grads / siggan_d_apply of the same iteration");
-    if (spec && (c->g_fwd_pending != B || z_dev))
+    if (spec && (cs.g_fwd_pending != B || z_dev))
         return fail(SIGGAN_E_STATE, "siggan_g_grads after siggan_step_begin must use the same batch and no explicit z (pass it to step_begin)");
-    if (!spec && !z_dev && c->zg_stash == B) z_dev = c->z_g;          // z given to a step_begin that could not pipeline
-    c->zg_stash = 0;
+    if (!spec && !z_dev && cs.zg_stash == B) z_dev = c->z_g;          // z given to a step_begin that could not pipeline
+    cs.zg_stash = 0;
     if (!spec && z_dev && z_dev != c->z) HIPCHK(hipMemcpyAsync(c->z, z_dev, (size_t)B * c->latent * sizeof(float), hipMemcpyDeviceToDevice, s));
     PhaseKey k = make_key(c, 1, B, z_dev != nullptr, false, hp, metrics_dev);
-    c->metrics_last = k.mt;
-    k.spec_g = spec; k.variant = c->variant; k.has_masks = c->abl_masks;
-    k.rode = (spec && c->conv1_rode == B && !c->d_dirty) ? 1 : 0;
-    c->conv1_rode = 0;
-    c->abl_masks = false;
+    cs.metrics_last = k.mt;
+    k.spec_g = spec; k.variant = c->variant; k.has_masks = cs.abl_masks;
+    if (spec) k.gfwd_joined = cs.gfwd_joined;
+    k.rode = (spec && cs.conv1_rode == B && !c->d_dirty) ? 1 : 0;
+    cs.conv1_rode = 0;
+    cs.abl_masks = false;
     // a staged next batch: start its D(real) forward beside this Generator backward (own lane: eager overlap mode only)
-    k.pre_real = c->staged_B == B && c->dreal_B == 0 && (c->mode & SIGGAN_MODE_OVERLAP) != 0 && (c->mode & SIGGAN_MODE_GRAPH) == 0 &&
-                 g_prof == nullptr && c->pending == 0 && !c->sn;
+    k.pre_real = cs.staged_B == B && cs.dreal_B == 0 && (c->mode & SIGGAN_MODE_OVERLAP) != 0 && (c->mode & SIGGAN_MODE_GRAPH) == 0 &&
+                 g_prof == nullptr && cs.pending == 0 && !c->sn;
+    if (k.pre_real) k.staged_src = cs.staged_src;
     if ((rc = run_phase(c, k, s))) return rc;
-    c->g_rode = k.rode ? B : 0; c->g_pre_real = k.pre_real ? B : 0;
-    if (k.pre_real) c->dreal_B = B;
-    c->g_fwd_pending = 0;
+    cs.g_rode = k.rode ? B : 0; cs.g_pre_real = k.pre_real ? B : 0;
+    if (k.pre_real) cs.dreal_B = B;
+    cs.g_fwd_pending = 0;
     c->d_dirty = false;
     c->g_dirty = true;                 // the training forward moved the BatchNorm running statistics
-    c->pending = 2;
+    cs.pending = 2;
     return SIGGAN_OK;
 }
 
@@ -1707,7 +1798,8 @@ extern "C" int siggan_comm_destroy(siggan_ctx* c) {
     if (!c->comm) return SIGGAN_OK;
     HIPCHK(hipDeviceSynchronize());
     NCCLCHK(rccl()->CommDestroy(c->comm));
-    c->comm = nullptr; c->comm_rank = 0; c->comm_world = 1; c->comm_err = 0; c->early_ar = false;
+    c->comm = nullptr; c->comm_rank = 0; c->comm_world = 1; c->comm_err = 0;
+    invalidate(c, INV_COMM);
     return SIGGAN_OK;
 }
 extern "C" int32_t siggan_comm_world(const siggan_ctx* c) { return c ? c->comm_world : -1; }
@@ -1779,7 +1871,7 @@ extern "C" int siggan_debug_tensor(siggan_ctx* c, const char* name, int32_t idx,
     else if (!strcmp(name, "d_a") && dl) { *ptr = c->d_a[idx]; *cap = dsz(idx); }
     else if (!strcmp(name, "d_dv") && dl) { *ptr = c->d_dv[idx]; *cap = dsz(idx); }
     else if (!strcmp(name, "d_a_g") && dl) {     // the Discriminator activations of the last G step (they may start at row B)
-        const int64_t H = c->S >> idx, off = (int64_t)c->g_r0 * H * H * c->dC[idx];
+        const int64_t H = c->S >> idx, off = (int64_t)c->cs.g_r0 * H * H * c->dC[idx];
         *ptr = c->d_a[idx] + (size_t)off * c->es; *cap = dsz(idx) - off;
     }
     else if (!strcmp(name, "z")) { *ptr = c->z; *cap = Bm * c->latent; typed = false; }
@@ -1795,7 +1887,7 @@ extern "C" int siggan_debug_tensor(siggan_ctx* c, const char* name, int32_t idx,
         if (n != 1) return fail(SIGGAN_E_INVALID, "debug scalar %s holds 1 float, %lld asked", name, (long long)n);
         DevGuard dg_(c->cfg.device); HIPCHK(dg_.err);
         HIPCHK(hipStreamSynchronize((hipStream_t)stream));
-        const float v = !strcmp(name, "rode") ? (float)c->g_rode : !strcmp(name, "pre_real") ? (float)c->g_pre_real
+        const float v = !strcmp(name, "rode") ? (float)c->cs.g_rode : !strcmp(name, "pre_real") ? (float)c->cs.g_pre_real
                                                                                                : (float)__atomic_load_n(c->ride_late, __ATOMIC_ACQUIRE);
         HIPCHK(hipMemcpy(out_dev, &v, sizeof v, hipMemcpyHostToDevice));
         return SIGGAN_OK;
@@ -1803,11 +1895,11 @@ extern "C" int siggan_debug_tensor(siggan_ctx* c, const char* name, int32_t idx,
     else return fail(SIGGAN_E_INVALID, "unknown debug tensor %s[%d]", name, idx);
     if (n > capv) return fail(SIGGAN_E_INVALID, "debug tensor %s[%d] holds %lld floats, %lld asked", name, idx, (long long)capv, (long long)n);
     DevGuard dg_(c->cfg.device); HIPCHK(dg_.err);
-    if (!strcmp(name, "g_a") && idx == c->Lg && c->ga_last_B) {
+    if (!strcmp(name, "g_a") && idx == c->Lg && c->cs.ga_last_B) {
         // after a training forward the last block's activation exists only as y + the BatchNorm table: form it now
         const int64_t H = c->S;
         HIPCHK(hipDeviceSynchronize());
-        launch_bn_relu(c->dt, c->g_y[idx], c->g_a[idx], (int64_t)c->ga_last_B * H * H, c->gC[idx], c->g_bn[idx], c->cfg.g_leaky_slope,
+        launch_bn_relu(c->dt, c->g_y[idx], c->g_a[idx], (int64_t)c->cs.ga_last_B * H * H, c->gC[idx], c->g_bn[idx], c->cfg.g_leaky_slope,
                        (hipStream_t)stream);
         LAUNCHCHK();
     }

@@ -417,6 +417,45 @@ def test_execution_modes_are_bitwise_identical_at_timed_shapes(dtype, size, late
     test_execution_modes_are_bitwise_identical(dtype, size, latent, batch)
 
 
+def test_debug_hooks_follow_a_replayed_g_step(size=64, latent=100):
+    """What a G step leaves behind for siggan_debug_tensor -- the first workspace row of its Discriminator pass ('d_a_g') and
+    the batch whose last Generator activation was not materialised ('g_a'[Lg]) -- is committed on every graph replay, not only
+    when the phase is captured: after G steps at batch 4, 5, an eval forward at batch 4 and a G step at batch 4, the hooks and
+    the arenas must be bit for bit what the eager engine leaves.  That fourth call is still a first capture (the eval forward
+    cleared the 'packs are stale' flags, which are part of the graph key), so calls 2-4 are made a second time, as replays of
+    graphs captured in the first round, and the hooks are also read right after the replayed batch-5 step, at batch 5: the
+    last capture before it was a batch-4 step, so state left by a capture alone reads from row 4 and forms 4 images there."""
+    from hipcommon import cuda, make_engine
+    zs = [cuda(torch.from_numpy(I.gen_z(b, latent, 70 + i))) for i, b in enumerate((4, 5, 4, 4))]
+    a, b = engs = [make_engine(size, latent, 5, warm=True) for _ in range(2)]
+    a.set_mode(graph=True, overlap=False)
+    b.set_mode(graph=False, overlap=False)
+    lg = len(O.G_CHAIN[size]) - 1
+
+    def same_hooks(batch, where):
+        for l, c in enumerate(O.D_CHAIN[size], start=1):
+            shape = (batch, size >> l, size >> l, c)
+            assert torch.equal(a.debug_tensor("d_a_g", l, shape), b.debug_tensor("d_a_g", l, shape)), (where, "d_a_g", l)
+        shape = (batch, size, size, 32)
+        assert torch.equal(a.debug_tensor("g_a", lg, shape), b.debug_tensor("g_a", lg, shape)), (where, "g_a")
+
+    for rnd in range(2):
+        for eng in engs:
+            if rnd == 0:
+                eng.g_step(4, zs[0])
+            eng.g_step(5, zs[1])
+        if rnd == 1:
+            same_hooks(5, "replayed batch-5 step")
+        for eng in engs:
+            eng.g_forward(zs[2], training=False)
+            eng.g_step(4, zs[3])
+        same_hooks(4, f"round {rnd}, batch-4 step")
+        for n in ("g_params", "d_params", "g_exp_avg", "g_exp_avg_sq", "d_exp_avg", "d_exp_avg_sq"):
+            assert torch.equal(getattr(a, n), getattr(b, n)), (rnd, n)
+    for eng in engs:
+        eng.close()
+
+
 @pytest.mark.parametrize("dtype,size,latent,batch", [("f32", 64, 100, 16), ("bf16", 64, 100, 16), ("f32", 128, 128, 4)] + TIMED)
 def test_update_launch_leaves_the_packs_the_prepare_pass_would(dtype, size, latent, batch):
     """k_adam_pack (the optimiser update that also writes the MFMA weight packs, the permuted one-channel weights and the
