@@ -11,8 +11,9 @@
  *            -> Linear(512,E) -> x / max(||x||_2, 1e-12)
  *   head     |e1 - e2| -> Linear(E,64) + ReLU -> Linear(64,1) -> sigmoid
  *
- * Dropout is the identity in eval mode.  Training the verifier (backward, contrastive loss, augmentations) and 16-bit
- * storage are not part of this interface.  fp32 only; conv2 / conv3 / fc1 run on v_mfma_f32_32x32x2_f32.
+ * Dropout is the identity in eval mode.  The train step (train-mode forward, BCE + contrastive loss, backward, Adam) is
+ * siggan_verifier_train.h's interface; the reference's random augmentations stay on the host and 16-bit storage is not
+ * built.  fp32 only; conv2 / conv3 / fc1 run on v_mfma_f32_32x32x2_f32.
  *
  * Conventions are those of siggan.h: plain pointers and sizes, every call enqueues on `stream` and never synchronises
  * the host, 0 = OK / negative = SIGGAN_E_* with the message in siggan_last_error(), entry points run on the context's

@@ -1,4 +1,4 @@
-"""ctypes binding of the C ABI in include/siggan.h (and siggan_mlp.h, siggan_verifier.h).
+"""ctypes binding of the C ABI in include/siggan.h (and siggan_mlp.h, siggan_verifier.h, siggan_verifier_train.h).
 
 The shared library is built in-tree by ``__graft_entry__.build()`` / ``csrc/Makefile`` and must be
 present: there is no CPU or PyTorch fallback for this path -- a missing or stale library raises.
@@ -145,6 +145,31 @@ _VERIFIER_SIGNATURES = {
 }
 VERIFIER_EXPORTS = tuple(_VERIFIER_SIGNATURES)
 
+# the verifier's train step (include/siggan_verifier_train.h): again only new symbols
+VT_PARAM_TENSORS, VT_METRICS = 20, 4
+VT_RUNNING_FIELDS = ("bn1_running_mean", "bn1_running_var", "bn2_running_mean", "bn2_running_var", "bn3_running_mean",
+                     "bn3_running_var")
+
+
+class VerifierTrainStorage(C.Structure):
+    _fields_ = [(n, C.c_void_p) for n in ("params", "grads", "exp_avg", "exp_avg_sq") + VT_RUNNING_FIELDS] + [("bn_eps", C.c_float)]
+
+
+_D = C.c_double
+_VERIFIER_TRAIN_SIGNATURES = {
+    "siggan_verifier_trainer_create": (C.c_int, [_I32, _I32, _I32, C.POINTER(_P)]),
+    "siggan_verifier_trainer_destroy": (C.c_int, [_P]),
+    "siggan_verifier_trainer_param_count": (_I64, [_P]),
+    "siggan_verifier_trainer_param_span": (C.c_int, [_P, _I32, C.POINTER(_I64), C.POINTER(_I64)]),
+    "siggan_verifier_trainer_bind": (C.c_int, [_P, C.POINTER(VerifierTrainStorage), _I64]),
+    "siggan_verifier_trainer_seed": (C.c_int, [_P, C.c_uint64, C.c_uint64]),
+    "siggan_verifier_train_grads": (C.c_int, [_P, _P, _P, _I32, _P, _I32, _P, _P, _I32, _P, _P]),
+    "siggan_verifier_train_apply": (C.c_int, [_P, _D, _D, _D, _D, _P]),
+    "siggan_verifier_train_step": (C.c_int, [_P, _P, _P, _I32, _P, _I32, _P, _P, _I32, _D, _D, _D, _D, _P, _P]),
+    "siggan_verifier_train_debug": (C.c_int, [_P, C.c_char_p, _P, _I64, _P]),
+}
+VERIFIER_TRAIN_EXPORTS = tuple(_VERIFIER_TRAIN_SIGNATURES)
+
 _lib = None
 
 
@@ -158,7 +183,7 @@ def load():
             f"{LIB_PATH} is missing: build it with `python -c 'import __graft_entry__ as g; g.build()'` "
             "(or `make -C signature-gan_amd/csrc`). This path has no CPU/PyTorch fallback.")
     lib = C.CDLL(LIB_PATH)
-    for name, (res, args) in {**_SIGNATURES, **_VERIFIER_SIGNATURES}.items():
+    for name, (res, args) in {**_SIGNATURES, **_VERIFIER_SIGNATURES, **_VERIFIER_TRAIN_SIGNATURES}.items():
         fn = getattr(lib, name)          # AttributeError if the library does not export the symbol
         fn.restype, fn.argtypes = res, args
     if lib.siggan_abi_version() != ABI_VERSION:
