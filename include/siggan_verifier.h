@@ -12,8 +12,8 @@
  *   head     |e1 - e2| -> Linear(E,64) + ReLU -> Linear(64,1) -> sigmoid
  *
  * Dropout is the identity in eval mode.  The train step (train-mode forward, BCE + contrastive loss, backward, Adam) is
- * siggan_verifier_train.h's interface; the reference's random augmentations stay on the host and 16-bit storage is not
- * built.  fp32 only; conv2 / conv3 / fc1 run on v_mfma_f32_32x32x2_f32.
+ * siggan_verifier_train.h's interface; the trainer's input pipeline with the reference's random augmentations is
+ * siggan_verifier_data.h's; 16-bit storage is not built.  fp32 only; conv2 / conv3 / fc1 run on v_mfma_f32_32x32x2_f32.
  *
  * Conventions are those of siggan.h: plain pointers and sizes, every call enqueues on `stream` and never synchronises
  * the host, 0 = OK / negative = SIGGAN_E_* with the message in siggan_last_error(), entry points run on the context's

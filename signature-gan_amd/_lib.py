@@ -1,4 +1,5 @@
-"""ctypes binding of the C ABI in include/siggan.h (and siggan_mlp.h, siggan_verifier.h, siggan_verifier_train.h).
+"""ctypes binding of the C ABI in include/siggan.h (and siggan_mlp.h, siggan_verifier.h, siggan_verifier_train.h,
+siggan_verifier_data.h).
 
 The shared library is built in-tree by ``__graft_entry__.build()`` / ``csrc/Makefile`` and must be
 present: there is no CPU or PyTorch fallback for this path -- a missing or stale library raises.
@@ -170,6 +171,12 @@ _VERIFIER_TRAIN_SIGNATURES = {
 }
 VERIFIER_TRAIN_EXPORTS = tuple(_VERIFIER_TRAIN_SIGNATURES)
 
+# the verifier trainer's input pipeline (include/siggan_verifier_data.h): one more symbol, listed on its own
+_VERIFIER_DATA_SIGNATURES = {
+    "siggan_pairs_augment": (C.c_int, [_I32, _P, _I64, _P, _P, _P, _P, _I32, _I32, _I32, _P]),
+}
+VERIFIER_DATA_EXPORTS = tuple(_VERIFIER_DATA_SIGNATURES)
+
 _lib = None
 
 
@@ -183,7 +190,8 @@ def load():
             f"{LIB_PATH} is missing: build it with `python -c 'import __graft_entry__ as g; g.build()'` "
             "(or `make -C signature-gan_amd/csrc`). This path has no CPU/PyTorch fallback.")
     lib = C.CDLL(LIB_PATH)
-    for name, (res, args) in {**_SIGNATURES, **_VERIFIER_SIGNATURES, **_VERIFIER_TRAIN_SIGNATURES}.items():
+    for name, (res, args) in {**_SIGNATURES, **_VERIFIER_SIGNATURES, **_VERIFIER_TRAIN_SIGNATURES,
+                              **_VERIFIER_DATA_SIGNATURES}.items():
         fn = getattr(lib, name)          # AttributeError if the library does not export the symbol
         fn.restype, fn.argtypes = res, args
     if lib.siggan_abi_version() != ABI_VERSION:

@@ -11,7 +11,10 @@ The parameters of a model that has trained are views into one flat arena (gradie
 are accumulated on the device and read once per epoch.
 
 The reference's random training transforms (RandomAffine, RandomHorizontalFlip) run on the CPU through torchvision when it
-can be imported; without it ``train_model`` trains on the deterministic chain and says so in one line.
+can be imported; without it ``train_model`` trains on the deterministic chain and says so in one line.  That is the default
+``input_pipeline="host"``.  With ``input_pipeline="device"`` (``--input_pipeline device``) the images are decoded once into an
+HBM-resident uint8 cache and every batch is gathered and augmented by one HIP launch with the reference's draws
+(``verifier_data.DevicePairLoader``); torchvision is not needed.
 """
 import argparse
 import ctypes as C
@@ -397,12 +400,21 @@ def _transforms():
     return train, SV.default_transform
 
 
-def _fit(tag: str, dataset, epochs, output_path, file_name, batch_size, learning_rate, embedding_dim, device, extra):
+INPUT_PIPELINES = ("host", "device")
+
+
+def _fit(tag: str, dataset, epochs, output_path, file_name, batch_size, learning_rate, embedding_dim, device, extra,
+         input_pipeline: str = "host"):
     train_size = int(0.8 * len(dataset))
     val_size = len(dataset) - train_size
     train_dataset, val_dataset = torch.utils.data.random_split(dataset, [train_size, val_size])
-    train_loader = DataLoader(train_dataset, batch_size=batch_size, shuffle=True, num_workers=0)
-    val_loader = DataLoader(val_dataset, batch_size=batch_size, shuffle=False, num_workers=0)
+    if input_pipeline == "device":
+        from .verifier_data import DevicePairLoader
+        train_loader = DevicePairLoader(train_dataset, batch_size, shuffle=True, augment=True, device=device)
+        val_loader = DevicePairLoader(val_dataset, batch_size, shuffle=False, augment=False, device=device)
+    else:
+        train_loader = DataLoader(train_dataset, batch_size=batch_size, shuffle=True, num_workers=0)
+        val_loader = DataLoader(val_dataset, batch_size=batch_size, shuffle=False, num_workers=0)
     model = SiameseNetwork(embedding_dim=embedding_dim, max_pairs=batch_size).to(device)
     optimizer = Adam(model, lr=learning_rate)
     scheduler = torch.optim.lr_scheduler.StepLR(optimizer, step_size=10, gamma=0.5)
@@ -432,9 +444,13 @@ def checkpoint_dict(model, embedding_dim, val_accuracy, epoch, **extra):
 
 
 def train_model(data_dir: str, synthetic_dir: Optional[str], epochs: int, model_output: str, batch_size: int = 32,
-                learning_rate: float = 0.001, embedding_dim: int = 128, device: Optional[str] = None) -> Dict[str, str]:
+                learning_rate: float = 0.001, embedding_dim: int = 128, device: Optional[str] = None,
+                input_pipeline: str = "host") -> Dict[str, str]:
     """Trains the baseline model (real signatures) and, with a synthetic directory, the augmented one (real + synthetic);
-    returns the paths of the saved best-validation checkpoints."""
+    returns the paths of the saved best-validation checkpoints.  input_pipeline: "host" (the reference's DataLoader over
+    Pillow decodes) or "device" (HBM-resident cache + one augmentation launch per batch; module docstring)."""
+    if input_pipeline not in INPUT_PIPELINES:
+        raise ValueError(f"input_pipeline must be one of {INPUT_PIPELINES}, got {input_pipeline!r}")
     if device is None:
         device = 'cuda' if torch.cuda.is_available() else 'cpu'
     device = torch.device(device)
@@ -443,7 +459,7 @@ def train_model(data_dir: str, synthetic_dir: Optional[str], epochs: int, model_
     print(f"Training on device: {device}")
     output_path = Path(model_output)
     output_path.mkdir(parents=True, exist_ok=True)
-    train_transform, _ = _transforms()
+    train_transform = None if input_pipeline == "device" else _transforms()[0]      # the device loader decodes the files itself
     saved_models = {}
 
     print("\n" + "="*60)
@@ -455,7 +471,7 @@ def train_model(data_dir: str, synthetic_dir: Optional[str], epochs: int, model_
         print("Please ensure data directory contains signature images organized by user.")
     else:
         baseline_path = _fit("baseline", baseline_dataset, epochs, output_path, 'baseline_siamese_model.pth', batch_size,
-                             learning_rate, embedding_dim, device, {})
+                             learning_rate, embedding_dim, device, {}, input_pipeline)
         saved_models['baseline'] = str(baseline_path)
         print(f"\nBaseline model saved to: {baseline_path}")
 
@@ -469,7 +485,7 @@ def train_model(data_dir: str, synthetic_dir: Optional[str], epochs: int, model_
             print("WARNING: No training pairs generated for augmented model.")
         else:
             augmented_path = _fit("augmented", augmented_dataset, epochs, output_path, 'augmented_siamese_model.pth', batch_size,
-                                  learning_rate, embedding_dim, device, {'includes_synthetic': True})
+                                  learning_rate, embedding_dim, device, {'includes_synthetic': True}, input_pipeline)
             saved_models['augmented'] = str(augmented_path)
             print(f"\nAugmented model saved to: {augmented_path}")
     else:
@@ -489,6 +505,8 @@ def main(argv=None):
     parser.add_argument('--learning_rate', type=float, default=0.001, help='Learning rate for optimizer')
     parser.add_argument('--embedding_dim', type=int, default=128, help='Dimension of embedding vectors')
     parser.add_argument('--device', type=str, default=None, choices=['cuda', 'cpu'], help='Device to train on (default: auto-detect)')
+    parser.add_argument('--input_pipeline', type=str, default='host', choices=list(INPUT_PIPELINES),
+                        help='host: DataLoader over Pillow decodes; device: HBM-resident cache + on-device augmentation')
     args = parser.parse_args(argv)
 
     print("="*60)
@@ -505,7 +523,7 @@ def main(argv=None):
 
     saved_models = train_model(data_dir=args.data_dir, synthetic_dir=args.synthetic_dir, epochs=args.epochs,
                                model_output=args.model_output, batch_size=args.batch_size, learning_rate=args.learning_rate,
-                               embedding_dim=args.embedding_dim, device=args.device)
+                               embedding_dim=args.embedding_dim, device=args.device, input_pipeline=args.input_pipeline)
 
     print("\n" + "="*60)
     print("Training Complete!")
