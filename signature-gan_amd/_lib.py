@@ -1,5 +1,5 @@
 """ctypes binding of the C ABI in include/siggan.h (and siggan_mlp.h, siggan_verifier.h, siggan_verifier_train.h,
-siggan_verifier_data.h).
+siggan_verifier_data.h, siggan_moments.h).
 
 The shared library is built in-tree by ``__graft_entry__.build()`` / ``csrc/Makefile`` and must be
 present: there is no CPU or PyTorch fallback for this path -- a missing or stale library raises.
@@ -177,6 +177,17 @@ _VERIFIER_DATA_SIGNATURES = {
 }
 VERIFIER_DATA_EXPORTS = tuple(_VERIFIER_DATA_SIGNATURES)
 
+# streaming fp64 feature moments (include/siggan_moments.h): new symbols again, listed on their own
+MOMENTS_MAX_DIM = 1024
+_MOMENTS_SIGNATURES = {
+    "siggan_moments_create": (C.c_int, [_I32, _I32, C.POINTER(_P)]),
+    "siggan_moments_destroy": (C.c_int, [_P]),
+    "siggan_moments_reset": (C.c_int, [_P, _P]),
+    "siggan_moments_update": (C.c_int, [_P, _P, _I32, _P]),
+    "siggan_moments_read": (C.c_int, [_P, _P, _P, C.POINTER(_I64), _P]),
+}
+MOMENTS_EXPORTS = tuple(_MOMENTS_SIGNATURES)
+
 _lib = None
 
 
@@ -191,7 +202,7 @@ def load():
             "(or `make -C signature-gan_amd/csrc`). This path has no CPU/PyTorch fallback.")
     lib = C.CDLL(LIB_PATH)
     for name, (res, args) in {**_SIGNATURES, **_VERIFIER_SIGNATURES, **_VERIFIER_TRAIN_SIGNATURES,
-                              **_VERIFIER_DATA_SIGNATURES}.items():
+                              **_VERIFIER_DATA_SIGNATURES, **_MOMENTS_SIGNATURES}.items():
         fn = getattr(lib, name)          # AttributeError if the library does not export the symbol
         fn.restype, fn.argtypes = res, args
     if lib.siggan_abi_version() != ABI_VERSION:

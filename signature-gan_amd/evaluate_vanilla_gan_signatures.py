@@ -7,7 +7,13 @@ What differs is where the work happens.  Generation goes through ``Engine.g_gene
 Generator's last kernel counts the pixels itself, so evaluating N samples brings 12 bytes per image to the host, plus the
 fp32 images of the samples the grids show -- not 4 * S * S bytes for every sample.  Real images are decoded and resized by
 the loader's helper, normalised on the device and counted by ``siggan_image_stats``.  FID / LPIPS are reported as not
-computed (utils/metrics.py of this package)."""
+computed (utils/metrics.py of this package).
+
+Beyond the reference: ``--verifier_checkpoint PATH`` adds a Frechet distance between the real and the generated images in
+the embedding space of the Siamese verifier (signature_verifier_eval), the FID construction over a network trained here.
+Every generated batch's bytes go through ``embed_u8`` into an fp64 accumulator while they are still on the device
+(utils/frechet.py), the real images take the same route, and dim * (dim + 1) doubles per set reach the host.  Without the
+flag nothing changes: stdout, report keys and exit codes are the reference's."""
 import argparse
 import json
 import sys
@@ -22,19 +28,25 @@ from .data_loader_signatures import FILL, SignatureDataset, normalize_lut
 from .generator_vanilla_gan import Generator
 from .train_vanilla_gan_signatures import save_sample_grid
 from .utils.inference import load_generator_and_config
-from .utils.metrics import (INCEPTION_AVAILABLE, LPIPS_AVAILABLE, calculate_fid, calculate_foreground_ratio,
-                            calculate_lpips_diversity, calculate_stroke_density, foreground_ratio_from_counts,
-                            stroke_density_from_counts)
+from .utils.frechet import FeatureMoments, embedding_spread, frechet_distance
+from .utils.metrics import (INCEPTION_AVAILABLE, LPIPS_AVAILABLE, accumulate_verifier_moments, calculate_fid,
+                            calculate_foreground_ratio, calculate_lpips_diversity, calculate_stroke_density,
+                            foreground_ratio_from_counts, stroke_density_from_counts)
 
 THRESHOLD = 0.5          # the threshold compute_metrics passes to both statistics (evaluate_vanilla_gan_signatures.py:306,318)
+VERIFIER_IMAGE_SIZE = 64
 
 
 class GeneratedSamples:
     """What generate_samples hands on: the per-image stroke counters of all N samples (``counts``, int (N, 3) against
-    ``threshold``) and the fp32 images of the first ``len(images)`` of them (CPU, (K, 1, S, S) in [-1, 1])."""
+    ``threshold``) and the fp32 images of the first ``len(images)`` of them (CPU, (K, 1, S, S) in [-1, 1]).  When the
+    samples were also embedded on the way (generate_samples' ``embedding_sink``): ``embedding_stats``, the finished
+    (n, mean, cov) of their embeddings, or ``embedding_error`` saying why there is none."""
 
-    def __init__(self, n: int, image_shape: Tuple[int, int, int], counts: np.ndarray, images: torch.Tensor, threshold: float):
+    def __init__(self, n: int, image_shape: Tuple[int, int, int], counts: np.ndarray, images: torch.Tensor, threshold: float,
+                 embedding_stats: Optional[Tuple[int, np.ndarray, np.ndarray]] = None, embedding_error: Optional[str] = None):
         self.n, self.image_shape, self.counts, self.images, self.threshold = n, tuple(image_shape), counts, images, threshold
+        self.embedding_stats, self.embedding_error = embedding_stats, embedding_error
 
     def __len__(self) -> int:
         return self.n
@@ -58,11 +70,50 @@ def load_generator_from_checkpoint(checkpoint_path: Path, device: torch.device) 
     return generator, config
 
 
+class EmbeddingSink:
+    """One image set on its way into the verifier's embedding space: ``update`` embeds a batch (uint8 (B, 64, 64) or fp32
+    (B, 1, 64, 64), on the device) and adds the embeddings to an fp64 accumulator there; ``finish`` -> (n, mean, cov)."""
+
+    def __init__(self, model) -> None:
+        self.model = model
+        self.moments = FeatureMoments(model.embedding_dim, next(model.parameters()).device)
+
+    def update(self, images: torch.Tensor) -> None:
+        accumulate_verifier_moments(self.moments, images, self.model)
+
+    def finish(self) -> Tuple[int, np.ndarray, np.ndarray]:
+        try:
+            return self.moments.finish()
+        finally:
+            self.moments.close()
+
+
+class VerifierFeatures:
+    """The Siamese verifier behind ``--verifier_checkpoint``: ``model`` (signature_verifier_eval.load_model), or ``error``
+    saying why the Frechet distance cannot be computed with it -- the report records that, the evaluation goes on."""
+
+    def __init__(self, checkpoint: Path, device: torch.device, image_size: int) -> None:
+        self.checkpoint, self.model, self.error = str(checkpoint), None, None
+        if image_size != VERIFIER_IMAGE_SIZE:
+            self.error = f"the verifier takes {VERIFIER_IMAGE_SIZE}x{VERIFIER_IMAGE_SIZE} images"
+            return
+        try:
+            from .signature_verifier_eval import load_model
+            self.model, _ = load_model(self.checkpoint, device)
+        except Exception as e:                                  # noqa: BLE001 -- recorded like fid_error
+            self.error = f"could not load the verifier checkpoint: {e}"
+
+    def sink(self) -> Optional[EmbeddingSink]:
+        return EmbeddingSink(self.model) if self.model is not None else None
+
+
 @torch.no_grad()
 def generate_samples(generator: Generator, n_samples: int, latent_dim: int, device: torch.device, batch_size: int = 64,
-                     keep_images: Optional[int] = None, threshold: float = THRESHOLD) -> GeneratedSamples:
+                     keep_images: Optional[int] = None, threshold: float = THRESHOLD,
+                     embedding_sink: Optional[EmbeddingSink] = None) -> GeneratedSamples:
     """N samples, z = torch.randn per batch as the reference draws it (so a seed means the same).  ``keep_images``: how
-    many leading samples to bring back as fp32 images (None: all, what the reference returns)."""
+    many leading samples to bring back as fp32 images (None: all, what the reference returns).  ``embedding_sink``: receives
+    every batch's uint8 tensor while it is on the device; its finished statistics travel in the result."""
     generator.eval()
     eng = generator._require_engine()
     keep = n_samples if keep_images is None else max(0, min(int(keep_images), n_samples))
@@ -74,17 +125,25 @@ def generate_samples(generator: Generator, n_samples: int, latent_dim: int, devi
         z = torch.randn(b, latent_dim, device=device)
         want = min(b, keep - i * batch_size)
         if want > 0:
-            _, st, img = eng.g_generate_u8(z, threshold=threshold, want_f32=True)
+            u8, st, img = eng.g_generate_u8(z, threshold=threshold, want_f32=True)
             images.append(img[:want].cpu())
         else:
-            _, st = eng.g_generate_u8(z, threshold=threshold)
+            u8, st = eng.g_generate_u8(z, threshold=threshold)
         counts.append(st)
+        if embedding_sink is not None:
+            embedding_sink.update(u8)
         if (i + 1) % 10 == 0 or i == n_batches - 1:
             print(f"  Generated {min((i + 1) * batch_size, n_samples)}/{n_samples} samples")
     s = generator.output_size
     kept = torch.cat(images, dim=0) if images else torch.empty(0, 1, s, s)
     all_counts = torch.cat(counts, dim=0).cpu().numpy() if counts else np.zeros((0, 3), np.int32)
-    return GeneratedSamples(n_samples, (1, s, s), all_counts, kept, threshold)
+    stats, error = None, None
+    if embedding_sink is not None:
+        try:
+            stats = embedding_sink.finish()
+        except ValueError as e:                                 # fewer than 2 samples: the report says so
+            error = str(e)
+    return GeneratedSamples(n_samples, (1, s, s), all_counts, kept, threshold, stats, error)
 
 
 def load_real_images(real_dir: Path, n_images: int, image_size: int, device: torch.device) -> torch.Tensor:
@@ -158,8 +217,34 @@ def _foreground(images) -> Dict[str, Any]:
     return calculate_foreground_ratio(images, threshold=THRESHOLD)
 
 
-def compute_metrics(fake_images, real_images: Optional[torch.Tensor], device: torch.device) -> Dict[str, Any]:
-    """The report's ``metrics`` dictionary.  ``fake_images``: a GeneratedSamples (its counters are used) or a tensor."""
+def _verifier_frechet(metrics: Dict[str, Any], fake_images, real_images: Optional[torch.Tensor],
+                      verifier: VerifierFeatures) -> None:
+    """The ``verifier_*`` keys of the report; any failure is recorded as ``verifier_frechet_error``, like ``fid_error``."""
+    metrics["verifier_checkpoint"] = verifier.checkpoint
+    print("Computing verifier Frechet distance...")
+    try:
+        if verifier.error:
+            raise ValueError(verifier.error)
+        if real_images is None:
+            raise ValueError("no real images provided")
+        fake_stats = getattr(fake_images, "embedding_stats", None)
+        if fake_stats is None:
+            raise ValueError(getattr(fake_images, "embedding_error", None) or "the generated samples were not embedded")
+        sink = verifier.sink()
+        sink.update(real_images)
+        (_, mu_r, cov_r), (_, mu_f, cov_f) = sink.finish(), fake_stats
+        metrics["verifier_frechet_distance"] = frechet_distance(mu_r, cov_r, mu_f, cov_f)
+        metrics["verifier_embedding_spread"] = {"generated": embedding_spread(cov_f), "real": embedding_spread(cov_r)}
+        print(f"  Verifier Frechet Distance: {metrics['verifier_frechet_distance']:.4f}")
+    except Exception as e:                                      # noqa: BLE001 -- the report records any failure
+        print(f"  Skipping verifier Frechet distance: {e}")
+        metrics["verifier_frechet_distance"], metrics["verifier_frechet_error"] = None, str(e)
+
+
+def compute_metrics(fake_images, real_images: Optional[torch.Tensor], device: torch.device,
+                    verifier: Optional[VerifierFeatures] = None) -> Dict[str, Any]:
+    """The report's ``metrics`` dictionary.  ``fake_images``: a GeneratedSamples (its counters are used) or a tensor.
+    ``verifier``: add the Frechet distance over its embeddings (the ``verifier_*`` keys; none without it)."""
     metrics: Dict[str, Any] = {"n_samples": len(fake_images), "image_shape": list(fake_images.shape[1:]),
                                "metrics_computed_at": datetime.now().isoformat()}
     if real_images is not None and INCEPTION_AVAILABLE:
@@ -189,6 +274,9 @@ def compute_metrics(fake_images, real_images: Optional[torch.Tensor], device: to
     else:
         print("  Skipping LPIPS: lpips package not available")
         metrics["lpips_diversity"], metrics["lpips_error"] = None, "lpips package not available"
+
+    if verifier is not None:
+        _verifier_frechet(metrics, fake_images, real_images, verifier)
 
     print("Computing stroke density distribution...")
     try:
@@ -221,6 +309,8 @@ def save_evaluation_report(metrics: Dict[str, Any], config: Dict[str, Any], outp
                            grid_paths: List[Path]) -> Path:
     output_dir = Path(output_dir)
     output_dir.mkdir(parents=True, exist_ok=True)
+    # the verifier's distance joins the summary of a report that has it; a report made without the flag keeps its keys
+    extra = {"verifier_frechet_distance": metrics["verifier_frechet_distance"]} if "verifier_frechet_distance" in metrics else {}
     report = {
         "evaluation_info": {"checkpoint": str(checkpoint_path), "evaluation_timestamp": datetime.now().isoformat(),
                             "sample_grids": [str(p) for p in grid_paths]},
@@ -229,7 +319,7 @@ def save_evaluation_report(metrics: Dict[str, Any], config: Dict[str, Any], outp
         "summary": {"fid_score": metrics.get("fid_score"), "lpips_diversity": metrics.get("lpips_diversity"),
                     "stroke_density_mean": (metrics.get("stroke_density") or {}).get("mean"),
                     "foreground_ratio_mean": (metrics.get("foreground_ratio") or {}).get("mean"),
-                    "n_samples_evaluated": metrics.get("n_samples")},
+                    "n_samples_evaluated": metrics.get("n_samples"), **extra},
     }
     path = output_dir / f"evaluation_report_{datetime.now().strftime('%Y%m%d_%H%M%S')}.json"
     with open(path, "w") as f:
@@ -249,6 +339,10 @@ def print_summary(metrics: Dict[str, Any]) -> None:
           else f"FID Score: Not computed - {metrics.get('fid_error', 'unknown reason')}")
     print(f"LPIPS Diversity: {lp:.4f} (higher = more diverse)" if lp is not None
           else f"LPIPS Diversity: Not computed - {metrics.get('lpips_error', 'unknown reason')}")
+    if "verifier_frechet_distance" in metrics:
+        vfd = metrics["verifier_frechet_distance"]
+        print(f"Verifier Frechet Distance: {vfd:.4f} (lower is better)" if vfd is not None
+              else f"Verifier Frechet Distance: Not computed - {metrics.get('verifier_frechet_error', 'unknown reason')}")
     print("\n--- Stroke Analysis ---")
     stroke = metrics.get("stroke_density")
     if stroke:
@@ -274,6 +368,12 @@ def print_summary(metrics: Dict[str, Any]) -> None:
     print("\n" + bar)
 
 
+class _Args(argparse.Namespace):
+    """The flags this tool adds to the reference's are opt-in all the way: they read as their default, and a command line
+    without them parses to the reference's attributes and nothing else."""
+    verifier_checkpoint = None
+
+
 def parse_args(argv=None) -> argparse.Namespace:
     p = argparse.ArgumentParser(description="Evaluate trained Vanilla GAN for signature generation (MI355X HIP engine)",
                                 formatter_class=argparse.ArgumentDefaultsHelpFormatter)
@@ -286,7 +386,9 @@ def parse_args(argv=None) -> argparse.Namespace:
     p.add_argument("--grid_size", type=int, default=64, help="Number of samples per grid")
     p.add_argument("--device", type=str, default=None, help="Device to use. Auto-detected if not specified.")
     p.add_argument("--seed", type=int, default=None, help="Random seed for reproducibility")
-    return p.parse_args(argv)
+    p.add_argument("--verifier_checkpoint", type=str, default=None,
+                   help="Siamese verifier checkpoint: adds a Frechet distance over its embeddings (needs --real_dir)")
+    return p.parse_args(argv, namespace=_Args())
 
 
 def main(argv=None) -> int:
@@ -301,8 +403,11 @@ def main(argv=None) -> int:
     real_dir = Path(a.real_dir) if a.real_dir else None
     try:
         generator, config = load_generator_from_checkpoint(checkpoint_path, device)
+        verifier = (VerifierFeatures(Path(a.verifier_checkpoint), device, generator.output_size)
+                    if a.verifier_checkpoint else None)
         fake = generate_samples(generator, a.n_samples, generator.latent_dim, device, a.batch_size,
-                                keep_images=max(0, a.n_grids) * a.grid_size)
+                                keep_images=max(0, a.n_grids) * a.grid_size,
+                                embedding_sink=verifier.sink() if verifier is not None else None)
         print("\nCreating sample grids...")
         grid_paths = create_sample_grids(fake, output_dir, a.n_grids, a.grid_size)
         real = None
@@ -312,7 +417,7 @@ def main(argv=None) -> int:
             except Exception as e:                              # noqa: BLE001 -- the evaluation goes on without them
                 print(f"Warning: Could not load real images: {e}")
         print("\nComputing evaluation metrics...")
-        metrics = compute_metrics(fake, real, device)
+        metrics = compute_metrics(fake, real, device, verifier)
         report_path = save_evaluation_report(metrics, config, output_dir, checkpoint_path, grid_paths)
         print_summary(metrics)
         print("\nEvaluation complete!")

@@ -8,14 +8,17 @@ the image sizes built here (P a power of two, count < 2**24), so it equals the r
 for another P the two may differ in the last bit.
 
 FID and LPIPS need downloaded network weights; computing them is not built.  The availability flags and the ImportError
-texts are the reference's, so callers (the evaluation CLI) report them the same way."""
+texts are the reference's, so callers (the evaluation CLI) report them the same way.  What IS built is the same
+construction over a network the user trains here: ``calculate_verifier_frechet_distance``, a Frechet distance between two
+image sets in the Siamese verifier's embedding space (utils/frechet.py; the statistics are accumulated on the device)."""
 from collections import defaultdict
-from typing import Dict, List, Optional, Union
+from typing import Any, Dict, List, Optional, Union
 
 import numpy as np
 import torch
 
 from .._lib import IS_INK_SIGNED, IS_INK_UNIT, IS_NEG
+from .frechet import FeatureMoments, embedding_spread, frechet_distance
 
 try:
     from torchvision.models import inception_v3  # noqa: F401
@@ -40,6 +43,44 @@ def calculate_lpips_diversity(images_list: List[torch.Tensor], device: Optional[
     if not LPIPS_AVAILABLE:
         raise ImportError("lpips package required: pip install lpips")
     raise NotImplementedError("LPIPS needs AlexNet weights, which this build does not ship or download")
+
+
+# ---- Frechet distance over verifier embeddings (device moments, host root) ---------------------------------------------
+def accumulate_verifier_moments(moments: FeatureMoments, images: torch.Tensor, verifier, max_batch: Optional[int] = None) -> None:
+    """Embed ``images`` -- fp32 (N, 1, 64, 64) in [-1, 1] or uint8 (N, 64, 64), on the verifier's device -- in chunks of at
+    most min(max_batch, verifier.max_images) and add every chunk's embeddings to ``moments``; nothing reaches the host."""
+    if images.dtype == torch.uint8:
+        embed = verifier.embed_u8
+    elif images.dtype == torch.float32:
+        embed = getattr(verifier, "forward_one", verifier)          # SiameseNetwork.forward_one / CNNEncoder.forward
+    else:
+        raise ValueError(f"images must be float32 or uint8, got {images.dtype}")
+    step = int(verifier.max_images) if max_batch is None else max(1, min(int(max_batch), int(verifier.max_images)))
+    for i in range(0, images.shape[0], step):
+        moments.update(embed(images[i:i + step]))
+
+
+def calculate_verifier_frechet_distance(real_images: torch.Tensor, fake_images: torch.Tensor, verifier,
+                                        max_batch: Optional[int] = None) -> Dict[str, Any]:
+    """Frechet distance between two image sets in the embedding space of ``verifier`` (a signature_verifier_eval
+    SiameseNetwork or CNNEncoder in eval mode on a ROCm device).  Each set: fp32 (N, 1, 64, 64) in [-1, 1] or uint8
+    (N, 64, 64), N >= 2.  -> {'frechet_distance', 'spread_real', 'spread_generated', 'n_real', 'n_generated',
+    'embedding_dim'}; a spread is tr(cov) of the set's embeddings (utils.frechet.embedding_spread)."""
+    dev = next(verifier.parameters()).device
+    dim = int(verifier.embedding_dim)
+    stats = []
+    for images in (real_images, fake_images):
+        if images.shape[0] < 2:
+            raise ValueError(f"a covariance needs at least 2 images per set, got {images.shape[0]}")
+        moments = FeatureMoments(dim, dev)
+        try:
+            accumulate_verifier_moments(moments, images.to(dev), verifier, max_batch)
+            stats.append(moments.finish())
+        finally:
+            moments.close()
+    (n_r, mu_r, cov_r), (n_f, mu_f, cov_f) = stats
+    return {"frechet_distance": frechet_distance(mu_r, cov_r, mu_f, cov_f), "spread_real": embedding_spread(cov_r),
+            "spread_generated": embedding_spread(cov_f), "n_real": n_r, "n_generated": n_f, "embedding_dim": dim}
 
 
 # ---- counters -> dictionaries (pure numpy) ---------------------------------------------------------------------------
