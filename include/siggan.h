@@ -49,7 +49,8 @@ extern "C" {
 
 #define SIGGAN_ABI_VERSION 4   /* 2: siggan_stage_real, siggan_augment_batch; 3: siggan_config.dtype, siggan_rng_state, siggan_comm_*;
                                 * 4: siggan_config.g_leaky_slope (appended); siggan_prof_launch (a test hook, added);
-                                *    siggan_g_generate_u8, siggan_image_stats (added: no existing call or struct changes) */
+                                *    siggan_g_generate_u8, siggan_image_stats (added: no existing call or struct changes);
+                                *    siggan_d_score_u8, siggan_dequant_table (added likewise) */
 
 enum {
     SIGGAN_OK = 0,
@@ -209,6 +210,18 @@ int siggan_g_generate_u8(siggan_ctx *ctx, const float *z_dev, int32_t batch, uin
  * them from the library RNG. */
 int siggan_d_forward(siggan_ctx *ctx, const float *x_dev, int32_t batch, int32_t training,
                      const float *masks_dev, float *probs_dev, float *features_dev, void *stream);
+
+/* Eval-mode Discriminator forward from the bytes generation ends in (siggan_g_generate_u8): the scoring step of the reference
+ * app's "Filter by Realism" (app_vanilla_gan_signatures.py:1364-1372).  u8_dev (B,S,S) uint8.  binarize -1: off; 0..255: a byte b
+ * becomes b < binarize ? 0 : 255 first (process_images, :863-904).  The first block dequantises on load, t = b / 127.5 - 1.0
+ * as the reference's fp32 expression on the CPU gives it (a correctly rounded division, then a subtraction: the values of
+ * siggan_dequant_table); the zero padding is 0.0f in that domain.  probs_dev (B) is bit for bit what
+ * siggan_d_forward(training = 0) gives for that fp32 tensor, which x_dev (optional, (B,1,S,S) fp32) receives; the call
+ * enqueues the launches of siggan_d_forward, no more, and leaves the context as that call does. */
+int siggan_d_score_u8(siggan_ctx *ctx, const uint8_t *u8_dev, int32_t batch, int32_t binarize, float *probs_dev,
+                      float *x_dev, void *stream);
+/* table_host[b], b in 0..255 (HOST memory): the fp32 value siggan_d_score_u8 gives byte b.  Needs no context and no device. */
+int siggan_dequant_table(float *table_host);
 
 /* ---- training steps ---------------------------------------------------------------------- */
 /* D step: D(real) vs label_smoothing, G_eval(z) under no-grad, D(fake) vs 0, backward into D,

@@ -1,5 +1,5 @@
 """ctypes binding of the C ABI in include/siggan.h (and siggan_mlp.h, siggan_verifier.h, siggan_verifier_train.h,
-siggan_verifier_data.h, siggan_moments.h).
+siggan_verifier_data.h, siggan_moments.h, siggan_select.h).
 
 The shared library is built in-tree by ``__graft_entry__.build()`` / ``csrc/Makefile`` and must be
 present: there is no CPU or PyTorch fallback for this path -- a missing or stale library raises.
@@ -93,6 +93,8 @@ _SIGNATURES = {
     "siggan_g_forward": (C.c_int, [_P, _P, _I32, _I32, _P, _P]),
     "siggan_g_generate_u8": (C.c_int, [_P, _P, _I32, _P, _P, _P, C.c_float, _P]),
     "siggan_d_forward": (C.c_int, [_P, _P, _I32, _I32, _P, _P, _P, _P]),
+    "siggan_d_score_u8": (C.c_int, [_P, _P, _I32, _I32, _P, _P, _P]),
+    "siggan_dequant_table": (C.c_int, [C.POINTER(C.c_float)]),
     "siggan_d_step": (C.c_int, [_P, _P, _I32, _P, _P, C.POINTER(Hyper), _P, _P, _P]),
     "siggan_g_step": (C.c_int, [_P, _I32, _P, C.POINTER(Hyper), _P, _P, _P]),
     "siggan_d_grads": (C.c_int, [_P, _P, _I32, _P, _P, C.POINTER(Hyper), _P, _P]),
@@ -188,6 +190,14 @@ _MOMENTS_SIGNATURES = {
 }
 MOMENTS_EXPORTS = tuple(_MOMENTS_SIGNATURES)
 
+# ranking and gathering of realism-filtered generation (include/siggan_select.h): context-free, new symbols again
+SELECT_MAX = 65536
+_SELECT_SIGNATURES = {
+    "siggan_select_topk": (C.c_int, [_I32, _P, _I32, _I32, _P, _P]),
+    "siggan_gather_u8": (C.c_int, [_I32, _P, _I32, _I64, _P, _I32, _I32, _P, _P]),
+}
+SELECT_EXPORTS = tuple(_SELECT_SIGNATURES)
+
 _lib = None
 
 
@@ -202,7 +212,7 @@ def load():
             "(or `make -C signature-gan_amd/csrc`). This path has no CPU/PyTorch fallback.")
     lib = C.CDLL(LIB_PATH)
     for name, (res, args) in {**_SIGNATURES, **_VERIFIER_SIGNATURES, **_VERIFIER_TRAIN_SIGNATURES,
-                              **_VERIFIER_DATA_SIGNATURES, **_MOMENTS_SIGNATURES}.items():
+                              **_VERIFIER_DATA_SIGNATURES, **_MOMENTS_SIGNATURES, **_SELECT_SIGNATURES}.items():
         fn = getattr(lib, name)          # AttributeError if the library does not export the symbol
         fn.restype, fn.argtypes = res, args
     if lib.siggan_abi_version() != ABI_VERSION:
@@ -213,6 +223,14 @@ def load():
 
 class SigganError(RuntimeError):
     pass
+
+
+def dequant_table():
+    """float32 (256,) numpy array: the value siggan_d_score_u8 gives each byte (siggan_dequant_table; needs no device)."""
+    import numpy as np
+    buf = (C.c_float * 256)()
+    check(load().siggan_dequant_table(buf))
+    return np.frombuffer(buf, dtype=np.float32).copy()
 
 
 def check(rc):

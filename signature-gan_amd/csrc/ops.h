@@ -114,6 +114,11 @@ void launch_final_bn_bwd_apply(int dt, const float* dpre, const float* Wt, const
 // first block (Cin = 1): x = two segments (x0: n < n0, x1: the rest), out [B][S/2][S/2][C]
 void launch_conv1_fwd(int dt, const float* x0, int n0, const float* x1, const float* W, const float* b,
                       const float* noise, float slope, void* out, int B, int S, int C, hipStream_t s);
+// the same block from bytes (eval mode, no dropout): u8 (B,S,S), binarize -1 (off) or 0..255 (b < binarize ? 0 : 255 first),
+// lut[256] the dequantised value of each byte, x_out optional (B,1,S,S) fp32: the tensor the block was fed
+struct Conv1U8 { const uint8_t* u8; const float* lut; float* x_out; int binarize; };
+void launch_conv1_fwd_u8(int dt, const Conv1U8& u, const float* W, const float* b, float slope, void* out, int B, int S, int C,
+                         hipStream_t s);
 void launch_conv1_wgrad(int dt, const void* dv, const float* x0, int n0, const float* x1, float* dW, float* db,
                         float* partial, int B, int S, int C, hipStream_t s);
 // d(image) = conv1 input-gradient, times tanh' = 1 - img^2  ->  dpre

@@ -1017,11 +1017,32 @@ __device__ __forceinline__ void stage_x(float* sx, const float* xp, int oh0, int
 // RIDE (k_adam_pack's riders): W and b are the arena's values BEFORE this launch's update; the block forms the updated ones
 // itself (same arithmetic as the workgroup that owns them) and reports that it has read them
 struct Conv1Ride { const float *pw, *gw, *mw, *vw, *pb, *gb, *mb, *vb; unsigned* counter; AdamK k; };
-template <class T, bool RIDE = false>
+// U8 (siggan_d_score_u8): the same rows from a (B,S,S) uint8 tensor -- a byte is binarised first when asked (b < binarize ? 0 : 255),
+// then becomes lut[b], the host-built table of the reference's dequantisation; the halo is 0.0f, not lut[0].  The block also owns
+// input rows [2*oh0, 2*oh0 + 2*RY) of its image: it writes them to x_out, when given, as the fp32 tensor the network was fed.
+template <int RY>
+__device__ __forceinline__ void stage_x_u8(float* sx, const Conv1U8& u, int n, int oh0, int S) {
+    const int Wp = S + 2;
+    const uint8_t* xp = u.u8 + (size_t)n * S * S;
+    float* xo = u.x_out ? u.x_out + (size_t)n * S * S : nullptr;
+    for (int i = threadIdx.x; i < (2 * RY + 2) * Wp; i += 256) {
+        const int r = i / Wp, cc = i - r * Wp, ih = 2 * oh0 - 1 + r, iw = cc - 1;
+        float v = 0.f;
+        if ((unsigned)ih < (unsigned)S && (unsigned)iw < (unsigned)S) {
+            int byte = xp[ih * S + iw];
+            if (u.binarize >= 0) byte = byte < u.binarize ? 0 : 255;
+            v = u.lut[byte];
+            if (xo && r >= 1 && r <= 2 * RY) xo[ih * S + iw] = v;
+        }
+        sx[i] = v;
+    }
+}
+template <class T, bool RIDE = false, bool U8 = false>
 __device__ __forceinline__ void conv1_fwd_block(const float* __restrict__ x0, int n0, const float* __restrict__ x1,
                                                 const float* __restrict__ W, const float* __restrict__ b,
                                                 const float* __restrict__ noise, float slope,
-                                                T* __restrict__ out, int S, unsigned bid, const Conv1Ride* rd = nullptr) {
+                                                T* __restrict__ out, int S, unsigned bid, const Conv1Ride* rd = nullptr,
+                                                const Conv1U8* u8 = nullptr) {
     constexpr int RY = 2, C = 64;
     __shared__ float sx[(2 * RY + 2) * 130];
     __shared__ __attribute__((aligned(16))) float sw[16 * (C + 4)];  // weights transposed to [tap][co] (row stride C + 4: conflict-free both ways)
@@ -1029,7 +1050,8 @@ __device__ __forceinline__ void conv1_fwd_block(const float* __restrict__ x0, in
     const int Ho = S >> 1, nby = Ho / RY, Wp = S + 2;
     const int n = bid / nby, oh0 = (bid % nby) * RY;
     const int q = threadIdx.x & 15, pl = threadIdx.x >> 4;
-    stage_x<RY>(sx, seg_ptr(x0, n0, x1, n, S), oh0, S);
+    if constexpr (U8) stage_x_u8<RY>(sx, *u8, n, oh0, S);
+    else stage_x<RY>(sx, seg_ptr(x0, n0, x1, n, S), oh0, S);
     f4v bias;
     if (RIDE) {
         for (int i = threadIdx.x; i < 16 * C; i += 256) {
@@ -1100,6 +1122,16 @@ bool launch_prepare_conv1(const PrepTable& t, float bn_eps, int dt, const float*
     SIGGAN_DT_SWITCH(dt, T, hipLaunchKernelGGL(k_prepare_conv1<T>, dim3(nprep + (unsigned)(B * (S / 4))), dim3(256), 512 * 17 * sizeof(float), s,
                                                 t, bn_eps, nprep, x, B, W, b, slope, (T*)out, S));
     return true;
+}
+template <class T>
+__global__ __launch_bounds__(256) void k_conv1_fwd_u8(const Conv1U8 u, const float* __restrict__ W, const float* __restrict__ b,
+                                                      float slope, T* __restrict__ out, int S) {
+    conv1_fwd_block<T, false, true>(nullptr, 0, nullptr, W, b, nullptr, slope, out, S, blockIdx.x, nullptr, &u);
+}
+void launch_conv1_fwd_u8(int dt, const Conv1U8& u, const float* W, const float* b, float slope, void* out, int B, int S, int C,
+                         hipStream_t s) {
+    (void)C;                                            // as launch_conv1_fwd
+    SIGGAN_DT_SWITCH(dt, T, hipLaunchKernelGGL(k_conv1_fwd_u8<T>, dim3(B * (S / 4)), dim3(256), 0, s, u, W, b, slope, (T*)out, S));
 }
 void launch_conv1_fwd(int dt, const float* x0, int n0, const float* x1, const float* W, const float* b, const float* noise,
                       float slope, void* out, int B, int S, int C, hipStream_t s) {

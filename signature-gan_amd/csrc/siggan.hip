@@ -228,6 +228,7 @@ struct siggan_ctx {
     char *g_up[MAXL + 1], *g_dn[MAXL + 1], *d_dn[MAXL + 1], *d_up[MAXL + 1];
     float *wcp;
     float *slab, *slab_k, *slab_k2, *slab_k3, *partial, *partial_b, *partial_c, *z_g, *img_g, *metrics, *zeros, *wfc_t, *wfin_t, *d_w1t, *real_stage, *mask_stage;
+    float* deq_lut;      // the 256 dequantised byte values (siggan_dequant_table), read by siggan_d_score_u8's first block
     char *op_pack;
     int64_t slab_floats, slab_k_floats;
     DevState* dev;
@@ -346,6 +347,22 @@ static void invalidate(siggan_ctx* c, Inval why) {
     }
 }
 
+// The fp32 value of a byte of a generated image as the reference's realism filter feeds it to the Discriminator
+// (app_vanilla_gan_signatures.py:1364-1372, torch.from_numpy(b).float() / 127.5 - 1.0 on the CPU): a correctly rounded fp32
+// division, then a separate fp32 subtraction -- two roundings.  Formed here on the host (the file is built without contraction),
+// so no device division or reciprocal has a say in it.
+static void dequant_table(float* lut) {
+    for (int b = 0; b < 256; ++b) {
+        volatile float q = (float)b / 127.5f;
+        lut[b] = q - 1.0f;
+    }
+}
+extern "C" int siggan_dequant_table(float* table_host) {
+    if (!table_host) return fail(SIGGAN_E_INVALID, "null table");
+    dequant_table(table_host);
+    return SIGGAN_OK;
+}
+
 extern "C" int siggan_create(const siggan_config* cfg, siggan_ctx** out) {
     if (!cfg || !out) return fail(SIGGAN_E_INVALID, "null argument");
     if (cfg->image_size != 64 && cfg->image_size != 128)
@@ -452,6 +469,7 @@ extern "C" int siggan_create(const siggan_config* cfg, siggan_ctx** out) {
         carve(&c->wfin_t, (int64_t)9 * c->gC[c->Lg]);
         carve(&c->d_w1t, (int64_t)16 * c->dC[1]);
         carve(&c->ride_ctr, 64);
+        carve(&c->deq_lut, 256);
         float* devp = nullptr;
         carve(&devp, 64);
         if (pass == 1) c->dev = (DevState*)devp;
@@ -466,6 +484,7 @@ extern "C" int siggan_create(const siggan_config* cfg, siggan_ctx** out) {
     DevState h; memset(&h, 0, sizeof h);
     h.seed = cfg->seed; h.rng_ctr = 0; h.grad_mul = 1.f;
     HIPCHK(hipMemcpy(c->dev, &h, sizeof h, hipMemcpyHostToDevice));
+    { float lut[256]; dequant_table(lut); HIPCHK(hipMemcpy(c->deq_lut, lut, sizeof lut, hipMemcpyHostToDevice)); }
     c->mode = SIGGAN_MODE_OVERLAP;   // hipGraph replay measured slower than eager launches on ROCm 7
     c->evi = 0;
     HIPCHK(hipStreamCreateWithFlags(&c->s_m, hipStreamNonBlocking));
@@ -868,12 +887,16 @@ static int g_forward_pass(const siggan_ctx* c, const float* z, int B, bool train
 // produces the fakes, then D(fake) into rows [B,2B); backward treats the 2B rows as one batch).
 // Returns the form the logits were left in: P > 0 partial dot products per image in lparts, 0: stored in `logits`.
 static int d_forward_rows(const siggan_ctx* c, const float* x, int r0, int nB, bool dropout, hipStream_t s, float* slab_k,
-                           bool fuse_cls = false, bool conv1_done = false) {
+                           bool fuse_cls = false, bool conv1_done = false, const uint8_t* u8 = nullptr, int binarize = -1,
+                           float* x_out = nullptr) {
     const float slope = c->cfg.leaky_slope;
     int P = 0;
     auto act = [&](int l) { const int64_t H = c->S >> l; return c->d_a[l] + (size_t)((int64_t)r0 * H * H * c->dC[l]) * c->es; };
     auto nz = [&](int l) { return dropout ? c->d_noise[l] + (int64_t)r0 * c->dC[l] : nullptr; };
-    if (!conv1_done)          // (done: it rode in the launch that re-packed D's weights, see repack)
+    if (u8)                   // siggan_d_score_u8: the same block fed from bytes (eval mode: no dropout multipliers)
+        launch_conv1_fwd_u8(c->dt, Conv1U8{u8, c->deq_lut, x_out, binarize}, c->sn ? c->d_w1s : DP(c, di_w(1)), DP(c, di_b(1)), slope,
+                            act(1), nB, c->S, c->dC[1], s);
+    else if (!conv1_done)     // (done: it rode in the launch that re-packed D's weights, see repack)
         launch_conv1_fwd(c->dt, x, nB, x, c->sn ? c->d_w1s : DP(c, di_w(1)), DP(c, di_b(1)), nz(1), slope, act(1), nB, c->S, c->dC[1], s);
     for (int l = 2; l <= c->Ld; ++l) {
         const int Hi = c->S >> (l - 1), Ho = Hi / 2;
@@ -1493,6 +1516,26 @@ extern "C" int siggan_d_forward(siggan_ctx* c, const float* x_dev, int32_t batch
     c->cs.lP[0] = d_forward_rows(c, x_dev, 0, batch, drop, s, c->slab_k);
     if (probs_dev) launch_bce(c->logits, batch, batch, 0.f, 0.f, probs_dev, nullptr, nullptr, 0, s);
     if (features_dev) launch_cls_features(c->dt, c->d_a[c->Ld], features_dev, batch, c->dC[c->Ld], s);
+    LAUNCHCHK();
+    return lane_check(c);
+}
+
+extern "C" int siggan_d_score_u8(siggan_ctx* c, const uint8_t* u8_dev, int32_t batch, int32_t binarize, float* probs_dev,
+                                 float* x_dev, void* stream) {
+    ENTER(c);
+    int rc = check_call(c, batch);
+    if (rc) return rc;
+    if (!u8_dev || !probs_dev) return fail(SIGGAN_E_INVALID, "null tensor");
+    if (binarize < -1 || binarize > 255) return fail(SIGGAN_E_INVALID, "binarize must be -1 (off) or a byte value, got %d", binarize);
+    hipStream_t s = (hipStream_t)stream;
+    invalidate(c, INV_ROWS);           // as siggan_d_forward(training = 0): rows [0, batch) are overwritten
+    if ((rc = settle(c, s))) return rc;
+    Lanes L(c, s);
+    if (c->sn) launch_sn_sigma(c->snt, 0, 2, SN_EPS, s);
+    repack(c, L, s, s, c->g_dirty, c->sn || c->d_dirty, 2);
+    c->g_dirty = c->d_dirty = false;
+    c->cs.lP[0] = d_forward_rows(c, nullptr, 0, batch, false, s, c->slab_k, false, false, u8_dev, binarize, x_dev);
+    launch_bce(c->logits, batch, batch, 0.f, 0.f, probs_dev, nullptr, nullptr, 0, s);
     LAUNCHCHK();
     return lane_check(c);
 }

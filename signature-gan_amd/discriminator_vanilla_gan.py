@@ -105,6 +105,16 @@ class Discriminator(EngineBacked):
     def forward_features(self, x: torch.Tensor) -> torch.Tensor:
         return self._forward(x, True)[1]
 
+    @torch.no_grad()
+    def score_u8(self, u8: torch.Tensor, binarize=None) -> torch.Tensor:
+        """uint8 (B, S, S) device images -> P(real) (B,): ``forward`` on ``u8.float() / 127.5 - 1.0`` (the reference's
+        dequantisation on the CPU, app_vanilla_gan_signatures.py:1364-1372) without that tensor ever being formed -- the first
+        block reads the bytes (Engine.d_score_u8).  ``binarize``: byte < binarize ? 0 : 255 first.  eval() mode only: the
+        realism filter scores with Dropout2d off, and a train()-mode call would also move the spectral-norm vectors."""
+        if self.training:
+            raise RuntimeError("score_u8 is the eval-mode score of the realism filter: call .eval() first")
+        return self._require_engine().d_score_u8(u8, binarize=binarize)
+
     def get_input_shape(self) -> Tuple[int, int, int]:
         return (self.input_channels, self.input_size, self.input_size)
 

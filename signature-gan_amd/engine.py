@@ -281,11 +281,13 @@ class Engine:
         _lib.check(self.lib.siggan_g_forward(self._h, _ptr(z), b, int(training), _ptr(out), self._stream()))
         return out
 
-    def g_generate_u8(self, z, threshold=None, want_f32=False):
+    def g_generate_u8(self, z, threshold=None, want_f32=False, out=None):
         """Eval-mode Generator forward ending in bytes (siggan_g_generate_u8): uint8 (B, S, S) by the reference's rule
         ((x + 1) * 127.5, clip, truncate -- utils/inference.tensor_to_uint8), written by the final-conv kernel itself.
         ``threshold``: also return the int32 (B, 3) per-image stroke counters (_lib.IS_NEG / IS_INK_SIGNED / IS_INK_UNIT)
         against it.  ``want_f32``: also return the fp32 (B, 1, S, S) images, bit-identical to g_forward(z).
+        ``out``: a caller-owned contiguous uint8 (B, S, S) device view the bytes are written into (a slice of a pool of
+        generated images); it is then what is returned as u8.
         Returns u8, or the tuple (u8[, stats][, images])."""
         b = 1
         if z is not None:                                 # (a null z goes to the library, which refuses it: ValueError)
@@ -295,7 +297,12 @@ class Engine:
             b = z.shape[0]
         self._check_batch(b)
         s = self.image_size
-        u8 = torch.empty(b, s, s, dtype=torch.uint8, device=self.device)
+        if out is None:
+            u8 = torch.empty(b, s, s, dtype=torch.uint8, device=self.device)
+        else:
+            if out.device != self.device or out.dtype != torch.uint8 or tuple(out.shape) != (b, s, s) or not out.is_contiguous():
+                raise ValueError(f"out must be a contiguous uint8 ({b}, {s}, {s}) tensor on {self.device}")
+            u8 = out
         stats = torch.empty(b, _lib.IS_COUNT, dtype=torch.int32, device=self.device) if threshold is not None else None
         img = torch.empty(b, 1, s, s, dtype=torch.float32, device=self.device) if want_f32 else None
         _lib.check(self.lib.siggan_g_generate_u8(self._h, _ptr(z), b, _ptr(u8), _ptr(img), _ptr(stats),
@@ -341,6 +348,67 @@ class Engine:
         _lib.check(self.lib.siggan_d_forward(self._h, _ptr(x), b, int(training), _ptr(masks), _ptr(probs), _ptr(feat),
                                              self._stream()))
         return (probs, feat) if want_features else probs
+
+    def d_score_u8(self, u8, binarize=None, out=None, want_input=False):
+        """Eval-mode Discriminator forward from bytes (siggan_d_score_u8): u8 a contiguous uint8 (B, S, S) device tensor as
+        g_generate_u8 writes it; ``binarize`` (0..255): every byte b is b < binarize ? 0 : 255 first.  The first block
+        dequantises on load by the reference's rule (byte / 127.5 - 1.0 in fp32 on the CPU, _lib.dequant_table()).  Returns
+        float32 (B,) probabilities, bit for bit d_forward's on that fp32 tensor -- written into ``out`` when given (a float32
+        device view of B elements, e.g. a slice of a pool's score vector).  ``want_input``: also return the fp32 (B, 1, S, S)
+        tensor the network was fed."""
+        s = self.image_size
+        if u8.device != self.device or u8.dtype != torch.uint8:
+            raise ValueError(f"u8 must be a uint8 tensor on {self.device}, got {u8.dtype} on {u8.device}")
+        if u8.dim() != 3 or tuple(u8.shape[1:]) != (s, s):
+            raise ValueError(f"u8 must be (B, {s}, {s}), got {tuple(u8.shape)}")
+        u8 = u8.contiguous()
+        b = u8.shape[0]
+        self._check_batch(b)
+        if binarize is not None and not 0 <= int(binarize) <= 255:
+            raise ValueError(f"binarize must be None or a byte value, got {binarize}")
+        if out is None:
+            out = torch.empty(b, dtype=torch.float32, device=self.device)
+        elif out.device != self.device or out.dtype != torch.float32 or out.numel() != b or not out.is_contiguous():
+            raise ValueError(f"out must be a contiguous float32 tensor of {b} elements on {self.device}")
+        x = torch.empty(b, 1, s, s, dtype=torch.float32, device=self.device) if want_input else None
+        _lib.check(self.lib.siggan_d_score_u8(self._h, _ptr(u8), b, -1 if binarize is None else int(binarize), _ptr(out),
+                                              _ptr(x), self._stream()))
+        return (out, x) if want_input else out
+
+    @staticmethod
+    def select_topk(scores, k):
+        """int32 (k,) device tensor: the indices of the k highest of the float32 device scores, highest first, equal scores by
+        ascending index -- sorted(range(m), key=scores.__getitem__, reverse=True)[:k] (siggan_select_topk; 1 <= k <= m <=
+        _lib.SELECT_MAX).  Needs no context."""
+        if scores.device.type != "cuda":
+            raise RuntimeError("select_topk runs on a ROCm device ('cuda:N'); there is no CPU path")
+        if scores.dtype != torch.float32 or scores.dim() != 1 or not scores.is_contiguous():
+            raise ValueError("select_topk needs a contiguous float32 (m,) tensor")
+        index = torch.empty(max(int(k), 0), dtype=torch.int32, device=scores.device)
+        _lib.check(_lib.load().siggan_select_topk(scores.device.index, _ptr(scores), scores.numel(), int(k), _ptr(index),
+                                                  C.c_void_p(torch.cuda.current_stream(scores.device).cuda_stream)))
+        return index
+
+    @staticmethod
+    def gather_u8(pool, index, binarize=None):
+        """uint8 (k, ...) device tensor: pool[index] for a contiguous uint8 (m, ...) pool and an int32 (k,) index on the same
+        device, optionally binarised like d_score_u8's input (siggan_gather_u8; the bytes per image must be a multiple of 4).
+        Needs no context."""
+        if pool.device.type != "cuda":
+            raise RuntimeError("gather_u8 runs on a ROCm device ('cuda:N'); there is no CPU path")
+        if pool.dtype != torch.uint8 or pool.dim() < 2 or not pool.is_contiguous():
+            raise ValueError("gather_u8 needs a contiguous uint8 (m, ...) pool")
+        if index.device != pool.device or index.dtype != torch.int32 or index.dim() != 1 or not index.is_contiguous():
+            raise ValueError("gather_u8 needs a contiguous int32 (k,) index on the pool's device")
+        if binarize is not None and not 0 <= int(binarize) <= 255:
+            raise ValueError(f"binarize must be None or a byte value, got {binarize}")
+        m, k = pool.shape[0], index.numel()
+        pixels = pool.numel() // m if m else 0
+        out = torch.empty((k,) + tuple(pool.shape[1:]), dtype=torch.uint8, device=pool.device)
+        _lib.check(_lib.load().siggan_gather_u8(pool.device.index, _ptr(pool), m, pixels, _ptr(index), k,
+                                                -1 if binarize is None else int(binarize), _ptr(out),
+                                                C.c_void_p(torch.cuda.current_stream(pool.device).cuda_stream)))
+        return out
 
     # ---- training steps --------------------------------------------------------------------------
     def _metrics(self, keys, sync):

@@ -1,28 +1,67 @@
 """Drop-in for the reference's ``generate_signatures.py`` CLI: checkpoint in -> PNG files out, with the
 Generator forward on the MI355X HIP engine (``siggan_g_forward``).  Flags, file naming
-(``<prefix>_%06d.png``) and the ``--seed`` semantics follow generate_signatures.py:50-249."""
+(``<prefix>_%06d.png``) and the ``--seed`` semantics follow generate_signatures.py:50-249.
+
+``--filter_by_realism`` adds the reference app's realism filter (app_vanilla_gan_signatures.py:1065-1385) to the CLI: oversample,
+score every image with the checkpoint's Discriminator, keep the best ``--n_samples`` -- on the device
+(utils.inference.generate_signatures_filtered).  ``--noise_scale`` and ``--threshold`` / ``--transparent`` (the app's
+post-processing) also apply to a plain run.  Without the new flags, files and stdout are what they were."""
 import argparse
+import json
 import os
+import sys
 from typing import Any, Dict, Optional
 
 import torch
 
-from .utils.inference import generate_signatures_batch, load_generator
+from .utils.inference import (generate_signatures_batch, generate_signatures_filtered, load_discriminator, load_generator,
+                              process_images)
 
 
 def generate_signatures(generator, n_samples: int, output_dir: str, batch_size: int = 64,
                         device: torch.device = torch.device("cuda"), seed: Optional[int] = None,
-                        prefix: str = "signature") -> None:
+                        prefix: str = "signature", noise_scale: float = 1.0, threshold: Optional[int] = None,
+                        transparent: bool = False) -> None:
     os.makedirs(output_dir, exist_ok=True)
     print(f"Output directory: {output_dir}")
     print(f"Generating {n_samples} signatures...")
     images = generate_signatures_batch(generator=generator, n_samples=n_samples, latent_dim=generator.latent_dim,
-                                       device=device, seed=seed, batch_size=batch_size)
+                                       device=device, seed=seed, batch_size=batch_size, noise_scale=noise_scale)
+    if threshold is not None:
+        images = process_images(images, threshold=threshold, make_transparent=transparent)
     print(f"Saving {len(images)} images...")
     for i, img in enumerate(images):
         img.save(os.path.join(output_dir, f"{prefix}_{i + 1:06d}.png"), "PNG")
     print("\nGeneration complete!")
     print(f"Generated {len(images)} signatures saved to: {output_dir}")
+
+
+def generate_filtered(generator, discriminator, n_samples: int, output_dir: str, batch_size: int = 64,
+                      device: torch.device = torch.device("cuda"), seed: Optional[int] = None, prefix: str = "signature",
+                      oversampling_ratio: float = 2.0, threshold: Optional[int] = None, transparent: bool = False,
+                      noise_scale: float = 1.0) -> None:
+    """The best ``n_samples`` of int(n_samples * oversampling_ratio) generated signatures by the Discriminator's score, written
+    in rank order under the usual names, plus ``<prefix>_scores.json``: [{file, score}, ...] in the same order."""
+    os.makedirs(output_dir, exist_ok=True)
+    print(f"Output directory: {output_dir}")
+    print(f"Generating {int(n_samples * oversampling_ratio)} signatures, keeping the {n_samples} most realistic...")
+    images, scores = generate_signatures_filtered(generator, discriminator, n_samples, generator.latent_dim, device, seed=seed,
+                                                  batch_size=batch_size, oversampling_ratio=oversampling_ratio,
+                                                  noise_scale=noise_scale, threshold=threshold)
+    if threshold is not None:
+        images = process_images(images, threshold=threshold, make_transparent=transparent)
+    print(f"Saving {len(images)} images...")
+    records = []
+    for i, (img, score) in enumerate(zip(images, scores)):
+        name = f"{prefix}_{i + 1:06d}.png"
+        img.save(os.path.join(output_dir, name), "PNG")
+        records.append({"file": name, "score": score})
+    with open(os.path.join(output_dir, f"{prefix}_scores.json"), "w") as f:
+        json.dump(records, f, indent=2)
+    print("\nGeneration complete!")
+    print(f"Generated {len(images)} signatures saved to: {output_dir}")
+    if scores:
+        print(f"Realism scores: best {scores[0]:.4f}, worst kept {scores[-1]:.4f}")
 
 
 def get_checkpoint_info(checkpoint_path: str) -> Dict[str, Any]:
@@ -49,7 +88,22 @@ def parse_args(argv=None) -> argparse.Namespace:
     p.add_argument("--prefix", type=str, default="signature", help="Filename prefix for generated images")
     p.add_argument("--device", type=str, default="auto", help="Device to use for inference")
     p.add_argument("--info", action="store_true", help="Display checkpoint information and exit")
-    return p.parse_args(argv)
+    p.add_argument("--filter_by_realism", action="store_true",
+                   help="Oversample, score with the checkpoint's Discriminator and keep the n_samples most realistic")
+    p.add_argument("--oversampling_ratio", type=float, default=2.0, help="Signatures generated per signature kept (>= 1.0)")
+    p.add_argument("--threshold", type=int, default=None, help="Binarise before scoring and saving: pixel < THRESHOLD -> 0, else 255")
+    p.add_argument("--transparent", action="store_true", help="With --threshold: save RGBA with the white background transparent")
+    p.add_argument("--noise_scale", type=float, default=1.0, help="Scale of the latent noise")
+    a = p.parse_args(argv)
+    if a.oversampling_ratio < 1.0:
+        p.error("--oversampling_ratio must be >= 1.0")
+    if a.threshold is not None and not 0 <= a.threshold <= 255:
+        p.error("--threshold must be a byte value (0..255)")
+    if not a.filter_by_realism and a.oversampling_ratio != 2.0:
+        p.error("--oversampling_ratio needs --filter_by_realism")
+    if a.transparent and a.threshold is None:
+        p.error("--transparent needs --threshold")
+    return a
 
 
 def main(argv=None) -> None:
@@ -62,7 +116,16 @@ def main(argv=None) -> None:
             print(f"  {k}: {v}")
         return
     generator, _ = load_generator(a.checkpoint, device)
-    generate_signatures(generator, a.n_samples, a.output_dir, a.batch_size, device, a.seed, a.prefix)
+    if a.filter_by_realism:
+        discriminator = load_discriminator(a.checkpoint, device, image_size=generator.output_size)
+        if discriminator is None:
+            sys.exit(f"error: {a.checkpoint} holds no discriminator_state_dict: --filter_by_realism needs the Discriminator's "
+                     "weights (a full training checkpoint, not a generator-only export)")
+        generate_filtered(generator, discriminator, a.n_samples, a.output_dir, a.batch_size, device, a.seed, a.prefix,
+                          a.oversampling_ratio, a.threshold, a.transparent, a.noise_scale)
+    else:
+        generate_signatures(generator, a.n_samples, a.output_dir, a.batch_size, device, a.seed, a.prefix, a.noise_scale,
+                            a.threshold, a.transparent)
     print("\n" + "=" * 50 + "\nGeneration Summary:")
     print(f"  Checkpoint: {a.checkpoint}\n  Samples generated: {a.n_samples}\n  Output directory: {a.output_dir}")
     print(f"  Seed: {a.seed if a.seed is not None else 'Random'}\n  Device: {device}\n" + "=" * 50)
