@@ -1,5 +1,5 @@
 """ctypes binding of the C ABI in include/siggan.h (and siggan_mlp.h, siggan_verifier.h, siggan_verifier_train.h,
-siggan_verifier_data.h, siggan_moments.h, siggan_select.h).
+siggan_verifier_data.h, siggan_moments.h, siggan_select.h, siggan_neighbors.h).
 
 The shared library is built in-tree by ``__graft_entry__.build()`` / ``csrc/Makefile`` and must be
 present: there is no CPU or PyTorch fallback for this path -- a missing or stale library raises.
@@ -198,6 +198,14 @@ _SELECT_SIGNATURES = {
 }
 SELECT_EXPORTS = tuple(_SELECT_SIGNATURES)
 
+# exact fp64 k-nearest-neighbour lists and ball counts (include/siggan_neighbors.h): context-free, new symbols again
+KNN_MAX_K, KNN_MAX_DIM = 16, 1024
+_NEIGHBORS_SIGNATURES = {
+    "siggan_knn": (C.c_int, [_I32, _P, _I32, _P, _I32, _I32, _I32, _I32, _P, _P, _P]),
+    "siggan_ball_count": (C.c_int, [_I32, _P, _I32, _P, _I32, _I32, _P, _P, _P]),
+}
+NEIGHBORS_EXPORTS = tuple(_NEIGHBORS_SIGNATURES)
+
 _lib = None
 
 
@@ -212,7 +220,8 @@ def load():
             "(or `make -C signature-gan_amd/csrc`). This path has no CPU/PyTorch fallback.")
     lib = C.CDLL(LIB_PATH)
     for name, (res, args) in {**_SIGNATURES, **_VERIFIER_SIGNATURES, **_VERIFIER_TRAIN_SIGNATURES,
-                              **_VERIFIER_DATA_SIGNATURES, **_MOMENTS_SIGNATURES, **_SELECT_SIGNATURES}.items():
+                              **_VERIFIER_DATA_SIGNATURES, **_MOMENTS_SIGNATURES, **_SELECT_SIGNATURES,
+                              **_NEIGHBORS_SIGNATURES}.items():
         fn = getattr(lib, name)          # AttributeError if the library does not export the symbol
         fn.restype, fn.argtypes = res, args
     if lib.siggan_abi_version() != ABI_VERSION:

@@ -12,8 +12,12 @@ computed (utils/metrics.py of this package).
 Beyond the reference: ``--verifier_checkpoint PATH`` adds a Frechet distance between the real and the generated images in
 the embedding space of the Siamese verifier (signature_verifier_eval), the FID construction over a network trained here.
 Every generated batch's bytes go through ``embed_u8`` into an fp64 accumulator while they are still on the device
-(utils/frechet.py), the real images take the same route, and dim * (dim + 1) doubles per set reach the host.  Without the
-flag nothing changes: stdout, report keys and exit codes are the reference's."""
+(utils/frechet.py), the real images take the same route, and dim * (dim + 1) doubles per set reach the host.
+``--verifier_neighbors K`` (with ``--verifier_checkpoint`` and ``--real_dir``) adds what one distance cannot say: improved
+precision / recall, density / coverage and the distance from every generated sample to its nearest real one, against the
+real set's own leave-one-out distances -- the memorisation check.  The embeddings of both sets are then also kept in a
+device buffer, and exact fp64 k-nearest-neighbour queries run there (utils/neighbors.py); k-lists and counts reach the
+host.  Without the flags nothing changes: stdout, report keys and exit codes are the reference's."""
 import argparse
 import json
 import sys
@@ -29,9 +33,10 @@ from .generator_vanilla_gan import Generator
 from .train_vanilla_gan_signatures import save_sample_grid
 from .utils.inference import load_generator_and_config
 from .utils.frechet import FeatureMoments, embedding_spread, frechet_distance
-from .utils.metrics import (INCEPTION_AVAILABLE, LPIPS_AVAILABLE, accumulate_verifier_moments, calculate_fid,
-                            calculate_foreground_ratio, calculate_lpips_diversity, calculate_stroke_density,
-                            foreground_ratio_from_counts, stroke_density_from_counts)
+from .utils.metrics import (INCEPTION_AVAILABLE, LPIPS_AVAILABLE, calculate_fid, calculate_foreground_ratio,
+                            calculate_lpips_diversity, calculate_stroke_density, foreground_ratio_from_counts,
+                            stroke_density_from_counts, verifier_embedding_chunks)
+from .utils.neighbors import manifold_metrics
 
 THRESHOLD = 0.5          # the threshold compute_metrics passes to both statistics (evaluate_vanilla_gan_signatures.py:306,318)
 VERIFIER_IMAGE_SIZE = 64
@@ -41,12 +46,14 @@ class GeneratedSamples:
     """What generate_samples hands on: the per-image stroke counters of all N samples (``counts``, int (N, 3) against
     ``threshold``) and the fp32 images of the first ``len(images)`` of them (CPU, (K, 1, S, S) in [-1, 1]).  When the
     samples were also embedded on the way (generate_samples' ``embedding_sink``): ``embedding_stats``, the finished
-    (n, mean, cov) of their embeddings, or ``embedding_error`` saying why there is none."""
+    (n, mean, cov) of their embeddings, or ``embedding_error`` saying why there is none; ``embeddings``, the (N, E) fp32
+    device buffer of a sink that keeps them."""
 
     def __init__(self, n: int, image_shape: Tuple[int, int, int], counts: np.ndarray, images: torch.Tensor, threshold: float,
-                 embedding_stats: Optional[Tuple[int, np.ndarray, np.ndarray]] = None, embedding_error: Optional[str] = None):
+                 embedding_stats: Optional[Tuple[int, np.ndarray, np.ndarray]] = None, embedding_error: Optional[str] = None,
+                 embeddings: Optional[torch.Tensor] = None):
         self.n, self.image_shape, self.counts, self.images, self.threshold = n, tuple(image_shape), counts, images, threshold
-        self.embedding_stats, self.embedding_error = embedding_stats, embedding_error
+        self.embedding_stats, self.embedding_error, self.embeddings = embedding_stats, embedding_error, embeddings
 
     def __len__(self) -> int:
         return self.n
@@ -72,14 +79,24 @@ def load_generator_from_checkpoint(checkpoint_path: Path, device: torch.device) 
 
 class EmbeddingSink:
     """One image set on its way into the verifier's embedding space: ``update`` embeds a batch (uint8 (B, 64, 64) or fp32
-    (B, 1, 64, 64), on the device) and adds the embeddings to an fp64 accumulator there; ``finish`` -> (n, mean, cov)."""
+    (B, 1, 64, 64), on the device) and adds the embeddings to an fp64 accumulator there; ``finish`` -> (n, mean, cov).
+    ``keep``: the embeddings also stay, and ``embeddings`` hands them on as one (n, E) fp32 device buffer."""
 
-    def __init__(self, model) -> None:
+    def __init__(self, model, keep: bool = False) -> None:
         self.model = model
         self.moments = FeatureMoments(model.embedding_dim, next(model.parameters()).device)
+        self.kept: Optional[List[torch.Tensor]] = [] if keep else None
 
     def update(self, images: torch.Tensor) -> None:
-        accumulate_verifier_moments(self.moments, images, self.model)
+        for emb in verifier_embedding_chunks(images, self.model):
+            self.moments.update(emb)
+            if self.kept is not None:
+                self.kept.append(emb)
+
+    def embeddings(self) -> Optional[torch.Tensor]:
+        if not self.kept:
+            return None
+        return torch.cat(self.kept, dim=0).contiguous()
 
     def finish(self) -> Tuple[int, np.ndarray, np.ndarray]:
         try:
@@ -92,8 +109,9 @@ class VerifierFeatures:
     """The Siamese verifier behind ``--verifier_checkpoint``: ``model`` (signature_verifier_eval.load_model), or ``error``
     saying why the Frechet distance cannot be computed with it -- the report records that, the evaluation goes on."""
 
-    def __init__(self, checkpoint: Path, device: torch.device, image_size: int) -> None:
+    def __init__(self, checkpoint: Path, device: torch.device, image_size: int, neighbors_k: Optional[int] = None) -> None:
         self.checkpoint, self.model, self.error = str(checkpoint), None, None
+        self.neighbors_k = neighbors_k                          # --verifier_neighbors: the sinks keep their embeddings
         if image_size != VERIFIER_IMAGE_SIZE:
             self.error = f"the verifier takes {VERIFIER_IMAGE_SIZE}x{VERIFIER_IMAGE_SIZE} images"
             return
@@ -104,7 +122,7 @@ class VerifierFeatures:
             self.error = f"could not load the verifier checkpoint: {e}"
 
     def sink(self) -> Optional[EmbeddingSink]:
-        return EmbeddingSink(self.model) if self.model is not None else None
+        return EmbeddingSink(self.model, keep=self.neighbors_k is not None) if self.model is not None else None
 
 
 @torch.no_grad()
@@ -137,13 +155,14 @@ def generate_samples(generator: Generator, n_samples: int, latent_dim: int, devi
     s = generator.output_size
     kept = torch.cat(images, dim=0) if images else torch.empty(0, 1, s, s)
     all_counts = torch.cat(counts, dim=0).cpu().numpy() if counts else np.zeros((0, 3), np.int32)
-    stats, error = None, None
+    stats, error, embeddings = None, None, None
     if embedding_sink is not None:
+        embeddings = embedding_sink.embeddings()
         try:
             stats = embedding_sink.finish()
         except ValueError as e:                                 # fewer than 2 samples: the report says so
             error = str(e)
-    return GeneratedSamples(n_samples, (1, s, s), all_counts, kept, threshold, stats, error)
+    return GeneratedSamples(n_samples, (1, s, s), all_counts, kept, threshold, stats, error, embeddings)
 
 
 def load_real_images(real_dir: Path, n_images: int, image_size: int, device: torch.device) -> torch.Tensor:
@@ -218,9 +237,11 @@ def _foreground(images) -> Dict[str, Any]:
 
 
 def _verifier_frechet(metrics: Dict[str, Any], fake_images, real_images: Optional[torch.Tensor],
-                      verifier: VerifierFeatures) -> None:
-    """The ``verifier_*`` keys of the report; any failure is recorded as ``verifier_frechet_error``, like ``fid_error``."""
+                      verifier: VerifierFeatures) -> Optional[torch.Tensor]:
+    """The ``verifier_*`` keys of the report; any failure is recorded as ``verifier_frechet_error``, like ``fid_error``.
+    -> the real images' embeddings when the sink kept them (``--verifier_neighbors``), else None."""
     metrics["verifier_checkpoint"] = verifier.checkpoint
+    real_embeddings = None
     print("Computing verifier Frechet distance...")
     try:
         if verifier.error:
@@ -232,6 +253,7 @@ def _verifier_frechet(metrics: Dict[str, Any], fake_images, real_images: Optiona
             raise ValueError(getattr(fake_images, "embedding_error", None) or "the generated samples were not embedded")
         sink = verifier.sink()
         sink.update(real_images)
+        real_embeddings = sink.embeddings()
         (_, mu_r, cov_r), (_, mu_f, cov_f) = sink.finish(), fake_stats
         metrics["verifier_frechet_distance"] = frechet_distance(mu_r, cov_r, mu_f, cov_f)
         metrics["verifier_embedding_spread"] = {"generated": embedding_spread(cov_f), "real": embedding_spread(cov_r)}
@@ -239,12 +261,47 @@ def _verifier_frechet(metrics: Dict[str, Any], fake_images, real_images: Optiona
     except Exception as e:                                      # noqa: BLE001 -- the report records any failure
         print(f"  Skipping verifier Frechet distance: {e}")
         metrics["verifier_frechet_distance"], metrics["verifier_frechet_error"] = None, str(e)
+    return real_embeddings
+
+
+NEIGHBOR_KEYS = ("verifier_precision", "verifier_recall", "verifier_density", "verifier_coverage", "verifier_nearest_real")
+
+
+def _verifier_neighbors(metrics: Dict[str, Any], fake_images, real_embeddings: Optional[torch.Tensor],
+                        verifier: Optional[VerifierFeatures], k: int) -> None:
+    """The keys ``--verifier_neighbors K`` adds (NEIGHBOR_KEYS, ``verifier_neighbors_k``), from the embeddings both sinks
+    kept; any failure is recorded as ``verifier_neighbors_error`` and the five figures are None."""
+    metrics["verifier_neighbors_k"] = k
+    print("Computing verifier precision / recall and nearest-real distances...")
+    try:
+        if verifier is None:
+            raise ValueError("--verifier_neighbors needs --verifier_checkpoint")
+        if verifier.error:
+            raise ValueError(verifier.error)
+        fake_embeddings = getattr(fake_images, "embeddings", None)
+        if fake_embeddings is None:
+            raise ValueError("the generated samples were not embedded")
+        if real_embeddings is None:
+            raise ValueError(metrics.get("verifier_frechet_error") or "no real images provided")
+        m = manifold_metrics(real_embeddings, fake_embeddings, k)
+        for key in NEIGHBOR_KEYS:
+            metrics[key] = m[key[len("verifier_"):]]
+        nr = m["nearest_real"]
+        print(f"  Verifier Precision: {m['precision']:.4f}, Recall: {m['recall']:.4f}, "
+              f"Density: {m['density']:.4f}, Coverage: {m['coverage']:.4f}")
+        print(f"  Nearest real - Median: {nr['median']:.4f} (real leave-one-out: {nr['real_loo_median']:.4f})")
+    except Exception as e:                                      # noqa: BLE001 -- the report records any failure
+        print(f"  Skipping verifier precision / recall: {e}")
+        for key in NEIGHBOR_KEYS:
+            metrics[key] = None
+        metrics["verifier_neighbors_error"] = str(e)
 
 
 def compute_metrics(fake_images, real_images: Optional[torch.Tensor], device: torch.device,
-                    verifier: Optional[VerifierFeatures] = None) -> Dict[str, Any]:
+                    verifier: Optional[VerifierFeatures] = None, neighbors_k: Optional[int] = None) -> Dict[str, Any]:
     """The report's ``metrics`` dictionary.  ``fake_images``: a GeneratedSamples (its counters are used) or a tensor.
-    ``verifier``: add the Frechet distance over its embeddings (the ``verifier_*`` keys; none without it)."""
+    ``verifier``: add the Frechet distance over its embeddings (the ``verifier_*`` keys; none without it).
+    ``neighbors_k``: add precision / recall, density / coverage and the nearest-real distances at that k."""
     metrics: Dict[str, Any] = {"n_samples": len(fake_images), "image_shape": list(fake_images.shape[1:]),
                                "metrics_computed_at": datetime.now().isoformat()}
     if real_images is not None and INCEPTION_AVAILABLE:
@@ -275,8 +332,11 @@ def compute_metrics(fake_images, real_images: Optional[torch.Tensor], device: to
         print("  Skipping LPIPS: lpips package not available")
         metrics["lpips_diversity"], metrics["lpips_error"] = None, "lpips package not available"
 
+    real_embeddings = None
     if verifier is not None:
-        _verifier_frechet(metrics, fake_images, real_images, verifier)
+        real_embeddings = _verifier_frechet(metrics, fake_images, real_images, verifier)
+    if neighbors_k is not None:
+        _verifier_neighbors(metrics, fake_images, real_embeddings, verifier, neighbors_k)
 
     print("Computing stroke density distribution...")
     try:
@@ -310,7 +370,7 @@ def save_evaluation_report(metrics: Dict[str, Any], config: Dict[str, Any], outp
     output_dir = Path(output_dir)
     output_dir.mkdir(parents=True, exist_ok=True)
     # the verifier's distance joins the summary of a report that has it; a report made without the flag keeps its keys
-    extra = {"verifier_frechet_distance": metrics["verifier_frechet_distance"]} if "verifier_frechet_distance" in metrics else {}
+    extra = {key: metrics[key] for key in ("verifier_frechet_distance", "verifier_precision", "verifier_recall") if key in metrics}
     report = {
         "evaluation_info": {"checkpoint": str(checkpoint_path), "evaluation_timestamp": datetime.now().isoformat(),
                             "sample_grids": [str(p) for p in grid_paths]},
@@ -343,6 +403,12 @@ def print_summary(metrics: Dict[str, Any]) -> None:
         vfd = metrics["verifier_frechet_distance"]
         print(f"Verifier Frechet Distance: {vfd:.4f} (lower is better)" if vfd is not None
               else f"Verifier Frechet Distance: Not computed - {metrics.get('verifier_frechet_error', 'unknown reason')}")
+    if "verifier_precision" in metrics:
+        for label, key, hint in (("Precision", "verifier_precision", "generated samples inside the real manifold"),
+                                 ("Recall", "verifier_recall", "real samples inside the generated manifold")):
+            v = metrics[key]
+            print(f"Verifier {label}: {v:.4f} ({hint}, k = {metrics.get('verifier_neighbors_k')})" if v is not None
+                  else f"Verifier {label}: Not computed - {metrics.get('verifier_neighbors_error', 'unknown reason')}")
     print("\n--- Stroke Analysis ---")
     stroke = metrics.get("stroke_density")
     if stroke:
@@ -372,6 +438,7 @@ class _Args(argparse.Namespace):
     """The flags this tool adds to the reference's are opt-in all the way: they read as their default, and a command line
     without them parses to the reference's attributes and nothing else."""
     verifier_checkpoint = None
+    verifier_neighbors = None
 
 
 def parse_args(argv=None) -> argparse.Namespace:
@@ -388,6 +455,9 @@ def parse_args(argv=None) -> argparse.Namespace:
     p.add_argument("--seed", type=int, default=None, help="Random seed for reproducibility")
     p.add_argument("--verifier_checkpoint", type=str, default=None,
                    help="Siamese verifier checkpoint: adds a Frechet distance over its embeddings (needs --real_dir)")
+    p.add_argument("--verifier_neighbors", type=int, default=None, metavar="K",
+                   help="With --verifier_checkpoint and --real_dir: adds precision / recall, density / coverage and "
+                        "nearest-real distances over the verifier's embeddings, from K nearest neighbours")
     return p.parse_args(argv, namespace=_Args())
 
 
@@ -403,7 +473,7 @@ def main(argv=None) -> int:
     real_dir = Path(a.real_dir) if a.real_dir else None
     try:
         generator, config = load_generator_from_checkpoint(checkpoint_path, device)
-        verifier = (VerifierFeatures(Path(a.verifier_checkpoint), device, generator.output_size)
+        verifier = (VerifierFeatures(Path(a.verifier_checkpoint), device, generator.output_size, a.verifier_neighbors)
                     if a.verifier_checkpoint else None)
         fake = generate_samples(generator, a.n_samples, generator.latent_dim, device, a.batch_size,
                                 keep_images=max(0, a.n_grids) * a.grid_size,
@@ -417,7 +487,7 @@ def main(argv=None) -> int:
             except Exception as e:                              # noqa: BLE001 -- the evaluation goes on without them
                 print(f"Warning: Could not load real images: {e}")
         print("\nComputing evaluation metrics...")
-        metrics = compute_metrics(fake, real, device, verifier)
+        metrics = compute_metrics(fake, real, device, verifier, a.verifier_neighbors)
         report_path = save_evaluation_report(metrics, config, output_dir, checkpoint_path, grid_paths)
         print_summary(metrics)
         print("\nEvaluation complete!")

@@ -10,7 +10,9 @@ for another P the two may differ in the last bit.
 FID and LPIPS need downloaded network weights; computing them is not built.  The availability flags and the ImportError
 texts are the reference's, so callers (the evaluation CLI) report them the same way.  What IS built is the same
 construction over a network the user trains here: ``calculate_verifier_frechet_distance``, a Frechet distance between two
-image sets in the Siamese verifier's embedding space (utils/frechet.py; the statistics are accumulated on the device)."""
+image sets in the Siamese verifier's embedding space (utils/frechet.py; the statistics are accumulated on the device),
+and ``calculate_verifier_manifold_metrics``: precision / recall, density / coverage and nearest-real distances in that space
+(utils/neighbors.py; exact fp64 nearest-neighbour queries on the device)."""
 from collections import defaultdict
 from typing import Any, Dict, List, Optional, Union
 
@@ -19,6 +21,7 @@ import torch
 
 from .._lib import IS_INK_SIGNED, IS_INK_UNIT, IS_NEG
 from .frechet import FeatureMoments, embedding_spread, frechet_distance
+from .neighbors import manifold_metrics
 
 try:
     from torchvision.models import inception_v3  # noqa: F401
@@ -46,9 +49,9 @@ def calculate_lpips_diversity(images_list: List[torch.Tensor], device: Optional[
 
 
 # ---- Frechet distance over verifier embeddings (device moments, host root) ---------------------------------------------
-def accumulate_verifier_moments(moments: FeatureMoments, images: torch.Tensor, verifier, max_batch: Optional[int] = None) -> None:
+def verifier_embedding_chunks(images: torch.Tensor, verifier, max_batch: Optional[int] = None):
     """Embed ``images`` -- fp32 (N, 1, 64, 64) in [-1, 1] or uint8 (N, 64, 64), on the verifier's device -- in chunks of at
-    most min(max_batch, verifier.max_images) and add every chunk's embeddings to ``moments``; nothing reaches the host."""
+    most min(max_batch, verifier.max_images); yields every chunk's (b, E) fp32 embeddings, which stay on the device."""
     if images.dtype == torch.uint8:
         embed = verifier.embed_u8
     elif images.dtype == torch.float32:
@@ -57,7 +60,13 @@ def accumulate_verifier_moments(moments: FeatureMoments, images: torch.Tensor, v
         raise ValueError(f"images must be float32 or uint8, got {images.dtype}")
     step = int(verifier.max_images) if max_batch is None else max(1, min(int(max_batch), int(verifier.max_images)))
     for i in range(0, images.shape[0], step):
-        moments.update(embed(images[i:i + step]))
+        yield embed(images[i:i + step])
+
+
+def accumulate_verifier_moments(moments: FeatureMoments, images: torch.Tensor, verifier, max_batch: Optional[int] = None) -> None:
+    """Add the embeddings of ``images`` (``verifier_embedding_chunks``) to ``moments``; nothing reaches the host."""
+    for emb in verifier_embedding_chunks(images, verifier, max_batch):
+        moments.update(emb)
 
 
 def calculate_verifier_frechet_distance(real_images: torch.Tensor, fake_images: torch.Tensor, verifier,
@@ -81,6 +90,32 @@ def calculate_verifier_frechet_distance(real_images: torch.Tensor, fake_images: 
     (n_r, mu_r, cov_r), (n_f, mu_f, cov_f) = stats
     return {"frechet_distance": frechet_distance(mu_r, cov_r, mu_f, cov_f), "spread_real": embedding_spread(cov_r),
             "spread_generated": embedding_spread(cov_f), "n_real": n_r, "n_generated": n_f, "embedding_dim": dim}
+
+
+# ---- precision / recall / nearest-real distances over verifier embeddings (device k-NN, host means) ------------------
+def verifier_embeddings(images: torch.Tensor, verifier, max_batch: Optional[int] = None) -> torch.Tensor:
+    """The (N, E) fp32 embeddings of ``images`` in one device buffer, embedded by the chunked route of the moments."""
+    with torch.no_grad():
+        chunks = [emb.detach().to(torch.float32) for emb in verifier_embedding_chunks(images, verifier, max_batch)]
+    if not chunks:
+        return torch.empty(0, int(verifier.embedding_dim), dtype=torch.float32, device=images.device)
+    return torch.cat(chunks, dim=0).contiguous()
+
+
+def calculate_verifier_manifold_metrics(real_images: torch.Tensor, fake_images: torch.Tensor, verifier, k: int = 3,
+                                        max_batch: Optional[int] = None) -> Dict[str, Any]:
+    """Improved precision / recall, density / coverage and nearest-real distances of two image sets in the embedding
+    space of ``verifier`` (as for ``calculate_verifier_frechet_distance``: the same image formats, the same chunks).  More
+    than k images per set, else ValueError.  -> utils.neighbors.manifold_metrics' dictionary plus 'embedding_dim'."""
+    dev = next(verifier.parameters()).device
+    if real_images.shape[0] <= k or fake_images.shape[0] <= k:
+        raise ValueError(f"the k-th neighbour inside a set needs more than k = {k} images per set, got "
+                         f"{real_images.shape[0]} and {fake_images.shape[0]}")
+    real_emb = verifier_embeddings(real_images.to(dev), verifier, max_batch)
+    fake_emb = verifier_embeddings(fake_images.to(dev), verifier, max_batch)
+    out = manifold_metrics(real_emb, fake_emb, k)
+    out["embedding_dim"] = int(verifier.embedding_dim)
+    return out
 
 
 # ---- counters -> dictionaries (pure numpy) ---------------------------------------------------------------------------
