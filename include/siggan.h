@@ -50,7 +50,7 @@ extern "C" {
 #define SIGGAN_ABI_VERSION 4   /* 2: siggan_stage_real, siggan_augment_batch; 3: siggan_config.dtype, siggan_rng_state, siggan_comm_*;
                                 * 4: siggan_config.g_leaky_slope (appended); siggan_prof_launch (a test hook, added);
                                 *    siggan_g_generate_u8, siggan_image_stats (added: no existing call or struct changes);
-                                *    siggan_d_score_u8, siggan_dequant_table (added likewise) */
+                                *    siggan_d_score_u8, siggan_dequant_table (added likewise); siggan_g_latent_grad (added likewise) */
 
 enum {
     SIGGAN_OK = 0,
@@ -203,6 +203,20 @@ enum { SIGGAN_IS_NEG = 0, SIGGAN_IS_INK_SIGNED = 1, SIGGAN_IS_INK_UNIT = 2, SIGG
  * stats_dev (B, SIGGAN_IS_COUNT) int32 optional, zeroed by the call (threshold must then be finite). */
 int siggan_g_generate_u8(siggan_ctx *ctx, const float *z_dev, int32_t batch, uint8_t *u8_dev,
                          float *images_dev, int32_t *stats_dev, float threshold, void *stream);
+
+/* Eval-mode Generator forward of z_dev (B,latent), the per-image reconstruction loss against a target batch and its
+ * gradient with respect to z: the primitive an optimiser on z runs around (projection of signatures into the latent space).
+ * Exactly one of target_u8_dev (B,S,S) uint8 (4-byte aligned) and target_f32_dev (B,1,S,S) fp32 (16-byte aligned) is given; a
+ * byte b stands for the fp32 value siggan_dequant_table gives it.
+ *   loss_dev[b]   = mean over the S*S pixels of (x - t)^2,  x = G(z)[b]  (fp32)
+ *   dz_dev[b, :]  = d loss_dev[b] / d z[b, :]               (eval mode: images do not interact)
+ *   images_dev    optional (B,1,S,S), 16-byte aligned: bit for bit siggan_g_forward(training = 0)
+ * fp32 contexts only.  Fixed-order sums, no atomics: equal inputs give equal bits.  A fixed sequence of launches on the
+ * caller's stream, no host synchronisation.  It overwrites the Generator's activations (as siggan_g_forward does) and
+ * training scratch no call carries over; a training step after it runs exactly as if it had not been called.  Refused with
+ * SIGGAN_E_STATE between siggan_step_begin and its siggan_g_grads (the pipelined forward's activations are still needed). */
+int siggan_g_latent_grad(siggan_ctx *ctx, const float *z_dev, int32_t batch, const uint8_t *target_u8_dev,
+                         const float *target_f32_dev, float *dz_dev, float *loss_dev, float *images_dev, void *stream);
 
 /* x_dev (B,1,S,S) -> probs_dev (B) probabilities.  features_dev (B,512*4*4, reference
  * flatten order c,h,w) optional.  training!=0 enables Dropout2d: masks_dev, if given, holds the

@@ -95,6 +95,7 @@ _SIGNATURES = {
     "siggan_d_forward": (C.c_int, [_P, _P, _I32, _I32, _P, _P, _P, _P]),
     "siggan_d_score_u8": (C.c_int, [_P, _P, _I32, _I32, _P, _P, _P]),
     "siggan_dequant_table": (C.c_int, [C.POINTER(C.c_float)]),
+    "siggan_g_latent_grad": (C.c_int, [_P, _P, _I32, _P, _P, _P, _P, _P, _P]),
     "siggan_d_step": (C.c_int, [_P, _P, _I32, _P, _P, C.POINTER(Hyper), _P, _P, _P]),
     "siggan_g_step": (C.c_int, [_P, _I32, _P, C.POINTER(Hyper), _P, _P, _P]),
     "siggan_d_grads": (C.c_int, [_P, _P, _I32, _P, _P, C.POINTER(Hyper), _P, _P]),

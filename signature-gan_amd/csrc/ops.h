@@ -110,6 +110,27 @@ void launch_final_bn_bwd_apply(int dt, const float* dpre, const float* Wt, const
                                const float* partial, const float* partial_w, float* dW, float* db, float* dgamma, float* dbeta,
                                float gslope, hipStream_t s, hipEvent_t done = nullptr);
 
+// ---- latent-space projection (latent.hip): eval-mode d(loss)/dz of a per-image reconstruction loss, fp32 tensors only -------
+// per-image partial sums of (x - t)^2 and dpre = (2 / S^2) (x - t) (1 - x^2) from the stored fp32 image x [B][S][S]; the target
+// is t_u8 (bytes through the 256-entry table lut) or t_f32, exactly one of them.  One partial per 1024 pixels:
+// part[b * (S*S/1024) + j], each a fixed shuffle / LDS tree (recon_loss_parts(S) of them per image).
+int recon_loss_parts(int S);
+void launch_recon_loss(const float* img, const uint8_t* t_u8, const float* t_f32, const float* lut, float* dpre, float* part,
+                       int B, int S, hipStream_t s);
+// ONE launch for the two small jobs behind it: loss[b] = (part[b][0] + part[b][1] + ...) / S^2 in index order, and the per-image
+// copies tab[b][c] = scale[c] of nt eval-mode BatchNorm scale rows (what EPI_LRELU_BWD multiplies by as its [B][C] table)
+struct ScaleTiles { static constexpr int MAXT = 8; int nt; const float* src[MAXT]; float* dst[MAXT]; int C[MAXT]; };
+void launch_loss_fin_tiles(const float* part, int nparts, float* loss, int B, int S, const ScaleTiles& t, hipStream_t s);
+// eval-mode input-gradient of the final 3x3 conv through the last block's activation and folded BatchNorm:
+// da[n][y][x][c] = g_dact(a[n][y][x][c]) * scale[c] * sum_{kh,kw} dpre[n][y+1-kh][x+1-kw] * Wt[kh*3+kw][c]   (C == 32)
+void launch_final_dgrad_eval(const float* dpre, const float* Wt, const float* a, const float* scale, float* da, int B, int S,
+                             float gslope, hipStream_t s);
+// dz[b][k] = sum_f' dh[b][f'] * g_dact(a0[b][f']) * scale0[f'] * W[f(f')][k], f' = hw*C0 + c <-> f = c*16 + hw (W: the torch-layout
+// (F, K) fc weight).  F is split over workgroups; the partial rows land in `part` (part_cap floats) and are added in split order.
+// Any K >= 1.
+void launch_fc_dz(const float* dh, const float* a0, const float* scale0, const float* W, float* dz, float* part, int64_t part_cap,
+                  int B, int K, int C0, float gslope, hipStream_t s);
+
 // ---- Discriminator pieces -----------------------------------------------------------------
 // first block (Cin = 1): x = two segments (x0: n < n0, x1: the rest), out [B][S/2][S/2][C]
 void launch_conv1_fwd(int dt, const float* x0, int n0, const float* x1, const float* W, const float* b,

@@ -229,6 +229,7 @@ struct siggan_ctx {
     float *wcp;
     float *slab, *slab_k, *slab_k2, *slab_k3, *partial, *partial_b, *partial_c, *z_g, *img_g, *metrics, *zeros, *wfc_t, *wfin_t, *d_w1t, *real_stage, *mask_stage;
     float* deq_lut;      // the 256 dequantised byte values (siggan_dequant_table), read by siggan_d_score_u8's first block
+    float* lg_tab;       // siggan_g_latent_grad: per-image copies [B][C_l] of the eval-mode BatchNorm scale rows of blocks 1 .. Lg-1
     char *op_pack;
     int64_t slab_floats, slab_k_floats;
     DevState* dev;
@@ -470,6 +471,7 @@ extern "C" int siggan_create(const siggan_config* cfg, siggan_ctx** out) {
         carve(&c->d_w1t, (int64_t)16 * c->dC[1]);
         carve(&c->ride_ctr, 64);
         carve(&c->deq_lut, 256);
+        { int64_t sumC = 0; for (int l = 1; l < c->Lg; ++l) sumC += c->gC[l]; carve(&c->lg_tab, Bm * sumC); }
         float* devp = nullptr;
         carve(&devp, 64);
         if (pass == 1) c->dev = (DevState*)devp;
@@ -1494,6 +1496,64 @@ extern "C" int siggan_g_generate_u8(siggan_ctx* c, const float* z_dev, int32_t b
     repack(c, L, s, s, c->g_dirty, !c->sn && c->d_dirty);
     c->g_dirty = false; if (!c->sn) c->d_dirty = false;
     c->cs.ga_last_B = g_forward_pass(c, z_dev, batch, false, images_dev, s, nullptr, nullptr, 0, nullptr, nullptr, u8_dev, stats_dev, threshold);
+    LAUNCHCHK();
+    return lane_check(c);
+}
+
+// The gradient of a per-image reconstruction loss with respect to z through the EVAL-mode Generator: forward with every
+// activation kept (g_a), then backward with BatchNorm as the per-channel affine it is in eval mode -- g . act'(a) . scale[c], none
+// of the training backward's batch sums -- down to dz = dh . W_fc.  Launches (2 Lg + 7, plus a split-K tail where launch_gconv
+// splits): forward Lg + 2, loss 1, loss sum + scale tables 1, final conv input-gradient 1, one implicit GEMM per block, fc 2.
+// The blocks' input-gradients are launch_gconv form 0 on the packs g_dn[l], as in g_backward_pass, with the EXISTING epilogue
+// EPI_LRELU_BWD: acc * (aref > 0 ? 1 : slope) * noise[n][c] on the stored activation is exactly block l-1's mask and eval scale
+// once `noise` is that block's scale row repeated per image (lg_tab, rebuilt every call: the running statistics move).  Block 0's
+// scale is per feature (F values), so the GEMM into it stores raw values and k_fc_dz applies mask and scale on load.
+// Scratch: dpre, g_da, partial, partial_b, lg_tab -- all rewritten by a training phase before it reads them, none carried
+// between calls; the activations g_a are the eval forward's to overwrite (Carried::ga_last_B says so).
+extern "C" int siggan_g_latent_grad(siggan_ctx* c, const float* z_dev, int32_t batch, const uint8_t* target_u8_dev,
+                                    const float* target_f32_dev, float* dz_dev, float* loss_dev, float* images_dev, void* stream) {
+    ENTER(c);
+    int rc = check_call(c, batch);
+    if (rc) return rc;
+    if (c->dt != DT_F32) return fail(SIGGAN_E_INVALID, "siggan_g_latent_grad needs an fp32 context (16-bit activations are not built for it)");
+    if ((target_u8_dev != nullptr) == (target_f32_dev != nullptr))
+        return fail(SIGGAN_E_INVALID, "exactly one of target_u8_dev and target_f32_dev must be given");
+    if (!z_dev || !dz_dev || !loss_dev) return fail(SIGGAN_E_INVALID, "null tensor");
+    if (reinterpret_cast<uintptr_t>(target_u8_dev) & 3) return fail(SIGGAN_E_INVALID, "target_u8_dev must be 4-byte aligned");
+    if ((reinterpret_cast<uintptr_t>(target_f32_dev) | reinterpret_cast<uintptr_t>(images_dev)) & 15)
+        return fail(SIGGAN_E_INVALID, "target_f32_dev and images_dev must be 16-byte aligned");
+    if (c->cs.g_fwd_pending)
+        return fail(SIGGAN_E_STATE, "siggan_step_begin must be followed by siggan_g_grads first: the pipelined forward's activations are in use");
+    hipStream_t s = (hipStream_t)stream;
+    if ((rc = settle(c, s))) return rc;
+    Lanes L(c, s);
+    repack(c, L, s, s, c->g_dirty, !c->sn && c->d_dirty);
+    c->g_dirty = false; if (!c->sn) c->d_dirty = false;
+    const int B = batch, Lg = c->Lg, S = c->S;
+    const float gs = c->cfg.g_leaky_slope;
+    float* const img = images_dev ? images_dev : c->img;
+    c->cs.ga_last_B = g_forward_pass(c, z_dev, B, false, img, s);
+    launch_recon_loss(img, target_u8_dev, target_f32_dev, c->deq_lut, c->dpre, c->partial_b, B, S, s);
+    ScaleTiles t; memset(&t, 0, sizeof t);
+    const float* tab[MAXL + 1] = {nullptr};
+    float* next = c->lg_tab;
+    for (int l = 1; l < Lg; ++l) {
+        t.src[t.nt] = c->g_bne[l]; t.dst[t.nt] = next; t.C[t.nt] = c->gC[l]; ++t.nt;
+        tab[l] = next; next += (int64_t)B * c->gC[l];
+    }
+    launch_loss_fin_tiles(c->partial_b, recon_loss_parts(S), loss_dev, B, S, t, s);
+    launch_final_dgrad_eval(c->dpre, c->wfin_t, (const float*)c->g_a[Lg], c->g_bne[Lg], (float*)c->g_da[Lg], B, S, gs, s);
+    for (int l = Lg; l >= 1; --l) {
+        const int Hi = 4 << (l - 1), Ho = 2 * Hi, Ci = c->gC[l - 1], Co = c->gC[l];
+        GConvArgs a = gconv_args(c);
+        a.in = c->g_da[l]; a.wp = c->g_dn[l]; a.out = c->g_da[l - 1];
+        a.B = B; a.Hi = Ho; a.Wi = Ho; a.Ci = Co; a.Co = Ci;
+        a.lgHr = ilog2i(Hi); a.lgWr = a.lgHr; a.Ho = Hi; a.Wo = Hi; a.form = 0; a.M = B * Hi * Hi; a.epi = EPI_RAW;
+        if (l >= 2) { a.epi = EPI_LRELU_BWD; a.aref = c->g_a[l - 1]; a.noise = tab[l - 1]; a.slope = gs; }
+        launch_gconv(a, s);
+    }
+    launch_fc_dz((const float*)c->g_da[0], (const float*)c->g_a[0], c->g_bne[0], GP(c, gi_fc_w()), dz_dev, c->partial,
+                 PARTIAL_FLOATS - 64, B, c->latent, c->gC[0], gs, s);      // (the last 64 floats: siggan_op_adam's scratch slot)
     LAUNCHCHK();
     return lane_check(c);
 }

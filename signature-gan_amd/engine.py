@@ -310,6 +310,38 @@ class Engine:
         out = (u8,) + ((stats,) if stats is not None else ()) + ((img,) if img is not None else ())
         return out[0] if len(out) == 1 else out
 
+    def g_latent_grad(self, z, target, want_images=False, dz_out=None, loss_out=None):
+        """Eval-mode forward of z (B, latent), the per-image reconstruction loss mean((G(z) - t)^2) against ``target`` and its
+        gradient with respect to z (siggan_g_latent_grad; fp32 contexts).  ``target``: a uint8 (B, S, S) device tensor -- a
+        byte stands for its _lib.dequant_table() value -- or an fp32 (B, 1, S, S) one.  Returns (dz, loss[, images]): dz
+        (B, latent), loss (B,), images (B, 1, S, S) bit for bit g_forward(z).  ``dz_out`` / ``loss_out``: caller-owned contiguous
+        fp32 device tensors of B * latent / B elements the results are written into (an optimiser loop's gradient buffer, a
+        row of its loss history); they are then what is returned.  Nothing synchronises with the host."""
+        z = _f32(z, self.device, "z")
+        if z.dim() != 2 or z.shape[1] != self.latent_dim:
+            raise ValueError(f"z must be (B, {self.latent_dim}), got {tuple(z.shape)}")
+        b, s = z.shape[0], self.image_size
+        if target.device != self.device:
+            raise ValueError(f"target must live on {self.device}, got {target.device}")
+        if target.dtype == torch.uint8:
+            shape, t_u8, t_f32 = (b, s, s), target.contiguous(), None
+        elif target.dtype == torch.float32:
+            shape, t_u8, t_f32 = (b, 1, s, s), None, target.contiguous()
+        else:
+            raise ValueError(f"target must be uint8 (B, S, S) or float32 (B, 1, S, S), got {target.dtype}")
+        if tuple(target.shape) != shape:
+            raise ValueError(f"target must be {shape}, got {tuple(target.shape)}")
+        self._check_batch(b)
+        for t, n, what in ((dz_out, b * self.latent_dim, "dz_out"), (loss_out, b, "loss_out")):
+            if t is not None and (t.device != self.device or t.dtype != torch.float32 or t.numel() != n or not t.is_contiguous()):
+                raise ValueError(f"{what} must be a contiguous float32 tensor of {n} elements on {self.device}")
+        dz = torch.empty(b, self.latent_dim, dtype=torch.float32, device=self.device) if dz_out is None else dz_out
+        loss = torch.empty(b, dtype=torch.float32, device=self.device) if loss_out is None else loss_out
+        img = torch.empty(b, 1, s, s, dtype=torch.float32, device=self.device) if want_images else None
+        _lib.check(self.lib.siggan_g_latent_grad(self._h, _ptr(z), b, _ptr(t_u8), _ptr(t_f32), _ptr(dz), _ptr(loss), _ptr(img),
+                                                 self._stream()))
+        return (dz, loss, img) if want_images else (dz, loss)
+
     @staticmethod
     def image_stats(x, threshold):
         """int32 (B, 3) per-image stroke counters of a contiguous fp32 (B, ...) device tensor against ``threshold``

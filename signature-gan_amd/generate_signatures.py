@@ -5,17 +5,23 @@ Generator forward on the MI355X HIP engine (``siggan_g_forward``).  Flags, file 
 ``--filter_by_realism`` adds the reference app's realism filter (app_vanilla_gan_signatures.py:1065-1385) to the CLI: oversample,
 score every image with the checkpoint's Discriminator, keep the best ``--n_samples`` -- on the device
 (utils.inference.generate_signatures_filtered).  ``--noise_scale`` and ``--threshold`` / ``--transparent`` (the app's
-post-processing) also apply to a plain run.  Without the new flags, files and stdout are what they were."""
+post-processing) also apply to a plain run.  Without the new flags, files and stdout are what they were.
+
+``--project PATH`` and ``--morph [A B]`` go the other way, from images to latent vectors (utils.inference.project_signatures:
+Adam on z around the library's eval-mode dL/dz), and build the app's second generation tab, "Morphing"
+(app_vanilla_gan_signatures.py:1631-1717), on it: ``--project`` reconstructs every image of a file or directory, ``--morph A B``
+projects two images and writes the strip of frames between them, ``--morph`` alone morphs between two random endpoints."""
 import argparse
 import json
 import os
 import sys
 from typing import Any, Dict, Optional
 
+import numpy as np
 import torch
 
 from .utils.inference import (generate_signatures_batch, generate_signatures_filtered, load_discriminator, load_generator,
-                              process_images)
+                              load_target_images, morph_sequence, morph_strip, process_images, project_signatures)
 
 
 def generate_signatures(generator, n_samples: int, output_dir: str, batch_size: int = 64,
@@ -64,6 +70,57 @@ def generate_filtered(generator, discriminator, n_samples: int, output_dir: str,
         print(f"Realism scores: best {scores[0]:.4f}, worst kept {scores[-1]:.4f}")
 
 
+def run_projection(generator, path: str, output_dir: str, prefix: str = "signature", steps: int = 200, lr: float = 0.05,
+                   restarts: int = 1, seed: Optional[int] = None) -> None:
+    """Reconstructions of the image file / the images of the directory ``path``: ``<prefix>_projection_%06d.png`` each, and
+    ``<prefix>_projection.json``: [{file, reconstruction, loss, z}, ...] in the same order."""
+    from PIL import Image
+    os.makedirs(output_dir, exist_ok=True)
+    files, targets = load_target_images(path, generator.output_size)
+    print(f"Projecting {len(files)} images into the latent space ({steps} steps, {restarts} restart(s))...")
+    z, recon, loss, _ = project_signatures(generator, targets, steps=steps, lr=lr, seed=seed, restarts=restarts)
+    z, loss = z.cpu(), loss.cpu()
+    records = []
+    for i, name in enumerate(files):
+        out = f"{prefix}_projection_{i + 1:06d}.png"
+        Image.fromarray(recon[i], mode="L").save(os.path.join(output_dir, out), "PNG")
+        records.append({"file": name, "reconstruction": out, "loss": float(loss[i]), "z": [float(v) for v in z[i]]})
+    with open(os.path.join(output_dir, f"{prefix}_projection.json"), "w") as f:
+        json.dump(records, f, indent=2)
+    print(f"Reconstruction loss (mean squared error in [-1, 1]): best {float(loss.min()):.3e}, worst {float(loss.max()):.3e}")
+    print(f"Saved {len(files)} reconstructions to: {output_dir}")
+
+
+def run_morph(generator, endpoints, output_dir: str, device: torch.device, prefix: str = "signature", n_frames: int = 10,
+              seed: Optional[int] = None, threshold: Optional[int] = None, transparent: bool = False, steps: int = 200,
+              lr: float = 0.05, restarts: int = 1) -> None:
+    """``<prefix>_morph.png``: the strip of ``n_frames`` frames between two latent endpoints -- the projections of the two image
+    files in ``endpoints`` (then ``<prefix>_morph.json`` holds their files, losses and z vectors), or two N(0, 1) draws seeded
+    by ``seed`` when ``endpoints`` is empty."""
+    os.makedirs(output_dir, exist_ok=True)
+    if endpoints:
+        files, targets = [], []
+        for p in endpoints:
+            f, t = load_target_images(p, generator.output_size)
+            if len(f) != 1:
+                raise ValueError(f"--morph takes two image files, {p} holds {len(f)} images")
+            files += f; targets.append(t[0])
+        z, _, loss, _ = project_signatures(generator, np.stack(targets), steps=steps, lr=lr, seed=seed, restarts=restarts)
+        with open(os.path.join(output_dir, f"{prefix}_morph.json"), "w") as f:
+            json.dump({"files": files, "losses": [float(v) for v in loss.cpu()], "z": [[float(v) for v in row] for row in z.cpu()]},
+                      f, indent=2)
+        print(f"Projected the endpoints: losses {float(loss[0]):.3e}, {float(loss[1]):.3e}")
+    else:
+        if seed is not None:
+            torch.manual_seed(seed)
+            if torch.cuda.is_available():
+                torch.cuda.manual_seed_all(seed)
+        z = torch.cat([torch.randn(1, generator.latent_dim, device=device), torch.randn(1, generator.latent_dim, device=device)])
+    frames = morph_sequence(generator, z[0:1], z[1:2], n_frames)
+    morph_strip(frames, threshold=threshold, make_transparent=transparent).save(os.path.join(output_dir, f"{prefix}_morph.png"), "PNG")
+    print(f"Saved a morph strip of {n_frames} frames to: {os.path.join(output_dir, prefix + '_morph.png')}")
+
+
 def get_checkpoint_info(checkpoint_path: str) -> Dict[str, Any]:
     if not os.path.exists(checkpoint_path):
         return {"error": f"Checkpoint not found: {checkpoint_path}"}
@@ -94,7 +151,23 @@ def parse_args(argv=None) -> argparse.Namespace:
     p.add_argument("--threshold", type=int, default=None, help="Binarise before scoring and saving: pixel < THRESHOLD -> 0, else 255")
     p.add_argument("--transparent", action="store_true", help="With --threshold: save RGBA with the white background transparent")
     p.add_argument("--noise_scale", type=float, default=1.0, help="Scale of the latent noise")
+    p.add_argument("--morph", type=str, nargs="*", default=None, metavar="IMAGE",
+                   help="Write <prefix>_morph.png, a strip of frames between two latent endpoints: the projections of two image "
+                        "files, or two random draws (from --seed) when no files are given")
+    p.add_argument("--morph_frames", type=int, default=10, help="Frames of the morph strip")
+    p.add_argument("--project", type=str, default=None, metavar="PATH",
+                   help="Project an image file, or every image of a directory, into the latent space; write the reconstructions "
+                        "and <prefix>_projection.json")
+    p.add_argument("--project_steps", type=int, default=200, help="Adam iterations of a projection")
+    p.add_argument("--project_lr", type=float, default=0.05, help="Adam learning rate of a projection")
+    p.add_argument("--project_restarts", type=int, default=1, help="Random starts per image (the lowest final loss is kept)")
     a = p.parse_args(argv)
+    if a.morph is not None and len(a.morph) not in (0, 2):
+        p.error("--morph takes no image files (random endpoints) or exactly two")
+    if a.morph_frames < 2:
+        p.error("--morph_frames must be >= 2")
+    if a.project_steps < 1 or a.project_restarts < 1 or not a.project_lr > 0:
+        p.error("--project_steps and --project_restarts must be >= 1, --project_lr > 0")
     if a.oversampling_ratio < 1.0:
         p.error("--oversampling_ratio must be >= 1.0")
     if a.threshold is not None and not 0 <= a.threshold <= 255:
@@ -116,6 +189,13 @@ def main(argv=None) -> None:
             print(f"  {k}: {v}")
         return
     generator, _ = load_generator(a.checkpoint, device)
+    if a.project is not None or a.morph is not None:
+        if a.project is not None:
+            run_projection(generator, a.project, a.output_dir, a.prefix, a.project_steps, a.project_lr, a.project_restarts, a.seed)
+        if a.morph is not None:
+            run_morph(generator, a.morph, a.output_dir, device, a.prefix, a.morph_frames, a.seed, a.threshold, a.transparent,
+                      a.project_steps, a.project_lr, a.project_restarts)
+        return
     if a.filter_by_realism:
         discriminator = load_discriminator(a.checkpoint, device, image_size=generator.output_size)
         if discriminator is None:

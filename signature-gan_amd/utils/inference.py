@@ -8,7 +8,11 @@ of ``upsample_blocks.N.block.0.weight`` keys (>= 5 -> 128x128).
 
 Realism-filtered generation (the reference app's "Filter by Realism", app_vanilla_gan_signatures.py:1065-1385, which is not UI:
 it is where a trained Discriminator is used after training) lives here too: ``load_discriminator``, ``binarize_uint8`` /
-``process_images``, ``filter_plan`` and ``generate_signatures_filtered``."""
+``process_images``, ``filter_plan`` and ``generate_signatures_filtered``.
+
+So does the way back from an image to a latent vector: ``project_signatures`` (an Adam loop on z around
+Engine.g_latent_grad), and on top of it the app's second generation tab, "Morphing" (app_vanilla_gan_signatures.py:1631-1717):
+``morph_blend``, ``morph_sequence`` and ``morph_strip``."""
 from typing import Any, Dict, List, Optional, Tuple
 
 import numpy as np
@@ -258,3 +262,157 @@ def generate_signatures_filtered(generator: Generator, discriminator: Discrimina
     picked = _to_host_u8(g_eng.gather_u8(pool, index, binarize=binarize))
     best = _to_host_u8(scores[index.long()].view(torch.uint8)).view(np.float32)
     return [Image.fromarray(arr, mode="L") for arr in picked], [float(sc) for sc in best]
+
+
+# ---- projection into the latent space and morphing ---------------------------------------------------------------------
+def load_target_images(path: str, image_size: int) -> Tuple[List[str], np.ndarray]:
+    """(file names, (N, S, S) uint8): the image file ``path``, or the images of the directory ``path`` in the loader's sorted
+    order, decoded and resized as evaluate_vanilla_gan_signatures.load_real_images does it (SignatureDataset.decode: PIL ->
+    'L' -> bilinear resize).  An unreadable file raises."""
+    import os
+    from pathlib import Path
+    from ..data_loader_signatures import SignatureDataset
+    p = Path(path)
+    if not p.exists():
+        raise FileNotFoundError(f"no such image file or directory: {path}")
+    ds = SignatureDataset(p if p.is_dir() else p.parent)
+    if not p.is_dir():
+        ds.image_paths = [p]
+    if len(ds) == 0:
+        raise ValueError(f"No images found in {path}")
+    names, out = [], []
+    for i in range(len(ds)):
+        arr = ds.decode(i, image_size)
+        if arr is None:
+            raise ValueError(f"unreadable image: {ds.get_image_path(i)}")
+        names.append(os.path.basename(str(ds.get_image_path(i)))); out.append(arr)
+    return names, np.stack(out)
+
+
+def projection_plan(n_targets: int, restarts: int, max_batch: int) -> List[Tuple[int, int, int]]:
+    """[(restart, first target, count), ...]: the batches of a projection, in the order they run.  Every restart walks the
+    targets in the same chunks of ``max_batch``, so the batch a candidate is optimised in -- and with it the kernels the
+    library picks, whose summation orders follow the batch size -- does not depend on how many restarts were asked for:
+    restart r of a run with R restarts is bit for bit the run with one restart seeded ``seed + r``.  Pure host code."""
+    if n_targets < 0 or restarts < 1 or max_batch < 1:
+        raise ValueError(f"need n_targets >= 0, restarts >= 1, max_batch >= 1, got {n_targets}, {restarts}, {max_batch}")
+    return [(r, t0, min(max_batch, n_targets - t0)) for r in range(restarts) for t0 in range(0, n_targets, max_batch)]
+
+
+def projection_starts(n_targets: int, latent_dim: int, restart: int, z0: Optional[torch.Tensor] = None,
+                      seed: Optional[int] = None) -> torch.Tensor:
+    """(n_targets, latent) fp32 on the CPU: where restart number ``restart`` starts.  Restart 0 starts at ``z0`` when that is
+    given; every other start is N(0, 1) from a CPU generator seeded ``seed + restart`` (unseeded: torch's global generator)."""
+    if restart == 0 and z0 is not None:
+        z0 = torch.as_tensor(z0, dtype=torch.float32).cpu()
+        if tuple(z0.shape) != (n_targets, latent_dim):
+            raise ValueError(f"z0 must be ({n_targets}, {latent_dim}), got {tuple(z0.shape)}")
+        return z0.clone()
+    gen = None if seed is None else torch.Generator().manual_seed(int(seed) + restart)
+    return torch.randn(n_targets, latent_dim, generator=gen)
+
+
+def project_signatures(generator: Generator, targets_u8, steps: int = 200, lr: float = 0.05,
+                       betas: Tuple[float, float] = (0.9, 0.999), z0: Optional[torch.Tensor] = None, seed: Optional[int] = None,
+                       restarts: int = 1, return_candidates: bool = False):
+    """Latent vectors whose images reproduce ``targets_u8`` ((N, S, S) uint8, numpy or tensor; a byte stands for
+    byte / 127.5 - 1.0): ``steps`` iterations of Adam on z against the per-image loss mean((G(z) - t)^2), every iteration one
+    Engine.g_latent_grad (eval forward + eval backward in HIP) and one Engine.op_adam on (z, dz, m, v), all enqueued without
+    a host synchronisation.  The Generator must be in eval() mode.  Batches: projection_plan; starts: projection_starts.
+
+    Returns (z (N, latent) fp32 device tensor, recon (N, S, S) uint8 numpy -- generate_uint8 at z --, loss (N,) device tensor:
+    the loss AT the returned z, history (steps, N) device tensor: the loss at the start of every iteration).  With
+    ``restarts`` > 1 each target keeps the start whose final loss is lowest (the first of equals); ``return_candidates`` adds
+    a dict with every candidate's ``z`` (R, N, latent), ``loss`` (R, N) and ``history`` (R, steps, N), and the kept ``choice``."""
+    if generator.training:
+        raise ValueError("project_signatures needs the Generator in eval() mode (running BatchNorm statistics)")
+    if steps < 1 or restarts < 1:
+        raise ValueError(f"steps and restarts must be >= 1, got {steps}, {restarts}")
+    eng = generator._require_engine()
+    dev, latent, size = eng.device, eng.latent_dim, eng.image_size
+    t_all = torch.as_tensor(np.ascontiguousarray(targets_u8) if isinstance(targets_u8, np.ndarray) else targets_u8)
+    if t_all.dtype != torch.uint8 or t_all.dim() != 3 or tuple(t_all.shape[1:]) != (size, size):
+        raise ValueError(f"targets_u8 must be uint8 (N, {size}, {size}), got {t_all.dtype} {tuple(t_all.shape)}")
+    t_all = t_all.to(dev).contiguous()
+    n = t_all.shape[0]
+    cand_z = torch.empty(restarts, n, latent, dtype=torch.float32, device=dev)
+    cand_loss = torch.empty(restarts, n, dtype=torch.float32, device=dev)
+    cand_hist = torch.empty(restarts, steps, n, dtype=torch.float32, device=dev)
+    starts = {}
+    for r, t0, b in projection_plan(n, restarts, eng.max_batch):
+        if r not in starts:
+            starts[r] = projection_starts(n, latent, r, z0, seed).to(dev)
+        z = starts[r][t0:t0 + b].contiguous().clone()
+        t = t_all[t0:t0 + b]
+        m, v = torch.zeros_like(z), torch.zeros_like(z)
+        dz = torch.empty_like(z)
+        hist = torch.empty(steps, b, dtype=torch.float32, device=dev)
+        for k in range(steps):
+            eng.g_latent_grad(z, t, dz_out=dz, loss_out=hist[k])
+            eng.op_adam(z, dz, m, v, k + 1, lr=lr, beta1=betas[0], beta2=betas[1])
+        eng.g_latent_grad(z, t, dz_out=dz, loss_out=cand_loss[r, t0:t0 + b])       # the loss at the z that is returned
+        cand_z[r, t0:t0 + b] = z
+        cand_hist[r, :, t0:t0 + b] = hist
+    choice = torch.argmin(cand_loss, dim=0)                                        # (plumbing: the first of equal minima)
+    pick = torch.arange(n, device=dev)
+    z_best, loss_best, hist_best = cand_z[choice, pick], cand_loss[choice, pick], cand_hist[choice, :, pick].t().contiguous()
+    recon = np.empty((n, size, size), dtype=np.uint8)
+    for t0 in range(0, n, eng.max_batch):
+        recon[t0:t0 + eng.max_batch] = generate_uint8(generator, z_best[t0:t0 + eng.max_batch].contiguous())
+    out = (z_best, recon, loss_best, hist_best)
+    if return_candidates:
+        out += ({"z": cand_z, "loss": cand_loss, "history": cand_hist, "choice": choice},)
+    return out
+
+
+def morph_blend(z_a: torch.Tensor, z_b: torch.Tensor, n_frames: int) -> torch.Tensor:
+    """(n_frames, latent): frame i is (1 - a) * z_a + a * z_b with a = i / (n_frames - 1), the app's expression
+    (app_vanilla_gan_signatures.py:1696-1697) evaluated frame by frame in fp32 on the endpoints' device.  The endpoints are
+    (1, latent) or (latent,) -- the app draws them as (1, latent, 1, 1), which its own nn.Linear rejects."""
+    if n_frames < 2:
+        raise ValueError(f"n_frames must be >= 2, got {n_frames}")
+    z_a, z_b = z_a.reshape(1, -1).float(), z_b.reshape(1, -1).float()
+    if z_a.shape != z_b.shape:
+        raise ValueError(f"endpoints differ in shape: {tuple(z_a.shape)} vs {tuple(z_b.shape)}")
+    frames = []
+    for i in range(n_frames):
+        a = i / (n_frames - 1)
+        frames.append((1 - a) * z_a + a * z_b)
+    return torch.cat(frames, dim=0)
+
+
+def morph_sequence(generator: Generator, z_a: torch.Tensor, z_b: torch.Tensor, n_frames: int) -> np.ndarray:
+    """(n_frames, S, S) uint8: the frames of the app's "Export Morph Sequence" between two latent endpoints, blended on the
+    device (morph_blend) and generated as bytes by the Generator's last kernel -- one latent vector per forward, as the app
+    generates them, so a frame's bytes are generate_uint8's at that vector whatever the number of frames (the library picks
+    its kernels by batch size); the frames land in one pool on the device and cross to the host together.  Deliberate
+    deviation: a frame's bytes follow this project's rule (tensor_to_uint8: (x + 1) * 127.5, clip, truncate), not the tab's
+    ((x + 1) / 2).clamp(0, 1) * 255."""
+    if generator.training:
+        raise ValueError("morph_sequence needs the Generator in eval() mode")
+    eng = generator._require_engine()
+    z = morph_blend(z_a.to(eng.device), z_b.to(eng.device), n_frames)
+    pool = torch.empty(n_frames, eng.image_size, eng.image_size, dtype=torch.uint8, device=eng.device)
+    for i in range(n_frames):
+        eng.g_generate_u8(z[i:i + 1].contiguous(), out=pool[i:i + 1])
+    return _to_host_u8(pool)
+
+
+def morph_strip(frames, threshold: Optional[int] = None, make_transparent: bool = False):
+    """The frames side by side as one PIL image, laid out as the app does (app_vanilla_gan_signatures.py:1706-1712): an 'L'
+    canvas of 255 -- or with ``make_transparent`` an 'RGBA' canvas of (255, 255, 255, 0) --, every frame converted to the
+    canvas' mode and pasted at x = i * width.  ``frames``: (n, H, W) uint8 or PIL images; with a ``threshold`` each goes
+    through process_images first (the app's apply_threshold), which is also what ``make_transparent`` acts through."""
+    from PIL import Image
+    images = [f if isinstance(f, Image.Image) else Image.fromarray(np.asarray(f, dtype=np.uint8), mode="L") for f in frames]
+    if not images:
+        raise ValueError("morph_strip needs at least one frame")
+    if threshold is not None:
+        images = process_images(images, threshold=threshold, make_transparent=make_transparent)
+    w, h = images[0].width, images[0].height
+    strip = Image.new("RGBA" if make_transparent else "L", (w * len(images), h), (255, 255, 255, 0) if make_transparent else 255)
+    for i, frame in enumerate(images):
+        if frame.mode != strip.mode:
+            frame = frame.convert(strip.mode)
+        strip.paste(frame, (i * w, 0))
+    return strip
