@@ -50,7 +50,8 @@ extern "C" {
 #define SIGGAN_ABI_VERSION 4   /* 2: siggan_stage_real, siggan_augment_batch; 3: siggan_config.dtype, siggan_rng_state, siggan_comm_*;
                                 * 4: siggan_config.g_leaky_slope (appended); siggan_prof_launch (a test hook, added);
                                 *    siggan_g_generate_u8, siggan_image_stats (added: no existing call or struct changes);
-                                *    siggan_d_score_u8, siggan_dequant_table (added likewise); siggan_g_latent_grad (added likewise) */
+                                *    siggan_d_score_u8, siggan_dequant_table (added likewise); siggan_g_latent_grad (added likewise);
+                                *    siggan_g_latent_objective_grad with its struct siggan_latent_objective, added likewise */
 
 enum {
     SIGGAN_OK = 0,
@@ -217,6 +218,42 @@ int siggan_g_generate_u8(siggan_ctx *ctx, const float *z_dev, int32_t batch, uin
  * SIGGAN_E_STATE between siggan_step_begin and its siggan_g_grads (the pipelined forward's activations are still needed). */
 int siggan_g_latent_grad(siggan_ctx *ctx, const float *z_dev, int32_t batch, const uint8_t *target_u8_dev,
                          const float *target_f32_dev, float *dz_dev, float *loss_dev, float *images_dev, void *stream);
+
+/* The gradient with respect to z of a per-image objective: what moves a latent vector towards images the Discriminator
+ * believes (realism-guided refinement), towards a target (projection), and keeps it where the Generator was trained (prior). */
+typedef struct siggan_latent_objective {
+    float recon_weight;    /* w_r >= 0, times mean over pixels of (G(z) - t)^2        (needs a target)            */
+    float realism_weight;  /* w_d >= 0, times -max(log D(G(z)), -100): BCE against 1, per image, D in eval mode  */
+    float prior_weight;    /* w_p >= 0, times 0.5 * mean_k z[b,k]^2                                             */
+} siggan_latent_objective;
+
+/* Modes: Generator AND Discriminator run in eval mode -- Generator BatchNorm is its running-statistics affine, the
+ * Discriminator has no dropout, and with spectral norm the weights are divided by sigma from the stored u, v, which do not move
+ * (siggan_d_forward(training = 0)'s behaviour).  Images do not interact: every output row depends only on its own z row and
+ * target.  The realism term and d(logit) use the G step's own expressions (BCE against 1 with the logarithm clamped at -100,
+ * (p - 1) / max((1 - p) p, 1e-12) times p (1 - p)) with a count of 1 per image, not 1/B; d(logit) is multiplied by
+ * realism_weight once.  A weight of 0 leaves that term's launches out: realism_weight == 0 runs no Discriminator kernel,
+ * recon_weight == 0 reads no target.
+ *   dz_dev (B,latent)      required: d objective[b] / d z[b,:]
+ *   objective_dev (B)      required: w_r*recon + w_d*realism + w_p*prior, in that order
+ *   terms_dev (3,B)        optional: the unweighted recon, realism, prior terms; a term whose weight is 0 is written as 0
+ *   probs_dev (B)          optional: D(G(z)); requires realism_weight > 0
+ *   images_dev (B,1,S,S)   optional, 16-byte aligned
+ * Refused with SIGGAN_E_INVALID, nothing enqueued: a negative or non-finite weight; all three weights 0; recon_weight > 0
+ * without exactly one target; recon_weight == 0 with a target; probs_dev with realism_weight == 0; a target or images_dev
+ * that breaks the alignment rules of siggan_g_latent_grad; a 16-bit context.  SIGGAN_E_STATE between siggan_step_begin and
+ * its siggan_g_grads, as siggan_g_latent_grad.
+ * Bits: with weights (1, 0, 0), dz_dev, objective_dev and images_dev are bit for bit siggan_g_latent_grad's dz, loss and
+ * images; images_dev is bit for bit siggan_g_forward(training = 0); probs_dev is bit for bit what siggan_d_forward(training = 0)
+ * returns for images_dev at the same batch size; byte and fp32 targets holding the same values give the same bits; two calls
+ * on equal inputs give equal bits (fixed-order sums, no atomics).
+ * A fixed sequence of launches on the caller's stream, no host synchronisation.  Training state, RNG, BatchNorm buffers and
+ * u, v are untouched; the context is left as a siggan_g_latent_grad followed by a siggan_d_forward(training = 0) would leave it
+ * (realism_weight == 0: as siggan_g_latent_grad alone), and a train step after it, eager or captured, runs exactly as if it had
+ * not been called. */
+int siggan_g_latent_objective_grad(siggan_ctx *ctx, const float *z_dev, int32_t batch, const uint8_t *target_u8_dev,
+                                   const float *target_f32_dev, const siggan_latent_objective *w, float *dz_dev,
+                                   float *objective_dev, float *terms_dev, float *probs_dev, float *images_dev, void *stream);
 
 /* x_dev (B,1,S,S) -> probs_dev (B) probabilities.  features_dev (B,512*4*4, reference
  * flatten order c,h,w) optional.  training!=0 enables Dropout2d: masks_dev, if given, holds the

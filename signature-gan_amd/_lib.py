@@ -47,6 +47,10 @@ class Hyper(C.Structure):
                 ("label_smoothing", C.c_float), ("clip_max_norm", C.c_float), ("grad_scale", C.c_float)]
 
 
+class LatentObjective(C.Structure):       # siggan_latent_objective
+    _fields_ = [("recon_weight", C.c_float), ("realism_weight", C.c_float), ("prior_weight", C.c_float)]
+
+
 class MlpConfig(C.Structure):       # include/siggan_mlp.h
     _fields_ = [("device", C.c_int32), ("latent_dim", C.c_int32), ("image_size", C.c_int32), ("n_hidden", C.c_int32),
                 ("hidden", C.c_int32 * 4), ("max_batch", C.c_int32), ("leaky_slope", C.c_float), ("seed", C.c_uint64)]
@@ -96,6 +100,7 @@ _SIGNATURES = {
     "siggan_d_score_u8": (C.c_int, [_P, _P, _I32, _I32, _P, _P, _P]),
     "siggan_dequant_table": (C.c_int, [C.POINTER(C.c_float)]),
     "siggan_g_latent_grad": (C.c_int, [_P, _P, _I32, _P, _P, _P, _P, _P, _P]),
+    "siggan_g_latent_objective_grad": (C.c_int, [_P, _P, _I32, _P, _P, C.POINTER(LatentObjective), _P, _P, _P, _P, _P, _P]),
     "siggan_d_step": (C.c_int, [_P, _P, _I32, _P, _P, C.POINTER(Hyper), _P, _P, _P]),
     "siggan_g_step": (C.c_int, [_P, _I32, _P, C.POINTER(Hyper), _P, _P, _P]),
     "siggan_d_grads": (C.c_int, [_P, _P, _I32, _P, _P, C.POINTER(Hyper), _P, _P]),

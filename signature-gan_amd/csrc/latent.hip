@@ -19,13 +19,16 @@ static inline int cdiv(int64_t a, int64_t b) { return (int)((a + b - 1) / b); }
 // loss: 256 threads x 4 pixels = 1024 pixels of ONE image per workgroup (S*S is a multiple of 1024)
 //   d = x - t,  dpre = ((2 / S^2) * d) * (1 - x * x),  part[workgroup] = sum d^2
 // The byte route reads t from the 256-entry table, the fp32 route reads it as given: the same t gives the same bits.
+// MODE (siggan_g_latent_objective_grad): 0 dpre as above; 1 dpre = wr * (the above); 2 dpre = fmaf(wr, the above, dpre) -- the
+// Discriminator's d(pre-tanh) is already there (k_conv1_dgrad_tanh) and the two seeds meet here, each element read and written
+// by its own thread.  wr = 1 in mode 1 would give mode 0's bits (a multiplication by 1 is exact); the host picks mode 0 for it.
 // =========================================================================================
 int recon_loss_parts(int S) { return S * S / 1024; }
 
-template <bool U8>
+template <bool U8, int MODE>
 __global__ __launch_bounds__(256) void k_recon_loss(const float* __restrict__ img, const uint8_t* __restrict__ tu,
                                                     const float* __restrict__ tf, const float* __restrict__ lut,
-                                                    float* __restrict__ dpre, float* __restrict__ part, float c2) {
+                                                    float* __restrict__ dpre, float* __restrict__ part, float c2, float wr) {
     __shared__ float sh[4];
     const size_t i = ((size_t)blockIdx.x * 256 + threadIdx.x) * 4;
     const f4v x = ldg4(img + i);
@@ -37,11 +40,13 @@ __global__ __launch_bounds__(256) void k_recon_loss(const float* __restrict__ im
         t = ldg4(tf + i);
     }
     f4v o;
+    if (MODE == 2) o = ldg4(dpre + i);
     float ss = 0.f;
 #pragma unroll
     for (int e = 0; e < 4; ++e) {
         const float d = x[e] - t[e];
-        o[e] = (c2 * d) * (1.0f - x[e] * x[e]);
+        const float r = (c2 * d) * (1.0f - x[e] * x[e]);
+        o[e] = MODE == 0 ? r : (MODE == 1 ? wr * r : fmaf(wr, r, o[e]));
         ss += d * d;
     }
     *reinterpret_cast<f4v*>(dpre + i) = o;
@@ -53,11 +58,14 @@ __global__ __launch_bounds__(256) void k_recon_loss(const float* __restrict__ im
 }
 
 void launch_recon_loss(const float* img, const uint8_t* t_u8, const float* t_f32, const float* lut, float* dpre, float* part,
-                       int B, int S, hipStream_t s) {
+                       int B, int S, hipStream_t s, float wr, bool onto_dpre) {
     const float c2 = 2.0f / (float)(S * S);              // a power of two (S = 64, 128): exact
     const dim3 grid((unsigned)(B * recon_loss_parts(S)));
-    if (t_u8) hipLaunchKernelGGL((k_recon_loss<true>), grid, dim3(256), 0, s, img, t_u8, t_f32, lut, dpre, part, c2);
-    else hipLaunchKernelGGL((k_recon_loss<false>), grid, dim3(256), 0, s, img, t_u8, t_f32, lut, dpre, part, c2);
+    const int mode = onto_dpre ? 2 : (wr == 1.0f ? 0 : 1);
+#define SIGGAN_RECON(U8, MODE) hipLaunchKernelGGL((k_recon_loss<U8, MODE>), grid, dim3(256), 0, s, img, t_u8, t_f32, lut, dpre, part, c2, wr)
+    if (t_u8) { if (mode == 0) SIGGAN_RECON(true, 0); else if (mode == 1) SIGGAN_RECON(true, 1); else SIGGAN_RECON(true, 2); }
+    else      { if (mode == 0) SIGGAN_RECON(false, 0); else if (mode == 1) SIGGAN_RECON(false, 1); else SIGGAN_RECON(false, 2); }
+#undef SIGGAN_RECON
 }
 
 // =========================================================================================
@@ -65,6 +73,16 @@ void launch_recon_loss(const float* img, const uint8_t* t_u8, const float* t_f32
 // thread per image adds its partials in index order), the rest copy tile t's scale row once per image (a float4 per thread)
 // =========================================================================================
 struct TileLaunch { ScaleTiles t; int prefix[ScaleTiles::MAXT + 1]; };
+
+__device__ __forceinline__ void copy_tile_block(const TileLaunch& tl, int bid, int B) {
+    int t = 0;
+    while (t + 1 < tl.t.nt && bid >= tl.prefix[t + 1]) ++t;
+    const int C4 = tl.t.C[t] / 4;
+    const int64_t i4 = (int64_t)(bid - tl.prefix[t]) * 256 + threadIdx.x;
+    if (i4 >= (int64_t)B * C4) return;
+    const int c4 = (int)(i4 % C4);
+    *reinterpret_cast<f4v*>(tl.t.dst[t] + i4 * 4) = ldg4(tl.t.src[t] + c4 * 4);
+}
 
 __global__ __launch_bounds__(256) void k_loss_fin_tiles(const float* __restrict__ part, int nparts, float* __restrict__ loss, int B,
                                                         float inv_pixels, int nbl, const TileLaunch tl) {
@@ -77,14 +95,7 @@ __global__ __launch_bounds__(256) void k_loss_fin_tiles(const float* __restrict_
         loss[b] = s * inv_pixels;
         return;
     }
-    bid -= nbl;
-    int t = 0;
-    while (t + 1 < tl.t.nt && bid >= tl.prefix[t + 1]) ++t;
-    const int C4 = tl.t.C[t] / 4;
-    const int64_t i4 = (int64_t)(bid - tl.prefix[t]) * 256 + threadIdx.x;
-    if (i4 >= (int64_t)B * C4) return;
-    const int c4 = (int)(i4 % C4);
-    *reinterpret_cast<f4v*>(tl.t.dst[t] + i4 * 4) = ldg4(tl.t.src[t] + c4 * 4);
+    copy_tile_block(tl, bid - nbl, B);
 }
 
 void launch_loss_fin_tiles(const float* part, int nparts, float* loss, int B, int S, const ScaleTiles& t, hipStream_t s) {
@@ -93,6 +104,46 @@ void launch_loss_fin_tiles(const float* part, int nparts, float* loss, int B, in
     const int nbl = cdiv(B, 256);
     hipLaunchKernelGGL(k_loss_fin_tiles, dim3((unsigned)(nbl + tl.prefix[t.nt])), dim3(256), 0, s, part, nparts, loss, B,
                        1.0f / (float)(S * S), nbl, tl);
+}
+
+// =========================================================================================
+// the same launch for siggan_g_latent_objective_grad: workgroups [0, nbl) finish the OBJECTIVE, one wave per image (four images
+// per workgroup), the rest copy the scale rows.  recon: the loss partials in index order, k_loss_fin_tiles' expression (every
+// lane forms the same sum).  prior 0.5 * mean_k z^2: lane j adds z[j]^2, z[j + 64]^2, ... in index order, then the shuffle tree.
+// The realism term was written by k_cls_bwd_eval.  A term whose weight is 0 is not read and counts (and is reported) as 0.
+// =========================================================================================
+__global__ __launch_bounds__(256) void k_obj_fin_tiles(const ObjFin q, int B, int nbl, const TileLaunch tl) {
+    const int bid = blockIdx.x;
+    if (bid >= nbl) { copy_tile_block(tl, bid - nbl, B); return; }
+    const int lane = threadIdx.x & 63, b = bid * 4 + (threadIdx.x >> 6);
+    if (b >= B) return;                                  // (a whole wave: the shuffles below see all 64 lanes)
+    float recon = 0.f, real = 0.f, prior = 0.f, obj = 0.f;
+    if (q.wr > 0.f) {
+        float s = q.part[(size_t)b * q.nparts];
+        for (int j = 1; j < q.nparts; ++j) s += q.part[(size_t)b * q.nparts + j];
+        recon = s * q.inv_pixels;
+        obj += q.wr * recon;
+    }
+    if (q.wd > 0.f) { real = q.realism[b]; obj += q.wd * real; }
+    if (q.wp > 0.f) {
+        float s = 0.f;
+        for (int k = lane; k < q.K; k += 64) { const float v = q.z[(size_t)b * q.K + k]; s = fmaf(v, v, s); }
+#pragma unroll
+        for (int k = 32; k > 0; k >>= 1) s += __shfl_xor(s, k, 64);
+        prior = 0.5f * (s / (float)q.K);
+        obj += q.wp * prior;
+    }
+    if (lane == 0) {
+        q.objective[b] = obj;
+        if (q.terms) { q.terms[b] = recon; q.terms[B + b] = real; q.terms[2 * (size_t)B + b] = prior; }
+    }
+}
+
+void launch_obj_fin_tiles(const ObjFin& q, int B, const ScaleTiles& t, hipStream_t s) {
+    TileLaunch tl; tl.t = t; tl.prefix[0] = 0;
+    for (int i = 0; i < t.nt; ++i) tl.prefix[i + 1] = tl.prefix[i] + cdiv((int64_t)B * (t.C[i] / 4), 256);
+    const int nbl = cdiv(B, 4);
+    hipLaunchKernelGGL(k_obj_fin_tiles, dim3((unsigned)(nbl + tl.prefix[t.nt])), dim3(256), 0, s, q, B, nbl, tl);
 }
 
 // =========================================================================================
@@ -209,16 +260,19 @@ __global__ __launch_bounds__(256) void k_fc_dz(const float* __restrict__ dh, con
     }
 }
 
-__global__ __launch_bounds__(256) void k_fc_dz_sum(const float* __restrict__ part, int nsplit, int64_t n, float* __restrict__ dz) {
+// PRIOR: the prior term's gradient wpl * z[i] (wpl = prior_weight / latent) is added here, behind the ordered sum (part may be dz
+// itself with nsplit 1: every thread reads and writes its own element)
+template <bool PRIOR>
+__global__ __launch_bounds__(256) void k_fc_dz_sum(const float* part, int nsplit, int64_t n, float* dz, const float* __restrict__ zin, float wpl) {
     const int64_t i = (int64_t)blockIdx.x * 256 + threadIdx.x;
     if (i >= n) return;
     float s = part[i];
     for (int z = 1; z < nsplit; ++z) s += part[(size_t)z * n + i];
-    dz[i] = s;
+    dz[i] = PRIOR ? fmaf(wpl, zin[i], s) : s;
 }
 
 void launch_fc_dz(const float* dh, const float* a0, const float* scale0, const float* W, float* dz, float* part, int64_t part_cap,
-                  int B, int K, int C0, float gslope, hipStream_t s) {
+                  int B, int K, int C0, float gslope, hipStream_t s, const float* z, float wpl) {
     const int F = C0 * 16;                               // a multiple of DZ_SUB (C0 = 256, 512)
     const int64_t n = (int64_t)B * K;
     int nsplit = F / DZ_SUB;
@@ -226,7 +280,18 @@ void launch_fc_dz(const float* dh, const float* a0, const float* scale0, const f
     float* const out = nsplit > 1 ? part : dz;
     const dim3 grid((unsigned)nsplit, (unsigned)cdiv(B, DZ_BT));
     SIGGAN_GS_SWITCH(gslope, LK, hipLaunchKernelGGL((k_fc_dz<LK>), grid, dim3(256), 0, s, dh, a0, scale0, W, out, B, K, C0, F, F / nsplit, gslope));
-    if (nsplit > 1) hipLaunchKernelGGL(k_fc_dz_sum, dim3((unsigned)cdiv(n, 256)), dim3(256), 0, s, part, nsplit, n, dz);
+    const dim3 gsum((unsigned)cdiv(n, 256));
+    if (z) hipLaunchKernelGGL((k_fc_dz_sum<true>), gsum, dim3(256), 0, s, out, nsplit, n, dz, z, wpl);
+    else if (nsplit > 1) hipLaunchKernelGGL((k_fc_dz_sum<false>), gsum, dim3(256), 0, s, part, nsplit, n, dz, z, wpl);
+}
+
+// the objective of the prior alone: dz = wpl * z, no chain behind it
+__global__ __launch_bounds__(256) void k_prior_dz(const float* __restrict__ z, float* __restrict__ dz, int64_t n, float wpl) {
+    const int64_t i = (int64_t)blockIdx.x * 256 + threadIdx.x;
+    if (i < n) dz[i] = wpl * z[i];
+}
+void launch_prior_dz(const float* z, float* dz, int64_t n, float wpl, hipStream_t s) {
+    hipLaunchKernelGGL(k_prior_dz, dim3((unsigned)cdiv(n, 256)), dim3(256), 0, s, z, dz, n, wpl);
 }
 
 }  // namespace siggan

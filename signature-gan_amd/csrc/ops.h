@@ -115,12 +115,19 @@ void launch_final_bn_bwd_apply(int dt, const float* dpre, const float* Wt, const
 // is t_u8 (bytes through the 256-entry table lut) or t_f32, exactly one of them.  One partial per 1024 pixels:
 // part[b * (S*S/1024) + j], each a fixed shuffle / LDS tree (recon_loss_parts(S) of them per image).
 int recon_loss_parts(int S);
+// wr / onto_dpre (siggan_g_latent_objective_grad): dpre = wr * (the above), or, onto_dpre, dpre = fmaf(wr, the above, dpre).
 void launch_recon_loss(const float* img, const uint8_t* t_u8, const float* t_f32, const float* lut, float* dpre, float* part,
-                       int B, int S, hipStream_t s);
+                       int B, int S, hipStream_t s, float wr = 1.0f, bool onto_dpre = false);
 // ONE launch for the two small jobs behind it: loss[b] = (part[b][0] + part[b][1] + ...) / S^2 in index order, and the per-image
 // copies tab[b][c] = scale[c] of nt eval-mode BatchNorm scale rows (what EPI_LRELU_BWD multiplies by as its [B][C] table)
 struct ScaleTiles { static constexpr int MAXT = 8; int nt; const float* src[MAXT]; float* dst[MAXT]; int C[MAXT]; };
 void launch_loss_fin_tiles(const float* part, int nparts, float* loss, int B, int S, const ScaleTiles& t, hipStream_t s);
+// the same launch with the objective in the place of the loss: objective[b] = wr * recon + wd * realism + wp * prior (in that
+// order; a weight of 0 leaves its term out and unread) and, optionally, terms[3][B].  recon as above from part, realism[b] as
+// given, prior = 0.5 * mean_k z[b][k]^2 (one wave per image)
+struct ObjFin { const float* part; int nparts; float inv_pixels; const float* realism; const float* z; int K; float wr, wd, wp;
+                float* objective; float* terms; };
+void launch_obj_fin_tiles(const ObjFin& q, int B, const ScaleTiles& t, hipStream_t s);
 // eval-mode input-gradient of the final 3x3 conv through the last block's activation and folded BatchNorm:
 // da[n][y][x][c] = g_dact(a[n][y][x][c]) * scale[c] * sum_{kh,kw} dpre[n][y+1-kh][x+1-kw] * Wt[kh*3+kw][c]   (C == 32)
 void launch_final_dgrad_eval(const float* dpre, const float* Wt, const float* a, const float* scale, float* da, int B, int S,
@@ -129,7 +136,8 @@ void launch_final_dgrad_eval(const float* dpre, const float* Wt, const float* a,
 // (F, K) fc weight).  F is split over workgroups; the partial rows land in `part` (part_cap floats) and are added in split order.
 // Any K >= 1.
 void launch_fc_dz(const float* dh, const float* a0, const float* scale0, const float* W, float* dz, float* part, int64_t part_cap,
-                  int B, int K, int C0, float gslope, hipStream_t s);
+                  int B, int K, int C0, float gslope, hipStream_t s, const float* z = nullptr, float wpl = 0.f);   // z: dz += wpl * z
+void launch_prior_dz(const float* z, float* dz, int64_t n, float wpl, hipStream_t s);       // dz = wpl * z
 
 // ---- Discriminator pieces -----------------------------------------------------------------
 // first block (Cin = 1): x = two segments (x0: n < n0, x1: the rest), out [B][S/2][S/2][C]
@@ -159,6 +167,10 @@ void launch_cls_bwd(int dt, const float* logits, int n0, float y0, float y1, con
                     float slope, void* dv, int B, int C, hipStream_t s, float gscale = 1.0f, float* bce_probs = nullptr,
                     float* bce_dlogit = nullptr, float* bce_metrics = nullptr, int bce_is_g = 0, bool with_bce = false,
                     const float* parts = nullptr, int P = 0, const float* bc = nullptr);
+// the same in eval form, per image (siggan_g_latent_objective_grad; fp32): no dropout table, target 1 with a count of 1,
+// d(logit) times wd;  term[n] = -max(log p[n], -100) and (optional) probs[n] = p[n] are written by one more block
+void launch_cls_bwd_eval(const float* logits, const float* parts, int P, const float* bc, const float* wcp, const float* act, float slope,
+                         float* dv, int B, int C, float wd, float* term, float* probs, hipStream_t s);
 // dWc (torch order c*16+hw) and dbc
 void launch_cls_wgrad(int dt, const float* dlogit, const void* act, float* dWc, float* dbc, int B, int C, hipStream_t s);
 // dst[i] = (float)src[i] for a tensor of element type dt

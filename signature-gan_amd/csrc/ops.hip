@@ -1444,6 +1444,39 @@ void launch_cls_bwd(int dt, const float* logits, int n0, float y0, float y1, con
     SIGGAN_DT_SWITCH(dt, T, hipLaunchKernelGGL(k_cls_bwd<T>, dim3(cdiv(total, 1024) + (with_bce ? 1 : 0)), dim3(256), 0, s, logits, B, n0, y0,
                                                 y1, wcp, (const T*)act, noise, slope, (T*)dv, total, C, gscale, b, with_bce ? 1 : 0));
 }
+// The classifier tail of siggan_g_latent_objective_grad: eval mode (no dropout multiplier), one loss PER IMAGE (target 1, a count
+// of 1 instead of the step's 1 / B), d(logit) times the realism weight wd once.  k_cls_bwd's element layout; the last block
+// writes what is per image -- the term -max(log p, -100) in bce_block's expression with y = 1, and p in k_bce's.
+__global__ __launch_bounds__(256) void k_cls_bwd_eval(const LogitSrc src, const float* __restrict__ wcp, const float* __restrict__ act,
+                                                      float slope, float* __restrict__ dv, int64_t total, int C, float wd, int B,
+                                                      float* __restrict__ term, float* __restrict__ probs) {
+    if (blockIdx.x == gridDim.x - 1) {
+        for (int n = threadIdx.x; n < B; n += 256) {
+            const float x = logit_of(src, n);
+            const float p = 1.0f / (1.0f + expf(-x));
+            const float y = 1.0f;
+            const float lp = fmaxf(logf(p), -100.f), lq = fmaxf(logf(1.0f - p), -100.f);
+            term[n] = -(y * lp + (1.0f - y) * lq);
+            if (probs) probs[n] = p;
+        }
+        return;
+    }
+    const int64_t i = ((int64_t)blockIdx.x * blockDim.x + threadIdx.x) * 4;
+    const int F = 16 * C;
+    if (i >= total) return;
+    const float dl = bce_dlogit(logit_of(src, i / F), 1.0f, 1.0f) * wd;
+    const f32x4 w4 = *reinterpret_cast<const f32x4*>(wcp + (int)(i % F)), a4 = *reinterpret_cast<const f32x4*>(act + i);
+    f32x4 g;
+#pragma unroll
+    for (int e = 0; e < 4; ++e) g[e] = dl * w4[e] * (a4[e] > 0.f ? 1.f : slope);
+    *reinterpret_cast<f32x4*>(dv + i) = g;
+}
+void launch_cls_bwd_eval(const float* logits, const float* parts, int P, const float* bc, const float* wcp, const float* act, float slope,
+                         float* dv, int B, int C, float wd, float* term, float* probs, hipStream_t s) {
+    const int64_t total = (int64_t)B * 16 * C;
+    hipLaunchKernelGGL(k_cls_bwd_eval, dim3(cdiv(total, 1024) + 1), dim3(256), 0, s, LogitSrc{logits, parts, P, bc}, wcp, act, slope, dv,
+                       total, C, wd, B, term, probs);
+}
 // dWc[f] = sum_n dlogit[n] * act[n][f'], dbc = sum_n dlogit[n]: 64 features x 4 row lanes per block (rows n = lane, lane + 4,
 // ...), the four partial sums are added in lane order through LDS
 template <class T>

@@ -1558,6 +1558,105 @@ extern "C" int siggan_g_latent_grad(siggan_ctx* c, const float* z_dev, int32_t b
     return lane_check(c);
 }
 
+// The gradient with respect to z of a per-image objective  wr * recon + wd * realism + wp * prior  through the EVAL-mode
+// Generator and, for the realism term -max(log D(G(z)), -100), the EVAL-mode Discriminator (no dropout; spectral norm: W / sigma
+// from the stored u, v, which do not move -- siggan_d_forward(training = 0)'s own preamble and forward).  The sequence, all on
+// the caller's stream: the Generator forward (Lg + 2 launches);  [wd > 0:  d_forward_rows at rows [0, B) with stored logits
+// (Ld + 1), the per-image classifier tail k_cls_bwd_eval (1), the Discriminator's input-gradient chain -- launch_gconv form 1 on
+// the d_up packs, EPI_LRELU_BWD without a dropout table (Ld - 1) -- and the first block's input-gradient times 1 - x^2 into dpre
+// (1)];  [wr > 0: k_recon_loss (1), which with wd > 0 adds its seed onto dpre as fmaf(wr, ., dpre): no axpy launch];  objective +
+// scale tables (1);  siggan_g_latent_grad's chain from dpre (Lg + 3), the prior's wp * z / latent riding in k_fc_dz_sum.
+// 2 Lg + 6 + [wr > 0] + [wd > 0] (2 Ld + 2) launches plus split-K tails: 15 / 24 / 25 at 64x64 for (1,0,0) / (0,1,0) / all three; the prior alone: Lg + 4, no backward chain.
+// Scratch: siggan_g_latent_grad's list (dpre, g_da, partial, partial_b, lg_tab, the activations g_a) plus the Discriminator's
+// rows [0, B) of d_a and d_dv, logits and dlogit (the realism terms when terms_dev is not given) -- all rewritten by a training
+// phase before it reads them; what a step carries in those rows is dropped exactly as siggan_d_forward drops it (INV_ROWS).
+extern "C" int siggan_g_latent_objective_grad(siggan_ctx* c, const float* z_dev, int32_t batch, const uint8_t* target_u8_dev,
+                                              const float* target_f32_dev, const siggan_latent_objective* w, float* dz_dev,
+                                              float* objective_dev, float* terms_dev, float* probs_dev, float* images_dev,
+                                              void* stream) {
+    ENTER(c);
+    int rc = check_call(c, batch);
+    if (rc) return rc;
+    if (c->dt != DT_F32) return fail(SIGGAN_E_INVALID, "siggan_g_latent_objective_grad needs an fp32 context (16-bit activations are not built for it)");
+    if (!w) return fail(SIGGAN_E_INVALID, "null weights");
+    const float wr = w->recon_weight, wd = w->realism_weight, wp = w->prior_weight;
+    if (!isfinite(wr) || !isfinite(wd) || !isfinite(wp) || wr < 0.f || wd < 0.f || wp < 0.f)
+        return fail(SIGGAN_E_INVALID, "the objective's weights must be finite and >= 0, got (%g, %g, %g)", (double)wr, (double)wd, (double)wp);
+    if (wr == 0.f && wd == 0.f && wp == 0.f) return fail(SIGGAN_E_INVALID, "all three weights of the objective are 0");
+    const int ntargets = (target_u8_dev != nullptr) + (target_f32_dev != nullptr);
+    if (wr > 0.f && ntargets != 1)
+        return fail(SIGGAN_E_INVALID, "recon_weight > 0 needs exactly one of target_u8_dev and target_f32_dev");
+    if (wr == 0.f && ntargets != 0) return fail(SIGGAN_E_INVALID, "a target was given but recon_weight is 0");
+    if (probs_dev && wd == 0.f) return fail(SIGGAN_E_INVALID, "probs_dev needs realism_weight > 0");
+    if (!z_dev || !dz_dev || !objective_dev) return fail(SIGGAN_E_INVALID, "null tensor");
+    if (reinterpret_cast<uintptr_t>(target_u8_dev) & 3) return fail(SIGGAN_E_INVALID, "target_u8_dev must be 4-byte aligned");
+    if ((reinterpret_cast<uintptr_t>(target_f32_dev) | reinterpret_cast<uintptr_t>(images_dev)) & 15)
+        return fail(SIGGAN_E_INVALID, "target_f32_dev and images_dev must be 16-byte aligned");
+    if (c->cs.g_fwd_pending)
+        return fail(SIGGAN_E_STATE, "siggan_step_begin must be followed by siggan_g_grads first: the pipelined forward's activations are in use");
+    hipStream_t s = (hipStream_t)stream;
+    if (wd > 0.f) invalidate(c, INV_ROWS);       // as siggan_d_forward: rows [0, batch) are overwritten
+    if ((rc = settle(c, s))) return rc;
+    Lanes L(c, s);
+    if (wd > 0.f) {                              // siggan_d_forward(training = 0)'s preamble
+        if (c->sn) launch_sn_sigma(c->snt, false, 2, SN_EPS, s);
+        repack(c, L, s, s, c->g_dirty, c->sn || c->d_dirty, 2);
+        c->g_dirty = c->d_dirty = false;
+    } else {                                     // siggan_g_latent_grad's
+        repack(c, L, s, s, c->g_dirty, !c->sn && c->d_dirty);
+        c->g_dirty = false; if (!c->sn) c->d_dirty = false;
+    }
+    const int B = batch, Lg = c->Lg, Ld = c->Ld, S = c->S;
+    const float gs = c->cfg.g_leaky_slope;
+    float* const img = images_dev ? images_dev : c->img;
+    c->cs.ga_last_B = g_forward_pass(c, z_dev, B, false, img, s);
+    float* const realism = terms_dev ? terms_dev + B : c->dlogit;
+    if (wd > 0.f) {
+        c->cs.lP[0] = d_forward_rows(c, img, 0, B, false, s, c->slab_k);            // stored logits: siggan_d_forward's bits
+        launch_cls_bwd_eval(c->logits, nullptr, 0, DP(c, di_cls_b(c)), c->wcp, (const float*)c->d_a[Ld], c->cfg.leaky_slope,
+                            (float*)c->d_dv[Ld], B, c->dC[Ld], wd, realism, probs_dev, s);
+        for (int l = Ld; l >= 2; --l) {
+            const int Ho = S >> l, Hi = 2 * Ho, Co = c->dC[l], Ci = c->dC[l - 1];
+            GConvArgs a = gconv_args(c);
+            a.in = c->d_dv[l]; a.wp = c->d_up[l]; a.out = c->d_dv[l - 1];
+            a.B = B; a.Hi = Ho; a.Wi = Ho; a.Ci = Co; a.Co = Ci;
+            a.lgHr = ilog2i(Ho); a.lgWr = a.lgHr; a.Ho = Hi; a.Wo = Hi; a.form = 1; a.M = B * Ho * Ho;
+            a.epi = EPI_LRELU_BWD; a.aref = c->d_a[l - 1]; a.noise = nullptr; a.slope = c->cfg.leaky_slope;
+            launch_gconv(a, s);
+        }
+        launch_conv1_dgrad_tanh(c->dt, c->d_dv[1], c->d_w1t, img, c->dpre, B, S, c->dC[1], s);
+    }
+    if (wr > 0.f)
+        launch_recon_loss(img, target_u8_dev, target_f32_dev, c->deq_lut, c->dpre, c->partial_b, B, S, s, wr, wd > 0.f);
+    ScaleTiles t; memset(&t, 0, sizeof t);
+    const float* tab[MAXL + 1] = {nullptr};
+    float* next = c->lg_tab;
+    for (int l = 1; l < Lg; ++l) {
+        t.src[t.nt] = c->g_bne[l]; t.dst[t.nt] = next; t.C[t.nt] = c->gC[l]; ++t.nt;
+        tab[l] = next; next += (int64_t)B * c->gC[l];
+    }
+    launch_obj_fin_tiles(ObjFin{c->partial_b, recon_loss_parts(S), 1.0f / (float)(S * S), realism, z_dev, c->latent, wr, wd, wp,
+                                objective_dev, terms_dev}, B, t, s);
+    if (wr > 0.f || wd > 0.f) {
+        launch_final_dgrad_eval(c->dpre, c->wfin_t, (const float*)c->g_a[Lg], c->g_bne[Lg], (float*)c->g_da[Lg], B, S, gs, s);
+        for (int l = Lg; l >= 1; --l) {
+            const int Hi = 4 << (l - 1), Ho = 2 * Hi, Ci = c->gC[l - 1], Co = c->gC[l];
+            GConvArgs a = gconv_args(c);
+            a.in = c->g_da[l]; a.wp = c->g_dn[l]; a.out = c->g_da[l - 1];
+            a.B = B; a.Hi = Ho; a.Wi = Ho; a.Ci = Co; a.Co = Ci;
+            a.lgHr = ilog2i(Hi); a.lgWr = a.lgHr; a.Ho = Hi; a.Wo = Hi; a.form = 0; a.M = B * Hi * Hi; a.epi = EPI_RAW;
+            if (l >= 2) { a.epi = EPI_LRELU_BWD; a.aref = c->g_a[l - 1]; a.noise = tab[l - 1]; a.slope = gs; }
+            launch_gconv(a, s);
+        }
+        launch_fc_dz((const float*)c->g_da[0], (const float*)c->g_a[0], c->g_bne[0], GP(c, gi_fc_w()), dz_dev, c->partial,
+                     PARTIAL_FLOATS - 64, B, c->latent, c->gC[0], gs, s, wp > 0.f ? z_dev : nullptr, wp / (float)c->latent);
+    } else {
+        launch_prior_dz(z_dev, dz_dev, (int64_t)B * c->latent, wp / (float)c->latent, s);   // the prior alone: dz = wp * z / latent
+    }
+    LAUNCHCHK();
+    return lane_check(c);
+}
+
 extern "C" int siggan_d_forward(siggan_ctx* c, const float* x_dev, int32_t batch, int32_t training, const float* masks_dev,
                                 float* probs_dev, float* features_dev, void* stream) {
     ENTER(c);

@@ -1,6 +1,7 @@
 """Host-side context of the HIP engine: owns the torch flat arenas the C ABI borrows and exposes
 the step / forward calls.  PyTorch here is plumbing only (device memory, streams)."""
 import ctypes as C
+import math
 
 import torch
 
@@ -19,6 +20,23 @@ def _f32(t, device, what):
     if t.dtype != torch.float32:
         raise ValueError(f"{what} must be float32, got {t.dtype}")
     return t.contiguous()
+
+
+def check_objective_weights(recon_weight, realism_weight, prior_weight, has_target, want_probs=False):
+    """The refusals of siggan_g_latent_objective_grad that need no device, raised as ValueError before anything is allocated;
+    returns the three weights as floats."""
+    w = (float(recon_weight), float(realism_weight), float(prior_weight))
+    if any(not math.isfinite(x) or x < 0.0 for x in w):
+        raise ValueError(f"the objective's weights must be finite and >= 0, got {w}")
+    if w == (0.0, 0.0, 0.0):
+        raise ValueError("all three weights of the objective are 0")
+    if w[0] > 0.0 and not has_target:
+        raise ValueError("recon_weight > 0 needs a target")
+    if w[0] == 0.0 and has_target:
+        raise ValueError("a target was given but recon_weight is 0")
+    if want_probs and w[1] == 0.0:
+        raise ValueError("want_probs needs realism_weight > 0")
+    return w
 
 
 class Engine:
@@ -341,6 +359,46 @@ class Engine:
         _lib.check(self.lib.siggan_g_latent_grad(self._h, _ptr(z), b, _ptr(t_u8), _ptr(t_f32), _ptr(dz), _ptr(loss), _ptr(img),
                                                  self._stream()))
         return (dz, loss, img) if want_images else (dz, loss)
+
+    def g_latent_objective_grad(self, z, target=None, recon_weight=0.0, realism_weight=1.0, prior_weight=0.0, want_terms=False,
+                                want_probs=False, want_images=False, dz_out=None, objective_out=None):
+        """The gradient with respect to z (B, latent) of the per-image objective recon_weight * mean((G(z) - t)^2) +
+        realism_weight * -max(log D(G(z)), -100) + prior_weight * 0.5 * mean(z^2), both networks in eval mode
+        (siggan_g_latent_objective_grad; fp32 contexts).  ``target`` as g_latent_grad's, given exactly when recon_weight > 0.
+        Returns (dz, objective[, terms][, probs][, images]): dz (B, latent), objective (B,), terms (3, B) the unweighted
+        recon / realism / prior terms (0 where the weight is 0), probs (B,) D(G(z)) (needs realism_weight > 0), images
+        (B, 1, S, S) bit for bit g_forward(z).  ``dz_out`` / ``objective_out``: as g_latent_grad's dz_out / loss_out.  Nothing
+        synchronises with the host."""
+        z = _f32(z, self.device, "z")
+        if z.dim() != 2 or z.shape[1] != self.latent_dim:
+            raise ValueError(f"z must be (B, {self.latent_dim}), got {tuple(z.shape)}")
+        b, s = z.shape[0], self.image_size
+        w = check_objective_weights(recon_weight, realism_weight, prior_weight, target is not None, want_probs)
+        t_u8 = t_f32 = None
+        if target is not None:
+            if target.device != self.device:
+                raise ValueError(f"target must live on {self.device}, got {target.device}")
+            if target.dtype == torch.uint8:
+                shape, t_u8 = (b, s, s), target.contiguous()
+            elif target.dtype == torch.float32:
+                shape, t_f32 = (b, 1, s, s), target.contiguous()
+            else:
+                raise ValueError(f"target must be uint8 (B, S, S) or float32 (B, 1, S, S), got {target.dtype}")
+            if tuple(target.shape) != shape:
+                raise ValueError(f"target must be {shape}, got {tuple(target.shape)}")
+        self._check_batch(b)
+        for t, n, what in ((dz_out, b * self.latent_dim, "dz_out"), (objective_out, b, "objective_out")):
+            if t is not None and (t.device != self.device or t.dtype != torch.float32 or t.numel() != n or not t.is_contiguous()):
+                raise ValueError(f"{what} must be a contiguous float32 tensor of {n} elements on {self.device}")
+        new = lambda *shape: torch.empty(*shape, dtype=torch.float32, device=self.device)
+        dz = new(b, self.latent_dim) if dz_out is None else dz_out
+        obj = new(b) if objective_out is None else objective_out
+        terms = new(3, b) if want_terms else None
+        probs = new(b) if want_probs else None
+        img = new(b, 1, s, s) if want_images else None
+        _lib.check(self.lib.siggan_g_latent_objective_grad(self._h, _ptr(z), b, _ptr(t_u8), _ptr(t_f32), C.byref(_lib.LatentObjective(*w)),
+                                                           _ptr(dz), _ptr(obj), _ptr(terms), _ptr(probs), _ptr(img), self._stream()))
+        return (dz, obj) + tuple(t for t in (terms, probs, img) if t is not None)
 
     @staticmethod
     def image_stats(x, threshold):

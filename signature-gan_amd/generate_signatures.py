@@ -10,7 +10,11 @@ post-processing) also apply to a plain run.  Without the new flags, files and st
 ``--project PATH`` and ``--morph [A B]`` go the other way, from images to latent vectors (utils.inference.project_signatures:
 Adam on z around the library's eval-mode dL/dz), and build the app's second generation tab, "Morphing"
 (app_vanilla_gan_signatures.py:1631-1717), on it: ``--project`` reconstructs every image of a file or directory, ``--morph A B``
-projects two images and writes the strip of frames between them, ``--morph`` alone morphs between two random endpoints."""
+projects two images and writes the strip of frames between them, ``--morph`` alone morphs between two random endpoints.
+
+``--refine_by_realism`` is the filter's counterpart that discards nothing: every latent vector is moved up the Discriminator's
+score for a few Adam steps (utils.inference.generate_signatures_refined) and ``<prefix>_refine.json`` records each image's score
+before and after.  ``--project_realism_weight`` / ``--project_prior_weight`` add the same terms to a projection."""
 import argparse
 import json
 import os
@@ -20,8 +24,9 @@ from typing import Any, Dict, Optional
 import numpy as np
 import torch
 
-from .utils.inference import (generate_signatures_batch, generate_signatures_filtered, load_discriminator, load_generator,
-                              load_target_images, morph_sequence, morph_strip, process_images, project_signatures)
+from .utils.inference import (generate_signatures_batch, generate_signatures_filtered, generate_signatures_refined,
+                              load_discriminator, load_generator, load_target_images, morph_sequence, morph_strip, process_images,
+                              project_signatures)
 
 
 def generate_signatures(generator, n_samples: int, output_dir: str, batch_size: int = 64,
@@ -70,21 +75,58 @@ def generate_filtered(generator, discriminator, n_samples: int, output_dir: str,
         print(f"Realism scores: best {scores[0]:.4f}, worst kept {scores[-1]:.4f}")
 
 
+def generate_refined(generator, discriminator, n_samples: int, output_dir: str, batch_size: int = 64,
+                     device: torch.device = torch.device("cuda"), seed: Optional[int] = None, prefix: str = "signature",
+                     steps: int = 20, lr: float = 0.02, prior_weight: float = 0.0, threshold: Optional[int] = None,
+                     transparent: bool = False, noise_scale: float = 1.0) -> None:
+    """``n_samples`` generated signatures whose latent vectors were refined by the Discriminator's score, written in generation
+    order under the usual names, plus ``<prefix>_refine.json``: [{file, before, after}, ...] in the same order."""
+    os.makedirs(output_dir, exist_ok=True)
+    print(f"Output directory: {output_dir}")
+    print(f"Generating {n_samples} signatures, refining each for {steps} steps by the Discriminator's score...")
+    images, after, before = generate_signatures_refined(generator, discriminator, n_samples, generator.latent_dim, device, seed=seed,
+                                                        batch_size=batch_size, noise_scale=noise_scale, steps=steps, lr=lr,
+                                                        prior_weight=prior_weight, threshold=threshold)
+    if threshold is not None:
+        images = process_images(images, threshold=threshold, make_transparent=transparent)
+    print(f"Saving {len(images)} images...")
+    records = []
+    for i, (img, b, a) in enumerate(zip(images, before, after)):
+        name = f"{prefix}_{i + 1:06d}.png"
+        img.save(os.path.join(output_dir, name), "PNG")
+        records.append({"file": name, "before": b, "after": a})
+    with open(os.path.join(output_dir, f"{prefix}_refine.json"), "w") as f:
+        json.dump(records, f, indent=2)
+    print("\nGeneration complete!")
+    print(f"Generated {len(images)} signatures saved to: {output_dir}")
+    if after:
+        print(f"Realism scores: mean {sum(before) / len(before):.4f} before, {sum(after) / len(after):.4f} after")
+
+
 def run_projection(generator, path: str, output_dir: str, prefix: str = "signature", steps: int = 200, lr: float = 0.05,
-                   restarts: int = 1, seed: Optional[int] = None) -> None:
+                   restarts: int = 1, seed: Optional[int] = None, discriminator=None, realism_weight: float = 0.0,
+                   prior_weight: float = 0.0) -> None:
     """Reconstructions of the image file / the images of the directory ``path``: ``<prefix>_projection_%06d.png`` each, and
-    ``<prefix>_projection.json``: [{file, reconstruction, loss, z}, ...] in the same order."""
+    ``<prefix>_projection.json``: [{file, reconstruction, loss, z}, ...] in the same order; with ``realism_weight`` > 0 every
+    record also holds ``realism``, the Discriminator's score of the reconstruction."""
     from PIL import Image
     os.makedirs(output_dir, exist_ok=True)
     files, targets = load_target_images(path, generator.output_size)
     print(f"Projecting {len(files)} images into the latent space ({steps} steps, {restarts} restart(s))...")
-    z, recon, loss, _ = project_signatures(generator, targets, steps=steps, lr=lr, seed=seed, restarts=restarts)
+    z, recon, loss, _ = project_signatures(generator, targets, steps=steps, lr=lr, seed=seed, restarts=restarts,
+                                           discriminator=discriminator, realism_weight=realism_weight, prior_weight=prior_weight)
+    realism = None
+    if realism_weight > 0:
+        mb = generator._require_engine().max_batch
+        realism = torch.cat([discriminator.score_u8(torch.from_numpy(recon[i:i + mb]).to(z.device)) for i in range(0, len(recon), mb)]).cpu()
     z, loss = z.cpu(), loss.cpu()
     records = []
     for i, name in enumerate(files):
         out = f"{prefix}_projection_{i + 1:06d}.png"
         Image.fromarray(recon[i], mode="L").save(os.path.join(output_dir, out), "PNG")
         records.append({"file": name, "reconstruction": out, "loss": float(loss[i]), "z": [float(v) for v in z[i]]})
+        if realism is not None:
+            records[-1]["realism"] = float(realism[i])
     with open(os.path.join(output_dir, f"{prefix}_projection.json"), "w") as f:
         json.dump(records, f, indent=2)
     print(f"Reconstruction loss (mean squared error in [-1, 1]): best {float(loss.min()):.3e}, worst {float(loss.max()):.3e}")
@@ -134,6 +176,15 @@ def get_checkpoint_info(checkpoint_path: str) -> Dict[str, Any]:
     return info
 
 
+LATER_DEFAULTS = dict(refine_by_realism=False, refine_steps=20, refine_lr=0.02, refine_prior=0.0, project_realism_weight=0.0,
+                      project_prior_weight=0.0)
+
+
+def opt(a: argparse.Namespace, name: str):
+    """A flag of LATER_DEFAULTS: its value on the command line, else its default."""
+    return getattr(a, name, LATER_DEFAULTS[name])
+
+
 def parse_args(argv=None) -> argparse.Namespace:
     p = argparse.ArgumentParser(description="Generate synthetic signatures (MI355X HIP engine)",
                                 formatter_class=argparse.ArgumentDefaultsHelpFormatter)
@@ -161,7 +212,32 @@ def parse_args(argv=None) -> argparse.Namespace:
     p.add_argument("--project_steps", type=int, default=200, help="Adam iterations of a projection")
     p.add_argument("--project_lr", type=float, default=0.05, help="Adam learning rate of a projection")
     p.add_argument("--project_restarts", type=int, default=1, help="Random starts per image (the lowest final loss is kept)")
+    # (the refinement flags appear in the namespace only when given -- LATER_DEFAULTS holds their defaults, opt() reads them --
+    #  so the namespace of a command line without them is what it was before they existed)
+    later = dict(default=argparse.SUPPRESS)
+    p.add_argument("--refine_by_realism", action="store_true", **later,
+                   help="Refine every latent vector by the checkpoint's Discriminator's score (Adam on z) before generating; "
+                        "write <prefix>_refine.json with each image's score before and after")
+    p.add_argument("--refine_steps", type=int, **later, help="Adam iterations of a refinement (default: 20)")
+    p.add_argument("--refine_lr", type=float, **later, help="Adam learning rate of a refinement (default: 0.02)")
+    p.add_argument("--refine_prior", type=float, **later, help="Weight of the prior term 0.5 * mean(z^2) of a refinement (default: 0)")
+    p.add_argument("--project_realism_weight", type=float, **later,
+                   help="With --project: weight of -log D(G(z)) beside the pixel error; needs the checkpoint's Discriminator (default: 0)")
+    p.add_argument("--project_prior_weight", type=float, **later,
+                   help="With --project: weight of the prior term 0.5 * mean(z^2) (default: 0)")
     a = p.parse_args(argv)
+    if opt(a, "refine_by_realism"):
+        for flag in ("filter_by_realism", "project", "morph"):
+            if getattr(a, flag) not in (None, False):
+                p.error(f"--refine_by_realism and --{flag} are mutually exclusive")
+    elif any(hasattr(a, k) for k in ("refine_steps", "refine_lr", "refine_prior")):
+        p.error("--refine_steps, --refine_lr and --refine_prior need --refine_by_realism")
+    if opt(a, "refine_steps") < 1 or not opt(a, "refine_lr") > 0 or not opt(a, "refine_prior") >= 0:
+        p.error("--refine_steps must be >= 1, --refine_lr > 0, --refine_prior >= 0")
+    if not opt(a, "project_realism_weight") >= 0 or not opt(a, "project_prior_weight") >= 0:
+        p.error("--project_realism_weight and --project_prior_weight must be >= 0")
+    if a.project is None and (hasattr(a, "project_realism_weight") or hasattr(a, "project_prior_weight")):
+        p.error("--project_realism_weight and --project_prior_weight need --project")
     if a.morph is not None and len(a.morph) not in (0, 2):
         p.error("--morph takes no image files (random endpoints) or exactly two")
     if a.morph_frames < 2:
@@ -189,18 +265,30 @@ def main(argv=None) -> None:
             print(f"  {k}: {v}")
         return
     generator, _ = load_generator(a.checkpoint, device)
+
+    def need_discriminator(flag):
+        discriminator = load_discriminator(a.checkpoint, device, image_size=generator.output_size)
+        if discriminator is None:
+            sys.exit(f"error: {a.checkpoint} holds no discriminator_state_dict: {flag} needs the Discriminator's "
+                     "weights (a full training checkpoint, not a generator-only export)")
+        return discriminator
+
     if a.project is not None or a.morph is not None:
         if a.project is not None:
-            run_projection(generator, a.project, a.output_dir, a.prefix, a.project_steps, a.project_lr, a.project_restarts, a.seed)
+            w_d, w_p = opt(a, "project_realism_weight"), opt(a, "project_prior_weight")
+            discriminator = need_discriminator("--project_realism_weight") if w_d > 0 else None
+            run_projection(generator, a.project, a.output_dir, a.prefix, a.project_steps, a.project_lr, a.project_restarts, a.seed,
+                           discriminator, w_d, w_p)
         if a.morph is not None:
             run_morph(generator, a.morph, a.output_dir, device, a.prefix, a.morph_frames, a.seed, a.threshold, a.transparent,
                       a.project_steps, a.project_lr, a.project_restarts)
         return
-    if a.filter_by_realism:
-        discriminator = load_discriminator(a.checkpoint, device, image_size=generator.output_size)
-        if discriminator is None:
-            sys.exit(f"error: {a.checkpoint} holds no discriminator_state_dict: --filter_by_realism needs the Discriminator's "
-                     "weights (a full training checkpoint, not a generator-only export)")
+    if opt(a, "refine_by_realism"):
+        generate_refined(generator, need_discriminator("--refine_by_realism"), a.n_samples, a.output_dir, a.batch_size, device, a.seed,
+                         a.prefix, opt(a, "refine_steps"), opt(a, "refine_lr"), opt(a, "refine_prior"), a.threshold, a.transparent,
+                         a.noise_scale)
+    elif a.filter_by_realism:
+        discriminator = need_discriminator("--filter_by_realism")
         generate_filtered(generator, discriminator, a.n_samples, a.output_dir, a.batch_size, device, a.seed, a.prefix,
                           a.oversampling_ratio, a.threshold, a.transparent, a.noise_scale)
     else:

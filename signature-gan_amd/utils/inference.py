@@ -12,7 +12,12 @@ it is where a trained Discriminator is used after training) lives here too: ``lo
 
 So does the way back from an image to a latent vector: ``project_signatures`` (an Adam loop on z around
 Engine.g_latent_grad), and on top of it the app's second generation tab, "Morphing" (app_vanilla_gan_signatures.py:1631-1717):
-``morph_blend``, ``morph_sequence`` and ``morph_strip``."""
+``morph_blend``, ``morph_sequence`` and ``morph_strip``.
+
+Realism-guided refinement joins the two: ``refine_latents`` moves latent vectors up the Discriminator's eval-mode score (an
+Adam loop on z around Engine.g_latent_objective_grad) instead of throwing low-scoring images away,
+``generate_signatures_refined`` is generation on top of it, and ``project_signatures`` takes the same realism and prior terms
+beside its pixel error.  ``adopt_discriminator`` brings the Discriminator into the Generator's context for them."""
 from typing import Any, Dict, List, Optional, Tuple
 
 import numpy as np
@@ -312,9 +317,133 @@ def projection_starts(n_targets: int, latent_dim: int, restart: int, z0: Optiona
     return torch.randn(n_targets, latent_dim, generator=gen)
 
 
+def discriminator_adoption(generator: Generator, discriminator: Discriminator) -> str:
+    """How ``discriminator`` comes into the Generator's context: 'shared' -- both modules already run on one engine, nothing is
+    copied -- or 'copy' -- the Generator's engine is its own and the Discriminator is the plain (no spectral norm) module of
+    the same image size: its parameters are copied into that engine's Discriminator arena.  Anything else raises ValueError.
+    Both modules must be in eval() mode.  Pure host code (it reads module attributes only)."""
+    if generator.training or discriminator.training:
+        raise ValueError("the latent objective runs both networks in eval mode: call .eval() on the Generator and the Discriminator")
+    if generator._engine is not None and generator._engine is discriminator._engine:
+        return "shared"
+    if not generator._shared_engine and not discriminator.use_spectral_norm and discriminator.input_size == generator.output_size:
+        return "copy"
+    raise ValueError("the Discriminator cannot be copied into the Generator's context (a spectral-norm Discriminator, another "
+                     "image size, or a Generator on a shared engine): build both modules on one engine -- pass it as the "
+                     "`_engine` constructor argument of Generator and Discriminator, as VanillaGAN does")
+
+
+def adopt_discriminator(generator: Generator, discriminator: Discriminator):
+    """The engine that holds both networks (discriminator_adoption): the shared one, or the Generator's own after the
+    Discriminator's parameters were copied into its views('d') and params_changed() was called.  Call once per public call."""
+    how = discriminator_adoption(generator, discriminator)
+    eng = generator._require_engine()
+    if how == "copy":
+        if eng.spectral_norm or abs(eng.leaky_slope - discriminator.leaky_slope) > 1e-12:
+            raise ValueError("the Generator's engine was created with another spectral_norm / leaky_slope setting than the "
+                             "Discriminator: build both modules on one engine (the `_engine` constructor argument)")
+        views = eng.views("d")
+        with torch.no_grad():
+            for name, p in discriminator.named_parameters():
+                views[name].copy_(p.detach().to(eng.device))
+        eng.params_changed()
+    return eng
+
+
+def refine_plan(n: int, max_batch: int) -> List[Tuple[int, int]]:
+    """[(first vector, count), ...]: the chunks of ``max_batch`` a refinement of ``n`` latent vectors runs in.  Pure host code."""
+    if n < 0 or max_batch < 1:
+        raise ValueError(f"need n >= 0 and max_batch >= 1, got {n}, {max_batch}")
+    return [(t0, min(max_batch, n - t0)) for t0 in range(0, n, max_batch)]
+
+
+def _check_refine(steps, lr, realism_weight, prior_weight):
+    from ..engine import check_objective_weights
+    if steps < 1 or not lr > 0:
+        raise ValueError(f"steps must be >= 1 and lr > 0, got {steps}, {lr}")
+    check_objective_weights(0.0, realism_weight, prior_weight, False)
+    if not realism_weight > 0:
+        raise ValueError("refinement follows the Discriminator's score: realism_weight must be > 0")
+
+
+def _refine(eng, generator, z0, steps, lr, betas, realism_weight, prior_weight):
+    dev, latent = eng.device, eng.latent_dim
+    z0 = torch.as_tensor(z0, dtype=torch.float32)
+    if z0.dim() != 2 or z0.shape[1] != latent:
+        raise ValueError(f"z0 must be (N, {latent}), got {tuple(z0.shape)}")
+    n = z0.shape[0]
+    z_all = z0.to(dev).contiguous().clone()
+    before, after = (torch.empty(n, dtype=torch.float32, device=dev) for _ in range(2))
+    hist = torch.empty(steps, n, dtype=torch.float32, device=dev)
+    w = dict(realism_weight=realism_weight, prior_weight=prior_weight)
+    for t0, b in refine_plan(n, eng.max_batch):
+        z = z_all[t0:t0 + b]                                   # (a contiguous view: Adam updates the returned tensor in place)
+        m, v = torch.zeros_like(z), torch.zeros_like(z)
+        dz = torch.empty_like(z)
+        h = torch.empty(steps, b, dtype=torch.float32, device=dev)
+        for k in range(steps):
+            out = eng.g_latent_objective_grad(z, want_probs=k == 0, dz_out=dz, objective_out=h[k], **w)
+            if k == 0:
+                before[t0:t0 + b] = out[2]
+            eng.op_adam(z, dz, m, v, k + 1, lr=lr, beta1=betas[0], beta2=betas[1])
+        after[t0:t0 + b] = eng.g_latent_objective_grad(z, want_probs=True, dz_out=dz, **w)[2]      # the score AT the returned z
+        hist[:, t0:t0 + b] = h
+    size = eng.image_size
+    u8 = np.empty((n, size, size), dtype=np.uint8)
+    for t0, b in refine_plan(n, eng.max_batch):
+        u8[t0:t0 + b] = generate_uint8(generator, z_all[t0:t0 + b])
+    return z_all, u8, before, after, hist
+
+
+def refine_latents(generator: Generator, discriminator: Discriminator, z0: torch.Tensor, steps: int = 20, lr: float = 0.02,
+                   betas: Tuple[float, float] = (0.9, 0.999), realism_weight: float = 1.0, prior_weight: float = 0.0):
+    """Move the latent vectors ``z0`` (N, latent) towards images the Discriminator believes: ``steps`` iterations of Adam on z
+    against the per-image objective realism_weight * -log D(G(z)) + prior_weight * 0.5 * mean(z^2), both networks in eval
+    mode, every iteration one Engine.g_latent_objective_grad and one Engine.op_adam on (z, dz, m, v), in chunks of the
+    engine's max_batch (refine_plan), all enqueued without a host synchronisation.  The Discriminator comes into the
+    Generator's context by adopt_discriminator.
+
+    Returns (z (N, latent) fp32 device tensor, images (N, S, S) uint8 numpy -- generate_uint8 at z --, probs_before (N,)
+    device tensor: D(G(z0)), probs_after (N,): D(G(z)) at the returned z, history (steps, N) device tensor: the objective at
+    the start of every iteration)."""
+    _check_refine(steps, lr, realism_weight, prior_weight)
+    eng = adopt_discriminator(generator, discriminator)
+    return _refine(eng, generator, z0, steps, lr, betas, realism_weight, prior_weight)
+
+
+def generate_signatures_refined(generator: Generator, discriminator: Discriminator, n_signatures: int, latent_dim: int,
+                                device: torch.device, seed: Optional[int] = None, batch_size: int = 32, noise_scale: float = 1.0,
+                                steps: int = 20, lr: float = 0.02, prior_weight: float = 0.0, threshold: Optional[int] = None
+                                ) -> Tuple[List[Any], List[float], List[float]]:
+    """Generation with every latent vector refined by the Discriminator's score instead of oversampling and discarding:
+    batch by batch (filter_plan with ratio 1.0: the same batches and seeds as generate_signatures_filtered draws first),
+    z = randn * noise_scale, then refine_latents' loop.  Returns (PIL 'L' images in generation order -- binarised when
+    ``threshold`` is given --, probs_after, probs_before): the scores D(G(z)) of the fp32 images after and before."""
+    from PIL import Image
+    _check_refine(steps, lr, 1.0, prior_weight)
+    if threshold is not None and not 0 <= int(threshold) <= 255:
+        raise ValueError(f"threshold must be a byte value, got {threshold}")
+    _, plan = filter_plan(n_signatures, 1.0, batch_size, seed)
+    if not plan:
+        return [], [], []
+    eng = adopt_discriminator(generator, discriminator)
+    images, before, after = [], [], []
+    for b, batch_seed in plan:
+        _seed_batch(batch_seed)
+        z = torch.randn(b, latent_dim, device=device) * noise_scale
+        _, u8, p0, p1, _ = _refine(eng, generator, z, steps, lr, (0.9, 0.999), 1.0, prior_weight)
+        if threshold is not None:
+            u8 = binarize_uint8(u8, threshold)
+        images += [Image.fromarray(arr, mode="L") for arr in u8]
+        before.append(p0); after.append(p1)
+    host = lambda ts: [float(x) for x in torch.cat(ts).cpu()]
+    return images, host(after), host(before)
+
+
 def project_signatures(generator: Generator, targets_u8, steps: int = 200, lr: float = 0.05,
                        betas: Tuple[float, float] = (0.9, 0.999), z0: Optional[torch.Tensor] = None, seed: Optional[int] = None,
-                       restarts: int = 1, return_candidates: bool = False):
+                       restarts: int = 1, return_candidates: bool = False, discriminator: Optional[Discriminator] = None,
+                       realism_weight: float = 0.0, prior_weight: float = 0.0):
     """Latent vectors whose images reproduce ``targets_u8`` ((N, S, S) uint8, numpy or tensor; a byte stands for
     byte / 127.5 - 1.0): ``steps`` iterations of Adam on z against the per-image loss mean((G(z) - t)^2), every iteration one
     Engine.g_latent_grad (eval forward + eval backward in HIP) and one Engine.op_adam on (z, dz, m, v), all enqueued without
@@ -323,13 +452,30 @@ def project_signatures(generator: Generator, targets_u8, steps: int = 200, lr: f
     Returns (z (N, latent) fp32 device tensor, recon (N, S, S) uint8 numpy -- generate_uint8 at z --, loss (N,) device tensor:
     the loss AT the returned z, history (steps, N) device tensor: the loss at the start of every iteration).  With
     ``restarts`` > 1 each target keeps the start whose final loss is lowest (the first of equals); ``return_candidates`` adds
-    a dict with every candidate's ``z`` (R, N, latent), ``loss`` (R, N) and ``history`` (R, steps, N), and the kept ``choice``."""
+    a dict with every candidate's ``z`` (R, N, latent), ``loss`` (R, N) and ``history`` (R, steps, N), and the kept ``choice``.
+
+    ``realism_weight`` / ``prior_weight`` > 0 add realism_weight * -log D(G(z)) (needs ``discriminator``, brought in by
+    adopt_discriminator) and prior_weight * 0.5 * mean(z^2) to the pixel error: every iteration is then one
+    Engine.g_latent_objective_grad with recon_weight = 1, and loss / history hold that objective.  With the defaults the
+    calls are exactly the ones above."""
     if generator.training:
         raise ValueError("project_signatures needs the Generator in eval() mode (running BatchNorm statistics)")
     if steps < 1 or restarts < 1:
         raise ValueError(f"steps and restarts must be >= 1, got {steps}, {restarts}")
-    eng = generator._require_engine()
+    from ..engine import check_objective_weights
+    check_objective_weights(1.0, realism_weight, prior_weight, True)
+    if realism_weight > 0 and discriminator is None:
+        raise ValueError("realism_weight > 0 needs the Discriminator")
+    guided = realism_weight > 0 or prior_weight > 0
+    eng = adopt_discriminator(generator, discriminator) if realism_weight > 0 else generator._require_engine()
     dev, latent, size = eng.device, eng.latent_dim, eng.image_size
+
+    def grad(z, t, dz, out):
+        if guided:
+            eng.g_latent_objective_grad(z, t, 1.0, realism_weight, prior_weight, dz_out=dz, objective_out=out)
+        else:
+            eng.g_latent_grad(z, t, dz_out=dz, loss_out=out)
+
     t_all = torch.as_tensor(np.ascontiguousarray(targets_u8) if isinstance(targets_u8, np.ndarray) else targets_u8)
     if t_all.dtype != torch.uint8 or t_all.dim() != 3 or tuple(t_all.shape[1:]) != (size, size):
         raise ValueError(f"targets_u8 must be uint8 (N, {size}, {size}), got {t_all.dtype} {tuple(t_all.shape)}")
@@ -348,9 +494,9 @@ def project_signatures(generator: Generator, targets_u8, steps: int = 200, lr: f
         dz = torch.empty_like(z)
         hist = torch.empty(steps, b, dtype=torch.float32, device=dev)
         for k in range(steps):
-            eng.g_latent_grad(z, t, dz_out=dz, loss_out=hist[k])
+            grad(z, t, dz, hist[k])
             eng.op_adam(z, dz, m, v, k + 1, lr=lr, beta1=betas[0], beta2=betas[1])
-        eng.g_latent_grad(z, t, dz_out=dz, loss_out=cand_loss[r, t0:t0 + b])       # the loss at the z that is returned
+        grad(z, t, dz, cand_loss[r, t0:t0 + b])                                    # the loss at the z that is returned
         cand_z[r, t0:t0 + b] = z
         cand_hist[r, :, t0:t0 + b] = hist
     choice = torch.argmin(cand_loss, dim=0)                                        # (plumbing: the first of equal minima)
