@@ -243,8 +243,8 @@ typedef struct siggan_latent_objective {
  * without exactly one target; recon_weight == 0 with a target; probs_dev with realism_weight == 0; a target or images_dev
  * that breaks the alignment rules of siggan_g_latent_grad; a 16-bit context.  SIGGAN_E_STATE between siggan_step_begin and
  * its siggan_g_grads, as siggan_g_latent_grad.
- * Bits: with weights (1, 0, 0), dz_dev, objective_dev and images_dev are bit for bit siggan_g_latent_grad's dz, loss and
- * images; images_dev is bit for bit siggan_g_forward(training = 0); probs_dev is bit for bit what siggan_d_forward(training = 0)
+ * Bits: siggan_g_latent_grad IS this call with the weights (1, 0, 0) -- one device sequence, its loss_dev in objective_dev's
+ * place, no terms and no probs -- so the two give the same dz, loss and images; images_dev is bit for bit siggan_g_forward(training = 0); probs_dev is bit for bit what siggan_d_forward(training = 0)
  * returns for images_dev at the same batch size; byte and fp32 targets holding the same values give the same bits; two calls
  * on equal inputs give equal bits (fixed-order sums, no atomics).
  * A fixed sequence of launches on the caller's stream, no host synchronisation.  Training state, RNG, BatchNorm buffers and

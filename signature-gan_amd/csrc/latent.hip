@@ -1,6 +1,7 @@
-// latent.hip -- the kernels of siggan_g_latent_grad that the training step does not already have (gfx950, fp32 tensors):
-// the per-image reconstruction loss with d(pre-tanh), the final conv's input-gradient in eval form, the per-image scale
-// tables the implicit-GEMM epilogue EPI_LRELU_BWD multiplies by, and the fc layer's input-gradient dz = dh . W.
+// latent.hip -- the kernels of siggan_g_latent_objective_grad (and siggan_g_latent_grad, its reconstruction-only case) that the
+// training step does not already have (gfx950, fp32 tensors): the per-image reconstruction loss with d(pre-tanh), the objective
+// with the per-image scale tables the implicit-GEMM epilogue EPI_LRELU_BWD multiplies by, the final conv's input-gradient in
+// eval form, and the fc layer's input-gradient dz = dh . W.
 //
 // Every sum has a fixed order (shuffle tree inside a wave, index order across waves, workgroups and splits) and nothing is
 // accumulated with atomics: equal inputs give equal bits.
@@ -69,8 +70,11 @@ void launch_recon_loss(const float* img, const uint8_t* t_u8, const float* t_f32
 }
 
 // =========================================================================================
-// the ordered sum of the loss partials and the per-image scale tables, one launch: workgroups [0, nbl) finish the loss (one
-// thread per image adds its partials in index order), the rest copy tile t's scale row once per image (a float4 per thread)
+// the objective and the per-image scale tables, one launch: workgroups [0, nbl) finish the OBJECTIVE, one wave per image (four
+// images per workgroup), the rest copy tile t's scale row once per image (a float4 per thread).  recon: the loss partials in
+// index order, times 1 / S^2 (every lane forms the same sum).  prior 0.5 * mean_k z^2: lane j adds z[j]^2, z[j + 64]^2, ... in
+// index order, then the shuffle tree.  The realism term was written by k_cls_bwd_eval.  A term whose weight is 0 is not read and
+// counts (and is reported) as 0; with the weights (1, 0, 0) the objective is the recon term's bits (0 + 1 * recon).
 // =========================================================================================
 struct TileLaunch { ScaleTiles t; int prefix[ScaleTiles::MAXT + 1]; };
 
@@ -84,34 +88,6 @@ __device__ __forceinline__ void copy_tile_block(const TileLaunch& tl, int bid, i
     *reinterpret_cast<f4v*>(tl.t.dst[t] + i4 * 4) = ldg4(tl.t.src[t] + c4 * 4);
 }
 
-__global__ __launch_bounds__(256) void k_loss_fin_tiles(const float* __restrict__ part, int nparts, float* __restrict__ loss, int B,
-                                                        float inv_pixels, int nbl, const TileLaunch tl) {
-    int bid = blockIdx.x;
-    if (bid < nbl) {
-        const int b = bid * 256 + threadIdx.x;
-        if (b >= B) return;
-        float s = part[(size_t)b * nparts];
-        for (int j = 1; j < nparts; ++j) s += part[(size_t)b * nparts + j];
-        loss[b] = s * inv_pixels;
-        return;
-    }
-    copy_tile_block(tl, bid - nbl, B);
-}
-
-void launch_loss_fin_tiles(const float* part, int nparts, float* loss, int B, int S, const ScaleTiles& t, hipStream_t s) {
-    TileLaunch tl; tl.t = t; tl.prefix[0] = 0;
-    for (int i = 0; i < t.nt; ++i) tl.prefix[i + 1] = tl.prefix[i] + cdiv((int64_t)B * (t.C[i] / 4), 256);
-    const int nbl = cdiv(B, 256);
-    hipLaunchKernelGGL(k_loss_fin_tiles, dim3((unsigned)(nbl + tl.prefix[t.nt])), dim3(256), 0, s, part, nparts, loss, B,
-                       1.0f / (float)(S * S), nbl, tl);
-}
-
-// =========================================================================================
-// the same launch for siggan_g_latent_objective_grad: workgroups [0, nbl) finish the OBJECTIVE, one wave per image (four images
-// per workgroup), the rest copy the scale rows.  recon: the loss partials in index order, k_loss_fin_tiles' expression (every
-// lane forms the same sum).  prior 0.5 * mean_k z^2: lane j adds z[j]^2, z[j + 64]^2, ... in index order, then the shuffle tree.
-// The realism term was written by k_cls_bwd_eval.  A term whose weight is 0 is not read and counts (and is reported) as 0.
-// =========================================================================================
 __global__ __launch_bounds__(256) void k_obj_fin_tiles(const ObjFin q, int B, int nbl, const TileLaunch tl) {
     const int bid = blockIdx.x;
     if (bid >= nbl) { copy_tile_block(tl, bid - nbl, B); return; }

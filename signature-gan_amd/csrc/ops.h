@@ -118,13 +118,11 @@ int recon_loss_parts(int S);
 // wr / onto_dpre (siggan_g_latent_objective_grad): dpre = wr * (the above), or, onto_dpre, dpre = fmaf(wr, the above, dpre).
 void launch_recon_loss(const float* img, const uint8_t* t_u8, const float* t_f32, const float* lut, float* dpre, float* part,
                        int B, int S, hipStream_t s, float wr = 1.0f, bool onto_dpre = false);
-// ONE launch for the two small jobs behind it: loss[b] = (part[b][0] + part[b][1] + ...) / S^2 in index order, and the per-image
-// copies tab[b][c] = scale[c] of nt eval-mode BatchNorm scale rows (what EPI_LRELU_BWD multiplies by as its [B][C] table)
+// ONE launch for the two small jobs behind it: the per-image copies tab[b][c] = scale[c] of nt eval-mode BatchNorm scale rows
+// (what EPI_LRELU_BWD multiplies by as its [B][C] table), and objective[b] = wr * recon + wd * realism + wp * prior (in that
+// order; a weight of 0 leaves its term out and unread) with, optionally, terms[3][B].  recon = (part[b][0] + part[b][1] + ...)
+// * inv_pixels in index order, realism[b] as given, prior = 0.5 * mean_k z[b][k]^2 (one wave per image)
 struct ScaleTiles { static constexpr int MAXT = 8; int nt; const float* src[MAXT]; float* dst[MAXT]; int C[MAXT]; };
-void launch_loss_fin_tiles(const float* part, int nparts, float* loss, int B, int S, const ScaleTiles& t, hipStream_t s);
-// the same launch with the objective in the place of the loss: objective[b] = wr * recon + wd * realism + wp * prior (in that
-// order; a weight of 0 leaves its term out and unread) and, optionally, terms[3][B].  recon as above from part, realism[b] as
-// given, prior = 0.5 * mean_k z[b][k]^2 (one wave per image)
 struct ObjFin { const float* part; int nparts; float inv_pixels; const float* realism; const float* z; int K; float wr, wd, wp;
                 float* objective; float* terms; };
 void launch_obj_fin_tiles(const ObjFin& q, int B, const ScaleTiles& t, hipStream_t s);

@@ -822,11 +822,32 @@ static bool ap_table_d(const siggan_ctx* c, ApTable& t, int nride) {
     return !t.overflow;
 }
 
-static GConvArgs gconv_args(const siggan_ctx* c) {
+// The ONE place the geometry of a 4x4 stride-2 implicit GEMM is derived.  form 0 ("down", a stride-2 convolution or the input-
+// gradient of a transposed one): h_in -> h_in / 2; form 1 ("up", a transposed convolution or the input-gradient of a stride-2
+// one): h_in -> 2 h_in.  A GEMM row is a pixel of the SMALL side in both forms.  The caller sets in / wp / out, the epilogue
+// fields, and slab where it runs beside another GEMM.
+static GConvArgs gconv_args(const siggan_ctx* c, int form, int B, int h_in, int c_in, int c_out) {
     GConvArgs a; memset(&a, 0, sizeof a);
     a.dt = c->dt; a.gslope = c->cfg.g_leaky_slope;
     a.slab = c->slab_k; a.slab_floats = c->slab_k_floats; a.zeros = c->zeros;
+    const int h_small = form == 0 ? h_in / 2 : h_in;
+    a.form = form; a.B = B; a.Hi = a.Wi = h_in; a.Ci = c_in; a.Co = c_out;
+    a.Ho = a.Wo = form == 0 ? h_in / 2 : 2 * h_in;
+    a.lgHr = a.lgWr = ilog2i(h_small); a.M = B * h_small * h_small;
     return a;
+}
+// ... and of its weight gradient: small [B][h_small]^2[c_small] x large [B][2 h_small]^2[c_large] -> dw, split over the pixels
+// into as many slabs as `slab` (slab_floats, every weight-gradient slab region has that size) holds.  db stays the caller's.
+struct WgradCall { WgradArgs w; int max_splits; };
+static WgradCall wgrad_args(const siggan_ctx* c, const void* small, const void* large, float* dw, float* slab, int B, int h_small,
+                            int c_small, int c_large) {
+    WgradCall g; memset(&g, 0, sizeof g);
+    WgradArgs& w = g.w;
+    w.zeros = c->zeros; w.dt = c->dt;
+    w.S = small; w.L = large; w.slab = slab; w.dw = dw; w.B = B; w.Cs = c_small; w.Cl = c_large;
+    w.lgHs = w.lgWs = ilog2i(h_small); w.lgCl = ilog2i(c_large); w.K = B * h_small * h_small;
+    g.max_splits = (int)(c->slab_floats / ((int64_t)c_small * (16 * c_large + 1)));
+    return g;
 }
 
 // Generator.forward (generator_vanilla_gan.py:189-209).  training: BN batch stats (+ running
@@ -855,12 +876,10 @@ static int g_forward_pass(const siggan_ctx* c, const float* z, int B, bool train
         launch_bn_relu(c->dt, c->fc_y, A[0], B, c->F, c->g_bn[0], gs, s);
     }
     for (int l = 1; l <= c->Lg; ++l) {
-        const int Hi = 4 << (l - 1), Ci = c->gC[l - 1], Co = c->gC[l];
-        GConvArgs a = gconv_args(c);
+        const int Hi = 4 << (l - 1), C = c->gC[l];
+        GConvArgs a = gconv_args(c, 1, B, Hi, c->gC[l - 1], C);
         if (slab_k) a.slab = slab_k;
-        a.in = A[l - 1]; a.wp = c->g_up[l]; a.B = B; a.Hi = Hi; a.Wi = Hi; a.Ci = Ci; a.Co = Co;
-        a.lgHr = ilog2i(Hi); a.lgWr = a.lgHr; a.Ho = 2 * Hi; a.Wo = 2 * Hi; a.form = 1; a.M = B * Hi * Hi;
-        const int C = Co;
+        a.in = A[l - 1]; a.wp = c->g_up[l];
         const int64_t off = c->g_bn_off[l];
         if (training) {
             a.out = c->g_y[l]; a.epi = EPI_RAW;
@@ -901,12 +920,9 @@ static int d_forward_rows(const siggan_ctx* c, const float* x, int r0, int nB, b
     else if (!conv1_done)     // (done: it rode in the launch that re-packed D's weights, see repack)
         launch_conv1_fwd(c->dt, x, nB, x, c->sn ? c->d_w1s : DP(c, di_w(1)), DP(c, di_b(1)), nz(1), slope, act(1), nB, c->S, c->dC[1], s);
     for (int l = 2; l <= c->Ld; ++l) {
-        const int Hi = c->S >> (l - 1), Ho = Hi / 2;
-        GConvArgs a = gconv_args(c);
+        GConvArgs a = gconv_args(c, 0, nB, c->S >> (l - 1), c->dC[l - 1], c->dC[l]);
         a.slab = slab_k;
         a.in = act(l - 1); a.wp = c->d_dn[l]; a.out = act(l);
-        a.B = nB; a.Hi = Hi; a.Wi = Hi; a.Ci = c->dC[l - 1]; a.Co = c->dC[l];
-        a.lgHr = ilog2i(Ho); a.lgWr = a.lgHr; a.Ho = Ho; a.Wo = Ho; a.form = 0; a.M = nB * Ho * Ho;
         a.epi = EPI_BIAS_LRELU_DROP; a.bias = DP(c, di_b(l)); a.noise = nz(l); a.slope = slope;
         // fuse_cls (the step phases, whose k_bce / k_cls_bwd read either form): when the last block ends in a split-K epilogue,
         // the classifier's dot product rides there as P partials per image and k_cls_fwd is not launched
@@ -962,18 +978,15 @@ static bool d_backward_pass(const siggan_ctx* c, Lanes& L, const float* x0, int 
     if (want_wgrad)
         launch_cls_wgrad(c->dt, c->dlogit + r0, act(Ld), G_(di_cls_w(c)), G_(di_cls_b(c)), Bd, c->dC[Ld], sb);
     for (int l = Ld; l >= 2; --l) {
-        const int Ho = c->S >> l, Hi = 2 * Ho, Co = c->dC[l], Ci = c->dC[l - 1];
+        const int Ho = c->S >> l, Co = c->dC[l], Ci = c->dC[l - 1];
         // 16-bit contexts (launch-latency-bound): the LAST block's weight gradient runs behind the input-gradient chain on the
         // main lane, own slab, so that lane a ends before the main lane does (measured with the three 16-bit lane rules
         // together: bf16 0.718 -> 0.707 ms; at fp32 each is within noise and the plain structure stays)
         const bool w_main = want_wgrad && l == 2 && c->dt != DT_F32 && garena == nullptr;
         auto wgrad_l = [&](hipStream_t st, float* slab) {
-            WgradArgs w; memset(&w, 0, sizeof w); w.zeros = c->zeros; w.dt = c->dt;
-            w.S = dvp(l); w.L = act(l - 1); w.slab = slab; w.dw = G_(di_w(l)); w.B = Bd; w.Cs = Co; w.Cl = Ci;
-            w.lgHs = ilog2i(Ho); w.lgWs = w.lgHs; w.lgCl = ilog2i(Ci); w.K = Bd * Ho * Ho;
-            w.db = G_(di_b(l));                              // bias gradient = column sums of d(pre-activation): rides in the same kernel
-            const int max_splits = (int)(c->slab_floats / ((int64_t)Co * (16 * Ci + 1)));
-            launch_wgrad(w, max_splits, st);
+            WgradCall g = wgrad_args(c, dvp(l), act(l - 1), G_(di_w(l)), slab, Bd, Ho, Co, Ci);
+            g.w.db = G_(di_b(l));                            // bias gradient = column sums of d(pre-activation): rides in the same kernel
+            launch_wgrad(g.w, g.max_splits, st);
         };
         if (want_wgrad && !w_main) {
             L.fork(L.a);                                   // d_dv[l] is complete on m here
@@ -992,11 +1005,9 @@ static bool d_backward_pass(const siggan_ctx* c, Lanes& L, const float* x0, int 
                 else { L.record(c->ev_ar, c->s_n); early_ar = true; }
             }
         }
-        // input gradient ("up" form): contract Cout, produce Cin at (Hi x Hi); fused leaky'/dropout of block l-1
-        GConvArgs a = gconv_args(c);
+        // input gradient ("up" form): contract Cout, produce Cin at (2 Ho x 2 Ho); fused leaky'/dropout of block l-1
+        GConvArgs a = gconv_args(c, 1, Bd, Ho, Co, Ci);
         a.in = dvp(l); a.wp = c->d_up[l]; a.out = dvp(l - 1);
-        a.B = Bd; a.Hi = Ho; a.Wi = Ho; a.Ci = Co; a.Co = Ci;
-        a.lgHr = ilog2i(Ho); a.lgWr = a.lgHr; a.Ho = Hi; a.Wo = Hi; a.form = 1; a.M = Bd * Ho * Ho;
         a.epi = EPI_LRELU_BWD; a.aref = act(l - 1); a.noise = nz(l - 1); a.slope = slope;
         launch_gconv(a, L.m);
         if (w_main) {
@@ -1045,16 +1056,11 @@ static void g_backward_pass(const siggan_ctx* c, Lanes& L, const float* z, int B
         L.fork_after(L.a, ef);
         // weight gradient: small = block input a[l-1] (Hi), large = dy[l] (Ho)
         // (one fork per block; per two blocks measured the same, weight gradients on the main lane 2.5 % slower: DESIGN 4)
-        WgradArgs w; memset(&w, 0, sizeof w); w.zeros = c->zeros; w.dt = c->dt;
-        w.S = c->g_a[l - 1]; w.L = c->g_da[l]; w.slab = c->slab; w.dw = GG(c, gi_up_w(l)); w.B = B; w.Cs = Ci; w.Cl = Co;
-        w.lgHs = ilog2i(Hi); w.lgWs = w.lgHs; w.lgCl = ilog2i(Co); w.K = B * Hi * Hi;
-        const int max_splits = (int)(c->slab_floats / ((int64_t)Ci * (16 * Co + 1)));
-        launch_wgrad(w, max_splits, L.a);
+        const WgradCall g = wgrad_args(c, c->g_a[l - 1], c->g_da[l], GG(c, gi_up_w(l)), c->slab, B, Hi, Ci, Co);
+        launch_wgrad(g.w, g.max_splits, L.a);
         // input gradient ("down" form): out = Cin at Hi, contract Cout over 16 taps
-        GConvArgs a = gconv_args(c);
-        a.in = c->g_da[l]; a.wp = c->g_dn[l]; a.out = c->g_da[l - 1];
-        a.B = B; a.Hi = Ho; a.Wi = Ho; a.Ci = Co; a.Co = Ci;
-        a.lgHr = ilog2i(Hi); a.lgWr = a.lgHr; a.Ho = Hi; a.Wo = Hi; a.form = 0; a.M = B * Hi * Hi; a.epi = EPI_RAW;
+        GConvArgs a = gconv_args(c, 0, B, Ho, Co, Ci);
+        a.in = c->g_da[l]; a.wp = c->g_dn[l]; a.out = c->g_da[l - 1]; a.epi = EPI_RAW;
         if (l >= 2) {              // its output is d(activation output) of block l-1: that block's BatchNorm-backward sums ride in the epilogue
             a.epi = EPI_BN_BWD_STATS; a.aref = c->g_y[l - 1]; a.bnp = c->g_bn[l - 1]; a.stat0 = c->partial; a.stat_cap = PARTIAL_FLOATS;
         }
@@ -1464,6 +1470,28 @@ extern "C" int siggan_set_mode(siggan_ctx* c, int32_t mode) {
     return SIGGAN_OK;
 }
 
+// What every forward / latent-gradient entry point enqueues on the caller's stream before its own kernels, behind its argument
+// checks (a refusal enqueues and invalidates nothing): wait for an abandoned early D(real) forward, then rebuild what the
+// arenas' changes made stale.  with_d: the call runs the Discriminator in workspace rows [0, batch) -- what a step carries in
+// those rows is dropped, and a spectral-norm context forms sigma into slot 2 first (sn_power_iteration: train(), u and v move
+// as under torch's hook; else from the stored u, v) and packs W / sigma.  Generator only: a spectral-norm context's
+// Discriminator packs follow sigma, not the arena, and are left alone (d_dirty stays).
+static int begin_eval(siggan_ctx* c, hipStream_t s, bool with_d, bool sn_power_iteration) {
+    if (with_d) invalidate(c, INV_ROWS);
+    const int rc = settle(c, s);
+    if (rc) return rc;
+    Lanes L(c, s);
+    if (with_d) {
+        if (c->sn) launch_sn_sigma(c->snt, sn_power_iteration, 2, SN_EPS, s);
+        repack(c, L, s, s, c->g_dirty, c->sn || c->d_dirty, 2);
+        c->g_dirty = c->d_dirty = false;
+    } else {
+        repack(c, L, s, s, c->g_dirty, !c->sn && c->d_dirty);
+        c->g_dirty = false; if (!c->sn) c->d_dirty = false;
+    }
+    return SIGGAN_OK;
+}
+
 extern "C" int siggan_g_forward(siggan_ctx* c, const float* z_dev, int32_t batch, int32_t training, float* images_dev,
                                 void* stream) {
     ENTER(c);
@@ -1472,10 +1500,7 @@ extern "C" int siggan_g_forward(siggan_ctx* c, const float* z_dev, int32_t batch
     if (training && (rc = check_bn_batch(c, batch))) return rc;
     if (!z_dev || !images_dev) return fail(SIGGAN_E_INVALID, "null tensor");
     hipStream_t s = (hipStream_t)stream;
-    if ((rc = settle(c, s))) return rc;
-    Lanes L(c, s);
-    repack(c, L, s, s, c->g_dirty, !c->sn && c->d_dirty);
-    c->g_dirty = false; if (!c->sn) c->d_dirty = false;
+    if ((rc = begin_eval(c, s, false, false))) return rc;
     c->cs.ga_last_B = g_forward_pass(c, z_dev, batch, training != 0, images_dev, s);
     if (training) c->g_dirty = true;   // running statistics moved: the eval-mode tables are stale
     LAUNCHCHK();
@@ -1491,122 +1516,43 @@ extern "C" int siggan_g_generate_u8(siggan_ctx* c, const float* z_dev, int32_t b
     if (reinterpret_cast<uintptr_t>(u8_dev) & 3) return fail(SIGGAN_E_INVALID, "u8_dev must be 4-byte aligned");
     if (stats_dev && !isfinite(threshold)) return fail(SIGGAN_E_INVALID, "threshold must be finite");
     hipStream_t s = (hipStream_t)stream;
-    if ((rc = settle(c, s))) return rc;
-    Lanes L(c, s);
-    repack(c, L, s, s, c->g_dirty, !c->sn && c->d_dirty);
-    c->g_dirty = false; if (!c->sn) c->d_dirty = false;
+    if ((rc = begin_eval(c, s, false, false))) return rc;
     c->cs.ga_last_B = g_forward_pass(c, z_dev, batch, false, images_dev, s, nullptr, nullptr, 0, nullptr, nullptr, u8_dev, stats_dev, threshold);
-    LAUNCHCHK();
-    return lane_check(c);
-}
-
-// The gradient of a per-image reconstruction loss with respect to z through the EVAL-mode Generator: forward with every
-// activation kept (g_a), then backward with BatchNorm as the per-channel affine it is in eval mode -- g . act'(a) . scale[c], none
-// of the training backward's batch sums -- down to dz = dh . W_fc.  Launches (2 Lg + 7, plus a split-K tail where launch_gconv
-// splits): forward Lg + 2, loss 1, loss sum + scale tables 1, final conv input-gradient 1, one implicit GEMM per block, fc 2.
-// The blocks' input-gradients are launch_gconv form 0 on the packs g_dn[l], as in g_backward_pass, with the EXISTING epilogue
-// EPI_LRELU_BWD: acc * (aref > 0 ? 1 : slope) * noise[n][c] on the stored activation is exactly block l-1's mask and eval scale
-// once `noise` is that block's scale row repeated per image (lg_tab, rebuilt every call: the running statistics move).  Block 0's
-// scale is per feature (F values), so the GEMM into it stores raw values and k_fc_dz applies mask and scale on load.
-// Scratch: dpre, g_da, partial, partial_b, lg_tab -- all rewritten by a training phase before it reads them, none carried
-// between calls; the activations g_a are the eval forward's to overwrite (Carried::ga_last_B says so).
-extern "C" int siggan_g_latent_grad(siggan_ctx* c, const float* z_dev, int32_t batch, const uint8_t* target_u8_dev,
-                                    const float* target_f32_dev, float* dz_dev, float* loss_dev, float* images_dev, void* stream) {
-    ENTER(c);
-    int rc = check_call(c, batch);
-    if (rc) return rc;
-    if (c->dt != DT_F32) return fail(SIGGAN_E_INVALID, "siggan_g_latent_grad needs an fp32 context (16-bit activations are not built for it)");
-    if ((target_u8_dev != nullptr) == (target_f32_dev != nullptr))
-        return fail(SIGGAN_E_INVALID, "exactly one of target_u8_dev and target_f32_dev must be given");
-    if (!z_dev || !dz_dev || !loss_dev) return fail(SIGGAN_E_INVALID, "null tensor");
-    if (reinterpret_cast<uintptr_t>(target_u8_dev) & 3) return fail(SIGGAN_E_INVALID, "target_u8_dev must be 4-byte aligned");
-    if ((reinterpret_cast<uintptr_t>(target_f32_dev) | reinterpret_cast<uintptr_t>(images_dev)) & 15)
-        return fail(SIGGAN_E_INVALID, "target_f32_dev and images_dev must be 16-byte aligned");
-    if (c->cs.g_fwd_pending)
-        return fail(SIGGAN_E_STATE, "siggan_step_begin must be followed by siggan_g_grads first: the pipelined forward's activations are in use");
-    hipStream_t s = (hipStream_t)stream;
-    if ((rc = settle(c, s))) return rc;
-    Lanes L(c, s);
-    repack(c, L, s, s, c->g_dirty, !c->sn && c->d_dirty);
-    c->g_dirty = false; if (!c->sn) c->d_dirty = false;
-    const int B = batch, Lg = c->Lg, S = c->S;
-    const float gs = c->cfg.g_leaky_slope;
-    float* const img = images_dev ? images_dev : c->img;
-    c->cs.ga_last_B = g_forward_pass(c, z_dev, B, false, img, s);
-    launch_recon_loss(img, target_u8_dev, target_f32_dev, c->deq_lut, c->dpre, c->partial_b, B, S, s);
-    ScaleTiles t; memset(&t, 0, sizeof t);
-    const float* tab[MAXL + 1] = {nullptr};
-    float* next = c->lg_tab;
-    for (int l = 1; l < Lg; ++l) {
-        t.src[t.nt] = c->g_bne[l]; t.dst[t.nt] = next; t.C[t.nt] = c->gC[l]; ++t.nt;
-        tab[l] = next; next += (int64_t)B * c->gC[l];
-    }
-    launch_loss_fin_tiles(c->partial_b, recon_loss_parts(S), loss_dev, B, S, t, s);
-    launch_final_dgrad_eval(c->dpre, c->wfin_t, (const float*)c->g_a[Lg], c->g_bne[Lg], (float*)c->g_da[Lg], B, S, gs, s);
-    for (int l = Lg; l >= 1; --l) {
-        const int Hi = 4 << (l - 1), Ho = 2 * Hi, Ci = c->gC[l - 1], Co = c->gC[l];
-        GConvArgs a = gconv_args(c);
-        a.in = c->g_da[l]; a.wp = c->g_dn[l]; a.out = c->g_da[l - 1];
-        a.B = B; a.Hi = Ho; a.Wi = Ho; a.Ci = Co; a.Co = Ci;
-        a.lgHr = ilog2i(Hi); a.lgWr = a.lgHr; a.Ho = Hi; a.Wo = Hi; a.form = 0; a.M = B * Hi * Hi; a.epi = EPI_RAW;
-        if (l >= 2) { a.epi = EPI_LRELU_BWD; a.aref = c->g_a[l - 1]; a.noise = tab[l - 1]; a.slope = gs; }
-        launch_gconv(a, s);
-    }
-    launch_fc_dz((const float*)c->g_da[0], (const float*)c->g_a[0], c->g_bne[0], GP(c, gi_fc_w()), dz_dev, c->partial,
-                 PARTIAL_FLOATS - 64, B, c->latent, c->gC[0], gs, s);      // (the last 64 floats: siggan_op_adam's scratch slot)
     LAUNCHCHK();
     return lane_check(c);
 }
 
 // The gradient with respect to z of a per-image objective  wr * recon + wd * realism + wp * prior  through the EVAL-mode
 // Generator and, for the realism term -max(log D(G(z)), -100), the EVAL-mode Discriminator (no dropout; spectral norm: W / sigma
-// from the stored u, v, which do not move -- siggan_d_forward(training = 0)'s own preamble and forward).  The sequence, all on
-// the caller's stream: the Generator forward (Lg + 2 launches);  [wd > 0:  d_forward_rows at rows [0, B) with stored logits
-// (Ld + 1), the per-image classifier tail k_cls_bwd_eval (1), the Discriminator's input-gradient chain -- launch_gconv form 1 on
-// the d_up packs, EPI_LRELU_BWD without a dropout table (Ld - 1) -- and the first block's input-gradient times 1 - x^2 into dpre
-// (1)];  [wr > 0: k_recon_loss (1), which with wd > 0 adds its seed onto dpre as fmaf(wr, ., dpre): no axpy launch];  objective +
-// scale tables (1);  siggan_g_latent_grad's chain from dpre (Lg + 3), the prior's wp * z / latent riding in k_fc_dz_sum.
-// 2 Lg + 6 + [wr > 0] + [wd > 0] (2 Ld + 2) launches plus split-K tails: 15 / 24 / 25 at 64x64 for (1,0,0) / (0,1,0) / all three; the prior alone: Lg + 4, no backward chain.
-// Scratch: siggan_g_latent_grad's list (dpre, g_da, partial, partial_b, lg_tab, the activations g_a) plus the Discriminator's
-// rows [0, B) of d_a and d_dv, logits and dlogit (the realism terms when terms_dev is not given) -- all rewritten by a training
-// phase before it reads them; what a step carries in those rows is dropped exactly as siggan_d_forward drops it (INV_ROWS).
-extern "C" int siggan_g_latent_objective_grad(siggan_ctx* c, const float* z_dev, int32_t batch, const uint8_t* target_u8_dev,
-                                              const float* target_f32_dev, const siggan_latent_objective* w, float* dz_dev,
-                                              float* objective_dev, float* terms_dev, float* probs_dev, float* images_dev,
-                                              void* stream) {
-    ENTER(c);
-    int rc = check_call(c, batch);
+// from the stored u, v, which do not move).  ONE device sequence serves both entry points: siggan_g_latent_grad is the call with
+// the weights (1, 0, 0), its loss in the objective's place, no terms and no probs.  All on the caller's stream:
+//   - the Generator forward with every activation kept (g_a): Lg + 2 launches;
+//   - [wd > 0]  d_forward_rows at rows [0, B) with stored logits (Ld + 1), the per-image classifier tail k_cls_bwd_eval (1), the
+//     Discriminator's input-gradient chain -- launch_gconv form 1 on the d_up packs, EPI_LRELU_BWD without a dropout table
+//     (Ld - 1) -- and the first block's input-gradient times 1 - x^2 into dpre (1);
+//   - [wr > 0]  k_recon_loss (1): the loss partials and its seed of dpre -- with wd > 0 added onto the Discriminator's as
+//     fmaf(wr, ., dpre): no axpy launch;
+//   - k_obj_fin_tiles (1): the objective (and terms) per image, and the per-image scale tables below;
+//   - the backward through the Generator with BatchNorm as the per-channel affine it is in eval mode -- g . act'(a) . scale[c],
+//     none of the training backward's batch sums -- (Lg + 3): the final conv's input-gradient (1), one implicit GEMM per block,
+//     fc (2, the prior's wp * z / latent riding in k_fc_dz_sum).  The blocks' input-gradients are launch_gconv form 0 on the packs
+//     g_dn[l], as in g_backward_pass, with the EXISTING epilogue EPI_LRELU_BWD: acc * (aref > 0 ? 1 : slope) * noise[n][c] on the
+//     stored activation is exactly block l-1's mask and eval scale once `noise` is that block's scale row repeated per image
+//     (lg_tab, rebuilt every call: the running statistics move).  Block 0's scale is per feature (F values), so the GEMM into it
+//     stores raw values and k_fc_dz applies mask and scale on load.
+// 2 Lg + 6 + [wr > 0] + [wd > 0] (2 Ld + 2) launches plus split-K tails.  (1, 0, 0): 2 Lg + 7, which is also siggan_g_latent_grad
+// -- 15 at 64x64; (0, 1, 0): 24; all three: 25; the prior alone: Lg + 4, no backward chain (dz = wp * z / latent).
+// Scratch: dpre, g_da, partial, partial_b, lg_tab, the activations g_a (the eval forward's to overwrite: Carried::ga_last_B
+// says so) and, with wd > 0, the Discriminator's rows [0, B) of d_a and d_dv, logits and dlogit (the realism terms when
+// terms_dev is not given) -- all rewritten by a training phase before it reads them, none carried between calls; what a step
+// carries in those rows is dropped exactly as siggan_d_forward drops it (begin_eval).
+// The caller has validated everything: exactly one target when wr > 0 (none otherwise), probs_dev only with wd > 0.
+static int latent_objective_grad(siggan_ctx* c, const float* z_dev, int B, const uint8_t* target_u8_dev, const float* target_f32_dev,
+                                 float wr, float wd, float wp, float* dz_dev, float* objective_dev, float* terms_dev,
+                                 float* probs_dev, float* images_dev, hipStream_t s) {
+    const int rc = begin_eval(c, s, wd > 0.f, false);
     if (rc) return rc;
-    if (c->dt != DT_F32) return fail(SIGGAN_E_INVALID, "siggan_g_latent_objective_grad needs an fp32 context (16-bit activations are not built for it)");
-    if (!w) return fail(SIGGAN_E_INVALID, "null weights");
-    const float wr = w->recon_weight, wd = w->realism_weight, wp = w->prior_weight;
-    if (!isfinite(wr) || !isfinite(wd) || !isfinite(wp) || wr < 0.f || wd < 0.f || wp < 0.f)
-        return fail(SIGGAN_E_INVALID, "the objective's weights must be finite and >= 0, got (%g, %g, %g)", (double)wr, (double)wd, (double)wp);
-    if (wr == 0.f && wd == 0.f && wp == 0.f) return fail(SIGGAN_E_INVALID, "all three weights of the objective are 0");
-    const int ntargets = (target_u8_dev != nullptr) + (target_f32_dev != nullptr);
-    if (wr > 0.f && ntargets != 1)
-        return fail(SIGGAN_E_INVALID, "recon_weight > 0 needs exactly one of target_u8_dev and target_f32_dev");
-    if (wr == 0.f && ntargets != 0) return fail(SIGGAN_E_INVALID, "a target was given but recon_weight is 0");
-    if (probs_dev && wd == 0.f) return fail(SIGGAN_E_INVALID, "probs_dev needs realism_weight > 0");
-    if (!z_dev || !dz_dev || !objective_dev) return fail(SIGGAN_E_INVALID, "null tensor");
-    if (reinterpret_cast<uintptr_t>(target_u8_dev) & 3) return fail(SIGGAN_E_INVALID, "target_u8_dev must be 4-byte aligned");
-    if ((reinterpret_cast<uintptr_t>(target_f32_dev) | reinterpret_cast<uintptr_t>(images_dev)) & 15)
-        return fail(SIGGAN_E_INVALID, "target_f32_dev and images_dev must be 16-byte aligned");
-    if (c->cs.g_fwd_pending)
-        return fail(SIGGAN_E_STATE, "siggan_step_begin must be followed by siggan_g_grads first: the pipelined forward's activations are in use");
-    hipStream_t s = (hipStream_t)stream;
-    if (wd > 0.f) invalidate(c, INV_ROWS);       // as siggan_d_forward: rows [0, batch) are overwritten
-    if ((rc = settle(c, s))) return rc;
-    Lanes L(c, s);
-    if (wd > 0.f) {                              // siggan_d_forward(training = 0)'s preamble
-        if (c->sn) launch_sn_sigma(c->snt, false, 2, SN_EPS, s);
-        repack(c, L, s, s, c->g_dirty, c->sn || c->d_dirty, 2);
-        c->g_dirty = c->d_dirty = false;
-    } else {                                     // siggan_g_latent_grad's
-        repack(c, L, s, s, c->g_dirty, !c->sn && c->d_dirty);
-        c->g_dirty = false; if (!c->sn) c->d_dirty = false;
-    }
-    const int B = batch, Lg = c->Lg, Ld = c->Ld, S = c->S;
+    const int Lg = c->Lg, Ld = c->Ld, S = c->S;
     const float gs = c->cfg.g_leaky_slope;
     float* const img = images_dev ? images_dev : c->img;
     c->cs.ga_last_B = g_forward_pass(c, z_dev, B, false, img, s);
@@ -1616,11 +1562,8 @@ extern "C" int siggan_g_latent_objective_grad(siggan_ctx* c, const float* z_dev,
         launch_cls_bwd_eval(c->logits, nullptr, 0, DP(c, di_cls_b(c)), c->wcp, (const float*)c->d_a[Ld], c->cfg.leaky_slope,
                             (float*)c->d_dv[Ld], B, c->dC[Ld], wd, realism, probs_dev, s);
         for (int l = Ld; l >= 2; --l) {
-            const int Ho = S >> l, Hi = 2 * Ho, Co = c->dC[l], Ci = c->dC[l - 1];
-            GConvArgs a = gconv_args(c);
+            GConvArgs a = gconv_args(c, 1, B, S >> l, c->dC[l], c->dC[l - 1]);
             a.in = c->d_dv[l]; a.wp = c->d_up[l]; a.out = c->d_dv[l - 1];
-            a.B = B; a.Hi = Ho; a.Wi = Ho; a.Ci = Co; a.Co = Ci;
-            a.lgHr = ilog2i(Ho); a.lgWr = a.lgHr; a.Ho = Hi; a.Wo = Hi; a.form = 1; a.M = B * Ho * Ho;
             a.epi = EPI_LRELU_BWD; a.aref = c->d_a[l - 1]; a.noise = nullptr; a.slope = c->cfg.leaky_slope;
             launch_gconv(a, s);
         }
@@ -1640,14 +1583,12 @@ extern "C" int siggan_g_latent_objective_grad(siggan_ctx* c, const float* z_dev,
     if (wr > 0.f || wd > 0.f) {
         launch_final_dgrad_eval(c->dpre, c->wfin_t, (const float*)c->g_a[Lg], c->g_bne[Lg], (float*)c->g_da[Lg], B, S, gs, s);
         for (int l = Lg; l >= 1; --l) {
-            const int Hi = 4 << (l - 1), Ho = 2 * Hi, Ci = c->gC[l - 1], Co = c->gC[l];
-            GConvArgs a = gconv_args(c);
-            a.in = c->g_da[l]; a.wp = c->g_dn[l]; a.out = c->g_da[l - 1];
-            a.B = B; a.Hi = Ho; a.Wi = Ho; a.Ci = Co; a.Co = Ci;
-            a.lgHr = ilog2i(Hi); a.lgWr = a.lgHr; a.Ho = Hi; a.Wo = Hi; a.form = 0; a.M = B * Hi * Hi; a.epi = EPI_RAW;
+            GConvArgs a = gconv_args(c, 0, B, 4 << l, c->gC[l], c->gC[l - 1]);
+            a.in = c->g_da[l]; a.wp = c->g_dn[l]; a.out = c->g_da[l - 1]; a.epi = EPI_RAW;
             if (l >= 2) { a.epi = EPI_LRELU_BWD; a.aref = c->g_a[l - 1]; a.noise = tab[l - 1]; a.slope = gs; }
             launch_gconv(a, s);
         }
+        // (the last 64 floats of `partial` are siggan_op_adam's scratch slot)
         launch_fc_dz((const float*)c->g_da[0], (const float*)c->g_a[0], c->g_bne[0], GP(c, gi_fc_w()), dz_dev, c->partial,
                      PARTIAL_FLOATS - 64, B, c->latent, c->gC[0], gs, s, wp > 0.f ? z_dev : nullptr, wp / (float)c->latent);
     } else {
@@ -1655,6 +1596,53 @@ extern "C" int siggan_g_latent_objective_grad(siggan_ctx* c, const float* z_dev,
     }
     LAUNCHCHK();
     return lane_check(c);
+}
+// The checks both entry points share behind their own (same order, same texts, nothing enqueued).
+static int check_latent_tensors(const siggan_ctx* c, const float* z_dev, const float* dz_dev, const float* out_dev,
+                                const uint8_t* target_u8_dev, const float* target_f32_dev, const float* images_dev) {
+    if (!z_dev || !dz_dev || !out_dev) return fail(SIGGAN_E_INVALID, "null tensor");
+    if (reinterpret_cast<uintptr_t>(target_u8_dev) & 3) return fail(SIGGAN_E_INVALID, "target_u8_dev must be 4-byte aligned");
+    if ((reinterpret_cast<uintptr_t>(target_f32_dev) | reinterpret_cast<uintptr_t>(images_dev)) & 15)
+        return fail(SIGGAN_E_INVALID, "target_f32_dev and images_dev must be 16-byte aligned");
+    if (c->cs.g_fwd_pending)
+        return fail(SIGGAN_E_STATE, "siggan_step_begin must be followed by siggan_g_grads first: the pipelined forward's activations are in use");
+    return SIGGAN_OK;
+}
+
+extern "C" int siggan_g_latent_grad(siggan_ctx* c, const float* z_dev, int32_t batch, const uint8_t* target_u8_dev,
+                                    const float* target_f32_dev, float* dz_dev, float* loss_dev, float* images_dev, void* stream) {
+    ENTER(c);
+    int rc = check_call(c, batch);
+    if (rc) return rc;
+    if (c->dt != DT_F32) return fail(SIGGAN_E_INVALID, "siggan_g_latent_grad needs an fp32 context (16-bit activations are not built for it)");
+    if ((target_u8_dev != nullptr) == (target_f32_dev != nullptr))
+        return fail(SIGGAN_E_INVALID, "exactly one of target_u8_dev and target_f32_dev must be given");
+    if ((rc = check_latent_tensors(c, z_dev, dz_dev, loss_dev, target_u8_dev, target_f32_dev, images_dev))) return rc;
+    return latent_objective_grad(c, z_dev, batch, target_u8_dev, target_f32_dev, 1.f, 0.f, 0.f, dz_dev, loss_dev, nullptr, nullptr,
+                                 images_dev, (hipStream_t)stream);
+}
+
+extern "C" int siggan_g_latent_objective_grad(siggan_ctx* c, const float* z_dev, int32_t batch, const uint8_t* target_u8_dev,
+                                              const float* target_f32_dev, const siggan_latent_objective* w, float* dz_dev,
+                                              float* objective_dev, float* terms_dev, float* probs_dev, float* images_dev,
+                                              void* stream) {
+    ENTER(c);
+    int rc = check_call(c, batch);
+    if (rc) return rc;
+    if (c->dt != DT_F32) return fail(SIGGAN_E_INVALID, "siggan_g_latent_objective_grad needs an fp32 context (16-bit activations are not built for it)");
+    if (!w) return fail(SIGGAN_E_INVALID, "null weights");
+    const float wr = w->recon_weight, wd = w->realism_weight, wp = w->prior_weight;
+    if (!isfinite(wr) || !isfinite(wd) || !isfinite(wp) || wr < 0.f || wd < 0.f || wp < 0.f)
+        return fail(SIGGAN_E_INVALID, "the objective's weights must be finite and >= 0, got (%g, %g, %g)", (double)wr, (double)wd, (double)wp);
+    if (wr == 0.f && wd == 0.f && wp == 0.f) return fail(SIGGAN_E_INVALID, "all three weights of the objective are 0");
+    const int ntargets = (target_u8_dev != nullptr) + (target_f32_dev != nullptr);
+    if (wr > 0.f && ntargets != 1)
+        return fail(SIGGAN_E_INVALID, "recon_weight > 0 needs exactly one of target_u8_dev and target_f32_dev");
+    if (wr == 0.f && ntargets != 0) return fail(SIGGAN_E_INVALID, "a target was given but recon_weight is 0");
+    if (probs_dev && wd == 0.f) return fail(SIGGAN_E_INVALID, "probs_dev needs realism_weight > 0");
+    if ((rc = check_latent_tensors(c, z_dev, dz_dev, objective_dev, target_u8_dev, target_f32_dev, images_dev))) return rc;
+    return latent_objective_grad(c, z_dev, batch, target_u8_dev, target_f32_dev, wr, wd, wp, dz_dev, objective_dev, terms_dev,
+                                 probs_dev, images_dev, (hipStream_t)stream);
 }
 
 extern "C" int siggan_d_forward(siggan_ctx* c, const float* x_dev, int32_t batch, int32_t training, const float* masks_dev,
@@ -1664,12 +1652,7 @@ extern "C" int siggan_d_forward(siggan_ctx* c, const float* x_dev, int32_t batch
     if (rc) return rc;
     if (!x_dev || (!probs_dev && !features_dev)) return fail(SIGGAN_E_INVALID, "null tensor");
     hipStream_t s = (hipStream_t)stream;
-    invalidate(c, INV_ROWS);           // rows [0, batch) are overwritten
-    if ((rc = settle(c, s))) return rc;
-    Lanes L(c, s);
-    if (c->sn) launch_sn_sigma(c->snt, training != 0, 2, SN_EPS, s);   // train(): one power iteration (u, v move), as torch's hook
-    repack(c, L, s, s, c->g_dirty, c->sn || c->d_dirty, 2);
-    c->g_dirty = c->d_dirty = false;
+    if ((rc = begin_eval(c, s, true, training != 0))) return rc;       // rows [0, batch) are overwritten
     const bool drop = training != 0 && c->cfg.dropout > 0.f;
     if (drop) { if (!masks_dev) launch_tick(c->dev, s); make_noise(c, masks_dev, batch, 0, 1, s); }
     c->cs.lP[0] = d_forward_rows(c, x_dev, 0, batch, drop, s, c->slab_k);
@@ -1687,12 +1670,7 @@ extern "C" int siggan_d_score_u8(siggan_ctx* c, const uint8_t* u8_dev, int32_t b
     if (!u8_dev || !probs_dev) return fail(SIGGAN_E_INVALID, "null tensor");
     if (binarize < -1 || binarize > 255) return fail(SIGGAN_E_INVALID, "binarize must be -1 (off) or a byte value, got %d", binarize);
     hipStream_t s = (hipStream_t)stream;
-    invalidate(c, INV_ROWS);           // as siggan_d_forward(training = 0): rows [0, batch) are overwritten
-    if ((rc = settle(c, s))) return rc;
-    Lanes L(c, s);
-    if (c->sn) launch_sn_sigma(c->snt, 0, 2, SN_EPS, s);
-    repack(c, L, s, s, c->g_dirty, c->sn || c->d_dirty, 2);
-    c->g_dirty = c->d_dirty = false;
+    if ((rc = begin_eval(c, s, true, false))) return rc;               // as siggan_d_forward(training = 0)
     c->cs.lP[0] = d_forward_rows(c, nullptr, 0, batch, false, s, c->slab_k, false, false, u8_dev, binarize, x_dev);
     launch_bce(c->logits, batch, batch, 0.f, 0.f, probs_dev, nullptr, nullptr, 0, s);
     LAUNCHCHK();
@@ -1911,19 +1889,13 @@ extern "C" int siggan_op_conv4x4s2(siggan_ctx* c, int32_t form, const void* in_d
     if (form == 0 && h_in < 2) return fail(SIGGAN_E_INVALID, "down form needs h_in >= 2");
     DevGuard dg_(c->cfg.device); HIPCHK(dg_.err);
     hipStream_t s = (hipStream_t)stream;
-    GConvArgs a = gconv_args(c);
-    a.in = in_dev; a.wp = c->op_pack; a.out = out_dev; a.B = batch; a.Hi = h_in; a.Wi = h_in; a.Ci = c_in; a.Co = c_out;
-    a.form = form; a.epi = EPI_RAW;
+    GConvArgs a = gconv_args(c, form, batch, h_in, c_in, c_out);
+    a.in = in_dev; a.wp = c->op_pack; a.out = out_dev; a.epi = EPI_RAW;
     PrepTable t; t.njobs = 0; t.overflow = 0;
     PrepJob j; memset(&j, 0, sizeof j);
     j.src = w_dev; j.dst = (float*)c->op_pack; j.dt = c->dt;
-    if (form == 0) {
-        j.type = PREP_PACK_DOWN; j.O = c_out; j.I = c_in;
-        a.Ho = a.Wo = h_in / 2; a.lgHr = a.lgWr = ilog2i(h_in / 2); a.M = batch * (h_in / 2) * (h_in / 2);
-    } else {
-        j.type = PREP_PACK_UP; j.I = c_in; j.O = c_out;
-        a.Ho = a.Wo = 2 * h_in; a.lgHr = a.lgWr = ilog2i(h_in); a.M = batch * h_in * h_in;
-    }
+    if (form == 0) { j.type = PREP_PACK_DOWN; j.O = c_out; j.I = c_in; }
+    else           { j.type = PREP_PACK_UP; j.I = c_in; j.O = c_out; }
     prep_add(t, j, (long long)c_in * c_out * 16);
     if (!launch_prepare(t, BN_EPS, s)) return fail(SIGGAN_E_STATE, "prepare table overflow");
     launch_gconv(a, s);
@@ -1940,11 +1912,8 @@ extern "C" int siggan_op_conv4x4s2_wgrad(siggan_ctx* c, const void* small_dev, c
         return fail(SIGGAN_E_INVALID, "shape not in the model family (pow2 dims, 32 <= C <= 512)");
     DevGuard dg_(c->cfg.device); HIPCHK(dg_.err);
     hipStream_t s = (hipStream_t)stream;
-    WgradArgs w; memset(&w, 0, sizeof w); w.zeros = c->zeros; w.dt = c->dt;
-    w.S = small_dev; w.L = large_dev; w.slab = c->slab; w.dw = dw_dev; w.B = batch; w.Cs = c_small; w.Cl = c_large;
-    w.lgHs = w.lgWs = ilog2i(h_small); w.lgCl = ilog2i(c_large); w.K = batch * h_small * h_small;
-    const int max_splits = (int)(c->slab_floats / ((int64_t)c_small * (16 * c_large + 1)));
-    launch_wgrad(w, max_splits, s);
+    const WgradCall g = wgrad_args(c, small_dev, large_dev, dw_dev, c->slab, batch, h_small, c_small, c_large);
+    launch_wgrad(g.w, g.max_splits, s);
     LAUNCHCHK();
     return SIGGAN_OK;
 }

@@ -328,34 +328,49 @@ class Engine:
         out = (u8,) + ((stats,) if stats is not None else ()) + ((img,) if img is not None else ())
         return out[0] if len(out) == 1 else out
 
-    def g_latent_grad(self, z, target, want_images=False, dz_out=None, loss_out=None):
-        """Eval-mode forward of z (B, latent), the per-image reconstruction loss mean((G(z) - t)^2) against ``target`` and its
-        gradient with respect to z (siggan_g_latent_grad; fp32 contexts).  ``target``: a uint8 (B, S, S) device tensor -- a
-        byte stands for its _lib.dequant_table() value -- or an fp32 (B, 1, S, S) one.  Returns (dz, loss[, images]): dz
-        (B, latent), loss (B,), images (B, 1, S, S) bit for bit g_forward(z).  ``dz_out`` / ``loss_out``: caller-owned contiguous
-        fp32 device tensors of B * latent / B elements the results are written into (an optimiser loop's gradient buffer, a
-        row of its loss history); they are then what is returned.  Nothing synchronises with the host."""
+    def _latent_inputs(self, z, target, target_optional=False):
+        """(z, B, t_u8, t_f32) of a latent-gradient call, validated: z fp32 (B, latent); ``target`` uint8 (B, S, S) or fp32
+        (B, 1, S, S) on the device -- None only where ``target_optional`` (both t_* are then None)."""
         z = _f32(z, self.device, "z")
         if z.dim() != 2 or z.shape[1] != self.latent_dim:
             raise ValueError(f"z must be (B, {self.latent_dim}), got {tuple(z.shape)}")
         b, s = z.shape[0], self.image_size
-        if target.device != self.device:
-            raise ValueError(f"target must live on {self.device}, got {target.device}")
-        if target.dtype == torch.uint8:
-            shape, t_u8, t_f32 = (b, s, s), target.contiguous(), None
-        elif target.dtype == torch.float32:
-            shape, t_u8, t_f32 = (b, 1, s, s), None, target.contiguous()
-        else:
-            raise ValueError(f"target must be uint8 (B, S, S) or float32 (B, 1, S, S), got {target.dtype}")
-        if tuple(target.shape) != shape:
-            raise ValueError(f"target must be {shape}, got {tuple(target.shape)}")
+        t_u8 = t_f32 = None
+        if target is not None or not target_optional:
+            if target.device != self.device:
+                raise ValueError(f"target must live on {self.device}, got {target.device}")
+            if target.dtype == torch.uint8:
+                shape, t_u8 = (b, s, s), target.contiguous()
+            elif target.dtype == torch.float32:
+                shape, t_f32 = (b, 1, s, s), target.contiguous()
+            else:
+                raise ValueError(f"target must be uint8 (B, S, S) or float32 (B, 1, S, S), got {target.dtype}")
+            if tuple(target.shape) != shape:
+                raise ValueError(f"target must be {shape}, got {tuple(target.shape)}")
         self._check_batch(b)
-        for t, n, what in ((dz_out, b * self.latent_dim, "dz_out"), (loss_out, b, "loss_out")):
-            if t is not None and (t.device != self.device or t.dtype != torch.float32 or t.numel() != n or not t.is_contiguous()):
-                raise ValueError(f"{what} must be a contiguous float32 tensor of {n} elements on {self.device}")
-        dz = torch.empty(b, self.latent_dim, dtype=torch.float32, device=self.device) if dz_out is None else dz_out
-        loss = torch.empty(b, dtype=torch.float32, device=self.device) if loss_out is None else loss_out
-        img = torch.empty(b, 1, s, s, dtype=torch.float32, device=self.device) if want_images else None
+        return z, b, t_u8, t_f32
+
+    def _out_f32(self, t, shape, what):
+        """A caller-owned output buffer ``t`` (argument ``what``), checked -- contiguous fp32 on this device with the element
+        count of ``shape`` -- or, for None, a new fp32 device tensor of that shape."""
+        if t is None:
+            return torch.empty(*shape, dtype=torch.float32, device=self.device)
+        n = torch.Size(shape).numel()
+        if t.device != self.device or t.dtype != torch.float32 or t.numel() != n or not t.is_contiguous():
+            raise ValueError(f"{what} must be a contiguous float32 tensor of {n} elements on {self.device}")
+        return t
+
+    def g_latent_grad(self, z, target, want_images=False, dz_out=None, loss_out=None):
+        """Eval-mode forward of z (B, latent), the per-image reconstruction loss mean((G(z) - t)^2) against ``target`` and its
+        gradient with respect to z (siggan_g_latent_grad, the library's objective call with the weights (1, 0, 0); fp32
+        contexts).  ``target``: a uint8 (B, S, S) device tensor -- a byte stands for its _lib.dequant_table() value -- or an
+        fp32 (B, 1, S, S) one.  Returns (dz, loss[, images]): dz (B, latent), loss (B,), images (B, 1, S, S) bit for bit
+        g_forward(z).  ``dz_out`` / ``loss_out``: caller-owned contiguous fp32 device tensors of B * latent / B elements the
+        results are written into (an optimiser loop's gradient buffer, a row of its loss history); they are then what is
+        returned.  Nothing synchronises with the host."""
+        z, b, t_u8, t_f32 = self._latent_inputs(z, target)
+        dz, loss = self._out_f32(dz_out, (b, self.latent_dim), "dz_out"), self._out_f32(loss_out, (b,), "loss_out")
+        img = torch.empty(b, 1, self.image_size, self.image_size, dtype=torch.float32, device=self.device) if want_images else None
         _lib.check(self.lib.siggan_g_latent_grad(self._h, _ptr(z), b, _ptr(t_u8), _ptr(t_f32), _ptr(dz), _ptr(loss), _ptr(img),
                                                  self._stream()))
         return (dz, loss, img) if want_images else (dz, loss)
@@ -369,33 +384,13 @@ class Engine:
         recon / realism / prior terms (0 where the weight is 0), probs (B,) D(G(z)) (needs realism_weight > 0), images
         (B, 1, S, S) bit for bit g_forward(z).  ``dz_out`` / ``objective_out``: as g_latent_grad's dz_out / loss_out.  Nothing
         synchronises with the host."""
-        z = _f32(z, self.device, "z")
-        if z.dim() != 2 or z.shape[1] != self.latent_dim:
-            raise ValueError(f"z must be (B, {self.latent_dim}), got {tuple(z.shape)}")
-        b, s = z.shape[0], self.image_size
         w = check_objective_weights(recon_weight, realism_weight, prior_weight, target is not None, want_probs)
-        t_u8 = t_f32 = None
-        if target is not None:
-            if target.device != self.device:
-                raise ValueError(f"target must live on {self.device}, got {target.device}")
-            if target.dtype == torch.uint8:
-                shape, t_u8 = (b, s, s), target.contiguous()
-            elif target.dtype == torch.float32:
-                shape, t_f32 = (b, 1, s, s), target.contiguous()
-            else:
-                raise ValueError(f"target must be uint8 (B, S, S) or float32 (B, 1, S, S), got {target.dtype}")
-            if tuple(target.shape) != shape:
-                raise ValueError(f"target must be {shape}, got {tuple(target.shape)}")
-        self._check_batch(b)
-        for t, n, what in ((dz_out, b * self.latent_dim, "dz_out"), (objective_out, b, "objective_out")):
-            if t is not None and (t.device != self.device or t.dtype != torch.float32 or t.numel() != n or not t.is_contiguous()):
-                raise ValueError(f"{what} must be a contiguous float32 tensor of {n} elements on {self.device}")
+        z, b, t_u8, t_f32 = self._latent_inputs(z, target, target_optional=True)
+        dz, obj = self._out_f32(dz_out, (b, self.latent_dim), "dz_out"), self._out_f32(objective_out, (b,), "objective_out")
         new = lambda *shape: torch.empty(*shape, dtype=torch.float32, device=self.device)
-        dz = new(b, self.latent_dim) if dz_out is None else dz_out
-        obj = new(b) if objective_out is None else objective_out
         terms = new(3, b) if want_terms else None
         probs = new(b) if want_probs else None
-        img = new(b, 1, s, s) if want_images else None
+        img = new(b, 1, self.image_size, self.image_size) if want_images else None
         _lib.check(self.lib.siggan_g_latent_objective_grad(self._h, _ptr(z), b, _ptr(t_u8), _ptr(t_f32), C.byref(_lib.LatentObjective(*w)),
                                                            _ptr(dz), _ptr(obj), _ptr(terms), _ptr(probs), _ptr(img), self._stream()))
         return (dz, obj) + tuple(t for t in (terms, probs, img) if t is not None)

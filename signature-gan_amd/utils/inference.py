@@ -11,7 +11,7 @@ it is where a trained Discriminator is used after training) lives here too: ``lo
 ``process_images``, ``filter_plan`` and ``generate_signatures_filtered``.
 
 So does the way back from an image to a latent vector: ``project_signatures`` (an Adam loop on z around
-Engine.g_latent_grad), and on top of it the app's second generation tab, "Morphing" (app_vanilla_gan_signatures.py:1631-1717):
+Engine.g_latent_objective_grad), and on top of it the app's second generation tab, "Morphing" (app_vanilla_gan_signatures.py:1631-1717):
 ``morph_blend``, ``morph_sequence`` and ``morph_strip``.
 
 Realism-guided refinement joins the two: ``refine_latents`` moves latent vectors up the Discriminator's eval-mode score (an
@@ -366,6 +366,21 @@ def _check_refine(steps, lr, realism_weight, prior_weight):
         raise ValueError("refinement follows the Discriminator's score: realism_weight must be > 0")
 
 
+def _descend(eng, z, steps, lr, betas, grad, final_out=None):
+    """The Adam-on-z loop of projection and refinement on one chunk: ``steps`` iterations of ``grad(k, z, dz, out)`` -- which
+    writes the gradient at z into dz and the per-image objective into out (None: not wanted) -- and one Engine.op_adam on
+    (z, dz, m, v), which updates ``z`` in place; then ``grad(steps, z, dz, final_out)``, the evaluation AT the returned z.
+    Returns the (steps, b) history: the objective at the start of every iteration.  Nothing synchronises with the host."""
+    m, v = torch.zeros_like(z), torch.zeros_like(z)
+    dz = torch.empty_like(z)
+    hist = torch.empty(steps, z.shape[0], dtype=torch.float32, device=z.device)
+    for k in range(steps):
+        grad(k, z, dz, hist[k])
+        eng.op_adam(z, dz, m, v, k + 1, lr=lr, beta1=betas[0], beta2=betas[1])
+    grad(steps, z, dz, final_out)
+    return hist
+
+
 def _refine(eng, generator, z0, steps, lr, betas, realism_weight, prior_weight):
     dev, latent = eng.device, eng.latent_dim
     z0 = torch.as_tensor(z0, dtype=torch.float32)
@@ -378,16 +393,14 @@ def _refine(eng, generator, z0, steps, lr, betas, realism_weight, prior_weight):
     w = dict(realism_weight=realism_weight, prior_weight=prior_weight)
     for t0, b in refine_plan(n, eng.max_batch):
         z = z_all[t0:t0 + b]                                   # (a contiguous view: Adam updates the returned tensor in place)
-        m, v = torch.zeros_like(z), torch.zeros_like(z)
-        dz = torch.empty_like(z)
-        h = torch.empty(steps, b, dtype=torch.float32, device=dev)
-        for k in range(steps):
-            out = eng.g_latent_objective_grad(z, want_probs=k == 0, dz_out=dz, objective_out=h[k], **w)
-            if k == 0:
-                before[t0:t0 + b] = out[2]
-            eng.op_adam(z, dz, m, v, k + 1, lr=lr, beta1=betas[0], beta2=betas[1])
-        after[t0:t0 + b] = eng.g_latent_objective_grad(z, want_probs=True, dz_out=dz, **w)[2]      # the score AT the returned z
-        hist[:, t0:t0 + b] = h
+
+        def grad(k, z, dz, out):
+            ends = k == 0 or k == steps                        # the scores at z0 and AT the returned z
+            res = eng.g_latent_objective_grad(z, want_probs=ends, dz_out=dz, objective_out=out, **w)
+            if ends:
+                (before if k == 0 else after)[t0:t0 + b] = res[2]
+
+        hist[:, t0:t0 + b] = _descend(eng, z, steps, lr, betas, grad)
     size = eng.image_size
     u8 = np.empty((n, size, size), dtype=np.uint8)
     for t0, b in refine_plan(n, eng.max_batch):
@@ -446,8 +459,8 @@ def project_signatures(generator: Generator, targets_u8, steps: int = 200, lr: f
                        realism_weight: float = 0.0, prior_weight: float = 0.0):
     """Latent vectors whose images reproduce ``targets_u8`` ((N, S, S) uint8, numpy or tensor; a byte stands for
     byte / 127.5 - 1.0): ``steps`` iterations of Adam on z against the per-image loss mean((G(z) - t)^2), every iteration one
-    Engine.g_latent_grad (eval forward + eval backward in HIP) and one Engine.op_adam on (z, dz, m, v), all enqueued without
-    a host synchronisation.  The Generator must be in eval() mode.  Batches: projection_plan; starts: projection_starts.
+    Engine.g_latent_objective_grad (eval forward + eval backward in HIP) and one Engine.op_adam on (z, dz, m, v), all enqueued
+    without a host synchronisation.  The Generator must be in eval() mode.  Batches: projection_plan; starts: projection_starts.
 
     Returns (z (N, latent) fp32 device tensor, recon (N, S, S) uint8 numpy -- generate_uint8 at z --, loss (N,) device tensor:
     the loss AT the returned z, history (steps, N) device tensor: the loss at the start of every iteration).  With
@@ -455,9 +468,8 @@ def project_signatures(generator: Generator, targets_u8, steps: int = 200, lr: f
     a dict with every candidate's ``z`` (R, N, latent), ``loss`` (R, N) and ``history`` (R, steps, N), and the kept ``choice``.
 
     ``realism_weight`` / ``prior_weight`` > 0 add realism_weight * -log D(G(z)) (needs ``discriminator``, brought in by
-    adopt_discriminator) and prior_weight * 0.5 * mean(z^2) to the pixel error: every iteration is then one
-    Engine.g_latent_objective_grad with recon_weight = 1, and loss / history hold that objective.  With the defaults the
-    calls are exactly the ones above."""
+    adopt_discriminator) and prior_weight * 0.5 * mean(z^2) to the pixel error, and loss / history hold that objective.  With
+    the defaults the weights are (1, 0, 0): the Discriminator is not run, and every bit is Engine.g_latent_grad's."""
     if generator.training:
         raise ValueError("project_signatures needs the Generator in eval() mode (running BatchNorm statistics)")
     if steps < 1 or restarts < 1:
@@ -466,16 +478,8 @@ def project_signatures(generator: Generator, targets_u8, steps: int = 200, lr: f
     check_objective_weights(1.0, realism_weight, prior_weight, True)
     if realism_weight > 0 and discriminator is None:
         raise ValueError("realism_weight > 0 needs the Discriminator")
-    guided = realism_weight > 0 or prior_weight > 0
     eng = adopt_discriminator(generator, discriminator) if realism_weight > 0 else generator._require_engine()
     dev, latent, size = eng.device, eng.latent_dim, eng.image_size
-
-    def grad(z, t, dz, out):
-        if guided:
-            eng.g_latent_objective_grad(z, t, 1.0, realism_weight, prior_weight, dz_out=dz, objective_out=out)
-        else:
-            eng.g_latent_grad(z, t, dz_out=dz, loss_out=out)
-
     t_all = torch.as_tensor(np.ascontiguousarray(targets_u8) if isinstance(targets_u8, np.ndarray) else targets_u8)
     if t_all.dtype != torch.uint8 or t_all.dim() != 3 or tuple(t_all.shape[1:]) != (size, size):
         raise ValueError(f"targets_u8 must be uint8 (N, {size}, {size}), got {t_all.dtype} {tuple(t_all.shape)}")
@@ -490,15 +494,9 @@ def project_signatures(generator: Generator, targets_u8, steps: int = 200, lr: f
             starts[r] = projection_starts(n, latent, r, z0, seed).to(dev)
         z = starts[r][t0:t0 + b].contiguous().clone()
         t = t_all[t0:t0 + b]
-        m, v = torch.zeros_like(z), torch.zeros_like(z)
-        dz = torch.empty_like(z)
-        hist = torch.empty(steps, b, dtype=torch.float32, device=dev)
-        for k in range(steps):
-            grad(z, t, dz, hist[k])
-            eng.op_adam(z, dz, m, v, k + 1, lr=lr, beta1=betas[0], beta2=betas[1])
-        grad(z, t, dz, cand_loss[r, t0:t0 + b])                                    # the loss at the z that is returned
+        grad = lambda k, z, dz, out: eng.g_latent_objective_grad(z, t, 1.0, realism_weight, prior_weight, dz_out=dz, objective_out=out)
+        cand_hist[r, :, t0:t0 + b] = _descend(eng, z, steps, lr, betas, grad, cand_loss[r, t0:t0 + b])  # (the loss at the returned z)
         cand_z[r, t0:t0 + b] = z
-        cand_hist[r, :, t0:t0 + b] = hist
     choice = torch.argmin(cand_loss, dim=0)                                        # (plumbing: the first of equal minima)
     pick = torch.arange(n, device=dev)
     z_best, loss_best, hist_best = cand_z[choice, pick], cand_loss[choice, pick], cand_hist[choice, :, pick].t().contiguous()
