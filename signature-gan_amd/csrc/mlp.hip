@@ -16,18 +16,12 @@
 #include <vector>
 
 #include "../../include/siggan_mlp.h"
+#include "host.h"
 #include "ops.h"
 
 using namespace siggan;
 
 extern "C" const char* siggan_last_error(void);
-int siggan_set_error(int code, const char* fmt, ...);     // siggan.hip
-#define MFAIL(...) siggan_set_error(__VA_ARGS__)
-#define MHIP(x)                                                                                     \
-    do {                                                                                            \
-        hipError_t e_ = (x);                                                                        \
-        if (e_ != hipSuccess) return MFAIL(SIGGAN_E_HIP, "%s -> %s (%s:%d)", #x, hipGetErrorString(e_), __FILE__, __LINE__); \
-    } while (0)
 
 namespace {
 
@@ -137,7 +131,6 @@ __global__ void k_bn_eval_relu(const float* __restrict__ y, float* __restrict__ 
     const float sc = gamma[c] / sqrtf(rv[c] + eps);
     a[i] = fmaxf(fmaf(y[i] - rm[c], sc, beta[c]), 0.f);
 }
-inline unsigned blocks(int64_t n) { return (unsigned)((n + 255) / 256); }
 
 }  // namespace
 
@@ -164,16 +157,16 @@ static const float MLP_BN_MOM = 0.1f, MLP_BN_EPS = 1e-5f;
 #define MDG(c, i) ((c)->st.d_grads + (c)->d_off[i])
 
 extern "C" int mlpgan_create(const mlpgan_config* cfg, mlpgan_ctx** out) {
-    if (!cfg || !out) return MFAIL(SIGGAN_E_INVALID, "null argument");
-    if (cfg->n_hidden < 1 || cfg->n_hidden > MLPGAN_MAX_HIDDEN) return MFAIL(SIGGAN_E_INVALID, "n_hidden out of range");
+    if (!cfg || !out) return FAIL(SIGGAN_E_INVALID, "null argument");
+    if (cfg->n_hidden < 1 || cfg->n_hidden > MLPGAN_MAX_HIDDEN) return FAIL(SIGGAN_E_INVALID, "n_hidden out of range");
     if (cfg->image_size < 4 || cfg->image_size > 128 || cfg->latent_dim < 1 || cfg->latent_dim > 4096 || cfg->max_batch < 1 ||
         cfg->max_batch > 4096)
-        return MFAIL(SIGGAN_E_INVALID, "bad geometry");
+        return FAIL(SIGGAN_E_INVALID, "bad geometry");
     for (int i = 0; i < cfg->n_hidden; ++i)
-        if (cfg->hidden[i] < 4 || cfg->hidden[i] > 8192 || (cfg->hidden[i] & 3)) return MFAIL(SIGGAN_E_INVALID, "hidden widths must be multiples of 4 in [4, 8192]");
-    MHIP(hipSetDevice(cfg->device));
+        if (cfg->hidden[i] < 4 || cfg->hidden[i] > 8192 || (cfg->hidden[i] & 3)) return FAIL(SIGGAN_E_INVALID, "hidden widths must be multiples of 4 in [4, 8192]");
+    HIPCHK(hipSetDevice(cfg->device));
     mlpgan_ctx* c = new (std::nothrow) mlpgan_ctx();
-    if (!c) return MFAIL(SIGGAN_E_NOMEM, "out of host memory");
+    if (!c) return FAIL(SIGGAN_E_NOMEM, "out of host memory");
     c->cfg = *cfg; c->nh = cfg->n_hidden; c->P = cfg->image_size * cfg->image_size; c->Bm = cfg->max_batch; c->bound = false;
     c->gdim[0] = cfg->latent_dim;
     for (int i = 0; i < c->nh; ++i) c->gdim[i + 1] = cfg->hidden[i];
@@ -207,13 +200,13 @@ extern "C" int mlpgan_create(const mlpgan_config* cfg, mlpgan_ctx** out) {
         if (pass == 1) c->dev = (DevState*)devp;
         if (pass == 0) {
             hipError_t e = hipMalloc((void**)&base, off);
-            if (e != hipSuccess) { delete c; return MFAIL(SIGGAN_E_NOMEM, "hipMalloc(%zu) -> %s", off, hipGetErrorString(e)); }
+            if (e != hipSuccess) { delete c; return FAIL(SIGGAN_E_NOMEM, "hipMalloc(%zu) -> %s", off, hipGetErrorString(e)); }
             c->ws = base;
             (void)hipMemset(base, 0, off);
         }
     }
     DevState h; memset(&h, 0, sizeof h); h.seed = cfg->seed; h.grad_mul = 1.f;
-    MHIP(hipMemcpy(c->dev, &h, sizeof h, hipMemcpyHostToDevice));
+    HIPCHK(hipMemcpy(c->dev, &h, sizeof h, hipMemcpyHostToDevice));
     *out = c;
     return SIGGAN_OK;
 }
@@ -228,23 +221,23 @@ extern "C" int64_t mlpgan_param_count(const mlpgan_ctx* c, int which) { return !
 extern "C" int32_t mlpgan_param_tensors(const mlpgan_ctx* c, int which) { return !c ? -1 : (int32_t)(which == 0 ? c->g_off.size() : c->d_off.size()); }
 extern "C" int64_t mlpgan_bn_count(const mlpgan_ctx* c) { return c ? c->bn_total : -1; }
 extern "C" int mlpgan_bind(mlpgan_ctx* c, const mlpgan_storage* st) {
-    if (!c || !st) return MFAIL(SIGGAN_E_INVALID, "null argument");
-    if (!st->g_params || !st->d_params || !st->g_bn_running_mean || !st->g_bn_running_var) return MFAIL(SIGGAN_E_INVALID, "mlpgan_bind: parameters and BatchNorm buffers are required");
+    if (!c || !st) return FAIL(SIGGAN_E_INVALID, "null argument");
+    if (!st->g_params || !st->d_params || !st->g_bn_running_mean || !st->g_bn_running_var) return FAIL(SIGGAN_E_INVALID, "mlpgan_bind: parameters and BatchNorm buffers are required");
     c->st = *st; c->bound = true;
     return SIGGAN_OK;
 }
 extern "C" int mlpgan_seed(mlpgan_ctx* c, uint64_t seed, uint64_t offset) {
-    if (!c) return MFAIL(SIGGAN_E_INVALID, "null context");
+    if (!c) return FAIL(SIGGAN_E_INVALID, "null context");
     unsigned long long v[2] = {seed, offset};
-    MHIP(hipMemcpy(c->dev, v, sizeof v, hipMemcpyHostToDevice));
+    HIPCHK(hipMemcpy(c->dev, v, sizeof v, hipMemcpyHostToDevice));
     return SIGGAN_OK;
 }
 static int mcheck(mlpgan_ctx* c, int B) {
-    if (!c) return MFAIL(SIGGAN_E_INVALID, "null context");
-    if (!c->bound) return MFAIL(SIGGAN_E_STATE, "mlpgan_bind has not been called");
-    if (B < 1 || B > c->Bm) return MFAIL(SIGGAN_E_INVALID, "batch %d outside [1, max_batch=%d]", B, c->Bm);
+    if (!c) return FAIL(SIGGAN_E_INVALID, "null context");
+    if (!c->bound) return FAIL(SIGGAN_E_STATE, "mlpgan_bind has not been called");
+    if (B < 1 || B > c->Bm) return FAIL(SIGGAN_E_INVALID, "batch %d outside [1, max_batch=%d]", B, c->Bm);
     hipError_t e = hipSetDevice(c->cfg.device);
-    if (e != hipSuccess) return MFAIL(SIGGAN_E_HIP, "hipSetDevice -> %s", hipGetErrorString(e));
+    if (e != hipSuccess) return FAIL(SIGGAN_E_HIP, "hipSetDevice -> %s", hipGetErrorString(e));
     return SIGGAN_OK;
 }
 
@@ -313,48 +306,48 @@ static void adam(mlpgan_ctx* c, int which, const siggan_hyper* hp, float* mt, hi
 static int need_train_arenas(const mlpgan_ctx* c, int which) {
     const float* a[] = {which ? c->st.d_grads : c->st.g_grads, which ? c->st.d_exp_avg : c->st.g_exp_avg,
                         which ? c->st.d_exp_avg_sq : c->st.g_exp_avg_sq, which ? c->st.d_adam_steps : c->st.g_adam_steps};
-    for (const float* p : a) if (!p) return MFAIL(SIGGAN_E_STATE, "gradient / Adam arenas were not bound");
+    for (const float* p : a) if (!p) return FAIL(SIGGAN_E_STATE, "gradient / Adam arenas were not bound");
     return SIGGAN_OK;
 }
 
 extern "C" int mlpgan_g_forward(mlpgan_ctx* c, const float* z, int32_t B, int32_t training, float* img, void* stream) {
     int rc = mcheck(c, B); if (rc) return rc;
-    if (!z || !img) return MFAIL(SIGGAN_E_INVALID, "null tensor");
+    if (!z || !img) return FAIL(SIGGAN_E_INVALID, "null tensor");
     g_fwd(c, z, B, training != 0, img, (hipStream_t)stream);
-    return hipGetLastError() == hipSuccess ? SIGGAN_OK : MFAIL(SIGGAN_E_HIP, "kernel launch failed");
+    return hipGetLastError() == hipSuccess ? SIGGAN_OK : FAIL(SIGGAN_E_HIP, "kernel launch failed");
 }
 extern "C" int mlpgan_d_forward(mlpgan_ctx* c, const float* x, int32_t B, float* probs, void* stream) {
     int rc = mcheck(c, B); if (rc) return rc;
-    if (!x || !probs) return MFAIL(SIGGAN_E_INVALID, "null tensor");
+    if (!x || !probs) return FAIL(SIGGAN_E_INVALID, "null tensor");
     hipStream_t s = (hipStream_t)stream;
     d_fwd(c, x, B, s);
     launch_bce(c->logits, B, B, 0.f, 0.f, probs, nullptr, nullptr, 0, s);
-    return hipGetLastError() == hipSuccess ? SIGGAN_OK : MFAIL(SIGGAN_E_HIP, "kernel launch failed");
+    return hipGetLastError() == hipSuccess ? SIGGAN_OK : FAIL(SIGGAN_E_HIP, "kernel launch failed");
 }
 extern "C" int mlpgan_d_step(mlpgan_ctx* c, const float* real, int32_t B, const float* z, const siggan_hyper* hp, float* mt, void* stream) {
     int rc = mcheck(c, B); if (rc) return rc;
-    if (!real || !hp) return MFAIL(SIGGAN_E_INVALID, "null argument");
+    if (!real || !hp) return FAIL(SIGGAN_E_INVALID, "null argument");
     if ((rc = need_train_arenas(c, 1))) return rc;
     hipStream_t s = (hipStream_t)stream;
     if (!mt) mt = c->metrics;
     const size_t ib = (size_t)B * c->P * sizeof(float);
-    if (z) MHIP(hipMemcpyAsync(c->z, z, (size_t)B * c->gdim[0] * sizeof(float), hipMemcpyDeviceToDevice, s));
+    if (z) HIPCHK(hipMemcpyAsync(c->z, z, (size_t)B * c->gdim[0] * sizeof(float), hipMemcpyDeviceToDevice, s));
     else launch_randn(c->z, (int64_t)B * c->gdim[0], c->dev, 1, s);
-    MHIP(hipMemcpyAsync(c->x2, real, ib, hipMemcpyDeviceToDevice, s));             // rows [0, B): real
+    HIPCHK(hipMemcpyAsync(c->x2, real, ib, hipMemcpyDeviceToDevice, s));             // rows [0, B): real
     g_fwd(c, c->z, B, false, c->x2 + (size_t)B * c->P, s);                          // rows [B, 2B): G.eval()(z), no grad
     d_fwd(c, c->x2, 2 * B, s);                                                      // no BatchNorm in D: one 2B-row pass
     launch_bce(c->logits, 2 * B, B, hp->label_smoothing, 0.f, c->probs, c->dlogit, mt, 0, s);
     d_bwd(c, c->x2, 2 * B, true, false, s);
     adam(c, 1, hp, mt, s);
-    return hipGetLastError() == hipSuccess ? SIGGAN_OK : MFAIL(SIGGAN_E_HIP, "kernel launch failed");
+    return hipGetLastError() == hipSuccess ? SIGGAN_OK : FAIL(SIGGAN_E_HIP, "kernel launch failed");
 }
 extern "C" int mlpgan_g_step(mlpgan_ctx* c, int32_t B, const float* z, const siggan_hyper* hp, float* mt, void* stream) {
     int rc = mcheck(c, B); if (rc) return rc;
-    if (!hp) return MFAIL(SIGGAN_E_INVALID, "null argument");
+    if (!hp) return FAIL(SIGGAN_E_INVALID, "null argument");
     if ((rc = need_train_arenas(c, 0))) return rc;
     hipStream_t s = (hipStream_t)stream;
     if (!mt) mt = c->metrics;
-    if (z) MHIP(hipMemcpyAsync(c->z, z, (size_t)B * c->gdim[0] * sizeof(float), hipMemcpyDeviceToDevice, s));
+    if (z) HIPCHK(hipMemcpyAsync(c->z, z, (size_t)B * c->gdim[0] * sizeof(float), hipMemcpyDeviceToDevice, s));
     else launch_randn(c->z, (int64_t)B * c->gdim[0], c->dev, 2, s);
     g_fwd(c, c->z, B, true, c->img, s);                                             // G.train(): BatchNorm batch statistics
     d_fwd(c, c->img, B, s);
@@ -374,12 +367,12 @@ extern "C" int mlpgan_g_step(mlpgan_ctx* c, int32_t B, const float* z, const sig
         if (i > 0) gemm(1, c->gda[i], MGP(c, 4 * i), c->gda[i - 1], B, K, N, nullptr, ACT_NONE, 0.f, s);
     }
     adam(c, 0, hp, mt, s);
-    return hipGetLastError() == hipSuccess ? SIGGAN_OK : MFAIL(SIGGAN_E_HIP, "kernel launch failed");
+    return hipGetLastError() == hipSuccess ? SIGGAN_OK : FAIL(SIGGAN_E_HIP, "kernel launch failed");
 }
 extern "C" int mlpgan_op_gemm(int32_t device, int32_t layout, const float* a, const float* b, float* cc, int32_t m, int32_t n, int32_t k,
                               void* stream) {
-    if (!a || !b || !cc || m < 1 || n < 1 || k < 1 || layout < 0 || layout > 2) return MFAIL(SIGGAN_E_INVALID, "bad argument");
-    MHIP(hipSetDevice(device));
+    if (!a || !b || !cc || m < 1 || n < 1 || k < 1 || layout < 0 || layout > 2) return FAIL(SIGGAN_E_INVALID, "bad argument");
+    HIPCHK(hipSetDevice(device));
     gemm(layout, a, b, cc, m, n, k, nullptr, ACT_NONE, 0.f, (hipStream_t)stream);
-    return hipGetLastError() == hipSuccess ? SIGGAN_OK : MFAIL(SIGGAN_E_HIP, "kernel launch failed");
+    return hipGetLastError() == hipSuccess ? SIGGAN_OK : FAIL(SIGGAN_E_HIP, "kernel launch failed");
 }

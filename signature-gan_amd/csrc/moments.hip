@@ -14,14 +14,7 @@
 #include <new>
 
 #include "../../include/siggan_moments.h"
-
-int siggan_set_error(int code, const char* fmt, ...);     // siggan.hip
-#define MFAIL(...) siggan_set_error(__VA_ARGS__)
-#define MHIP(x)                                                                                     \
-    do {                                                                                            \
-        hipError_t e_ = (x);                                                                        \
-        if (e_ != hipSuccess) return MFAIL(SIGGAN_E_HIP, "%s -> %s (%s:%d)", #x, hipGetErrorString(e_), __FILE__, __LINE__); \
-    } while (0)
+#include "host.h"
 
 struct siggan_moments {
     int device, dim;
@@ -31,17 +24,6 @@ struct siggan_moments {
 };
 
 namespace {
-
-// same behaviour as siggan.hip's guard: run on the asked device, put the caller's device back on return
-struct DevGuard {
-    int prev = -1, dev;
-    hipError_t err = hipSuccess;
-    explicit DevGuard(int d) : dev(d) {
-        if (hipGetDevice(&prev) != hipSuccess) prev = -1;
-        if (prev != dev) err = hipSetDevice(dev);
-    }
-    ~DevGuard() { if (prev >= 0 && prev != dev) (void)hipSetDevice(prev); }
-};
 
 typedef double double4_t __attribute__((ext_vector_type(4)));
 constexpr int MT = 16;                                   // tile edge
@@ -90,23 +72,23 @@ __global__ __launch_bounds__(64) void k_moments_update(const float* __restrict__
 }  // namespace
 
 extern "C" int siggan_moments_create(int32_t device, int32_t dim, siggan_moments** out) {
-    if (!out) return MFAIL(SIGGAN_E_INVALID, "siggan_moments_create: null argument");
+    if (!out) return FAIL(SIGGAN_E_INVALID, "siggan_moments_create: null argument");
     *out = nullptr;
     if (dim < 1 || dim > SIGGAN_MOMENTS_MAX_DIM)
-        return MFAIL(SIGGAN_E_INVALID, "siggan_moments_create: dim %d outside [1, %d]", dim, SIGGAN_MOMENTS_MAX_DIM);
-    DevGuard dg(device); MHIP(dg.err);
+        return FAIL(SIGGAN_E_INVALID, "siggan_moments_create: dim %d outside [1, %d]", dim, SIGGAN_MOMENTS_MAX_DIM);
+    DevGuard dg(device); HIPCHK(dg.err);
     siggan_moments* m = new (std::nothrow) siggan_moments();
-    if (!m) return MFAIL(SIGGAN_E_NOMEM, "out of host memory");
+    if (!m) return FAIL(SIGGAN_E_NOMEM, "out of host memory");
     m->device = device; m->dim = dim; m->count = 0; m->sum = nullptr; m->gram = nullptr;
     const size_t bytes = sizeof(double) * (size_t)dim * ((size_t)dim + 1);
     hipError_t e = hipMalloc((void**)&m->sum, bytes);
-    if (e != hipSuccess) { delete m; return MFAIL(SIGGAN_E_NOMEM, "hipMalloc(%zu) -> %s", bytes, hipGetErrorString(e)); }
+    if (e != hipSuccess) { delete m; return FAIL(SIGGAN_E_NOMEM, "hipMalloc(%zu) -> %s", bytes, hipGetErrorString(e)); }
     m->gram = m->sum + dim;
     e = hipMemset(m->sum, 0, bytes);
     if (e == hipSuccess) e = hipDeviceSynchronize();                      // zeroed before any stream's first update
     if (e != hipSuccess) {
         (void)hipFree(m->sum); delete m;
-        return MFAIL(SIGGAN_E_HIP, "siggan_moments_create: clearing the accumulator -> %s", hipGetErrorString(e));
+        return FAIL(SIGGAN_E_HIP, "siggan_moments_create: clearing the accumulator -> %s", hipGetErrorString(e));
     }
     *out = m;
     return SIGGAN_OK;
@@ -122,31 +104,31 @@ extern "C" int siggan_moments_destroy(siggan_moments* m) {
 }
 
 extern "C" int siggan_moments_reset(siggan_moments* m, void* stream) {
-    if (!m) return MFAIL(SIGGAN_E_INVALID, "siggan_moments_reset: null argument");
-    DevGuard dg(m->device); MHIP(dg.err);
-    MHIP(hipMemsetAsync(m->sum, 0, sizeof(double) * (size_t)m->dim * ((size_t)m->dim + 1), (hipStream_t)stream));
+    if (!m) return FAIL(SIGGAN_E_INVALID, "siggan_moments_reset: null argument");
+    DevGuard dg(m->device); HIPCHK(dg.err);
+    HIPCHK(hipMemsetAsync(m->sum, 0, sizeof(double) * (size_t)m->dim * ((size_t)m->dim + 1), (hipStream_t)stream));
     m->count = 0;
     return SIGGAN_OK;
 }
 
 extern "C" int siggan_moments_update(siggan_moments* m, const float* x_dev, int32_t n_rows, void* stream) {
-    if (!m || !x_dev) return MFAIL(SIGGAN_E_INVALID, "siggan_moments_update: null argument");
-    if (n_rows < 1) return MFAIL(SIGGAN_E_INVALID, "siggan_moments_update: n_rows must be >= 1, got %d", n_rows);
-    DevGuard dg(m->device); MHIP(dg.err);
+    if (!m || !x_dev) return FAIL(SIGGAN_E_INVALID, "siggan_moments_update: null argument");
+    if (n_rows < 1) return FAIL(SIGGAN_E_INVALID, "siggan_moments_update: n_rows must be >= 1, got %d", n_rows);
+    DevGuard dg(m->device); HIPCHK(dg.err);
     const int tiles = (m->dim + MT - 1) / MT;
     hipLaunchKernelGGL(k_moments_update, dim3((unsigned)(tiles * (tiles + 1) / 2)), dim3(64), 0, (hipStream_t)stream, x_dev,
                        n_rows, m->dim, tiles, m->sum, m->gram);
-    if (hipGetLastError() != hipSuccess) return MFAIL(SIGGAN_E_HIP, "siggan_moments_update: kernel launch failed");
+    if (hipGetLastError() != hipSuccess) return FAIL(SIGGAN_E_HIP, "siggan_moments_update: kernel launch failed");
     m->count += n_rows;
     return SIGGAN_OK;
 }
 
 extern "C" int siggan_moments_read(siggan_moments* m, double* sum_dev, double* gram_dev, int64_t* count, void* stream) {
-    if (!m) return MFAIL(SIGGAN_E_INVALID, "siggan_moments_read: null argument");
-    DevGuard dg(m->device); MHIP(dg.err);
+    if (!m) return FAIL(SIGGAN_E_INVALID, "siggan_moments_read: null argument");
+    DevGuard dg(m->device); HIPCHK(dg.err);
     const size_t d = (size_t)m->dim;
-    if (sum_dev) MHIP(hipMemcpyAsync(sum_dev, m->sum, sizeof(double) * d, hipMemcpyDeviceToDevice, (hipStream_t)stream));
-    if (gram_dev) MHIP(hipMemcpyAsync(gram_dev, m->gram, sizeof(double) * d * d, hipMemcpyDeviceToDevice, (hipStream_t)stream));
+    if (sum_dev) HIPCHK(hipMemcpyAsync(sum_dev, m->sum, sizeof(double) * d, hipMemcpyDeviceToDevice, (hipStream_t)stream));
+    if (gram_dev) HIPCHK(hipMemcpyAsync(gram_dev, m->gram, sizeof(double) * d * d, hipMemcpyDeviceToDevice, (hipStream_t)stream));
     if (count) *count = m->count;
     return SIGGAN_OK;
 }

@@ -25,27 +25,9 @@
 #include <stdint.h>
 
 #include "../../include/siggan_neighbors.h"
-
-int siggan_set_error(int code, const char* fmt, ...);     // siggan.hip
-#define NFAIL(...) siggan_set_error(__VA_ARGS__)
-#define NHIP(x)                                                                                     \
-    do {                                                                                            \
-        hipError_t e_ = (x);                                                                        \
-        if (e_ != hipSuccess) return NFAIL(SIGGAN_E_HIP, "%s -> %s (%s:%d)", #x, hipGetErrorString(e_), __FILE__, __LINE__); \
-    } while (0)
+#include "host.h"
 
 namespace {
-
-// same behaviour as siggan.hip's guard: run on the asked device, put the caller's device back on return
-struct DevGuard {
-    int prev = -1, dev;
-    hipError_t err = hipSuccess;
-    explicit DevGuard(int d) : dev(d) {
-        if (hipGetDevice(&prev) != hipSuccess) prev = -1;
-        if (prev != dev) err = hipSetDevice(dev);
-    }
-    ~DevGuard() { if (prev >= 0 && prev != dev) (void)hipSetDevice(prev); }
-};
 
 typedef double double4_t __attribute__((ext_vector_type(4)));
 constexpr int NT = 16;                                   // tile edge: query rows per workgroup, reference rows per tile
@@ -220,9 +202,9 @@ void launch(bool vec, hipStream_t st, const float* q, int nq, const float* r, in
 }
 
 int check_sets(const char* who, const float* q, int nq, const float* r, int nr, int dim) {
-    if (!q || !r) return NFAIL(SIGGAN_E_INVALID, "%s: null tensor", who);
-    if (nq < 1 || nr < 1) return NFAIL(SIGGAN_E_INVALID, "%s: nq = %d and nr = %d must be >= 1", who, nq, nr);
-    if (dim < 1 || dim > SIGGAN_KNN_MAX_DIM) return NFAIL(SIGGAN_E_INVALID, "%s: dim %d outside [1, %d]", who, dim, SIGGAN_KNN_MAX_DIM);
+    if (!q || !r) return FAIL(SIGGAN_E_INVALID, "%s: null tensor", who);
+    if (nq < 1 || nr < 1) return FAIL(SIGGAN_E_INVALID, "%s: nq = %d and nr = %d must be >= 1", who, nq, nr);
+    if (dim < 1 || dim > SIGGAN_KNN_MAX_DIM) return FAIL(SIGGAN_E_INVALID, "%s: dim %d outside [1, %d]", who, dim, SIGGAN_KNN_MAX_DIM);
     return SIGGAN_OK;
 }
 
@@ -235,11 +217,11 @@ bool rows_allow_16_byte_loads(const float* q, const float* r, int dim) {
 extern "C" int siggan_knn(int32_t device, const float* q_dev, int32_t nq, const float* r_dev, int32_t nr, int32_t dim, int32_t k,
                           int32_t exclude_diagonal, double* dist2_dev, int32_t* index_dev, void* stream) {
     if (int rc = check_sets("siggan_knn", q_dev, nq, r_dev, nr, dim)) return rc;
-    if (!dist2_dev && !index_dev) return NFAIL(SIGGAN_E_INVALID, "siggan_knn: null output: dist2_dev and index_dev are both NULL");
-    if (k < 1 || k > SIGGAN_KNN_MAX_K) return NFAIL(SIGGAN_E_INVALID, "siggan_knn: k = %d outside [1, %d]", k, SIGGAN_KNN_MAX_K);
+    if (!dist2_dev && !index_dev) return FAIL(SIGGAN_E_INVALID, "siggan_knn: null output: dist2_dev and index_dev are both NULL");
+    if (k < 1 || k > SIGGAN_KNN_MAX_K) return FAIL(SIGGAN_E_INVALID, "siggan_knn: k = %d outside [1, %d]", k, SIGGAN_KNN_MAX_K);
     const int avail = nr - (exclude_diagonal ? 1 : 0);
-    if (k > avail) return NFAIL(SIGGAN_E_INVALID, "siggan_knn: k = %d exceeds the %d reference rows a query may take", k, avail);
-    DevGuard dg(device); NHIP(dg.err);
+    if (k > avail) return FAIL(SIGGAN_E_INVALID, "siggan_knn: k = %d exceeds the %d reference rows a query may take", k, avail);
+    DevGuard dg(device); HIPCHK(dg.err);
     const bool vec = rows_allow_16_byte_loads(q_dev, r_dev, dim);
     const hipStream_t st = (hipStream_t)stream;
     const int excl = exclude_diagonal ? 1 : 0;
@@ -247,17 +229,17 @@ extern "C" int siggan_knn(int32_t device, const float* q_dev, int32_t nq, const 
     else if (k <= 4) launch<4, false>(vec, st, q_dev, nq, r_dev, nr, dim, k, excl, dist2_dev, index_dev, nullptr, nullptr);
     else if (k <= 8) launch<8, false>(vec, st, q_dev, nq, r_dev, nr, dim, k, excl, dist2_dev, index_dev, nullptr, nullptr);
     else             launch<16, false>(vec, st, q_dev, nq, r_dev, nr, dim, k, excl, dist2_dev, index_dev, nullptr, nullptr);
-    NHIP(hipGetLastError());
+    HIPCHK(hipGetLastError());
     return SIGGAN_OK;
 }
 
 extern "C" int siggan_ball_count(int32_t device, const float* q_dev, int32_t nq, const float* r_dev, int32_t nr, int32_t dim,
                                  const double* radius2_dev, int32_t* count_dev, void* stream) {
     if (int rc = check_sets("siggan_ball_count", q_dev, nq, r_dev, nr, dim)) return rc;
-    if (!radius2_dev || !count_dev) return NFAIL(SIGGAN_E_INVALID, "siggan_ball_count: null tensor");
-    DevGuard dg(device); NHIP(dg.err);
+    if (!radius2_dev || !count_dev) return FAIL(SIGGAN_E_INVALID, "siggan_ball_count: null tensor");
+    DevGuard dg(device); HIPCHK(dg.err);
     launch<1, true>(rows_allow_16_byte_loads(q_dev, r_dev, dim), (hipStream_t)stream, q_dev, nq, r_dev, nr, dim, 0, 0, nullptr,
                     nullptr, radius2_dev, count_dev);
-    NHIP(hipGetLastError());
+    HIPCHK(hipGetLastError());
     return SIGGAN_OK;
 }

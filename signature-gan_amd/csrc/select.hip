@@ -12,27 +12,9 @@
 #include <stdint.h>
 
 #include "../../include/siggan_select.h"
-
-int siggan_set_error(int code, const char* fmt, ...);     // siggan.hip
-#define SFAIL(...) siggan_set_error(__VA_ARGS__)
-#define SHIP(x)                                                                                     \
-    do {                                                                                            \
-        hipError_t e_ = (x);                                                                        \
-        if (e_ != hipSuccess) return SFAIL(SIGGAN_E_HIP, "%s -> %s (%s:%d)", #x, hipGetErrorString(e_), __FILE__, __LINE__); \
-    } while (0)
+#include "host.h"
 
 namespace {
-
-// same behaviour as siggan.hip's guard: run on the asked device, put the caller's device back on return
-struct DevGuard {
-    int prev = -1, dev;
-    hipError_t err = hipSuccess;
-    explicit DevGuard(int d) : dev(d) {
-        if (hipGetDevice(&prev) != hipSuccess) prev = -1;
-        if (prev != dev) err = hipSetDevice(dev);
-    }
-    ~DevGuard() { if (prev >= 0 && prev != dev) (void)hipSetDevice(prev); }
-};
 
 constexpr int TILE = 2048;                               // keys per LDS tile (8 KiB)
 
@@ -83,28 +65,28 @@ __global__ __launch_bounds__(256) void k_gather_u8(const unsigned* __restrict__ 
 }  // namespace
 
 extern "C" int siggan_select_topk(int32_t device, const float* scores_dev, int32_t m, int32_t k, int32_t* index_dev, void* stream) {
-    if (!scores_dev || !index_dev) return SFAIL(SIGGAN_E_INVALID, "null tensor");
-    if (m < 1 || m > SIGGAN_SELECT_MAX) return SFAIL(SIGGAN_E_INVALID, "m = %d outside [1, %d]", m, SIGGAN_SELECT_MAX);
-    if (k < 1 || k > m) return SFAIL(SIGGAN_E_INVALID, "k = %d outside [1, m = %d]", k, m);
-    DevGuard dg(device); SHIP(dg.err);
+    if (!scores_dev || !index_dev) return FAIL(SIGGAN_E_INVALID, "null tensor");
+    if (m < 1 || m > SIGGAN_SELECT_MAX) return FAIL(SIGGAN_E_INVALID, "m = %d outside [1, %d]", m, SIGGAN_SELECT_MAX);
+    if (k < 1 || k > m) return FAIL(SIGGAN_E_INVALID, "k = %d outside [1, m = %d]", k, m);
+    DevGuard dg(device); HIPCHK(dg.err);
     hipLaunchKernelGGL(k_select_rank, dim3((unsigned)((m + 255) / 256)), dim3(256), 0, (hipStream_t)stream, scores_dev, m, k, index_dev);
-    SHIP(hipGetLastError());
+    HIPCHK(hipGetLastError());
     return SIGGAN_OK;
 }
 
 extern "C" int siggan_gather_u8(int32_t device, const uint8_t* pool_dev, int32_t m, int64_t pixels, const int32_t* index_dev,
                                 int32_t k, int32_t binarize, uint8_t* out_dev, void* stream) {
-    if (!pool_dev || !index_dev || !out_dev) return SFAIL(SIGGAN_E_INVALID, "null tensor");
-    if (m < 1 || k < 1) return SFAIL(SIGGAN_E_INVALID, "bad pool size m = %d / selection size k = %d", m, k);
-    if (pixels < 4 || (pixels & 3)) return SFAIL(SIGGAN_E_INVALID, "pixels must be a positive multiple of 4, got %lld", (long long)pixels);
-    if (binarize < -1 || binarize > 255) return SFAIL(SIGGAN_E_INVALID, "binarize must be -1 (off) or a byte value, got %d", binarize);
+    if (!pool_dev || !index_dev || !out_dev) return FAIL(SIGGAN_E_INVALID, "null tensor");
+    if (m < 1 || k < 1) return FAIL(SIGGAN_E_INVALID, "bad pool size m = %d / selection size k = %d", m, k);
+    if (pixels < 4 || (pixels & 3)) return FAIL(SIGGAN_E_INVALID, "pixels must be a positive multiple of 4, got %lld", (long long)pixels);
+    if (binarize < -1 || binarize > 255) return FAIL(SIGGAN_E_INVALID, "binarize must be -1 (off) or a byte value, got %d", binarize);
     if ((reinterpret_cast<uintptr_t>(pool_dev) | reinterpret_cast<uintptr_t>(out_dev)) & 3)
-        return SFAIL(SIGGAN_E_INVALID, "pool_dev and out_dev must be 4-byte aligned");
+        return FAIL(SIGGAN_E_INVALID, "pool_dev and out_dev must be 4-byte aligned");
     const int64_t words = pixels >> 2, chunks = (words + 255) / 256;
-    if (words > INT32_MAX || (int64_t)k * chunks > INT32_MAX) return SFAIL(SIGGAN_E_INVALID, "selection too large for one launch");
-    DevGuard dg(device); SHIP(dg.err);
+    if (words > INT32_MAX || (int64_t)k * chunks > INT32_MAX) return FAIL(SIGGAN_E_INVALID, "selection too large for one launch");
+    DevGuard dg(device); HIPCHK(dg.err);
     hipLaunchKernelGGL(k_gather_u8, dim3((unsigned)((int64_t)k * chunks)), dim3(256), 0, (hipStream_t)stream, (const unsigned*)pool_dev, m,
                        (int)words, (int)chunks, index_dev, binarize, (unsigned*)out_dev);
-    SHIP(hipGetLastError());
+    HIPCHK(hipGetLastError());
     return SIGGAN_OK;
 }

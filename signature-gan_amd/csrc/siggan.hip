@@ -16,6 +16,7 @@
 
 #include "../../include/siggan.h"
 #include "gconv.h"
+#include "host.h"
 #include "ops.h"
 
 using namespace siggan;
@@ -28,7 +29,7 @@ static int fail(int code, const char* fmt, ...) {
     va_end(ap);
     return code;
 }
-// (mlp.hip reports through the same thread-local message)
+// (every other file reports through the same thread-local message, host.h)
 int siggan_set_error(int code, const char* fmt, ...) {
     va_list ap;
     va_start(ap, fmt);
@@ -36,28 +37,11 @@ int siggan_set_error(int code, const char* fmt, ...) {
     va_end(ap);
     return code;
 }
-#define HIPCHK(x)                                                                                   \
-    do {                                                                                            \
-        hipError_t e_ = (x);                                                                        \
-        if (e_ != hipSuccess) return fail(SIGGAN_E_HIP, "%s -> %s (%s:%d)", #x, hipGetErrorString(e_), __FILE__, __LINE__); \
-    } while (0)
 #define LAUNCHCHK()                                                                                 \
     do {                                                                                            \
         hipError_t e_ = hipGetLastError();                                                          \
         if (e_ != hipSuccess) return fail(SIGGAN_E_HIP, "kernel launch -> %s (%s:%d)", hipGetErrorString(e_), __FILE__, __LINE__); \
     } while (0)
-
-// Entry points run on the context's device and put the caller's current device back on return (a process whose
-// torch current device is another GPU must not find it switched behind its back).
-struct DevGuard {
-    int prev = -1, dev;
-    hipError_t err = hipSuccess;
-    explicit DevGuard(int d) : dev(d) {
-        if (hipGetDevice(&prev) != hipSuccess) prev = -1;
-        if (prev != dev) err = hipSetDevice(dev);
-    }
-    ~DevGuard() { if (prev >= 0 && prev != dev) (void)hipSetDevice(prev); }
-};
 
 static const float BN_MOMENTUM = 0.1f, BN_EPS = 1e-5f;   // nn.BatchNorm defaults (generator_vanilla_gan.py:58,126)
 static const int MAXL = 6;

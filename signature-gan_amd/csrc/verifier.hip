@@ -20,34 +20,12 @@
 #include <new>
 
 #include "../../include/siggan_verifier.h"
-#include "act.h"
+#include "host.h"
+#include "verifier_parts.h"
 
 using namespace siggan;
 
-int siggan_set_error(int code, const char* fmt, ...);     // siggan.hip
-#define VFAIL(...) siggan_set_error(__VA_ARGS__)
-#define VHIP(x)                                                                                     \
-    do {                                                                                            \
-        hipError_t e_ = (x);                                                                        \
-        if (e_ != hipSuccess) return VFAIL(SIGGAN_E_HIP, "%s -> %s (%s:%d)", #x, hipGetErrorString(e_), __FILE__, __LINE__); \
-    } while (0)
-
 namespace {
-
-// same behaviour as siggan.hip's guard: run on the context's device, put the caller's device back on return
-struct DevGuard {
-    int prev = -1, dev;
-    hipError_t err = hipSuccess;
-    explicit DevGuard(int d) : dev(d) {
-        if (hipGetDevice(&prev) != hipSuccess) prev = -1;
-        if (prev != dev) err = hipSetDevice(dev);
-    }
-    ~DevGuard() { if (prev >= 0 && prev != dev) (void)hipSetDevice(prev); }
-};
-
-constexpr int VS = 64;                 // image size (fixed by fc1)
-constexpr int VFC1_K = 8192, VFC1_N = 512, VFC1_SPLIT = 16, VFC1_KS = VFC1_K / VFC1_SPLIT;
-constexpr int VHID = 64;               // classifier hidden width
 
 // ---------------------------------------------------------------- bind-time packing
 // scale = gamma / sqrt(var + eps); shift = (conv_bias - mean) * scale + beta
@@ -77,14 +55,6 @@ __global__ void k_vpack_fc1(const float* __restrict__ w, float* __restrict__ wp)
 }
 
 // ---------------------------------------------------------------- conv1 + affine + ReLU + pool
-template <bool U8>
-__device__ __forceinline__ float vload(const void* img, int i) {
-    if (U8) {
-        const float v = (float)((const uint8_t*)img)[i] / 255.0f;     // ToTensor
-        return (v - 0.5f) / 0.5f;                                      // Normalize([0.5], [0.5])
-    }
-    return ((const float*)img)[i];
-}
 // thread = (pooled pixel, 8 output channels); block = 64 pooled pixels x 4 channel groups.  Images [0, nsplit) come from
 // x1, the rest from x2.  out: (N, 32, 32, 32) NHWC.
 template <bool U8>
@@ -98,9 +68,7 @@ __global__ __launch_bounds__(256) void k_vconv1(const void* __restrict__ x1, con
     const int cg = tid & 3;
     const int64_t P = (int64_t)blockIdx.x * 64 + (tid >> 2);
     const int n = (int)(P >> 10), ph = (int)(P >> 5) & 31, pw = (int)P & 31;
-    const size_t esz = U8 ? 1 : 4;
-    const void* img = n < nsplit ? (const void*)((const char*)x1 + (size_t)n * VS * VS * esz)
-                                 : (const void*)((const char*)x2 + (size_t)(n - nsplit) * VS * VS * esz);
+    const void* img = vimage<U8>(x1, x2, nsplit, n);
     float patch[6][6];
 #pragma unroll
     for (int r = 0; r < 6; ++r)
@@ -140,68 +108,18 @@ __global__ __launch_bounds__(256) void k_vconv1(const void* __restrict__ x1, con
 }
 
 // ---------------------------------------------------------------- conv2 / conv3: implicit GEMM + affine + ReLU + pool
-// x: (N, H, H, CI) NHWC; wp: [CO][KS*KS*CI]; out: (N, H/2, H/2, CO).  Block tile 128 (M) x 64 (N), K-tiles of 32 (one tap,
-// or half of one at CI = 64) staged k-major in LDS; wave w owns rows [32w, 32w+32) x all 64 columns (two accumulators that
-// share the A operand).  M = N * H * H is a multiple of 256, CO of 64: no ragged tiles.
+// x: (N, H, H, CI) NHWC; wp: [CO][KS*KS*CI]; out: (N, H/2, H/2, CO).  conv_tile's 128 x 64 block tile over rows in pooling-window
+// order (PoolRows): registers 4g..4g+3 of an accumulator are one window, so the max is taken in registers.
 template <int KS, int CI, int CO, int H>
 __global__ __launch_bounds__(256) void k_vconv(const float* __restrict__ x, const float* __restrict__ wp,
                                                const float* __restrict__ sc, const float* __restrict__ sh,
                                                float* __restrict__ out) {
-    constexpr int BM = 128, BN = 64, BK = 32, LDA = BM + 4, LDB = BN + 4, PAD = KS / 2, K = KS * KS * CI, HP = H / 2;
-    static_assert(CI % BK == 0 && CO % BN == 0 && (H * H) % BM == 0, "tile geometry");
-    __shared__ float sA[BK][LDA], sB[BK][LDB];
-    const int tid = threadIdx.x, lane = tid & 63, wave = tid >> 6, li = lane & 31, lh = lane >> 5;
+    constexpr int BM = 128, BN = 64;
+    const int lane = threadIdx.x & 63, wave = threadIdx.x >> 6, li = lane & 31, lh = lane >> 5;
     const int64_t m0 = (int64_t)blockIdx.x * BM;
     const int n0 = blockIdx.y * BN;
-    // staging: thread -> (row, 16-float half) of A, (row, 8-float quarter) of B; consecutive lanes write consecutive LDS words
-    const int ar = tid & 127, ah = tid >> 7;
-    const int64_t m = m0 + ar, q = m >> 2;
-    const int sub = (int)(m & 3), pw = (int)(q % HP), ph = (int)((q / HP) % HP);
-    const int64_t n = q / (HP * HP);
-    const int y = 2 * ph + (sub >> 1), xx = 2 * pw + (sub & 1);
-    const float* xim = x + (size_t)n * H * H * CI + ah * 16;
-    const int br = tid & 63, bq = tid >> 6;
-    const float* wrow = wp + (size_t)(n0 + br) * K + bq * 8;
-
-    f32x4 ra[4], rb[2];
-    auto fetch = [&](int k0) {
-        const int tap = k0 / CI, ci0 = k0 % CI;
-        const int iy = y + tap / KS - PAD, ix = xx + tap % KS - PAD;
-        if (iy >= 0 && iy < H && ix >= 0 && ix < H) {                  // out-of-image taps read zeros
-            const float* src = xim + ((size_t)iy * H + ix) * CI + ci0;
-#pragma unroll
-            for (int j = 0; j < 4; ++j) ra[j] = *reinterpret_cast<const f32x4*>(src + 4 * j);
-        } else {
-#pragma unroll
-            for (int j = 0; j < 4; ++j) ra[j] = f32x4{0.f, 0.f, 0.f, 0.f};
-        }
-        rb[0] = *reinterpret_cast<const f32x4*>(wrow + k0);
-        rb[1] = *reinterpret_cast<const f32x4*>(wrow + k0 + 4);
-    };
     f32x16 acc[2];
-#pragma unroll
-    for (int r = 0; r < 16; ++r) { acc[0][r] = 0.f; acc[1][r] = 0.f; }
-    fetch(0);
-    for (int k0 = 0; k0 < K; k0 += BK) {
-#pragma unroll
-        for (int j = 0; j < 4; ++j)
-#pragma unroll
-            for (int e = 0; e < 4; ++e) sA[ah * 16 + 4 * j + e][ar] = ra[j][e];
-#pragma unroll
-        for (int j = 0; j < 2; ++j)
-#pragma unroll
-            for (int e = 0; e < 4; ++e) sB[bq * 8 + 4 * j + e][br] = rb[j][e];
-        __syncthreads();
-        if (k0 + BK < K) fetch(k0 + BK);                               // next tile's loads fly under this tile's MFMAs
-#pragma unroll
-        for (int s = 0; s < BK / 2; ++s) {
-            const float a = sA[2 * s + lh][wave * 32 + li];
-            acc[0] = __builtin_amdgcn_mfma_f32_32x32x2f32(a, sB[2 * s + lh][li], acc[0], 0, 0, 0);
-            acc[1] = __builtin_amdgcn_mfma_f32_32x32x2f32(a, sB[2 * s + lh][32 + li], acc[1], 0, 0, 0);
-        }
-        __syncthreads();
-    }
-    // C/D: row = (r & 3) + 8 * (r >> 2) + 4 * lh, col = li.  Registers 4g..4g+3 are one pooling window.
+    conv_tile<KS, CI, CO, H, BN, PoolRows>(x, wp, m0, n0, acc);
 #pragma unroll
     for (int j = 0; j < 2; ++j) {
         const int co = n0 + 32 * j + li;
@@ -268,11 +186,6 @@ __global__ __launch_bounds__(256) void k_vfc1(const float* __restrict__ A, const
 }
 
 // ---------------------------------------------------------------- tail: fc1 finish, fc2, L2 normalise (one block per row)
-__device__ __forceinline__ float wave_sum(float v) {
-#pragma unroll
-    for (int o = 32; o > 0; o >>= 1) v += __shfl_xor(v, o, 64);
-    return v;
-}
 // rows [0, nsplit) are written to out1, the rest to out2 (row - nsplit)
 __global__ __launch_bounds__(256) void k_vtail(const float* __restrict__ part, int M, const float* __restrict__ b1,
                                                const float* __restrict__ w2 /* (E, 512) */, const float* __restrict__ b2, int E,
@@ -280,31 +193,13 @@ __global__ __launch_bounds__(256) void k_vtail(const float* __restrict__ part, i
                                                int nsplit) {
     extern __shared__ float se[];                      // E embedding entries
     __shared__ float sh1[VFC1_N];
-    __shared__ float sred[4];
-    const int row = blockIdx.x, tid = threadIdx.x, lane = tid & 63, wave = tid >> 6;
+    const int row = blockIdx.x, tid = threadIdx.x;
     for (int j = tid; j < VFC1_N; j += 256) {
-        float a = 0.f;
-        for (int z = 0; z < VFC1_SPLIT; ++z) a += part[((size_t)z * M + row) * VFC1_N + j];
-        a = fmaxf(a + b1[j], 0.f);
+        const float a = fc1_finish(part, M, row, j, b1);
         sh1[j] = a;
         fc1[(size_t)row * VFC1_N + j] = a;
     }
-    __syncthreads();
-    for (int o = wave; o < E; o += 4) {                // one wave per output: 8 products per lane, then a butterfly
-        const float* wr = w2 + (size_t)o * VFC1_N;
-        float a = 0.f;
-#pragma unroll
-        for (int i = 0; i < VFC1_N / 64; ++i) a = fmaf(sh1[lane + 64 * i], wr[lane + 64 * i], a);
-        a = wave_sum(a);
-        if (lane == 0) se[o] = a + b2[o];
-    }
-    __syncthreads();
-    float ss = 0.f;
-    for (int o = tid; o < E; o += 256) ss = fmaf(se[o], se[o], ss);
-    ss = wave_sum(ss);
-    if (lane == 0) sred[wave] = ss;
-    __syncthreads();
-    const float nrm = fmaxf(sqrtf((sred[0] + sred[1]) + (sred[2] + sred[3])), 1e-12f);     // F.normalize's eps
+    const float nrm = fc2_norm(sh1, w2, b2, E, se);
     float* o = row < nsplit ? out1 + (size_t)row * E : out2 + (size_t)(row - nsplit) * E;
     for (int i = tid; i < E; i += 256) o[i] = se[i] / nrm;
 }
@@ -326,16 +221,6 @@ __global__ __launch_bounds__(64) void k_vhead(const float* __restrict__ e1, cons
     if (j == 0) score[p] = 1.0f / (1.0f + expf(-logit));
 }
 
-// ---------------------------------------------------------------- debug: NHWC -> NCHW
-__global__ void k_vnchw(const float* __restrict__ in, float* __restrict__ out, int64_t total, int C, int HW) {
-    const int64_t i = (int64_t)blockIdx.x * blockDim.x + threadIdx.x;     // index into out (n, c, hw)
-    if (i >= total) return;
-    const int hw = (int)(i % HW), c = (int)((i / HW) % C);
-    const int64_t n = i / ((int64_t)HW * C);
-    out[i] = in[(n * HW + hw) * C + c];
-}
-inline unsigned blocks(int64_t n) { return (unsigned)((n + 255) / 256); }
-
 }  // namespace
 
 struct siggan_verifier {
@@ -350,14 +235,14 @@ struct siggan_verifier {
 };
 
 extern "C" int siggan_verifier_create(int32_t device, int32_t E, int32_t max_images, siggan_verifier** out) {
-    if (!out) return VFAIL(SIGGAN_E_ARG, "siggan_verifier_create: null argument");
+    if (!out) return FAIL(SIGGAN_E_ARG, "siggan_verifier_create: null argument");
     *out = nullptr;
     if (E < 1 || E > SIGGAN_VERIFIER_MAX_EMBEDDING)
-        return VFAIL(SIGGAN_E_ARG, "embedding_dim %d outside [1, %d]", E, SIGGAN_VERIFIER_MAX_EMBEDDING);
-    if (max_images < 1 || max_images > 8192) return VFAIL(SIGGAN_E_ARG, "max_images %d outside [1, 8192]", max_images);
-    DevGuard dg(device); VHIP(dg.err);
+        return FAIL(SIGGAN_E_ARG, "embedding_dim %d outside [1, %d]", E, SIGGAN_VERIFIER_MAX_EMBEDDING);
+    if (max_images < 1 || max_images > 8192) return FAIL(SIGGAN_E_ARG, "max_images %d outside [1, 8192]", max_images);
+    DevGuard dg(device); HIPCHK(dg.err);
     siggan_verifier* v = new (std::nothrow) siggan_verifier();
-    if (!v) return VFAIL(SIGGAN_E_NOMEM, "out of host memory");
+    if (!v) return FAIL(SIGGAN_E_NOMEM, "out of host memory");
     v->device = device; v->E = E; v->Nmax = max_images; v->bound = false; v->last_n = 0; v->ws = nullptr;
     const int64_t N = max_images;
     size_t off = 0; char* base = nullptr;
@@ -374,7 +259,7 @@ extern "C" int siggan_verifier_create(int32_t device, int32_t E, int32_t max_ima
         carve(&v->part, N * VFC1_SPLIT * VFC1_N); carve(&v->fc1, N * VFC1_N); carve(&v->emb, N * E);
         if (pass == 0) {
             hipError_t e = hipMalloc((void**)&base, off);
-            if (e != hipSuccess) { delete v; return VFAIL(SIGGAN_E_NOMEM, "hipMalloc(%zu) -> %s", off, hipGetErrorString(e)); }
+            if (e != hipSuccess) { delete v; return FAIL(SIGGAN_E_NOMEM, "hipMalloc(%zu) -> %s", off, hipGetErrorString(e)); }
             v->ws = base;
         }
     }
@@ -392,23 +277,23 @@ extern "C" int siggan_verifier_destroy(siggan_verifier* v) {
 }
 
 extern "C" int siggan_verifier_bind(siggan_verifier* v, const siggan_verifier_weights* w, void* stream) {
-    if (!v || !w) return VFAIL(SIGGAN_E_ARG, "siggan_verifier_bind: null argument");
+    if (!v || !w) return FAIL(SIGGAN_E_ARG, "siggan_verifier_bind: null argument");
     const float* const* p = reinterpret_cast<const float* const*>(w);
     for (int i = 0; i < 26; ++i)
-        if (!p[i]) return VFAIL(SIGGAN_E_ARG, "siggan_verifier_bind: weight pointer %d is null", i);
-    if (!(w->bn_eps > 0.f)) return VFAIL(SIGGAN_E_ARG, "siggan_verifier_bind: bn_eps must be positive");
-    DevGuard dg(v->device); VHIP(dg.err);
+        if (!p[i]) return FAIL(SIGGAN_E_ARG, "siggan_verifier_bind: weight pointer %d is null", i);
+    if (!(w->bn_eps > 0.f)) return FAIL(SIGGAN_E_ARG, "siggan_verifier_bind: bn_eps must be positive");
+    DevGuard dg(v->device); HIPCHK(dg.err);
     hipStream_t s = (hipStream_t)stream;
     const int E = v->E;
     auto copy = [&](float* dst, const float* src, int64_t n) { return hipMemcpyAsync(dst, src, (size_t)n * 4, hipMemcpyDeviceToDevice, s); };
-    VHIP(copy(v->w1, w->conv1_weight, 800));
-    VHIP(copy(v->bfc1, w->fc1_bias, VFC1_N));
-    VHIP(copy(v->wfc2, w->fc2_weight, (int64_t)E * VFC1_N));
-    VHIP(copy(v->bfc2, w->fc2_bias, E));
-    VHIP(copy(v->wc0, w->cls0_weight, (int64_t)VHID * E));
-    VHIP(copy(v->bc0, w->cls0_bias, VHID));
-    VHIP(copy(v->wc3, w->cls3_weight, VHID));
-    VHIP(copy(v->bc3, w->cls3_bias, 1));
+    HIPCHK(copy(v->w1, w->conv1_weight, 800));
+    HIPCHK(copy(v->bfc1, w->fc1_bias, VFC1_N));
+    HIPCHK(copy(v->wfc2, w->fc2_weight, (int64_t)E * VFC1_N));
+    HIPCHK(copy(v->bfc2, w->fc2_bias, E));
+    HIPCHK(copy(v->wc0, w->cls0_weight, (int64_t)VHID * E));
+    HIPCHK(copy(v->bc0, w->cls0_bias, VHID));
+    HIPCHK(copy(v->wc3, w->cls3_weight, VHID));
+    HIPCHK(copy(v->bc3, w->cls3_bias, 1));
     hipLaunchKernelGGL(k_vfold, dim3(1), dim3(128), 0, s, w->conv1_bias, w->bn1_weight, w->bn1_bias, w->bn1_running_mean,
                        w->bn1_running_var, w->bn_eps, v->sc1, v->sh1, 32);
     hipLaunchKernelGGL(k_vfold, dim3(1), dim3(128), 0, s, w->conv2_bias, w->bn2_weight, w->bn2_bias, w->bn2_running_mean,
@@ -418,7 +303,7 @@ extern "C" int siggan_verifier_bind(siggan_verifier* v, const siggan_verifier_we
     hipLaunchKernelGGL(k_vpack_conv, dim3(blocks(64 * 32 * 25)), dim3(256), 0, s, w->conv2_weight, v->wp2, 64, 32, 25);
     hipLaunchKernelGGL(k_vpack_conv, dim3(blocks(128 * 64 * 9)), dim3(256), 0, s, w->conv3_weight, v->wp3, 128, 64, 9);
     hipLaunchKernelGGL(k_vpack_fc1, dim3(blocks((int64_t)VFC1_N * VFC1_K)), dim3(256), 0, s, w->fc1_weight, v->wfc1);
-    if (hipGetLastError() != hipSuccess) return VFAIL(SIGGAN_E_HIP, "siggan_verifier_bind: kernel launch failed");
+    if (hipGetLastError() != hipSuccess) return FAIL(SIGGAN_E_HIP, "siggan_verifier_bind: kernel launch failed");
     v->bound = true;
     return SIGGAN_OK;
 }
@@ -436,43 +321,43 @@ static int encode(siggan_verifier* v, const void* x1, const void* x2, int fmt, i
     hipLaunchKernelGGL(k_vtail, dim3(n), dim3(256), (size_t)v->E * 4, s, v->part, n, v->bfc1, v->wfc2, v->bfc2, v->E, v->fc1, out1,
                        out2, nsplit);
     v->last_n = n;
-    return hipGetLastError() == hipSuccess ? SIGGAN_OK : VFAIL(SIGGAN_E_HIP, "verifier encoder: kernel launch failed");
+    return hipGetLastError() == hipSuccess ? SIGGAN_OK : FAIL(SIGGAN_E_HIP, "verifier encoder: kernel launch failed");
 }
 static int head(siggan_verifier* v, const float* e1, const float* e2, int np, float* score, hipStream_t s) {
     hipLaunchKernelGGL(k_vhead, dim3(np), dim3(VHID), (size_t)v->E * 4, s, e1, e2, v->E, v->wc0, v->bc0, v->wc3, v->bc3, score);
-    return hipGetLastError() == hipSuccess ? SIGGAN_OK : VFAIL(SIGGAN_E_HIP, "verifier head: kernel launch failed");
+    return hipGetLastError() == hipSuccess ? SIGGAN_OK : FAIL(SIGGAN_E_HIP, "verifier head: kernel launch failed");
 }
 static int vcheck(const siggan_verifier* v, const char* fn) {
-    if (!v) return VFAIL(SIGGAN_E_ARG, "%s: null context", fn);
-    if (!v->bound) return VFAIL(SIGGAN_E_ARG, "%s: siggan_verifier_bind has not been called", fn);
+    if (!v) return FAIL(SIGGAN_E_ARG, "%s: null context", fn);
+    if (!v->bound) return FAIL(SIGGAN_E_ARG, "%s: siggan_verifier_bind has not been called", fn);
     return SIGGAN_OK;
 }
 
 extern "C" int siggan_verifier_embed(siggan_verifier* v, const void* x, int32_t fmt, int32_t n, float* emb, void* stream) {
     int rc = vcheck(v, "siggan_verifier_embed"); if (rc) return rc;
-    if (!x || !emb) return VFAIL(SIGGAN_E_ARG, "siggan_verifier_embed: null tensor");
-    if (fmt != SIGGAN_VFMT_F32 && fmt != SIGGAN_VFMT_U8) return VFAIL(SIGGAN_E_ARG, "siggan_verifier_embed: unknown fmt %d", fmt);
-    if (n < 1 || n > v->Nmax) return VFAIL(SIGGAN_E_ARG, "siggan_verifier_embed: n_images %d outside [1, max_images=%d]", n, v->Nmax);
-    DevGuard dg(v->device); VHIP(dg.err);
+    if (!x || !emb) return FAIL(SIGGAN_E_ARG, "siggan_verifier_embed: null tensor");
+    if (fmt != SIGGAN_VFMT_F32 && fmt != SIGGAN_VFMT_U8) return FAIL(SIGGAN_E_ARG, "siggan_verifier_embed: unknown fmt %d", fmt);
+    if (n < 1 || n > v->Nmax) return FAIL(SIGGAN_E_ARG, "siggan_verifier_embed: n_images %d outside [1, max_images=%d]", n, v->Nmax);
+    DevGuard dg(v->device); HIPCHK(dg.err);
     return encode(v, x, x, fmt, n, n, emb, emb, (hipStream_t)stream);
 }
 
 extern "C" int siggan_verifier_compare(siggan_verifier* v, const float* e1, const float* e2, int32_t np, float* score, void* stream) {
     int rc = vcheck(v, "siggan_verifier_compare"); if (rc) return rc;
-    if (!e1 || !e2 || !score) return VFAIL(SIGGAN_E_ARG, "siggan_verifier_compare: null tensor");
-    if (np < 1) return VFAIL(SIGGAN_E_ARG, "siggan_verifier_compare: n_pairs %d < 1", np);
-    DevGuard dg(v->device); VHIP(dg.err);
+    if (!e1 || !e2 || !score) return FAIL(SIGGAN_E_ARG, "siggan_verifier_compare: null tensor");
+    if (np < 1) return FAIL(SIGGAN_E_ARG, "siggan_verifier_compare: n_pairs %d < 1", np);
+    DevGuard dg(v->device); HIPCHK(dg.err);
     return head(v, e1, e2, np, score, (hipStream_t)stream);
 }
 
 extern "C" int siggan_verifier_score(siggan_verifier* v, const void* x1, const void* x2, int32_t fmt, int32_t np, float* e1,
                                      float* e2, float* score, void* stream) {
     int rc = vcheck(v, "siggan_verifier_score"); if (rc) return rc;
-    if (!x1 || !x2 || !score) return VFAIL(SIGGAN_E_ARG, "siggan_verifier_score: null tensor");
-    if (fmt != SIGGAN_VFMT_F32 && fmt != SIGGAN_VFMT_U8) return VFAIL(SIGGAN_E_ARG, "siggan_verifier_score: unknown fmt %d", fmt);
+    if (!x1 || !x2 || !score) return FAIL(SIGGAN_E_ARG, "siggan_verifier_score: null tensor");
+    if (fmt != SIGGAN_VFMT_F32 && fmt != SIGGAN_VFMT_U8) return FAIL(SIGGAN_E_ARG, "siggan_verifier_score: unknown fmt %d", fmt);
     if (np < 1 || 2 * (int64_t)np > v->Nmax)
-        return VFAIL(SIGGAN_E_ARG, "siggan_verifier_score: 2 * n_pairs = %lld outside [2, max_images=%d]", 2 * (long long)np, v->Nmax);
-    DevGuard dg(v->device); VHIP(dg.err);
+        return FAIL(SIGGAN_E_ARG, "siggan_verifier_score: 2 * n_pairs = %lld outside [2, max_images=%d]", 2 * (long long)np, v->Nmax);
+    DevGuard dg(v->device); HIPCHK(dg.err);
     hipStream_t s = (hipStream_t)stream;
     float* o1 = e1 ? e1 : v->emb;
     float* o2 = e2 ? e2 : v->emb + (size_t)np * v->E;
@@ -482,18 +367,18 @@ extern "C" int siggan_verifier_score(siggan_verifier* v, const void* x1, const v
 
 extern "C" int siggan_verifier_debug_tensor(siggan_verifier* v, const char* name, float* out, int64_t n, void* stream) {
     int rc = vcheck(v, "siggan_verifier_debug_tensor"); if (rc) return rc;
-    if (!name || !out) return VFAIL(SIGGAN_E_ARG, "siggan_verifier_debug_tensor: null argument");
-    if (v->last_n < 1) return VFAIL(SIGGAN_E_ARG, "siggan_verifier_debug_tensor: no embed / score call yet");
+    if (!name || !out) return FAIL(SIGGAN_E_ARG, "siggan_verifier_debug_tensor: null argument");
+    if (v->last_n < 1) return FAIL(SIGGAN_E_ARG, "siggan_verifier_debug_tensor: no embed / score call yet");
     const float* src; int C, HW;
     if (!strcmp(name, "pool1")) { src = v->pool1; C = 32; HW = 1024; }
     else if (!strcmp(name, "pool2")) { src = v->pool2; C = 64; HW = 256; }
     else if (!strcmp(name, "pool3")) { src = v->pool3; C = 128; HW = 64; }
     else if (!strcmp(name, "fc1")) { src = v->fc1; C = VFC1_N; HW = 1; }
-    else return VFAIL(SIGGAN_E_ARG, "siggan_verifier_debug_tensor: unknown tensor '%s'", name);
+    else return FAIL(SIGGAN_E_ARG, "siggan_verifier_debug_tensor: unknown tensor '%s'", name);
     const int64_t total = (int64_t)v->last_n * C * HW;
-    if (n != total) return VFAIL(SIGGAN_E_ARG, "siggan_verifier_debug_tensor: '%s' holds %lld floats, caller asked for %lld", name,
+    if (n != total) return FAIL(SIGGAN_E_ARG, "siggan_verifier_debug_tensor: '%s' holds %lld floats, caller asked for %lld", name,
                                  (long long)total, (long long)n);
-    DevGuard dg(v->device); VHIP(dg.err);
-    hipLaunchKernelGGL(k_vnchw, dim3(blocks(total)), dim3(256), 0, (hipStream_t)stream, src, out, total, C, HW);
-    return hipGetLastError() == hipSuccess ? SIGGAN_OK : VFAIL(SIGGAN_E_HIP, "siggan_verifier_debug_tensor: kernel launch failed");
+    DevGuard dg(v->device); HIPCHK(dg.err);
+    hipLaunchKernelGGL(k_nchw<float>, dim3(blocks(total)), dim3(256), 0, (hipStream_t)stream, src, out, total, C, HW);
+    return hipGetLastError() == hipSuccess ? SIGGAN_OK : FAIL(SIGGAN_E_HIP, "siggan_verifier_debug_tensor: kernel launch failed");
 }

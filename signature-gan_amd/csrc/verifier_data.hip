@@ -8,22 +8,9 @@
 #include <stdint.h>
 
 #include "../../include/siggan_verifier_data.h"
-
-int siggan_set_error(int code, const char* fmt, ...);     // siggan.hip
-#define DFAIL(...) siggan_set_error(__VA_ARGS__)
+#include "host.h"
 
 namespace {
-
-// same behaviour as siggan.hip's guard: run on the asked device, put the caller's device back on return
-struct DevGuard {
-    int prev = -1, dev;
-    hipError_t err = hipSuccess;
-    explicit DevGuard(int d) : dev(d) {
-        if (hipGetDevice(&prev) != hipSuccess) prev = -1;
-        if (prev != dev) err = hipSetDevice(dev);
-    }
-    ~DevGuard() { if (prev >= 0 && prev != dev) (void)hipSetDevice(prev); }
-};
 
 constexpr int PS = SIGGAN_PAIRS_IMAGE_SIZE;             // 64
 constexpr int PWORDS = PS * PS / 4;                     // 32-bit words per image
@@ -78,16 +65,16 @@ __global__ __launch_bounds__(PTHREADS) void k_pairs_augment(const uint8_t* __res
 extern "C" int siggan_pairs_augment(int32_t device, const uint8_t* cache_dev, int64_t n_images, const int32_t* index_dev,
                                     const int32_t* params_dev, const int16_t* tables_dev, uint8_t* out_dev, int32_t n, int32_t size,
                                     int32_t fill, void* stream) {
-    if (!cache_dev || !index_dev || !out_dev) return DFAIL(SIGGAN_E_INVALID, "siggan_pairs_augment: null tensor");
-    if (size != PS) return DFAIL(SIGGAN_E_INVALID, "siggan_pairs_augment: size must be %d, got %d", PS, size);
-    if (n < 1 || n > (1 << 20)) return DFAIL(SIGGAN_E_INVALID, "siggan_pairs_augment: n must be in 1..2^20, got %d", n);
-    if (n_images < 1) return DFAIL(SIGGAN_E_INVALID, "siggan_pairs_augment: empty cache");
-    if (fill < 0 || fill > 255) return DFAIL(SIGGAN_E_INVALID, "siggan_pairs_augment: fill must be a byte value");
+    if (!cache_dev || !index_dev || !out_dev) return FAIL(SIGGAN_E_INVALID, "siggan_pairs_augment: null tensor");
+    if (size != PS) return FAIL(SIGGAN_E_INVALID, "siggan_pairs_augment: size must be %d, got %d", PS, size);
+    if (n < 1 || n > (1 << 20)) return FAIL(SIGGAN_E_INVALID, "siggan_pairs_augment: n must be in 1..2^20, got %d", n);
+    if (n_images < 1) return FAIL(SIGGAN_E_INVALID, "siggan_pairs_augment: empty cache");
+    if (fill < 0 || fill > 255) return FAIL(SIGGAN_E_INVALID, "siggan_pairs_augment: fill must be a byte value");
     if ((reinterpret_cast<uintptr_t>(cache_dev) | reinterpret_cast<uintptr_t>(out_dev)) & 3)
-        return DFAIL(SIGGAN_E_INVALID, "siggan_pairs_augment: cache_dev and out_dev must be 4-byte aligned");
+        return FAIL(SIGGAN_E_INVALID, "siggan_pairs_augment: cache_dev and out_dev must be 4-byte aligned");
     DevGuard dg(device);
-    if (dg.err != hipSuccess) return DFAIL(SIGGAN_E_HIP, "siggan_pairs_augment: hipSetDevice(%d) -> %s", device, hipGetErrorString(dg.err));
+    if (dg.err != hipSuccess) return FAIL(SIGGAN_E_HIP, "siggan_pairs_augment: hipSetDevice(%d) -> %s", device, hipGetErrorString(dg.err));
     hipLaunchKernelGGL(k_pairs_augment, dim3((unsigned)n * PBLOCKS), dim3(PTHREADS), 0, (hipStream_t)stream, cache_dev, index_dev,
                        params_dev, tables_dev, reinterpret_cast<uint32_t*>(out_dev), (uint32_t)fill, n_images);
-    return hipGetLastError() == hipSuccess ? SIGGAN_OK : DFAIL(SIGGAN_E_HIP, "siggan_pairs_augment: kernel launch failed");
+    return hipGetLastError() == hipSuccess ? SIGGAN_OK : FAIL(SIGGAN_E_HIP, "siggan_pairs_augment: kernel launch failed");
 }

@@ -6,7 +6,7 @@
 // running mean) -> per-half column sums (mean, then centred sum of squares: partial rows + an ordered sum) -> one pass that
 // applies BatchNorm, ReLU and the 2x2 max and writes the pooled tensor and one route byte per pooled element.
 //   k_tconv1    direct 5x5 stencil (Cin = 1), fp32 or uint8 images
-//   k_tconv     stride-1 implicit GEMM on v_mfma_f32_32x32x2_f32 (k_vconv's tile loop, raw store): conv2 / conv3 forward and,
+//   k_tconv     stride-1 implicit GEMM on v_mfma_f32_32x32x2_f32 (verifier_parts.h's conv_tile, the one k_vconv runs; raw store): conv2 / conv3 forward and,
 //               over a tap-flipped channel-transposed pack, their input gradients
 //   k_tgemm     64 x 64 MFMA tiles with either operand K- or M-contiguous: fc1 forward (16 K slices), dX = dY.W, dW = dY^T.X
 //   k_ttail     per image row: ordered K-slice sum + bias + ReLU + dropout, fc2, L2 normalise
@@ -21,46 +21,19 @@
 #include <new>
 
 #include "../../include/siggan_verifier_train.h"
-#include "act.h"
+#include "host.h"
 #include "ops.h"
 #include "rng.h"
+#include "verifier_parts.h"
 
 using namespace siggan;
 
-int siggan_set_error(int code, const char* fmt, ...);     // siggan.hip
-#define TFAIL(...) siggan_set_error(__VA_ARGS__)
-#define THIP(x)                                                                                     \
-    do {                                                                                            \
-        hipError_t e_ = (x);                                                                        \
-        if (e_ != hipSuccess) return TFAIL(SIGGAN_E_HIP, "%s -> %s (%s:%d)", #x, hipGetErrorString(e_), __FILE__, __LINE__); \
-    } while (0)
-
 namespace {
 
-struct DevGuard {
-    int prev = -1, dev;
-    hipError_t err = hipSuccess;
-    explicit DevGuard(int d) : dev(d) {
-        if (hipGetDevice(&prev) != hipSuccess) prev = -1;
-        if (prev != dev) err = hipSetDevice(dev);
-    }
-    ~DevGuard() { if (prev >= 0 && prev != dev) (void)hipSetDevice(prev); }
-};
-
-constexpr int VS = 64;
-constexpr int FK = 8192, FN = 512, FSPLIT = 16, FKS = FK / FSPLIT;
-constexpr int VHID = 64;
 constexpr float P_FC = 0.5f, P_CLS = 0.3f;
 constexpr uint32_t SID_FC1 = 0x56540001u, SID_FC2 = 0x56540002u, SID_CLS = 0x56540003u;   // dropout sites: fc (x1), fc (x2), classifier
 constexpr float BN_MOMENTUM = 0.1f;
 
-inline unsigned blocks(int64_t n) { return (unsigned)((n + 255) / 256); }
-
-__device__ __forceinline__ float wave_sum(float v) {
-#pragma unroll
-    for (int o = 32; o > 0; o >>= 1) v += __shfl_xor(v, o, 64);
-    return v;
-}
 // keep decision of element i of a dropout site
 __device__ __forceinline__ bool drawn_keep(unsigned long long seed, unsigned long long ctr, uint64_t i, uint32_t sid, float keep) {
     const uint4 r = draw_raw(seed, ctr, i >> 2, sid);
@@ -80,20 +53,6 @@ __global__ void k_tpack(const float* __restrict__ w, float* __restrict__ fwd, fl
 }
 
 // ---------------------------------------------------------------- conv1 forward (no bias): y (N, 64, 64, 32)
-template <bool U8>
-__device__ __forceinline__ float tload(const void* img, int i) {
-    if (U8) {
-        const float v = (float)((const uint8_t*)img)[i] / 255.0f;     // ToTensor
-        return (v - 0.5f) / 0.5f;                                      // Normalize([0.5], [0.5])
-    }
-    return ((const float*)img)[i];
-}
-template <bool U8>
-__device__ __forceinline__ const void* timage(const void* x1, const void* x2, int nsplit, int n) {
-    const size_t esz = U8 ? 1 : 4;
-    return n < nsplit ? (const void*)((const char*)x1 + (size_t)n * VS * VS * esz)
-                      : (const void*)((const char*)x2 + (size_t)(n - nsplit) * VS * VS * esz);
-}
 // thread = (pixel, 8 output channels); block = 64 pixels (one image row) x 4 channel groups
 template <bool U8>
 __global__ __launch_bounds__(256) void k_tconv1(const void* __restrict__ x1, const void* __restrict__ x2, int nsplit,
@@ -105,7 +64,7 @@ __global__ __launch_bounds__(256) void k_tconv1(const void* __restrict__ x1, con
     const int cg = tid & 3;
     const int64_t P = (int64_t)blockIdx.x * 64 + (tid >> 2);
     const int n = (int)(P >> 12), py = (int)(P >> 6) & 63, px = (int)P & 63;
-    const void* img = timage<U8>(x1, x2, nsplit, n);
+    const void* img = vimage<U8>(x1, x2, nsplit, n);
     float acc[8];
 #pragma unroll
     for (int c = 0; c < 8; ++c) acc[c] = 0.f;
@@ -114,7 +73,7 @@ __global__ __launch_bounds__(256) void k_tconv1(const void* __restrict__ x1, con
 #pragma unroll
         for (int kx = 0; kx < 5; ++kx) {
             const int iy = py + ky - 2, ix = px + kx - 2;
-            const float xv = (iy >= 0 && iy < VS && ix >= 0 && ix < VS) ? tload<U8>(img, iy * VS + ix) : 0.f;
+            const float xv = (iy >= 0 && iy < VS && ix >= 0 && ix < VS) ? vload<U8>(img, iy * VS + ix) : 0.f;
 #pragma unroll
             for (int c = 0; c < 8; ++c) acc[c] = fmaf(xv, sW[ky * 5 + kx][cg * 8 + c], acc[c]);
         }
@@ -130,11 +89,11 @@ __global__ __launch_bounds__(256) void k_tconv1_wgrad(const void* __restrict__ x
                                                       const float* __restrict__ dy /* (N, 64, 64, 32) */, float* __restrict__ part) {
     __shared__ float sX[20][68];
     const int tid = threadIdx.x, n = blockIdx.x >> 2, band = blockIdx.x & 3;
-    const void* img = timage<U8>(x1, x2, nsplit, n);
+    const void* img = vimage<U8>(x1, x2, nsplit, n);
     for (int i = tid; i < 20 * 68; i += 256) {
         const int r = i / 68, c = i % 68;
         const int iy = band * 16 + r - 2, ix = c - 2;
-        sX[r][c] = (iy >= 0 && iy < VS && ix >= 0 && ix < VS) ? tload<U8>(img, iy * VS + ix) : 0.f;
+        sX[r][c] = (iy >= 0 && iy < VS && ix >= 0 && ix < VS) ? vload<U8>(img, iy * VS + ix) : 0.f;
     }
     __syncthreads();
     const int co = tid & 31, tg = tid >> 5;
@@ -157,66 +116,15 @@ __global__ __launch_bounds__(256) void k_tconv1_wgrad(const void* __restrict__ x
 }
 
 // ---------------------------------------------------------------- conv2 / conv3: implicit GEMM, raw store
-// x: (N, H, H, CI) NHWC; wp: [CO][KS*KS*CI]; out: (N, H, H, CO).  Block tile 128 (M) x BN, K-tiles of 32 staged k-major in LDS;
-// wave w owns rows [32w, 32w+32) x all BN columns.  M = N * H * H is a multiple of 128, CO of BN: no ragged tiles.
+// x: (N, H, H, CI) NHWC; wp: [CO][KS*KS*CI]; out: (N, H, H, CO).  conv_tile's 128 x BN block tile over rows in raster order.
 template <int KS, int CI, int CO, int H, int BN>
 __global__ __launch_bounds__(256) void k_tconv(const float* __restrict__ x, const float* __restrict__ wp, float* __restrict__ out) {
-    constexpr int BM = 128, BK = 32, LDA = BM + 4, LDB = BN + 4, PAD = KS / 2, K = KS * KS * CI, NACC = BN / 32;
-    constexpr int BPT = BN * BK / 256;          // B floats per thread: 8 or 4
-    static_assert(CI % BK == 0 && CO % BN == 0 && (H * H) % BM == 0 && (BN == 32 || BN == 64), "tile geometry");
-    __shared__ float sA[BK][LDA], sB[BK][LDB];
-    const int tid = threadIdx.x, lane = tid & 63, wave = tid >> 6, li = lane & 31, lh = lane >> 5;
+    constexpr int BM = 128, NACC = BN / 32;
+    const int lane = threadIdx.x & 63, wave = threadIdx.x >> 6, li = lane & 31, lh = lane >> 5;
     const int64_t m0 = (int64_t)blockIdx.x * BM;
     const int n0 = blockIdx.y * BN;
-    const int ar = tid & 127, ah = tid >> 7;
-    const int64_t m = m0 + ar;
-    const int xx = (int)(m % H), y = (int)((m / H) % H);
-    const int64_t n = m / (H * H);
-    const float* xim = x + (size_t)n * H * H * CI + ah * 16;
-    const int br = tid % BN, bq = tid / BN;
-    const float* wrow = wp + (size_t)(n0 + br) * K + bq * BPT;
-
-    f32x4 ra[4], rb[BPT / 4];
-    auto fetch = [&](int k0) {
-        const int tap = k0 / CI, ci0 = k0 % CI;
-        const int iy = y + tap / KS - PAD, ix = xx + tap % KS - PAD;
-        if (iy >= 0 && iy < H && ix >= 0 && ix < H) {                  // out-of-image taps read zeros
-            const float* src = xim + ((size_t)iy * H + ix) * CI + ci0;
-#pragma unroll
-            for (int j = 0; j < 4; ++j) ra[j] = *reinterpret_cast<const f32x4*>(src + 4 * j);
-        } else {
-#pragma unroll
-            for (int j = 0; j < 4; ++j) ra[j] = f32x4{0.f, 0.f, 0.f, 0.f};
-        }
-#pragma unroll
-        for (int j = 0; j < BPT / 4; ++j) rb[j] = *reinterpret_cast<const f32x4*>(wrow + k0 + 4 * j);
-    };
     f32x16 acc[NACC];
-#pragma unroll
-    for (int j = 0; j < NACC; ++j)
-#pragma unroll
-        for (int r = 0; r < 16; ++r) acc[j][r] = 0.f;
-    fetch(0);
-    for (int k0 = 0; k0 < K; k0 += BK) {
-#pragma unroll
-        for (int j = 0; j < 4; ++j)
-#pragma unroll
-            for (int e = 0; e < 4; ++e) sA[ah * 16 + 4 * j + e][ar] = ra[j][e];
-#pragma unroll
-        for (int j = 0; j < BPT / 4; ++j)
-#pragma unroll
-            for (int e = 0; e < 4; ++e) sB[bq * BPT + 4 * j + e][br] = rb[j][e];
-        __syncthreads();
-        if (k0 + BK < K) fetch(k0 + BK);
-#pragma unroll
-        for (int s = 0; s < BK / 2; ++s) {
-            const float a = sA[2 * s + lh][wave * 32 + li];
-#pragma unroll
-            for (int j = 0; j < NACC; ++j) acc[j] = __builtin_amdgcn_mfma_f32_32x32x2f32(a, sB[2 * s + lh][32 * j + li], acc[j], 0, 0, 0);
-        }
-        __syncthreads();
-    }
-    // C/D: row = (r & 3) + 8 * (r >> 2) + 4 * lh, col = li
+    conv_tile<KS, CI, CO, H, BN, RasterRows>(x, wp, m0, n0, acc);
 #pragma unroll
     for (int j = 0; j < NACC; ++j)
 #pragma unroll
@@ -521,17 +429,14 @@ __global__ __launch_bounds__(256) void k_ttail(const float* __restrict__ part, i
                                                float* __restrict__ hmul, uint8_t* __restrict__ relu1, uint8_t* __restrict__ keep1,
                                                float* __restrict__ eraw, float* __restrict__ nrm_out, float* __restrict__ emb) {
     extern __shared__ float se[];                      // E embedding entries
-    __shared__ float sh1[FN];
-    __shared__ float sred[4];
-    const int row = blockIdx.x, tid = threadIdx.x, lane = tid & 63, wave = tid >> 6;
+    __shared__ float sh1[VFC1_N];
+    const int row = blockIdx.x, tid = threadIdx.x;
     const int half = row >= nsplit;
-    for (int j = tid; j < FN; j += 256) {
-        float a = 0.f;
-        for (int z = 0; z < FSPLIT; ++z) a += part[((size_t)z * M + row) * FN + j];
-        a = fmaxf(a + b1[j], 0.f);
-        const size_t o = (size_t)row * FN + j;
+    for (int j = tid; j < VFC1_N; j += 256) {
+        const float a = fc1_finish(part, M, row, j, b1);
+        const size_t o = (size_t)row * VFC1_N + j;
         const bool keep = keep_in ? keep_in[o] != 0.f
-                                  : drawn_keep(rng.seed, rng.ctr, (uint64_t)(row - half * nsplit) * FN + j, half ? SID_FC2 : SID_FC1, 1.0f - P_FC);
+                                  : drawn_keep(rng.seed, rng.ctr, (uint64_t)(row - half * nsplit) * VFC1_N + j, half ? SID_FC2 : SID_FC1, 1.0f - P_FC);
         const float mul = keep ? 1.0f / (1.0f - P_FC) : 0.f;
         const float h = a * mul;
         sh1[j] = h;
@@ -540,22 +445,7 @@ __global__ __launch_bounds__(256) void k_ttail(const float* __restrict__ part, i
         relu1[o] = a > 0.f;
         keep1[o] = keep;
     }
-    __syncthreads();
-    for (int o = wave; o < E; o += 4) {                // one wave per output: 8 products per lane, then a butterfly
-        const float* wr = w2 + (size_t)o * FN;
-        float a = 0.f;
-#pragma unroll
-        for (int i = 0; i < FN / 64; ++i) a = fmaf(sh1[lane + 64 * i], wr[lane + 64 * i], a);
-        a = wave_sum(a);
-        if (lane == 0) se[o] = a + b2[o];
-    }
-    __syncthreads();
-    float ss = 0.f;
-    for (int o = tid; o < E; o += 256) ss = fmaf(se[o], se[o], ss);
-    ss = wave_sum(ss);
-    if (lane == 0) sred[wave] = ss;
-    __syncthreads();
-    const float nrm = fmaxf(sqrtf((sred[0] + sred[1]) + (sred[2] + sred[3])), 1e-12f);     // F.normalize's eps
+    const float nrm = fc2_norm(sh1, w2, b2, E, se);
     if (tid == 0) nrm_out[row] = nrm;
     for (int i = tid; i < E; i += 256) {
         eraw[(size_t)row * E + i] = se[i];
@@ -684,41 +574,32 @@ __global__ __launch_bounds__(256) void k_tembbwd(const float* __restrict__ de, i
         deraw[(size_t)row * E + k] = v;
     }
     __syncthreads();
-    for (int j = tid; j < FN; j += 256) {
+    for (int j = tid; j < VFC1_N; j += 256) {
         float a = 0.f;
-        for (int o = 0; o < E; ++o) a = fmaf(sg[o], w2[(size_t)o * FN + j], a);
-        dH[(size_t)row * FN + j] = a * hmul[(size_t)row * FN + j];
+        for (int o = 0; o < E; ++o) a = fmaf(sg[o], w2[(size_t)o * VFC1_N + j], a);
+        dH[(size_t)row * VFC1_N + j] = a * hmul[(size_t)row * VFC1_N + j];
     }
 }
 // fc2.weight (E, 512), fc2.bias (E), fc1.bias (512) gradients: one thread per output, rows in order
 __global__ void k_tfc2_sum(const float* __restrict__ deraw, const float* __restrict__ hdrop, const float* __restrict__ dH, int M,
                            int E, float* __restrict__ gw2, float* __restrict__ gb2, float* __restrict__ gb1) {
-    const int64_t i = (int64_t)blockIdx.x * blockDim.x + threadIdx.x, nw = (int64_t)E * FN;
+    const int64_t i = (int64_t)blockIdx.x * blockDim.x + threadIdx.x, nw = (int64_t)E * VFC1_N;
     if (i < nw) {
-        const int o = (int)(i / FN), j = (int)(i % FN);
+        const int o = (int)(i / VFC1_N), j = (int)(i % VFC1_N);
         float a = 0.f;
-        for (int r = 0; r < M; ++r) a = fmaf(deraw[(size_t)r * E + o], hdrop[(size_t)r * FN + j], a);
+        for (int r = 0; r < M; ++r) a = fmaf(deraw[(size_t)r * E + o], hdrop[(size_t)r * VFC1_N + j], a);
         gw2[i] = a;
     } else if (i < nw + E) {
         const int o = (int)(i - nw);
         float a = 0.f;
         for (int r = 0; r < M; ++r) a += deraw[(size_t)r * E + o];
         gb2[o] = a;
-    } else if (i < nw + E + FN) {
+    } else if (i < nw + E + VFC1_N) {
         const int j = (int)(i - nw - E);
         float a = 0.f;
-        for (int r = 0; r < M; ++r) a += dH[(size_t)r * FN + j];
+        for (int r = 0; r < M; ++r) a += dH[(size_t)r * VFC1_N + j];
         gb1[j] = a;
     }
-}
-
-// ---------------------------------------------------------------- debug copies
-__global__ void k_route_nchw(const uint8_t* __restrict__ in, uint8_t* __restrict__ out, int64_t total, int C, int HW) {
-    const int64_t i = (int64_t)blockIdx.x * blockDim.x + threadIdx.x;     // index into out (n, c, hw)
-    if (i >= total) return;
-    const int hw = (int)(i % HW), c = (int)((i / HW) % C);
-    const int64_t n = i / ((int64_t)HW * C);
-    out[i] = in[(n * HW + hw) * C + c];
 }
 
 }  // namespace
@@ -746,18 +627,18 @@ struct siggan_verifier_trainer {
 };
 
 extern "C" int siggan_verifier_trainer_create(int32_t device, int32_t E, int32_t max_pairs, siggan_verifier_trainer** out) {
-    if (!out) return TFAIL(SIGGAN_E_ARG, "siggan_verifier_trainer_create: null argument");
+    if (!out) return FAIL(SIGGAN_E_ARG, "siggan_verifier_trainer_create: null argument");
     *out = nullptr;
     if (E < 1 || E > SIGGAN_VERIFIER_MAX_EMBEDDING)
-        return TFAIL(SIGGAN_E_ARG, "embedding_dim %d outside [1, %d]", E, SIGGAN_VERIFIER_MAX_EMBEDDING);
-    if (max_pairs < 1 || max_pairs > 1024) return TFAIL(SIGGAN_E_ARG, "max_pairs %d outside [1, 1024]", max_pairs);
-    DevGuard dg(device); THIP(dg.err);
+        return FAIL(SIGGAN_E_ARG, "embedding_dim %d outside [1, %d]", E, SIGGAN_VERIFIER_MAX_EMBEDDING);
+    if (max_pairs < 1 || max_pairs > 1024) return FAIL(SIGGAN_E_ARG, "max_pairs %d outside [1, 1024]", max_pairs);
+    DevGuard dg(device); HIPCHK(dg.err);
     siggan_verifier_trainer* t = new (std::nothrow) siggan_verifier_trainer();
-    if (!t) return TFAIL(SIGGAN_E_NOMEM, "out of host memory");
+    if (!t) return FAIL(SIGGAN_E_NOMEM, "out of host memory");
     t->device = device; t->E = E; t->Bmax = max_pairs; t->bound = false; t->last_b = 0; t->ws = nullptr;
     t->seed = 0; t->rng_ctr = 0; t->adam_t = 0.0;
-    const int64_t cnt[SIGGAN_VT_PARAM_TENSORS] = {800, 32, 32, 32, 51200, 64, 64, 64, 73728, 128, 128, 128, (int64_t)FN * FK, FN,
-                                                  (int64_t)E * FN, E, (int64_t)VHID * E, VHID, VHID, 1};
+    const int64_t cnt[SIGGAN_VT_PARAM_TENSORS] = {800, 32, 32, 32, 51200, 64, 64, 64, 73728, 128, 128, 128, (int64_t)VFC1_N * VFC1_K, VFC1_N,
+                                                  (int64_t)E * VFC1_N, E, (int64_t)VHID * E, VHID, VHID, 1};
     t->off[0] = 0;
     for (int i = 0; i < SIGGAN_VT_PARAM_TENSORS; ++i) t->off[i + 1] = t->off[i] + cnt[i];
     const int64_t B = max_pairs, N = 2 * B;
@@ -775,25 +656,25 @@ extern "C" int siggan_verifier_trainer_create(int32_t device, int32_t E, int32_t
         cf(&t->wp2, 51200); cf(&t->wf2, 51200); cf(&t->wp3, 73728); cf(&t->wf3, 73728);
         cf(&t->y1, N * 4096 * 32); cf(&t->y2, N * 1024 * 64); cf(&t->y3, N * 256 * 128);
         cf(&t->dy1, N * 4096 * 32); cf(&t->dy2, N * 1024 * 64); cf(&t->dy3, N * 256 * 128);
-        cf(&t->pool1, N * 1024 * 32); cf(&t->pool2, N * 256 * 64); cf(&t->pool3, N * FK);
-        cf(&t->dp1, N * 1024 * 32); cf(&t->dp2, N * 256 * 64); cf(&t->dp3, N * FK);
-        cb(&t->r1, N * 1024 * 32); cb(&t->r2, N * 256 * 64); cb(&t->r3, N * FK);
-        cb(&t->relu1, N * FN); cb(&t->keep1, N * FN); cb(&t->reluc, B * VHID); cb(&t->keepc, B * VHID);
+        cf(&t->pool1, N * 1024 * 32); cf(&t->pool2, N * 256 * 64); cf(&t->pool3, N * VFC1_K);
+        cf(&t->dp1, N * 1024 * 32); cf(&t->dp2, N * 256 * 64); cf(&t->dp3, N * VFC1_K);
+        cb(&t->r1, N * 1024 * 32); cb(&t->r2, N * 256 * 64); cb(&t->r3, N * VFC1_K);
+        cb(&t->relu1, N * VFC1_N); cb(&t->keep1, N * VFC1_N); cb(&t->reluc, B * VHID); cb(&t->keepc, B * VHID);
         cf(&t->bnpart, nbnpart); cf(&t->mean, 3 * 2 * 128); cf(&t->invstd, 3 * 2 * 128); cf(&t->bsums, 3 * 4 * 128);
-        cf(&t->part, N * FSPLIT * FN); cf(&t->hdrop, N * FN); cf(&t->hmul, N * FN);
-        cf(&t->eraw, N * E); cf(&t->nrm, N); cf(&t->emb, N * E); cf(&t->deraw, N * E); cf(&t->dH, N * FN);
+        cf(&t->part, N * VFC1_SPLIT * VFC1_N); cf(&t->hdrop, N * VFC1_N); cf(&t->hmul, N * VFC1_N);
+        cf(&t->eraw, N * E); cf(&t->nrm, N); cf(&t->emb, N * E); cf(&t->deraw, N * E); cf(&t->dH, N * VFC1_N);
         cf(&t->absd, B * E); cf(&t->hd, B * VHID); cf(&t->dhid, B * VHID); cf(&t->de, B * E); cf(&t->sim, B); cf(&t->dist, B);
         cf(&t->pm, B * 4);
         cf(&t->slab, nslab);
         if (pass == 0) {
             hipError_t e = hipMalloc((void**)&base, off);
-            if (e != hipSuccess) { delete t; return TFAIL(SIGGAN_E_NOMEM, "hipMalloc(%zu) -> %s", off, hipGetErrorString(e)); }
+            if (e != hipSuccess) { delete t; return FAIL(SIGGAN_E_NOMEM, "hipMalloc(%zu) -> %s", off, hipGetErrorString(e)); }
             t->ws = base;
         }
     }
     hipError_t e = hipMemset(t->dst, 0, sizeof(DevState));
     if (e == hipSuccess) e = hipMemset(t->steps, 0, 32 * 4);
-    if (e != hipSuccess) { (void)hipFree(t->ws); delete t; return TFAIL(SIGGAN_E_HIP, "hipMemset -> %s", hipGetErrorString(e)); }
+    if (e != hipSuccess) { (void)hipFree(t->ws); delete t; return FAIL(SIGGAN_E_HIP, "hipMemset -> %s", hipGetErrorString(e)); }
     *out = t;
     return SIGGAN_OK;
 }
@@ -812,23 +693,23 @@ extern "C" int64_t siggan_verifier_trainer_param_count(const siggan_verifier_tra
 }
 
 extern "C" int siggan_verifier_trainer_param_span(const siggan_verifier_trainer* t, int32_t index, int64_t* offset, int64_t* count) {
-    if (!t || !offset || !count) return TFAIL(SIGGAN_E_ARG, "siggan_verifier_trainer_param_span: null argument");
+    if (!t || !offset || !count) return FAIL(SIGGAN_E_ARG, "siggan_verifier_trainer_param_span: null argument");
     if (index < 0 || index >= SIGGAN_VT_PARAM_TENSORS)
-        return TFAIL(SIGGAN_E_ARG, "siggan_verifier_trainer_param_span: index %d outside [0, %d)", index, SIGGAN_VT_PARAM_TENSORS);
+        return FAIL(SIGGAN_E_ARG, "siggan_verifier_trainer_param_span: index %d outside [0, %d)", index, SIGGAN_VT_PARAM_TENSORS);
     *offset = t->off[index];
     *count = t->off[index + 1] - t->off[index];
     return SIGGAN_OK;
 }
 
 extern "C" int siggan_verifier_trainer_bind(siggan_verifier_trainer* t, const siggan_verifier_train_storage* s, int64_t adam_step) {
-    if (!t || !s) return TFAIL(SIGGAN_E_ARG, "siggan_verifier_trainer_bind: null argument");
+    if (!t || !s) return FAIL(SIGGAN_E_ARG, "siggan_verifier_trainer_bind: null argument");
     const float* const* p = reinterpret_cast<const float* const*>(s);
     for (int i = 0; i < 10; ++i)
-        if (!p[i]) return TFAIL(SIGGAN_E_ARG, "siggan_verifier_trainer_bind: storage pointer %d is null", i);
-    if (!(s->bn_eps > 0.f)) return TFAIL(SIGGAN_E_ARG, "siggan_verifier_trainer_bind: bn_eps must be positive");
-    if (adam_step < 0) return TFAIL(SIGGAN_E_ARG, "siggan_verifier_trainer_bind: adam_step %lld < 0", (long long)adam_step);
+        if (!p[i]) return FAIL(SIGGAN_E_ARG, "siggan_verifier_trainer_bind: storage pointer %d is null", i);
+    if (!(s->bn_eps > 0.f)) return FAIL(SIGGAN_E_ARG, "siggan_verifier_trainer_bind: bn_eps must be positive");
+    if (adam_step < 0) return FAIL(SIGGAN_E_ARG, "siggan_verifier_trainer_bind: adam_step %lld < 0", (long long)adam_step);
     if (((uintptr_t)s->params | (uintptr_t)s->grads | (uintptr_t)s->exp_avg | (uintptr_t)s->exp_avg_sq) & 15)
-        return TFAIL(SIGGAN_E_ARG, "siggan_verifier_trainer_bind: the arenas must be 16-byte aligned");
+        return FAIL(SIGGAN_E_ARG, "siggan_verifier_trainer_bind: the arenas must be 16-byte aligned");
     t->st = *s;
     t->adam_t = (double)adam_step;
     t->bound = true;
@@ -836,14 +717,14 @@ extern "C" int siggan_verifier_trainer_bind(siggan_verifier_trainer* t, const si
 }
 
 extern "C" int siggan_verifier_trainer_seed(siggan_verifier_trainer* t, uint64_t seed, uint64_t offset) {
-    if (!t) return TFAIL(SIGGAN_E_ARG, "siggan_verifier_trainer_seed: null context");
+    if (!t) return FAIL(SIGGAN_E_ARG, "siggan_verifier_trainer_seed: null context");
     t->seed = seed; t->rng_ctr = offset;
     return SIGGAN_OK;
 }
 
 static int tcheck(const siggan_verifier_trainer* t, const char* fn) {
-    if (!t) return TFAIL(SIGGAN_E_ARG, "%s: null context", fn);
-    if (!t->bound) return TFAIL(SIGGAN_E_ARG, "%s: siggan_verifier_trainer_bind has not been called", fn);
+    if (!t) return FAIL(SIGGAN_E_ARG, "%s: null context", fn);
+    if (!t->bound) return FAIL(SIGGAN_E_ARG, "%s: siggan_verifier_trainer_bind has not been called", fn);
     return SIGGAN_OK;
 }
 
@@ -899,8 +780,8 @@ static int train_grads(siggan_verifier_trainer* t, const void* x1, const void* x
     bn_forward<false>(t, 1, t->y2, 64, 32, 256, B, p(P_C2B), p(P_G2), p(P_B2), t->st.bn2_running_mean, t->st.bn2_running_var, t->pool2, t->r2, s);
     hipLaunchKernelGGL((k_tconv<3, 64, 128, 16, 64>), dim3(N * 256 / 128, 2), dim3(256), 0, s, (const float*)t->pool2, (const float*)t->wp3, t->y3);
     bn_forward<true>(t, 2, t->y3, 128, 16, 256, B, p(P_C3B), p(P_G3), p(P_B3), t->st.bn3_running_mean, t->st.bn3_running_var, t->pool3, t->r3, s);
-    hipLaunchKernelGGL((k_tgemm<true, true>), dim3(FN / 64, (N + 63) / 64, FSPLIT), dim3(256), 0, s, (const float*)t->pool3, p(P_F1W), t->part,
-                       N, FN, FK, FKS, FK, FK, FN);
+    hipLaunchKernelGGL((k_tgemm<true, true>), dim3(VFC1_N / 64, (N + 63) / 64, VFC1_SPLIT), dim3(256), 0, s, (const float*)t->pool3, p(P_F1W), t->part,
+                       N, VFC1_N, VFC1_K, VFC1_KS, VFC1_K, VFC1_K, VFC1_N);
     hipLaunchKernelGGL(k_ttail, dim3(N), dim3(256), (size_t)E * 4, s, (const float*)t->part, N, B, p(P_F1B), p(P_F2W), p(P_F2B), E, fc_keep, rng,
                        t->hdrop, t->hmul, t->relu1, t->keep1, t->eraw, t->nrm, t->emb);
     hipLaunchKernelGGL(k_thead, dim3(B), dim3(VHID), (size_t)E * 4, s, (const float*)t->emb, B, E, p(P_K0W), p(P_K0B), p(P_K3W), p(P_K3B), labels,
@@ -910,13 +791,13 @@ static int train_grads(siggan_verifier_trainer* t, const void* x1, const void* x
                        (const float*)t->hd, (const float*)t->pm, B, E, use_c, g(P_K0W), g(P_K0B), g(P_K3W), g(P_K3B), metrics);
     hipLaunchKernelGGL(k_tembbwd, dim3(N), dim3(256), (size_t)E * 4, s, (const float*)t->de, B, E, (const float*)t->eraw, (const float*)t->nrm,
                        (const float*)t->emb, p(P_F2W), (const float*)t->hmul, t->deraw, t->dH);
-    hipLaunchKernelGGL(k_tfc2_sum, dim3(blocks((int64_t)E * FN + E + FN)), dim3(256), 0, s, (const float*)t->deraw, (const float*)t->hdrop,
+    hipLaunchKernelGGL(k_tfc2_sum, dim3(blocks((int64_t)E * VFC1_N + E + VFC1_N)), dim3(256), 0, s, (const float*)t->deraw, (const float*)t->hdrop,
                        (const float*)t->dH, N, E, g(P_F2W), g(P_F2B), g(P_F1B));
     // d(pool3) (N, 8192) = dH (N, 512) . W (512, 8192);  dW (512, 8192) = dH^T . pool3
-    hipLaunchKernelGGL((k_tgemm<true, false>), dim3(FK / 64, (N + 63) / 64, 1), dim3(256), 0, s, (const float*)t->dH, p(P_F1W), t->dp3,
-                       N, FK, FN, FN, FN, FK, FK);
-    hipLaunchKernelGGL((k_tgemm<false, false>), dim3(FK / 64, FN / 64, 1), dim3(256), 0, s, (const float*)t->dH, (const float*)t->pool3, g(P_F1W),
-                       FN, FK, N, ((N + 31) / 32) * 32, FN, FK, FK);
+    hipLaunchKernelGGL((k_tgemm<true, false>), dim3(VFC1_K / 64, (N + 63) / 64, 1), dim3(256), 0, s, (const float*)t->dH, p(P_F1W), t->dp3,
+                       N, VFC1_K, VFC1_N, VFC1_N, VFC1_N, VFC1_K, VFC1_K);
+    hipLaunchKernelGGL((k_tgemm<false, false>), dim3(VFC1_K / 64, VFC1_N / 64, 1), dim3(256), 0, s, (const float*)t->dH, (const float*)t->pool3, g(P_F1W),
+                       VFC1_N, VFC1_K, N, ((N + 31) / 32) * 32, VFC1_N, VFC1_K, VFC1_K);
     // ---- conv3
     bn_backward<true>(t, 2, t->dp3, t->r3, t->y3, 128, 16, 64, B, p(P_G3), g(P_G3), g(P_B3), t->dy3, s);
     hipLaunchKernelGGL((k_twgrad<3, 64, 128, 16, 256>), dim3(576 / 32, N), dim3(256), 0, s, (const float*)t->dy3, (const float*)t->pool2, t->slab);
@@ -935,16 +816,16 @@ static int train_grads(siggan_verifier_trainer* t, const void* x1, const void* x
     // conv biases in front of a train-mode BatchNorm: the gradient is exactly zero
     if (hipMemsetAsync(g(P_C1B), 0, 32 * 4, s) != hipSuccess || hipMemsetAsync(g(P_C2B), 0, 64 * 4, s) != hipSuccess ||
         hipMemsetAsync(g(P_C3B), 0, 128 * 4, s) != hipSuccess)
-        return TFAIL(SIGGAN_E_HIP, "siggan_verifier_train_grads: hipMemsetAsync failed");
+        return FAIL(SIGGAN_E_HIP, "siggan_verifier_train_grads: hipMemsetAsync failed");
     t->last_b = B;
-    return hipGetLastError() == hipSuccess ? SIGGAN_OK : TFAIL(SIGGAN_E_HIP, "siggan_verifier_train_grads: kernel launch failed");
+    return hipGetLastError() == hipSuccess ? SIGGAN_OK : FAIL(SIGGAN_E_HIP, "siggan_verifier_train_grads: kernel launch failed");
 }
 
 static int grads_args(const siggan_verifier_trainer* t, const char* fn, const void* x1, const void* x2, int fmt, const float* labels, int B) {
     int rc = tcheck(t, fn); if (rc) return rc;
-    if (!x1 || !x2 || !labels) return TFAIL(SIGGAN_E_ARG, "%s: null tensor", fn);
-    if (fmt != SIGGAN_VFMT_F32 && fmt != SIGGAN_VFMT_U8) return TFAIL(SIGGAN_E_ARG, "%s: unknown fmt %d", fn, fmt);
-    if (B < 1 || B > t->Bmax) return TFAIL(SIGGAN_E_ARG, "%s: n_pairs %d outside [1, max_pairs=%d]", fn, B, t->Bmax);
+    if (!x1 || !x2 || !labels) return FAIL(SIGGAN_E_ARG, "%s: null tensor", fn);
+    if (fmt != SIGGAN_VFMT_F32 && fmt != SIGGAN_VFMT_U8) return FAIL(SIGGAN_E_ARG, "%s: unknown fmt %d", fn, fmt);
+    if (B < 1 || B > t->Bmax) return FAIL(SIGGAN_E_ARG, "%s: n_pairs %d outside [1, max_pairs=%d]", fn, B, t->Bmax);
     return SIGGAN_OK;
 }
 
@@ -952,7 +833,7 @@ extern "C" int siggan_verifier_train_grads(siggan_verifier_trainer* t, const voi
                                            int32_t B, const float* fc_keep, const float* cls_keep, int32_t use_c, float* metrics,
                                            void* stream) {
     int rc = grads_args(t, "siggan_verifier_train_grads", x1, x2, fmt, labels, B); if (rc) return rc;
-    DevGuard dg(t->device); THIP(dg.err);
+    DevGuard dg(t->device); HIPCHK(dg.err);
     return train_grads(t, x1, x2, fmt, labels, B, fc_keep, cls_keep, use_c ? 1 : 0, metrics, (hipStream_t)stream);
 }
 
@@ -960,18 +841,18 @@ static int train_apply(siggan_verifier_trainer* t, double lr, double beta1, doub
     t->adam_t += 1.0;
     launch_adam_fused(t->st.params, t->st.grads, t->st.exp_avg, t->st.exp_avg_sq, t->off[SIGGAN_VT_PARAM_TENSORS], t->dst, t->steps,
                       SIGGAN_VT_PARAM_TENSORS, t->adam_t, lr, beta1, beta2, eps, 1.0f, 0.f, nullptr, nullptr, s);
-    return hipGetLastError() == hipSuccess ? SIGGAN_OK : TFAIL(SIGGAN_E_HIP, "siggan_verifier_train_apply: kernel launch failed");
+    return hipGetLastError() == hipSuccess ? SIGGAN_OK : FAIL(SIGGAN_E_HIP, "siggan_verifier_train_apply: kernel launch failed");
 }
 static int apply_args(const siggan_verifier_trainer* t, const char* fn, double lr, double beta1, double beta2, double eps) {
     int rc = tcheck(t, fn); if (rc) return rc;
     if (!(lr >= 0.0) || !(beta1 >= 0.0 && beta1 < 1.0) || !(beta2 >= 0.0 && beta2 < 1.0) || !(eps >= 0.0))
-        return TFAIL(SIGGAN_E_ARG, "%s: invalid Adam hyper-parameters", fn);
+        return FAIL(SIGGAN_E_ARG, "%s: invalid Adam hyper-parameters", fn);
     return SIGGAN_OK;
 }
 
 extern "C" int siggan_verifier_train_apply(siggan_verifier_trainer* t, double lr, double beta1, double beta2, double eps, void* stream) {
     int rc = apply_args(t, "siggan_verifier_train_apply", lr, beta1, beta2, eps); if (rc) return rc;
-    DevGuard dg(t->device); THIP(dg.err);
+    DevGuard dg(t->device); HIPCHK(dg.err);
     return train_apply(t, lr, beta1, beta2, eps, (hipStream_t)stream);
 }
 
@@ -980,37 +861,37 @@ extern "C" int siggan_verifier_train_step(siggan_verifier_trainer* t, const void
                                           double beta1, double beta2, double eps, float* metrics, void* stream) {
     int rc = grads_args(t, "siggan_verifier_train_step", x1, x2, fmt, labels, B); if (rc) return rc;
     if ((rc = apply_args(t, "siggan_verifier_train_step", lr, beta1, beta2, eps))) return rc;
-    DevGuard dg(t->device); THIP(dg.err);
+    DevGuard dg(t->device); HIPCHK(dg.err);
     if ((rc = train_grads(t, x1, x2, fmt, labels, B, fc_keep, cls_keep, use_c ? 1 : 0, metrics, (hipStream_t)stream))) return rc;
     return train_apply(t, lr, beta1, beta2, eps, (hipStream_t)stream);
 }
 
 extern "C" int siggan_verifier_train_debug(siggan_verifier_trainer* t, const char* name, void* out, int64_t n, void* stream) {
     int rc = tcheck(t, "siggan_verifier_train_debug"); if (rc) return rc;
-    if (!name || !out) return TFAIL(SIGGAN_E_ARG, "siggan_verifier_train_debug: null argument");
-    if (t->last_b < 1) return TFAIL(SIGGAN_E_ARG, "siggan_verifier_train_debug: no _grads call yet");
+    if (!name || !out) return FAIL(SIGGAN_E_ARG, "siggan_verifier_train_debug: null argument");
+    if (t->last_b < 1) return FAIL(SIGGAN_E_ARG, "siggan_verifier_train_debug: no _grads call yet");
     const int64_t B = t->last_b, N = 2 * B, E = t->E;
     const void* src = nullptr; int64_t total = 0, esz = 1; int C = 0, HW = 0;
     if (!strcmp(name, "route1")) { src = t->r1; total = N * 32 * 1024; C = 32; HW = 1024; }
     else if (!strcmp(name, "route2")) { src = t->r2; total = N * 64 * 256; C = 64; HW = 256; }
-    else if (!strcmp(name, "route3")) { src = t->r3; total = N * FK; }
-    else if (!strcmp(name, "fc1_mask")) { src = t->relu1; total = N * FN; }
-    else if (!strcmp(name, "fc_keep")) { src = t->keep1; total = N * FN; }
+    else if (!strcmp(name, "route3")) { src = t->r3; total = N * VFC1_K; }
+    else if (!strcmp(name, "fc1_mask")) { src = t->relu1; total = N * VFC1_N; }
+    else if (!strcmp(name, "fc_keep")) { src = t->keep1; total = N * VFC1_N; }
     else if (!strcmp(name, "cls_mask")) { src = t->reluc; total = B * VHID; }
     else if (!strcmp(name, "cls_keep")) { src = t->keepc; total = B * VHID; }
     else if (!strcmp(name, "e1")) { src = t->emb; total = B * E; esz = 4; }
     else if (!strcmp(name, "e2")) { src = t->emb + B * E; total = B * E; esz = 4; }
     else if (!strcmp(name, "similarity")) { src = t->sim; total = B; esz = 4; }
     else if (!strcmp(name, "distance")) { src = t->dist; total = B; esz = 4; }
-    else return TFAIL(SIGGAN_E_ARG, "siggan_verifier_train_debug: unknown stage '%s'", name);
-    if (n != total) return TFAIL(SIGGAN_E_ARG, "siggan_verifier_train_debug: '%s' holds %lld elements, caller asked for %lld", name,
+    else return FAIL(SIGGAN_E_ARG, "siggan_verifier_train_debug: unknown stage '%s'", name);
+    if (n != total) return FAIL(SIGGAN_E_ARG, "siggan_verifier_train_debug: '%s' holds %lld elements, caller asked for %lld", name,
                                  (long long)total, (long long)n);
-    DevGuard dg(t->device); THIP(dg.err);
+    DevGuard dg(t->device); HIPCHK(dg.err);
     hipStream_t s = (hipStream_t)stream;
     if (C) {
-        hipLaunchKernelGGL(k_route_nchw, dim3(blocks(total)), dim3(256), 0, s, (const uint8_t*)src, (uint8_t*)out, total, C, HW);
-        return hipGetLastError() == hipSuccess ? SIGGAN_OK : TFAIL(SIGGAN_E_HIP, "siggan_verifier_train_debug: kernel launch failed");
+        hipLaunchKernelGGL(k_nchw<uint8_t>, dim3(blocks(total)), dim3(256), 0, s, (const uint8_t*)src, (uint8_t*)out, total, C, HW);
+        return hipGetLastError() == hipSuccess ? SIGGAN_OK : FAIL(SIGGAN_E_HIP, "siggan_verifier_train_debug: kernel launch failed");
     }
-    THIP(hipMemcpyAsync(out, src, (size_t)(total * esz), hipMemcpyDeviceToDevice, s));
+    HIPCHK(hipMemcpyAsync(out, src, (size_t)(total * esz), hipMemcpyDeviceToDevice, s));
     return SIGGAN_OK;
 }
