@@ -48,10 +48,10 @@ struct PrepTable {
     static constexpr int MAXJ = 32;
     int njobs;
     int overflow;                // set by prep_add when a job did not fit: launch_prepare then fails instead of dropping it
-    long long prefix[MAXJ + 1];  // prefix sums of the jobs' element counts
+    long long prefix[MAXJ + 1];  // prefix sums of the jobs' unit (workgroup) counts
     PrepJob job[MAXJ];
 };
-void prep_add(PrepTable& t, const PrepJob& j, long long count);
+void prep_add(PrepTable& t, const PrepJob& j);
 bool launch_prepare(const PrepTable& t, float bn_eps, hipStream_t s);   // false: the table overflowed (nothing launched)
 // the same plus a first-Discriminator-block forward (no dropout table) of B images, as further blocks of the one launch
 bool launch_prepare_conv1(const PrepTable& t, float bn_eps, int dt, const float* x, const float* W, const float* b, float slope,
@@ -205,7 +205,7 @@ void launch_sn_combine(const SnTable& t, const float* g0, const float* g1, float
 // them itself in one fixed order (k_adam_prepare when handed `sumsq_partial`, every block of the fused k_adam): no finalize launch.
 // launch_adam_prepare: reads steps[0], writes steps[i] += 1 for every tensor, derives the Adam scalars; with clip_max_norm > 0
 // (or check_finite) it needs launch_grad_sumsq first and its `partial` as sumsq_partial
-void launch_grad_sumsq(const float* g, int64_t n, DevState* st, float* partial, hipStream_t s);
+void launch_grad_sumsq(const float* g, int64_t n, float* partial, hipStream_t s);
 // check_finite (fp16 chains; needs launch_grad_sumsq first): a non-finite sum of squares marks the update as skipped
 // (DevState::skip: k_adam returns at once, the step counts stay) and writes 1 to *metric_skipped, else 0
 void launch_adam_prepare(DevState* st, float* steps, int ntensors, double lr, double beta1, double beta2,
@@ -233,16 +233,17 @@ void launch_adam(float* p, float* g, float* m, float* v, int64_t n, const DevSta
 // launch_adam_fused plus launch_prepare's work in ONE launch: the arena is covered by a job table; a workgroup that owns a
 // 16 x 16 x 16-tap tile of a convolution weight updates it and writes both MFMA packs from LDS (64-byte runs each way), the
 // classifier / one-channel weights and the BatchNorm eval tables likewise.  Same update arithmetic, same pack values as the
-// two launches it replaces (bitwise: tests/test_engine_gpu.py compares the execution modes).
+// two launches it replaces (bitwise: tests/test_engine_gpu.py compares the execution modes).  Both job tables are built from
+// one list of records (siggan.hip, struct Derived: which fields mean what is said there, once); the destination layouts are
+// the functions both kernels call (ops.hip, pack_down_idx / pack_up_idx / bn_eval_store).
 enum ApType : int { AP_FLAT = 0, AP_CONV, AP_T16, AP_TAPS, AP_BN };
 struct ApJob {
     int type;
-    int A, Bc;                   // CONV: the weight is [A][Bc][4][4]; T16: A rows of 16; TAPS: A channels x Bc taps; BN: A channels, Bc = perm_c0
-    int dt;                      // CONV: element type of the two packs
-    long long off, n;            // first arena element, element count (BN: off = gamma)
+    int A, Bc, dt;               // as in the record (BN: Bc = perm_c0)
+    long long off, n;            // first arena element, element count (FLAT / TAPS; the other types know it from A, Bc)
     long long off2, n2;          // TAPS: a second flat range owned by the same workgroup (the layer's bias); BN: off2 = beta
-    float* dst;                  // CONV: the pack whose unit is dim 0 (PREP_PACK_DOWN); T16 / TAPS: the permuted copy; BN: the table
-    float* dst2;                 // CONV: the pack whose unit is dim 1 (PREP_PACK_UP)
+    float* dst;                  // CONV: the down pack; T16 / TAPS: the permuted copy; BN: the table
+    float* dst2;                 // CONV: the up pack
     const float* rmean;          // BN: running statistics
     const float* rvar;
     int wait;                    // TAPS: riders that must have read this job's ranges before it writes them (ApRide), 0: none

@@ -59,6 +59,28 @@ void launch_tick(DevState* st, hipStream_t s) { hipLaunchKernelGGL(k_tick, dim3(
 
 __device__ __forceinline__ int perm16(int c, int perm_c0) { return perm_c0 > 0 ? (c % perm_c0) * 16 + c / perm_c0 : c; }
 
+// ---- the layouts of what is derived from a parameter arena: k_prepare and k_adam_pack both write through these -------------
+// a packed weight goes out in the element type the consuming kernel reads (dt: fp32, or bf16 / f16 rounded to nearest)
+__device__ __forceinline__ void put_w(float* dst, int dt, size_t idx, float v) {
+    if (dt == DT_F32) dst[idx] = v;
+    else if (dt == DT_BF16) reinterpret_cast<bf16_t*>(dst)[idx] = (bf16_t)v;
+    else reinterpret_cast<f16_t*>(dst)[idx] = (f16_t)v;
+}
+// down pack of a weight [O][I][4][4]: dst[o][tap * I + i]
+__device__ __forceinline__ size_t pack_down_idx(int o, int tap, int i, int I) { return ((size_t)o * 16 + tap) * I + i; }
+// up pack of a weight [I][O][4][4]: dst[cls][o][tt * I + i], tt = the four taps up_tap(cls, tt) of output-parity class cls
+__device__ __forceinline__ int up_tap(int cls, int tt) {
+    const int kh = 1 - (cls >> 1) + 2 * (tt >> 1), kw = 1 - (cls & 1) + 2 * (tt & 1);
+    return kh * 4 + kw;
+}
+__device__ __forceinline__ size_t pack_up_idx(int cls, int o, int tt, int i, int O, int I) { return (((size_t)cls * O + o) * 4 + tt) * I + i; }
+// BatchNorm eval table [scale | shift | mean | rstd] of C channels, entry c (the caller reads its four values at perm16(c))
+__device__ __forceinline__ void bn_eval_store(float* dst, int C, int c, float gam, float bet, float mean, float var, float eps) {
+    const float rstd = 1.0f / sqrtf(var + eps);
+    const float sc = gam * rstd;
+    dst[c] = sc; dst[C + c] = bet - mean * sc; dst[2 * C + c] = mean; dst[3 * C + c] = rstd;
+}
+
 // the optimiser's per-element arithmetic (k_adam, k_adam_pack and the riders of k_adam_pack share it: bitwise the same values)
 struct AdamK { float mul, ss, bc2, w1, beta2, w2, eps; };     // w1 = (float)(1 - beta1), w2 = (float)(1 - beta2): formed in double on the host, as torch does
 __device__ __forceinline__ void adam_upd(const AdamK& k, float& pp, float& gg, float& mm, float& vv) {
@@ -92,19 +114,16 @@ static long long prep_units(const PrepJob& j) {
         default: return (j.O + 255) / 256;
     }
 }
-void prep_add(PrepTable& t, const PrepJob& j, long long /*count*/) {
+void prep_add(PrepTable& t, const PrepJob& j) {
     if (t.njobs >= PrepTable::MAXJ) { t.overflow = 1; return; }   // launch_prepare refuses an incomplete table
     if (t.njobs == 0) t.prefix[0] = 0;
     t.job[t.njobs] = j;
     t.prefix[t.njobs + 1] = t.prefix[t.njobs] + prep_units(j);
     ++t.njobs;
 }
-// a packed weight goes out in the element type the consuming kernel reads (q.dt: fp32, or bf16 / f16 rounded to nearest)
-__device__ __forceinline__ void put_w(const PrepJob& q, size_t idx, float v) {
+__device__ __forceinline__ void prep_put(const PrepJob& q, size_t idx, float v) {       // put_w, times the job's optional multiplier
     if (q.mul) v *= q.mul[0];
-    if (q.dt == DT_F32) q.dst[idx] = v;
-    else if (q.dt == DT_BF16) reinterpret_cast<bf16_t*>(q.dst)[idx] = (bf16_t)v;
-    else reinterpret_cast<f16_t*>(q.dst)[idx] = (f16_t)v;
+    put_w(q.dst, q.dt, idx, v);
 }
 __device__ __forceinline__ void prepare_unit(const PrepTable& t, float eps, unsigned bid) {
     extern __shared__ float tile[];
@@ -119,13 +138,12 @@ __device__ __forceinline__ void prepare_unit(const PrepTable& t, float eps, unsi
 #pragma unroll 4
         for (int e = tid; e < I * 16; e += 256) tile[(e >> 4) * 17 + (e & 15)] = src[e];
         __syncthreads();
-        const size_t d0 = (size_t)u * I * 16;
         if ((I & (I - 1)) == 0) {                  // channel counts are powers of two: shifts instead of a division per element
             const int lgI = 31 - __builtin_clz(I);
 #pragma unroll 4
-            for (int e = tid; e < I * 16; e += 256) { const int tap = e >> lgI, i = e & (I - 1); put_w(q, d0 + e, tile[i * 17 + tap]); }
+            for (int e = tid; e < I * 16; e += 256) { const int tap = e >> lgI, i = e & (I - 1); prep_put(q, pack_down_idx(u, tap, i, I), tile[i * 17 + tap]); }
         } else {
-            for (int e = tid; e < I * 16; e += 256) { const int tap = e / I, i = e - tap * I; put_w(q, d0 + e, tile[i * 17 + tap]); }
+            for (int e = tid; e < I * 16; e += 256) { const int tap = e / I, i = e - tap * I; prep_put(q, pack_down_idx(u, tap, i, I), tile[i * 17 + tap]); }
         }
     } else if (q.type == PREP_PACK_UP) {
         const int I = q.I, O = q.O;
@@ -137,14 +155,12 @@ __device__ __forceinline__ void prepare_unit(const PrepTable& t, float eps, unsi
 #pragma unroll 4
             for (int e = tid; e < I * 16; e += 256) {
                 const int i = e & (I - 1), tt = (e >> lgI) & 3, cls = e >> (lgI + 2);
-                const int kh = 1 - (cls >> 1) + 2 * (tt >> 1), kw = 1 - (cls & 1) + 2 * (tt & 1);
-                put_w(q, ((size_t)cls * O + u) * 4 * I + tt * I + i, tile[i * 17 + kh * 4 + kw]);
+                prep_put(q, pack_up_idx(cls, u, tt, i, O, I), tile[i * 17 + up_tap(cls, tt)]);
             }
         } else {
             for (int e = tid; e < I * 16; e += 256) {
                 const int i = e % I, tt = (e / I) & 3, cls = e / (4 * I);
-                const int kh = 1 - (cls >> 1) + 2 * (tt >> 1), kw = 1 - (cls & 1) + 2 * (tt & 1);
-                put_w(q, ((size_t)cls * O + u) * 4 * I + tt * I + i, tile[i * 17 + kh * 4 + kw]);
+                prep_put(q, pack_up_idx(cls, u, tt, i, O, I), tile[i * 17 + up_tap(cls, tt)]);
             }
         }
     } else if (q.type == PREP_FC_T) {            // K = q.O, C0 = q.I
@@ -166,9 +182,7 @@ __device__ __forceinline__ void prepare_unit(const PrepTable& t, float eps, unsi
         const int C = q.O, c = u * 256 + tid;
         if (c < C) {
             const int tix = perm16(c, q.perm);
-            const float rstd = 1.0f / sqrtf(q.src4[tix] + eps);
-            const float sc = q.src[tix] * rstd;
-            q.dst[c] = sc; q.dst[C + c] = q.src2[tix] - q.src3[tix] * sc; q.dst[2 * C + c] = q.src3[tix]; q.dst[3 * C + c] = rstd;
+            bn_eval_store(q.dst, C, c, q.src[tix], q.src2[tix], q.src3[tix], q.src4[tix], eps);
         }
     }
 }
@@ -1635,8 +1649,7 @@ __device__ __forceinline__ float sum_partials_wave(const float* __restrict__ par
     return acc;
 }
 static constexpr int SUMSQ_BLOCKS = 512;
-void launch_grad_sumsq(const float* g, int64_t n, DevState* st, float* partial, hipStream_t s) {
-    (void)st;
+void launch_grad_sumsq(const float* g, int64_t n, float* partial, hipStream_t s) {
     hipLaunchKernelGGL(k_sumsq, dim3(SUMSQ_BLOCKS), dim3(256), 0, s, g, n, partial);
 }
 
@@ -1790,11 +1803,6 @@ void ap_add(ApTable& t, const ApJob& j) {
     ++t.njobs;
 }
 struct ApArena { float *p, *g, *m, *v; int wb; };
-__device__ __forceinline__ void ap_put(float* dst, int dt, size_t idx, float v) {
-    if (dt == DT_F32) dst[idx] = v;
-    else if (dt == DT_BF16) reinterpret_cast<bf16_t*>(dst)[idx] = (bf16_t)v;
-    else reinterpret_cast<f16_t*>(dst)[idx] = (f16_t)v;
-}
 // one element / one aligned group of four: update in place, return the new parameter(s)
 __device__ __forceinline__ float ap_upd1(const ApArena& a, const AdamK& k, size_t e) {
     float pp = a.p[e], gg = a.g[e], mm = a.m[e], vv = a.v[e];
@@ -1831,19 +1839,18 @@ __device__ __forceinline__ void ap_unit(const ApTable& t, const ApArena& a, cons
             d[0] = w.x; d[1] = w.y; d[2] = w.z; d[3] = w.w;
         }
         __syncthreads();
-        // unit = dim 0 (PREP_PACK_DOWN, I = Bc): dst[a][tap * Bc + b]
+        // down pack: O = A, I = Bc
 #pragma unroll 4
         for (int r = 0; r < 16; ++r) {
             const int e = tid + 256 * r, bl = e & 15, tap = (e >> 4) & 15, al = e >> 8;
-            ap_put(q.dst, q.dt, ((size_t)(a0 + al) * 16 + tap) * q.Bc + b0 + bl, tile[al * AP_TS + bl * 17 + tap]);
+            put_w(q.dst, q.dt, pack_down_idx(a0 + al, tap, b0 + bl, q.Bc), tile[al * AP_TS + bl * 17 + tap]);
         }
-        // unit = dim 1 (PREP_PACK_UP, I = A, O = Bc): dst[cls][b][t * A + a], the four taps of each output-parity class
+        // up pack: I = A, O = Bc
 #pragma unroll 4
         for (int r = 0; r < 16; ++r) {
             const int e = tid + 256 * r, al = e & 15, ct = (e >> 4) & 15, bl = e >> 8;
             const int cls = ct >> 2, tt = ct & 3;
-            const int kh = 1 - (cls >> 1) + 2 * (tt >> 1), kw = 1 - (cls & 1) + 2 * (tt & 1);
-            ap_put(q.dst2, q.dt, (((size_t)cls * q.Bc + b0 + bl) * 4 + tt) * q.A + a0 + al, tile[al * AP_TS + bl * 17 + kh * 4 + kw]);
+            put_w(q.dst2, q.dt, pack_up_idx(cls, b0 + bl, tt, a0 + al, q.Bc, q.A), tile[al * AP_TS + bl * 17 + up_tap(cls, tt)]);
         }
     } else if (q.type == AP_FLAT) {
         const long long e = (long long)u * 1024 + tid * 4;
@@ -1895,14 +1902,12 @@ __device__ __forceinline__ void ap_unit(const ApTable& t, const ApArena& a, cons
             a.p[q.off2 + tid] = pb; a.m[q.off2 + tid] = mb; a.v[q.off2 + tid] = vb;
             if (a.wb) a.g[q.off2 + tid] = gb;
         }
-    } else {                                      // BN: gamma / beta of 256 channels, then [scale | shift | mean | rstd] (prepare_unit's expressions)
+    } else {                                      // BN: gamma / beta of 256 channels, then their eval table
         const int C = q.A, c = u * 256 + tid;
         if (c < C) {
             const int tix = perm16(c, q.Bc);
             const float gam = ap_upd1(a, k, (size_t)q.off + tix), bet = ap_upd1(a, k, (size_t)q.off2 + tix);
-            const float rstd = 1.0f / sqrtf(q.rvar[tix] + bn_eps);
-            const float sc = gam * rstd;
-            q.dst[c] = sc; q.dst[C + c] = bet - q.rmean[tix] * sc; q.dst[2 * C + c] = q.rmean[tix]; q.dst[3 * C + c] = rstd;
+            bn_eval_store(q.dst, C, c, gam, bet, q.rmean[tix], q.rvar[tix], bn_eps);
         }
     }
 }

@@ -177,6 +177,29 @@ struct PhaseResult {
 };
 struct CachedPhase { PhaseKey key; hipGraphExec_t exec; PhaseResult res; };
 
+// What the kernels read besides a parameter arena is derived from it, and THIS is where that is said: one record per arena
+// tensor (or adjacent pair of tensors), in arena order, covering the whole arena.  Both job tables are built from the list --
+// prep_table for k_prepare / k_prepare_conv1 (graph mode, fp16, spectral norm, after siggan_params_changed) and ap_table for
+// k_adam_pack (the eager update that rebuilds the derived state in its own launch) -- so a derived tensor is on both paths or
+// on neither.  build_layout fills in shapes and offsets, siggan_create the destinations and whether the network's update can
+// be the packed one; pointers that exist only after siggan_bind (arenas, running statistics) are resolved per table.
+//   DV_FLAT  nothing derived: the Discriminator's biases
+//   DV_FC    Generator.fc weight [F][A] + bias, Bc = C0 -> dst: the k-major copy of the generic fc kernel (null when fc_fused)
+//   DV_CONV  weight [A][Bc][4][4] -> dst: the down pack (O = A, I = Bc), dst2: the up pack (I = A, O = Bc), element type dt.
+//            The same for the Generator's (Cin, Cout) and the Discriminator's (Cout, Cin) layout: a forward pass contracts
+//            Cin, so G runs on the up pack and D on the down pack, and each input-gradient on the other one
+//   DV_BN    gamma + beta of A channels, Bc = perm_c0, running statistics at bn_off -> dst: [scale | shift | mean | rstd]
+//   DV_TAPS  one-channel convolution weight [A][Bc taps] + bias (k_adam_pack: both ranges belong to ONE workgroup, the one
+//            the riders wait on) -> dst: [tap][c]; dst2 (spectral norm): an fp32 scaled copy in the weight's own layout
+//   DV_T16   classifier weight [A][16] -> dst: [16][A], the last block's NHWC order
+enum DvKind : int { DV_FLAT = 0, DV_FC, DV_CONV, DV_BN, DV_TAPS, DV_T16 };
+struct Derived {
+    int kind, layer, A, Bc;      // layer: the block; a Discriminator weight's spectral-norm layer is layer - 1
+    int64_t off, n, off2, n2;    // arena span of the tensor and of the second one of a pair (bias / beta; n2 = 0: none)
+    int64_t bn_off;              // BN: offset of the layer's running statistics
+    float *dst, *dst2;
+};
+
 struct siggan_ctx {
     siggan_config cfg;
     int S, latent, Lg, Ld, Bm;
@@ -195,6 +218,9 @@ struct siggan_ctx {
     std::vector<int64_t> g_off, g_num, d_off, d_num;
     int64_t g_total, d_total, bn_total;
     int64_t g_bn_off[MAXL + 1];
+    std::vector<Derived> rec[2];   // what is derived from each arena ([0] G, [1] D)
+    bool packable[2];   // the network's eager update can be k_adam_pack: fc_fused, channel counts the 16 x 16 tiles divide,
+                        // one-channel convs that fit one workgroup, no spectral norm (the packs then follow sigma, not the update)
     siggan_storage st;
     bool bound;
     bool g_dirty, d_dirty;
@@ -267,31 +293,36 @@ static void build_layout(siggan_ctx* c) {
     if (c->S == 64) { c->Lg = 4; c->Ld = 4; memcpy(c->gC, g64, sizeof g64); memcpy(c->dC, d64, sizeof d64); }
     else            { c->Lg = 5; c->Ld = 5; memcpy(c->gC, g128, sizeof g128); memcpy(c->dC, d128, sizeof d128); }
     c->F = c->gC[0] * 16;
-    auto push = [](std::vector<int64_t>& off, std::vector<int64_t>& num, int64_t& tot, int64_t n) {
-        off.push_back(tot); num.push_back(n); tot += n;
-    };
-    c->g_total = 0;
-    push(c->g_off, c->g_num, c->g_total, (int64_t)c->F * c->latent);
-    push(c->g_off, c->g_num, c->g_total, c->F);
-    push(c->g_off, c->g_num, c->g_total, c->F);
-    push(c->g_off, c->g_num, c->g_total, c->F);
-    for (int l = 1; l <= c->Lg; ++l) {
-        push(c->g_off, c->g_num, c->g_total, (int64_t)c->gC[l - 1] * c->gC[l] * 16);
-        push(c->g_off, c->g_num, c->g_total, c->gC[l]);
-        push(c->g_off, c->g_num, c->g_total, c->gC[l]);
-    }
-    push(c->g_off, c->g_num, c->g_total, (int64_t)c->gC[c->Lg] * 9);
-    push(c->g_off, c->g_num, c->g_total, 1);
-    c->d_total = 0;
-    for (int l = 1; l <= c->Ld; ++l) {
-        push(c->d_off, c->d_num, c->d_total, (int64_t)c->dC[l] * c->dC[l - 1] * 16);
-        push(c->d_off, c->d_num, c->d_total, c->dC[l]);
-    }
-    push(c->d_off, c->d_num, c->d_total, (int64_t)c->dC[c->Ld] * 16);
-    push(c->d_off, c->d_num, c->d_total, 1);
-    c->bn_total = 0;
     c->g_bn_off[0] = 0; c->bn_total = c->F;
     for (int l = 1; l <= c->Lg; ++l) { c->g_bn_off[l] = c->bn_total; c->bn_total += c->gC[l]; }
+    // The arenas, in parameters() order, as the records of what is derived from each tensor (struct Derived): a tensor of n
+    // elements, followed, n2 > 0, by the one it is paired with
+    c->g_total = c->d_total = 0;
+    auto rec = [c](int w, int kind, int layer, int64_t n, int64_t n2, int A = 0, int Bc = 0) {
+        auto& off = w == 0 ? c->g_off : c->d_off;
+        auto& num = w == 0 ? c->g_num : c->d_num;
+        int64_t& tot = w == 0 ? c->g_total : c->d_total;
+        Derived r; memset(&r, 0, sizeof r);
+        r.kind = kind; r.layer = layer; r.A = A; r.Bc = Bc; r.off = tot; r.n = n; r.n2 = n2;
+        if (n2) r.off2 = tot + n;
+        if (kind == DV_BN) r.bn_off = c->g_bn_off[layer];
+        for (int64_t k : {n, n2}) if (k) { off.push_back(tot); num.push_back(k); tot += k; }
+        c->rec[w].push_back(r);
+    };
+    rec(0, DV_FC, 0, (int64_t)c->F * c->latent, c->F, c->latent, c->gC[0]);
+    for (int l = 0; l <= c->Lg; ++l) {
+        const int C = l == 0 ? c->F : c->gC[l];
+        if (l > 0) rec(0, DV_CONV, l, (int64_t)c->gC[l - 1] * C * 16, 0, c->gC[l - 1], C);
+        rec(0, DV_BN, l, C, C, C, l == 0 ? c->gC[0] : 0);
+    }
+    rec(0, DV_TAPS, c->Lg, (int64_t)c->gC[c->Lg] * 9, 1, c->gC[c->Lg], 9);
+    rec(1, DV_TAPS, 1, (int64_t)c->dC[1] * 16, c->dC[1], c->dC[1], 16);
+    for (int l = 2; l <= c->Ld; ++l) {
+        rec(1, DV_CONV, l, (int64_t)c->dC[l] * c->dC[l - 1] * 16, 0, c->dC[l], c->dC[l - 1]);
+        rec(1, DV_FLAT, l, c->dC[l], 0);
+    }
+    rec(1, DV_T16, c->Ld + 1, (int64_t)c->dC[c->Ld] * 16, 0, c->dC[c->Ld]);
+    rec(1, DV_FLAT, c->Ld + 1, 1, 0);
 }
 
 // A D(real) forward that siggan_g_grads started ahead of time on lane c (siggan_stage_real) and that no D step will
@@ -465,6 +496,22 @@ extern "C" int siggan_create(const siggan_config* cfg, siggan_ctx** out) {
             if (e != hipSuccess) { delete c; return fail(SIGGAN_E_NOMEM, "hipMalloc(%zu) -> %s", off, hipGetErrorString(e)); }
             c->ws = base;
         }
+    }
+    for (int w = 0; w < 2; ++w) {                      // where each record's derived tensors live; can the update be k_adam_pack
+        bool ok = w == 0 || !c->sn;
+        for (Derived& r : c->rec[w]) {
+            const int l = r.layer;
+            switch (r.kind) {
+            case DV_FC:   r.dst = c->fc_fused ? nullptr : c->wfc_t; ok = ok && c->fc_fused; break;
+            case DV_CONV: r.dst = (float*)(w ? c->d_dn : c->g_dn)[l]; r.dst2 = (float*)(w ? c->d_up : c->g_up)[l];
+                          ok = ok && r.A % 16 == 0 && r.Bc % 16 == 0; break;
+            case DV_BN:   r.dst = c->g_bne[l]; break;
+            case DV_TAPS: r.dst = w ? c->d_w1t : c->wfin_t; r.dst2 = w && c->sn ? c->d_w1s : nullptr;
+                          ok = ok && r.n <= 1024 && r.n2 <= 256; break;
+            case DV_T16:  r.dst = c->wcp; break;
+            }
+        }
+        c->packable[w] = ok;
     }
     HIPCHK(hipMemset(c->ws, 0, c->ws_bytes));
     DevState h; memset(&h, 0, sizeof h);
@@ -673,69 +720,53 @@ public:
     void wait(hipStream_t s, hipEvent_t e) { note(hipStreamWaitEvent(s, e, 0)); }
 };
 
-// One launch per network rebuilds everything derived from its arena: GEMM-friendly weight copies and
-// (for G) the BatchNorm eval-mode scale/shift tables.  sg / sd: the lanes the two launches go to.
+// 1 / sigma of spectral-norm layer `layer` as pass `slot` left it (null without spectral norm): what a D pack is scaled by
+static const float* sn_inv_sigma(const siggan_ctx* c, int slot, int layer) {
+    return c->sn ? c->sn_sig + (slot * 2 + 1) * SnTable::MAXS + layer : nullptr;
+}
+// k_prepare's jobs of network `which` from its records (struct Derived).  Job order: by kind, arena order within a kind.
+static void prep_table(const siggan_ctx* c, int which, int sn_slot, PrepTable& t) {
+    t.njobs = 0; t.overflow = 0;
+    const float* P = which == 0 ? c->st.g_params : c->st.d_params;
+    for (int kind : {DV_FC, DV_CONV, DV_T16, DV_BN, DV_TAPS})
+        for (const Derived& r : c->rec[which]) {
+            if (r.kind != kind || !r.dst) continue;
+            PrepJob j; memset(&j, 0, sizeof j);
+            j.src = P + r.off; j.dst = r.dst;
+            if (which == 1) j.mul = sn_inv_sigma(c, sn_slot, r.layer - 1);   // W / sigma of this pass
+            if (kind == DV_CONV) {
+                j.dt = c->dt;
+                PrepJob up = j;
+                j.type = PREP_PACK_DOWN; j.O = r.A; j.I = r.Bc;
+                up.type = PREP_PACK_UP; up.I = r.A; up.O = r.Bc; up.dst = r.dst2;
+                prep_add(t, which == 0 ? up : j);                            // the forward pass's pack first
+                prep_add(t, which == 0 ? j : up);
+                continue;
+            }
+            if (kind == DV_FC) { j.type = PREP_FC_T; j.O = r.A; j.I = r.Bc; }
+            else if (kind == DV_T16) { j.type = PREP_CLS; j.O = r.A; }
+            else if (kind == DV_BN) {
+                j.type = PREP_BN_EVAL; j.O = r.A; j.perm = r.Bc; j.src2 = P + r.off2;
+                j.src3 = c->st.g_bn_running_mean + r.bn_off; j.src4 = c->st.g_bn_running_var + r.bn_off;
+            } else {
+                if (r.dst2) { PrepJob sc = j; sc.type = PREP_SCALE; sc.O = (int)r.n; sc.dst = r.dst2; prep_add(t, sc); }
+                j.type = PREP_TAPS; j.O = r.A; j.I = r.Bc;
+            }
+            prep_add(t, j);
+        }
+}
+// One launch per network rebuilds everything derived from its arena.  sg / sd: the lanes the two launches go to.
 // conv1_x != nullptr (G step, no spectral norm): the D table's launch also runs the first-block forward of conv1_B images at
 // conv1_x into workspace rows [conv1_r0, ...) -- it reads the raw block-1 weights, not a pack (launch_prepare_conv1)
 static void repack(const siggan_ctx* c, Lanes& L, hipStream_t sg, hipStream_t sd, bool do_g, bool do_d, int sn_slot = 0, const float* conv1_x = nullptr,
                    int conv1_r0 = 0, int conv1_B = 0) {
+    PrepTable t;
     if (do_g) {
-        PrepTable t; t.njobs = 0; t.overflow = 0;
-        PrepJob j; memset(&j, 0, sizeof j);
-        if (!c->fc_fused) {                                            // the generic fc kernel reads a k-major copy
-            j.type = PREP_FC_T; j.O = c->latent; j.I = c->gC[0]; j.src = GP(c, gi_fc_w()); j.dst = c->wfc_t;
-            prep_add(t, j, (long long)c->latent * c->F);
-        }
-        for (int l = 1; l <= c->Lg; ++l) {
-            const long long n = (long long)c->gC[l - 1] * c->gC[l] * 16;
-            memset(&j, 0, sizeof j);
-            j.src = GP(c, gi_up_w(l)); j.dt = c->dt;                   // (Cin, Cout, 4, 4)
-            j.type = PREP_PACK_UP; j.I = c->gC[l - 1]; j.O = c->gC[l]; j.dst = (float*)c->g_up[l];   // forward: contract Cin
-            prep_add(t, j, n);
-            j.type = PREP_PACK_DOWN; j.O = c->gC[l - 1]; j.I = c->gC[l]; j.dst = (float*)c->g_dn[l]; // input-gradient: out = Cin
-            prep_add(t, j, n);
-        }
-        for (int l = 0; l <= c->Lg; ++l) {
-            const int C = l == 0 ? c->F : c->gC[l];
-            memset(&j, 0, sizeof j);
-            j.type = PREP_BN_EVAL; j.O = C; j.perm = l == 0 ? c->gC[0] : 0;
-            j.src = GP(c, gi_bn_w(l)); j.src2 = GP(c, gi_bn_b(l));
-            j.src3 = c->st.g_bn_running_mean + c->g_bn_off[l]; j.src4 = c->st.g_bn_running_var + c->g_bn_off[l];
-            j.dst = c->g_bne[l];
-            prep_add(t, j, C);
-        }
-        memset(&j, 0, sizeof j);                                       // final conv: [tap][c] for the strip kernels
-        j.type = PREP_TAPS; j.I = 9; j.O = c->gC[c->Lg]; j.src = GP(c, gi_fin_w(c)); j.dst = c->wfin_t;
-        prep_add(t, j, 9 * j.O);
+        prep_table(c, 0, 0, t);
         if (!launch_prepare(t, BN_EPS, sg)) L.note(hipErrorInvalidValue);          // table overflow: reported by the caller
     }
     if (do_d) {
-        PrepTable t; t.njobs = 0; t.overflow = 0;
-        PrepJob j;
-        for (int l = 2; l <= c->Ld; ++l) {
-            const long long n = (long long)c->dC[l - 1] * c->dC[l] * 16;
-            memset(&j, 0, sizeof j);
-            j.src = DP(c, di_w(l)); j.dt = c->dt;                      // (Cout, Cin, 4, 4)
-            if (c->sn) j.mul = c->sn_sig + (sn_slot * 2 + 1) * SnTable::MAXS + (l - 1);   // W / sigma of this pass
-            j.type = PREP_PACK_DOWN; j.O = c->dC[l]; j.I = c->dC[l - 1]; j.dst = (float*)c->d_dn[l];  // forward
-            prep_add(t, j, n);
-            j.type = PREP_PACK_UP; j.I = c->dC[l]; j.O = c->dC[l - 1]; j.dst = (float*)c->d_up[l];    // input-gradient: contract Cout
-            prep_add(t, j, n);
-        }
-        memset(&j, 0, sizeof j);
-        j.type = PREP_CLS; j.O = c->dC[c->Ld]; j.src = DP(c, di_cls_w(c)); j.dst = c->wcp;
-        if (c->sn) j.mul = c->sn_sig + (sn_slot * 2 + 1) * SnTable::MAXS + c->Ld;
-        prep_add(t, j, (long long)c->dC[c->Ld] * 16);
-        if (c->sn) {                                                   // block 1 is not an MFMA kernel: an fp32 scaled copy
-            memset(&j, 0, sizeof j);
-            j.type = PREP_SCALE; j.O = c->dC[1] * 16; j.src = DP(c, di_w(1)); j.dst = c->d_w1s;
-            j.mul = c->sn_sig + (sn_slot * 2 + 1) * SnTable::MAXS;
-            prep_add(t, j, j.O);
-        }
-        memset(&j, 0, sizeof j);                                       // block 1 as [tap][co] for its input-gradient kernel
-        j.type = PREP_TAPS; j.I = 16; j.O = c->dC[1]; j.src = DP(c, di_w(1)); j.dst = c->d_w1t;
-        if (c->sn) j.mul = c->sn_sig + (sn_slot * 2 + 1) * SnTable::MAXS;
-        prep_add(t, j, j.O * 16);
+        prep_table(c, 1, sn_slot, t);
         bool ok;
         if (conv1_x && !c->sn) {
             const int64_t H = c->S >> 1;
@@ -747,63 +778,23 @@ static void repack(const siggan_ctx* c, Lanes& L, hipStream_t sg, hipStream_t sd
         if (!ok) L.note(hipErrorInvalidValue);
     }
 }
-
-// The job tables of the one-launch update (launch_adam_pack): the whole arena, tensor by tensor, with what launch_prepare
-// would derive from each.  false: this context keeps the two-launch path (the generic fc kernel's k-major copy, channel
-// counts the 16 x 16 tiles do not divide).
-static bool ap_table_g(const siggan_ctx* c, ApTable& t) {
-    if (!c->fc_fused || c->gC[c->Lg] * 9 > 1024) return false;
-    for (int l = 0; l <= c->Lg; ++l) if (c->gC[l] % 16) return false;
+// k_adam_pack's jobs of network `which` (c->packable[which]) from the same records: the whole arena, record by record, so
+// the Discriminator's block 1 -- what the nride riders read -- comes first
+static void ap_table(const siggan_ctx* c, int which, int nride, ApTable& t) {
     t.njobs = 0; t.overflow = 0;
-    ApJob j;
-    memset(&j, 0, sizeof j);                                           // fc weight + bias: adjacent in the arena, nothing derived
-    j.type = AP_FLAT; j.off = c->g_off[gi_fc_w()]; j.n = c->g_num[gi_fc_w()] + c->g_num[gi_fc_b()];
-    ap_add(t, j);
-    for (int l = 0; l <= c->Lg; ++l) {
-        if (l > 0) {
-            memset(&j, 0, sizeof j);                                   // (Cin, Cout, 4, 4): forward contracts Cin, input-gradient Cout
-            j.type = AP_CONV; j.A = c->gC[l - 1]; j.Bc = c->gC[l]; j.dt = c->dt; j.off = c->g_off[gi_up_w(l)];
-            j.dst = (float*)c->g_dn[l]; j.dst2 = (float*)c->g_up[l];
-            ap_add(t, j);
-        }
-        memset(&j, 0, sizeof j);
-        j.type = AP_BN; j.A = l == 0 ? c->F : c->gC[l]; j.Bc = l == 0 ? c->gC[0] : 0;
-        j.off = c->g_off[gi_bn_w(l)]; j.off2 = c->g_off[gi_bn_b(l)];
-        j.rmean = c->st.g_bn_running_mean + c->g_bn_off[l]; j.rvar = c->st.g_bn_running_var + c->g_bn_off[l];
-        j.dst = c->g_bne[l];
+    for (const Derived& r : c->rec[which]) {
+        ApJob j; memset(&j, 0, sizeof j);
+        j.off = r.off; j.dst = r.dst;
+        if (r.kind == DV_FLAT || r.kind == DV_FC) { j.type = AP_FLAT; j.n = r.n + r.n2; ap_add(t, j); continue; }
+        j.A = r.A; j.Bc = r.Bc;
+        if (r.kind == DV_CONV) { j.type = AP_CONV; j.dt = c->dt; j.dst2 = r.dst2; }
+        else if (r.kind == DV_T16) j.type = AP_T16;
+        else if (r.kind == DV_BN) {
+            j.type = AP_BN; j.off2 = r.off2;
+            j.rmean = c->st.g_bn_running_mean + r.bn_off; j.rvar = c->st.g_bn_running_var + r.bn_off;
+        } else { j.type = AP_TAPS; j.n = r.n; j.off2 = r.off2; j.n2 = r.n2; j.wait = nride; }
         ap_add(t, j);
     }
-    memset(&j, 0, sizeof j);                                           // final conv: [tap][c] for the strip kernels, and its bias
-    j.type = AP_TAPS; j.A = c->gC[c->Lg]; j.Bc = 9; j.off = c->g_off[gi_fin_w(c)]; j.n = 9 * c->gC[c->Lg];
-    j.off2 = c->g_off[gi_fin_b(c)]; j.n2 = 1; j.dst = c->wfin_t;
-    ap_add(t, j);
-    return !t.overflow;
-}
-static bool ap_table_d(const siggan_ctx* c, ApTable& t, int nride) {
-    if (c->sn || c->dC[1] * 16 > 1024 || c->dC[1] > 256) return false;     // (spectral norm: the packs follow sigma, not the update)
-    for (int l = 1; l <= c->Ld; ++l) if (c->dC[l] % 16) return false;
-    t.njobs = 0; t.overflow = 0;
-    ApJob j;
-    memset(&j, 0, sizeof j);                                           // block 1 (weight + bias: what the riders read) first
-    j.type = AP_TAPS; j.A = c->dC[1]; j.Bc = 16; j.off = c->d_off[di_w(1)]; j.n = 16 * c->dC[1];
-    j.off2 = c->d_off[di_b(1)]; j.n2 = c->dC[1]; j.dst = c->d_w1t; j.wait = nride;
-    ap_add(t, j);
-    for (int l = 2; l <= c->Ld; ++l) {
-        memset(&j, 0, sizeof j);                                       // (Cout, Cin, 4, 4): forward contracts Cin, input-gradient Cout
-        j.type = AP_CONV; j.A = c->dC[l]; j.Bc = c->dC[l - 1]; j.dt = c->dt; j.off = c->d_off[di_w(l)];
-        j.dst = (float*)c->d_dn[l]; j.dst2 = (float*)c->d_up[l];
-        ap_add(t, j);
-        memset(&j, 0, sizeof j);
-        j.type = AP_FLAT; j.off = c->d_off[di_b(l)]; j.n = c->dC[l];
-        ap_add(t, j);
-    }
-    memset(&j, 0, sizeof j);
-    j.type = AP_T16; j.A = c->dC[c->Ld]; j.off = c->d_off[di_cls_w(c)]; j.dst = c->wcp;
-    ap_add(t, j);
-    memset(&j, 0, sizeof j);
-    j.type = AP_FLAT; j.off = c->d_off[di_cls_b(c)]; j.n = 1;
-    ap_add(t, j);
-    return !t.overflow;
 }
 
 // The ONE place the geometry of a 4x4 stride-2 implicit GEMM is derived.  form 0 ("down", a stride-2 convolution or the input-
@@ -1283,15 +1274,21 @@ static void phase_g_grads(const siggan_ctx* c, Lanes& L, const PhaseKey& k, Phas
     if (real_early && c->dt != DT_F32) { L.wait(L.m, c->ev_dreal); r.dreal_joined = 1; }
 }
 
+// one network's optimiser state (which: 0 G, 1 D): its arenas, their size and tensor count, its two metric slots
+struct Net { float *p, *g, *m, *v, *steps; int64_t n; int nt, m_norm, m_skipped; };
+static Net net_of(const siggan_ctx* c, int which) {
+    const siggan_storage& s = c->st;
+    if (which == 0) return {s.g_params, s.g_grads, s.g_exp_avg, s.g_exp_avg_sq, s.g_adam_steps, c->g_total, (int)c->g_off.size(),
+                            SIGGAN_M_G_GRAD_NORM, SIGGAN_M_G_SKIPPED};
+    return {s.d_params, s.d_grads, s.d_exp_avg, s.d_exp_avg_sq, s.d_adam_steps, c->d_total, (int)c->d_off.size(),
+            SIGGAN_M_D_GRAD_NORM, SIGGAN_M_D_SKIPPED};
+}
+
 static void phase_apply(const siggan_ctx* c, Lanes& L, const PhaseKey& k, PhaseResult& r) {
     const int which = k.phase == 2 ? 1 : 0;                          // phase 2 = D apply, 3 = G apply
-    float* p = which == 0 ? c->st.g_params : c->st.d_params;
-    float* g = which == 0 ? c->st.g_grads : c->st.d_grads;
-    float* m = which == 0 ? c->st.g_exp_avg : c->st.d_exp_avg;
-    float* v = which == 0 ? c->st.g_exp_avg_sq : c->st.d_exp_avg_sq;
-    float* steps = which == 0 ? c->st.g_adam_steps : c->st.d_adam_steps;
-    const int64_t n = which == 0 ? c->g_total : c->d_total;
-    const int nt = (int)(which == 0 ? c->g_off.size() : c->d_off.size());
+    const Net N = net_of(c, which);
+    float* const g = N.g;
+    float *const mt_norm = k.mt + N.m_norm, *const mt_skipped = k.mt + N.m_skipped;
     const bool clip = k.clip > 0.f;
     // the arena holds gscale x the gradient (fp16 chains; 1 otherwise): the optimiser's multiplier takes it out again, and
     // the gradient is written back unscaled (as torch leaves a clipped .grad)
@@ -1312,13 +1309,13 @@ static void phase_apply(const siggan_ctx* c, Lanes& L, const PhaseKey& k, PhaseR
             if (e != NCCL_SUCCESS) { L.comm_fail(e); return; }
             L.wait(L.m, c->ev_ar);
         } else {
-        const int e = rccl()->AllReduce(g, g, (size_t)n, NCCL_FLOAT32, NCCL_SUM, c->comm, L.m);
+        const int e = rccl()->AllReduce(g, g, (size_t)N.n, NCCL_FLOAT32, NCCL_SUM, c->comm, L.m);
         if (e != NCCL_SUCCESS) { L.comm_fail(e); return; }
         }
         gs *= 1.0f / (float)c->comm_world;
     }
     const bool guard = c->dt == DT_F16;                              // static gradient scale: skip the update on an overflow
-    if (clip || guard) launch_grad_sumsq(g, n, c->dev, c->partial, L.m);
+    if (clip || guard) launch_grad_sumsq(g, N.n, c->partial, L.m);
     if (k.fused_t > 0.0 && k.pack) {
         // ... and the same launch rebuilds what the next pass derives from the arena (weight packs, eval tables): no
         // k_prepare between the update and the forward pass that follows it on the step's critical lane
@@ -1331,25 +1328,22 @@ static void phase_apply(const siggan_ctx* c, Lanes& L, const PhaseKey& k, PhaseR
             rd.dt = c->dt; rd.slope = c->cfg.leaky_slope; rd.w_off = c->d_off[di_w(1)]; rd.b_off = c->d_off[di_b(1)];
             rd.counter = (unsigned*)c->ride_ctr; rd.late = c->ride_late_dev;
         }
-        const bool ok = (which == 0 ? ap_table_g(c, t) : ap_table_d(c, t, k.ride ? k.ride * (c->S / 4) : 0)) &&
-            launch_adam_pack(t, p, g, m, v, c->dev, steps, nt, k.fused_t, k.lr, k.beta1, k.beta2, k.eps, gs, k.clip,
-                             k.mt + (which == 0 ? SIGGAN_M_G_GRAD_NORM : SIGGAN_M_D_GRAD_NORM), clip ? c->partial : nullptr,
-                             k.mt + (which == 0 ? SIGGAN_M_G_SKIPPED : SIGGAN_M_D_SKIPPED), BN_EPS, k.ride ? &rd : nullptr, L.m);
-        if (!ok) L.note(hipErrorInvalidValue);                          // (apply_common checked the table: not reached)
+        ap_table(c, which, k.ride * (c->S / 4), t);
+        if (!launch_adam_pack(t, N.p, g, N.m, N.v, c->dev, N.steps, N.nt, k.fused_t, k.lr, k.beta1, k.beta2, k.eps, gs, k.clip, mt_norm,
+                              clip ? c->partial : nullptr, mt_skipped, BN_EPS, k.ride ? &rd : nullptr, L.m))
+            L.note(hipErrorInvalidValue);                               // (table overflow: not reached)
         return;
     }
     if (k.fused_t > 0.0) {
         // ONE launch: the host knows the step count (apply_common), so the bias corrections are kernel arguments and
         // k_adam_prepare (a 5 us kernel plus a kernel boundary on the step's critical lane, twice per step) is not needed
-        launch_adam_fused(p, g, m, v, n, c->dev, steps, nt, k.fused_t, k.lr, k.beta1, k.beta2, k.eps, gs, k.clip,
-                          k.mt + (which == 0 ? SIGGAN_M_G_GRAD_NORM : SIGGAN_M_D_GRAD_NORM), clip ? c->partial : nullptr, L.m,
-                          k.mt + (which == 0 ? SIGGAN_M_G_SKIPPED : SIGGAN_M_D_SKIPPED));
+        launch_adam_fused(N.p, g, N.m, N.v, N.n, c->dev, N.steps, N.nt, k.fused_t, k.lr, k.beta1, k.beta2, k.eps, gs, k.clip, mt_norm,
+                          clip ? c->partial : nullptr, L.m, mt_skipped);
         return;
     }
-    launch_adam_prepare(c->dev, steps, nt, k.lr, k.beta1, k.beta2, gs, k.clip,
-                        k.mt + (which == 0 ? SIGGAN_M_G_GRAD_NORM : SIGGAN_M_D_GRAD_NORM), L.m, guard ? 1 : 0,
-                        k.mt + (which == 0 ? SIGGAN_M_G_SKIPPED : SIGGAN_M_D_SKIPPED), (clip || guard) ? c->partial : nullptr);
-    launch_adam(p, g, m, v, n, c->dev, k.beta1, k.beta2, k.eps, (clip || gs != 1.0f) ? 1 : 0, L.m);
+    launch_adam_prepare(c->dev, N.steps, N.nt, k.lr, k.beta1, k.beta2, gs, k.clip, mt_norm, L.m, guard ? 1 : 0, mt_skipped,
+                        (clip || guard) ? c->partial : nullptr);
+    launch_adam(N.p, g, N.m, N.v, N.n, c->dev, k.beta1, k.beta2, k.eps, (clip || gs != 1.0f) ? 1 : 0, L.m);
 }
 
 static PhaseResult run_phase_body(const siggan_ctx* c, Lanes& L, const PhaseKey& k) {
@@ -1750,9 +1744,8 @@ static int apply_common(siggan_ctx* c, int which, const siggan_hyper* hp, float*
     if ((rc = check_hyper(hp))) return rc;
     if (cs.pending != (which == 1 ? 1 : 2))
         return fail(SIGGAN_E_STATE, "siggan_%c_apply without a preceding siggan_%c_grads", which ? 'd' : 'g', which ? 'd' : 'g');
-    const float* need[] = {which ? c->st.d_grads : c->st.g_grads, which ? c->st.d_exp_avg : c->st.g_exp_avg,
-                           which ? c->st.d_exp_avg_sq : c->st.g_exp_avg_sq, which ? c->st.d_adam_steps : c->st.g_adam_steps};
-    for (const float* p : need)
+    const Net N = net_of(c, which);
+    for (const float* p : {N.g, N.m, N.v, N.steps})
         if (!p) return fail(SIGGAN_E_STATE, "gradient / Adam arenas were not bound");
     hipStream_t s = (hipStream_t)stream;
     if ((rc = settle(c, s))) return rc;
@@ -1770,12 +1763,11 @@ static int apply_common(siggan_ctx* c, int which, const siggan_hyper* hp, float*
         if (!c->adam_t_known[wi]) {
             float t0 = 0.f;
             HIPCHK(hipStreamSynchronize(s));
-            HIPCHK(hipMemcpy(&t0, which == 1 ? c->st.d_adam_steps : c->st.g_adam_steps, sizeof t0, hipMemcpyDeviceToHost));
+            HIPCHK(hipMemcpy(&t0, N.steps, sizeof t0, hipMemcpyDeviceToHost));
             c->adam_t[wi] = (double)t0; c->adam_t_known[wi] = true;
         }
         k.fused_t = c->adam_t[wi] + 1.0;
-        ApTable probe;
-        k.pack = (which == 0 ? ap_table_g(c, probe) : ap_table_d(c, probe, 0)) ? 1 : 0;
+        k.pack = c->packable[which] ? 1 : 0;
         // trainer step with the G step's training forward already enqueued (siggan_step_begin): its first Discriminator block
         // needs nothing but the updated block-1 weights -- it rides in the update's launch (phase_g_grads then skips it).
         // fp32 only: 1.4201 -> 1.4105 ms; at bf16 the separate launch measured better (0.6216 vs 0.6245 ms)
@@ -1880,7 +1872,7 @@ extern "C" int siggan_op_conv4x4s2(siggan_ctx* c, int32_t form, const void* in_d
     j.src = w_dev; j.dst = (float*)c->op_pack; j.dt = c->dt;
     if (form == 0) { j.type = PREP_PACK_DOWN; j.O = c_out; j.I = c_in; }
     else           { j.type = PREP_PACK_UP; j.I = c_in; j.O = c_out; }
-    prep_add(t, j, (long long)c_in * c_out * 16);
+    prep_add(t, j);
     if (!launch_prepare(t, BN_EPS, s)) return fail(SIGGAN_E_STATE, "prepare table overflow");
     launch_gconv(a, s);
     LAUNCHCHK();
@@ -1916,7 +1908,7 @@ extern "C" int siggan_op_adam(siggan_ctx* c, float* p, float* g, float* m, float
     HIPCHK(hipMemcpyAsync(steps, &prev, sizeof prev, hipMemcpyHostToDevice, s));
     const bool clip = hp->clip_max_norm > 0.f;
     const float gs = hp->grad_scale > 0.f ? hp->grad_scale : 1.0f;
-    if (clip) launch_grad_sumsq(g, n, c->dev, c->partial, s);
+    if (clip) launch_grad_sumsq(g, n, c->partial, s);
     launch_adam_prepare(c->dev, steps, 1, hp->lr, hp->beta1, hp->beta2, gs, hp->clip_max_norm, nullptr, s, 0, nullptr,
                         clip ? c->partial : nullptr);
     launch_adam(p, g, m, v, n, c->dev, hp->beta1, hp->beta2, hp->eps, (clip || gs != 1.0f) ? 1 : 0, s);
