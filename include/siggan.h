@@ -51,7 +51,8 @@ extern "C" {
                                 * 4: siggan_config.g_leaky_slope (appended); siggan_prof_launch (a test hook, added);
                                 *    siggan_g_generate_u8, siggan_image_stats (added: no existing call or struct changes);
                                 *    siggan_d_score_u8, siggan_dequant_table (added likewise); siggan_g_latent_grad (added likewise);
-                                *    siggan_g_latent_objective_grad with its struct siggan_latent_objective, added likewise */
+                                *    siggan_g_latent_objective_grad with its struct siggan_latent_objective, added likewise;
+                                *    siggan_g_param_grad, siggan_op_anchor (added likewise) */
 
 enum {
     SIGGAN_OK = 0,
@@ -255,6 +256,38 @@ int siggan_g_latent_objective_grad(siggan_ctx *ctx, const float *z_dev, int32_t 
                                    const float *target_f32_dev, const siggan_latent_objective *w, float *dz_dev,
                                    float *objective_dev, float *terms_dev, float *probs_dev, float *images_dev, void *stream);
 
+/* The gradient with respect to the Generator's PARAMETERS of the same per-image objective, summed over the batch: what adapts
+ * the model to a handful of target signatures (pivotal tuning: hold the projected latents fixed, run Adam on the weights).
+ * obj_b = w_r * mean((G(z_b) - t_b)^2) + w_d * -max(log D(G(z_b)), -100), both networks in eval mode, the expressions, the
+ * byte dequantisation and the count of 1 per image of siggan_g_latent_objective_grad; prior_weight must be 0 (the prior does
+ * not depend on the parameters).  BatchNorm is the fixed per-channel affine of its running statistics: one sample is fine,
+ * nothing moves, dbeta[c] = sum dpost, dgamma[c] = sum dpost * xhat with xhat from the pre-BatchNorm tensor and the running
+ * statistics -- right for gamma of either sign and for gamma == 0 -- and no batch-correction terms.
+ *   dparams_dev            required, 16-byte aligned, caller-owned (NOT the bound g_grads): siggan_param_count(ctx, 0) floats
+ *                          in the arena's layout (siggan_param_span); receives sum_b d obj_b / d theta -- pass grad_scale = 1/B
+ *                          to siggan_op_adam for the mean
+ *   first_layer            0 .. Lg + 1 (Lg = siggan_bn_layers(ctx) - 1 blocks).  Layer 0: fc.0.{weight,bias}, fc.1.{weight,bias};
+ *                          layer l = 1 .. Lg: upsample_blocks.{l-1} (ConvT weight, BatchNorm weight, bias); layer Lg + 1:
+ *                          final_conv.0.{weight,bias}.  Tensors of layers >= first_layer get their gradient, the spans below
+ *                          are written as 0, and the backward chain stops where it is no longer needed (Lg + 1: no block GEMM;
+ *                          l: the input-gradient GEMMs of blocks Lg .. l + 1 only)
+ *   objective_dev (B)      optional;  terms_dev (3,B) optional, the prior row written as 0;  probs_dev (B) optional, requires
+ *                          realism_weight > 0;  images_dev (B,1,S,S) optional, 16-byte aligned
+ * Refused with SIGGAN_E_INVALID, nothing enqueued: what siggan_g_latent_objective_grad refuses, prior_weight != 0, both
+ * weights 0, first_layer out of range, a null or misaligned dparams_dev.  SIGGAN_E_STATE between siggan_step_begin and its
+ * siggan_g_grads.
+ * Bits: fixed-order sums, no float atomics -- two calls on equal inputs give equal bits; byte and fp32 targets holding the same
+ * values give the same bits; the trainable spans do not depend on first_layer.  The forward keeps every block's pre-BatchNorm
+ * tensor (raw GEMM, then the eval affine as its own launch); images, objective, terms and probs are those of
+ * siggan_g_latent_objective_grad to within the README's forward tolerance (the same expression on the same accumulators).
+ * A fixed sequence of launches on the caller's stream, no host synchronisation, capturable.  Parameters, Adam state, the RNG,
+ * the BatchNorm running tensors and counters and u, v are untouched; a train step after it, eager or captured, runs exactly as
+ * if it had not been called. */
+int siggan_g_param_grad(siggan_ctx *ctx, const float *z_dev, int32_t batch, const uint8_t *target_u8_dev,
+                        const float *target_f32_dev, const siggan_latent_objective *w, int32_t first_layer,
+                        float *dparams_dev, float *objective_dev, float *terms_dev, float *probs_dev, float *images_dev,
+                        void *stream);
+
 /* x_dev (B,1,S,S) -> probs_dev (B) probabilities.  features_dev (B,512*4*4, reference
  * flatten order c,h,w) optional.  training!=0 enables Dropout2d: masks_dev, if given, holds the
  * keep masks (1 keep / 0 drop) of all blocks concatenated [(B,C_1),(B,C_2),...]; NULL draws
@@ -361,6 +394,11 @@ int siggan_op_conv4x4s2_wgrad(siggan_ctx *ctx, const void *small_dev, const void
 /* fused Adam over a flat arena (torch.optim.Adam single step, step = count AFTER increment) */
 int siggan_op_adam(siggan_ctx *ctx, float *p_dev, float *g_dev, float *m_dev, float *v_dev,
                    int64_t n, int32_t step, const siggan_hyper *hp, void *stream);
+/* g[i] += weight * (p[i] - p0[i]), i < n: the gradient of 0.5 * weight * |p - p0|^2 (an anchor to a snapshot p0 of the
+ * parameters, the regulariser of few-shot adaptation).  Any n >= 1; weight finite and >= 0; three separately rounded fp32
+ * operations per element. */
+int siggan_op_anchor(siggan_ctx *ctx, float *g_dev, const float *p_dev, const float *p0_dev, int64_t n, float weight,
+                     void *stream);
 /* library RNG: n standard normals / n Bernoulli(keep) keep-masks */
 int siggan_op_randn(siggan_ctx *ctx, float *out_dev, int64_t n, void *stream);
 /* Input pipeline (replaces SignatureDataset.__getitem__ + the transform chain of

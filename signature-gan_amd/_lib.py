@@ -101,6 +101,8 @@ _SIGNATURES = {
     "siggan_dequant_table": (C.c_int, [C.POINTER(C.c_float)]),
     "siggan_g_latent_grad": (C.c_int, [_P, _P, _I32, _P, _P, _P, _P, _P, _P]),
     "siggan_g_latent_objective_grad": (C.c_int, [_P, _P, _I32, _P, _P, C.POINTER(LatentObjective), _P, _P, _P, _P, _P, _P]),
+    "siggan_g_param_grad": (C.c_int, [_P, _P, _I32, _P, _P, C.POINTER(LatentObjective), _I32, _P, _P, _P, _P, _P, _P]),
+    "siggan_op_anchor": (C.c_int, [_P, _P, _P, _P, _I64, C.c_float, _P]),
     "siggan_d_step": (C.c_int, [_P, _P, _I32, _P, _P, C.POINTER(Hyper), _P, _P, _P]),
     "siggan_g_step": (C.c_int, [_P, _I32, _P, C.POINTER(Hyper), _P, _P, _P]),
     "siggan_d_grads": (C.c_int, [_P, _P, _I32, _P, _P, C.POINTER(Hyper), _P, _P]),

@@ -137,6 +137,24 @@ void launch_fc_dz(const float* dh, const float* a0, const float* scale0, const f
                   int B, int K, int C0, float gslope, hipStream_t s, const float* z = nullptr, float wpl = 0.f);   // z: dz += wpl * z
 void launch_prior_dz(const float* z, float* dz, int64_t n, float wpl, hipStream_t s);       // dz = wpl * z
 
+// ---- eval-mode parameter gradient (paramgrad.hip): what siggan_g_param_grad adds to the pieces above, fp32 tensors only ------
+// BatchNorm as the fixed affine of eval mode.  g [R][C]: dpost = d(activation output) * act' in, dy = scale[c] * dpost out (in
+// place); y [R][C] the block's PRE-BatchNorm output; bne the eval table [scale | shift | mean | rstd].  dbeta[c] = sum dpost,
+// dgamma[c] = sum dpost * (y - mean) * rstd (right for gamma of either sign and for gamma == 0), two launches, fixed order.
+// false (nothing launched): a channel count the kernel does not cover.
+bool launch_bn_eval_bwd(float* g, const float* y, int64_t R, int C, const float* bne, float* part, int64_t part_cap,
+                        float* dgamma, float* dbeta, hipStream_t s);
+// the final 3x3 conv's dW (torch order [c][kh][kw], C == 32) and db from dpre and the stored last activation a [B][S][S][32];
+// two launches, `part` holds one row of 289 floats per workgroup.  false (nothing launched): part_cap cannot hold them.
+bool launch_final_wgrad_eval(const float* dpre, const float* a, float* part, int64_t part_cap, float* dW, float* db, int B, int S,
+                             hipStream_t s);
+// the fc block: dh [B][F] (NHWC feature order f') = d(activation output) in, scale0[f'] * g_dact(a0) * dh out (in place: what
+// launch_fc_wgrad takes as dy); dgamma / dbeta of the BatchNorm1d in torch order, xhat from z . W + bias formed again
+void launch_fc_bn_eval_bwd(float* dh, const float* a0, const float* bne, const float* W, const float* bias, const float* z,
+                           float* dgamma, float* dbeta, int B, int K, int C0, float gslope, hipStream_t s);
+// g[i] = g[i] + weight * (p[i] - p0[i]), i < n: the gradient of 0.5 * weight * |p - p0|^2 added onto g (siggan_op_anchor)
+void launch_anchor(float* g, const float* p, const float* p0, int64_t n, float weight, hipStream_t s);
+
 // ---- Discriminator pieces -----------------------------------------------------------------
 // first block (Cin = 1): x = two segments (x0: n < n0, x1: the rest), out [B][S/2][S/2][C]
 void launch_conv1_fwd(int dt, const float* x0, int n0, const float* x1, const float* W, const float* b,

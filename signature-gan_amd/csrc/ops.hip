@@ -1950,4 +1950,33 @@ bool launch_adam_pack(const ApTable& t, float* p, float* g, float* m, float* v, 
     return true;
 }
 
+// =========================================================================================
+// siggan_op_anchor: g[i] = g[i] + weight * (p[i] - p0[i]) -- the gradient of 0.5 * weight * |p - p0|^2 added onto g.  Three
+// separately rounded fp32 operations (the file is built without contraction), i.e. numpy's float32 g + w * (p - p0).  VEC (all
+// three pointers 16-byte aligned): a float4 per thread and the n % 4 last elements by the first threads; else one element each.
+// =========================================================================================
+template <bool VEC>
+__global__ __launch_bounds__(256) void k_anchor(float* g, const float* __restrict__ p, const float* __restrict__ p0, int64_t n, float w) {
+    const int64_t i = (int64_t)blockIdx.x * 256 + threadIdx.x;
+    if (VEC) {
+        const int64_t n4 = n >> 2;
+        if (i < n4) {
+            const f32x4 a = ld4<float>(p + i * 4), b = ld4<float>(p0 + i * 4);
+            f32x4 o = ld4<float>(g + i * 4);
+#pragma unroll
+            for (int e = 0; e < 4; ++e) o[e] = o[e] + w * (a[e] - b[e]);
+            st4<float>(g + i * 4, o);
+        }
+        const int64_t j = n4 * 4 + i;                      // the ragged tail: at most three elements
+        if (i < 3 && j < n) g[j] = g[j] + w * (p[j] - p0[j]);
+    } else if (i < n) {
+        g[i] = g[i] + w * (p[i] - p0[i]);
+    }
+}
+void launch_anchor(float* g, const float* p, const float* p0, int64_t n, float weight, hipStream_t s) {
+    const bool vec = (((uintptr_t)g | (uintptr_t)p | (uintptr_t)p0) & 15) == 0;
+    if (vec) hipLaunchKernelGGL((k_anchor<true>), dim3((unsigned)cdiv(n / 4 > 0 ? n / 4 : 1, 256)), dim3(256), 0, s, g, p, p0, n, weight);
+    else hipLaunchKernelGGL((k_anchor<false>), dim3((unsigned)cdiv(n, 256)), dim3(256), 0, s, g, p, p0, n, weight);
+}
+
 }  // namespace siggan

@@ -239,6 +239,7 @@ struct siggan_ctx {
     float *wcp;
     float *slab, *slab_k, *slab_k2, *slab_k3, *partial, *partial_b, *partial_c, *z_g, *img_g, *metrics, *zeros, *wfc_t, *wfin_t, *d_w1t, *real_stage, *mask_stage;
     float* deq_lut;      // the 256 dequantised byte values (siggan_dequant_table), read by siggan_d_score_u8's first block
+    float* ones;         // 64 floats of 1.0f: a BatchNorm scale row that leaves a gradient as it is (siggan_g_param_grad)
     float* lg_tab;       // siggan_g_latent_grad: per-image copies [B][C_l] of the eval-mode BatchNorm scale rows of blocks 1 .. Lg-1
     char *op_pack;
     int64_t slab_floats, slab_k_floats;
@@ -486,6 +487,7 @@ extern "C" int siggan_create(const siggan_config* cfg, siggan_ctx** out) {
         carve(&c->d_w1t, (int64_t)16 * c->dC[1]);
         carve(&c->ride_ctr, 64);
         carve(&c->deq_lut, 256);
+        carve(&c->ones, 64);
         { int64_t sumC = 0; for (int l = 1; l < c->Lg; ++l) sumC += c->gC[l]; carve(&c->lg_tab, Bm * sumC); }
         float* devp = nullptr;
         carve(&devp, 64);
@@ -518,6 +520,7 @@ extern "C" int siggan_create(const siggan_config* cfg, siggan_ctx** out) {
     h.seed = cfg->seed; h.rng_ctr = 0; h.grad_mul = 1.f;
     HIPCHK(hipMemcpy(c->dev, &h, sizeof h, hipMemcpyHostToDevice));
     { float lut[256]; dequant_table(lut); HIPCHK(hipMemcpy(c->deq_lut, lut, sizeof lut, hipMemcpyHostToDevice)); }
+    { float one[64]; for (float& v : one) v = 1.0f; HIPCHK(hipMemcpy(c->ones, one, sizeof one, hipMemcpyHostToDevice)); }
     c->mode = SIGGAN_MODE_OVERLAP;   // hipGraph replay measured slower than eager launches on ROCm 7
     c->evi = 0;
     HIPCHK(hipStreamCreateWithFlags(&c->s_m, hipStreamNonBlocking));
@@ -832,7 +835,9 @@ static WgradCall wgrad_args(const siggan_ctx* c, const void* small, const void* 
 static int g_forward_pass(const siggan_ctx* c, const float* z, int B, bool training, float* img, hipStream_t s,
                            float* partial = nullptr, float* slab_k = nullptr, uint32_t rng_sid = 0, float* z_out = nullptr,
                            hipEvent_t done = nullptr,       // done: completion event of the pass' last launch
-                           uint8_t* u8 = nullptr, int32_t* stats = nullptr, float thr = 0.f) {   // eval only: see launch_final_fwd
+                           uint8_t* u8 = nullptr, int32_t* stats = nullptr, float thr = 0.f,    // eval only: see launch_final_fwd
+                           bool keep_y = false) {   // eval only (siggan_g_param_grad): the blocks run in the training forward's shape --
+                                                    // raw GEMM output kept in g_y[l], then the apply with the EVAL table -- no statistics
     if (!partial) partial = c->partial;
     char* const* const A = training ? c->g_a : c->g_ae;     // (fp32: the same buffers)
     const float gs = c->cfg.g_leaky_slope;                   // the Generator's activation: 0 = ReLU, else LeakyReLU(gs)
@@ -866,6 +871,10 @@ static int g_forward_pass(const siggan_ctx* c, const float* z, int B, bool train
                                   c->st.g_bn_running_var + off, c->st.g_bn_batches + l, c->g_bn[l], partial, 0,
                                   BN_MOMENTUM, BN_EPS, s);
             if (l < c->Lg) launch_bn_relu(c->dt, c->g_y[l], A[l], R, C, c->g_bn[l], gs, s);
+        } else if (keep_y) {      // (g_bne[l] begins [scale | shift], the two rows k_bn_relu reads: the folded epilogue's expression)
+            a.out = c->g_y[l]; a.epi = EPI_RAW;
+            launch_gconv(a, s);
+            launch_bn_relu(c->dt, c->g_y[l], A[l], (int64_t)B * 4 * Hi * Hi, C, c->g_bne[l], gs, s);
         } else {
             a.out = A[l]; a.epi = EPI_AFFINE_RELU; a.scale = c->g_bne[l]; a.shift = c->g_bne[l] + C;
             launch_gconv(a, s);
@@ -1500,6 +1509,32 @@ extern "C" int siggan_g_generate_u8(siggan_ctx* c, const float* z_dev, int32_t b
     return lane_check(c);
 }
 
+// The seeds of the per-image objective's backward pass in dpre = d objective / d(pre-tanh image), from the stored fp32 images
+// `img` of an eval-mode Generator forward -- shared by the latent calls and siggan_g_param_grad (one sequence, the same bits):
+//   [wd > 0]  d_forward_rows at rows [0, B) with stored logits (Ld + 1), the per-image classifier tail k_cls_bwd_eval (1; the
+//     realism terms into `realism`, D(G(z)) into probs_dev when given), the Discriminator's input-gradient chain (Ld - 1) and
+//     the first block's input-gradient times 1 - x^2 into dpre (1): 2 Ld + 2 launches;
+//   [wr > 0]  k_recon_loss (1): the loss partials into partial_b and its seed of dpre -- with wd > 0 added onto the
+//     Discriminator's as fmaf(wr, ., dpre).
+static void objective_seeds(siggan_ctx* c, const float* img, int B, const uint8_t* target_u8_dev, const float* target_f32_dev,
+                            float wr, float wd, float* realism, float* probs_dev, hipStream_t s) {
+    const int Ld = c->Ld, S = c->S;
+    if (wd > 0.f) {
+        c->cs.lP[0] = d_forward_rows(c, img, 0, B, false, s, c->slab_k);            // stored logits: siggan_d_forward's bits
+        launch_cls_bwd_eval(c->logits, nullptr, 0, DP(c, di_cls_b(c)), c->wcp, (const float*)c->d_a[Ld], c->cfg.leaky_slope,
+                            (float*)c->d_dv[Ld], B, c->dC[Ld], wd, realism, probs_dev, s);
+        for (int l = Ld; l >= 2; --l) {
+            GConvArgs a = gconv_args(c, 1, B, S >> l, c->dC[l], c->dC[l - 1]);
+            a.in = c->d_dv[l]; a.wp = c->d_up[l]; a.out = c->d_dv[l - 1];
+            a.epi = EPI_LRELU_BWD; a.aref = c->d_a[l - 1]; a.noise = nullptr; a.slope = c->cfg.leaky_slope;
+            launch_gconv(a, s);
+        }
+        launch_conv1_dgrad_tanh(c->dt, c->d_dv[1], c->d_w1t, img, c->dpre, B, S, c->dC[1], s);
+    }
+    if (wr > 0.f)
+        launch_recon_loss(img, target_u8_dev, target_f32_dev, c->deq_lut, c->dpre, c->partial_b, B, S, s, wr, wd > 0.f);
+}
+
 // The gradient with respect to z of a per-image objective  wr * recon + wd * realism + wp * prior  through the EVAL-mode
 // Generator and, for the realism term -max(log D(G(z)), -100), the EVAL-mode Discriminator (no dropout; spectral norm: W / sigma
 // from the stored u, v, which do not move).  ONE device sequence serves both entry points: siggan_g_latent_grad is the call with
@@ -1530,25 +1565,12 @@ static int latent_objective_grad(siggan_ctx* c, const float* z_dev, int B, const
                                  float* probs_dev, float* images_dev, hipStream_t s) {
     const int rc = begin_eval(c, s, wd > 0.f, false);
     if (rc) return rc;
-    const int Lg = c->Lg, Ld = c->Ld, S = c->S;
+    const int Lg = c->Lg, S = c->S;
     const float gs = c->cfg.g_leaky_slope;
     float* const img = images_dev ? images_dev : c->img;
     c->cs.ga_last_B = g_forward_pass(c, z_dev, B, false, img, s);
     float* const realism = terms_dev ? terms_dev + B : c->dlogit;
-    if (wd > 0.f) {
-        c->cs.lP[0] = d_forward_rows(c, img, 0, B, false, s, c->slab_k);            // stored logits: siggan_d_forward's bits
-        launch_cls_bwd_eval(c->logits, nullptr, 0, DP(c, di_cls_b(c)), c->wcp, (const float*)c->d_a[Ld], c->cfg.leaky_slope,
-                            (float*)c->d_dv[Ld], B, c->dC[Ld], wd, realism, probs_dev, s);
-        for (int l = Ld; l >= 2; --l) {
-            GConvArgs a = gconv_args(c, 1, B, S >> l, c->dC[l], c->dC[l - 1]);
-            a.in = c->d_dv[l]; a.wp = c->d_up[l]; a.out = c->d_dv[l - 1];
-            a.epi = EPI_LRELU_BWD; a.aref = c->d_a[l - 1]; a.noise = nullptr; a.slope = c->cfg.leaky_slope;
-            launch_gconv(a, s);
-        }
-        launch_conv1_dgrad_tanh(c->dt, c->d_dv[1], c->d_w1t, img, c->dpre, B, S, c->dC[1], s);
-    }
-    if (wr > 0.f)
-        launch_recon_loss(img, target_u8_dev, target_f32_dev, c->deq_lut, c->dpre, c->partial_b, B, S, s, wr, wd > 0.f);
+    objective_seeds(c, img, B, target_u8_dev, target_f32_dev, wr, wd, realism, probs_dev, s);
     ScaleTiles t; memset(&t, 0, sizeof t);
     const float* tab[MAXL + 1] = {nullptr};
     float* next = c->lg_tab;
@@ -1621,6 +1643,103 @@ extern "C" int siggan_g_latent_objective_grad(siggan_ctx* c, const float* z_dev,
     if ((rc = check_latent_tensors(c, z_dev, dz_dev, objective_dev, target_u8_dev, target_f32_dev, images_dev))) return rc;
     return latent_objective_grad(c, z_dev, batch, target_u8_dev, target_f32_dev, wr, wd, wp, dz_dev, objective_dev, terms_dev,
                                  probs_dev, images_dev, (hipStream_t)stream);
+}
+
+// The gradient with respect to the Generator's PARAMETERS of the same per-image objective (prior weight 0: it does not depend
+// on them), summed over the batch, into a caller-owned arena-shaped buffer.  Both networks in eval mode; BatchNorm is the fixed
+// per-channel affine of its running statistics, so one sample is fine and nothing moves.  All on the caller's stream:
+//   - the Generator forward in the training forward's SHAPE with the eval tables (g_forward_pass keep_y): fc folded (1), per
+//     block the raw GEMM into g_y[l] and k_bn_relu with g_bne[l] (2 Lg), the final conv (1) -- the folded forward's expression
+//     on the same accumulators, every activation g_a and every pre-BatchNorm tensor g_y[1..Lg] kept: 2 Lg + 2 launches;
+//   - objective_seeds: [wd > 0] 2 Ld + 2, [wr > 0] 1;  k_obj_fin_tiles without tiles (1);
+//   - the final conv's weight / bias gradient from dpre and g_a[Lg] (2);
+//   - [first_layer <= Lg]  the final conv's input-gradient through the last activation with a scale row of ones (1): dpost[Lg];
+//     then for l = Lg .. max(first_layer, 1): k_bn_eval_bwd + k_part_sum (2: dgamma, dbeta, g_da[l] becomes dy = scale * dpost),
+//     k_wgrad on (g_a[l-1], g_da[l]) as in g_backward_pass (1), and, while l > first_layer, the input-gradient GEMM on g_dn[l]
+//     into g_da[l-1] (1) -- EPI_LRELU_BWD on the stored activation without a table (the mask alone: dpost[l-1]) for l >= 2, raw
+//     into block 0;
+//   - [first_layer == 0]  k_fc_bn_eval_bwd (1: the BatchNorm1d sums, g_da[0] becomes d(fc output)) and k_fc_wgrad (1);
+//   - [first_layer > 0]  one memset node over the frozen prefix of dparams.
+// With nb = Lg - max(first_layer, 1) + 1 trainable blocks (0 for first_layer = Lg + 1) and nd = Lg - first_layer input-gradient
+// GEMMs (Lg for first_layer 0, 0 for Lg + 1):  2 Lg + 5 + [wr > 0] + [wd > 0] (2 Ld + 2) + [first_layer <= Lg] (1 + 3 nb + nd)
+// + [first_layer == 0] 2 launches plus split-K tails; at 64x64 with the weights (1, 0): 33 for first_layer 0, 22 for 3, 14 for 5.
+// Of these the implicit GEMMs and weight gradients (what siggan_prof_* counts): Lg + [wd > 0] 2 (Ld - 1) + nb + nd.
+// Scratch: what latent_objective_grad uses (dpre, g_da, partial, partial_b, the activations g_a, with wd > 0 the Discriminator's
+// rows [0, B), logits, dlogit) plus g_y[1..Lg], slab (the weight-gradient slabs, the final conv's partial rows) and probs (the
+// objective when objective_dev is not given) -- all rewritten by a training phase before it reads them, none carried between
+// calls.  Carried: ga_last_B = 0 (every activation was materialised), lP[0] as d_forward_rows left it, and begin_eval's
+// invalidate(INV_ROWS) with wd > 0, exactly as latent_objective_grad.
+static int param_grad(siggan_ctx* c, const float* z_dev, int B, const uint8_t* target_u8_dev, const float* target_f32_dev, float wr,
+                      float wd, int fl, float* dparams, float* objective_dev, float* terms_dev, float* probs_dev, float* images_dev,
+                      hipStream_t s) {
+    const int rc = begin_eval(c, s, wd > 0.f, false);
+    if (rc) return rc;
+    const int Lg = c->Lg, S = c->S;
+    const float gs = c->cfg.g_leaky_slope;
+    float* const img = images_dev ? images_dev : c->img;
+    c->cs.ga_last_B = g_forward_pass(c, z_dev, B, false, img, s, nullptr, nullptr, 0, nullptr, nullptr, nullptr, nullptr, 0.f, true);
+    float* const realism = terms_dev ? terms_dev + B : c->dlogit;
+    objective_seeds(c, img, B, target_u8_dev, target_f32_dev, wr, wd, realism, probs_dev, s);
+    ScaleTiles t; memset(&t, 0, sizeof t);
+    launch_obj_fin_tiles(ObjFin{c->partial_b, recon_loss_parts(S), 1.0f / (float)(S * S), realism, z_dev, c->latent, wr, wd, 0.f,
+                                objective_dev ? objective_dev : c->probs, terms_dev}, B, t, s);
+    auto G_ = [&](int i) { return dparams + c->g_off[i]; };
+    bool ok = launch_final_wgrad_eval(c->dpre, (const float*)c->g_a[Lg], c->slab, c->slab_floats, G_(gi_fin_w(c)), G_(gi_fin_b(c)), B, S, s);
+    if (fl <= Lg) {
+        launch_final_dgrad_eval(c->dpre, c->wfin_t, (const float*)c->g_a[Lg], c->ones, (float*)c->g_da[Lg], B, S, gs, s);
+        for (int l = Lg; l >= (fl > 1 ? fl : 1); --l) {
+            const int Hi = 4 << (l - 1), Ho = 2 * Hi, Ci = c->gC[l - 1], Co = c->gC[l];
+            // (the last 64 floats of `partial` are siggan_op_adam's scratch slot)
+            ok = launch_bn_eval_bwd((float*)c->g_da[l], (const float*)c->g_y[l], (int64_t)B * Ho * Ho, Co, c->g_bne[l], c->partial,
+                                    PARTIAL_FLOATS - 64, G_(gi_bn_w(l)), G_(gi_bn_b(l)), s) && ok;
+            const WgradCall g = wgrad_args(c, c->g_a[l - 1], c->g_da[l], G_(gi_up_w(l)), c->slab, B, Hi, Ci, Co);
+            launch_wgrad(g.w, g.max_splits, s);
+            if (l > fl) {
+                GConvArgs a = gconv_args(c, 0, B, Ho, Co, Ci);
+                a.in = c->g_da[l]; a.wp = c->g_dn[l]; a.out = c->g_da[l - 1]; a.epi = EPI_RAW;
+                if (l >= 2) { a.epi = EPI_LRELU_BWD; a.aref = c->g_a[l - 1]; a.noise = nullptr; a.slope = gs; }
+                launch_gconv(a, s);
+            }
+        }
+    }
+    if (fl == 0) {
+        launch_fc_bn_eval_bwd((float*)c->g_da[0], (const float*)c->g_a[0], c->g_bne[0], GP(c, gi_fc_w()), GP(c, gi_fc_b()), z_dev,
+                              G_(gi_bn0_w()), G_(gi_bn0_b()), B, c->latent, c->gC[0], gs, s);
+        launch_fc_wgrad(c->dt, c->g_da[0], z_dev, G_(gi_fc_w()), G_(gi_fc_b()), B, c->latent, c->gC[0], s);
+    } else {      // the frozen layers' spans: a prefix of the arena
+        const int first = fl > Lg ? gi_fin_w(c) : gi_up_w(fl);
+        HIPCHK(hipMemsetAsync(dparams, 0, (size_t)c->g_off[first] * sizeof(float), s));
+    }
+    if (!ok) return fail(SIGGAN_E_STATE, "siggan_g_param_grad: a reduction's partial rows had no carve (batch too large for the workspace)");
+    LAUNCHCHK();
+    return lane_check(c);
+}
+
+extern "C" int siggan_g_param_grad(siggan_ctx* c, const float* z_dev, int32_t batch, const uint8_t* target_u8_dev,
+                                   const float* target_f32_dev, const siggan_latent_objective* w, int32_t first_layer,
+                                   float* dparams_dev, float* objective_dev, float* terms_dev, float* probs_dev, float* images_dev,
+                                   void* stream) {
+    ENTER(c);
+    int rc = check_call(c, batch);
+    if (rc) return rc;
+    if (c->dt != DT_F32) return fail(SIGGAN_E_INVALID, "siggan_g_param_grad needs an fp32 context (16-bit activations are not built for it)");
+    if (!w) return fail(SIGGAN_E_INVALID, "null weights");
+    const float wr = w->recon_weight, wd = w->realism_weight, wp = w->prior_weight;
+    if (!isfinite(wr) || !isfinite(wd) || !isfinite(wp) || wr < 0.f || wd < 0.f || wp < 0.f)
+        return fail(SIGGAN_E_INVALID, "the objective's weights must be finite and >= 0, got (%g, %g, %g)", (double)wr, (double)wd, (double)wp);
+    if (wp != 0.f) return fail(SIGGAN_E_INVALID, "prior_weight must be 0: the prior does not depend on the parameters, got %g", (double)wp);
+    if (wr == 0.f && wd == 0.f) return fail(SIGGAN_E_INVALID, "both weights of the objective are 0");
+    const int ntargets = (target_u8_dev != nullptr) + (target_f32_dev != nullptr);
+    if (wr > 0.f && ntargets != 1)
+        return fail(SIGGAN_E_INVALID, "recon_weight > 0 needs exactly one of target_u8_dev and target_f32_dev");
+    if (wr == 0.f && ntargets != 0) return fail(SIGGAN_E_INVALID, "a target was given but recon_weight is 0");
+    if (probs_dev && wd == 0.f) return fail(SIGGAN_E_INVALID, "probs_dev needs realism_weight > 0");
+    if (first_layer < 0 || first_layer > c->Lg + 1)
+        return fail(SIGGAN_E_INVALID, "first_layer %d outside [0, %d]", first_layer, c->Lg + 1);
+    if (reinterpret_cast<uintptr_t>(dparams_dev) & 15) return fail(SIGGAN_E_INVALID, "dparams_dev must be 16-byte aligned");
+    if ((rc = check_latent_tensors(c, z_dev, dparams_dev, dparams_dev, target_u8_dev, target_f32_dev, images_dev))) return rc;
+    return param_grad(c, z_dev, batch, target_u8_dev, target_f32_dev, wr, wd, first_layer, dparams_dev, objective_dev, terms_dev,
+                      probs_dev, images_dev, (hipStream_t)stream);
 }
 
 extern "C" int siggan_d_forward(siggan_ctx* c, const float* x_dev, int32_t batch, int32_t training, const float* masks_dev,
@@ -1912,6 +2031,17 @@ extern "C" int siggan_op_adam(siggan_ctx* c, float* p, float* g, float* m, float
     launch_adam_prepare(c->dev, steps, 1, hp->lr, hp->beta1, hp->beta2, gs, hp->clip_max_norm, nullptr, s, 0, nullptr,
                         clip ? c->partial : nullptr);
     launch_adam(p, g, m, v, n, c->dev, hp->beta1, hp->beta2, hp->eps, (clip || gs != 1.0f) ? 1 : 0, s);
+    LAUNCHCHK();
+    return SIGGAN_OK;
+}
+
+extern "C" int siggan_op_anchor(siggan_ctx* c, float* g, const float* p, const float* p0, int64_t n, float weight, void* stream) {
+    if (!c) return fail(SIGGAN_E_INVALID, "null context");
+    if (!g || !p || !p0 || n < 1) return fail(SIGGAN_E_INVALID, "bad argument");
+    if (!isfinite(weight) || weight < 0.f) return fail(SIGGAN_E_INVALID, "weight must be finite and >= 0, got %g", (double)weight);
+    if ((((uintptr_t)g | (uintptr_t)p | (uintptr_t)p0) & 3) != 0) return fail(SIGGAN_E_INVALID, "tensors must be 4-byte aligned");
+    DevGuard dg_(c->cfg.device); HIPCHK(dg_.err);
+    launch_anchor(g, p, p0, n, weight, (hipStream_t)stream);
     LAUNCHCHK();
     return SIGGAN_OK;
 }

@@ -395,6 +395,57 @@ class Engine:
                                                            _ptr(dz), _ptr(obj), _ptr(terms), _ptr(probs), _ptr(img), self._stream()))
         return (dz, obj) + tuple(t for t in (terms, probs, img) if t is not None)
 
+    @property
+    def g_layers(self):
+        """Lg: the number of upsample blocks.  Layer 0 is fc, 1 .. Lg the blocks, Lg + 1 the final conv (g_param_grad)."""
+        return len(layout.G_CHAIN[self.image_size]) - 1
+
+    def layer_span(self, first_layer):
+        """(offset, numel) of the contiguous suffix of the Generator's parameter arena that layers >= ``first_layer`` occupy:
+        what an adaptation with that ``first_layer`` trains (layout.adaptation_plan names the tensors)."""
+        keys = layout.adaptation_plan(first_layer, self.g_layers)[0]
+        total = self.g_params.numel()
+        off = self.g_spans[keys[0]][0]
+        return off, total - off
+
+    def g_param_grad(self, z, target=None, recon_weight=1.0, realism_weight=0.0, first_layer=0, want_terms=False,
+                     want_probs=False, want_images=False, dparams_out=None, objective_out=None):
+        """The gradient with respect to the Generator's parameters of the per-image objective recon_weight * mean((G(z) - t)^2)
+        + realism_weight * -max(log D(G(z)), -100), summed over the batch, both networks in eval mode -- BatchNorm is the fixed
+        affine of its running statistics, nothing moves (siggan_g_param_grad; fp32 contexts).  ``z`` (B, latent), ``target`` as
+        g_latent_grad's, given exactly when recon_weight > 0.  ``first_layer`` (0 .. g_layers + 1): tensors of layers below it
+        get 0 and the backward chain stops early (layer_span).  Returns (dparams, objective[, terms][, probs][, images]):
+        dparams a flat fp32 tensor in g_params' layout (NOT g_grads), objective (B,), terms (3, B) with the prior row 0, probs
+        (B,), images (B, 1, S, S).  ``dparams_out`` / ``objective_out``: caller-owned contiguous fp32 device tensors the results
+        are written into.  Nothing synchronises with the host."""
+        w = check_objective_weights(recon_weight, realism_weight, 0.0, target is not None, want_probs)
+        fl = int(first_layer)
+        if not 0 <= fl <= self.g_layers + 1:
+            raise ValueError(f"first_layer must be in [0, {self.g_layers + 1}], got {first_layer}")
+        z, b, t_u8, t_f32 = self._latent_inputs(z, target, target_optional=True)
+        dp = self._out_f32(dparams_out, (self.g_params.numel(),), "dparams_out")
+        obj = self._out_f32(objective_out, (b,), "objective_out")
+        new = lambda *shape: torch.empty(*shape, dtype=torch.float32, device=self.device)
+        terms = new(3, b) if want_terms else None
+        probs = new(b) if want_probs else None
+        img = new(b, 1, self.image_size, self.image_size) if want_images else None
+        _lib.check(self.lib.siggan_g_param_grad(self._h, _ptr(z), b, _ptr(t_u8), _ptr(t_f32), C.byref(_lib.LatentObjective(*w)), fl,
+                                                _ptr(dp), _ptr(obj), _ptr(terms), _ptr(probs), _ptr(img), self._stream()))
+        return (dp, obj) + tuple(t for t in (terms, probs, img) if t is not None)
+
+    def op_anchor(self, g, p, p0, weight):
+        """g += weight * (p - p0) in place over flat fp32 device tensors of one size (siggan_op_anchor): the gradient of
+        0.5 * weight * |p - p0|^2, the pull back to a snapshot p0."""
+        weight = float(weight)
+        if not math.isfinite(weight) or weight < 0.0:
+            raise ValueError(f"weight must be finite and >= 0, got {weight}")
+        for name, t in (("g", g), ("p", p), ("p0", p0)):
+            if t.device != self.device or t.dtype != torch.float32 or not t.is_contiguous() or t.numel() != g.numel():
+                raise ValueError(f"{name} must be a contiguous float32 tensor of {g.numel()} elements on {self.device}")
+        if g.numel() < 1:
+            raise ValueError("op_anchor needs at least one element")
+        _lib.check(self.lib.siggan_op_anchor(self._h, _ptr(g), _ptr(p), _ptr(p0), g.numel(), weight, self._stream()))
+
     @staticmethod
     def image_stats(x, threshold):
         """int32 (B, 3) per-image stroke counters of a contiguous fp32 (B, ...) device tensor against ``threshold``

@@ -14,7 +14,12 @@ projects two images and writes the strip of frames between them, ``--morph`` alo
 
 ``--refine_by_realism`` is the filter's counterpart that discards nothing: every latent vector is moved up the Discriminator's
 score for a few Adam steps (utils.inference.generate_signatures_refined) and ``<prefix>_refine.json`` records each image's score
-before and after.  ``--project_realism_weight`` / ``--project_prior_weight`` add the same terms to a projection."""
+before and after.  ``--project_realism_weight`` / ``--project_prior_weight`` add the same terms to a projection.
+
+``--adapt PATH`` changes the model instead of the latent vectors (utils.inference.adapt_generator: the images of PATH are
+projected to pivots, then Adam runs on the Generator's weights around the library's eval-mode dL/dtheta); ``--n_samples``
+signatures are then generated at z = pivot[i mod N] + S * randn with S = ``--adapt_sigma`` (default 0.25 * ``--noise_scale``),
+``<prefix>_adapt.json`` records each target's loss before and after, and ``--adapt_save CKPT`` keeps the adapted weights."""
 import argparse
 import json
 import os
@@ -163,6 +168,51 @@ def run_morph(generator, endpoints, output_dir: str, device: torch.device, prefi
     print(f"Saved a morph strip of {n_frames} frames to: {os.path.join(output_dir, prefix + '_morph.png')}")
 
 
+def run_adapt(generator, path: str, output_dir: str, device: torch.device, n_samples: int, prefix: str = "signature",
+              steps: int = 100, lr: float = 1e-4, first_layer: int = 0, anchor_weight: float = 0.0, discriminator=None,
+              realism_weight: float = 0.0, sigma: float = 0.25, save: Optional[str] = None, seed: Optional[int] = None,
+              project_steps: int = 200, project_lr: float = 0.05, project_restarts: int = 1, threshold: Optional[int] = None,
+              transparent: bool = False, config: Optional[Dict[str, Any]] = None) -> None:
+    """Adapt the Generator to the image file / the images of the directory ``path`` (utils.inference.adapt_generator: project
+    them to pivots, then Adam on the weights of layers >= ``first_layer``), then write ``n_samples`` signatures
+    ``<prefix>_%06d.png`` generated at z = pivot[i mod N] + sigma * randn (seeded by ``seed``) and ``<prefix>_adapt.json``:
+    {steps, lr, first_layer, anchor_weight, realism_weight, sigma, trainable: [keys], targets: [{file, loss_before,
+    loss_after}, ...]}.  ``save``: also a checkpoint {generator_state_dict, config} of the adapted weights that
+    load_generator reads back."""
+    from PIL import Image
+    from .utils.inference import adapt_generator, generate_uint8
+    os.makedirs(output_dir, exist_ok=True)
+    files, targets = load_target_images(path, generator.output_size)
+    print(f"Adapting the Generator to {len(files)} signatures ({steps} steps, lr {lr:g}, layers >= {first_layer})...")
+    res = adapt_generator(generator, targets, steps=steps, lr=lr, first_layer=first_layer, anchor_weight=anchor_weight,
+                          discriminator=discriminator, realism_weight=realism_weight, seed=seed,
+                          project_kwargs=dict(steps=project_steps, lr=project_lr, restarts=project_restarts))
+    before, after = res["loss_before"].cpu(), res["loss_after"].cpu()
+    gen = None if seed is None else torch.Generator().manual_seed(int(seed))
+    pivots, n = res["z"], len(files)
+    images, mb = [], generator._require_engine().max_batch
+    for i0 in range(0, n_samples, mb):
+        idx = torch.arange(i0, min(i0 + mb, n_samples)) % n
+        noise = torch.randn(len(idx), generator.latent_dim, generator=gen).to(device)
+        images += [Image.fromarray(arr, mode="L") for arr in generate_uint8(generator, (pivots[idx.to(device)] + sigma * noise).contiguous())]
+    if threshold is not None:
+        images = process_images(images, threshold=threshold, make_transparent=transparent)
+    for i, img in enumerate(images):
+        img.save(os.path.join(output_dir, f"{prefix}_{i + 1:06d}.png"), "PNG")
+    report = {"steps": steps, "lr": lr, "first_layer": first_layer, "anchor_weight": anchor_weight, "realism_weight": realism_weight,
+              "sigma": sigma, "trainable": res["trainable"],
+              "targets": [{"file": f, "loss_before": float(before[i]), "loss_after": float(after[i])} for i, f in enumerate(files)]}
+    with open(os.path.join(output_dir, f"{prefix}_adapt.json"), "w") as f:
+        json.dump(report, f, indent=2)
+    if save:
+        cfg = dict(config or {})
+        cfg.update(latent_dim=generator.latent_dim, image_size=generator.output_size, image_channels=generator.output_channels)
+        torch.save({"generator_state_dict": {k: v.detach().cpu().clone() for k, v in generator.state_dict().items()}, "config": cfg}, save)
+        print(f"Saved the adapted Generator to: {save}")
+    print(f"Objective per target: mean {float(before.mean()):.3e} before, {float(after.mean()):.3e} after")
+    print(f"Saved {len(images)} signatures to: {output_dir}")
+
+
 def get_checkpoint_info(checkpoint_path: str) -> Dict[str, Any]:
     if not os.path.exists(checkpoint_path):
         return {"error": f"Checkpoint not found: {checkpoint_path}"}
@@ -183,6 +233,16 @@ LATER_DEFAULTS = dict(refine_by_realism=False, refine_steps=20, refine_lr=0.02, 
 def opt(a: argparse.Namespace, name: str):
     """A flag of LATER_DEFAULTS: its value on the command line, else its default."""
     return getattr(a, name, LATER_DEFAULTS[name])
+
+
+# the adaptation flags, added later still and kept out of the namespace the same way (adapt_sigma None: 0.25 * --noise_scale)
+ADAPT_DEFAULTS = dict(adapt=None, adapt_steps=100, adapt_lr=1e-4, adapt_first_layer=0, adapt_anchor=0.0, adapt_realism_weight=0.0,
+                      adapt_sigma=None, adapt_save=None)
+
+
+def adapt_opt(a: argparse.Namespace, name: str):
+    """A flag of ADAPT_DEFAULTS: its value on the command line, else its default."""
+    return getattr(a, name, ADAPT_DEFAULTS[name])
 
 
 def parse_args(argv=None) -> argparse.Namespace:
@@ -225,7 +285,34 @@ def parse_args(argv=None) -> argparse.Namespace:
                    help="With --project: weight of -log D(G(z)) beside the pixel error; needs the checkpoint's Discriminator (default: 0)")
     p.add_argument("--project_prior_weight", type=float, **later,
                    help="With --project: weight of the prior term 0.5 * mean(z^2) (default: 0)")
+    p.add_argument("--adapt", type=str, metavar="PATH", **later,
+                   help="Adapt the Generator's weights to an image file, or the images of a directory (pivotal tuning: project, then "
+                        "Adam on the weights), generate n_samples signatures near the pivots and write <prefix>_adapt.json")
+    p.add_argument("--adapt_steps", type=int, **later, help="Adam iterations of an adaptation (default: 100)")
+    p.add_argument("--adapt_lr", type=float, **later, help="Adam learning rate of an adaptation (default: 1e-4)")
+    p.add_argument("--adapt_first_layer", type=int, **later,
+                   help="First trained layer: 0 fc, 1..L the upsample blocks, L+1 the final conv; the layers below stay frozen (default: 0)")
+    p.add_argument("--adapt_anchor", type=float, **later, help="Weight of the pull 0.5 * |theta - theta0|^2 back to the checkpoint (default: 0)")
+    p.add_argument("--adapt_realism_weight", type=float, **later,
+                   help="Weight of -log D(G(z)) beside the pixel error; needs the checkpoint's Discriminator (default: 0)")
+    p.add_argument("--adapt_sigma", type=float, **later,
+                   help="Signatures are generated at z = pivot[i mod N] + SIGMA * randn (default: 0.25 * noise_scale)")
+    p.add_argument("--adapt_save", type=str, metavar="CKPT", **later, help="Also save the adapted Generator as a checkpoint")
     a = p.parse_args(argv)
+    if adapt_opt(a, "adapt") is not None:
+        for flag in ("filter_by_realism", "project", "morph"):
+            if getattr(a, flag) not in (None, False):
+                p.error(f"--adapt and --{flag} are mutually exclusive")
+        if opt(a, "refine_by_realism"):
+            p.error("--adapt and --refine_by_realism are mutually exclusive")
+        sigma = adapt_opt(a, "adapt_sigma")
+        if (adapt_opt(a, "adapt_steps") < 1 or not adapt_opt(a, "adapt_lr") > 0 or adapt_opt(a, "adapt_first_layer") < 0
+                or not adapt_opt(a, "adapt_anchor") >= 0 or not adapt_opt(a, "adapt_realism_weight") >= 0
+                or (sigma is not None and not sigma >= 0)):
+            p.error("--adapt_steps must be >= 1, --adapt_lr > 0, --adapt_first_layer, --adapt_anchor, --adapt_realism_weight and "
+                    "--adapt_sigma >= 0")
+    elif any(hasattr(a, k) for k in ADAPT_DEFAULTS):
+        p.error("the --adapt_* flags need --adapt")
     if opt(a, "refine_by_realism"):
         for flag in ("filter_by_realism", "project", "morph"):
             if getattr(a, flag) not in (None, False):
@@ -264,7 +351,11 @@ def main(argv=None) -> None:
         for k, v in get_checkpoint_info(a.checkpoint).items():
             print(f"  {k}: {v}")
         return
-    generator, _ = load_generator(a.checkpoint, device)
+    if adapt_opt(a, "adapt") is not None:
+        from .utils.inference import load_generator_and_config
+        generator, _, config = load_generator_and_config(a.checkpoint, device)
+    else:
+        generator, _ = load_generator(a.checkpoint, device)
 
     def need_discriminator(flag):
         discriminator = load_discriminator(a.checkpoint, device, image_size=generator.output_size)
@@ -273,6 +364,14 @@ def main(argv=None) -> None:
                      "weights (a full training checkpoint, not a generator-only export)")
         return discriminator
 
+    if adapt_opt(a, "adapt") is not None:
+        w_d, sigma = adapt_opt(a, "adapt_realism_weight"), adapt_opt(a, "adapt_sigma")
+        run_adapt(generator, adapt_opt(a, "adapt"), a.output_dir, device, a.n_samples, a.prefix, adapt_opt(a, "adapt_steps"),
+                  adapt_opt(a, "adapt_lr"), adapt_opt(a, "adapt_first_layer"), adapt_opt(a, "adapt_anchor"),
+                  need_discriminator("--adapt_realism_weight") if w_d > 0 else None, w_d,
+                  0.25 * a.noise_scale if sigma is None else sigma, adapt_opt(a, "adapt_save"), a.seed, a.project_steps,
+                  a.project_lr, a.project_restarts, a.threshold, a.transparent, config)
+        return
     if a.project is not None or a.morph is not None:
         if a.project is not None:
             w_d, w_p = opt(a, "project_realism_weight"), opt(a, "project_prior_weight")

@@ -42,6 +42,29 @@ def discriminator_entries(size, channels=1):
     return e
 
 
+def generator_layer_keys(n_blocks):
+    """[[state_dict parameter keys of layer 0], ..., [of layer n_blocks + 1]] in parameters() order: layer 0 is fc (Linear +
+    BatchNorm1d), layer l = 1 .. n_blocks upsample_blocks.{l-1} (ConvT weight, BatchNorm weight, bias), the last the final conv."""
+    layers = [["fc.0.weight", "fc.0.bias", "fc.1.weight", "fc.1.bias"]]
+    for i in range(n_blocks):
+        p = f"upsample_blocks.{i}.block."
+        layers.append([p + "0.weight", p + "1.weight", p + "1.bias"])
+    layers.append(["final_conv.0.weight", "final_conv.0.bias"])
+    return layers
+
+
+def adaptation_plan(first_layer, n_blocks):
+    """(trainable keys, frozen keys) of a Generator adaptation that trains layers >= ``first_layer`` (0 .. n_blocks + 1) of a
+    Generator with ``n_blocks`` upsample blocks (4 at 64x64, 5 at 128x128), each in parameters() order: the trainable keys are a
+    suffix of the parameter arena, the frozen ones its prefix.  Pure host code."""
+    first_layer, n_blocks = int(first_layer), int(n_blocks)
+    if n_blocks < 1 or not 0 <= first_layer <= n_blocks + 1:
+        raise ValueError(f"first_layer must be in [0, {n_blocks + 1}], got {first_layer}")
+    layers = generator_layer_keys(n_blocks)
+    flat = lambda ls: [k for layer in ls for k in layer]
+    return flat(layers[first_layer:]), flat(layers[:first_layer])
+
+
 def numel(shape):
     n = 1
     for s in shape:

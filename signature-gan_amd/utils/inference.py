@@ -509,6 +509,92 @@ def project_signatures(generator: Generator, targets_u8, steps: int = 200, lr: f
     return out
 
 
+# ---- few-shot adaptation of the Generator's weights (pivotal tuning) --------------------------------------------------------
+def adaptation_plan(first_layer: int, n_blocks: int) -> Tuple[List[str], List[str]]:
+    """(trainable state_dict keys, frozen keys) of an adaptation that trains layers >= ``first_layer`` (layout.adaptation_plan:
+    layer 0 fc, 1 .. n_blocks the upsample blocks, n_blocks + 1 the final conv).  Pure host code."""
+    from .. import layout
+    return layout.adaptation_plan(first_layer, n_blocks)
+
+
+def _check_adapt(steps, lr, first_layer, n_blocks, anchor_weight, realism_weight):
+    import math
+    from ..engine import check_objective_weights
+    if steps < 1 or not lr > 0:
+        raise ValueError(f"steps must be >= 1 and lr > 0, got {steps}, {lr}")
+    adaptation_plan(first_layer, n_blocks)
+    if not math.isfinite(float(anchor_weight)) or anchor_weight < 0:
+        raise ValueError(f"anchor_weight must be finite and >= 0, got {anchor_weight}")
+    check_objective_weights(1.0, realism_weight, 0.0, True)
+
+
+def adapt_generator(generator: Generator, targets_u8, z: Optional[torch.Tensor] = None, steps: int = 100, lr: float = 1e-4,
+                    betas: Tuple[float, float] = (0.9, 0.999), first_layer: int = 0, anchor_weight: float = 0.0,
+                    discriminator: Optional[Discriminator] = None, realism_weight: float = 0.0,
+                    project_kwargs: Optional[Dict[str, Any]] = None, seed: Optional[int] = None) -> Dict[str, Any]:
+    """Adapt the Generator's WEIGHTS to a few target signatures ``targets_u8`` ((N, S, S) uint8, N <= the engine's max_batch) --
+    pivotal tuning: the pivots are ``z`` (N, latent), or project_signatures(generator, targets_u8, seed=seed, **project_kwargs)
+    when ``z`` is None; they stay fixed while Adam runs on the parameters of layers >= ``first_layer`` (adaptation_plan) against
+    mean((G(z) - t)^2) + realism_weight * -log D(G(z)), both networks in eval mode: BatchNorm stays the affine of its running
+    statistics, which do not move.  Every iteration is one Engine.g_param_grad, Engine.op_anchor (``anchor_weight`` != 0: the
+    pull anchor_weight * (theta - theta0) back to the starting weights), Engine.op_adam on the trainable suffix of the arena
+    with the loop's own moments and grad_scale = 1 / N, and Engine.params_changed(); nothing synchronises with the host.
+
+    The Generator's parameters are changed IN PLACE.  Returns a dict: ``z`` the pivots (device), ``history`` (steps, N) the
+    objective at the start of every iteration, ``loss_before`` / ``loss_after`` (N,) device tensors (history[0]; the
+    objective at the adapted weights), ``recon`` (N, S, S) uint8 numpy -- generate_uint8 at the pivots --, ``snapshot`` a
+    device copy of the parameters before the first update (restore_generator puts them back), ``trainable`` the keys."""
+    if generator.training:
+        raise ValueError("adapt_generator needs the Generator in eval() mode (running BatchNorm statistics)")
+    eng = generator._require_engine()
+    _check_adapt(steps, lr, first_layer, eng.g_layers, anchor_weight, realism_weight)
+    if realism_weight > 0 and discriminator is None:
+        raise ValueError("realism_weight > 0 needs the Discriminator")
+    dev, latent, size = eng.device, eng.latent_dim, eng.image_size
+    t = torch.as_tensor(np.ascontiguousarray(targets_u8) if isinstance(targets_u8, np.ndarray) else targets_u8)
+    if t.dtype != torch.uint8 or t.dim() != 3 or tuple(t.shape[1:]) != (size, size):
+        raise ValueError(f"targets_u8 must be uint8 (N, {size}, {size}), got {t.dtype} {tuple(t.shape)}")
+    n = t.shape[0]
+    if n < 1 or n > eng.max_batch:
+        raise ValueError(f"adaptation is few-shot: 1 <= N <= max_batch = {eng.max_batch} targets in one batch, got {n}")
+    if z is None:
+        z = project_signatures(generator, t, seed=seed, **(project_kwargs or {}))[0]
+    z = torch.as_tensor(z, dtype=torch.float32).to(dev).contiguous().clone()
+    if tuple(z.shape) != (n, latent):
+        raise ValueError(f"z must be ({n}, {latent}), got {tuple(z.shape)}")
+    if realism_weight > 0:
+        eng = adopt_discriminator(generator, discriminator)
+    t = t.to(dev).contiguous()
+    off, num = eng.layer_span(first_layer)
+    snapshot = eng.g_params.clone()
+    p, p0 = eng.g_params[off:off + num], snapshot[off:off + num]
+    dparams = torch.empty_like(eng.g_params)
+    g = dparams[off:off + num]
+    m, v = torch.zeros_like(p), torch.zeros_like(p)
+    hist = torch.empty(steps, n, dtype=torch.float32, device=dev)
+    after = torch.empty(n, dtype=torch.float32, device=dev)
+    grad = lambda out: eng.g_param_grad(z, t, 1.0, realism_weight, first_layer, dparams_out=dparams, objective_out=out)
+    for k in range(steps):
+        grad(hist[k])
+        if anchor_weight != 0:
+            eng.op_anchor(g, p, p0, anchor_weight)
+        eng.op_adam(p, g, m, v, k + 1, lr=lr, beta1=betas[0], beta2=betas[1], grad_scale=1.0 / n)
+        eng.params_changed()
+    grad(after)
+    return {"z": z, "history": hist, "loss_before": hist[0].clone(), "loss_after": after, "recon": generate_uint8(generator, z),
+            "snapshot": snapshot, "trainable": adaptation_plan(first_layer, eng.g_layers)[0]}
+
+
+def restore_generator(generator: Generator, snapshot: torch.Tensor) -> None:
+    """Put the parameters adapt_generator saved (its ``snapshot``) back into the Generator's arena."""
+    eng = generator._require_engine()
+    if snapshot.shape != eng.g_params.shape or snapshot.dtype != torch.float32:
+        raise ValueError(f"snapshot must be the float32 ({eng.g_params.numel()},) tensor adapt_generator returned")
+    with torch.no_grad():
+        eng.g_params.copy_(snapshot.to(eng.device))
+    eng.params_changed()
+
+
 def morph_blend(z_a: torch.Tensor, z_b: torch.Tensor, n_frames: int) -> torch.Tensor:
     """(n_frames, latent): frame i is (1 - a) * z_a + a * z_b with a = i / (n_frames - 1), the app's expression
     (app_vanilla_gan_signatures.py:1696-1697) evaluated frame by frame in fp32 on the endpoints' device.  The endpoints are
