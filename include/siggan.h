@@ -52,7 +52,8 @@ extern "C" {
                                 *    siggan_g_generate_u8, siggan_image_stats (added: no existing call or struct changes);
                                 *    siggan_d_score_u8, siggan_dequant_table (added likewise); siggan_g_latent_grad (added likewise);
                                 *    siggan_g_latent_objective_grad with its struct siggan_latent_objective, added likewise;
-                                *    siggan_g_param_grad, siggan_op_anchor (added likewise) */
+                                *    siggan_g_param_grad, siggan_op_anchor (added likewise);
+                                *    siggan_g_latent_objective_grad_seeded (added likewise) */
 
 enum {
     SIGGAN_OK = 0,
@@ -255,6 +256,19 @@ typedef struct siggan_latent_objective {
 int siggan_g_latent_objective_grad(siggan_ctx *ctx, const float *z_dev, int32_t batch, const uint8_t *target_u8_dev,
                                    const float *target_f32_dev, const siggan_latent_objective *w, float *dz_dev,
                                    float *objective_dev, float *terms_dev, float *probs_dev, float *images_dev, void *stream);
+
+/* siggan_g_latent_objective_grad plus <image_grad[b], G(z)[b]> linearised: dz[b,:] additionally receives J_G(z_b)^T image_grad[b]
+ * -- the call becomes a general vector-Jacobian product of the eval-mode Generator (an identity term from the verifier's
+ * siggan_verifier_input_grad on 64x64 contexts, or any image-space loss the caller owns).
+ * image_grad_dev (B,1,S,S) fp32, 16-byte aligned, required (use the unseeded call otherwise).  With a seed all three weights may be 0:
+ * objective_dev is then written as 0.  objective / terms / probs / images never include the seed's term -- the caller owns that loss.
+ * The seed joins d(pre-tanh) behind the Discriminator's and the reconstruction's seeds, in that order: fmaf(seed, 1 - x^2, dpre),
+ * or seed * (1 - x^2) when nothing is there yet (one more launch); everything downstream is the unseeded call's chain, so a zero
+ * seed gives the unseeded call's bits.  Refusals (plus a null or misaligned image_grad_dev; minus "all three weights 0"),
+ * SIGGAN_E_STATE and the "training state untouched" contract are those of siggan_g_latent_objective_grad. */
+int siggan_g_latent_objective_grad_seeded(siggan_ctx *ctx, const float *z_dev, int32_t batch, const uint8_t *target_u8_dev,
+        const float *target_f32_dev, const siggan_latent_objective *w, const float *image_grad_dev, float *dz_dev,
+        float *objective_dev, float *terms_dev, float *probs_dev, float *images_dev, void *stream);
 
 /* The gradient with respect to the Generator's PARAMETERS of the same per-image objective, summed over the batch: what adapts
  * the model to a handful of target signatures (pivotal tuning: hold the projected latents fixed, run Adam on the weights).

@@ -1,4 +1,4 @@
-"""ctypes binding of the C ABI in include/siggan.h (and siggan_mlp.h, siggan_verifier.h, siggan_verifier_train.h,
+"""ctypes binding of the C ABI in include/siggan.h (and siggan_mlp.h, siggan_verifier.h, siggan_verifier_grad.h, siggan_verifier_train.h,
 siggan_verifier_data.h, siggan_moments.h, siggan_select.h, siggan_neighbors.h).
 
 The shared library is built in-tree by ``__graft_entry__.build()`` / ``csrc/Makefile`` and must be
@@ -75,6 +75,10 @@ class VerifierWeights(C.Structure):
     _fields_ = [(n, C.c_void_p) for n in VERIFIER_WEIGHT_FIELDS] + [("bn_eps", C.c_float)]
 
 
+class VerifierIdentity(C.Structure):      # siggan_verifier_identity
+    _fields_ = [("embed_weight", C.c_float), ("score_weight", C.c_float)]
+
+
 _P, _I32, _I64 = C.c_void_p, C.c_int32, C.c_int64
 _SIGNATURES = {
     "siggan_abi_version": (C.c_int, []),
@@ -101,6 +105,7 @@ _SIGNATURES = {
     "siggan_dequant_table": (C.c_int, [C.POINTER(C.c_float)]),
     "siggan_g_latent_grad": (C.c_int, [_P, _P, _I32, _P, _P, _P, _P, _P, _P]),
     "siggan_g_latent_objective_grad": (C.c_int, [_P, _P, _I32, _P, _P, C.POINTER(LatentObjective), _P, _P, _P, _P, _P, _P]),
+    "siggan_g_latent_objective_grad_seeded": (C.c_int, [_P, _P, _I32, _P, _P, C.POINTER(LatentObjective), _P, _P, _P, _P, _P, _P, _P]),
     "siggan_g_param_grad": (C.c_int, [_P, _P, _I32, _P, _P, C.POINTER(LatentObjective), _I32, _P, _P, _P, _P, _P, _P]),
     "siggan_op_anchor": (C.c_int, [_P, _P, _P, _P, _I64, C.c_float, _P]),
     "siggan_d_step": (C.c_int, [_P, _P, _I32, _P, _P, C.POINTER(Hyper), _P, _P, _P]),
@@ -155,6 +160,13 @@ _VERIFIER_SIGNATURES = {
     "siggan_verifier_debug_tensor": (C.c_int, [_P, C.c_char_p, _P, _I64, _P]),
 }
 VERIFIER_EXPORTS = tuple(_VERIFIER_SIGNATURES)
+# the verifier's eval-mode input gradient (include/siggan_verifier_grad.h): again only new symbols, on the same context
+_VERIFIER_GRAD_SIGNATURES = {
+    "siggan_verifier_input_grad_enable": (C.c_int, [_P]),
+    "siggan_verifier_input_grad": (C.c_int, [_P, _P, _P, _I32, C.POINTER(VerifierIdentity), _P, _P, _P, _P, _P, _P]),
+    "siggan_verifier_input_grad_debug": (C.c_int, [_P, C.c_char_p, _P, _I64, _P]),
+}
+VERIFIER_GRAD_EXPORTS = tuple(_VERIFIER_GRAD_SIGNATURES)
 
 # the verifier's train step (include/siggan_verifier_train.h): again only new symbols
 VT_PARAM_TENSORS, VT_METRICS = 20, 4
@@ -227,7 +239,7 @@ def load():
             f"{LIB_PATH} is missing: build it with `python -c 'import __graft_entry__ as g; g.build()'` "
             "(or `make -C signature-gan_amd/csrc`). This path has no CPU/PyTorch fallback.")
     lib = C.CDLL(LIB_PATH)
-    for name, (res, args) in {**_SIGNATURES, **_VERIFIER_SIGNATURES, **_VERIFIER_TRAIN_SIGNATURES,
+    for name, (res, args) in {**_SIGNATURES, **_VERIFIER_SIGNATURES, **_VERIFIER_GRAD_SIGNATURES, **_VERIFIER_TRAIN_SIGNATURES,
                               **_VERIFIER_DATA_SIGNATURES, **_MOMENTS_SIGNATURES, **_SELECT_SIGNATURES,
                               **_NEIGHBORS_SIGNATURES}.items():
         fn = getattr(lib, name)          # AttributeError if the library does not export the symbol

@@ -70,6 +70,32 @@ void launch_recon_loss(const float* img, const uint8_t* t_u8, const float* t_f32
 }
 
 // =========================================================================================
+// a caller-supplied image-space gradient (siggan_g_latent_objective_grad_seeded) joins the seeds of d(pre-tanh):
+// dpre = fmaf(seed, 1 - x * x, dpre) behind the Discriminator's and the reconstruction's, or seed * (1 - x * x) when nothing is
+// there yet.  Four pixels per thread, each element read and written by its own thread.
+// =========================================================================================
+template <bool ONTO>
+__global__ __launch_bounds__(256) void k_seed_dpre(const float* __restrict__ img, const float* __restrict__ seed,
+                                                   float* __restrict__ dpre) {
+    const size_t i = ((size_t)blockIdx.x * 256 + threadIdx.x) * 4;
+    const f4v x = ldg4(img + i), g = ldg4(seed + i);
+    f4v o;
+    if (ONTO) o = ldg4(dpre + i);
+#pragma unroll
+    for (int e = 0; e < 4; ++e) {
+        const float t = 1.0f - x[e] * x[e];
+        o[e] = ONTO ? fmaf(g[e], t, o[e]) : g[e] * t;
+    }
+    *reinterpret_cast<f4v*>(dpre + i) = o;
+}
+
+void launch_seed_dpre(const float* img, const float* seed, float* dpre, int B, int S, bool onto_dpre, hipStream_t s) {
+    const dim3 grid((unsigned)(B * (S * S / 1024)));
+    if (onto_dpre) hipLaunchKernelGGL(k_seed_dpre<true>, grid, dim3(256), 0, s, img, seed, dpre);
+    else hipLaunchKernelGGL(k_seed_dpre<false>, grid, dim3(256), 0, s, img, seed, dpre);
+}
+
+// =========================================================================================
 // the objective and the per-image scale tables, one launch: workgroups [0, nbl) finish the OBJECTIVE, one wave per image (four
 // images per workgroup), the rest copy tile t's scale row once per image (a float4 per thread).  recon: the loss partials in
 // index order, times 1 / S^2 (every lane forms the same sum).  prior 0.5 * mean_k z^2: lane j adds z[j]^2, z[j + 64]^2, ... in

@@ -118,6 +118,8 @@ int recon_loss_parts(int S);
 // wr / onto_dpre (siggan_g_latent_objective_grad): dpre = wr * (the above), or, onto_dpre, dpre = fmaf(wr, the above, dpre).
 void launch_recon_loss(const float* img, const uint8_t* t_u8, const float* t_f32, const float* lut, float* dpre, float* part,
                        int B, int S, hipStream_t s, float wr = 1.0f, bool onto_dpre = false);
+// a caller's image-space gradient `seed` (B, S, S) as a further seed: dpre = seed * (1 - img^2), or, onto_dpre, fmaf(seed, 1 - img^2, dpre)
+void launch_seed_dpre(const float* img, const float* seed, float* dpre, int B, int S, bool onto_dpre, hipStream_t s);
 // ONE launch for the two small jobs behind it: the per-image copies tab[b][c] = scale[c] of nt eval-mode BatchNorm scale rows
 // (what EPI_LRELU_BWD multiplies by as its [B][C] table), and objective[b] = wr * recon + wd * realism + wp * prior (in that
 // order; a weight of 0 leaves its term out and unread) with, optionally, terms[3][B].  recon = (part[b][0] + part[b][1] + ...)

@@ -1559,10 +1559,13 @@ static void objective_seeds(siggan_ctx* c, const float* img, int B, const uint8_
 // says so) and, with wd > 0, the Discriminator's rows [0, B) of d_a and d_dv, logits and dlogit (the realism terms when
 // terms_dev is not given) -- all rewritten by a training phase before it reads them, none carried between calls; what a step
 // carries in those rows is dropped exactly as siggan_d_forward drops it (begin_eval).
+// seed_dev (siggan_g_latent_objective_grad_seeded): a caller-supplied image-space gradient joins dpre behind the two seeds above
+// as k_seed_dpre (1) -- fmaf(seed, 1 - x^2, dpre), or seed * (1 - x^2) when nothing is there yet -- and the backward chain runs
+// whatever the weights; the objective and the terms never include it.  Null: exactly the sequence above.
 // The caller has validated everything: exactly one target when wr > 0 (none otherwise), probs_dev only with wd > 0.
 static int latent_objective_grad(siggan_ctx* c, const float* z_dev, int B, const uint8_t* target_u8_dev, const float* target_f32_dev,
                                  float wr, float wd, float wp, float* dz_dev, float* objective_dev, float* terms_dev,
-                                 float* probs_dev, float* images_dev, hipStream_t s) {
+                                 float* probs_dev, float* images_dev, hipStream_t s, const float* seed_dev = nullptr) {
     const int rc = begin_eval(c, s, wd > 0.f, false);
     if (rc) return rc;
     const int Lg = c->Lg, S = c->S;
@@ -1571,6 +1574,7 @@ static int latent_objective_grad(siggan_ctx* c, const float* z_dev, int B, const
     c->cs.ga_last_B = g_forward_pass(c, z_dev, B, false, img, s);
     float* const realism = terms_dev ? terms_dev + B : c->dlogit;
     objective_seeds(c, img, B, target_u8_dev, target_f32_dev, wr, wd, realism, probs_dev, s);
+    if (seed_dev) launch_seed_dpre(img, seed_dev, c->dpre, B, S, wr > 0.f || wd > 0.f, s);
     ScaleTiles t; memset(&t, 0, sizeof t);
     const float* tab[MAXL + 1] = {nullptr};
     float* next = c->lg_tab;
@@ -1580,7 +1584,7 @@ static int latent_objective_grad(siggan_ctx* c, const float* z_dev, int B, const
     }
     launch_obj_fin_tiles(ObjFin{c->partial_b, recon_loss_parts(S), 1.0f / (float)(S * S), realism, z_dev, c->latent, wr, wd, wp,
                                 objective_dev, terms_dev}, B, t, s);
-    if (wr > 0.f || wd > 0.f) {
+    if (wr > 0.f || wd > 0.f || seed_dev) {
         launch_final_dgrad_eval(c->dpre, c->wfin_t, (const float*)c->g_a[Lg], c->g_bne[Lg], (float*)c->g_da[Lg], B, S, gs, s);
         for (int l = Lg; l >= 1; --l) {
             GConvArgs a = gconv_args(c, 0, B, 4 << l, c->gC[l], c->gC[l - 1]);
@@ -1643,6 +1647,30 @@ extern "C" int siggan_g_latent_objective_grad(siggan_ctx* c, const float* z_dev,
     if ((rc = check_latent_tensors(c, z_dev, dz_dev, objective_dev, target_u8_dev, target_f32_dev, images_dev))) return rc;
     return latent_objective_grad(c, z_dev, batch, target_u8_dev, target_f32_dev, wr, wd, wp, dz_dev, objective_dev, terms_dev,
                                  probs_dev, images_dev, (hipStream_t)stream);
+}
+
+extern "C" int siggan_g_latent_objective_grad_seeded(siggan_ctx* c, const float* z_dev, int32_t batch, const uint8_t* target_u8_dev,
+                                                     const float* target_f32_dev, const siggan_latent_objective* w,
+                                                     const float* image_grad_dev, float* dz_dev, float* objective_dev,
+                                                     float* terms_dev, float* probs_dev, float* images_dev, void* stream) {
+    ENTER(c);
+    int rc = check_call(c, batch);
+    if (rc) return rc;
+    if (c->dt != DT_F32) return fail(SIGGAN_E_INVALID, "siggan_g_latent_objective_grad_seeded needs an fp32 context (16-bit activations are not built for it)");
+    if (!w) return fail(SIGGAN_E_INVALID, "null weights");
+    const float wr = w->recon_weight, wd = w->realism_weight, wp = w->prior_weight;
+    if (!isfinite(wr) || !isfinite(wd) || !isfinite(wp) || wr < 0.f || wd < 0.f || wp < 0.f)
+        return fail(SIGGAN_E_INVALID, "the objective's weights must be finite and >= 0, got (%g, %g, %g)", (double)wr, (double)wd, (double)wp);
+    if (!image_grad_dev) return fail(SIGGAN_E_INVALID, "null image_grad_dev (use siggan_g_latent_objective_grad without a seed)");
+    if (reinterpret_cast<uintptr_t>(image_grad_dev) & 15) return fail(SIGGAN_E_INVALID, "image_grad_dev must be 16-byte aligned");
+    const int ntargets = (target_u8_dev != nullptr) + (target_f32_dev != nullptr);
+    if (wr > 0.f && ntargets != 1)
+        return fail(SIGGAN_E_INVALID, "recon_weight > 0 needs exactly one of target_u8_dev and target_f32_dev");
+    if (wr == 0.f && ntargets != 0) return fail(SIGGAN_E_INVALID, "a target was given but recon_weight is 0");
+    if (probs_dev && wd == 0.f) return fail(SIGGAN_E_INVALID, "probs_dev needs realism_weight > 0");
+    if ((rc = check_latent_tensors(c, z_dev, dz_dev, objective_dev, target_u8_dev, target_f32_dev, images_dev))) return rc;
+    return latent_objective_grad(c, z_dev, batch, target_u8_dev, target_f32_dev, wr, wd, wp, dz_dev, objective_dev, terms_dev,
+                                 probs_dev, images_dev, (hipStream_t)stream, image_grad_dev);
 }
 
 // The gradient with respect to the Generator's PARAMETERS of the same per-image objective (prior weight 0: it does not depend

@@ -1,6 +1,7 @@
-// verifier_parts.h -- device parts the Siamese verifier's inference (verifier.hip) and training (verifier_train.hip)
-// kernels are built from: the geometry, the image loads, the implicit-GEMM tile loop of conv2 / conv3 and the two halves of
-// the fc tail.  Every sum here has one fixed order, and both files get the same one.
+// verifier_parts.h -- device parts the Siamese verifier's inference and input-gradient (verifier.hip) and training
+// (verifier_train.hip) kernels are built from: the geometry, the image loads, the implicit-GEMM tile loop of conv2 / conv3, the
+// raw-store conv kernel and the 64 x 64 GEMM both backward passes run, and the two halves of the fc tail.  Every sum here has
+// one fixed order, and both files get the same one.
 #pragma once
 #include <hip/hip_runtime.h>
 #include <stdint.h>
@@ -121,6 +122,95 @@ __device__ __forceinline__ void conv_tile(const float* __restrict__ x, const flo
             for (int j = 0; j < NACC; ++j) acc[j] = __builtin_amdgcn_mfma_f32_32x32x2f32(a, sB[2 * s + lh][32 * j + li], acc[j], 0, 0, 0);
         }
         __syncthreads();
+    }
+}
+
+// ---------------------------------------------------------------- conv2 / conv3: implicit GEMM, raw store
+// x: (N, H, H, CI) NHWC; wp: [CO][KS*KS*CI]; out: (N, H, H, CO).  conv_tile's 128 x BN block tile over rows in raster order.
+template <int KS, int CI, int CO, int H, int BN>
+__global__ __launch_bounds__(256) void k_tconv(const float* __restrict__ x, const float* __restrict__ wp, float* __restrict__ out) {
+    constexpr int BM = 128, NACC = BN / 32;
+    const int lane = threadIdx.x & 63, wave = threadIdx.x >> 6, li = lane & 31, lh = lane >> 5;
+    const int64_t m0 = (int64_t)blockIdx.x * BM;
+    const int n0 = blockIdx.y * BN;
+    f32x16 acc[NACC];
+    conv_tile<KS, CI, CO, H, BN, RasterRows>(x, wp, m0, n0, acc);
+#pragma unroll
+    for (int j = 0; j < NACC; ++j)
+#pragma unroll
+        for (int r = 0; r < 16; ++r) {
+            const int64_t row = m0 + wave * 32 + (r & 3) + 8 * (r >> 2) + 4 * lh;
+            out[(size_t)row * CO + n0 + 32 * j + li] = acc[j][r];
+        }
+}
+
+// ---------------------------------------------------------------- 64 x 64 MFMA GEMM, operands K- or M/N-contiguous
+// A(m, k) = AKC ? A[m * lda + k] : A[k * lda + m];  B(k, n) = BKC ? B[n * ldb + k] : B[k * ldb + n];
+// C[z][m * ldc + n] over k in [z * Ks, min((z + 1) * Ks, K)).  K-contiguous operands need K % 8 == 0 and Ks % 32 == 0; the other
+// kind needs its M (N) % 4 == 0.  Rows / columns / k outside the problem are staged as zeros and never stored.
+template <bool AKC, bool BKC>
+__global__ __launch_bounds__(256) void k_tgemm(const float* __restrict__ A, const float* __restrict__ B, float* __restrict__ Cm,
+                                               int M, int N, int K, int Ks, int lda, int ldb, int ldc) {
+    constexpr int BK = 32, LD = 64 + 4;
+    __shared__ __attribute__((aligned(16))) float sA[BK][LD];
+    __shared__ __attribute__((aligned(16))) float sB[BK][LD];
+    const int tid = threadIdx.x, lane = tid & 63, wave = tid >> 6, li = lane & 31, lh = lane >> 5;
+    const int wm = wave >> 1, wn = wave & 1;
+    const int n0 = blockIdx.x * 64, m0 = blockIdx.y * 64, kb = blockIdx.z * Ks, ke = min(kb + Ks, K);
+    const int row = tid & 63, qd = tid >> 6;              // K-contiguous staging: (row, 8 k)
+    const int c4 = (tid & 15) * 4, kk = tid >> 4;         // M-contiguous staging: (4 rows, k = kk and kk + 16)
+    f32x16 acc;
+#pragma unroll
+    for (int r = 0; r < 16; ++r) acc[r] = 0.f;
+    for (int k0 = kb; k0 < ke; k0 += BK) {
+        if (AKC) {
+            const bool ok = m0 + row < M;
+#pragma unroll
+            for (int j = 0; j < 2; ++j) {
+                const int k = k0 + qd * 8 + 4 * j;
+                const f32x4 v = (ok && k < ke) ? *reinterpret_cast<const f32x4*>(A + (size_t)(m0 + row) * lda + k) : f32x4{0.f, 0.f, 0.f, 0.f};
+#pragma unroll
+                for (int e = 0; e < 4; ++e) sA[qd * 8 + 4 * j + e][row] = v[e];
+            }
+        } else {
+#pragma unroll
+            for (int j = 0; j < 2; ++j) {
+                const int k = k0 + kk + 16 * j;
+                const f32x4 v = (k < ke && m0 + c4 < M) ? *reinterpret_cast<const f32x4*>(A + (size_t)k * lda + m0 + c4) : f32x4{0.f, 0.f, 0.f, 0.f};
+                *reinterpret_cast<f32x4*>(&sA[kk + 16 * j][c4]) = v;
+            }
+        }
+        if (BKC) {
+            const bool ok = n0 + row < N;
+#pragma unroll
+            for (int j = 0; j < 2; ++j) {
+                const int k = k0 + qd * 8 + 4 * j;
+                const f32x4 v = (ok && k < ke) ? *reinterpret_cast<const f32x4*>(B + (size_t)(n0 + row) * ldb + k) : f32x4{0.f, 0.f, 0.f, 0.f};
+#pragma unroll
+                for (int e = 0; e < 4; ++e) sB[qd * 8 + 4 * j + e][row] = v[e];
+            }
+        } else {
+#pragma unroll
+            for (int j = 0; j < 2; ++j) {
+                const int k = k0 + kk + 16 * j;
+                const f32x4 v = (k < ke && n0 + c4 < N) ? *reinterpret_cast<const f32x4*>(B + (size_t)k * ldb + n0 + c4) : f32x4{0.f, 0.f, 0.f, 0.f};
+                *reinterpret_cast<f32x4*>(&sB[kk + 16 * j][c4]) = v;
+            }
+        }
+        __syncthreads();
+#pragma unroll
+        for (int s = 0; s < BK / 2; ++s)
+            acc = __builtin_amdgcn_mfma_f32_32x32x2f32(sA[2 * s + lh][wm * 32 + li], sB[2 * s + lh][wn * 32 + li], acc, 0, 0, 0);
+        __syncthreads();
+    }
+    float* cz = Cm + (size_t)blockIdx.z * M * ldc;
+    const int nn = n0 + wn * 32 + li;
+    if (nn < N) {
+#pragma unroll
+        for (int r = 0; r < 16; ++r) {
+            const int mm = m0 + wm * 32 + (r & 3) + 8 * (r >> 2) + 4 * lh;
+            if (mm < M) cz[(size_t)mm * ldc + nn] = acc[r];
+        }
     }
 }
 

@@ -6,9 +6,9 @@
 // running mean) -> per-half column sums (mean, then centred sum of squares: partial rows + an ordered sum) -> one pass that
 // applies BatchNorm, ReLU and the 2x2 max and writes the pooled tensor and one route byte per pooled element.
 //   k_tconv1    direct 5x5 stencil (Cin = 1), fp32 or uint8 images
-//   k_tconv     stride-1 implicit GEMM on v_mfma_f32_32x32x2_f32 (verifier_parts.h's conv_tile, the one k_vconv runs; raw store): conv2 / conv3 forward and,
+//   k_tconv     (verifier_parts.h) stride-1 implicit GEMM on v_mfma_f32_32x32x2_f32 (conv_tile, the one k_vconv runs; raw store): conv2 / conv3 forward and,
 //               over a tap-flipped channel-transposed pack, their input gradients
-//   k_tgemm     64 x 64 MFMA tiles with either operand K- or M-contiguous: fc1 forward (16 K slices), dX = dY.W, dW = dY^T.X
+//   k_tgemm     (verifier_parts.h) 64 x 64 MFMA tiles with either operand K- or M-contiguous: fc1 forward (16 K slices), dX = dY.W, dW = dY^T.X
 //   k_ttail     per image row: ordered K-slice sum + bias + ReLU + dropout, fc2, L2 normalise
 //   k_thead     per pair: head forward, both losses and the head's backward down to d(e1) = -d(e2)
 // Backward: k_tembbwd (normalise / fc2 / dropout / ReLU per row), k_tgemm twice, then per conv layer k_bnbwd_red (scatter by
@@ -113,25 +113,6 @@ __global__ __launch_bounds__(256) void k_tconv1_wgrad(const void* __restrict__ x
         const int t = tg + 8 * i;
         if (t < 25) part[(size_t)blockIdx.x * 800 + co * 25 + t] = acc[i];
     }
-}
-
-// ---------------------------------------------------------------- conv2 / conv3: implicit GEMM, raw store
-// x: (N, H, H, CI) NHWC; wp: [CO][KS*KS*CI]; out: (N, H, H, CO).  conv_tile's 128 x BN block tile over rows in raster order.
-template <int KS, int CI, int CO, int H, int BN>
-__global__ __launch_bounds__(256) void k_tconv(const float* __restrict__ x, const float* __restrict__ wp, float* __restrict__ out) {
-    constexpr int BM = 128, NACC = BN / 32;
-    const int lane = threadIdx.x & 63, wave = threadIdx.x >> 6, li = lane & 31, lh = lane >> 5;
-    const int64_t m0 = (int64_t)blockIdx.x * BM;
-    const int n0 = blockIdx.y * BN;
-    f32x16 acc[NACC];
-    conv_tile<KS, CI, CO, H, BN, RasterRows>(x, wp, m0, n0, acc);
-#pragma unroll
-    for (int j = 0; j < NACC; ++j)
-#pragma unroll
-        for (int r = 0; r < 16; ++r) {
-            const int64_t row = m0 + wave * 32 + (r & 3) + 8 * (r >> 2) + 4 * lh;
-            out[(size_t)row * CO + n0 + 32 * j + li] = acc[j][r];
-        }
 }
 
 // ---------------------------------------------------------------- conv weight gradient: split-K GEMM into slabs
@@ -348,76 +329,6 @@ __global__ void k_bnbwd_apply(const float* __restrict__ dpool, const uint8_t* __
         const size_t a = ((size_t)(n * H + 2 * ph + (e >> 1)) * H + 2 * pw + (e & 1)) * C + c;
         const float xh = (y[a] - mu) * is;
         dy[a] = gi * ((r == e ? d : 0.f) - m1 - xh * m2);
-    }
-}
-
-// ---------------------------------------------------------------- 64 x 64 MFMA GEMM, operands K- or M/N-contiguous
-// A(m, k) = AKC ? A[m * lda + k] : A[k * lda + m];  B(k, n) = BKC ? B[n * ldb + k] : B[k * ldb + n];
-// C[z][m * ldc + n] over k in [z * Ks, min((z + 1) * Ks, K)).  K-contiguous operands need K % 8 == 0 and Ks % 32 == 0; the other
-// kind needs its M (N) % 4 == 0.  Rows / columns / k outside the problem are staged as zeros and never stored.
-template <bool AKC, bool BKC>
-__global__ __launch_bounds__(256) void k_tgemm(const float* __restrict__ A, const float* __restrict__ B, float* __restrict__ Cm,
-                                               int M, int N, int K, int Ks, int lda, int ldb, int ldc) {
-    constexpr int BK = 32, LD = 64 + 4;
-    __shared__ __attribute__((aligned(16))) float sA[BK][LD];
-    __shared__ __attribute__((aligned(16))) float sB[BK][LD];
-    const int tid = threadIdx.x, lane = tid & 63, wave = tid >> 6, li = lane & 31, lh = lane >> 5;
-    const int wm = wave >> 1, wn = wave & 1;
-    const int n0 = blockIdx.x * 64, m0 = blockIdx.y * 64, kb = blockIdx.z * Ks, ke = min(kb + Ks, K);
-    const int row = tid & 63, qd = tid >> 6;              // K-contiguous staging: (row, 8 k)
-    const int c4 = (tid & 15) * 4, kk = tid >> 4;         // M-contiguous staging: (4 rows, k = kk and kk + 16)
-    f32x16 acc;
-#pragma unroll
-    for (int r = 0; r < 16; ++r) acc[r] = 0.f;
-    for (int k0 = kb; k0 < ke; k0 += BK) {
-        if (AKC) {
-            const bool ok = m0 + row < M;
-#pragma unroll
-            for (int j = 0; j < 2; ++j) {
-                const int k = k0 + qd * 8 + 4 * j;
-                const f32x4 v = (ok && k < ke) ? *reinterpret_cast<const f32x4*>(A + (size_t)(m0 + row) * lda + k) : f32x4{0.f, 0.f, 0.f, 0.f};
-#pragma unroll
-                for (int e = 0; e < 4; ++e) sA[qd * 8 + 4 * j + e][row] = v[e];
-            }
-        } else {
-#pragma unroll
-            for (int j = 0; j < 2; ++j) {
-                const int k = k0 + kk + 16 * j;
-                const f32x4 v = (k < ke && m0 + c4 < M) ? *reinterpret_cast<const f32x4*>(A + (size_t)k * lda + m0 + c4) : f32x4{0.f, 0.f, 0.f, 0.f};
-                *reinterpret_cast<f32x4*>(&sA[kk + 16 * j][c4]) = v;
-            }
-        }
-        if (BKC) {
-            const bool ok = n0 + row < N;
-#pragma unroll
-            for (int j = 0; j < 2; ++j) {
-                const int k = k0 + qd * 8 + 4 * j;
-                const f32x4 v = (ok && k < ke) ? *reinterpret_cast<const f32x4*>(B + (size_t)(n0 + row) * ldb + k) : f32x4{0.f, 0.f, 0.f, 0.f};
-#pragma unroll
-                for (int e = 0; e < 4; ++e) sB[qd * 8 + 4 * j + e][row] = v[e];
-            }
-        } else {
-#pragma unroll
-            for (int j = 0; j < 2; ++j) {
-                const int k = k0 + kk + 16 * j;
-                const f32x4 v = (k < ke && n0 + c4 < N) ? *reinterpret_cast<const f32x4*>(B + (size_t)k * ldb + n0 + c4) : f32x4{0.f, 0.f, 0.f, 0.f};
-                *reinterpret_cast<f32x4*>(&sB[kk + 16 * j][c4]) = v;
-            }
-        }
-        __syncthreads();
-#pragma unroll
-        for (int s = 0; s < BK / 2; ++s)
-            acc = __builtin_amdgcn_mfma_f32_32x32x2f32(sA[2 * s + lh][wm * 32 + li], sB[2 * s + lh][wn * 32 + li], acc, 0, 0, 0);
-        __syncthreads();
-    }
-    float* cz = Cm + (size_t)blockIdx.z * M * ldc;
-    const int nn = n0 + wn * 32 + li;
-    if (nn < N) {
-#pragma unroll
-        for (int r = 0; r < 16; ++r) {
-            const int mm = m0 + wm * 32 + (r & 3) + 8 * (r >> 2) + 4 * lh;
-            if (mm < M) cz[(size_t)mm * ldc + nn] = acc[r];
-        }
     }
 }
 

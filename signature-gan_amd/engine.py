@@ -22,13 +22,13 @@ def _f32(t, device, what):
     return t.contiguous()
 
 
-def check_objective_weights(recon_weight, realism_weight, prior_weight, has_target, want_probs=False):
+def check_objective_weights(recon_weight, realism_weight, prior_weight, has_target, want_probs=False, seeded=False):
     """The refusals of siggan_g_latent_objective_grad that need no device, raised as ValueError before anything is allocated;
-    returns the three weights as floats."""
+    returns the three weights as floats.  ``seeded``: the call carries an image-space seed, so all three weights may be 0."""
     w = (float(recon_weight), float(realism_weight), float(prior_weight))
     if any(not math.isfinite(x) or x < 0.0 for x in w):
         raise ValueError(f"the objective's weights must be finite and >= 0, got {w}")
-    if w == (0.0, 0.0, 0.0):
+    if w == (0.0, 0.0, 0.0) and not seeded:
         raise ValueError("all three weights of the objective are 0")
     if w[0] > 0.0 and not has_target:
         raise ValueError("recon_weight > 0 needs a target")
@@ -376,21 +376,37 @@ class Engine:
         return (dz, loss, img) if want_images else (dz, loss)
 
     def g_latent_objective_grad(self, z, target=None, recon_weight=0.0, realism_weight=1.0, prior_weight=0.0, want_terms=False,
-                                want_probs=False, want_images=False, dz_out=None, objective_out=None):
+                                want_probs=False, want_images=False, dz_out=None, objective_out=None, image_grad=None):
         """The gradient with respect to z (B, latent) of the per-image objective recon_weight * mean((G(z) - t)^2) +
         realism_weight * -max(log D(G(z)), -100) + prior_weight * 0.5 * mean(z^2), both networks in eval mode
         (siggan_g_latent_objective_grad; fp32 contexts).  ``target`` as g_latent_grad's, given exactly when recon_weight > 0.
         Returns (dz, objective[, terms][, probs][, images]): dz (B, latent), objective (B,), terms (3, B) the unweighted
         recon / realism / prior terms (0 where the weight is 0), probs (B,) D(G(z)) (needs realism_weight > 0), images
         (B, 1, S, S) bit for bit g_forward(z).  ``dz_out`` / ``objective_out``: as g_latent_grad's dz_out / loss_out.  Nothing
-        synchronises with the host."""
-        w = check_objective_weights(recon_weight, realism_weight, prior_weight, target is not None, want_probs)
+        synchronises with the host.
+
+        ``image_grad`` (B, 1, S, S) or (B, S, S) fp32 on the device: a caller-supplied image-space gradient; dz additionally
+        receives J_G(z)^T image_grad (siggan_g_latent_objective_grad_seeded).  All three weights may then be 0; objective,
+        terms, probs and images never include the seed's term.  None calls exactly the unseeded symbol."""
+        w = check_objective_weights(recon_weight, realism_weight, prior_weight, target is not None, want_probs,
+                                    seeded=image_grad is not None)
+        if image_grad is not None:
+            s = self.image_size
+            if (not isinstance(image_grad, torch.Tensor) or image_grad.dtype != torch.float32 or image_grad.device != self.device
+                    or image_grad.numel() != z.shape[0] * s * s or tuple(image_grad.shape[-2:]) != (s, s)):
+                raise ValueError(f"image_grad must be float32 ({z.shape[0]}, 1, {s}, {s}) on {self.device}")
+            image_grad = image_grad.contiguous()
         z, b, t_u8, t_f32 = self._latent_inputs(z, target, target_optional=True)
         dz, obj = self._out_f32(dz_out, (b, self.latent_dim), "dz_out"), self._out_f32(objective_out, (b,), "objective_out")
         new = lambda *shape: torch.empty(*shape, dtype=torch.float32, device=self.device)
         terms = new(3, b) if want_terms else None
         probs = new(b) if want_probs else None
         img = new(b, 1, self.image_size, self.image_size) if want_images else None
+        if image_grad is not None:
+            _lib.check(self.lib.siggan_g_latent_objective_grad_seeded(
+                self._h, _ptr(z), b, _ptr(t_u8), _ptr(t_f32), C.byref(_lib.LatentObjective(*w)), _ptr(image_grad), _ptr(dz), _ptr(obj),
+                _ptr(terms), _ptr(probs), _ptr(img), self._stream()))
+            return (dz, obj) + tuple(t for t in (terms, probs, img) if t is not None)
         _lib.check(self.lib.siggan_g_latent_objective_grad(self._h, _ptr(z), b, _ptr(t_u8), _ptr(t_f32), C.byref(_lib.LatentObjective(*w)),
                                                            _ptr(dz), _ptr(obj), _ptr(terms), _ptr(probs), _ptr(img), self._stream()))
         return (dz, obj) + tuple(t for t in (terms, probs, img) if t is not None)

@@ -110,16 +110,27 @@ def generate_refined(generator, discriminator, n_samples: int, output_dir: str, 
 
 def run_projection(generator, path: str, output_dir: str, prefix: str = "signature", steps: int = 200, lr: float = 0.05,
                    restarts: int = 1, seed: Optional[int] = None, discriminator=None, realism_weight: float = 0.0,
-                   prior_weight: float = 0.0) -> None:
+                   prior_weight: float = 0.0, verifier=None, identity_weight: float = 0.0,
+                   identity_score_weight: float = 0.0) -> None:
     """Reconstructions of the image file / the images of the directory ``path``: ``<prefix>_projection_%06d.png`` each, and
     ``<prefix>_projection.json``: [{file, reconstruction, loss, z}, ...] in the same order; with ``realism_weight`` > 0 every
-    record also holds ``realism``, the Discriminator's score of the reconstruction."""
+    record also holds ``realism``, the Discriminator's score of the reconstruction.  With a ``verifier`` every record holds
+    ``identity``: {embedding_distance, verifier_score} of G(z) against the target at the returned z, and
+    ``identity_pixel_only``: the same two numbers for the projection without the identity term (what the term bought)."""
     from PIL import Image
     os.makedirs(output_dir, exist_ok=True)
     files, targets = load_target_images(path, generator.output_size)
     print(f"Projecting {len(files)} images into the latent space ({steps} steps, {restarts} restart(s))...")
-    z, recon, loss, _ = project_signatures(generator, targets, steps=steps, lr=lr, seed=seed, restarts=restarts,
-                                           discriminator=discriminator, realism_weight=realism_weight, prior_weight=prior_weight)
+    kw = dict(steps=steps, lr=lr, seed=seed, restarts=restarts, discriminator=discriminator, realism_weight=realism_weight,
+              prior_weight=prior_weight)
+    z, recon, loss, _ = project_signatures(generator, targets, verifier=verifier, identity_weight=identity_weight,
+                                           identity_score_weight=identity_score_weight, **kw)
+    identity = pixel_only = None
+    if verifier is not None:
+        identity = identity_report(generator, verifier, targets, z)
+        pixel_only = identity
+        if identity_weight > 0 or identity_score_weight > 0:
+            pixel_only = identity_report(generator, verifier, targets, project_signatures(generator, targets, **kw)[0])
     realism = None
     if realism_weight > 0:
         mb = generator._require_engine().max_batch
@@ -132,10 +143,28 @@ def run_projection(generator, path: str, output_dir: str, prefix: str = "signatu
         records.append({"file": name, "reconstruction": out, "loss": float(loss[i]), "z": [float(v) for v in z[i]]})
         if realism is not None:
             records[-1]["realism"] = float(realism[i])
+        if identity is not None:
+            records[-1]["identity"] = identity[i]
+            records[-1]["identity_pixel_only"] = pixel_only[i]
     with open(os.path.join(output_dir, f"{prefix}_projection.json"), "w") as f:
         json.dump(records, f, indent=2)
     print(f"Reconstruction loss (mean squared error in [-1, 1]): best {float(loss.min()):.3e}, worst {float(loss.max()):.3e}")
     print(f"Saved {len(files)} reconstructions to: {output_dir}")
+
+
+def identity_report(generator, verifier, targets_u8, z):
+    """[{embedding_distance, verifier_score}, ...]: the verifier's view of G(z[i]) against target i -- the Euclidean distance of
+    the two unit embeddings and the head's similarity -- on the fp32 images of the eval-mode Generator."""
+    eng = generator._require_engine()
+    t = torch.as_tensor(targets_u8).to(z.device).contiguous()
+    step = min(eng.max_batch, verifier.max_images)
+    out = []
+    for i in range(0, z.shape[0], step):
+        e = verifier.forward_one(eng.g_forward(z[i:i + step].contiguous(), training=False))
+        r = verifier.embed_u8(t[i:i + step])
+        dist, score = (e - r).norm(dim=1).cpu(), verifier.compare(e, r).reshape(-1).cpu()
+        out += [{"embedding_distance": float(d), "verifier_score": float(s)} for d, s in zip(dist, score)]
+    return out
 
 
 def run_morph(generator, endpoints, output_dir: str, device: torch.device, prefix: str = "signature", n_frames: int = 10,
@@ -240,6 +269,15 @@ ADAPT_DEFAULTS = dict(adapt=None, adapt_steps=100, adapt_lr=1e-4, adapt_first_la
                       adapt_sigma=None, adapt_save=None)
 
 
+# the identity flags of a projection, kept out of the namespace the same way
+IDENTITY_DEFAULTS = dict(verifier_checkpoint=None, project_identity_weight=0.0, project_identity_score_weight=0.0)
+
+
+def identity_opt(a: argparse.Namespace, name: str):
+    """A flag of IDENTITY_DEFAULTS: its value on the command line, else its default."""
+    return getattr(a, name, IDENTITY_DEFAULTS[name])
+
+
 def adapt_opt(a: argparse.Namespace, name: str):
     """A flag of ADAPT_DEFAULTS: its value on the command line, else its default."""
     return getattr(a, name, ADAPT_DEFAULTS[name])
@@ -285,6 +323,13 @@ def parse_args(argv=None) -> argparse.Namespace:
                    help="With --project: weight of -log D(G(z)) beside the pixel error; needs the checkpoint's Discriminator (default: 0)")
     p.add_argument("--project_prior_weight", type=float, **later,
                    help="With --project: weight of the prior term 0.5 * mean(z^2) (default: 0)")
+    p.add_argument("--verifier_checkpoint", type=str, metavar="CKPT", **later,
+                   help="With --project: the Siamese verifier's checkpoint; <prefix>_projection.json then records the verifier's "
+                        "embedding distance and score of every reconstruction against its target")
+    p.add_argument("--project_identity_weight", type=float, **later,
+                   help="With --project and --verifier_checkpoint: weight of 0.5 * |e(G(z)) - e(target)|^2 beside the pixel error (default: 0)")
+    p.add_argument("--project_identity_score_weight", type=float, **later,
+                   help="With --project and --verifier_checkpoint: weight of -log verifier_score(G(z), target) (default: 0)")
     p.add_argument("--adapt", type=str, metavar="PATH", **later,
                    help="Adapt the Generator's weights to an image file, or the images of a directory (pivotal tuning: project, then "
                         "Adam on the weights), generate n_samples signatures near the pivots and write <prefix>_adapt.json")
@@ -325,6 +370,13 @@ def parse_args(argv=None) -> argparse.Namespace:
         p.error("--project_realism_weight and --project_prior_weight must be >= 0")
     if a.project is None and (hasattr(a, "project_realism_weight") or hasattr(a, "project_prior_weight")):
         p.error("--project_realism_weight and --project_prior_weight need --project")
+    if a.project is None and any(hasattr(a, k) for k in IDENTITY_DEFAULTS):
+        p.error("--verifier_checkpoint, --project_identity_weight and --project_identity_score_weight need --project")
+    w_i = (identity_opt(a, "project_identity_weight"), identity_opt(a, "project_identity_score_weight"))
+    if not w_i[0] >= 0 or not w_i[1] >= 0:
+        p.error("--project_identity_weight and --project_identity_score_weight must be >= 0")
+    if (w_i[0] > 0 or w_i[1] > 0) and identity_opt(a, "verifier_checkpoint") is None:
+        p.error("--project_identity_weight and --project_identity_score_weight need --verifier_checkpoint")
     if a.morph is not None and len(a.morph) not in (0, 2):
         p.error("--morph takes no image files (random endpoints) or exactly two")
     if a.morph_frames < 2:
@@ -376,8 +428,13 @@ def main(argv=None) -> None:
         if a.project is not None:
             w_d, w_p = opt(a, "project_realism_weight"), opt(a, "project_prior_weight")
             discriminator = need_discriminator("--project_realism_weight") if w_d > 0 else None
+            verifier = None
+            if identity_opt(a, "verifier_checkpoint") is not None:
+                from .signature_verifier_eval import load_model
+                verifier = load_model(identity_opt(a, "verifier_checkpoint"), device)[0]
             run_projection(generator, a.project, a.output_dir, a.prefix, a.project_steps, a.project_lr, a.project_restarts, a.seed,
-                           discriminator, w_d, w_p)
+                           discriminator, w_d, w_p, verifier, identity_opt(a, "project_identity_weight"),
+                           identity_opt(a, "project_identity_score_weight"))
         if a.morph is not None:
             run_morph(generator, a.morph, a.output_dir, device, a.prefix, a.morph_frames, a.seed, a.threshold, a.transparent,
                       a.project_steps, a.project_lr, a.project_restarts)

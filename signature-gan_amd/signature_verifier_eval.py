@@ -54,6 +54,7 @@ class _Context:
         h = C.c_void_p()
         _lib.check(self.lib.siggan_verifier_create(self.device.index, self.E, self.max_images, C.byref(h)))
         self._h = h
+        self._grad_enabled = False
 
     def _stream(self):
         return C.c_void_p(torch.cuda.current_stream(self.device).cuda_stream)
@@ -125,6 +126,29 @@ class _Context:
             _lib.check(self.lib.siggan_verifier_compare(self._h, _ptr(e1), _ptr(e2), e1.shape[0], _ptr(s), self._stream()))
         return s
 
+    def input_grad(self, x, ref_emb, embed_weight, score_weight, want_terms, want_score, want_emb, dx_out, objective_out):
+        if not self._grad_enabled:                          # lazily: contexts that never ask for a gradient pay nothing
+            _lib.check(self.lib.siggan_verifier_input_grad_enable(self._h))
+            self._grad_enabled = True
+        n = x.shape[0]
+        new = lambda *shape: torch.empty(*shape, dtype=torch.float32, device=self.device)
+        dx = dx_out if dx_out is not None else new(n, 1, IMAGE_SIZE, IMAGE_SIZE)
+        obj = objective_out if objective_out is not None else new(n)
+        terms = new(2, n) if want_terms else None
+        score = new(n) if want_score else None
+        emb = new(n, self.E) if want_emb else None
+        w = _lib.VerifierIdentity(embed_weight, score_weight)
+        _lib.check(self.lib.siggan_verifier_input_grad(self._h, _ptr(x), _ptr(ref_emb), n, C.byref(w), _ptr(dx), _ptr(obj), _ptr(terms),
+                                                       _ptr(score), _ptr(emb), self._stream()))
+        return (dx, obj) + tuple(t for t in (terms, score, emb) if t is not None)
+
+    def input_grad_debug(self, name, shape, dtype=torch.uint8):
+        """'route1|2|3' (NCHW), 'fc1_mask', 'cls_mask' uint8, 'diff_sign' int8 of the last input_grad call (test hook)."""
+        n = int(np.prod(shape))
+        out = torch.empty(n, dtype=dtype, device=self.device)
+        _lib.check(self.lib.siggan_verifier_input_grad_debug(self._h, name.encode(), _ptr(out), n, self._stream()))
+        return out.view(*shape)
+
     def debug_tensor(self, name, shape):
         """Stage 'pool1' | 'pool2' | 'pool3' | 'fc1' of the last call in torch's layout (test hook)."""
         n = int(np.prod(shape))
@@ -142,6 +166,36 @@ class _Context:
             self.close()
         except Exception:                                   # interpreter shutdown
             pass
+
+
+def check_identity_weights(embed_weight, score_weight):
+    """The refusals of siggan_verifier_input_grad's weights, raised as ValueError before anything is allocated."""
+    import math
+    w = (float(embed_weight), float(score_weight))
+    if any(not math.isfinite(v) or v < 0.0 for v in w):
+        raise ValueError(f"the identity weights must be finite and >= 0, got {w}")
+    if w == (0.0, 0.0):
+        raise ValueError("both identity weights are 0")
+    return w
+
+
+def check_input_grad_shapes(x, ref_emb, embedding_dim, max_images, dx_out=None, objective_out=None):
+    """Shape / dtype refusals of input_grad (host only); returns N."""
+    for t, what in ((x, "x"), (ref_emb, "ref_emb")):
+        if not isinstance(t, torch.Tensor) or t.dtype != torch.float32:
+            raise ValueError(f"{what} must be a float32 tensor")
+    if not ((x.dim() == 4 and tuple(x.shape[1:]) == (1, IMAGE_SIZE, IMAGE_SIZE))
+            or (x.dim() == 3 and tuple(x.shape[1:]) == (IMAGE_SIZE, IMAGE_SIZE))):
+        raise ValueError(f"x must be (N, 1, {IMAGE_SIZE}, {IMAGE_SIZE}), got {tuple(x.shape)}")
+    n = x.shape[0]
+    if not 1 <= n <= max_images:
+        raise ValueError(f"input_grad takes 1 .. max_images = {max_images} images per call, got {n}")
+    if tuple(ref_emb.shape) != (n, embedding_dim):
+        raise ValueError(f"ref_emb must be ({n}, {embedding_dim}), got {tuple(ref_emb.shape)}")
+    for t, shape, what in ((dx_out, (n, 1, IMAGE_SIZE, IMAGE_SIZE), "dx_out"), (objective_out, (n,), "objective_out")):
+        if t is not None and (not isinstance(t, torch.Tensor) or t.dtype != torch.float32 or t.numel() != int(np.prod(shape))):
+            raise ValueError(f"{what} must be float32 with {int(np.prod(shape))} elements")
+    return n
 
 
 class _HipModule(nn.Module):
@@ -316,6 +370,29 @@ class SiameseNetwork(_HipModule):
         """Similarity (B, 1) of embeddings computed earlier (forward_one / embed_u8)."""
         self._on_device(e1, e2)
         return self._context().compare(e1, e2)
+
+    def input_grad(self, x: torch.Tensor, ref_emb: torch.Tensor, embed_weight: float = 1.0, score_weight: float = 0.0,
+                   want_terms: bool = False, want_score: bool = False, dx_out: Optional[torch.Tensor] = None,
+                   objective_out: Optional[torch.Tensor] = None, want_emb: bool = False):
+        """The eval-mode gradient with respect to the images ``x`` (N, 1, 64, 64) fp32 of the per-image identity objective
+        embed_weight * 0.5 * |e(x) - r|^2 + score_weight * -max(log s(e(x), r), -100) against the constant reference
+        embeddings ``ref_emb`` (N, E) (forward_one / embed_u8 of the targets), in HIP (include/siggan_verifier_grad.h): BatchNorm
+        is its running-statistics affine, no dropout, images do not interact.  Returns (dx (N, 1, 64, 64), objective (N,)
+        [, terms (2, N) unweighted, 0 where the weight is 0][, score (N,)][, emb (N, E)]).  ``dx_out`` / ``objective_out``:
+        caller-owned contiguous fp32 device tensors the results are written into.  At most ``max_images`` images per call.
+        Nothing synchronises with the host."""
+        we, ws = check_identity_weights(embed_weight, score_weight)
+        n = check_input_grad_shapes(x, ref_emb, self.embedding_dim, self.max_images, dx_out, objective_out)
+        self._on_device(x, ref_emb)
+        ctx = self._context()
+        for t, what in ((x, "x"), (ref_emb, "ref_emb"), (dx_out, "dx_out"), (objective_out, "objective_out")):
+            if t is not None and (t.device != ctx.device or not t.is_contiguous()):
+                raise ValueError(f"{what} must be contiguous on {ctx.device}")
+        return ctx.input_grad(x.view(n, 1, IMAGE_SIZE, IMAGE_SIZE), ref_emb, we, ws, want_terms, want_score, want_emb, dx_out,
+                              objective_out)
+
+    def input_grad_debug(self, name, shape, dtype=torch.uint8):
+        return self._context().input_grad_debug(name, shape, dtype)
 
     def debug_tensor(self, name, shape):
         return self._context().debug_tensor(name, shape)

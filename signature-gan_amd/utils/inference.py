@@ -18,6 +18,7 @@ Realism-guided refinement joins the two: ``refine_latents`` moves latent vectors
 Adam loop on z around Engine.g_latent_objective_grad) instead of throwing low-scoring images away,
 ``generate_signatures_refined`` is generation on top of it, and ``project_signatures`` takes the same realism and prior terms
 beside its pixel error.  ``adopt_discriminator`` brings the Discriminator into the Generator's context for them."""
+import math
 from typing import Any, Dict, List, Optional, Tuple
 
 import numpy as np
@@ -453,10 +454,47 @@ def generate_signatures_refined(generator: Generator, discriminator: Discriminat
     return images, host(after), host(before)
 
 
+def check_identity_projection(generator, verifier, identity_weight, identity_score_weight):
+    """The host-side refusals of project_signatures' identity term, raised as ValueError before anything is allocated.
+    Returns None when both weights are 0 -- the verifier is then not looked at -- else the two weights as floats."""
+    w = (float(identity_weight), float(identity_score_weight))
+    if any(not math.isfinite(x) or x < 0.0 for x in w):
+        raise ValueError(f"the identity weights must be finite and >= 0, got {w}")
+    if w == (0.0, 0.0):
+        return None
+    if verifier is None:
+        raise ValueError("identity_weight / identity_score_weight > 0 need the verifier")
+    if generator.output_size != 64:
+        raise ValueError(f"the verifier reads 64x64 images: the identity term needs a 64x64 Generator, got {generator.output_size}")
+    if verifier.training:
+        raise ValueError("the identity term runs the verifier in eval mode: call .eval() on it")
+    g_dev, v_dev = next(generator.parameters()).device, next(verifier.parameters()).device
+    if g_dev != v_dev:
+        raise ValueError(f"the verifier lives on {v_dev}, the Generator on {g_dev}: move them to one device")
+    return w
+
+
+def _identity_grad(eng, verifier, t, ref_emb, realism_weight, prior_weight, w_e, w_s):
+    """The ``grad`` of _descend with the identity term: g_forward -> verifier.input_grad (the image-space gradient of the
+    identity objective at G(z)) -> the seeded latent call (J_G^T of it joins dz) -> the identity objective added in torch."""
+    b = t.shape[0]
+    dx = torch.empty(b, 1, eng.image_size, eng.image_size, dtype=torch.float32, device=eng.device)
+    ident = torch.empty(b, dtype=torch.float32, device=eng.device)
+
+    def grad(k, z, dz, out):
+        img = eng.g_forward(z, training=False)
+        verifier.input_grad(img, ref_emb, w_e, w_s, dx_out=dx, objective_out=ident)
+        eng.g_latent_objective_grad(z, t, 1.0, realism_weight, prior_weight, dz_out=dz, objective_out=out, image_grad=dx)
+        if out is not None:
+            out += ident
+    return grad
+
+
 def project_signatures(generator: Generator, targets_u8, steps: int = 200, lr: float = 0.05,
                        betas: Tuple[float, float] = (0.9, 0.999), z0: Optional[torch.Tensor] = None, seed: Optional[int] = None,
                        restarts: int = 1, return_candidates: bool = False, discriminator: Optional[Discriminator] = None,
-                       realism_weight: float = 0.0, prior_weight: float = 0.0):
+                       realism_weight: float = 0.0, prior_weight: float = 0.0, verifier=None, identity_weight: float = 0.0,
+                       identity_score_weight: float = 0.0):
     """Latent vectors whose images reproduce ``targets_u8`` ((N, S, S) uint8, numpy or tensor; a byte stands for
     byte / 127.5 - 1.0): ``steps`` iterations of Adam on z against the per-image loss mean((G(z) - t)^2), every iteration one
     Engine.g_latent_objective_grad (eval forward + eval backward in HIP) and one Engine.op_adam on (z, dz, m, v), all enqueued
@@ -469,7 +507,15 @@ def project_signatures(generator: Generator, targets_u8, steps: int = 200, lr: f
 
     ``realism_weight`` / ``prior_weight`` > 0 add realism_weight * -log D(G(z)) (needs ``discriminator``, brought in by
     adopt_discriminator) and prior_weight * 0.5 * mean(z^2) to the pixel error, and loss / history hold that objective.  With
-    the defaults the weights are (1, 0, 0): the Discriminator is not run, and every bit is Engine.g_latent_grad's."""
+    the defaults the weights are (1, 0, 0): the Discriminator is not run, and every bit is Engine.g_latent_grad's.
+
+    ``identity_weight`` / ``identity_score_weight`` > 0 add the Siamese ``verifier``'s (signature_verifier_eval.SiameseNetwork,
+    eval mode, the Generator's device; 64x64 Generators only) judgement that G(z) is the target's hand: identity_weight *
+    0.5 * |e(G(z)) - e(t)|^2 + identity_score_weight * -log s(e(G(z)), e(t)).  The targets are embedded once (embed_u8);
+    every iteration is then Engine.g_forward -> verifier.input_grad -> the seeded Engine.g_latent_objective_grad -> op_adam,
+    still without a host synchronisation, and loss / history hold the full objective (restart selection uses it).  With both
+    weights 0 the verifier is never touched and every bit is as without these arguments."""
+    identity = check_identity_projection(generator, verifier, identity_weight, identity_score_weight)
     if generator.training:
         raise ValueError("project_signatures needs the Generator in eval() mode (running BatchNorm statistics)")
     if steps < 1 or restarts < 1:
@@ -495,6 +541,8 @@ def project_signatures(generator: Generator, targets_u8, steps: int = 200, lr: f
         z = starts[r][t0:t0 + b].contiguous().clone()
         t = t_all[t0:t0 + b]
         grad = lambda k, z, dz, out: eng.g_latent_objective_grad(z, t, 1.0, realism_weight, prior_weight, dz_out=dz, objective_out=out)
+        if identity:
+            grad = _identity_grad(eng, verifier, t, verifier.embed_u8(t), realism_weight, prior_weight, *identity)
         cand_hist[r, :, t0:t0 + b] = _descend(eng, z, steps, lr, betas, grad, cand_loss[r, t0:t0 + b])  # (the loss at the returned z)
         cand_z[r, t0:t0 + b] = z
     choice = torch.argmin(cand_loss, dim=0)                                        # (plumbing: the first of equal minima)
