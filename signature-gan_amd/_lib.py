@@ -1,5 +1,5 @@
-"""ctypes binding of the C ABI in include/siggan.h (and siggan_mlp.h, siggan_verifier.h, siggan_verifier_grad.h, siggan_verifier_train.h,
-siggan_verifier_data.h, siggan_moments.h, siggan_select.h, siggan_neighbors.h).
+"""ctypes binding of the C ABI in include/siggan.h (and siggan_mlp.h, siggan_verifier.h, siggan_verifier_grad.h, siggan_verifier_pairs.h,
+siggan_verifier_train.h, siggan_verifier_data.h, siggan_moments.h, siggan_select.h, siggan_neighbors.h).
 
 The shared library is built in-tree by ``__graft_entry__.build()`` / ``csrc/Makefile`` and must be
 present: there is no CPU or PyTorch fallback for this path -- a missing or stale library raises.
@@ -168,6 +168,24 @@ _VERIFIER_GRAD_SIGNATURES = {
 }
 VERIFIER_GRAD_EXPORTS = tuple(_VERIFIER_GRAD_SIGNATURES)
 
+# the verifier's pair head over every (query, reference) pair (include/siggan_verifier_pairs.h): new symbols, same context
+PAIR_MAX_DIM, PAIR_MAX_THRESHOLDS = 1024, 4096
+
+
+class PairOutputs(C.Structure):           # siggan_pair_outputs
+    _fields_ = [("score_dev", C.c_void_p), ("threshold_dev", C.c_void_p), ("n_thresholds", C.c_int32),
+                ("genuine_count_dev", C.c_void_p), ("impostor_count_dev", C.c_void_p),
+                ("best_genuine_dev", C.c_void_p), ("best_genuine_index_dev", C.c_void_p),
+                ("best_impostor_dev", C.c_void_p), ("best_impostor_index_dev", C.c_void_p)]
+
+
+_VERIFIER_PAIRS_SIGNATURES = {
+    "siggan_verifier_pairs_enable": (C.c_int, [C.c_void_p, C.c_int32]),
+    "siggan_verifier_pairs": (C.c_int, [C.c_void_p, C.c_void_p, C.c_void_p, C.c_int32, C.c_void_p, C.c_void_p, C.c_int32, C.c_int32,
+                                        C.POINTER(PairOutputs), C.c_void_p]),
+}
+VERIFIER_PAIRS_EXPORTS = tuple(_VERIFIER_PAIRS_SIGNATURES)
+
 # the verifier's train step (include/siggan_verifier_train.h): again only new symbols
 VT_PARAM_TENSORS, VT_METRICS = 20, 4
 VT_RUNNING_FIELDS = ("bn1_running_mean", "bn1_running_var", "bn2_running_mean", "bn2_running_var", "bn3_running_mean",
@@ -239,7 +257,8 @@ def load():
             f"{LIB_PATH} is missing: build it with `python -c 'import __graft_entry__ as g; g.build()'` "
             "(or `make -C signature-gan_amd/csrc`). This path has no CPU/PyTorch fallback.")
     lib = C.CDLL(LIB_PATH)
-    for name, (res, args) in {**_SIGNATURES, **_VERIFIER_SIGNATURES, **_VERIFIER_GRAD_SIGNATURES, **_VERIFIER_TRAIN_SIGNATURES,
+    for name, (res, args) in {**_SIGNATURES, **_VERIFIER_SIGNATURES, **_VERIFIER_GRAD_SIGNATURES, **_VERIFIER_PAIRS_SIGNATURES,
+                              **_VERIFIER_TRAIN_SIGNATURES,
                               **_VERIFIER_DATA_SIGNATURES, **_MOMENTS_SIGNATURES, **_SELECT_SIGNATURES,
                               **_NEIGHBORS_SIGNATURES}.items():
         fn = getattr(lib, name)          # AttributeError if the library does not export the symbol

@@ -18,16 +18,21 @@
 // siggan_verifier_input_grad (include/siggan_verifier_grad.h) is 16 launches: the five encoder launches in their REC form (one
 // route byte per pooled element, the row norms), k_vhead_grad, k_vemb_bwd, k_tgemm (d pool3 = dh . Wfc1), and per conv layer
 // k_vunpool + the input gradient (k_tconv over the flipped packs of k_vflip for conv3 / conv2, k_vconv1_dgrad for conv1).
+//
+// siggan_verifier_pairs (include/siggan_verifier_pairs.h) is k_vpairs (+ k_vpairs_best for the row maxima) of verifier_pairs.h.
 #include <hip/hip_runtime.h>
 #include <stdio.h>
 #include <string.h>
 #include <cmath>
+#include <algorithm>
 #include <new>
 
 #include "../../include/siggan_verifier.h"
 #include "../../include/siggan_verifier_grad.h"
+#include "../../include/siggan_verifier_pairs.h"
 #include "host.h"
 #include "verifier_parts.h"
+#include "verifier_pairs.h"
 
 using namespace siggan;
 
@@ -241,9 +246,8 @@ __device__ __forceinline__ float head_score(const float* sd, int E, const float*
     const float* wr = w0 + (size_t)j * E;
     a = 0.f;
     for (int k = 0; k < E; ++k) a = fmaf(sd[k], wr[k], a);
-    a = fmaxf(a + b0[j], 0.f);
-    const float logit = wave_sum(a * w3[j]) + b3[0];
-    return 1.0f / (1.0f + expf(-logit));
+    a = head_hidden(a, b0[j]);
+    return head_sigmoid(wave_sum(a * w3[j]), b3[0]);
 }
 __global__ __launch_bounds__(64) void k_vhead(const float* __restrict__ e1, const float* __restrict__ e2, int E,
                                               const float* __restrict__ w0 /* (64, E) */, const float* __restrict__ b0,
@@ -415,6 +419,11 @@ struct siggan_verifier {
     uint8_t *r1, *r2, *r3, *fc1_mask, *cls_mask;
     int8_t* diff_sign;
     float *nrm, *de, *dh, *dp1, *dy1, *dp2, *dy2, *dp3, *dy3;   // dp3, dy3, dp2, dy2 share dy1's bytes (dead before it is written)
+    // siggan_verifier_pairs (allocated by _enable; pws null before)
+    char* pws;
+    int pair_max, pair_kp;               // query rows the key workspace holds; E rounded up to PBK
+    float* wpk;                          // classifier.0.weight in the B operand's lane order (k_vpairs_pack)
+    unsigned long long* pkeys;           // [pair_max][PSPLIT_MAX][2]
 };
 
 extern "C" int siggan_verifier_create(int32_t device, int32_t E, int32_t max_images, siggan_verifier** out) {
@@ -427,6 +436,7 @@ extern "C" int siggan_verifier_create(int32_t device, int32_t E, int32_t max_ima
     siggan_verifier* v = new (std::nothrow) siggan_verifier();
     if (!v) return FAIL(SIGGAN_E_NOMEM, "out of host memory");
     v->device = device; v->E = E; v->Nmax = max_images; v->bound = false; v->last_n = 0; v->ws = nullptr; v->gws = nullptr; v->grad_n = 0;
+    v->pws = nullptr; v->pair_max = 0; v->pair_kp = 0;
     const int64_t N = max_images;
     size_t off = 0; char* base = nullptr;
     auto carve = [&](float** p, int64_t n) { if (base) *p = (float*)(base + off); off += ((size_t)n * 4 + 255) & ~(size_t)255; };
@@ -456,6 +466,7 @@ extern "C" int siggan_verifier_destroy(siggan_verifier* v) {
     (void)hipDeviceSynchronize();
     if (v->ws) (void)hipFree(v->ws);
     if (v->gws) (void)hipFree(v->gws);
+    if (v->pws) (void)hipFree(v->pws);
     delete v;
     return SIGGAN_OK;
 }
@@ -463,6 +474,10 @@ extern "C" int siggan_verifier_destroy(siggan_verifier* v) {
 static void flip_packs(siggan_verifier* v, hipStream_t s) {
     hipLaunchKernelGGL(k_vflip, dim3(blocks(64 * 32 * 25)), dim3(256), 0, s, (const float*)v->wp2, v->wf2, 64, 32, 25);
     hipLaunchKernelGGL(k_vflip, dim3(blocks(128 * 64 * 9)), dim3(256), 0, s, (const float*)v->wp3, v->wf3, 128, 64, 9);
+}
+
+static void pairs_pack(siggan_verifier* v, hipStream_t s) {
+    hipLaunchKernelGGL(k_vpairs_pack, dim3(blocks((int64_t)v->pair_kp * VHID)), dim3(256), 0, s, (const float*)v->wc0, v->E, v->pair_kp, v->wpk);
 }
 
 extern "C" int siggan_verifier_bind(siggan_verifier* v, const siggan_verifier_weights* w, void* stream) {
@@ -493,6 +508,7 @@ extern "C" int siggan_verifier_bind(siggan_verifier* v, const siggan_verifier_we
     hipLaunchKernelGGL(k_vpack_conv, dim3(blocks(128 * 64 * 9)), dim3(256), 0, s, w->conv3_weight, v->wp3, 128, 64, 9);
     hipLaunchKernelGGL(k_vpack_fc1, dim3(blocks((int64_t)VFC1_N * VFC1_K)), dim3(256), 0, s, w->fc1_weight, v->wfc1);
     if (v->gws) flip_packs(v, s);
+    if (v->pws) pairs_pack(v, s);
     if (hipGetLastError() != hipSuccess) return FAIL(SIGGAN_E_HIP, "siggan_verifier_bind: kernel launch failed");
     v->bound = true;
     return SIGGAN_OK;
@@ -681,4 +697,91 @@ extern "C" int siggan_verifier_input_grad_debug(siggan_verifier* v, const char* 
     }
     HIPCHK(hipMemcpyAsync(out, src, (size_t)total, hipMemcpyDeviceToDevice, s));
     return SIGGAN_OK;
+}
+
+// ---------------------------------------------------------------- siggan_verifier_pairs
+extern "C" int siggan_verifier_pairs_enable(siggan_verifier* v, int32_t max_queries) {
+    if (!v) return FAIL(SIGGAN_E_ARG, "siggan_verifier_pairs_enable: null context");
+    if (v->E > SIGGAN_PAIR_MAX_DIM)
+        return FAIL(SIGGAN_E_ARG, "siggan_verifier_pairs_enable: embedding_dim %d above SIGGAN_PAIR_MAX_DIM = %d", v->E, SIGGAN_PAIR_MAX_DIM);
+    if (max_queries < 1) return FAIL(SIGGAN_E_ARG, "siggan_verifier_pairs_enable: max_queries %d < 1", max_queries);
+    if (v->pws && max_queries <= v->pair_max) return SIGGAN_OK;
+    DevGuard dg(v->device); HIPCHK(dg.err);
+    HIPCHK(hipDeviceSynchronize());                              // a set-up call: nothing may still read the workspace it replaces
+    if (v->pws) { (void)hipFree(v->pws); v->pws = nullptr; v->pair_max = 0; }
+    const int Kp = (v->E + PBK - 1) / PBK * PBK;
+    const size_t pack = ((size_t)Kp * VHID * 4 + 255) & ~(size_t)255;
+    const size_t keys = (size_t)max_queries * PSPLIT_MAX * 2 * sizeof(unsigned long long);
+    char* base = nullptr;
+    hipError_t e = hipMalloc((void**)&base, pack + keys);
+    if (e != hipSuccess) return FAIL(SIGGAN_E_NOMEM, "hipMalloc(%zu) -> %s", pack + keys, hipGetErrorString(e));
+    v->pws = base; v->wpk = (float*)base; v->pkeys = (unsigned long long*)(base + pack);
+    v->pair_kp = Kp; v->pair_max = max_queries;
+    if (v->bound) {                      // behind whatever stream bind packed on (synchronised above), and done on return
+        pairs_pack(v, nullptr);
+        if (hipGetLastError() != hipSuccess) return FAIL(SIGGAN_E_HIP, "siggan_verifier_pairs_enable: kernel launch failed");
+        HIPCHK(hipDeviceSynchronize());
+    }
+    return SIGGAN_OK;
+}
+
+extern "C" int siggan_verifier_pairs(siggan_verifier* v, const float* q, const int32_t* qid, int32_t nq, const float* r, const int32_t* rid,
+                                     int32_t nr, int32_t same_set, const siggan_pair_outputs* out, void* stream) {
+    const char* fn = "siggan_verifier_pairs";
+    int rc = vcheck(v, fn); if (rc) return rc;
+    if (v->E > SIGGAN_PAIR_MAX_DIM) return FAIL(SIGGAN_E_ARG, "%s: embedding_dim %d above SIGGAN_PAIR_MAX_DIM = %d", fn, v->E, SIGGAN_PAIR_MAX_DIM);
+    if (!v->pws) return FAIL(SIGGAN_E_ARG, "%s: siggan_verifier_pairs_enable has not been called", fn);
+    if (!q || !r || !out) return FAIL(SIGGAN_E_ARG, "%s: null argument", fn);
+    if (nq < 1 || nr < 1) return FAIL(SIGGAN_E_ARG, "%s: nq = %d, nr = %d: both must be >= 1", fn, nq, nr);
+    if ((int64_t)nq * nr >= ((int64_t)1 << 62)) return FAIL(SIGGAN_E_ARG, "%s: nq * nr >= 2^62", fn);
+    if (same_set && nq != nr) return FAIL(SIGGAN_E_ARG, "%s: same_set needs nq == nr, got %d and %d", fn, nq, nr);
+    const int T = out->n_thresholds;
+    const bool want_counts = out->threshold_dev || out->genuine_count_dev || out->impostor_count_dev || T != 0;
+    const bool want_best = out->best_genuine_dev || out->best_genuine_index_dev || out->best_impostor_dev || out->best_impostor_index_dev;
+    if (!out->score_dev && !want_counts && !want_best) return FAIL(SIGGAN_E_ARG, "%s: no output requested", fn);
+    if (want_counts) {
+        if (!out->threshold_dev || !out->genuine_count_dev || !out->impostor_count_dev)
+            return FAIL(SIGGAN_E_ARG, "%s: the counts need threshold_dev, genuine_count_dev and impostor_count_dev", fn);
+        if (T < 1 || T > SIGGAN_PAIR_MAX_THRESHOLDS)
+            return FAIL(SIGGAN_E_ARG, "%s: n_thresholds %d outside [1, %d]", fn, T, SIGGAN_PAIR_MAX_THRESHOLDS);
+    }
+    if (want_best && nq > v->pair_max)
+        return FAIL(SIGGAN_E_ARG, "%s: row maxima for nq = %d rows, siggan_verifier_pairs_enable was given max_queries = %d", fn, nq, v->pair_max);
+    const bool vec = v->E % 4 == 0;
+    auto mis = [](const void* p, uintptr_t a) { return (reinterpret_cast<uintptr_t>(p) & (a - 1)) != 0; };
+    if (mis(q, vec ? 16 : 4) || mis(r, vec ? 16 : 4))
+        return FAIL(SIGGAN_E_ARG, "%s: the embeddings must be %d-byte aligned", fn, vec ? 16 : 4);
+    if (mis(qid, 4) || mis(rid, 4) || mis(out->score_dev, 4) || mis(out->threshold_dev, 4) || mis(out->genuine_count_dev, 8) ||
+        mis(out->impostor_count_dev, 8) || mis(out->best_genuine_dev, 4) || mis(out->best_genuine_index_dev, 4) ||
+        mis(out->best_impostor_dev, 4) || mis(out->best_impostor_index_dev, 4))
+        return FAIL(SIGGAN_E_ARG, "%s: a pointer is not aligned to its element type", fn);
+    DevGuard dg(v->device); HIPCHK(dg.err);
+    hipStream_t s = (hipStream_t)stream;
+    // Grid: one block column per 16 query rows; the reference tiles are split over S block rows only while the query tiles
+    // alone leave the device short of blocks, and never so few that a block's uint32 LDS counters could wrap (2^22 tiles of 512).
+    const int QT = (nq + PQ - 1) / PQ, ntiles = (nr + PR - 1) / PR;
+    int S = 1;
+    if (QT < 1024) S = std::min(std::min(PSPLIT_MAX, ntiles), (1024 + QT - 1) / QT);
+    S = std::max(S, (ntiles + (1 << 22) - 1) >> 22);
+    const int tps = (ntiles + S - 1) / S;
+    PairOut o;
+    o.score = out->score_dev;
+    o.thr = want_counts ? out->threshold_dev : nullptr;
+    o.T = want_counts ? T : 0;
+    o.gcnt = (unsigned long long*)out->genuine_count_dev;
+    o.icnt = (unsigned long long*)out->impostor_count_dev;
+    o.keys = want_best ? v->pkeys : nullptr;
+    if (want_counts) {
+        HIPCHK(hipMemsetAsync(out->genuine_count_dev, 0, (size_t)(T + 1) * 8, s));
+        HIPCHK(hipMemsetAsync(out->impostor_count_dev, 0, (size_t)(T + 1) * 8, s));
+    }
+    const size_t lds = want_counts ? ((size_t)T + 2 * ((size_t)T + 1)) * 4 : 0;
+    const int upper_only = same_set && !out->score_dev && !want_best;
+    auto kern = vec ? k_vpairs<true> : k_vpairs<false>;
+    hipLaunchKernelGGL(kern, dim3(QT, S), dim3(256), lds, s, q, qid, (int)nq, r, rid, (int)nr, v->E, v->pair_kp, (const float*)v->wpk,
+                       (const float*)v->bc0, (const float*)v->wc3, (const float*)v->bc3, (int)(same_set != 0), upper_only, tps, o);
+    if (want_best)
+        hipLaunchKernelGGL(k_vpairs_best, dim3(blocks(nq)), dim3(256), 0, s, (const unsigned long long*)v->pkeys, (int)nq, S,
+                           out->best_genuine_dev, out->best_genuine_index_dev, out->best_impostor_dev, out->best_impostor_index_dev);
+    return hipGetLastError() == hipSuccess ? SIGGAN_OK : FAIL(SIGGAN_E_HIP, "%s: kernel launch failed", fn);
 }

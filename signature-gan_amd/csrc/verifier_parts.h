@@ -23,6 +23,15 @@ __device__ __forceinline__ float wave_sum(float v) {
     return v;
 }
 
+// ---------------------------------------------------------------- pair head: the expressions every kernel that scores a pair shares
+// hidden unit j after bias + ReLU, from its finished dot product over |e1 - e2|
+__device__ __forceinline__ float head_hidden(float dot, float b0j) { return fmaxf(dot + b0j, 0.f); }
+// the similarity, from the 64 products hidden[j] * w3[j] summed in wave_sum's order
+__device__ __forceinline__ float head_sigmoid(float sum, float b3) {
+    const float logit = sum + b3;
+    return 1.0f / (1.0f + expf(-logit));
+}
+
 // ---------------------------------------------------------------- images: fp32 as given, or bytes normalised on load
 template <bool U8>
 __device__ __forceinline__ float vload(const void* img, int i) {

@@ -8,7 +8,9 @@ or on CPU tensors raises.  Training the verifier is not part of this package.
 
 Beyond the reference: ``embed_u8`` / ``score_u8`` take uint8 (N, 64, 64) images (what ``Engine.g_generate_u8`` writes and
 what a PNG holds) and normalise them on load exactly as ToTensor + Normalize([0.5], [0.5]) would; ``compare`` scores
-embeddings that were computed earlier (one query against an enrolled gallery).
+embeddings that were computed earlier (one query against an enrolled gallery).  ``score_matrix`` / ``pair_counts`` /
+``best_matches`` run the pair head over EVERY (query, reference) pair in one HIP call (include/siggan_verifier_pairs.h), and
+``evaluate_all_pairs`` / ``--all_pairs`` evaluate a test directory on all N (N - 1) / 2 pairs instead of a sample.
 
 The metrics are numpy only (this package imports neither scikit-learn nor matplotlib at module level); the ROC points are
 those of ``sklearn.metrics.roc_curve`` with its defaults.  The plots are written when matplotlib can be imported.
@@ -55,6 +57,7 @@ class _Context:
         _lib.check(self.lib.siggan_verifier_create(self.device.index, self.E, self.max_images, C.byref(h)))
         self._h = h
         self._grad_enabled = False
+        self._pairs_rows = 0
 
     def _stream(self):
         return C.c_void_p(torch.cuda.current_stream(self.device).cuda_stream)
@@ -126,6 +129,38 @@ class _Context:
             _lib.check(self.lib.siggan_verifier_compare(self._h, _ptr(e1), _ptr(e2), e1.shape[0], _ptr(s), self._stream()))
         return s
 
+    def pairs(self, e_q, ids_q, e_r, ids_r, same_set=False, want_matrix=False, thresholds=None, want_best=False):
+        """siggan_verifier_pairs: the head over every pair (q_i, r_j) in one pass.  Returns a dict with the requested groups:
+        'score' (nq, nr); 'thresholds' (T,) fp32, 'genuine_counts', 'impostor_counts' (T + 1,) int64; 'best_genuine',
+        'best_impostor' (nq,) fp32 with 'best_genuine_index', 'best_impostor_index' (nq,) int32.  ``thresholds``: a host
+        sequence / array (or tensor, read back once) of ascending values; that they ascend is checked here, on the host.
+        Refusals are ValueError before anything is allocated."""
+        nq, nr, thr = check_pairs_args(e_q, ids_q, e_r, ids_r, same_set, want_matrix, thresholds, want_best, self.E, self.device)
+        if self._pairs_rows < nq:
+            _lib.check(self.lib.siggan_verifier_pairs_enable(self._h, nq))
+            self._pairs_rows = nq
+        e_q, e_r = e_q.contiguous(), e_r.contiguous()
+        ids_q = ids_q.contiguous() if ids_q is not None else None
+        ids_r = ids_r.contiguous() if ids_r is not None else None
+        new = lambda n, dt: torch.empty(n, dtype=dt, device=self.device)
+        res, o = {}, _lib.PairOutputs()
+        if want_matrix:
+            res["score"] = torch.empty(nq, nr, dtype=torch.float32, device=self.device)
+            o.score_dev = res["score"].data_ptr()
+        if thr is not None:
+            res["thresholds"] = torch.from_numpy(thr).to(self.device)
+            res["genuine_counts"], res["impostor_counts"] = new(thr.size + 1, torch.int64), new(thr.size + 1, torch.int64)
+            o.threshold_dev, o.n_thresholds = res["thresholds"].data_ptr(), int(thr.size)
+            o.genuine_count_dev, o.impostor_count_dev = res["genuine_counts"].data_ptr(), res["impostor_counts"].data_ptr()
+        if want_best:
+            for k, f, dt in (("best_genuine", "best_genuine_dev", torch.float32), ("best_genuine_index", "best_genuine_index_dev", torch.int32),
+                             ("best_impostor", "best_impostor_dev", torch.float32), ("best_impostor_index", "best_impostor_index_dev", torch.int32)):
+                res[k] = new(nq, dt)
+                setattr(o, f, res[k].data_ptr())
+        _lib.check(self.lib.siggan_verifier_pairs(self._h, _ptr(e_q), _ptr(ids_q), nq, _ptr(e_r), _ptr(ids_r), nr, int(bool(same_set)),
+                                                  C.byref(o), self._stream()))
+        return res
+
     def input_grad(self, x, ref_emb, embed_weight, score_weight, want_terms, want_score, want_emb, dx_out, objective_out):
         if not self._grad_enabled:                          # lazily: contexts that never ask for a gradient pay nothing
             _lib.check(self.lib.siggan_verifier_input_grad_enable(self._h))
@@ -166,6 +201,41 @@ class _Context:
             self.close()
         except Exception:                                   # interpreter shutdown
             pass
+
+
+def check_pairs_args(e_q, ids_q, e_r, ids_r, same_set, want_matrix, thresholds, want_best, embedding_dim, device=None):
+    """The refusals of siggan_verifier_pairs that can be decided on the host, raised as ValueError before anything is allocated;
+    returns (nq, nr, thresholds as an ascending float32 numpy array or None)."""
+    if embedding_dim > _lib.PAIR_MAX_DIM:
+        raise ValueError(f"all-pairs scoring takes embedding_dim <= {_lib.PAIR_MAX_DIM}, got {embedding_dim}")
+    for e, what in ((e_q, "e_q"), (e_r, "e_r")):
+        if not isinstance(e, torch.Tensor) or e.dtype != torch.float32 or e.dim() != 2 or e.shape[1] != embedding_dim:
+            raise ValueError(f"{what} must be a float32 (N, {embedding_dim}) tensor")
+        if e.shape[0] < 1:
+            raise ValueError(f"{what} has no rows")
+        if device is not None and e.device != device:
+            raise ValueError(f"{what} must live on {device}, got {e.device}")
+    nq, nr = e_q.shape[0], e_r.shape[0]
+    if nq * nr >= 2 ** 62:
+        raise ValueError("nq * nr >= 2^62")
+    for ids, n, what in ((ids_q, nq, "ids_q"), (ids_r, nr, "ids_r")):
+        if ids is not None and (not isinstance(ids, torch.Tensor) or ids.dtype != torch.int32 or tuple(ids.shape) != (n,)
+                                or ids.device != e_q.device):
+            raise ValueError(f"{what} must be an int32 ({n},) tensor on the embeddings' device, or None")
+    if same_set and nq != nr:
+        raise ValueError(f"same_set needs the same rows on both sides, got nq = {nq} and nr = {nr}")
+    if not (want_matrix or want_best or thresholds is not None):
+        raise ValueError("no output requested: ask for the matrix, the counts (thresholds) or the best matches")
+    thr = None
+    if thresholds is not None:
+        if isinstance(thresholds, torch.Tensor):
+            thresholds = thresholds.detach().cpu().numpy()
+        thr = np.ascontiguousarray(np.asarray(thresholds, dtype=np.float32).reshape(-1))
+        if not 1 <= thr.size <= _lib.PAIR_MAX_THRESHOLDS:
+            raise ValueError(f"the thresholds must hold 1 .. {_lib.PAIR_MAX_THRESHOLDS} values, got {thr.size}")
+        if not np.all(np.isfinite(thr)) or np.any(np.diff(thr) < 0):
+            raise ValueError("the thresholds must be finite and ascending")
+    return nq, nr, thr
 
 
 def check_identity_weights(embed_weight, score_weight):
@@ -371,6 +441,37 @@ class SiameseNetwork(_HipModule):
         self._on_device(e1, e2)
         return self._context().compare(e1, e2)
 
+    def pairs(self, e_q: torch.Tensor, ids_q: Optional[torch.Tensor], e_r: torch.Tensor, ids_r: Optional[torch.Tensor],
+              same_set: bool = False, want_matrix: bool = False, thresholds=None, want_best: bool = False) -> Dict[str, torch.Tensor]:
+        """The pair head over every (query, reference) pair of two embedding sets in ONE HIP call (see _Context.pairs): any
+        of the score matrix, the per-class threshold histograms and each query row's best genuine / impostor match.  A pair is
+        genuine when its int32 ids agree; without ids every pair counts as impostor.  ``same_set``: both sides are the same
+        rows -- counts cover j > i, a row is never its own match.  score[i, j] is compare(e_q[i], e_r[j]) bit for bit."""
+        check_pairs_args(e_q, ids_q, e_r, ids_r, same_set, want_matrix, thresholds, want_best, self.embedding_dim)
+        self._on_device(e_q, e_r)
+        return self._context().pairs(e_q, ids_q, e_r, ids_r, same_set, want_matrix, thresholds, want_best)
+
+    def score_matrix(self, e_q: torch.Tensor, e_r: torch.Tensor) -> torch.Tensor:
+        """Similarity (nq, nr) of every query embedding against every reference embedding."""
+        return self.pairs(e_q, None, e_r, None, want_matrix=True)["score"]
+
+    def pair_counts(self, e: torch.Tensor, ids: Optional[torch.Tensor], thresholds, other: Optional[torch.Tensor] = None,
+                    other_ids: Optional[torch.Tensor] = None) -> Tuple[torch.Tensor, torch.Tensor]:
+        """(genuine_counts, impostor_counts), int64 (T + 1,): bin b counts the pairs with t[b-1] <= score < t[b].  Without
+        ``other`` the pairs are the N (N - 1) / 2 unordered pairs of ``e``; with it, every (e_i, other_j)."""
+        if other is None:
+            out = self.pairs(e, ids, e, ids, same_set=True, thresholds=thresholds)
+        else:
+            out = self.pairs(e, ids, other, other_ids, thresholds=thresholds)
+        return out["genuine_counts"], out["impostor_counts"]
+
+    def best_matches(self, e_q: torch.Tensor, ids_q: Optional[torch.Tensor], e_r: torch.Tensor, ids_r: Optional[torch.Tensor],
+                     same_set: bool = False) -> Tuple[torch.Tensor, torch.Tensor, torch.Tensor, torch.Tensor]:
+        """(best_genuine, best_genuine_index, best_impostor, best_impostor_index) per query row: the highest score among the
+        genuine / impostor references and its row (the lower row on equal scores); -1.0 and -1 where a row has none."""
+        out = self.pairs(e_q, ids_q, e_r, ids_r, same_set=same_set, want_best=True)
+        return out["best_genuine"], out["best_genuine_index"], out["best_impostor"], out["best_impostor_index"]
+
     def input_grad(self, x: torch.Tensor, ref_emb: torch.Tensor, embed_weight: float = 1.0, score_weight: float = 0.0,
                    want_terms: bool = False, want_score: bool = False, dx_out: Optional[torch.Tensor] = None,
                    objective_out: Optional[torch.Tensor] = None, want_emb: bool = False):
@@ -572,7 +673,11 @@ def _binary_clf_curve(y_true: np.ndarray, y_scores: np.ndarray):
 def roc_curve(y_true: np.ndarray, y_scores: np.ndarray) -> Tuple[np.ndarray, np.ndarray, np.ndarray]:
     """(fpr, tpr, thresholds) as sklearn.metrics.roc_curve with its defaults: collinear intermediate points dropped, a
     leading (0, 0) point at threshold inf; a class with no samples gives NaN rates."""
-    fps, tps, thr = _binary_clf_curve(y_true, y_scores)
+    return _roc_from_counts(*_binary_clf_curve(y_true, y_scores))
+
+
+def _roc_from_counts(fps, tps, thr):
+    """roc_curve's points from the cumulative false / true positive counts at descending thresholds."""
     if len(fps) > 2:
         keep = np.where(np.r_[True, np.logical_or(np.diff(fps, 2), np.diff(tps, 2)), True])[0]
         fps, tps, thr = fps[keep], tps[keep], thr[keep]
@@ -663,6 +768,121 @@ def compute_eer_from_scores(y_true: np.ndarray, y_scores: np.ndarray) -> Tuple[f
 
 
 # =============================================================================
+# Metrics from threshold histograms (the counts of SiameseNetwork.pair_counts)
+# =============================================================================
+
+
+def threshold_as_float32(threshold: float) -> np.float32:
+    """The smallest float32 >= threshold: for a float32 score s, s >= threshold (as evaluate_model compares, in float64)
+    holds exactly when s >= this value."""
+    f = np.float32(threshold)
+    if float(f) < float(threshold):
+        f = np.nextafter(f, np.float32(np.inf))
+    return f
+
+
+def default_threshold_grid(threshold: float = 0.5) -> np.ndarray:
+    """Sorted unique float32 thresholds, at most 4096: k / 1024, the sigmoid of a uniform logit grid on [-16, 16] (resolution
+    where saturated scores live) and ``threshold`` itself (as threshold_as_float32)."""
+    lin = np.arange(1025, dtype=np.float64) / 1024.0
+    logit = np.linspace(-16.0, 16.0, _lib.PAIR_MAX_THRESHOLDS - lin.size - 1)
+    grid = np.concatenate([lin, 1.0 / (1.0 + np.exp(-logit))]).astype(np.float32)
+    return np.unique(np.concatenate([grid, np.array([threshold_as_float32(threshold)], dtype=np.float32)]))
+
+
+def metrics_from_counts(thresholds, genuine_counts, impostor_counts, threshold: float = 0.5) -> Dict[str, Any]:
+    """compute_verification_metrics' dictionary from per-class histograms over an ascending float32 threshold grid (bin b of
+    T + 1 counts the pairs with t[b-1] <= score < t[b]) instead of from the scores.
+
+    The confusion matrix at ``threshold`` is exact; threshold_as_float32(threshold) must be one of the grid's values
+    (default_threshold_grid puts it there), else ValueError.  The ROC points are the exact points of the true curve at the
+    grid's thresholds, ``roc_auc`` is their trapezoid and ``eer`` / ``eer_threshold`` come from them as in
+    compute_verification_metrics; with every distinct score in the grid all of these are the true values.
+
+    Two more keys say how far a coarser grid can be off.  Between two exact points the true (monotone) curve cannot leave the
+    rectangle they span: ``roc_auc_bounds`` sums the rectangles' lower and upper areas, and ``eer_bounds`` is the range of
+    (FAR + FRR) / 2 over the stretch of curve in which the reference's EER point must lie (from the last provable corner before
+    the FAR = FRR crossing to the first one after it; roc_curve drops interior points of straight runs, so the point can sit
+    at the end of a run).  A bin that spans a single float32 value holds tied scores only, so nothing is unknown inside it:
+    when that is true of every occupied bin, both brackets collapse onto the value."""
+    t = np.asarray(thresholds, dtype=np.float32).reshape(-1)
+    g = np.asarray(genuine_counts, dtype=np.int64).reshape(-1)
+    im = np.asarray(impostor_counts, dtype=np.int64).reshape(-1)
+    if t.size < 1 or g.size != t.size + 1 or im.size != t.size + 1 or np.any(np.diff(t) < 0):
+        raise ValueError("metrics_from_counts takes T ascending thresholds and two arrays of T + 1 counts")
+    k = int(np.searchsorted(t, threshold_as_float32(threshold), side="left"))
+    if k >= t.size or t[k] != threshold_as_float32(threshold):
+        raise ValueError(f"threshold {threshold} is not one of the grid's values: the confusion matrix would not be exact")
+    total_genuine, total_forgeries = int(g.sum()), int(im.sum())
+    # pairs with score >= t[b], per class: everything in bins b + 1 .. T
+    tp_at = np.cumsum(g[::-1])[::-1][1:]
+    fp_at = np.cumsum(im[::-1])[::-1][1:]
+    tp, fp = int(tp_at[k]), int(fp_at[k])
+    fn, tn = total_genuine - tp, total_forgeries - fp
+    n = total_genuine + total_forgeries
+    accuracy = (tp + tn) / n if n else float('nan')
+    far = fp / total_forgeries if total_forgeries > 0 else 0.0
+    frr = fn / total_genuine if total_genuine > 0 else 0.0
+    precision = tp / (tp + fp) if (tp + fp) > 0 else 0.0
+    recall = tp / (tp + fn) if (tp + fn) > 0 else 0.0
+    f1 = 2 * precision * recall / (precision + recall) if (precision + recall) > 0 else 0.0
+    specificity = tn / (tn + fp) if (tn + fp) > 0 else 0.0
+
+    # the curve's distinct exact points, thresholds descending: grid value b gives a new point when bin b + 1 is occupied;
+    # scores below the lowest grid value (bin 0) add the end point at threshold -inf
+    occupied = (g + im) > 0
+    keep = np.where(occupied[1:])[0][::-1]
+    fps, tps, thr = fp_at[keep].astype(np.float64), tp_at[keep].astype(np.float64), t[keep].astype(np.float64)
+    if occupied[0]:
+        fps, tps, thr = np.r_[fps, float(total_forgeries)], np.r_[tps, float(total_genuine)], np.r_[thr, -np.inf]
+    if fps.size == 0:
+        raise ValueError("metrics_from_counts: the counts are all zero")
+    fpr, tpr, roc_thresholds = _roc_from_counts(fps, tps, thr)
+    roc_auc = auc(fpr, tpr)
+    fnr = 1 - tpr
+    eer_idx = np.nanargmin(np.abs(fpr - fnr))
+    eer = (fpr[eer_idx] + fnr[eer_idx]) / 2
+    eer_threshold = roc_thresholds[eer_idx] if len(roc_thresholds) > eer_idx else threshold
+
+    # brackets, on every exact point (nothing dropped), (0, 0) first
+    x = np.r_[0.0, fps] / total_forgeries if total_forgeries > 0 else np.full(fps.size + 1, np.nan)
+    y = np.r_[0.0, tps] / total_genuine if total_genuine > 0 else np.full(tps.size + 1, np.nan)
+    upper_edge = np.r_[t[1:], np.float32(np.inf)]
+    single = np.r_[False, np.nextafter(t, np.float32(np.inf)) == upper_edge]          # per bin: one float32 value only
+    exact = bool(np.all(single[occupied]))
+    if exact or not (total_forgeries > 0 and total_genuine > 0):
+        auc_bounds, eer_bounds = (roc_auc, roc_auc), (float(eer), float(eer))
+    else:
+        dx = np.diff(x)
+        auc_bounds = (float(np.sum(dx * y[:-1])), float(np.sum(dx * y[1:])))
+        cx, cy = np.r_[0.0, fps], np.r_[0.0, tps]                                     # counts: exact collinearity tests
+        d = cx * total_genuine + cy * total_forgeries - float(total_genuine) * total_forgeries
+        ia, ib = int(np.where(d <= 0)[0][-1]), int(np.where(d >= 0)[0][0])
+        last = cx.size - 1
+
+        def straight(i):                                                               # points i - 1, i, i + 1 on one line
+            if i < 1 or i > last - 1:
+                return False
+            return (cx[i] - cx[i - 1]) * (cy[i + 1] - cy[i]) == (cy[i] - cy[i - 1]) * (cx[i + 1] - cx[i])
+        lo = ia - 2
+        while lo > 0 and straight(lo + 1):
+            lo -= 1
+        hi = ib + 2
+        while hi < last and straight(hi - 1):
+            hi += 1
+        lo, hi = max(lo, 0), min(hi, last)
+        eer_bounds = (float((x[lo] + 1 - y[hi]) / 2), float((x[hi] + 1 - y[lo]) / 2))
+
+    return {
+        'accuracy': float(accuracy), 'far': float(far), 'frr': float(frr), 'eer': float(eer), 'eer_threshold': float(eer_threshold),
+        'precision': float(precision), 'recall': float(recall), 'f1_score': float(f1), 'specificity': float(specificity),
+        'roc_auc': float(roc_auc), 'true_positives': tp, 'true_negatives': tn, 'false_positives': fp, 'false_negatives': fn,
+        'total_genuine': total_genuine, 'total_forgeries': total_forgeries, 'threshold': float(threshold),
+        'roc_auc_bounds': [float(auc_bounds[0]), float(auc_bounds[1])], 'eer_bounds': [eer_bounds[0], eer_bounds[1]],
+    }
+
+
+# =============================================================================
 # Model Evaluation
 # =============================================================================
 
@@ -686,6 +906,72 @@ def evaluate_model(model: SiameseNetwork, dataloader: DataLoader, device: torch.
     y_pred = (y_scores >= threshold).astype(int)
     metrics = compute_verification_metrics(y_true, y_scores, y_pred, threshold)
     return metrics, y_true, y_scores, y_pred
+
+
+def evaluate_all_pairs(model: SiameseNetwork, test_dir: Union[str, Path], threshold: float = 0.5, batch_size: int = 256,
+                       thresholds=None) -> Dict[str, Any]:
+    """Evaluate on EVERY pair of the test directory's signatures instead of a sample: N signatures give N (N - 1) / 2 pairs,
+    genuine where the writers agree.  The files are those SignatureTestDataset lists; each image is decoded once, embedded
+    through the byte route, and one ``pairs`` call (same_set) yields the threshold histograms and every signature's best
+    genuine and best impostor match.  ``thresholds`` replaces default_threshold_grid(threshold) (it must hold
+    threshold_as_float32(threshold)).
+
+    Returns {'metrics': metrics_from_counts' dictionary, 'num_signatures', 'num_writers', 'total_pairs', 'genuine_pairs',
+    'impostor_pairs', 'rank1_identification_rate': the share of signatures that have a genuine candidate and whose best genuine
+    score exceeds their best impostor score, 'hardest_impostors': per writer the highest-scoring pair with another writer}."""
+    model.eval()
+    ds = SignatureTestDataset.__new__(SignatureTestDataset)          # the listing alone: no sampled pairs, no np.random
+    ds.test_dir, ds.user_signatures = Path(test_dir), {}
+    ds._load_signatures()
+    writers = list(ds.user_signatures.keys())
+    paths = [p for w in writers for p in ds.user_signatures[w]]
+    writer_of = np.array([wi for wi, w in enumerate(writers) for _ in ds.user_signatures[w]], dtype=np.int32)
+    if len(paths) < 2:
+        raise ValueError(f"No test pairs in: {test_dir}")
+    device = next(model.parameters()).device
+    chunks = []
+    with torch.no_grad():
+        for i in range(0, len(paths), batch_size):
+            imgs = np.stack([load_uint8(p) for p in paths[i:i + batch_size]])
+            chunks.append(model.embed_u8(torch.from_numpy(imgs).to(device)))
+        emb = torch.cat(chunks, dim=0)
+        ids = torch.from_numpy(writer_of).to(device)
+        grid = default_threshold_grid(threshold) if thresholds is None else thresholds
+        out = model.pairs(emb, ids, emb, ids, same_set=True, thresholds=grid, want_best=True)
+    host = {k: v.cpu().numpy() for k, v in out.items()}
+    metrics = metrics_from_counts(host["thresholds"], host["genuine_counts"], host["impostor_counts"], threshold)
+    bg, bi, bii = host["best_genuine"], host["best_impostor"], host["best_impostor_index"]
+    has_genuine = host["best_genuine_index"] >= 0
+    rank1 = float(np.sum(has_genuine & (bg > bi)) / len(paths))
+    hardest = {}
+    for wi, w in enumerate(writers):
+        rows = np.where((writer_of == wi) & (bii >= 0))[0]
+        if rows.size:
+            r = int(rows[np.argmax(bi[rows])])                        # the first of equal maxima
+            hardest[w] = {'score': float(bi[r]), 'signature': str(paths[r]), 'impostor': str(paths[int(bii[r])]),
+                          'impostor_writer': writers[int(writer_of[int(bii[r])])]}
+    n = len(paths)
+    return {'metrics': metrics, 'num_signatures': n, 'num_writers': len(writers), 'total_pairs': n * (n - 1) // 2,
+            'genuine_pairs': metrics['total_genuine'], 'impostor_pairs': metrics['total_forgeries'],
+            'num_thresholds': int(host["thresholds"].size), 'rank1_identification_rate': rank1, 'hardest_impostors': hardest}
+
+
+def print_all_pairs_summary(results: Dict[str, Dict[str, Any]]) -> None:
+    """The --all_pairs block: the same figures on every pair of the test directory."""
+    print("ALL PAIRS")
+    print("-" * 70)
+    for model_name, data in results.items():
+        ap = data['all_pairs']
+        m = ap['metrics']
+        print(f"\n{model_name.upper()}: {ap['num_signatures']} signatures of {ap['num_writers']} writers, {ap['total_pairs']} pairs "
+              f"({ap['genuine_pairs']} genuine, {ap['impostor_pairs']} impostor)")
+        print(f"  Accuracy:     {m['accuracy']:.4f}")
+        print(f"  FAR:          {m['far']:.6f}")
+        print(f"  FRR:          {m['frr']:.6f}")
+        print(f"  EER:          {m['eer']:.6f}  in [{m['eer_bounds'][0]:.6f}, {m['eer_bounds'][1]:.6f}]")
+        print(f"  ROC-AUC:      {m['roc_auc']:.6f}  in [{m['roc_auc_bounds'][0]:.6f}, {m['roc_auc_bounds'][1]:.6f}]")
+        print(f"  Rank-1 identification rate: {ap['rank1_identification_rate']:.4f}")
+    print("\n" + "=" * 70)
 
 
 # =============================================================================
@@ -842,6 +1128,8 @@ def generate_evaluation_report(results: Dict[str, Dict[str, Any]], output_path: 
             'genuine_samples': int(np.sum(data['y_true'] == 1)),
             'forgery_samples': int(np.sum(data['y_true'] == 0)),
         }
+        if 'all_pairs' in data:
+            report['models'][model_name]['all_pairs'] = data['all_pairs']
 
     if len(results) > 1:
         comparison = {}
@@ -930,9 +1218,11 @@ def evaluate_signature_verifier(
     batch_size: int = 32,
     pairs_per_user: int = 20,
     threshold: float = 0.5,
-    device: Optional[str] = None
+    device: Optional[str] = None,
+    all_pairs: bool = False
 ) -> Dict[str, Any]:
-    """Run the complete signature verification evaluation pipeline; returns the report dictionary."""
+    """Run the complete signature verification evaluation pipeline; returns the report dictionary.  ``all_pairs`` adds
+    evaluate_all_pairs' result per model (report key 'all_pairs') and a block to the printed summary."""
     if device is None:
         device = 'cuda' if torch.cuda.is_available() else 'cpu'
     device = torch.device(device)
@@ -959,11 +1249,15 @@ def evaluate_signature_verifier(
         model, metadata = load_model(path, device)
         metrics, y_true, y_scores, y_pred = evaluate_model(model, test_loader, device, threshold)
         results[name] = {'metrics': metrics, 'y_true': y_true, 'y_scores': y_scores, 'y_pred': y_pred, 'metadata': metadata}
+        if all_pairs:
+            results[name]['all_pairs'] = evaluate_all_pairs(model, test_dir, threshold)
 
     if not results:
         raise ValueError("At least one model path must be provided for evaluation.")
 
     print_evaluation_summary(results)
+    if all_pairs:
+        print_all_pairs_summary(results)
 
     print("\n[Plots] Generating visualizations...")
     plotted = plot_roc_curve(results, output_path / 'roc_curve.png')
@@ -1009,6 +1303,8 @@ def main() -> None:
     parser.add_argument('--pairs_per_user', type=int, default=20,
                         help='Number of genuine/forgery pairs to generate per user')
     parser.add_argument('--threshold', type=float, default=0.5, help='Decision threshold for binary classification')
+    parser.add_argument('--all_pairs', action='store_true',
+                        help='Also evaluate on every pair of the test directory (N (N - 1) / 2 pairs) in one HIP pass')
     parser.add_argument('--device', type=str, default=None, choices=['cuda', 'cpu'],
                         help='Device to run evaluation on (default: auto-detect)')
     args = parser.parse_args()
@@ -1038,7 +1334,8 @@ def main() -> None:
         batch_size=args.batch_size,
         pairs_per_user=args.pairs_per_user,
         threshold=args.threshold,
-        device=args.device
+        device=args.device,
+        all_pairs=args.all_pairs
     )
 
 
