@@ -1,4 +1,4 @@
-"""ctypes binding of the C ABI in include/siggan.h (and siggan_mlp.h, siggan_verifier.h, siggan_verifier_grad.h, siggan_verifier_pairs.h,
+"""ctypes binding of the C ABI in include/siggan.h (and siggan_mlp.h, siggan_verifier.h, siggan_verifier_grad.h, siggan_verifier_pairs.h, siggan_verifier_topk.h,
 siggan_verifier_train.h, siggan_verifier_data.h, siggan_moments.h, siggan_select.h, siggan_neighbors.h).
 
 The shared library is built in-tree by ``__graft_entry__.build()`` / ``csrc/Makefile`` and must be
@@ -186,6 +186,22 @@ _VERIFIER_PAIRS_SIGNATURES = {
 }
 VERIFIER_PAIRS_EXPORTS = tuple(_VERIFIER_PAIRS_SIGNATURES)
 
+# per-row top-k lists out of the same pass (include/siggan_verifier_topk.h): new symbols again, listed on their own
+PAIR_TOPK_MAX = 16
+
+
+class PairTopk(C.Structure):              # siggan_pair_topk
+    _fields_ = [("impostor_score_dev", C.c_void_p), ("impostor_index_dev", C.c_void_p),
+                ("genuine_score_dev", C.c_void_p), ("genuine_index_dev", C.c_void_p)]
+
+
+_VERIFIER_TOPK_SIGNATURES = {
+    "siggan_verifier_pairs_topk_enable": (C.c_int, [C.c_void_p, C.c_int32, C.c_int32]),
+    "siggan_verifier_pairs_topk": (C.c_int, [C.c_void_p, C.c_void_p, C.c_void_p, C.c_int32, C.c_void_p, C.c_void_p, C.c_int32, C.c_int32,
+                                             C.c_int32, C.c_int32, C.POINTER(PairTopk), C.c_void_p]),
+}
+VERIFIER_TOPK_EXPORTS = tuple(_VERIFIER_TOPK_SIGNATURES)
+
 # the verifier's train step (include/siggan_verifier_train.h): again only new symbols
 VT_PARAM_TENSORS, VT_METRICS = 20, 4
 VT_RUNNING_FIELDS = ("bn1_running_mean", "bn1_running_var", "bn2_running_mean", "bn2_running_var", "bn3_running_mean",
@@ -258,7 +274,7 @@ def load():
             "(or `make -C signature-gan_amd/csrc`). This path has no CPU/PyTorch fallback.")
     lib = C.CDLL(LIB_PATH)
     for name, (res, args) in {**_SIGNATURES, **_VERIFIER_SIGNATURES, **_VERIFIER_GRAD_SIGNATURES, **_VERIFIER_PAIRS_SIGNATURES,
-                              **_VERIFIER_TRAIN_SIGNATURES,
+                              **_VERIFIER_TOPK_SIGNATURES, **_VERIFIER_TRAIN_SIGNATURES,
                               **_VERIFIER_DATA_SIGNATURES, **_MOMENTS_SIGNATURES, **_SELECT_SIGNATURES,
                               **_NEIGHBORS_SIGNATURES}.items():
         fn = getattr(lib, name)          # AttributeError if the library does not export the symbol

@@ -30,6 +30,7 @@
 #include "../../include/siggan_verifier.h"
 #include "../../include/siggan_verifier_grad.h"
 #include "../../include/siggan_verifier_pairs.h"
+#include "../../include/siggan_verifier_topk.h"
 #include "host.h"
 #include "verifier_parts.h"
 #include "verifier_pairs.h"
@@ -424,6 +425,9 @@ struct siggan_verifier {
     int pair_max, pair_kp;               // query rows the key workspace holds; E rounded up to PBK
     float* wpk;                          // classifier.0.weight in the B operand's lane order (k_vpairs_pack)
     unsigned long long* pkeys;           // [pair_max][PSPLIT_MAX][2]
+    // siggan_verifier_pairs_topk (allocated by _topk_enable; tkeys null before)
+    unsigned long long* tkeys;           // [topk_max][PSPLIT_MAX][2][topk_k]
+    int topk_max, topk_k;
 };
 
 extern "C" int siggan_verifier_create(int32_t device, int32_t E, int32_t max_images, siggan_verifier** out) {
@@ -437,6 +441,7 @@ extern "C" int siggan_verifier_create(int32_t device, int32_t E, int32_t max_ima
     if (!v) return FAIL(SIGGAN_E_NOMEM, "out of host memory");
     v->device = device; v->E = E; v->Nmax = max_images; v->bound = false; v->last_n = 0; v->ws = nullptr; v->gws = nullptr; v->grad_n = 0;
     v->pws = nullptr; v->pair_max = 0; v->pair_kp = 0;
+    v->tkeys = nullptr; v->topk_max = 0; v->topk_k = 0;
     const int64_t N = max_images;
     size_t off = 0; char* base = nullptr;
     auto carve = [&](float** p, int64_t n) { if (base) *p = (float*)(base + off); off += ((size_t)n * 4 + 255) & ~(size_t)255; };
@@ -467,6 +472,7 @@ extern "C" int siggan_verifier_destroy(siggan_verifier* v) {
     if (v->ws) (void)hipFree(v->ws);
     if (v->gws) (void)hipFree(v->gws);
     if (v->pws) (void)hipFree(v->pws);
+    if (v->tkeys) (void)hipFree(v->tkeys);
     delete v;
     return SIGGAN_OK;
 }
@@ -725,6 +731,17 @@ extern "C" int siggan_verifier_pairs_enable(siggan_verifier* v, int32_t max_quer
     return SIGGAN_OK;
 }
 
+// Grid: one block column per 16 query rows; the reference tiles are split over S block rows only while the query tiles
+// alone leave the device short of blocks, and never so few that a block's uint32 LDS counters could wrap (2^22 tiles of 512).
+static void pair_grid(int nq, int nr, int* QT, int* S, int* tps) {
+    const int ntiles = (nr + PR - 1) / PR;
+    *QT = (nq + PQ - 1) / PQ;
+    *S = 1;
+    if (*QT < 1024) *S = std::min(std::min(PSPLIT_MAX, ntiles), (1024 + *QT - 1) / *QT);
+    *S = std::max(*S, (ntiles + (1 << 22) - 1) >> 22);
+    *tps = (ntiles + *S - 1) / *S;
+}
+
 extern "C" int siggan_verifier_pairs(siggan_verifier* v, const float* q, const int32_t* qid, int32_t nq, const float* r, const int32_t* rid,
                                      int32_t nr, int32_t same_set, const siggan_pair_outputs* out, void* stream) {
     const char* fn = "siggan_verifier_pairs";
@@ -757,14 +774,10 @@ extern "C" int siggan_verifier_pairs(siggan_verifier* v, const float* q, const i
         return FAIL(SIGGAN_E_ARG, "%s: a pointer is not aligned to its element type", fn);
     DevGuard dg(v->device); HIPCHK(dg.err);
     hipStream_t s = (hipStream_t)stream;
-    // Grid: one block column per 16 query rows; the reference tiles are split over S block rows only while the query tiles
-    // alone leave the device short of blocks, and never so few that a block's uint32 LDS counters could wrap (2^22 tiles of 512).
-    const int QT = (nq + PQ - 1) / PQ, ntiles = (nr + PR - 1) / PR;
-    int S = 1;
-    if (QT < 1024) S = std::min(std::min(PSPLIT_MAX, ntiles), (1024 + QT - 1) / QT);
-    S = std::max(S, (ntiles + (1 << 22) - 1) >> 22);
-    const int tps = (ntiles + S - 1) / S;
+    int QT, S, tps;
+    pair_grid(nq, nr, &QT, &S, &tps);
     PairOut o;
+    o.list_k = o.list_flags = 0;
     o.score = out->score_dev;
     o.thr = want_counts ? out->threshold_dev : nullptr;
     o.T = want_counts ? T : 0;
@@ -783,5 +796,65 @@ extern "C" int siggan_verifier_pairs(siggan_verifier* v, const float* q, const i
     if (want_best)
         hipLaunchKernelGGL(k_vpairs_best, dim3(blocks(nq)), dim3(256), 0, s, (const unsigned long long*)v->pkeys, (int)nq, S,
                            out->best_genuine_dev, out->best_genuine_index_dev, out->best_impostor_dev, out->best_impostor_index_dev);
+    return hipGetLastError() == hipSuccess ? SIGGAN_OK : FAIL(SIGGAN_E_HIP, "%s: kernel launch failed", fn);
+}
+
+// ---------------------------------------------------------------- siggan_verifier_pairs_topk
+extern "C" int siggan_verifier_pairs_topk_enable(siggan_verifier* v, int32_t max_queries, int32_t max_k) {
+    const char* fn = "siggan_verifier_pairs_topk_enable";
+    if (!v) return FAIL(SIGGAN_E_ARG, "%s: null context", fn);
+    if (!v->pws) return FAIL(SIGGAN_E_ARG, "%s: siggan_verifier_pairs_enable has not been called", fn);
+    if (max_queries < 1) return FAIL(SIGGAN_E_ARG, "%s: max_queries %d < 1", fn, max_queries);
+    if (max_k < 1 || max_k > SIGGAN_PAIR_TOPK_MAX) return FAIL(SIGGAN_E_ARG, "%s: max_k %d outside [1, %d]", fn, max_k, SIGGAN_PAIR_TOPK_MAX);
+    if (v->tkeys && max_queries <= v->topk_max && max_k <= v->topk_k) return SIGGAN_OK;
+    DevGuard dg(v->device); HIPCHK(dg.err);
+    HIPCHK(hipDeviceSynchronize());                              // a set-up call: nothing may still read the slots it replaces
+    const int rows = std::max(max_queries, v->topk_max), k = std::max(max_k, v->topk_k);      // never shrinks
+    if (v->tkeys) { (void)hipFree(v->tkeys); v->tkeys = nullptr; v->topk_max = 0; v->topk_k = 0; }
+    const size_t bytes = (size_t)rows * PSPLIT_MAX * 2 * k * sizeof(unsigned long long);
+    hipError_t e = hipMalloc((void**)&v->tkeys, bytes);
+    if (e != hipSuccess) { v->tkeys = nullptr; return FAIL(SIGGAN_E_NOMEM, "hipMalloc(%zu) -> %s", bytes, hipGetErrorString(e)); }
+    v->topk_max = rows; v->topk_k = k;
+    return SIGGAN_OK;
+}
+
+extern "C" int siggan_verifier_pairs_topk(siggan_verifier* v, const float* q, const int32_t* qid, int32_t nq, const float* r,
+                                          const int32_t* rid, int32_t nr, int32_t same_set, int32_t k, int32_t genuine_lowest,
+                                          const siggan_pair_topk* out, void* stream) {
+    const char* fn = "siggan_verifier_pairs_topk";
+    int rc = vcheck(v, fn); if (rc) return rc;
+    if (!v->pws) return FAIL(SIGGAN_E_ARG, "%s: siggan_verifier_pairs_enable has not been called", fn);
+    if (!v->tkeys) return FAIL(SIGGAN_E_ARG, "%s: siggan_verifier_pairs_topk_enable has not been called", fn);
+    if (!q || !r || !out) return FAIL(SIGGAN_E_ARG, "%s: null argument", fn);
+    if (nq < 1 || nr < 1) return FAIL(SIGGAN_E_ARG, "%s: nq = %d, nr = %d: both must be >= 1", fn, nq, nr);
+    if ((int64_t)nq * nr >= ((int64_t)1 << 62)) return FAIL(SIGGAN_E_ARG, "%s: nq * nr >= 2^62", fn);
+    if (same_set && nq != nr) return FAIL(SIGGAN_E_ARG, "%s: same_set needs nq == nr, got %d and %d", fn, nq, nr);
+    if (k < 1 || k > v->topk_k) return FAIL(SIGGAN_E_ARG, "%s: k = %d outside [1, max_k = %d]", fn, k, v->topk_k);
+    if (nq > v->topk_max)
+        return FAIL(SIGGAN_E_ARG, "%s: nq = %d rows, siggan_verifier_pairs_topk_enable was given max_queries = %d", fn, nq, v->topk_max);
+    const bool want_imp = out->impostor_score_dev || out->impostor_index_dev, want_gen = out->genuine_score_dev || out->genuine_index_dev;
+    if (!want_imp && !want_gen) return FAIL(SIGGAN_E_ARG, "%s: no output requested", fn);
+    const bool vec = v->E % 4 == 0;
+    auto mis = [](const void* p, uintptr_t a) { return (reinterpret_cast<uintptr_t>(p) & (a - 1)) != 0; };
+    if (mis(q, vec ? 16 : 4) || mis(r, vec ? 16 : 4))
+        return FAIL(SIGGAN_E_ARG, "%s: the embeddings must be %d-byte aligned", fn, vec ? 16 : 4);
+    if (mis(qid, 4) || mis(rid, 4) || mis(out->impostor_score_dev, 4) || mis(out->impostor_index_dev, 4) ||
+        mis(out->genuine_score_dev, 4) || mis(out->genuine_index_dev, 4))
+        return FAIL(SIGGAN_E_ARG, "%s: a pointer is not aligned to its element type", fn);
+    DevGuard dg(v->device); HIPCHK(dg.err);
+    hipStream_t s = (hipStream_t)stream;
+    int QT, S, tps;
+    pair_grid(nq, nr, &QT, &S, &tps);            // S <= PSPLIT_MAX for every int32 nr (at most 2^26 tiles): the slots hold it
+    PairOut o;
+    o.score = nullptr; o.thr = nullptr; o.T = 0; o.gcnt = o.icnt = nullptr;
+    o.keys = v->tkeys;
+    o.list_k = k;
+    o.list_flags = (want_gen ? 1 : 0) | (want_imp ? 2 : 0) | (genuine_lowest ? 4 : 0);
+    auto kern = vec ? k_vpairs<true, 1> : k_vpairs<false, 1>;
+    hipLaunchKernelGGL(kern, dim3(QT, S), dim3(256), 0, s, q, qid, (int)nq, r, rid, (int)nr, v->E, v->pair_kp, (const float*)v->wpk,
+                       (const float*)v->bc0, (const float*)v->wc3, (const float*)v->bc3, (int)(same_set != 0), 0, tps, o);
+    hipLaunchKernelGGL(k_vpairs_topk_merge, dim3((2 * (int64_t)nq + 3) / 4), dim3(256), 0, s, (const unsigned long long*)v->tkeys, (int)nq,
+                       S, (int)k, (int)(genuine_lowest != 0), out->genuine_score_dev, out->genuine_index_dev, out->impostor_score_dev,
+                       out->impostor_index_dev);
     return hipGetLastError() == hipSuccess ? SIGGAN_OK : FAIL(SIGGAN_E_HIP, "%s: kernel launch failed", fn);
 }

@@ -18,6 +18,14 @@
 //
 // Grid (ceil(nq / 16), S): block (x, y) walks the reference tiles of split y.  S > 1 only when nq is too small to fill the
 // device; every (row, split) has its own slot for the row maxima and k_vpairs_best merges the slots in split order.
+//
+// LIST (siggan_verifier_pairs_topk, include/siggan_verifier_topk.h): instead of one maximum per (query, class) the wave keeps the k
+// best keys, k <= 16, distributed over its lanes 0 .. k-1 in descending order -- the same eight 64-bit registers per lane the row
+// maxima use.  A tile's 32 candidates of one query all sit in the writer lanes of the wave that owns the query: the lanes whose
+// key beats the current k-th entry are balloted and inserted one at a time (one ballot-popcount for the position, one shfl_up
+// for the shift); after the first tiles that ballot is almost always empty.  Keys are unique (the row is in the key), so the list
+// is the exact top k of the total order whatever the insertion order, the split count or the grid.  Every (row, split, class)
+// writes its k keys to its own slot and k_vpairs_topk_merge takes the S k <= 512 keys of a (row, class) into one wave.
 #pragma once
 #include "verifier_parts.h"
 
@@ -63,19 +71,39 @@ __device__ __forceinline__ unsigned long long wave_max_u64(unsigned long long v)
     }
     return v;
 }
+// pair_key with the order of the scores reversed: "lower score, then lower row"; never 0 for a score in [0, 1]
+__device__ __forceinline__ unsigned long long pair_key_low(float s, int j) {
+    return ((unsigned long long)(~__float_as_uint(s)) << 32) | (unsigned long long)(PKEY_IDX - (uint32_t)j);
+}
+// One list per wave: lane l < k holds the l-th largest key seen so far (0 = empty), lanes >= k hold 0.  Inserts every lane's
+// `cand` (0 = none) that belongs to the k largest; all 64 lanes must be active.  The loop is wave-uniform.
+__device__ __forceinline__ void pair_list_insert(unsigned long long& list, unsigned long long cand, int k, int lane) {
+    const unsigned long long kth = __shfl(list, k - 1, 64);
+    unsigned long long m = __ballot(cand > kth);
+    while (m) {
+        const int src = __ffsll((long long)m) - 1;
+        m &= m - 1;
+        const unsigned long long c = __shfl(cand, src, 64);
+        const int pos = __popcll(__ballot(lane < k && list > c));       // the list descends: exactly lanes 0 .. pos-1 stay
+        const unsigned long long up = __shfl_up(list, 1, 64);
+        if (lane < k && lane >= pos) list = lane == pos ? c : up;       // pos == k (the list moved on since the ballot): nothing
+    }
+}
 
 struct PairOut {
     float* score;                        // (nq, nr) or null
     const float* thr;                    // T ascending thresholds or null
     int T;
     unsigned long long *gcnt, *icnt;     // T + 1 bins each (zeroed before the launch) or null
-    unsigned long long* keys;            // [nq][S][2] or null
+    unsigned long long* keys;            // [nq][S][2] or null; LIST: [nq][S][2][list_k]
+    int list_k, list_flags;              // LIST only: k; bit 0 / 1: the genuine / impostor list is wanted, bit 2: genuine lowest
 };
 
 // dynamic LDS: T thresholds, then 2 (T + 1) counters (nothing when the counts are not asked for).  Two workgroups per CU (two
 // waves per SIMD: 256 registers, a few spilled in the epilogue): the second hides the first one's barriers, chunk-opening LDS
 // reads and epilogue -- measured 18 % faster at 16384^2 than the 374-register build that runs one wave per SIMD.
-template <bool VEC>
+// LIST: the k best per (query, class) instead of the maximum (file comment); the same budget -- the lists live in best[][].
+template <bool VEC, int LIST = 0>
 __global__ __launch_bounds__(256, 2) void k_vpairs(const float* __restrict__ q, const int32_t* __restrict__ qid, int nq,
                                                 const float* __restrict__ r, const int32_t* __restrict__ rid, int nr, int E, int Kp,
                                                 const float* __restrict__ wpk, const float* __restrict__ b0,
@@ -200,6 +228,14 @@ __global__ __launch_bounds__(256, 2) void k_vpairs(const float* __restrict__ q, 
                 }
                 atomicAdd(&hist[(genuine ? 0 : T + 1) + lo], 1u);
             }
+            if constexpr (LIST) {
+                const bool cand = live && !(same && j == i);
+                if (o.list_flags & 1) {
+                    const unsigned long long key = (o.list_flags & 4) ? pair_key_low(sc, (int)j) : pair_key(sc, (int)j);
+                    pair_list_insert(best[qq][0], cand && genuine ? key : 0ull, o.list_k, lane);
+                }
+                if (o.list_flags & 2) pair_list_insert(best[qq][1], cand && !genuine ? pair_key(sc, (int)j) : 0ull, o.list_k, lane);
+            } else
             if (o.keys && live && !(same && j == i)) {
                 const unsigned long long key = pair_key(sc, (int)j);
                 const unsigned long long kg = genuine ? key : 0ull, ki = genuine ? 0ull : key;
@@ -209,6 +245,15 @@ __global__ __launch_bounds__(256, 2) void k_vpairs(const float* __restrict__ q, 
         }
     }
 
+    if constexpr (LIST) {
+#pragma unroll
+        for (int qq = 0; qq < 4; ++qq) {
+            const int64_t i = i0 + 4 * wave + qq;
+#pragma unroll
+            for (int c = 0; c < 2; ++c)
+                if (lane < o.list_k && i < nq) o.keys[(((size_t)i * S + split) * 2 + c) * o.list_k + lane] = best[qq][c];
+        }
+    } else
     if (o.keys) {
 #pragma unroll
         for (int qq = 0; qq < 4; ++qq) {
@@ -247,6 +292,45 @@ __global__ void k_vpairs_best(const unsigned long long* __restrict__ keys, int n
         int32_t* io = c ? bii : bgi;
         if (so) so[i] = sc;
         if (io) io[i] = idx;
+    }
+}
+
+// One wave per (query row, class): the S k <= 512 keys of the row's slots, up to eight per lane, and k rounds of "take the wave's
+// maximum, clear it where it came from" (keys are unique: a reference row lies in one split).  Decoded as k_vpairs_best does;
+// `low`: the genuine keys carry the complemented score bits.  A class without an output pointer is skipped.
+__global__ __launch_bounds__(256) void k_vpairs_topk_merge(const unsigned long long* __restrict__ keys, int nq, int S, int k, int low,
+                                                         float* __restrict__ gs, int32_t* __restrict__ gi, float* __restrict__ is,
+                                                         int32_t* __restrict__ ii) {
+    const int lane = threadIdx.x & 63;
+    const int64_t w = (int64_t)blockIdx.x * 4 + (threadIdx.x >> 6);
+    const int64_t i = w >> 1;
+    const int c = (int)(w & 1);
+    if (i >= nq) return;
+    float* so = c ? is : gs;
+    int32_t* io = c ? ii : gi;
+    if (!so && !io) return;
+    const bool flip = low && c == 0;
+    const int n = S * k;
+    unsigned long long v[8];
+#pragma unroll
+    for (int t = 0; t < 8; ++t) {
+        const int e = lane + 64 * t;                                   // slot e / k, entry e % k
+        v[t] = e < n ? keys[(((size_t)i * S + e / k) * 2 + c) * k + e % k] : 0ull;
+    }
+    for (int p = 0; p < k; ++p) {
+        unsigned long long m = v[0];
+#pragma unroll
+        for (int t = 1; t < 8; ++t) m = v[t] > m ? v[t] : m;
+        m = wave_max_u64(m);
+        if (m) {
+#pragma unroll
+            for (int t = 0; t < 8; ++t) v[t] = v[t] == m ? 0ull : v[t];
+        }
+        if (lane == 0) {
+            const uint32_t hi = (uint32_t)(m >> 32);
+            if (so) so[(size_t)i * k + p] = m ? __uint_as_float(flip ? ~hi : hi) : -1.0f;
+            if (io) io[(size_t)i * k + p] = m ? (int32_t)(PKEY_IDX - (uint32_t)m) : -1;
+        }
     }
 }
 

@@ -11,6 +11,8 @@ what a PNG holds) and normalise them on load exactly as ToTensor + Normalize([0.
 embeddings that were computed earlier (one query against an enrolled gallery).  ``score_matrix`` / ``pair_counts`` /
 ``best_matches`` run the pair head over EVERY (query, reference) pair in one HIP call (include/siggan_verifier_pairs.h), and
 ``evaluate_all_pairs`` / ``--all_pairs`` evaluate a test directory on all N (N - 1) / 2 pairs instead of a sample.
+``pair_topk`` takes per-row lists out of the same pass (include/siggan_verifier_topk.h): each row's k highest-scoring
+impostors and k lowest- or highest-scoring genuine partners, which is what the trainer's hard-pair mining runs on.
 
 The metrics are numpy only (this package imports neither scikit-learn nor matplotlib at module level); the ROC points are
 those of ``sklearn.metrics.roc_curve`` with its defaults.  The plots are written when matplotlib can be imported.
@@ -58,6 +60,7 @@ class _Context:
         self._h = h
         self._grad_enabled = False
         self._pairs_rows = 0
+        self._topk = (0, 0)                                 # (max_queries, max_k) of siggan_verifier_pairs_topk_enable
 
     def _stream(self):
         return C.c_void_p(torch.cuda.current_stream(self.device).cuda_stream)
@@ -161,8 +164,32 @@ class _Context:
                                                   C.byref(o), self._stream()))
         return res
 
+    def pair_topk(self, e_q, ids_q, e_r, ids_r, k, same_set, genuine_lowest, want):
+        """siggan_verifier_pairs_topk on one chunk of queries (nq <= PAIR_TOPK_CHUNK is the caller's business): a dict of
+        (nq, k) tensors, '<class>_score' fp32 and '<class>_index' int32 for every class in ``want``."""
+        nq, nr = e_q.shape[0], e_r.shape[0]
+        if self._pairs_rows < 1:
+            _lib.check(self.lib.siggan_verifier_pairs_enable(self._h, 1))            # the weight pack; the lists have their own slots
+            self._pairs_rows = 1
+        rows, kmax = self._topk
+        if rows < nq or kmax < k:
+            _lib.check(self.lib.siggan_verifier_pairs_topk_enable(self._h, max(rows, nq), max(kmax, k)))
+            self._topk = (max(rows, nq), max(kmax, k))
+        e_q, e_r = e_q.contiguous(), e_r.contiguous()
+        ids_q = ids_q.contiguous() if ids_q is not None else None
+        ids_r = ids_r.contiguous() if ids_r is not None else None
+        res, o = {}, _lib.PairTopk()
+        for c in want:
+            res[f"{c}_score"] = torch.empty(nq, k, dtype=torch.float32, device=self.device)
+            res[f"{c}_index"] = torch.empty(nq, k, dtype=torch.int32, device=self.device)
+            setattr(o, f"{c}_score_dev", res[f"{c}_score"].data_ptr())
+            setattr(o, f"{c}_index_dev", res[f"{c}_index"].data_ptr())
+        _lib.check(self.lib.siggan_verifier_pairs_topk(self._h, _ptr(e_q), _ptr(ids_q), nq, _ptr(e_r), _ptr(ids_r), nr, int(bool(same_set)),
+                                                       int(k), int(bool(genuine_lowest)), C.byref(o), self._stream()))
+        return res
+
     def input_grad(self, x, ref_emb, embed_weight, score_weight, want_terms, want_score, want_emb, dx_out, objective_out):
-        if not self._grad_enabled:                          # lazily: contexts that never ask for a gradient pay nothing
+        if not self._grad_enabled:                         # lazily: contexts that never ask for a gradient pay nothing
             _lib.check(self.lib.siggan_verifier_input_grad_enable(self._h))
             self._grad_enabled = True
         n = x.shape[0]
@@ -236,6 +263,36 @@ def check_pairs_args(e_q, ids_q, e_r, ids_r, same_set, want_matrix, thresholds, 
         if not np.all(np.isfinite(thr)) or np.any(np.diff(thr) < 0):
             raise ValueError("the thresholds must be finite and ascending")
     return nq, nr, thr
+
+
+PAIR_TOPK_CLASSES = ("impostor", "genuine")
+PAIR_TOPK_CHUNK = 4096                      # query rows per siggan_verifier_pairs_topk call: bounds the key slots (32 MiB at k = 16)
+
+
+def check_pair_topk_args(e_q, ids_q, e_r, ids_r, k, same_set, want, embedding_dim, device=None):
+    """The refusals of siggan_verifier_pairs_topk that can be decided on the host, raised as ValueError before anything is
+    allocated; returns (nq, nr, the wanted classes in PAIR_TOPK_CLASSES order)."""
+    nq, nr, _ = check_pairs_args(e_q, ids_q, e_r, ids_r, same_set, True, None, False, embedding_dim, device)
+    if isinstance(k, bool) or not isinstance(k, (int, np.integer)) or not 1 <= k <= _lib.PAIR_TOPK_MAX:
+        raise ValueError(f"k must be an integer in 1 .. {_lib.PAIR_TOPK_MAX}, got {k!r}")
+    if isinstance(want, str):
+        want = (want,)
+    want = tuple(want)
+    if not want or any(c not in PAIR_TOPK_CLASSES for c in want):
+        raise ValueError(f"want must name at least one of {PAIR_TOPK_CLASSES}, got {want!r}")
+    return nq, nr, tuple(c for c in PAIR_TOPK_CLASSES if c in want)
+
+
+def _merge_topk(parts, k, lowest):
+    """Lists of the same query rows over disjoint reference ranges -> the list over their union: parts is a sequence of
+    (score (n, k), index (n, k)) already holding rows of the whole reference set.  Two stable sorts give the kernel's total
+    order (score, then row ascending); padding sorts last."""
+    score, index = torch.cat([p[0] for p in parts], 1), torch.cat([p[1] for p in parts], 1)
+    none = index < 0
+    o = torch.sort(torch.where(none, torch.iinfo(torch.int32).max, index), dim=1, stable=True).indices
+    score, index, none = score.gather(1, o), index.gather(1, o), none.gather(1, o)
+    o = torch.sort(torch.where(none, float("inf") if lowest else float("-inf"), score), dim=1, stable=True, descending=not lowest).indices
+    return score.gather(1, o)[:, :k].contiguous(), index.gather(1, o)[:, :k].contiguous()
 
 
 def check_identity_weights(embed_weight, score_weight):
@@ -471,6 +528,44 @@ class SiameseNetwork(_HipModule):
         genuine / impostor references and its row (the lower row on equal scores); -1.0 and -1 where a row has none."""
         out = self.pairs(e_q, ids_q, e_r, ids_r, same_set=same_set, want_best=True)
         return out["best_genuine"], out["best_genuine_index"], out["best_impostor"], out["best_impostor_index"]
+
+    def pair_topk(self, e_q: torch.Tensor, ids_q: Optional[torch.Tensor], e_r: torch.Tensor, ids_r: Optional[torch.Tensor], k: int,
+                  same_set: bool = False, genuine_lowest: bool = True, want=PAIR_TOPK_CLASSES) -> Dict[str, torch.Tensor]:
+        """Per query row the ``k`` (1 .. 16) highest-scoring impostor references and the ``k`` lowest-scoring (``genuine_lowest``,
+        the hard ones) or highest-scoring genuine references, out of the all-pairs pass in HIP (include/siggan_verifier_topk.h):
+        {'impostor_score', 'impostor_index', 'genuine_score', 'genuine_index'} (those of the classes in ``want``), each (nq, k),
+        fp32 scores that are ``score_matrix``'s bit for bit and int32 rows of ``e_r``.  Highest lists are ordered by (score
+        descending, row ascending), lowest lists by (score ascending, row ascending); positions beyond a row's candidates hold
+        -1.0 / -1.  ids, ``same_set``: as in ``pairs``.  The matrix is not formed; queries go through in chunks of
+        PAIR_TOPK_CHUNK rows (rows are independent: the chunking does not show in the result).  With ``same_set`` a chunk that
+        is not the whole set scores its own rows (same_set), the rows before and the rows after in three calls and merges
+        the lists by the same order."""
+        nq, nr, want = check_pair_topk_args(e_q, ids_q, e_r, ids_r, k, same_set, want, self.embedding_dim)
+        self._on_device(e_q, e_r)
+        ctx = self._context()
+        check_pair_topk_args(e_q, ids_q, e_r, ids_r, k, same_set, want, self.embedding_dim, ctx.device)
+        e_q, e_r = e_q.contiguous(), e_r.contiguous()
+        chunk = int(PAIR_TOPK_CHUNK)
+        if nq <= chunk:
+            return ctx.pair_topk(e_q, ids_q, e_r, ids_r, k, same_set, genuine_lowest, want)
+        outs = []
+        for a in range(0, nq, chunk):
+            b = min(a + chunk, nq)
+            q, qi = e_q[a:b], (ids_q[a:b] if ids_q is not None else None)
+            if not same_set:
+                outs.append(ctx.pair_topk(q, qi, e_r, ids_r, k, False, genuine_lowest, want))
+                continue
+            parts = []
+            for lo, hi, same in ((0, a, False), (a, b, True), (b, nr, False)):
+                if hi > lo:
+                    o = ctx.pair_topk(q, qi, e_r[lo:hi], ids_r[lo:hi] if ids_r is not None else None, k, same, genuine_lowest, want)
+                    parts.append({n: (torch.where(t < 0, t, t + lo) if n.endswith("_index") else t) for n, t in o.items()})
+            merged = {}
+            for c in want:
+                s, i = _merge_topk([(p[f"{c}_score"], p[f"{c}_index"]) for p in parts], k, genuine_lowest and c == "genuine")
+                merged[f"{c}_score"], merged[f"{c}_index"] = s, i
+            outs.append(merged)
+        return {n: torch.cat([o[n] for o in outs]) for n in outs[0]}
 
     def input_grad(self, x: torch.Tensor, ref_emb: torch.Tensor, embed_weight: float = 1.0, score_weight: float = 0.0,
                    want_terms: bool = False, want_score: bool = False, dx_out: Optional[torch.Tensor] = None,

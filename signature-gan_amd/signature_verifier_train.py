@@ -15,6 +15,10 @@ can be imported; without it ``train_model`` trains on the deterministic chain an
 ``input_pipeline="host"``.  With ``input_pipeline="device"`` (``--input_pipeline device``) the images are decoded once into an
 HBM-resident uint8 cache and every batch is gathered and augmented by one HIP launch with the reference's draws
 (``verifier_data.DevicePairLoader``); torchvision is not needed.
+
+Beyond the reference, and off by default: ``hard_mining`` (``--hard_mining K``, device pipeline only) adds to every epoch from
+``hard_mining_start`` on the pairs the current weights get most wrong -- per signature its K highest-scoring impostors and its
+lowest-scoring genuine partners, taken from one all-pairs pass in HIP (``verifier_mining``).
 """
 import argparse
 import ctypes as C
@@ -401,16 +405,42 @@ def _transforms():
 
 
 INPUT_PIPELINES = ("host", "device")
+MINING_FLAGS = ("hard_mining", "hard_mining_genuine", "hard_mining_start", "hard_mining_every")
+
+
+def check_hard_mining(input_pipeline, hard_mining, hard_mining_genuine=None, hard_mining_start=2, hard_mining_every=1):
+    """None when mining is off, else the checked (k_impostor, k_genuine, first epoch (1-based), period in epochs)."""
+    if hard_mining is None:
+        if hard_mining_genuine is not None:
+            raise ValueError("hard_mining_genuine needs hard_mining")
+        return None
+    if input_pipeline != "device":
+        raise ValueError("hard mining needs --input_pipeline device (the signatures are mined from the device loader's cache); "
+                         f"got input_pipeline={input_pipeline!r}")
+    k_imp = int(hard_mining)
+    k_gen = k_imp if hard_mining_genuine is None else int(hard_mining_genuine)
+    if not 1 <= k_imp <= _lib.PAIR_TOPK_MAX or not 0 <= k_gen <= _lib.PAIR_TOPK_MAX:
+        raise ValueError(f"hard_mining must be in 1 .. {_lib.PAIR_TOPK_MAX} and hard_mining_genuine in 0 .. {_lib.PAIR_TOPK_MAX}, "
+                         f"got {hard_mining} and {hard_mining_genuine}")
+    start, every = int(hard_mining_start), int(hard_mining_every)
+    if start < 1 or every < 1:
+        raise ValueError(f"hard_mining_start and hard_mining_every must be >= 1, got {hard_mining_start} and {hard_mining_every}")
+    return k_imp, k_gen, start, every
 
 
 def _fit(tag: str, dataset, epochs, output_path, file_name, batch_size, learning_rate, embedding_dim, device, extra,
-         input_pipeline: str = "host"):
+         input_pipeline: str = "host", mining=None):
     train_size = int(0.8 * len(dataset))
     val_size = len(dataset) - train_size
     train_dataset, val_dataset = torch.utils.data.random_split(dataset, [train_size, val_size])
     if input_pipeline == "device":
         from .verifier_data import DevicePairLoader
-        train_loader = DevicePairLoader(train_dataset, batch_size, shuffle=True, augment=True, device=device)
+        if mining is not None:
+            from .verifier_mining import MiningPairLoader
+            train_loader = MiningPairLoader(train_dataset, batch_size, shuffle=True, augment=True, k_impostor=mining[0],
+                                            k_genuine=mining[1], exclude_dataset=val_dataset, device=device)
+        else:
+            train_loader = DevicePairLoader(train_dataset, batch_size, shuffle=True, augment=True, device=device)
         val_loader = DevicePairLoader(val_dataset, batch_size, shuffle=False, augment=False, device=device)
     else:
         train_loader = DataLoader(train_dataset, batch_size=batch_size, shuffle=True, num_workers=0)
@@ -422,6 +452,8 @@ def _fit(tag: str, dataset, epochs, output_path, file_name, batch_size, learning
     best_val_acc = 0.0
     path = output_path / file_name
     for epoch in range(epochs):
+        if mining is not None and epoch + 1 >= mining[2] and (epoch + 1 - mining[2]) % mining[3] == 0:
+            print("  -> Mined %d hard pairs (%d impostor, %d genuine)" % train_loader.remine(model))
         train_metrics = train_epoch(model, train_loader, optimizer, criterion_bce, None, device)
         val_metrics = evaluate(model, val_loader, criterion_bce, device)
         scheduler.step()
@@ -445,12 +477,18 @@ def checkpoint_dict(model, embedding_dim, val_accuracy, epoch, **extra):
 
 def train_model(data_dir: str, synthetic_dir: Optional[str], epochs: int, model_output: str, batch_size: int = 32,
                 learning_rate: float = 0.001, embedding_dim: int = 128, device: Optional[str] = None,
-                input_pipeline: str = "host") -> Dict[str, str]:
+                input_pipeline: str = "host", hard_mining: Optional[int] = None, hard_mining_genuine: Optional[int] = None,
+                hard_mining_start: int = 2, hard_mining_every: int = 1) -> Dict[str, str]:
     """Trains the baseline model (real signatures) and, with a synthetic directory, the augmented one (real + synthetic);
     returns the paths of the saved best-validation checkpoints.  input_pipeline: "host" (the reference's DataLoader over
-    Pillow decodes) or "device" (HBM-resident cache + one augmentation launch per batch; module docstring)."""
+    Pillow decodes) or "device" (HBM-resident cache + one augmentation launch per batch; module docstring).
+    hard_mining: K (1 .. 16) turns hard-pair mining on (device pipeline only): from epoch ``hard_mining_start`` (1-based) on,
+    every ``hard_mining_every`` epochs, each real signature's K highest-scoring impostors and ``hard_mining_genuine`` (default K)
+    lowest-scoring genuine partners under the current weights join the epoch's pairs; the validation split's pairs are never
+    mined."""
     if input_pipeline not in INPUT_PIPELINES:
         raise ValueError(f"input_pipeline must be one of {INPUT_PIPELINES}, got {input_pipeline!r}")
+    mining = check_hard_mining(input_pipeline, hard_mining, hard_mining_genuine, hard_mining_start, hard_mining_every)
     if device is None:
         device = 'cuda' if torch.cuda.is_available() else 'cpu'
     device = torch.device(device)
@@ -471,7 +509,7 @@ def train_model(data_dir: str, synthetic_dir: Optional[str], epochs: int, model_
         print("Please ensure data directory contains signature images organized by user.")
     else:
         baseline_path = _fit("baseline", baseline_dataset, epochs, output_path, 'baseline_siamese_model.pth', batch_size,
-                             learning_rate, embedding_dim, device, {}, input_pipeline)
+                             learning_rate, embedding_dim, device, {}, input_pipeline, mining)
         saved_models['baseline'] = str(baseline_path)
         print(f"\nBaseline model saved to: {baseline_path}")
 
@@ -485,7 +523,7 @@ def train_model(data_dir: str, synthetic_dir: Optional[str], epochs: int, model_
             print("WARNING: No training pairs generated for augmented model.")
         else:
             augmented_path = _fit("augmented", augmented_dataset, epochs, output_path, 'augmented_siamese_model.pth', batch_size,
-                                  learning_rate, embedding_dim, device, {'includes_synthetic': True}, input_pipeline)
+                                  learning_rate, embedding_dim, device, {'includes_synthetic': True}, input_pipeline, mining)
             saved_models['augmented'] = str(augmented_path)
             print(f"\nAugmented model saved to: {augmented_path}")
     else:
@@ -507,7 +545,19 @@ def main(argv=None):
     parser.add_argument('--device', type=str, default=None, choices=['cuda', 'cpu'], help='Device to train on (default: auto-detect)')
     parser.add_argument('--input_pipeline', type=str, default='host', choices=list(INPUT_PIPELINES),
                         help='host: DataLoader over Pillow decodes; device: HBM-resident cache + on-device augmentation')
+    # (the mining flags appear in the namespace only when given, so the namespace of a command line without them is what it
+    #  was before they existed; train_model holds their defaults)
+    later = dict(type=int, default=argparse.SUPPRESS)
+    parser.add_argument('--hard_mining', metavar='K', **later,
+                        help='Hard-pair mining (needs --input_pipeline device): add each signature\'s K highest-scoring impostors '
+                             'under the current weights to the epoch\'s pairs (1 .. 16; default: off)')
+    parser.add_argument('--hard_mining_genuine', metavar='K', **later,
+                        help='With --hard_mining: lowest-scoring genuine partners per signature (default: the value of --hard_mining)')
+    parser.add_argument('--hard_mining_start', metavar='E', **later,
+                        help='With --hard_mining: first epoch, 1-based, that trains on mined pairs (default: 2)')
+    parser.add_argument('--hard_mining_every', metavar='N', **later, help='With --hard_mining: mine again every N epochs (default: 1)')
     args = parser.parse_args(argv)
+    mining = {k: getattr(args, k) for k in MINING_FLAGS if hasattr(args, k)}
 
     print("="*60)
     print("Signature Verification Model Training")
@@ -523,7 +573,7 @@ def main(argv=None):
 
     saved_models = train_model(data_dir=args.data_dir, synthetic_dir=args.synthetic_dir, epochs=args.epochs,
                                model_output=args.model_output, batch_size=args.batch_size, learning_rate=args.learning_rate,
-                               embedding_dim=args.embedding_dim, device=args.device, input_pipeline=args.input_pipeline)
+                               embedding_dim=args.embedding_dim, device=args.device, input_pipeline=args.input_pipeline, **mining)
 
     print("\n" + "="*60)
     print("Training Complete!")

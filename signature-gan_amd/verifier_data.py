@@ -145,10 +145,7 @@ class DevicePairLoader:
         self.device, self.dataset = dev, pairs_dataset
         self.batch_size, self.shuffle, self.augment, self.drop_last = int(batch_size), bool(shuffle), bool(augment), bool(drop_last)
         pairs = _pairs_of(pairs_dataset)
-        slot = {}
-        for p1, p2, _ in pairs:
-            for p in (p1, p2):
-                slot.setdefault(p, len(slot))
+        slot = self._cache_slots(pairs)
         cache = np.zeros((max(len(slot), 1), SIZE, SIZE), np.uint8)
         for p, k in slot.items():                            # decode + resize once; an unreadable file raises, as in the reference
             cache[k] = load_uint8(p)
@@ -156,21 +153,34 @@ class DevicePairLoader:
         self._slots = np.array([[slot[p1], slot[p2]] for p1, p2, _ in pairs], np.int32).reshape(len(pairs), 2)
         self._labels = np.array([float(y) for _, _, y in pairs], np.float32)
 
+    def _cache_slots(self, pairs) -> dict:
+        """file -> row of the cache: every distinct file of the pairs, in order of first use."""
+        slot = {}
+        for p1, p2, _ in pairs:
+            for p in (p1, p2):
+                slot.setdefault(p, len(slot))
+        return slot
+
+    def _epoch_pairs(self) -> Tuple[np.ndarray, np.ndarray]:
+        """(slots (n, 2) int32, labels (n,) float32) of the pairs one epoch runs over."""
+        return self._slots, self._labels
+
     def __len__(self) -> int:
-        n = len(self._labels)
+        n = len(self._epoch_pairs()[1])
         return n // self.batch_size if self.drop_last else (n + self.batch_size - 1) // self.batch_size
 
     def __iter__(self):
         dev = self.device
-        batches, draws = plan_pair_epoch(len(self._labels), self.batch_size, self.shuffle, self.drop_last, self.augment)
+        slots, labels = self._epoch_pairs()
+        batches, draws = plan_pair_epoch(len(labels), self.batch_size, self.shuffle, self.drop_last, self.augment)
         if not batches:
             return
         # rows of one batch of m pairs: its m first images, then its m second images (x1's rows first)
         starts = np.cumsum([0] + [len(b) for b in batches])
         order = np.concatenate([np.asarray(b, np.int64) for b in batches])
         rows = np.concatenate([np.concatenate([2 * np.arange(s, e), 2 * np.arange(s, e) + 1]) for s, e in zip(starts[:-1], starts[1:])])
-        index_dev = torch.from_numpy(np.ascontiguousarray(self._slots[order].reshape(-1)[rows])).to(dev)
-        labels_dev = torch.from_numpy(self._labels[order]).to(dev)
+        index_dev = torch.from_numpy(np.ascontiguousarray(slots[order].reshape(-1)[rows])).to(dev)
+        labels_dev = torch.from_numpy(labels[order]).to(dev)
         prm_dev = tab_dev = None
         if draws is not None:
             prm, tab = build_pair_params(*(draws[k].reshape(-1)[rows] for k in ("angle", "tx", "ty", "scale", "flip")))
