@@ -61,7 +61,11 @@ int64_t mlpgan_bn_count(const mlpgan_ctx *ctx);
 int mlpgan_bind(mlpgan_ctx *ctx, const mlpgan_storage *st);
 int mlpgan_seed(mlpgan_ctx *ctx, uint64_t seed, uint64_t offset);
 
-/* z_dev (B,latent) -> images_dev (B,1,S,S); training != 0: BatchNorm batch statistics (+ running update) */
+/* z_dev (B,latent) -> images_dev (B,1,S,S); training != 0: BatchNorm batch statistics (+ running update).
+ * BatchNorm batch statistics over ONE row are refused, as torch's BatchNorm1d refuses them: mlpgan_g_forward(training != 0)
+ * and mlpgan_g_step with batch == 1 return SIGGAN_E_INVALID ("BatchNorm1d: Expected more than 1 value per channel when
+ * training ...") before anything is enqueued -- parameters, gradients, moments, step counts, running statistics and the
+ * batch counters are untouched.  The eval-mode forward, mlpgan_d_forward and mlpgan_d_step accept batch == 1. */
 int mlpgan_g_forward(mlpgan_ctx *ctx, const float *z_dev, int32_t batch, int32_t training, float *images_dev, void *stream);
 /* x_dev (B,1,S,S) -> probs_dev (B) */
 int mlpgan_d_forward(mlpgan_ctx *ctx, const float *x_dev, int32_t batch, float *probs_dev, void *stream);

@@ -240,6 +240,11 @@ static int mcheck(mlpgan_ctx* c, int B) {
     if (e != hipSuccess) return FAIL(SIGGAN_E_HIP, "hipSetDevice -> %s", hipGetErrorString(e));
     return SIGGAN_OK;
 }
+// torch's BatchNorm1d refuses batch statistics over a single row (its variance is undefined); so does this path, with torch's text
+static int bn_train_check(const mlpgan_ctx* c, int B) {
+    if (B == 1) return FAIL(SIGGAN_E_INVALID, "BatchNorm1d: Expected more than 1 value per channel when training, got input size torch.Size([1, %d])", c->gdim[1]);
+    return SIGGAN_OK;
+}
 
 // Generator forward; training keeps y_i / a_i and the BatchNorm tables for the backward pass
 static void g_fwd(mlpgan_ctx* c, const float* z, int B, bool training, float* img, hipStream_t s) {
@@ -313,6 +318,7 @@ static int need_train_arenas(const mlpgan_ctx* c, int which) {
 extern "C" int mlpgan_g_forward(mlpgan_ctx* c, const float* z, int32_t B, int32_t training, float* img, void* stream) {
     int rc = mcheck(c, B); if (rc) return rc;
     if (!z || !img) return FAIL(SIGGAN_E_INVALID, "null tensor");
+    if (training != 0 && (rc = bn_train_check(c, B))) return rc;
     g_fwd(c, z, B, training != 0, img, (hipStream_t)stream);
     return hipGetLastError() == hipSuccess ? SIGGAN_OK : FAIL(SIGGAN_E_HIP, "kernel launch failed");
 }
@@ -345,6 +351,7 @@ extern "C" int mlpgan_g_step(mlpgan_ctx* c, int32_t B, const float* z, const sig
     int rc = mcheck(c, B); if (rc) return rc;
     if (!hp) return FAIL(SIGGAN_E_INVALID, "null argument");
     if ((rc = need_train_arenas(c, 0))) return rc;
+    if ((rc = bn_train_check(c, B))) return rc;
     hipStream_t s = (hipStream_t)stream;
     if (!mt) mt = c->metrics;
     if (z) HIPCHK(hipMemcpyAsync(c->z, z, (size_t)B * c->gdim[0] * sizeof(float), hipMemcpyDeviceToDevice, s));
