@@ -1,5 +1,5 @@
 """ctypes binding of the C ABI in include/siggan.h (and siggan_mlp.h, siggan_verifier.h, siggan_verifier_grad.h, siggan_verifier_pairs.h, siggan_verifier_topk.h,
-siggan_verifier_train.h, siggan_verifier_data.h, siggan_moments.h, siggan_select.h, siggan_neighbors.h).
+siggan_verifier_train.h, siggan_verifier_data.h, siggan_moments.h, siggan_select.h, siggan_neighbors.h, siggan_resize.h).
 
 The shared library is built in-tree by ``__graft_entry__.build()`` / ``csrc/Makefile`` and must be
 present: there is no CPU or PyTorch fallback for this path -- a missing or stale library raises.
@@ -260,6 +260,19 @@ _NEIGHBORS_SIGNATURES = {
 }
 NEIGHBORS_EXPORTS = tuple(_NEIGHBORS_SIGNATURES)
 
+# Pillow's antialiased bilinear resize, bytes and fp32 with its transpose (include/siggan_resize.h): new symbols again
+RESIZE_MAX_IN, RESIZE_MAX_OUT = 1024, 128
+_RESIZE_SIGNATURES = {
+    "siggan_resize_create": (C.c_int, [_I32, C.POINTER(_P)]),
+    "siggan_resize_destroy": (C.c_int, [_P]),
+    "siggan_resize_ksize": (_I32, [_I32, _I32]),
+    "siggan_resize_table": (C.c_int, [_I32, _I32, _P, _P, _P]),
+    "siggan_resize_u8": (C.c_int, [_P, _P, _I32, _I32, _I32, _P, _I32, _I32, _P]),
+    "siggan_resize_f32": (C.c_int, [_P, _P, _I32, _I32, _I32, _P, _I32, _I32, _P]),
+    "siggan_resize_f32_adjoint": (C.c_int, [_P, _P, _I32, _I32, _I32, _P, _I32, _I32, _P]),
+}
+RESIZE_EXPORTS = tuple(_RESIZE_SIGNATURES)
+
 _lib = None
 
 
@@ -276,7 +289,7 @@ def load():
     for name, (res, args) in {**_SIGNATURES, **_VERIFIER_SIGNATURES, **_VERIFIER_GRAD_SIGNATURES, **_VERIFIER_PAIRS_SIGNATURES,
                               **_VERIFIER_TOPK_SIGNATURES, **_VERIFIER_TRAIN_SIGNATURES,
                               **_VERIFIER_DATA_SIGNATURES, **_MOMENTS_SIGNATURES, **_SELECT_SIGNATURES,
-                              **_NEIGHBORS_SIGNATURES}.items():
+                              **_NEIGHBORS_SIGNATURES, **_RESIZE_SIGNATURES}.items():
         fn = getattr(lib, name)          # AttributeError if the library does not export the symbol
         fn.restype, fn.argtypes = res, args
     if lib.siggan_abi_version() != ABI_VERSION:

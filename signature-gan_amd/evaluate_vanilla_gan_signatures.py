@@ -17,7 +17,10 @@ Every generated batch's bytes go through ``embed_u8`` into an fp64 accumulator w
 precision / recall, density / coverage and the distance from every generated sample to its nearest real one, against the
 real set's own leave-one-out distances -- the memorisation check.  The embeddings of both sets are then also kept in a
 device buffer, and exact fp64 k-nearest-neighbour queries run there (utils/neighbors.py); k-lists and counts reach the
-host.  Without the flags nothing changes: stdout, report keys and exit codes are the reference's."""
+host.  A 128x128 Generator's bytes are shrunk to the verifier's 64x64 on the device first (resize.py: Pillow's antialiased
+bilinear filter, byte for byte what the reference's verifier transform makes of the written PNG), the real files are
+decoded at 64x64 for the verifier, and the report says so in ``verifier_input_resize``.
+Without the flags nothing changes: stdout, report keys and exit codes are the reference's."""
 import argparse
 import json
 import sys
@@ -30,6 +33,7 @@ import torch
 
 from .data_loader_signatures import FILL, SignatureDataset, normalize_lut
 from .generator_vanilla_gan import Generator
+from .resize import resize_f32, resize_u8
 from .train_vanilla_gan_signatures import save_sample_grid
 from .utils.inference import load_generator_and_config
 from .utils.frechet import FeatureMoments, embedding_spread, frechet_distance
@@ -80,14 +84,20 @@ def load_generator_from_checkpoint(checkpoint_path: Path, device: torch.device) 
 class EmbeddingSink:
     """One image set on its way into the verifier's embedding space: ``update`` embeds a batch (uint8 (B, 64, 64) or fp32
     (B, 1, 64, 64), on the device) and adds the embeddings to an fp64 accumulator there; ``finish`` -> (n, mean, cov).
-    ``keep``: the embeddings also stay, and ``embeddings`` hands them on as one (n, E) fp32 device buffer."""
+    ``keep``: the embeddings also stay, and ``embeddings`` hands them on as one (n, E) fp32 device buffer.  ``resize``: uint8
+    batches of another size (the 128x128 Generator's) go through resize.resize_u8 first -- Pillow's antialiased bilinear
+    filter on the device, what the reference's verifier transform does to a written file."""
 
-    def __init__(self, model, keep: bool = False) -> None:
-        self.model = model
+    def __init__(self, model, keep: bool = False, resize: bool = False) -> None:
+        self.model, self.resize = model, bool(resize)
         self.moments = FeatureMoments(model.embedding_dim, next(model.parameters()).device)
         self.kept: Optional[List[torch.Tensor]] = [] if keep else None
 
     def update(self, images: torch.Tensor) -> None:
+        if self.resize and tuple(images.shape[-2:]) != (VERIFIER_IMAGE_SIZE,) * 2:
+            # (fp32 images of another size: the same map without the byte roundings -- main() never sends any, it hands
+            # the real files over decoded at 64x64)
+            images = (resize_u8 if images.dtype == torch.uint8 else resize_f32)(images.contiguous(), VERIFIER_IMAGE_SIZE)
         for emb in verifier_embedding_chunks(images, self.model):
             self.moments.update(emb)
             if self.kept is not None:
@@ -107,14 +117,15 @@ class EmbeddingSink:
 
 class VerifierFeatures:
     """The Siamese verifier behind ``--verifier_checkpoint``: ``model`` (signature_verifier_eval.load_model), or ``error``
-    saying why the Frechet distance cannot be computed with it -- the report records that, the evaluation goes on."""
+    saying why the Frechet distance cannot be computed with it -- the report records that, the evaluation goes on.
+    ``input_resize``: None for a 64x64 Generator; for another size the name of the resize the generated bytes take on the
+    device before the verifier sees them (``verifier_input_resize`` in the report)."""
 
     def __init__(self, checkpoint: Path, device: torch.device, image_size: int, neighbors_k: Optional[int] = None) -> None:
         self.checkpoint, self.model, self.error = str(checkpoint), None, None
         self.neighbors_k = neighbors_k                          # --verifier_neighbors: the sinks keep their embeddings
-        if image_size != VERIFIER_IMAGE_SIZE:
-            self.error = f"the verifier takes {VERIFIER_IMAGE_SIZE}x{VERIFIER_IMAGE_SIZE} images"
-            return
+        self.input_resize = (None if image_size == VERIFIER_IMAGE_SIZE
+                             else f"pillow_bilinear_{image_size}_to_{VERIFIER_IMAGE_SIZE}")
         try:
             from .signature_verifier_eval import load_model
             self.model, _ = load_model(self.checkpoint, device)
@@ -122,7 +133,9 @@ class VerifierFeatures:
             self.error = f"could not load the verifier checkpoint: {e}"
 
     def sink(self) -> Optional[EmbeddingSink]:
-        return EmbeddingSink(self.model, keep=self.neighbors_k is not None) if self.model is not None else None
+        if self.model is None:
+            return None
+        return EmbeddingSink(self.model, keep=self.neighbors_k is not None, resize=self.input_resize is not None)
 
 
 @torch.no_grad()
@@ -165,9 +178,12 @@ def generate_samples(generator: Generator, n_samples: int, latent_dim: int, devi
     return GeneratedSamples(n_samples, (1, s, s), all_counts, kept, threshold, stats, error, embeddings)
 
 
-def load_real_images(real_dir: Path, n_images: int, image_size: int, device: torch.device) -> torch.Tensor:
+def load_real_images(real_dir: Path, n_images: int, image_size: int, device: torch.device,
+                     verifier_size: Optional[int] = None):
     """Up to ``n_images`` files of ``real_dir`` as (N, 1, S, S) fp32 in [-1, 1] ON THE DEVICE: decoded and resized by the
-    loader's helper (PIL -> 'L' -> bilinear), normalised by its byte table in the input-pipeline kernel."""
+    loader's helper (PIL -> 'L' -> bilinear), normalised by its byte table in the input-pipeline kernel.
+    ``verifier_size``: -> (that tensor, the SAME files decoded at verifier_size as uint8 (N, V, V) on the device) -- what the
+    reference's verifier sees of a real file, which it resizes from the file and not from a 128x128 copy."""
     from . import _lib
     real_dir = Path(real_dir)
     if not real_dir.exists():
@@ -179,13 +195,15 @@ def load_real_images(real_dir: Path, n_images: int, image_size: int, device: tor
     if len(picks) > n_images:
         picks = [int(i) for i in np.random.choice(len(picks), n_images, replace=False)]
     print(f"Loading {len(picks)} real images from {real_dir}")
-    decoded = []
+    decoded, small = [], []
     for i in picks:
         arr = ds.decode(i, image_size)
         if arr is None:
             print(f"  Warning: Failed to load {ds.get_image_path(i)}: unreadable image")
         else:
             decoded.append(arr)
+            if verifier_size is not None:
+                small.append(ds.decode(i, verifier_size))
     if not decoded:
         raise ValueError("No images could be loaded successfully")
     dev = torch.device(device)
@@ -201,6 +219,8 @@ def load_real_images(real_dir: Path, n_images: int, image_size: int, device: tor
     _lib.check(_lib.load().siggan_augment_batch(dev.index, cache.data_ptr(), n, index.data_ptr(), None, None, lut.data_ptr(),
                                                 out.data_ptr(), n, image_size, 0, FILL,
                                                 torch.cuda.current_stream(dev).cuda_stream))
+    if verifier_size is not None:
+        return out, torch.from_numpy(np.stack(small)).to(dev)
     return out
 
 
@@ -239,8 +259,10 @@ def _foreground(images) -> Dict[str, Any]:
 def _verifier_frechet(metrics: Dict[str, Any], fake_images, real_images: Optional[torch.Tensor],
                       verifier: VerifierFeatures) -> Optional[torch.Tensor]:
     """The ``verifier_*`` keys of the report; any failure is recorded as ``verifier_frechet_error``, like ``fid_error``.
+    ``real_images``: what the verifier is to see of the real set -- fp32 (N, 1, 64, 64) or uint8 (N, 64, 64).
     -> the real images' embeddings when the sink kept them (``--verifier_neighbors``), else None."""
     metrics["verifier_checkpoint"] = verifier.checkpoint
+    metrics["verifier_input_resize"] = verifier.input_resize
     real_embeddings = None
     print("Computing verifier Frechet distance...")
     try:
@@ -298,9 +320,12 @@ def _verifier_neighbors(metrics: Dict[str, Any], fake_images, real_embeddings: O
 
 
 def compute_metrics(fake_images, real_images: Optional[torch.Tensor], device: torch.device,
-                    verifier: Optional[VerifierFeatures] = None, neighbors_k: Optional[int] = None) -> Dict[str, Any]:
+                    verifier: Optional[VerifierFeatures] = None, neighbors_k: Optional[int] = None,
+                    verifier_real: Optional[torch.Tensor] = None) -> Dict[str, Any]:
     """The report's ``metrics`` dictionary.  ``fake_images``: a GeneratedSamples (its counters are used) or a tensor.
     ``verifier``: add the Frechet distance over its embeddings (the ``verifier_*`` keys; none without it).
+    ``verifier_real``: the real set as the verifier is to see it when that is not ``real_images`` (a 128x128 Generator: the
+    files decoded at 64x64, load_real_images' second result); the pixel-space metrics keep ``real_images``.
     ``neighbors_k``: add precision / recall, density / coverage and the nearest-real distances at that k."""
     metrics: Dict[str, Any] = {"n_samples": len(fake_images), "image_shape": list(fake_images.shape[1:]),
                                "metrics_computed_at": datetime.now().isoformat()}
@@ -334,7 +359,7 @@ def compute_metrics(fake_images, real_images: Optional[torch.Tensor], device: to
 
     real_embeddings = None
     if verifier is not None:
-        real_embeddings = _verifier_frechet(metrics, fake_images, real_images, verifier)
+        real_embeddings = _verifier_frechet(metrics, fake_images, real_images if verifier_real is None else verifier_real, verifier)
     if neighbors_k is not None:
         _verifier_neighbors(metrics, fake_images, real_embeddings, verifier, neighbors_k)
 
@@ -480,14 +505,17 @@ def main(argv=None) -> int:
                                 embedding_sink=verifier.sink() if verifier is not None else None)
         print("\nCreating sample grids...")
         grid_paths = create_sample_grids(fake, output_dir, a.n_grids, a.grid_size)
-        real = None
+        real = verifier_real = None
         if real_dir:
             try:
-                real = load_real_images(real_dir, a.n_samples, generator.output_size, device)
+                if verifier is not None and verifier.input_resize is not None:
+                    real, verifier_real = load_real_images(real_dir, a.n_samples, generator.output_size, device, VERIFIER_IMAGE_SIZE)
+                else:
+                    real = load_real_images(real_dir, a.n_samples, generator.output_size, device)
             except Exception as e:                              # noqa: BLE001 -- the evaluation goes on without them
                 print(f"Warning: Could not load real images: {e}")
         print("\nComputing evaluation metrics...")
-        metrics = compute_metrics(fake, real, device, verifier, a.verifier_neighbors)
+        metrics = compute_metrics(fake, real, device, verifier, a.verifier_neighbors, verifier_real)
         report_path = save_evaluation_report(metrics, config, output_dir, checkpoint_path, grid_paths)
         print_summary(metrics)
         print("\nEvaluation complete!")

@@ -111,12 +111,13 @@ def generate_refined(generator, discriminator, n_samples: int, output_dir: str, 
 def run_projection(generator, path: str, output_dir: str, prefix: str = "signature", steps: int = 200, lr: float = 0.05,
                    restarts: int = 1, seed: Optional[int] = None, discriminator=None, realism_weight: float = 0.0,
                    prior_weight: float = 0.0, verifier=None, identity_weight: float = 0.0,
-                   identity_score_weight: float = 0.0) -> None:
+                   identity_score_weight: float = 0.0, verifier_resize: bool = False) -> None:
     """Reconstructions of the image file / the images of the directory ``path``: ``<prefix>_projection_%06d.png`` each, and
     ``<prefix>_projection.json``: [{file, reconstruction, loss, z}, ...] in the same order; with ``realism_weight`` > 0 every
     record also holds ``realism``, the Discriminator's score of the reconstruction.  With a ``verifier`` every record holds
     ``identity``: {embedding_distance, verifier_score} of G(z) against the target at the returned z, and
-    ``identity_pixel_only``: the same two numbers for the projection without the identity term (what the term bought)."""
+    ``identity_pixel_only``: the same two numbers for the projection without the identity term (what the term bought).
+    ``verifier_resize``: the verifier reads targets and reconstructions through the device resize to 64x64 (a 128x128 Generator)."""
     from PIL import Image
     os.makedirs(output_dir, exist_ok=True)
     files, targets = load_target_images(path, generator.output_size)
@@ -124,13 +125,13 @@ def run_projection(generator, path: str, output_dir: str, prefix: str = "signatu
     kw = dict(steps=steps, lr=lr, seed=seed, restarts=restarts, discriminator=discriminator, realism_weight=realism_weight,
               prior_weight=prior_weight)
     z, recon, loss, _ = project_signatures(generator, targets, verifier=verifier, identity_weight=identity_weight,
-                                           identity_score_weight=identity_score_weight, **kw)
+                                           identity_score_weight=identity_score_weight, verifier_resize=verifier_resize, **kw)
     identity = pixel_only = None
     if verifier is not None:
-        identity = identity_report(generator, verifier, targets, z)
+        identity = identity_report(generator, verifier, targets, z, verifier_resize)
         pixel_only = identity
         if identity_weight > 0 or identity_score_weight > 0:
-            pixel_only = identity_report(generator, verifier, targets, project_signatures(generator, targets, **kw)[0])
+            pixel_only = identity_report(generator, verifier, targets, project_signatures(generator, targets, **kw)[0], verifier_resize)
     realism = None
     if realism_weight > 0:
         mb = generator._require_engine().max_batch
@@ -152,16 +153,18 @@ def run_projection(generator, path: str, output_dir: str, prefix: str = "signatu
     print(f"Saved {len(files)} reconstructions to: {output_dir}")
 
 
-def identity_report(generator, verifier, targets_u8, z):
+def identity_report(generator, verifier, targets_u8, z, resize: bool = False):
     """[{embedding_distance, verifier_score}, ...]: the verifier's view of G(z[i]) against target i -- the Euclidean distance of
-    the two unit embeddings and the head's similarity -- on the fp32 images of the eval-mode Generator."""
+    the two unit embeddings and the head's similarity -- on the fp32 images of the eval-mode Generator.  ``resize``: both go
+    through the device resize to 64x64 first (SiameseNetwork.embed_resized)."""
+    embed_f32, embed_u8 = (verifier.embed_resized,) * 2 if resize else (verifier.forward_one, verifier.embed_u8)
     eng = generator._require_engine()
     t = torch.as_tensor(targets_u8).to(z.device).contiguous()
     step = min(eng.max_batch, verifier.max_images)
     out = []
     for i in range(0, z.shape[0], step):
-        e = verifier.forward_one(eng.g_forward(z[i:i + step].contiguous(), training=False))
-        r = verifier.embed_u8(t[i:i + step])
+        e = embed_f32(eng.g_forward(z[i:i + step].contiguous(), training=False))
+        r = embed_u8(t[i:i + step])
         dist, score = (e - r).norm(dim=1).cpu(), verifier.compare(e, r).reshape(-1).cpu()
         out += [{"embedding_distance": float(d), "verifier_score": float(s)} for d, s in zip(dist, score)]
     return out
@@ -270,7 +273,8 @@ ADAPT_DEFAULTS = dict(adapt=None, adapt_steps=100, adapt_lr=1e-4, adapt_first_la
 
 
 # the identity flags of a projection, kept out of the namespace the same way
-IDENTITY_DEFAULTS = dict(verifier_checkpoint=None, project_identity_weight=0.0, project_identity_score_weight=0.0)
+IDENTITY_DEFAULTS = dict(verifier_checkpoint=None, project_identity_weight=0.0, project_identity_score_weight=0.0,
+                         project_identity_resize=False)
 
 
 def identity_opt(a: argparse.Namespace, name: str):
@@ -330,6 +334,9 @@ def parse_args(argv=None) -> argparse.Namespace:
                    help="With --project and --verifier_checkpoint: weight of 0.5 * |e(G(z)) - e(target)|^2 beside the pixel error (default: 0)")
     p.add_argument("--project_identity_score_weight", type=float, **later,
                    help="With --project and --verifier_checkpoint: weight of -log verifier_score(G(z), target) (default: 0)")
+    p.add_argument("--project_identity_resize", action="store_true", **later,
+                   help="With --project and --verifier_checkpoint: the verifier reads targets and G(z) through the device resize to "
+                        "64x64 (Pillow's antialiased bilinear filter), so a 128x128 Generator can be used (default: off)")
     p.add_argument("--adapt", type=str, metavar="PATH", **later,
                    help="Adapt the Generator's weights to an image file, or the images of a directory (pivotal tuning: project, then "
                         "Adam on the weights), generate n_samples signatures near the pivots and write <prefix>_adapt.json")
@@ -377,6 +384,8 @@ def parse_args(argv=None) -> argparse.Namespace:
         p.error("--project_identity_weight and --project_identity_score_weight must be >= 0")
     if (w_i[0] > 0 or w_i[1] > 0) and identity_opt(a, "verifier_checkpoint") is None:
         p.error("--project_identity_weight and --project_identity_score_weight need --verifier_checkpoint")
+    if identity_opt(a, "project_identity_resize") and identity_opt(a, "verifier_checkpoint") is None:
+        p.error("--project_identity_resize needs --verifier_checkpoint")
     if a.morph is not None and len(a.morph) not in (0, 2):
         p.error("--morph takes no image files (random endpoints) or exactly two")
     if a.morph_frames < 2:
@@ -434,7 +443,7 @@ def main(argv=None) -> None:
                 verifier = load_model(identity_opt(a, "verifier_checkpoint"), device)[0]
             run_projection(generator, a.project, a.output_dir, a.prefix, a.project_steps, a.project_lr, a.project_restarts, a.seed,
                            discriminator, w_d, w_p, verifier, identity_opt(a, "project_identity_weight"),
-                           identity_opt(a, "project_identity_score_weight"))
+                           identity_opt(a, "project_identity_score_weight"), identity_opt(a, "project_identity_resize"))
         if a.morph is not None:
             run_morph(generator, a.morph, a.output_dir, device, a.prefix, a.morph_frames, a.seed, a.threshold, a.transparent,
                       a.project_steps, a.project_lr, a.project_restarts)

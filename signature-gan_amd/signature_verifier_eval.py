@@ -13,6 +13,8 @@ embeddings that were computed earlier (one query against an enrolled gallery).  
 ``evaluate_all_pairs`` / ``--all_pairs`` evaluate a test directory on all N (N - 1) / 2 pairs instead of a sample.
 ``pair_topk`` takes per-row lists out of the same pass (include/siggan_verifier_topk.h): each row's k highest-scoring
 impostors and k lowest- or highest-scoring genuine partners, which is what the trainer's hard-pair mining runs on.
+``embed_resized`` / ``input_grad_resized`` take images of another size (the 128x128 Generator's) and shrink them to 64x64 on
+the device with Pillow's antialiased bilinear filter (resize.py), as the reference's transform shrinks a file.
 
 The metrics are numpy only (this package imports neither scikit-learn nor matplotlib at module level); the ROC points are
 those of ``sklearn.metrics.roc_curve`` with its defaults.  The plots are written when matplotlib can be imported.
@@ -31,6 +33,7 @@ from PIL import Image
 from torch.utils.data import DataLoader, Dataset
 
 from . import _lib
+from . import resize as _resize
 
 IMAGE_SIZE = 64
 DEFAULT_MAX_IMAGES = 512
@@ -586,6 +589,35 @@ class SiameseNetwork(_HipModule):
                 raise ValueError(f"{what} must be contiguous on {ctx.device}")
         return ctx.input_grad(x.view(n, 1, IMAGE_SIZE, IMAGE_SIZE), ref_emb, we, ws, want_terms, want_score, want_emb, dx_out,
                               objective_out)
+
+    def embed_resized(self, images: torch.Tensor) -> torch.Tensor:
+        """Embeddings of uint8 or fp32 images (N, H, W) / (N, 1, H, W) of any size the resize takes (1 .. 1024 per side), shrunk
+        to 64x64 on the device the way the reference's transforms.Resize((64, 64)) shrinks a file (resize.py): bytes by
+        resize_u8 -- Pillow's bytes -- then embed_u8, fp32 by resize_f32 then forward_one.  64x64 input goes to those two
+        directly: no copy, the same bits."""
+        self._on_device(images)
+        if images.dtype not in (torch.uint8, torch.float32):
+            raise ValueError(f"embed_resized takes uint8 or float32 images, got {images.dtype}")
+        if tuple(images.shape[-2:]) != (IMAGE_SIZE, IMAGE_SIZE):
+            images = (_resize.resize_u8 if images.dtype == torch.uint8 else _resize.resize_f32)(images.contiguous(), IMAGE_SIZE)
+        return self._context().embed(images)
+
+    def input_grad_resized(self, x: torch.Tensor, ref_emb: torch.Tensor, embed_weight: float = 1.0, score_weight: float = 0.0,
+                           want_terms: bool = False, want_score: bool = False, dx_out: Optional[torch.Tensor] = None,
+                           objective_out: Optional[torch.Tensor] = None, want_emb: bool = False):
+        """input_grad of the identity objective at resize_f32(x) for fp32 images ``x`` (N, 1, H, W) of any size the resize
+        takes, carried back to x: resize_f32 -> input_grad -> resize_f32_adjoint, three HIP calls and nothing else.  Returns
+        what input_grad returns with dx (N, 1, H, W); ``dx_out`` is of that size too.  64x64 input is input_grad itself."""
+        if not isinstance(x, torch.Tensor) or tuple(x.shape[-2:]) == (IMAGE_SIZE, IMAGE_SIZE):
+            return self.input_grad(x, ref_emb, embed_weight, score_weight, want_terms, want_score, dx_out, objective_out, want_emb)
+        check_identity_weights(embed_weight, score_weight)
+        if x.dtype != torch.float32 or not (x.dim() == 4 and x.shape[1] == 1):
+            raise ValueError(f"x must be float32 (N, 1, H, W), got {x.dtype} {tuple(x.shape)}")
+        self._on_device(x, ref_emb)
+        small = _resize.resize_f32(x, IMAGE_SIZE)
+        res = self.input_grad(small, ref_emb, embed_weight, score_weight, want_terms, want_score, None, objective_out, want_emb)
+        dx = _resize.resize_f32_adjoint(res[0], tuple(x.shape[-2:]), out=dx_out)
+        return (dx.view(x.shape),) + tuple(res[1:])
 
     def input_grad_debug(self, name, shape, dtype=torch.uint8):
         return self._context().input_grad_debug(name, shape, dtype)

@@ -454,9 +454,10 @@ def generate_signatures_refined(generator: Generator, discriminator: Discriminat
     return images, host(after), host(before)
 
 
-def check_identity_projection(generator, verifier, identity_weight, identity_score_weight):
+def check_identity_projection(generator, verifier, identity_weight, identity_score_weight, verifier_resize=False):
     """The host-side refusals of project_signatures' identity term, raised as ValueError before anything is allocated.
-    Returns None when both weights are 0 -- the verifier is then not looked at -- else the two weights as floats."""
+    Returns None when both weights are 0 -- the verifier is then not looked at -- else the two weights as floats.
+    ``verifier_resize``: the verifier reads G(z) through the device resize, so the Generator need not be a 64x64 one."""
     w = (float(identity_weight), float(identity_score_weight))
     if any(not math.isfinite(x) or x < 0.0 for x in w):
         raise ValueError(f"the identity weights must be finite and >= 0, got {w}")
@@ -464,7 +465,7 @@ def check_identity_projection(generator, verifier, identity_weight, identity_sco
         return None
     if verifier is None:
         raise ValueError("identity_weight / identity_score_weight > 0 need the verifier")
-    if generator.output_size != 64:
+    if generator.output_size != 64 and not verifier_resize:
         raise ValueError(f"the verifier reads 64x64 images: the identity term needs a 64x64 Generator, got {generator.output_size}")
     if verifier.training:
         raise ValueError("the identity term runs the verifier in eval mode: call .eval() on it")
@@ -474,16 +475,18 @@ def check_identity_projection(generator, verifier, identity_weight, identity_sco
     return w
 
 
-def _identity_grad(eng, verifier, t, ref_emb, realism_weight, prior_weight, w_e, w_s):
+def _identity_grad(eng, verifier, t, ref_emb, realism_weight, prior_weight, w_e, w_s, resize=False):
     """The ``grad`` of _descend with the identity term: g_forward -> verifier.input_grad (the image-space gradient of the
-    identity objective at G(z)) -> the seeded latent call (J_G^T of it joins dz) -> the identity objective added in torch."""
+    identity objective at G(z)) -> the seeded latent call (J_G^T of it joins dz) -> the identity objective added in torch.
+    ``resize``: verifier.input_grad_resized instead, which is input_grad itself at 64x64."""
     b = t.shape[0]
+    input_grad = verifier.input_grad_resized if resize else verifier.input_grad
     dx = torch.empty(b, 1, eng.image_size, eng.image_size, dtype=torch.float32, device=eng.device)
     ident = torch.empty(b, dtype=torch.float32, device=eng.device)
 
     def grad(k, z, dz, out):
         img = eng.g_forward(z, training=False)
-        verifier.input_grad(img, ref_emb, w_e, w_s, dx_out=dx, objective_out=ident)
+        input_grad(img, ref_emb, w_e, w_s, dx_out=dx, objective_out=ident)
         eng.g_latent_objective_grad(z, t, 1.0, realism_weight, prior_weight, dz_out=dz, objective_out=out, image_grad=dx)
         if out is not None:
             out += ident
@@ -494,7 +497,7 @@ def project_signatures(generator: Generator, targets_u8, steps: int = 200, lr: f
                        betas: Tuple[float, float] = (0.9, 0.999), z0: Optional[torch.Tensor] = None, seed: Optional[int] = None,
                        restarts: int = 1, return_candidates: bool = False, discriminator: Optional[Discriminator] = None,
                        realism_weight: float = 0.0, prior_weight: float = 0.0, verifier=None, identity_weight: float = 0.0,
-                       identity_score_weight: float = 0.0):
+                       identity_score_weight: float = 0.0, verifier_resize: bool = False):
     """Latent vectors whose images reproduce ``targets_u8`` ((N, S, S) uint8, numpy or tensor; a byte stands for
     byte / 127.5 - 1.0): ``steps`` iterations of Adam on z against the per-image loss mean((G(z) - t)^2), every iteration one
     Engine.g_latent_objective_grad (eval forward + eval backward in HIP) and one Engine.op_adam on (z, dz, m, v), all enqueued
@@ -514,8 +517,12 @@ def project_signatures(generator: Generator, targets_u8, steps: int = 200, lr: f
     0.5 * |e(G(z)) - e(t)|^2 + identity_score_weight * -log s(e(G(z)), e(t)).  The targets are embedded once (embed_u8);
     every iteration is then Engine.g_forward -> verifier.input_grad -> the seeded Engine.g_latent_objective_grad -> op_adam,
     still without a host synchronisation, and loss / history hold the full objective (restart selection uses it).  With both
-    weights 0 the verifier is never touched and every bit is as without these arguments."""
-    identity = check_identity_projection(generator, verifier, identity_weight, identity_score_weight)
+    weights 0 the verifier is never touched and every bit is as without these arguments.
+
+    ``verifier_resize``: the verifier reads the targets and G(z) through the device resize to 64x64 (Pillow's antialiased
+    bilinear filter, resize.py: embed_resized for the targets' bytes, input_grad_resized -- resize_f32, input_grad, the
+    resize's transpose -- for G(z)), so a 128x128 Generator can take the identity term.  On a 64x64 Generator it changes no bit."""
+    identity = check_identity_projection(generator, verifier, identity_weight, identity_score_weight, verifier_resize)
     if generator.training:
         raise ValueError("project_signatures needs the Generator in eval() mode (running BatchNorm statistics)")
     if steps < 1 or restarts < 1:
@@ -542,7 +549,8 @@ def project_signatures(generator: Generator, targets_u8, steps: int = 200, lr: f
         t = t_all[t0:t0 + b]
         grad = lambda k, z, dz, out: eng.g_latent_objective_grad(z, t, 1.0, realism_weight, prior_weight, dz_out=dz, objective_out=out)
         if identity:
-            grad = _identity_grad(eng, verifier, t, verifier.embed_u8(t), realism_weight, prior_weight, *identity)
+            ref_emb = verifier.embed_resized(t) if verifier_resize else verifier.embed_u8(t)
+            grad = _identity_grad(eng, verifier, t, ref_emb, realism_weight, prior_weight, *identity, resize=bool(verifier_resize))
         cand_hist[r, :, t0:t0 + b] = _descend(eng, z, steps, lr, betas, grad, cand_loss[r, t0:t0 + b])  # (the loss at the returned z)
         cand_z[r, t0:t0 + b] = z
     choice = torch.argmin(cand_loss, dim=0)                                        # (plumbing: the first of equal minima)
