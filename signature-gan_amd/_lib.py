@@ -1,5 +1,5 @@
 """ctypes binding of the C ABI in include/siggan.h (and siggan_mlp.h, siggan_verifier.h, siggan_verifier_grad.h, siggan_verifier_pairs.h, siggan_verifier_topk.h,
-siggan_verifier_train.h, siggan_verifier_data.h, siggan_moments.h, siggan_select.h, siggan_neighbors.h, siggan_resize.h).
+siggan_verifier_train.h, siggan_verifier_data.h, siggan_moments.h, siggan_select.h, siggan_neighbors.h, siggan_resize.h, siggan_components.h).
 
 The shared library is built in-tree by ``__graft_entry__.build()`` / ``csrc/Makefile`` and must be
 present: there is no CPU or PyTorch fallback for this path -- a missing or stale library raises.
@@ -273,6 +273,13 @@ _RESIZE_SIGNATURES = {
 }
 RESIZE_EXPORTS = tuple(_RESIZE_SIGNATURES)
 
+# connected ink components of byte images (include/siggan_components.h): context-free, one more symbol
+CC_MAX_SIZE, CC_COUNT = 128, 9
+_COMPONENTS_SIGNATURES = {
+    "siggan_components_u8": (C.c_int, [_I32, _P, _I32, _I32, _I32, _I32, _I32, _I32, _I32, _P, _P, _P, _P]),
+}
+COMPONENTS_EXPORTS = tuple(_COMPONENTS_SIGNATURES)
+
 _lib = None
 
 
@@ -289,7 +296,7 @@ def load():
     for name, (res, args) in {**_SIGNATURES, **_VERIFIER_SIGNATURES, **_VERIFIER_GRAD_SIGNATURES, **_VERIFIER_PAIRS_SIGNATURES,
                               **_VERIFIER_TOPK_SIGNATURES, **_VERIFIER_TRAIN_SIGNATURES,
                               **_VERIFIER_DATA_SIGNATURES, **_MOMENTS_SIGNATURES, **_SELECT_SIGNATURES,
-                              **_NEIGHBORS_SIGNATURES, **_RESIZE_SIGNATURES}.items():
+                              **_NEIGHBORS_SIGNATURES, **_RESIZE_SIGNATURES, **_COMPONENTS_SIGNATURES}.items():
         fn = getattr(lib, name)          # AttributeError if the library does not export the symbol
         fn.restype, fn.argtypes = res, args
     if lib.siggan_abi_version() != ABI_VERSION:

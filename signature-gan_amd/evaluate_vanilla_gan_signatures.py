@@ -39,11 +39,12 @@ from .utils.inference import load_generator_and_config
 from .utils.frechet import FeatureMoments, embedding_spread, frechet_distance
 from .utils.metrics import (INCEPTION_AVAILABLE, LPIPS_AVAILABLE, calculate_fid, calculate_foreground_ratio,
                             calculate_lpips_diversity, calculate_stroke_density, foreground_ratio_from_counts,
-                            stroke_density_from_counts, verifier_embedding_chunks)
+                            fragmentation_from_counters, stroke_density_from_counts, verifier_embedding_chunks)
 from .utils.neighbors import manifold_metrics
 
 THRESHOLD = 0.5          # the threshold compute_metrics passes to both statistics (evaluate_vanilla_gan_signatures.py:306,318)
 VERIFIER_IMAGE_SIZE = 64
+COMPONENT_THRESHOLD, COMPONENT_CONNECTIVITY = 128, 8      # --components: ink is byte < 128, 8-connected
 
 
 class GeneratedSamples:
@@ -138,13 +139,34 @@ class VerifierFeatures:
         return EmbeddingSink(self.model, keep=self.neighbors_k is not None, resize=self.input_resize is not None)
 
 
+class ComponentSink:
+    """Collects the component counters (components.component_stats, int32 (B, 9)) of every uint8 batch it is shown while the
+    batch is on the device; ``counters()`` brings all of them to the host at once.  ``min_area`` None: resolved to
+    components.default_min_area of the first batch's size."""
+
+    def __init__(self, min_area: Optional[int] = None, threshold: int = COMPONENT_THRESHOLD,
+                 connectivity: int = COMPONENT_CONNECTIVITY) -> None:
+        self.min_area, self.threshold, self.connectivity, self.parts = min_area, threshold, connectivity, []
+
+    def update(self, u8: torch.Tensor) -> None:
+        from .components import component_stats, default_min_area
+        if self.min_area is None:
+            self.min_area = default_min_area(u8.shape[-2], u8.shape[-1])
+        self.parts.append(component_stats(u8.contiguous(), self.threshold, self.connectivity, self.min_area))
+
+    def counters(self) -> np.ndarray:
+        return torch.cat(self.parts).cpu().numpy() if self.parts else np.zeros((0, 9), np.int32)
+
+
 @torch.no_grad()
 def generate_samples(generator: Generator, n_samples: int, latent_dim: int, device: torch.device, batch_size: int = 64,
                      keep_images: Optional[int] = None, threshold: float = THRESHOLD,
-                     embedding_sink: Optional[EmbeddingSink] = None) -> GeneratedSamples:
+                     embedding_sink: Optional[EmbeddingSink] = None,
+                     component_sink: Optional[ComponentSink] = None) -> GeneratedSamples:
     """N samples, z = torch.randn per batch as the reference draws it (so a seed means the same).  ``keep_images``: how
     many leading samples to bring back as fp32 images (None: all, what the reference returns).  ``embedding_sink``: receives
-    every batch's uint8 tensor while it is on the device; its finished statistics travel in the result."""
+    every batch's uint8 tensor while it is on the device; its finished statistics travel in the result.  ``component_sink``:
+    is shown the same bytes and keeps their component counters."""
     generator.eval()
     eng = generator._require_engine()
     keep = n_samples if keep_images is None else max(0, min(int(keep_images), n_samples))
@@ -163,6 +185,8 @@ def generate_samples(generator: Generator, n_samples: int, latent_dim: int, devi
         counts.append(st)
         if embedding_sink is not None:
             embedding_sink.update(u8)
+        if component_sink is not None:
+            component_sink.update(u8)
         if (i + 1) % 10 == 0 or i == n_batches - 1:
             print(f"  Generated {min((i + 1) * batch_size, n_samples)}/{n_samples} samples")
     s = generator.output_size
@@ -179,11 +203,12 @@ def generate_samples(generator: Generator, n_samples: int, latent_dim: int, devi
 
 
 def load_real_images(real_dir: Path, n_images: int, image_size: int, device: torch.device,
-                     verifier_size: Optional[int] = None):
+                     verifier_size: Optional[int] = None, component_sink: Optional[ComponentSink] = None):
     """Up to ``n_images`` files of ``real_dir`` as (N, 1, S, S) fp32 in [-1, 1] ON THE DEVICE: decoded and resized by the
     loader's helper (PIL -> 'L' -> bilinear), normalised by its byte table in the input-pipeline kernel.
     ``verifier_size``: -> (that tensor, the SAME files decoded at verifier_size as uint8 (N, V, V) on the device) -- what the
-    reference's verifier sees of a real file, which it resizes from the file and not from a 128x128 copy."""
+    reference's verifier sees of a real file, which it resizes from the file and not from a 128x128 copy.
+    ``component_sink``: is shown the decoded BYTES (the cache the normalisation reads), not a re-quantised fp32 copy."""
     from . import _lib
     real_dir = Path(real_dir)
     if not real_dir.exists():
@@ -213,6 +238,8 @@ def load_real_images(real_dir: Path, n_images: int, image_size: int, device: tor
         dev = torch.device("cuda", torch.cuda.current_device())
     n = len(decoded)
     cache = torch.from_numpy(np.stack(decoded)).to(dev)
+    if component_sink is not None:
+        component_sink.update(cache)
     index = torch.arange(n, dtype=torch.int32, device=dev)
     lut = normalize_lut((-1.0, 1.0)).to(dev)
     out = torch.empty(n, 1, image_size, image_size, dtype=torch.float32, device=dev)
@@ -321,12 +348,13 @@ def _verifier_neighbors(metrics: Dict[str, Any], fake_images, real_embeddings: O
 
 def compute_metrics(fake_images, real_images: Optional[torch.Tensor], device: torch.device,
                     verifier: Optional[VerifierFeatures] = None, neighbors_k: Optional[int] = None,
-                    verifier_real: Optional[torch.Tensor] = None) -> Dict[str, Any]:
+                    verifier_real: Optional[torch.Tensor] = None, fragmentation: Optional[Dict[str, Any]] = None) -> Dict[str, Any]:
     """The report's ``metrics`` dictionary.  ``fake_images``: a GeneratedSamples (its counters are used) or a tensor.
     ``verifier``: add the Frechet distance over its embeddings (the ``verifier_*`` keys; none without it).
     ``verifier_real``: the real set as the verifier is to see it when that is not ``real_images`` (a 128x128 Generator: the
     files decoded at 64x64, load_real_images' second result); the pixel-space metrics keep ``real_images``.
-    ``neighbors_k``: add precision / recall, density / coverage and the nearest-real distances at that k."""
+    ``neighbors_k``: add precision / recall, density / coverage and the nearest-real distances at that k.
+    ``fragmentation``: the finished ``fragmentation`` block (fragmentation_block), added as it is; no key without it."""
     metrics: Dict[str, Any] = {"n_samples": len(fake_images), "image_shape": list(fake_images.shape[1:]),
                                "metrics_computed_at": datetime.now().isoformat()}
     if real_images is not None and INCEPTION_AVAILABLE:
@@ -387,7 +415,21 @@ def compute_metrics(fake_images, real_images: Optional[torch.Tensor], device: to
             print(f"  Real Foreground Ratio - Mean: {rf['mean']:.4f}")
         except Exception as e:                                  # noqa: BLE001
             print(f"  Warning: Real image statistics failed: {e}")
+    if fragmentation is not None:
+        metrics["fragmentation"] = fragmentation
+        g = fragmentation["generated"]
+        print(f"  Ink components per image - Mean: {g['components_mean']:.2f}, speckle ink ratio: {g['speckle_ink_ratio']:.4f}")
     return metrics
+
+
+def fragmentation_block(generated: ComponentSink, real: Optional[ComponentSink] = None) -> Dict[str, Any]:
+    """The report's ``fragmentation`` key: {generated, real (only when a real set was counted), threshold, connectivity,
+    min_area}, each side a utils.metrics.fragmentation_from_counters dictionary."""
+    block: Dict[str, Any] = {"generated": fragmentation_from_counters(generated.counters())}
+    if real is not None and real.parts:
+        block["real"] = fragmentation_from_counters(real.counters())
+    block.update(threshold=generated.threshold, connectivity=generated.connectivity, min_area=generated.min_area)
+    return block
 
 
 def save_evaluation_report(metrics: Dict[str, Any], config: Dict[str, Any], output_dir: Path, checkpoint_path: Path,
@@ -456,6 +498,16 @@ def print_summary(metrics: Dict[str, Any]) -> None:
         print(f"Real Stroke Density Mean: {rs['mean']:.4f} (Generated: {stroke['mean']:.4f})")
         if rf:
             print(f"Real Foreground Ratio Mean: {rf['mean']:.4f} (Generated: {fg['mean']:.4f})")
+    if "fragmentation" in metrics:
+        fr = metrics["fragmentation"]
+        print(f"\n--- Fragmentation (ink components, min area {fr['min_area']} px, {fr['connectivity']}-connected) ---")
+        for side in ("generated", "real"):
+            if side in fr:
+                d = fr[side]
+                share = d["largest_component_share_mean"]
+                print(f"{side.capitalize()}: {d['components_mean']:.2f} components per image (median {d['components_median']:.1f}), "
+                      f"{d['small_components_mean']:.2f} specks, speckle ink ratio {d['speckle_ink_ratio']:.4f}, largest component share "
+                      f"{'n/a' if share is None else format(share, '.4f')}, {d['empty_images']} empty")
     print("\n" + bar)
 
 
@@ -464,6 +516,7 @@ class _Args(argparse.Namespace):
     without them parses to the reference's attributes and nothing else."""
     verifier_checkpoint = None
     verifier_neighbors = None
+    components = None
 
 
 def parse_args(argv=None) -> argparse.Namespace:
@@ -483,7 +536,14 @@ def parse_args(argv=None) -> argparse.Namespace:
     p.add_argument("--verifier_neighbors", type=int, default=None, metavar="K",
                    help="With --verifier_checkpoint and --real_dir: adds precision / recall, density / coverage and "
                         "nearest-real distances over the verifier's embeddings, from K nearest neighbours")
-    return p.parse_args(argv, namespace=_Args())
+    p.add_argument("--components", nargs="?", type=lambda v: v if v == "auto" else int(v), const="auto", default=None, metavar="MIN_AREA",
+                   help="Label the ink components of every generated (and real) image on the device and add a 'fragmentation' "
+                        "block to the report; a component of fewer than MIN_AREA pixels counts as a speck "
+                        "(MIN_AREA omitted: max(2, round(0.001 * H * W)))")
+    a = p.parse_args(argv, namespace=_Args())
+    if a.components is not None and a.components != "auto" and a.components < 1:
+        p.error("--components MIN_AREA must be >= 1")
+    return a
 
 
 def main(argv=None) -> int:
@@ -500,22 +560,28 @@ def main(argv=None) -> int:
         generator, config = load_generator_from_checkpoint(checkpoint_path, device)
         verifier = (VerifierFeatures(Path(a.verifier_checkpoint), device, generator.output_size, a.verifier_neighbors)
                     if a.verifier_checkpoint else None)
+        frag_fake = frag_real = None
+        if a.components is not None:
+            min_area = None if a.components == "auto" else a.components
+            frag_fake, frag_real = ComponentSink(min_area), ComponentSink(min_area)
         fake = generate_samples(generator, a.n_samples, generator.latent_dim, device, a.batch_size,
                                 keep_images=max(0, a.n_grids) * a.grid_size,
-                                embedding_sink=verifier.sink() if verifier is not None else None)
+                                embedding_sink=verifier.sink() if verifier is not None else None, component_sink=frag_fake)
         print("\nCreating sample grids...")
         grid_paths = create_sample_grids(fake, output_dir, a.n_grids, a.grid_size)
         real = verifier_real = None
         if real_dir:
             try:
                 if verifier is not None and verifier.input_resize is not None:
-                    real, verifier_real = load_real_images(real_dir, a.n_samples, generator.output_size, device, VERIFIER_IMAGE_SIZE)
+                    real, verifier_real = load_real_images(real_dir, a.n_samples, generator.output_size, device, VERIFIER_IMAGE_SIZE,
+                                                           component_sink=frag_real)
                 else:
-                    real = load_real_images(real_dir, a.n_samples, generator.output_size, device)
+                    real = load_real_images(real_dir, a.n_samples, generator.output_size, device, component_sink=frag_real)
             except Exception as e:                              # noqa: BLE001 -- the evaluation goes on without them
                 print(f"Warning: Could not load real images: {e}")
         print("\nComputing evaluation metrics...")
-        metrics = compute_metrics(fake, real, device, verifier, a.verifier_neighbors, verifier_real)
+        metrics = compute_metrics(fake, real, device, verifier, a.verifier_neighbors, verifier_real,
+                                  fragmentation_block(frag_fake, frag_real) if frag_fake is not None else None)
         report_path = save_evaluation_report(metrics, config, output_dir, checkpoint_path, grid_paths)
         print_summary(metrics)
         print("\nEvaluation complete!")

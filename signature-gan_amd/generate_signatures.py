@@ -19,7 +19,15 @@ before and after.  ``--project_realism_weight`` / ``--project_prior_weight`` add
 ``--adapt PATH`` changes the model instead of the latent vectors (utils.inference.adapt_generator: the images of PATH are
 projected to pivots, then Adam runs on the Generator's weights around the library's eval-mode dL/dtheta); ``--n_samples``
 signatures are then generated at z = pivot[i mod N] + S * randn with S = ``--adapt_sigma`` (default 0.25 * ``--noise_scale``),
-``<prefix>_adapt.json`` records each target's loss before and after, and ``--adapt_save CKPT`` keeps the adapted weights."""
+``<prefix>_adapt.json`` records each target's loss before and after, and ``--adapt_save CKPT`` keeps the adapted weights.
+
+``--despeckle [MIN_AREA]`` cleans every generated signature on the device before it is written (components.despeckle_u8): an
+ink component (byte < ``--threshold``, 128 without it; 8-connected) of fewer than MIN_AREA pixels becomes white, every other
+byte stays.  It applies to the plain run, ``--filter_by_realism`` (the pool is cleaned before it is scored, so a score belongs
+to the file it stands beside), ``--refine_by_realism`` and ``--adapt``; projections and morph strips are left alone.  What
+was removed is recorded as ``despeckle: {min_area, threshold, connectivity, removed_components, removed_pixels}``: in
+``<prefix>_despeckle.json`` for a plain run, as a key of ``<prefix>_adapt.json``, and in ``<prefix>_scores.json`` /
+``<prefix>_refine.json``, which then are ``{"despeckle": {...}, "records": [...]}`` instead of the bare list."""
 import argparse
 import json
 import os
@@ -29,7 +37,7 @@ from typing import Any, Dict, Optional
 import numpy as np
 import torch
 
-from .utils.inference import (generate_signatures_batch, generate_signatures_filtered, generate_signatures_refined,
+from .utils.inference import (Despeckle, generate_signatures_batch, generate_signatures_filtered, generate_signatures_refined,
                               load_discriminator, load_generator, load_target_images, morph_sequence, morph_strip, process_images,
                               project_signatures)
 
@@ -37,25 +45,45 @@ from .utils.inference import (generate_signatures_batch, generate_signatures_fil
 def generate_signatures(generator, n_samples: int, output_dir: str, batch_size: int = 64,
                         device: torch.device = torch.device("cuda"), seed: Optional[int] = None,
                         prefix: str = "signature", noise_scale: float = 1.0, threshold: Optional[int] = None,
-                        transparent: bool = False) -> None:
+                        transparent: bool = False, despeckle: Optional[Despeckle] = None) -> None:
     os.makedirs(output_dir, exist_ok=True)
     print(f"Output directory: {output_dir}")
     print(f"Generating {n_samples} signatures...")
     images = generate_signatures_batch(generator=generator, n_samples=n_samples, latent_dim=generator.latent_dim,
-                                       device=device, seed=seed, batch_size=batch_size, noise_scale=noise_scale)
+                                       device=device, seed=seed, batch_size=batch_size, noise_scale=noise_scale,
+                                       **with_despeckle(despeckle))
     if threshold is not None:
         images = process_images(images, threshold=threshold, make_transparent=transparent)
     print(f"Saving {len(images)} images...")
     for i, img in enumerate(images):
         img.save(os.path.join(output_dir, f"{prefix}_{i + 1:06d}.png"), "PNG")
+    if despeckle is not None:
+        with open(os.path.join(output_dir, f"{prefix}_despeckle.json"), "w") as f:
+            json.dump({"despeckle": despeckle.report()}, f, indent=2)
+        print_despeckle(despeckle)
     print("\nGeneration complete!")
     print(f"Generated {len(images)} signatures saved to: {output_dir}")
+
+
+def with_despeckle(despeckle: Optional[Despeckle]) -> Dict[str, Any]:
+    """The keyword a generation call gets: none at all without --despeckle, so such a call is what it was."""
+    return {} if despeckle is None else {"despeckle": despeckle}
+
+
+def print_despeckle(despeckle: Despeckle) -> None:
+    r = despeckle.report()
+    print(f"Despeckle: removed {r['removed_components']} components ({r['removed_pixels']} pixels) smaller than {r['min_area']} pixels")
+
+
+def records_json(records, despeckle: Optional[Despeckle]):
+    """What <prefix>_scores.json / <prefix>_refine.json hold: the bare list, or with --despeckle the list beside its report."""
+    return records if despeckle is None else {"despeckle": despeckle.report(), "records": records}
 
 
 def generate_filtered(generator, discriminator, n_samples: int, output_dir: str, batch_size: int = 64,
                       device: torch.device = torch.device("cuda"), seed: Optional[int] = None, prefix: str = "signature",
                       oversampling_ratio: float = 2.0, threshold: Optional[int] = None, transparent: bool = False,
-                      noise_scale: float = 1.0) -> None:
+                      noise_scale: float = 1.0, despeckle: Optional[Despeckle] = None) -> None:
     """The best ``n_samples`` of int(n_samples * oversampling_ratio) generated signatures by the Discriminator's score, written
     in rank order under the usual names, plus ``<prefix>_scores.json``: [{file, score}, ...] in the same order."""
     os.makedirs(output_dir, exist_ok=True)
@@ -63,7 +91,7 @@ def generate_filtered(generator, discriminator, n_samples: int, output_dir: str,
     print(f"Generating {int(n_samples * oversampling_ratio)} signatures, keeping the {n_samples} most realistic...")
     images, scores = generate_signatures_filtered(generator, discriminator, n_samples, generator.latent_dim, device, seed=seed,
                                                   batch_size=batch_size, oversampling_ratio=oversampling_ratio,
-                                                  noise_scale=noise_scale, threshold=threshold)
+                                                  noise_scale=noise_scale, threshold=threshold, **with_despeckle(despeckle))
     if threshold is not None:
         images = process_images(images, threshold=threshold, make_transparent=transparent)
     print(f"Saving {len(images)} images...")
@@ -73,7 +101,9 @@ def generate_filtered(generator, discriminator, n_samples: int, output_dir: str,
         img.save(os.path.join(output_dir, name), "PNG")
         records.append({"file": name, "score": score})
     with open(os.path.join(output_dir, f"{prefix}_scores.json"), "w") as f:
-        json.dump(records, f, indent=2)
+        json.dump(records_json(records, despeckle), f, indent=2)
+    if despeckle is not None:
+        print_despeckle(despeckle)
     print("\nGeneration complete!")
     print(f"Generated {len(images)} signatures saved to: {output_dir}")
     if scores:
@@ -83,7 +113,7 @@ def generate_filtered(generator, discriminator, n_samples: int, output_dir: str,
 def generate_refined(generator, discriminator, n_samples: int, output_dir: str, batch_size: int = 64,
                      device: torch.device = torch.device("cuda"), seed: Optional[int] = None, prefix: str = "signature",
                      steps: int = 20, lr: float = 0.02, prior_weight: float = 0.0, threshold: Optional[int] = None,
-                     transparent: bool = False, noise_scale: float = 1.0) -> None:
+                     transparent: bool = False, noise_scale: float = 1.0, despeckle: Optional[Despeckle] = None) -> None:
     """``n_samples`` generated signatures whose latent vectors were refined by the Discriminator's score, written in generation
     order under the usual names, plus ``<prefix>_refine.json``: [{file, before, after}, ...] in the same order."""
     os.makedirs(output_dir, exist_ok=True)
@@ -91,7 +121,7 @@ def generate_refined(generator, discriminator, n_samples: int, output_dir: str, 
     print(f"Generating {n_samples} signatures, refining each for {steps} steps by the Discriminator's score...")
     images, after, before = generate_signatures_refined(generator, discriminator, n_samples, generator.latent_dim, device, seed=seed,
                                                         batch_size=batch_size, noise_scale=noise_scale, steps=steps, lr=lr,
-                                                        prior_weight=prior_weight, threshold=threshold)
+                                                        prior_weight=prior_weight, threshold=threshold, **with_despeckle(despeckle))
     if threshold is not None:
         images = process_images(images, threshold=threshold, make_transparent=transparent)
     print(f"Saving {len(images)} images...")
@@ -101,7 +131,9 @@ def generate_refined(generator, discriminator, n_samples: int, output_dir: str, 
         img.save(os.path.join(output_dir, name), "PNG")
         records.append({"file": name, "before": b, "after": a})
     with open(os.path.join(output_dir, f"{prefix}_refine.json"), "w") as f:
-        json.dump(records, f, indent=2)
+        json.dump(records_json(records, despeckle), f, indent=2)
+    if despeckle is not None:
+        print_despeckle(despeckle)
     print("\nGeneration complete!")
     print(f"Generated {len(images)} signatures saved to: {output_dir}")
     if after:
@@ -204,7 +236,7 @@ def run_adapt(generator, path: str, output_dir: str, device: torch.device, n_sam
               steps: int = 100, lr: float = 1e-4, first_layer: int = 0, anchor_weight: float = 0.0, discriminator=None,
               realism_weight: float = 0.0, sigma: float = 0.25, save: Optional[str] = None, seed: Optional[int] = None,
               project_steps: int = 200, project_lr: float = 0.05, project_restarts: int = 1, threshold: Optional[int] = None,
-              transparent: bool = False, config: Optional[Dict[str, Any]] = None) -> None:
+              transparent: bool = False, config: Optional[Dict[str, Any]] = None, despeckle: Optional[Despeckle] = None) -> None:
     """Adapt the Generator to the image file / the images of the directory ``path`` (utils.inference.adapt_generator: project
     them to pivots, then Adam on the weights of layers >= ``first_layer``), then write ``n_samples`` signatures
     ``<prefix>_%06d.png`` generated at z = pivot[i mod N] + sigma * randn (seeded by ``seed``) and ``<prefix>_adapt.json``:
@@ -226,7 +258,8 @@ def run_adapt(generator, path: str, output_dir: str, device: torch.device, n_sam
     for i0 in range(0, n_samples, mb):
         idx = torch.arange(i0, min(i0 + mb, n_samples)) % n
         noise = torch.randn(len(idx), generator.latent_dim, generator=gen).to(device)
-        images += [Image.fromarray(arr, mode="L") for arr in generate_uint8(generator, (pivots[idx.to(device)] + sigma * noise).contiguous())]
+        images += [Image.fromarray(arr, mode="L") for arr in generate_uint8(generator, (pivots[idx.to(device)] + sigma * noise).contiguous(),
+                                                                              **with_despeckle(despeckle))]
     if threshold is not None:
         images = process_images(images, threshold=threshold, make_transparent=transparent)
     for i, img in enumerate(images):
@@ -234,6 +267,9 @@ def run_adapt(generator, path: str, output_dir: str, device: torch.device, n_sam
     report = {"steps": steps, "lr": lr, "first_layer": first_layer, "anchor_weight": anchor_weight, "realism_weight": realism_weight,
               "sigma": sigma, "trainable": res["trainable"],
               "targets": [{"file": f, "loss_before": float(before[i]), "loss_after": float(after[i])} for i, f in enumerate(files)]}
+    if despeckle is not None:
+        report["despeckle"] = despeckle.report()
+        print_despeckle(despeckle)
     with open(os.path.join(output_dir, f"{prefix}_adapt.json"), "w") as f:
         json.dump(report, f, indent=2)
     if save:
@@ -275,6 +311,18 @@ ADAPT_DEFAULTS = dict(adapt=None, adapt_steps=100, adapt_lr=1e-4, adapt_first_la
 # the identity flags of a projection, kept out of the namespace the same way
 IDENTITY_DEFAULTS = dict(verifier_checkpoint=None, project_identity_weight=0.0, project_identity_score_weight=0.0,
                          project_identity_resize=False)
+
+
+# --despeckle, kept out of the namespace the same way: absent = off, "auto" = components.default_min_area, else MIN_AREA
+DESPECKLE_DEFAULTS = dict(despeckle=None)
+
+
+def despeckle_opt(a: argparse.Namespace) -> Optional[Despeckle]:
+    """The Despeckle of a command line with --despeckle (its ink threshold is --threshold, 128 without it), else None."""
+    v = getattr(a, "despeckle", DESPECKLE_DEFAULTS["despeckle"])
+    if v is None:
+        return None
+    return Despeckle(None if v == "auto" else v, 128 if a.threshold is None else a.threshold)
 
 
 def identity_opt(a: argparse.Namespace, name: str):
@@ -350,7 +398,18 @@ def parse_args(argv=None) -> argparse.Namespace:
     p.add_argument("--adapt_sigma", type=float, **later,
                    help="Signatures are generated at z = pivot[i mod N] + SIGMA * randn (default: 0.25 * noise_scale)")
     p.add_argument("--adapt_save", type=str, metavar="CKPT", **later, help="Also save the adapted Generator as a checkpoint")
+    p.add_argument("--despeckle", nargs="?", type=lambda v: v if v == "auto" else int(v), const="auto", metavar="MIN_AREA", **later,
+                   help="Remove ink components of fewer than MIN_AREA pixels from every generated signature before it is scored and "
+                        "written (MIN_AREA omitted: max(2, round(0.001 * H * W))); ink is byte < --threshold, 128 without it "
+                        "(default: off)")
     a = p.parse_args(argv)
+    if hasattr(a, "despeckle"):
+        if a.project is not None or a.morph is not None:
+            p.error("--despeckle cleans generated signatures; projections and morph strips are left alone")
+        if a.despeckle != "auto" and a.despeckle < 1:
+            p.error("--despeckle MIN_AREA must be >= 1")
+        if a.threshold is not None and not 1 <= a.threshold <= 255:
+            p.error("--despeckle needs --threshold in 1..255")
     if adapt_opt(a, "adapt") is not None:
         for flag in ("filter_by_realism", "project", "morph"):
             if getattr(a, flag) not in (None, False):
@@ -431,7 +490,7 @@ def main(argv=None) -> None:
                   adapt_opt(a, "adapt_lr"), adapt_opt(a, "adapt_first_layer"), adapt_opt(a, "adapt_anchor"),
                   need_discriminator("--adapt_realism_weight") if w_d > 0 else None, w_d,
                   0.25 * a.noise_scale if sigma is None else sigma, adapt_opt(a, "adapt_save"), a.seed, a.project_steps,
-                  a.project_lr, a.project_restarts, a.threshold, a.transparent, config)
+                  a.project_lr, a.project_restarts, a.threshold, a.transparent, config, **with_despeckle(despeckle_opt(a)))
         return
     if a.project is not None or a.morph is not None:
         if a.project is not None:
@@ -451,14 +510,14 @@ def main(argv=None) -> None:
     if opt(a, "refine_by_realism"):
         generate_refined(generator, need_discriminator("--refine_by_realism"), a.n_samples, a.output_dir, a.batch_size, device, a.seed,
                          a.prefix, opt(a, "refine_steps"), opt(a, "refine_lr"), opt(a, "refine_prior"), a.threshold, a.transparent,
-                         a.noise_scale)
+                         a.noise_scale, **with_despeckle(despeckle_opt(a)))
     elif a.filter_by_realism:
         discriminator = need_discriminator("--filter_by_realism")
         generate_filtered(generator, discriminator, a.n_samples, a.output_dir, a.batch_size, device, a.seed, a.prefix,
-                          a.oversampling_ratio, a.threshold, a.transparent, a.noise_scale)
+                          a.oversampling_ratio, a.threshold, a.transparent, a.noise_scale, **with_despeckle(despeckle_opt(a)))
     else:
         generate_signatures(generator, a.n_samples, a.output_dir, a.batch_size, device, a.seed, a.prefix, a.noise_scale,
-                            a.threshold, a.transparent)
+                            a.threshold, a.transparent, **with_despeckle(despeckle_opt(a)))
     print("\n" + "=" * 50 + "\nGeneration Summary:")
     print(f"  Checkpoint: {a.checkpoint}\n  Samples generated: {a.n_samples}\n  Output directory: {a.output_dir}")
     print(f"  Seed: {a.seed if a.seed is not None else 'Random'}\n  Device: {device}\n" + "=" * 50)

@@ -92,13 +92,63 @@ def _to_host_u8(u8: torch.Tensor) -> np.ndarray:
     return buf[:n].numpy().reshape(tuple(u8.shape)).copy()       # (the buffer is reused by the next call)
 
 
-def generate_uint8(generator: Generator, z: torch.Tensor) -> np.ndarray:
+class Despeckle:
+    """The settings of ``generate_signatures --despeckle`` and what the cleaning has removed so far: every ink component
+    (byte < ``threshold``, ``connectivity``-connected) of fewer than ``min_area`` pixels becomes white (255), every other byte
+    stays what it is (components.despeckle_u8, on the device).  ``min_area`` None: components.default_min_area of the first
+    images cleaned.  ``clean_device`` / ``clean_host`` return the (N, 9) component counters of the images BEFORE cleaning;
+    ``count`` adds the removed components and pixels of such rows to the totals ``report`` hands out."""
+
+    def __init__(self, min_area: Optional[int] = None, threshold: int = 128, connectivity: int = 8) -> None:
+        if not 1 <= int(threshold) <= 255:
+            raise ValueError(f"despeckle needs an ink threshold in 1..255, got {threshold}")
+        if min_area is not None and int(min_area) < 1:
+            raise ValueError(f"min_area = {min_area} < 1")
+        self.min_area, self.threshold, self.connectivity = min_area, int(threshold), int(connectivity)
+        self.removed_components = self.removed_pixels = 0
+
+    def clean_device(self, u8: torch.Tensor) -> torch.Tensor:
+        """Clean the contiguous uint8 (N, H, W) device tensor IN PLACE -> int32 (N, 9) device counters of its former content."""
+        from ..components import default_min_area, despeckle_u8
+        if self.min_area is None:
+            self.min_area = default_min_area(u8.shape[-2], u8.shape[-1])
+        stats = torch.empty(u8.shape[0], 9, dtype=torch.int32, device=u8.device)
+        despeckle_u8(u8, self.threshold, self.connectivity, self.min_area, 255, out=u8, stats=stats)
+        return stats
+
+    def clean_host(self, u8: np.ndarray, device: torch.device) -> Tuple[np.ndarray, np.ndarray]:
+        """(N, H, W) uint8 on the host -> (cleaned copy, (N, 9) counters), through the device."""
+        t = torch.from_numpy(np.ascontiguousarray(u8)).to(device)
+        stats = self.clean_device(t)
+        return _to_host_u8(t), stats.cpu().numpy()
+
+    def count(self, stats) -> None:
+        from ..components import SMALL_COMPONENTS, SMALL_INK
+        rows = stats.cpu().numpy() if isinstance(stats, torch.Tensor) else np.asarray(stats)
+        rows = rows.reshape(-1, 9).astype(np.int64)
+        self.removed_components += int(rows[:, SMALL_COMPONENTS].sum())
+        self.removed_pixels += int(rows[:, SMALL_INK].sum())
+
+    def report(self) -> Dict[str, int]:
+        return {"min_area": self.min_area, "threshold": self.threshold, "connectivity": self.connectivity,
+                "removed_components": self.removed_components, "removed_pixels": self.removed_pixels}
+
+
+def generate_uint8(generator: Generator, z: torch.Tensor, despeckle: Optional[Despeckle] = None) -> np.ndarray:
     """z (B, latent) -> (B, H, W) uint8, the bytes of ``tensor_to_uint8(generator(z))``.  In eval mode the Generator's last
     kernel writes them itself (Engine.g_generate_u8) and one byte per pixel crosses to the host; a Generator left in train()
-    mode (BatchNorm batch statistics) has no such kernel and takes the fp32 route."""
+    mode (BatchNorm batch statistics) has no such kernel and takes the fp32 route.  ``despeckle``: the bytes are cleaned
+    (and what was removed is counted) before they are returned -- on the device, before the copy, in eval mode."""
     if generator.training:
-        return tensor_to_uint8(generator(z))
-    return _to_host_u8(generator._require_engine().g_generate_u8(z))
+        u8 = tensor_to_uint8(generator(z))
+        if despeckle is not None:
+            u8, stats = despeckle.clean_host(u8, z.device)
+            despeckle.count(stats)
+        return u8
+    u8 = generator._require_engine().g_generate_u8(z)
+    if despeckle is not None:
+        despeckle.count(despeckle.clean_device(u8))
+    return _to_host_u8(u8)
 
 
 def tensor_to_pil_image(tensor: torch.Tensor):
@@ -108,9 +158,10 @@ def tensor_to_pil_image(tensor: torch.Tensor):
 
 def generate_signatures_batch(generator: Generator, n_samples: int, latent_dim: int, device: torch.device,
                               seed: Optional[int] = None, batch_size: int = 32, progress_callback=None,
-                              noise_scale: float = 1.0) -> List[Any]:
+                              noise_scale: float = 1.0, despeckle: Optional[Despeckle] = None) -> List[Any]:
     """Reference semantics (utils/inference.py:136-194): optional torch.manual_seed, then per batch
-    z = randn(b, latent, device=device) * noise_scale -> generator(z) -> one PIL image per sample."""
+    z = randn(b, latent, device=device) * noise_scale -> generator(z) -> one PIL image per sample.  ``despeckle``: every
+    batch's bytes are cleaned on the way (generate_uint8)."""
     from PIL import Image
     if seed is not None:
         torch.manual_seed(seed)
@@ -122,7 +173,7 @@ def generate_signatures_batch(generator: Generator, n_samples: int, latent_dim: 
     while done < n_samples:
         b = min(batch_size, n_samples - done)
         z = torch.randn(b, latent_dim, device=device) * noise_scale
-        for arr in generate_uint8(generator, z):
+        for arr in generate_uint8(generator, z, despeckle):
             out.append(Image.fromarray(arr, mode="L"))
         done += b
         if progress_callback is not None:
@@ -206,7 +257,8 @@ def dequantize_uint8(u8: np.ndarray) -> torch.Tensor:
 def generate_signatures_filtered(generator: Generator, discriminator: Discriminator, n_signatures: int, latent_dim: int,
                                  device: torch.device, seed: Optional[int] = None, batch_size: int = 32,
                                  oversampling_ratio: float = 2.0, noise_scale: float = 1.0, threshold: Optional[int] = None,
-                                 route: str = "device", progress_callback=None) -> Tuple[List[Any], List[float]]:
+                                 route: str = "device", progress_callback=None, despeckle: Optional[Despeckle] = None
+                                 ) -> Tuple[List[Any], List[float]]:
     """The reference app's "Filter by Realism": generate int(n * ratio) signatures batch by batch (filter_plan), binarise them
     when ``threshold`` is given, score each with the Discriminator on byte / 127.5 - 1.0, and return the best min(n, total)
     as (PIL 'L' images, scores), highest score first, equal scores in generation order.
@@ -216,7 +268,10 @@ def generate_signatures_filtered(generator: Generator, discriminator: Discrimina
     gather_u8 run, and only the selected images and scores cross to the host.  route="host": the reference's loop on the
     existing pieces -- bytes to the host, numpy binarisation, CPU dequantisation, Discriminator.forward, Python's sort.  Both
     give identical images and scores.  The device route falls back to the host route where it does not apply: a Generator or
-    Discriminator in train() mode, or more than _lib.SELECT_MAX images."""
+    Discriminator in train() mode, or more than _lib.SELECT_MAX images.
+
+    ``despeckle``: every batch is cleaned IN PLACE in the pool before it is scored (and before ``threshold`` binarises it on
+    load), so a returned score belongs to the image that is returned; what was removed from the RETURNED images is counted."""
     from PIL import Image
     from .. import _lib
     if route not in ("device", "host"):
@@ -243,14 +298,20 @@ def generate_signatures_filtered(generator: Generator, discriminator: Discrimina
             _seed_batch(batch_seed)
             z = torch.randn(b, latent_dim, device=device) * noise_scale
             u8 = generate_uint8(generator, z)
+            removed = np.zeros((b, 9), np.int32)
+            if despeckle is not None:
+                u8, removed = despeckle.clean_host(u8, device)
             if threshold is not None:
                 u8 = binarize_uint8(u8, threshold)
             with torch.no_grad():
                 scores = discriminator(dequantize_uint8(u8).to(device)).cpu().numpy().flatten().tolist()
-            records += [(arr, float(sc)) for arr, sc in zip(u8, scores)]
+            records += [(arr, float(sc), row) for arr, sc, row in zip(u8, scores, removed)]
             tick(b)
         records.sort(key=lambda r: r[1], reverse=True)
         records = records[:keep]
+        if despeckle is not None:
+            despeckle.count(np.stack([row for _, _, row in records]))
+        records = [(arr, sc) for arr, sc, _ in records]
         return [Image.fromarray(arr, mode="L") for arr, _ in records], [sc for _, sc in records]
 
     g_eng, d_eng = generator._require_engine(), discriminator._require_engine()
@@ -258,13 +319,18 @@ def generate_signatures_filtered(generator: Generator, discriminator: Discrimina
     pool = torch.empty(total, size, size, dtype=torch.uint8, device=g_eng.device)
     scores = torch.empty(total, dtype=torch.float32, device=g_eng.device)
     binarize = None if threshold is None else int(threshold)
+    removed = torch.empty(total, 9, dtype=torch.int32, device=g_eng.device) if despeckle is not None else None
     for b, batch_seed in plan:
         _seed_batch(batch_seed)
         z = torch.randn(b, latent_dim, device=device) * noise_scale
         g_eng.g_generate_u8(z, out=pool[done:done + b])
+        if despeckle is not None:
+            removed[done:done + b] = despeckle.clean_device(pool[done:done + b])
         d_eng.d_score_u8(pool[done:done + b], binarize=binarize, out=scores[done:done + b])
         tick(b)
     index = g_eng.select_topk(scores, keep)
+    if despeckle is not None:
+        despeckle.count(removed[index.long()])
     picked = _to_host_u8(g_eng.gather_u8(pool, index, binarize=binarize))
     best = _to_host_u8(scores[index.long()].view(torch.uint8)).view(np.float32)
     return [Image.fromarray(arr, mode="L") for arr in picked], [float(sc) for sc in best]
@@ -382,7 +448,7 @@ def _descend(eng, z, steps, lr, betas, grad, final_out=None):
     return hist
 
 
-def _refine(eng, generator, z0, steps, lr, betas, realism_weight, prior_weight):
+def _refine(eng, generator, z0, steps, lr, betas, realism_weight, prior_weight, despeckle=None):
     dev, latent = eng.device, eng.latent_dim
     z0 = torch.as_tensor(z0, dtype=torch.float32)
     if z0.dim() != 2 or z0.shape[1] != latent:
@@ -405,7 +471,7 @@ def _refine(eng, generator, z0, steps, lr, betas, realism_weight, prior_weight):
     size = eng.image_size
     u8 = np.empty((n, size, size), dtype=np.uint8)
     for t0, b in refine_plan(n, eng.max_batch):
-        u8[t0:t0 + b] = generate_uint8(generator, z_all[t0:t0 + b])
+        u8[t0:t0 + b] = generate_uint8(generator, z_all[t0:t0 + b], despeckle)
     return z_all, u8, before, after, hist
 
 
@@ -427,12 +493,13 @@ def refine_latents(generator: Generator, discriminator: Discriminator, z0: torch
 
 def generate_signatures_refined(generator: Generator, discriminator: Discriminator, n_signatures: int, latent_dim: int,
                                 device: torch.device, seed: Optional[int] = None, batch_size: int = 32, noise_scale: float = 1.0,
-                                steps: int = 20, lr: float = 0.02, prior_weight: float = 0.0, threshold: Optional[int] = None
-                                ) -> Tuple[List[Any], List[float], List[float]]:
+                                steps: int = 20, lr: float = 0.02, prior_weight: float = 0.0, threshold: Optional[int] = None,
+                                despeckle: Optional[Despeckle] = None) -> Tuple[List[Any], List[float], List[float]]:
     """Generation with every latent vector refined by the Discriminator's score instead of oversampling and discarding:
     batch by batch (filter_plan with ratio 1.0: the same batches and seeds as generate_signatures_filtered draws first),
     z = randn * noise_scale, then refine_latents' loop.  Returns (PIL 'L' images in generation order -- binarised when
-    ``threshold`` is given --, probs_after, probs_before): the scores D(G(z)) of the fp32 images after and before."""
+    ``threshold`` is given --, probs_after, probs_before): the scores D(G(z)) of the fp32 images after and before.
+    ``despeckle``: the final bytes are cleaned before they are returned (the scores stay those of the fp32 images)."""
     from PIL import Image
     _check_refine(steps, lr, 1.0, prior_weight)
     if threshold is not None and not 0 <= int(threshold) <= 255:
@@ -445,7 +512,7 @@ def generate_signatures_refined(generator: Generator, discriminator: Discriminat
     for b, batch_seed in plan:
         _seed_batch(batch_seed)
         z = torch.randn(b, latent_dim, device=device) * noise_scale
-        _, u8, p0, p1, _ = _refine(eng, generator, z, steps, lr, (0.9, 0.999), 1.0, prior_weight)
+        _, u8, p0, p1, _ = _refine(eng, generator, z, steps, lr, (0.9, 0.999), 1.0, prior_weight, despeckle)
         if threshold is not None:
             u8 = binarize_uint8(u8, threshold)
         images += [Image.fromarray(arr, mode="L") for arr in u8]

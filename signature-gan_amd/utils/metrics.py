@@ -180,6 +180,51 @@ def calculate_foreground_ratio(images: torch.Tensor, threshold: float = 0.5) -> 
     return _foreground_dict(_densities(images, threshold))
 
 
+# ---- fragmentation: connected ink components (components.py) ------------------------------------------------------------
+def fragmentation_from_counters(counters) -> Dict[str, Any]:
+    """The fragmentation dictionary from (N, 9) component counters (components.STAT_NAMES), pure numpy on integers:
+    components_mean / components_median: ink components per image; small_components_mean: those below min_area;
+    speckle_ink_ratio: sum of small_ink over sum of ink (0.0 without any ink); largest_component_share_mean: the mean of
+    largest / ink over the images that have ink (None when none has); empty_images: images without ink; n."""
+    from ..components import COMPONENTS, INK, LARGEST, SMALL_COMPONENTS, SMALL_INK
+    c = np.asarray(counters, dtype=np.int64).reshape(-1, 9)
+    if c.shape[0] == 0:
+        raise ValueError("no images")
+    if (c[:, COMPONENTS] < 0).any():
+        raise RuntimeError("siggan_components_u8 hit its safety bound (COMPONENTS = -1): a bug in the kernel, not an input")
+    ink = c[:, INK]
+    has = ink > 0
+    total = int(ink.sum())
+    return {"components_mean": float(np.mean(c[:, COMPONENTS])), "components_median": float(np.median(c[:, COMPONENTS])),
+            "small_components_mean": float(np.mean(c[:, SMALL_COMPONENTS])),
+            "speckle_ink_ratio": float(int(c[:, SMALL_INK].sum()) / total) if total else 0.0,
+            "largest_component_share_mean": float(np.mean(c[has, LARGEST] / ink[has])) if has.any() else None,
+            "empty_images": int((~has).sum()), "n": int(c.shape[0])}
+
+
+def quantize_generated(images: torch.Tensor) -> torch.Tensor:
+    """fp32 in [-1, 1] -> uint8 by the generation rule ((x + 1) * 127.5, clip to 0..255, truncate), where the tensor lives."""
+    return ((images.detach().to(torch.float32) + 1) * 127.5).clamp(0, 255).to(torch.uint8)
+
+
+def calculate_fragmentation(images: torch.Tensor, threshold: int = 128, connectivity: int = 8,
+                            min_area: Optional[int] = None) -> Dict[str, Any]:
+    """How broken up the ink of ``images`` is: uint8 (B, S, S) / (B, 1, S, S), or fp32 in [-1, 1] quantised by the generation
+    rule first.  Ink is byte < ``threshold``; ``min_area`` None: components.default_min_area.  The components are labelled on
+    the device (components.component_stats) and only the (B, 9) counters reach the host; a structural metric that needs
+    no network weights.  Returns fragmentation_from_counters' dictionary."""
+    from ..components import component_stats
+    if not isinstance(images, torch.Tensor):
+        raise ValueError(f"images must be a tensor, got {type(images).__name__}")
+    if images.device.type != "cuda":
+        if not torch.cuda.is_available():
+            raise RuntimeError("the components are labelled on a ROCm device ('cuda:N'); there is no CPU path")
+        images = images.cuda()
+    if images.dtype != torch.uint8:
+        images = quantize_generated(images)
+    return fragmentation_from_counters(component_stats(images.contiguous(), threshold, connectivity, min_area).cpu().numpy())
+
+
 class MetricsTracker:
     """Per-epoch running values and the history of their epoch averages (utils/metrics.py:177-213)."""
 
