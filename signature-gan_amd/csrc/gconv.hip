@@ -15,31 +15,28 @@
 // VALU have a large budget and the kernels are MFMA-bound once the grid fills the chip.
 // Global->LDS staging is register-staged and software-pipelined one K-tile ahead (loads for tile
 // t+1 are issued before the MFMAs of tile t, written to the other LDS buffer after them).
-#include "gconv.h"
+//
+// Shared with the 16-bit kernels (gconv16.hip) and kept in gconv_parts.h: the XCD remap, the block setup (GconvBlock),
+// the per-row staging coordinates and tap cursor (GconvRows), the KQ = 2 accumulator hand-over (kq_handover), the fused
+// epilogues and their statistics reduction (epi_load / epi_apply / epi_stats_reduce, also k_splitk_epilogue's) and the
+// weight-gradient tail (wgrad_tail).  This file keeps the fp32 operand path -- LDS layouts, staging, fragment reads,
+// MFMA -- and the one-pass move of the accumulator tile through LDS.
+#include "gconv_parts.h"
+#include "host.h"
 #include <hip/hip_ext.h>
 
 namespace siggan {
 
-
-static constexpr int BK = 32;    // K-tile (floats)
 static constexpr int PAD = 4;    // LDS row padding (floats)
-
-// XCD-aware bijective remap (8 XCDs, blocks b and b+8 share an L2): consecutive logical tiles,
-// which share an A row-panel, land on one XCD.
-__device__ __forceinline__ int xcd_remap(int bid, int nwg) {
-    const int q = nwg >> 3, r = nwg & 7, xcd = bid & 7, idx = bid >> 3;
-    return (xcd < r ? xcd * (q + 1) : r * (q + 1) + (xcd - r) * q) + idx;
-}
 
 // KQ = 2: two wave quads per workgroup, each running the whole pipeline on its own half of the workgroup's K range and its
 // own LDS buffers; the second quad's accumulators are added to the first's through LDS before the epilogue.  This is a
 // two-way K split WITHOUT slabs or a second kernel (sum order quad 0 + quad 1 = slab 0 + slab 1 of the split-K protocol:
 // bit-identical); used for the launches that would otherwise be split in two.
-template <int BM, int BN, int WM, int WN, int BK = 32, int DEEP = 0, int KQ = 1, bool LK = false>   // LK: g_act's variant
+template <int BM, int BN, int WM, int WN, int KQ = 1, bool LK = false>   // LK: g_act's variant
 __global__ __launch_bounds__(256 * KQ) void k_gconv(const GConvArgs a) {
     constexpr int TM = BM / (32 * WM), TN = BN / (32 * WN);
     constexpr int PA = BM / 32, PB = BN / 32;
-    constexpr int KC = BK / 32;        // 16-byte chunks a thread stages per row and K-tile
     // LDS tiles are [row][k] with a row stride of 36 floats (= 4 * odd): a staged float4 is ONE
     // ds_write_b128 (8 lanes cover a row's 128 B), and a lane's MFMA operands for 4 consecutive
     // sub-steps are ONE conflict-free ds_read_b128 (the 16 lanes of a b128 group hit 16 distinct
@@ -47,95 +44,43 @@ __global__ __launch_bounds__(256 * KQ) void k_gconv(const GConvArgs a) {
     // k = 8c + 4*(lane>>5) + t, identical for A and B, so only the fp32 summation order changes.
     constexpr int LD = BK + 4;
     __shared__ __attribute__((aligned(16))) float smem[KQ * 2 * LD * (BM + BN)];
-    const int quad = KQ > 1 ? (int)(threadIdx.x >> 8) : 0;
-    float* const sA = smem + quad * (2 * LD * (BM + BN));
+    const GconvBlock<BM, BN, KQ> b(a);
+    const int nk = b.nk;
+    float* const sA = smem + b.quad * (2 * LD * (BM + BN));
     float* const sB = sA + 2 * LD * BM;
 
-    const int tid = threadIdx.x & 255, lane = tid & 63, wave = tid >> 6;      // thread / wave index inside the quad
+    const int lane = b.tid & 63, wave = b.tid >> 6;      // wave index inside the quad
     const int li = lane & 31, lh = lane >> 5;
     const int wm = wave / WN, wn = wave % WN;
-    const float* const a_in = static_cast<const float*>(a.in);
     const float* const a_wp = static_cast<const float*>(a.wp);
 
-    const int tiles_n = a.Co / BN;
-    const int bid = xcd_remap(blockIdx.x, gridDim.x);
-    const int m0 = (bid / tiles_n) * BM, n0 = (bid % tiles_n) * BN;
-    const int cls = blockIdx.z, ph = cls >> 1, pw = cls & 1;
-    const int Hr = 1 << a.lgHr, Wr = 1 << a.lgWr;
-    const int ntaps = a.form == 0 ? 16 : 4;
-    const int Ktot = ntaps * a.Ci;
-    const int lgcpt = 31 - __builtin_clz(a.Ci / BK);      // K-tiles per tap = Ci / 32, a power of two
-    const int nk_all = ntaps << lgcpt;
-    // split-K: this block (this quad of it) owns K-tiles [k_lo, k_hi); with KQ = 2 the launcher guarantees equal halves,
-    // so both quads pass the same number of barriers
-    const int kper = (nk_all + gridDim.y * KQ - 1) / (gridDim.y * KQ);
-    const int k_lo = (blockIdx.y * KQ + quad) * kper;
-    const int k_hi = min(nk_all, k_lo + kper);
-    const int nk = k_hi - k_lo;
-
     // ---- per-thread staging coordinates: row rloc + 32p, 16-byte chunk kc of the 32-float k-row ------
-    const int kc = tid & 7, rloc = tid >> 3;
-    const float* a_base[PA];     // &in[n, 0, 0, kc*4] of the row's image
-    int a_ih0[PA], a_iw0[PA];
+    const int kc = b.tid & 7, rloc = b.tid >> 3;
+    GconvRows<float, PA> rows;
 #pragma unroll
-    for (int p = 0; p < PA; ++p) {
-        const int m = m0 + rloc + 32 * p;
-        if (m < a.M) {
-            const int n = m >> (a.lgHr + a.lgWr);
-            const int rh = (m >> a.lgWr) & (Hr - 1), rw = m & (Wr - 1);
-            a_base[p] = a_in + (size_t)n * a.Hi * a.Wi * a.Ci + kc * 4;
-            if (a.form == 0) { a_ih0[p] = 2 * rh - 1; a_iw0[p] = 2 * rw - 1; }
-            else             { a_ih0[p] = rh + ph;    a_iw0[p] = rw + pw; }
-        } else {
-            a_base[p] = a_in; a_ih0[p] = -(1 << 20); a_iw0[p] = -(1 << 20);
-        }
-    }
-    const float* wcur = a_wp + ((size_t)cls * a.Co + n0 + rloc) * Ktot + kc * 4 + (size_t)k_lo * BK;
-
-    // load cursor: walks (tap, channel chunk) in K order; per-row source pointers are rebuilt only
-    // when the tap changes, otherwise they advance by 32 floats (0 for out-of-image taps, which
-    // read a 16-byte page of zeros so that the loads stay unconditional)
-    const float* a_cur[PA];
-    int a_step[PA];
-    int l_tap = k_lo >> lgcpt, l_cc = k_lo & ((1 << lgcpt) - 1);
-    auto set_tap = [&]() __attribute__((always_inline)) {
-        int dh, dw;
-        if (a.form == 0) { dh = l_tap >> 2; dw = l_tap & 3; } else { dh = -(l_tap >> 1); dw = -(l_tap & 1); }
+    for (int p = 0; p < PA; ++p) gconv_row(a, b, rows, p, b.m0 + rloc + 32 * p, kc * 4);
+    const float* wcur = a_wp + ((size_t)b.cls * a.Co + b.n0 + rloc) * b.Ktot + kc * 4 + (size_t)b.k_lo * BK;
+    int l_tap = b.k_lo >> b.lgcpt, l_cc = b.k_lo & ((1 << b.lgcpt) - 1);
+    auto set_tap = [&]() __attribute__((always_inline)) { gconv_set_tap(a, rows, l_tap, l_cc); };
+    f32x4 ra[2][PA], rb[2][PB];          // two register sets: tile t waits in set t & 1 (the short path uses set 0 alone)
+    auto load_tile = [&](int set) __attribute__((always_inline)) {
 #pragma unroll
         for (int p = 0; p < PA; ++p) {
-            const int ih = a_ih0[p] + dh, iw = a_iw0[p] + dw;
-            const bool ok = (unsigned)ih < (unsigned)a.Hi && (unsigned)iw < (unsigned)a.Wi;
-            a_cur[p] = ok ? a_base[p] + ((size_t)(ih * a.Wi + iw) * a.Ci + l_cc * BK) : a.zeros;
-            a_step[p] = ok ? BK : 0;
-        }
-    };
-    constexpr int NSET = DEEP ? 2 : 1;      // register sets: tile t waits in set t % NSET
-    f32x4 ra[NSET][PA][KC], rb[NSET][PB][KC];
-    auto load_tile = [&](int set = 0) __attribute__((always_inline)) {
-#pragma unroll
-        for (int p = 0; p < PA; ++p) {
-#pragma unroll
-            for (int q = 0; q < KC; ++q) ra[set][p][q] = *reinterpret_cast<const f32x4*>(a_cur[p] + 32 * q);   // (zero page: 256 B)
-            a_cur[p] += a_step[p];
+            ra[set][p] = *reinterpret_cast<const f32x4*>(rows.cur[p]);      // (zero page: 256 B)
+            rows.cur[p] += rows.step[p];
         }
 #pragma unroll
-        for (int p = 0; p < PB; ++p)
-#pragma unroll
-            for (int q = 0; q < KC; ++q) rb[set][p][q] = *reinterpret_cast<const f32x4*>(wcur + (size_t)(32 * p) * Ktot + 32 * q);
+        for (int p = 0; p < PB; ++p) rb[set][p] = *reinterpret_cast<const f32x4*>(wcur + (size_t)(32 * p) * b.Ktot);
         wcur += BK;
-        if (++l_cc == (1 << lgcpt)) { l_cc = 0; ++l_tap; set_tap(); }
+        if (++l_cc == (1 << b.lgcpt)) { l_cc = 0; ++l_tap; set_tap(); }
     };
-    auto store_tile = [&](int buf, int set = 0) __attribute__((always_inline)) {
+    auto store_tile = [&](int buf, int set) __attribute__((always_inline)) {
         float* dA = sA + buf * LD * BM + rloc * LD + kc * 4;
         float* dB = sB + buf * LD * BN + rloc * LD + kc * 4;
 #pragma unroll
-        for (int p = 0; p < PA; ++p)
+        for (int p = 0; p < PA; ++p) *reinterpret_cast<f32x4*>(dA + 32 * p * LD) = ra[set][p];
 #pragma unroll
-            for (int q = 0; q < KC; ++q) *reinterpret_cast<f32x4*>(dA + 32 * p * LD + 32 * q) = ra[set][p][q];
-#pragma unroll
-        for (int p = 0; p < PB; ++p)
-#pragma unroll
-            for (int q = 0; q < KC; ++q) *reinterpret_cast<f32x4*>(dB + 32 * p * LD + 32 * q) = rb[set][p][q];
+        for (int p = 0; p < PB; ++p) *reinterpret_cast<f32x4*>(dB + 32 * p * LD) = rb[set][p];
     };
 
     f32x16 acc[TM][TN];
@@ -146,75 +91,11 @@ __global__ __launch_bounds__(256 * KQ) void k_gconv(const GConvArgs a) {
 #pragma unroll
             for (int r = 0; r < 16; ++r) acc[i][j][r] = 0.f;
 
-    // The register set always holds the NEXT tile: it is written to the other LDS buffer right
-    // behind the first MFMAs of a tile and immediately re-loaded with the tile after that, so every
-    // global load has a full K-tile of MFMA time to land (hipcc drains vmcnt to 0 at the LDS write
-    // whatever is newer in flight, so the write sits where nothing newer is).
-    if (DEEP && nk >= 5) {
-        // Two tiles ahead: the loads of tile t are issued while tile t-3 is multiplied and are needed (LDS write) while tile
-        // t-1 is -- two K-tiles of time to land instead of one.  A K-tile of this kernel lasts about as long as a load
-        // that misses L2 takes, so with one tile of slack every tile waited for its slowest load.  Two register sets; the
-        // loop is unrolled by two so that set and buffer indices are compile-time, and the steady part issues its loads
-        // unconditionally: only then can hipcc count the loads in flight and wait for the OLDER set alone (vmcnt(4));
-        // one conditional load anywhere on the path and it drains the queue (vmcnt(0)) at every LDS write.
-        auto tile = [&](const int h, const int kt, const bool st, const bool ld) __attribute__((always_inline)) {
-            const float* pA = sA + h * LD * BM + (wm * (32 * TM) + li) * LD + 4 * lh;
-            const float* pB = sB + h * LD * BN + (wn * (32 * TN) + li) * LD + 4 * lh;
-            f32x4 fa[2][TM], fb[2][TN];
-#pragma unroll
-            for (int i = 0; i < TM; ++i) fa[0][i] = *reinterpret_cast<const f32x4*>(pA + 32 * i * LD);
-#pragma unroll
-            for (int j = 0; j < TN; ++j) fb[0][j] = *reinterpret_cast<const f32x4*>(pB + 32 * j * LD);
-#pragma unroll
-            for (int c = 0; c < BK / 8; ++c) {
-                const int cur = c & 1, nxt = cur ^ 1;
-                if (c + 1 < BK / 8) {
-#pragma unroll
-                    for (int i = 0; i < TM; ++i) fa[nxt][i] = *reinterpret_cast<const f32x4*>(pA + 32 * i * LD + 8 * (c + 1));
-#pragma unroll
-                    for (int j = 0; j < TN; ++j) fb[nxt][j] = *reinterpret_cast<const f32x4*>(pB + 32 * j * LD + 8 * (c + 1));
-                }
-                __builtin_amdgcn_sched_barrier(0);
-#pragma unroll
-                for (int t = 0; t < 4; ++t)
-#pragma unroll
-                    for (int i = 0; i < TM; ++i)
-#pragma unroll
-                        for (int j = 0; j < TN; ++j)
-                            acc[i][j] = __builtin_amdgcn_mfma_f32_32x32x2f32(fa[cur][i][t], fb[cur][j][t], acc[i][j], 0, 0, 0);
-                if (c == 0 && st) store_tile(h ^ 1, h ^ 1);     // tile kt+1 (set (kt+1)&1): loaded two tiles ago
-                if (c == 1 && ld) load_tile(h ^ 1);             // tile kt+3 into the set just written out
-            }
-            __syncthreads();
-        };
-        set_tap();
-        load_tile(0);
-        load_tile(1);
-        store_tile(0, 0);
-        load_tile(0);
-        __syncthreads();
-        int kt = 0;
-        for (; kt + 4 < nk; kt += 2) {           // both halves have a tile kt+3 to load
-            tile(0, kt, true, true);
-            tile(1, kt + 1, true, true);
-        }
-        for (; kt < nk; kt += 2) {               // the last three or four tiles
-            tile(0, kt, kt + 1 < nk, kt + 3 < nk);
-            if (kt + 1 < nk) tile(1, kt + 1, kt + 2 < nk, kt + 4 < nk);
-        }
-    } else {
-    if (nk > 0) {
-        set_tap();
-        load_tile();
-        store_tile(0);
-        if (nk > 1) load_tile();
-    }
-    __syncthreads();
-
-    for (int kt = 0; kt < nk; ++kt) {
-        const int buf = kt & 1;
-        const float* pA = sA + buf * LD * BM + (wm * (32 * TM) + li) * LD + 4 * lh;
-        const float* pB = sB + buf * LD * BN + (wn * (32 * TN) + li) * LD + 4 * lh;
+    // one K-tile out of LDS buffer h; st: the LDS write of the next tile out of register set `sset` rides along behind the
+    // first MFMAs, ld: the loads of a later tile into that set behind the second chunk's
+    auto tile = [&](const int h, const int sset, const bool st, const bool ld) __attribute__((always_inline)) {
+        const float* pA = sA + h * LD * BM + (wm * (32 * TM) + li) * LD + 4 * lh;
+        const float* pB = sB + h * LD * BN + (wn * (32 * TN) + li) * LD + 4 * lh;
         f32x4 fa[2][TM], fb[2][TN];
 #pragma unroll
         for (int i = 0; i < TM; ++i) fa[0][i] = *reinterpret_cast<const f32x4*>(pA + 32 * i * LD);
@@ -237,11 +118,48 @@ __global__ __launch_bounds__(256 * KQ) void k_gconv(const GConvArgs a) {
 #pragma unroll
                     for (int j = 0; j < TN; ++j)
                         acc[i][j] = __builtin_amdgcn_mfma_f32_32x32x2f32(fa[cur][i][t], fb[cur][j][t], acc[i][j], 0, 0, 0);
-            if (c == 0 && kt + 1 < nk) store_tile(buf ^ 1);     // tile kt+1: loaded a tile ago
-            if (c == 1 && kt + 2 < nk) load_tile();             // tile kt+2: lands during this tile
+            if (c == 0 && st) store_tile(h ^ 1, sset);
+            if (c == 1 && ld) load_tile(sset);
         }
         __syncthreads();
-    }
+    };
+    // The register set always holds the NEXT tile: it is written to the other LDS buffer right
+    // behind the first MFMAs of a tile and immediately re-loaded with the tile after that, so every
+    // global load has a full K-tile of MFMA time to land (hipcc drains vmcnt to 0 at the LDS write
+    // whatever is newer in flight, so the write sits where nothing newer is).
+    if (nk >= 5) {
+        // Two tiles ahead: the loads of tile t are issued while tile t-3 is multiplied and are needed (LDS write) while tile
+        // t-1 is -- two K-tiles of time to land instead of one.  A K-tile of this kernel lasts about as long as a load
+        // that misses L2 takes, so with one tile of slack every tile waited for its slowest load.  Two register sets; the
+        // loop is unrolled by two so that set and buffer indices are compile-time, and the steady part issues its loads
+        // unconditionally: only then can hipcc count the loads in flight and wait for the OLDER set alone (vmcnt(4));
+        // one conditional load anywhere on the path and it drains the queue (vmcnt(0)) at every LDS write.
+        // tile kt (buffer kt & 1) writes out tile kt+1 (set (kt+1) & 1, loaded two tiles ago) and loads tile kt+3 into that set.
+        set_tap();
+        load_tile(0);
+        load_tile(1);
+        store_tile(0, 0);
+        load_tile(0);
+        __syncthreads();
+        int kt = 0;
+        for (; kt + 4 < nk; kt += 2) {           // both halves have a tile kt+3 to load
+            tile(0, 1, true, true);
+            tile(1, 0, true, true);
+        }
+        for (; kt < nk; kt += 2) {               // the last three or four tiles
+            tile(0, 1, kt + 1 < nk, kt + 3 < nk);
+            if (kt + 1 < nk) tile(1, 0, kt + 2 < nk, kt + 4 < nk);
+        }
+    } else {
+        // one tile ahead: tile kt+1 was loaded a tile ago, tile kt+2 lands during this tile
+        if (nk > 0) {
+            set_tap();
+            load_tile(0);
+            store_tile(0, 0);
+            if (nk > 1) load_tile(0);
+        }
+        __syncthreads();
+        for (int kt = 0; kt < nk; ++kt) tile(kt & 1, 0, kt + 1 < nk, kt + 2 < nk);
     }
 
     // ---- epilogue ----------------------------------------------------------------------
@@ -253,27 +171,8 @@ __global__ __launch_bounds__(256 * KQ) void k_gconv(const GConvArgs a) {
     constexpr int LDT = BN + 4;                      // 16-byte slots per row: odd multiple for BN = 32, 64, 128
     static_assert(BM * LDT <= 2 * LD * (BM + BN), "output tile must fit the staging buffers");
     float* const sT = smem;
-    if (KQ > 1) {                                    // quad 1's accumulators -> LDS -> added to quad 0's (lane-for-lane)
-        float* const red = smem + 2 * LD * (BM + BN);        // quad 1's own staging area
-        if (quad == 1) {
-#pragma unroll
-            for (int i = 0; i < TM; ++i)
-#pragma unroll
-                for (int j = 0; j < TN; ++j)
-#pragma unroll
-                    for (int r = 0; r < 16; ++r) red[(((wave * TM + i) * TN + j) * 16 + r) * 64 + lane] = acc[i][j][r];
-        }
-        __syncthreads();
-        if (quad == 0) {
-#pragma unroll
-            for (int i = 0; i < TM; ++i)
-#pragma unroll
-                for (int j = 0; j < TN; ++j)
-#pragma unroll
-                    for (int r = 0; r < 16; ++r) acc[i][j][r] += red[(((wave * TM + i) * TN + j) * 16 + r) * 64 + lane];
-        }
-    }
-    if (quad == 0) {
+    if (KQ > 1) kq_handover(smem + 2 * LD * (BM + BN), b.quad, wave, lane, acc);      // (red: b.quad 1's own staging area)
+    if (b.quad == 0) {
 #pragma unroll
         for (int i = 0; i < TM; ++i)
 #pragma unroll
@@ -283,75 +182,30 @@ __global__ __launch_bounds__(256 * KQ) void k_gconv(const GConvArgs a) {
                     sT[(wm * (32 * TM) + 32 * i + (r & 3) + 8 * (r >> 2) + 4 * lh) * LDT + wn * (32 * TN) + 32 * j + li] = acc[i][j][r];
     }
     __syncthreads();
-    if (quad != 0 && epi != EPI_BN_BWD_STATS) return;       // (with the statistics every wave stays for the barriers below)
+    if (b.quad != 0 && epi != EPI_BN_BWD_STATS) return;       // (with the statistics every wave stays for the barriers below)
     constexpr int C4 = BN / 4, RPP = 256 / C4;       // float4 columns per row, rows per pass
-    const int c4 = tid % C4, r0 = tid / C4;
-    const int co = n0 + c4 * 4;
-    BnBwdParams bq;
-    f32x4 st0 = {0.f, 0.f, 0.f, 0.f}, st1 = st0;
-    if (epi == EPI_BN_BWD_STATS) bq = bn_bwd_params(a.bnp, a.Co, co);
-    const f32x4 bias4 = epi == EPI_BIAS_LRELU_DROP ? *reinterpret_cast<const f32x4*>(a.bias + co) : f32x4{0.f, 0.f, 0.f, 0.f};
-    f32x4 sc4 = {1.f, 1.f, 1.f, 1.f}, sh4 = {0.f, 0.f, 0.f, 0.f};
-    if (epi == EPI_AFFINE_RELU) { sc4 = *reinterpret_cast<const f32x4*>(a.scale + co); sh4 = *reinterpret_cast<const f32x4*>(a.shift + co); }
-    const bool use_noise = (epi == EPI_BIAS_LRELU_DROP || epi == EPI_LRELU_BWD) && a.noise != nullptr;
+    const int c4 = b.tid % C4, r0 = b.tid / C4;
+    const int co = b.n0 + c4 * 4;
+    EpiState q = epi_load(a, epi, co);
 #pragma unroll
     for (int p = 0; p < BM / RPP; ++p) {
-        const int row = r0 + RPP * p, m = m0 + row;
-        if (m >= a.M || quad != 0) continue;
+        const int row = r0 + RPP * p, m = b.m0 + row;
+        if (m >= a.M || b.quad != 0) continue;
         const int n = m >> (a.lgHr + a.lgWr);
         size_t opix;
         if (a.form == 0) {
             opix = (size_t)m;
         } else {
-            const int rh = (m >> a.lgWr) & (Hr - 1), rw = m & (Wr - 1);
-            opix = ((size_t)n * a.Ho + 2 * rh + ph) * a.Wo + 2 * rw + pw;
+            const int rh = (m >> a.lgWr) & (b.Hr - 1), rw = m & (b.Wr - 1);
+            opix = ((size_t)n * a.Ho + 2 * rh + b.ph) * a.Wo + 2 * rw + b.pw;
         }
         const size_t o = opix * a.Co + co;
-        f32x4 v = *reinterpret_cast<const f32x4*>(sT + row * LDT + c4 * 4);
-        if (epi == EPI_BN_BWD_STATS) {
-            bn_bwd_stat_terms<float, LK>(v, *reinterpret_cast<const f32x4*>(static_cast<const float*>(a.aref) + o), bq, a.gslope, st0, st1);
-        } else if (epi == EPI_BIAS_LRELU_DROP) {
-#pragma unroll
-            for (int e = 0; e < 4; ++e) { float t = v[e] + bias4[e]; v[e] = t > 0.f ? t : t * a.slope; }
-            if (use_noise) {
-                const f32x4 nz = *reinterpret_cast<const f32x4*>(a.noise + (size_t)n * a.Co + co);
-#pragma unroll
-                for (int e = 0; e < 4; ++e) v[e] *= nz[e];
-            }
-        } else if (epi == EPI_AFFINE_RELU) {
-#pragma unroll
-            for (int e = 0; e < 4; ++e) v[e] = g_act<LK>(fmaf(v[e], sc4[e], sh4[e]), a.gslope);
-        } else if (epi == EPI_LRELU_BWD) {
-            const f32x4 ar = *reinterpret_cast<const f32x4*>(static_cast<const float*>(a.aref) + o);
-#pragma unroll
-            for (int e = 0; e < 4; ++e) v[e] *= ar[e] > 0.f ? 1.f : a.slope;
-            if (use_noise) {
-                const f32x4 nz = *reinterpret_cast<const f32x4*>(a.noise + (size_t)n * a.Co + co);
-#pragma unroll
-                for (int e = 0; e < 4; ++e) v[e] *= nz[e];
-            }
-        }
+        const f32x4 v = epi_apply<float, LK>(a, q, *reinterpret_cast<const f32x4*>(sT + row * LDT + c4 * 4), o, n, co);
         *reinterpret_cast<f32x4*>(outp + o) = v;
     }
-    if (epi == EPI_BN_BWD_STATS) {
-        // the tile's column sums: the RPP row lanes of a channel group meet in LDS (the tile is stored: sT is free after the
-        // barrier) and are added in lane order -- one partial row per workgroup, a fixed sum order
-        __syncthreads();
-        if (quad == 0) {
-            *reinterpret_cast<f32x4*>(sT + (size_t)tid * 8) = st0;
-            *reinterpret_cast<f32x4*>(sT + (size_t)tid * 8 + 4) = st1;
-        }
-        __syncthreads();
-        if (quad == 0 && r0 == 0) {
-#pragma unroll 4
-            for (int k = 1; k < RPP; ++k) {
-                st0 += *reinterpret_cast<const f32x4*>(sT + (size_t)(k * C4 + c4) * 8);
-                st1 += *reinterpret_cast<const f32x4*>(sT + (size_t)(k * C4 + c4) * 8 + 4);
-            }
-            const size_t prow = (size_t)cls * (gridDim.x / tiles_n) + bid / tiles_n;
-            *reinterpret_cast<f32x4*>(a.stat0 + prow * a.Co + co) = st0;
-            *reinterpret_cast<f32x4*>(a.stat1 + prow * a.Co + co) = st1;
-        }
+    if (q.stats) {
+        __syncthreads();                             // the tile is stored: sT is free
+        epi_stats_reduce(a, q, sT, b.tid, b.quad == 0, c4, r0, C4, RPP, (size_t)b.cls * (gridDim.x / b.tiles_n) + b.bid / b.tiles_n, co);
     }
 }
 
@@ -502,80 +356,40 @@ __global__ __launch_bounds__(256) void k_gconv_up4(const GConvArgs a) {
     for (int q = 0; q < (BM * 4 * BN / 4) / 256; ++q) dst[q * 256 + tid] = src[q * 256 + tid];
 }
 
-// split-K tail: out = epilogue(sum_z slab[z]) over the NHWC output (4 channels per thread)
+// split-K tail: out = epilogue(sum_z slab[z]) over the NHWC output (4 channels per thread; the epilogues of gconv_parts.h)
 template <class T, bool LK>
 __global__ __launch_bounds__(256) void k_splitk_epilogue(const GConvArgs a, int nsplit, int64_t total4) {
+    __shared__ __attribute__((aligned(16))) float sh[256 * 8];
     const int64_t i = (int64_t)blockIdx.x * 256 + threadIdx.x;
-    if (a.epi == EPI_BN_BWD_STATS) {
-        // 256 consecutive float4 = 256 / C4 rows of all C4 channel groups (launch_gconv checks C4 | 256): the row lanes of a
-        // group meet in LDS, one partial row per workgroup, a fixed sum order
-        __shared__ __attribute__((aligned(16))) float sh[256 * 8];
-        const int C4 = a.Co / 4, c4 = threadIdx.x & (C4 - 1);
-        f32x4 s0 = {0.f, 0.f, 0.f, 0.f}, s1 = s0;
-        if (i < total4) {
-            const f32x4* sl = reinterpret_cast<const f32x4*>(a.slab);
-            const size_t stride4 = a.slab_stride / 4;
-            f32x4 v = sl[i];
-            for (int z = 1; z < nsplit; ++z) v += sl[(size_t)z * stride4 + i];
-            bn_bwd_stat_terms<T, LK>(v, ld4<T>(static_cast<const T*>(a.aref) + i * 4), bn_bwd_params(a.bnp, a.Co, c4 * 4), a.gslope, s0, s1);
-            st4<T>(static_cast<T*>(a.out) + i * 4, v);
-        }
-        *reinterpret_cast<f32x4*>(sh + threadIdx.x * 8) = s0;
-        *reinterpret_cast<f32x4*>(sh + threadIdx.x * 8 + 4) = s1;
-        __syncthreads();
-        if ((int)threadIdx.x < C4) {
-            for (int k = 1; k < 256 / C4; ++k) {
-                s0 += *reinterpret_cast<const f32x4*>(sh + (k * C4 + c4) * 8);
-                s1 += *reinterpret_cast<const f32x4*>(sh + (k * C4 + c4) * 8 + 4);
-            }
-            *reinterpret_cast<f32x4*>(a.stat0 + (size_t)blockIdx.x * a.Co + c4 * 4) = s0;
-            *reinterpret_cast<f32x4*>(a.stat1 + (size_t)blockIdx.x * a.Co + c4 * 4) = s1;
-        }
-        return;
-    }
-    if (i >= total4) return;
-    const float4* sl = reinterpret_cast<const float4*>(a.slab);
-    const size_t stride4 = a.slab_stride / 4;
-    float4 v = sl[i];
-    for (int z = 1; z < nsplit; ++z) {
-        const float4 w = sl[(size_t)z * stride4 + i];
-        v.x += w.x; v.y += w.y; v.z += w.z; v.w += w.w;
-    }
     const int C4 = a.Co / 4;
     const int64_t per_img = (int64_t)C4 * a.Ho * a.Wo;
     const bool p2 = (C4 & (C4 - 1)) == 0 && (per_img & (per_img - 1)) == 0;       // every layer: shifts instead of 64-bit divisions
-    const int c = (p2 ? (int)(i & (C4 - 1)) : (int)(i % C4)) * 4;
+    const int c4 = p2 ? (int)(i & (C4 - 1)) : (int)(i % C4);
     const int64_t n = p2 ? i >> (63 - __builtin_clzll(per_img)) : i / per_img;
-    float* e = reinterpret_cast<float*>(&v);
-    if (a.epi == EPI_BIAS_LRELU_DROP) {
-#pragma unroll
-        for (int k = 0; k < 4; ++k) {
-            float x = e[k] + a.bias[c + k];
-            x = x > 0.f ? x : x * a.slope;
-            if (a.noise) x *= a.noise[n * a.Co + c + k];
-            e[k] = x;
-        }
-    } else if (a.epi == EPI_AFFINE_RELU) {
-#pragma unroll
-        for (int k = 0; k < 4; ++k) e[k] = g_act<LK>(fmaf(e[k], a.scale[c + k], a.shift[c + k]), a.gslope);
-    } else if (a.epi == EPI_LRELU_BWD) {
-        const f32x4 ar = ld4<T>(static_cast<const T*>(a.aref) + i * 4);
-        const float* r = reinterpret_cast<const float*>(&ar);
-#pragma unroll
-        for (int k = 0; k < 4; ++k) {
-            float x = e[k] * (r[k] > 0.f ? 1.f : a.slope);
-            if (a.noise) x *= a.noise[n * a.Co + c + k];
-            e[k] = x;
-        }
+    EpiState q = epi_load(a, a.epi, c4 * 4);
+    if (i >= total4 && !q.stats) return;
+    f32x4 v = {0.f, 0.f, 0.f, 0.f};
+    if (i < total4) {
+        const f32x4* sl = reinterpret_cast<const f32x4*>(a.slab);
+        const size_t stride4 = a.slab_stride / 4;
+        v = sl[i];
+        for (int z = 1; z < nsplit; ++z) v += sl[(size_t)z * stride4 + i];
+        v = epi_apply<T, LK>(a, q, v, (size_t)i * 4, (int)n, c4 * 4);
+        st4<T>(static_cast<T*>(a.out) + i * 4, v);
     }
-    st4<T>(static_cast<T*>(a.out) + i * 4, f32x4{v.x, v.y, v.z, v.w});
+    if (q.stats) {
+        // 256 consecutive float4 = 256 / C4 rows of all C4 channel groups (launch_gconv checks C4 | 256): one partial row per
+        // workgroup; a ragged last workgroup's idle threads bring zeros
+        epi_stats_reduce(a, q, sh, threadIdx.x, true, c4, (int)threadIdx.x / C4, C4, 256 / C4, blockIdx.x, c4 * 4);
+        return;
+    }
     if (a.cls_w) {
         // the classifier's dot product over the values just stored (as stored: rounded to T), 1024 of them per workgroup; every
         // thread is here (launch_gconv: total4 % 256 == 0, per_img % 256 == 0)
         __shared__ float shc[4];
         const f32x4 w4 = *reinterpret_cast<const f32x4*>(a.cls_w + (size_t)(p2 ? (i & (per_img - 1)) : (i % per_img)) * 4);
-        float d = (float)(T)v.x * w4[0];
-        d = fmaf((float)(T)v.y, w4[1], d); d = fmaf((float)(T)v.z, w4[2], d); d = fmaf((float)(T)v.w, w4[3], d);
+        float d = (float)(T)v[0] * w4[0];
+        d = fmaf((float)(T)v[1], w4[1], d); d = fmaf((float)(T)v[2], w4[2], d); d = fmaf((float)(T)v[3], w4[3], d);
 #pragma unroll
         for (int o = 32; o > 0; o >>= 1) d += __shfl_down(d, o, 64);
         if ((threadIdx.x & 63) == 0) shc[threadIdx.x >> 6] = d;
@@ -622,7 +436,7 @@ static double wgrad_bytes(const WgradArgs& a) {
     return es * ((double)a.K * a.Cs + 4.0 * a.K * a.Cl) + 4.0 * 16.0 * a.Cs * a.Cl;
 }
 
-template <int BM, int BN, int WM, int WN, int BKT = 32, int DEEP = 0, int KQ = 1>
+template <int BM, int BN, int WM, int WN, int KQ = 1>
 static int launch_cfg(const GConvArgs& a_in, hipStream_t st, int id, int nsplit) {
     GConvArgs a = a_in;
     const int tiles = ((a.M + BM - 1) / BM) * (a.Co / BN);
@@ -651,11 +465,11 @@ static int launch_cfg(const GConvArgs& a_in, hipStream_t st, int id, int nsplit)
     if (a.dt != DT_F32) {
         launch_gconv16(id, a, grid, st, e0, e1, KQ);
     } else if (gen_lk(a)) {
-        hipExtLaunchKernelGGL((k_gconv<BM, BN, WM, WN, BKT, DEEP, KQ, true>), grid, dim3(256 * KQ), 0, st, e0, e1, 0, a);
+        hipExtLaunchKernelGGL((k_gconv<BM, BN, WM, WN, KQ, true>), grid, dim3(256 * KQ), 0, st, e0, e1, 0, a);
     } else if (g_prof) {
-        hipExtLaunchKernelGGL((k_gconv<BM, BN, WM, WN, BKT, DEEP, KQ>), grid, dim3(256 * KQ), 0, st, e0, e1, 0, a);
+        hipExtLaunchKernelGGL((k_gconv<BM, BN, WM, WN, KQ>), grid, dim3(256 * KQ), 0, st, e0, e1, 0, a);
     } else {
-        hipLaunchKernelGGL((k_gconv<BM, BN, WM, WN, BKT, DEEP, KQ>), grid, dim3(256 * KQ), 0, st, a);
+        hipLaunchKernelGGL((k_gconv<BM, BN, WM, WN, KQ>), grid, dim3(256 * KQ), 0, st, a);
     }
     if (nsplit > 1)
         SIGGAN_GS_SWITCH(gen_lk(a) ? 1.f : 0.f, LK, SIGGAN_DT_SWITCH(a.dt, T, hipLaunchKernelGGL((k_splitk_epilogue<T, LK>),
@@ -693,16 +507,16 @@ int launch_gconv(const GConvArgs& a_in, hipStream_t st) {
     if (a.Co >= 64) {
         // 128x128 (four accumulators per wave, 82 % MFMA-busy) only when it still yields two workgroups per CU; the
         // 128x64 middle size measured below 64x64 on every shape of the step (86 vs 93 TFLOP/s) and is not built
-        if (a.Co >= 128 && blocks(128, 128) >= 512) return launch_cfg<128, 128, 2, 2, 32, 1>(a, st, 0, 1);
+        if (a.Co >= 128 && blocks(128, 128) >= 512) return launch_cfg<128, 128, 2, 2>(a, st, 0, 1);
         const int ns = splits(blocks(64, 64));
         // a two-way split runs as ONE launch of 8-wave workgroups (no slabs, no k_splitk_epilogue); nk is a power of two,
         // so the halves are equal
-        if (ns == 2 && (nk & 1) == 0) return launch_cfg<64, 64, 2, 2, 32, 1, 2>(a, st, 2, 1);
+        if (ns == 2 && (nk & 1) == 0) return launch_cfg<64, 64, 2, 2, 2>(a, st, 2, 1);
         // 16-bit: a four-way split too (unless the classifier rides in the slab epilogue) -- the K loop is twice as long but
         // short either way, the epilogue launch is what counts: bf16 step 0.6172 -> 0.6077 ms (fp32: step unchanged, the
         // Generator's eval forward 87.7 -> 90.4 us: stays split)
-        if (ns == 4 && !a.cls_w && a.dt != DT_F32 && (nk & 1) == 0) return launch_cfg<64, 64, 2, 2, 32, 1, 2>(a, st, 2, 1);
-        return launch_cfg<64, 64, 2, 2, 32, 1>(a, st, 2, ns);
+        if (ns == 4 && !a.cls_w && a.dt != DT_F32 && (nk & 1) == 0) return launch_cfg<64, 64, 2, 2, 2>(a, st, 2, 1);
+        return launch_cfg<64, 64, 2, 2>(a, st, 2, ns);
     }
     if (a.dt == DT_F32 && a.form == 1 && a.Co == 32 && (a.epi == EPI_RAW || a.epi == EPI_AFFINE_RELU) && (a.Ci == 32 || a.Ci == 64) &&
         a.M / 128 >= (a.Ci == 32 ? 384 : 768) && a.M % 128 == 0 &&
@@ -724,7 +538,7 @@ int launch_gconv(const GConvArgs& a_in, hipStream_t st) {
         return 0;
     }
     const int ns = splits(blocks(128, 32));
-    return launch_cfg<128, 32, 4, 1, 32, 1>(a, st, 3, ns);   // Co == 32
+    return launch_cfg<128, 32, 4, 1>(a, st, 3, ns);   // Co == 32
 }
 
 // ------------------------------------------------------------------------------------------
@@ -890,42 +704,7 @@ __global__ __launch_bounds__(256) void k_wgrad(const WgradArgs a) {
 
 #undef WG_LOAD_TILE
 #undef WG_STORE_TILE
-    if (bias_blk) {                                   // the main loop's last barrier has passed: LDS is free
-        smem[kq * BM + bcol] = bsum;
-        __syncthreads();
-        if (tid < BM) {
-            float t = smem[tid];
-#pragma unroll
-            for (int q = 1; q < NQ; ++q) t += smem[q * BM + tid];
-            if (gridDim.z == 1) a.db[i0 + tid] = t;
-            else a.slab[(size_t)gridDim.z * a.Cs * N + (size_t)bz * a.Cs + i0 + tid] = t;
-        }
-    }
-    if (gridDim.z == 1 && a.dw) {
-        // a single split: un-permute straight into the torch layout, column j = tap*Cl + l -> dw[(row*Cl + l)*16 + tap]
-#pragma unroll
-        for (int i = 0; i < TM; ++i)
-#pragma unroll
-            for (int r = 0; r < 16; ++r) {
-                const int row = i0 + wm * (32 * TM) + 32 * i + (r & 3) + 8 * (r >> 2) + 4 * lh;
-#pragma unroll
-                for (int j = 0; j < TN; ++j) {
-                    const int col = j0 + wn * (32 * TN) + 32 * j + li;
-                    a.dw[((size_t)row * Cl + (col & (Cl - 1))) * 16 + (col >> a.lgCl)] = acc[i][j][r];
-                }
-            }
-        return;
-    }
-    float* const out = a.slab + (size_t)bz * a.Cs * N;
-#pragma unroll
-    for (int i = 0; i < TM; ++i)
-#pragma unroll
-        for (int r = 0; r < 16; ++r) {
-            const int row = i0 + wm * (32 * TM) + 32 * i + (r & 3) + 8 * (r >> 2) + 4 * lh;
-#pragma unroll
-            for (int j = 0; j < TN; ++j)
-                out[(size_t)row * N + j0 + wn * (32 * TN) + 32 * j + li] = acc[i][j][r];
-        }
+    wgrad_tail<BM, BN, WM, WN>(a, smem, bias_blk, bsum, i0, j0, bz, acc);
 }
 
 static void launch_wgrad_reduce(const float* slab, float* dw, float* db, int nsplit, int Cs, int Cl, hipStream_t st);
@@ -994,8 +773,6 @@ __global__ __launch_bounds__(1024) void k_wgrad_reduce(const float* __restrict__
     const int tap = j >> lgCl, l = j & (Cl - 1);
     dw[((size_t)s_ * Cl + l) * 16 + tap] = acc;
 }
-
-static int ilog2(int v) { int l = 0; while ((1 << l) < v) ++l; return l; }
 
 static void launch_wgrad_reduce(const float* slab, float* dw, float* db, int nsplit, int Cs, int Cl, hipStream_t st) {
     const size_t total = (size_t)Cs * 16 * Cl;                 // a multiple of 64 (Cs, Cl >= 32)

@@ -1,8 +1,11 @@
 // gconv16.hip -- the implicit-GEMM kernels of gconv.hip for 16-bit operands (bf16 / f16 activations and packed
 // weights, fp32 accumulate): v_mfma_f32_32x32x16_{bf16,f16}, gfx950 only.  BASELINE.json configs[2] / configs[4].
 //
-// Same GEMM views, tile shapes, split-K / slab protocol and fused epilogues as the fp32 kernels; what differs is the
-// operand path.  A K-tile is 32 elements (64 bytes per row):
+// Same GEMM views, tile shapes, split-K / slab protocol and fused epilogues as the fp32 kernels, built from the same parts
+// (gconv_parts.h: XCD remap, block setup GconvBlock, row coordinates and tap cursor GconvRows, the KQ = 2 hand-over
+// kq_handover, the epilogues epi_load / epi_apply / epi_stats_reduce, the weight-gradient tail wgrad_tail); what differs,
+// and is kept here, is the operand path and the move of the accumulator tile through LDS in 64-row slices.
+// A K-tile is 32 elements (64 bytes per row):
 //   k_gconv16 : both operands are K-contiguous in memory (NHWC im2col rows; [Co][tap*Ci + ci] weight packs), so the LDS
 //               tiles are [row][32 + 8 pad] (80-byte row stride = 5 sixteen-byte slots, odd) and a lane's MFMA
 //               fragment -- A[row l&31][k = 8(l>>5) .. +7] -- is ONE conflict-free ds_read_b128;
@@ -13,17 +16,10 @@
 // 16-bit storage makes the step launch- and HBM-bound rather than MFMA-bound, so these kernels keep the
 // fp32 kernels' simple one-tile-ahead register staging; the accumulators, split-K slabs, weight-gradient outputs and
 // every epilogue computation are fp32.
-#include "gconv.h"
+#include "gconv_parts.h"
 #include <hip/hip_ext.h>
 
 namespace siggan {
-
-static constexpr int BK = 32;     // K-tile, elements
-
-__device__ __forceinline__ int xcd_remap16(int bid, int nwg) {
-    const int q = nwg >> 3, r = nwg & 7, xcd = bid & 7, idx = bid >> 3;
-    return (xcd < r ? xcd * (q + 1) : r * (q + 1) + (xcd - r) * q) + idx;
-}
 
 template <class T> struct Mma;
 template <> struct Mma<bf16_t> {
@@ -47,75 +43,35 @@ __global__ __launch_bounds__(256 * KQ) void k_gconv16(const GConvArgs a) {
     // (KQ = 2: the fp32 hand-over of quad 1's accumulators needs 64 lanes x 16 registers x 4 waves x 4 bytes per 32x32 block)
     constexpr int RED_SHORTS = KQ > 1 ? TM * TN * 4 * 16 * 64 * 2 : 0;
     __shared__ __attribute__((aligned(16))) unsigned short smem_raw[KQ * QUAD_SHORTS > QUAD_SHORTS + RED_SHORTS ? KQ * QUAD_SHORTS : QUAD_SHORTS + RED_SHORTS];
-    const int quad = KQ > 1 ? (int)(threadIdx.x >> 8) : 0;
-    T* const sA = reinterpret_cast<T*>(smem_raw) + quad * QUAD_SHORTS;
+    const GconvBlock<BM, BN, KQ> b(a);
+    const int nk = b.nk;
+    T* const sA = reinterpret_cast<T*>(smem_raw) + b.quad * QUAD_SHORTS;
     T* const sB = sA + 2 * LD * BM;
 
-    const int tid = threadIdx.x & 255, lane = tid & 63, wave = tid >> 6;      // thread / wave index inside the quad
+    const int lane = b.tid & 63, wave = b.tid >> 6;      // wave index inside the quad
     const int li = lane & 31, lh = lane >> 5;
     const int wm = wave / WN, wn = wave % WN;
-    const T* const in = reinterpret_cast<const T*>(a.in);
     const T* const wp = reinterpret_cast<const T*>(a.wp);
 
-    const int tiles_n = a.Co / BN;
-    const int bid = xcd_remap16(blockIdx.x, gridDim.x);
-    const int m0 = (bid / tiles_n) * BM, n0 = (bid % tiles_n) * BN;
-    const int cls = blockIdx.z, ph = cls >> 1, pw = cls & 1;
-    const int Hr = 1 << a.lgHr, Wr = 1 << a.lgWr;
-    const int ntaps = a.form == 0 ? 16 : 4;
-    const int Ktot = ntaps * a.Ci;
-    const int lgcpt = 31 - __builtin_clz(a.Ci / BK);
-    const int nk_all = ntaps << lgcpt;
-    const int kper = (nk_all + gridDim.y * KQ - 1) / (gridDim.y * KQ);
-    const int k_lo = (blockIdx.y * KQ + quad) * kper;
-    const int k_hi = min(nk_all, k_lo + kper);
-    const int nk = k_hi - k_lo;
-
     // staging coordinates: row rloc + 64p, 16-byte chunk kc (8 elements) of the 32-element k-row
-    const int kc = tid & 3, rloc = tid >> 2;
-    const T* a_base[PA];
-    int a_ih0[PA], a_iw0[PA];
+    const int kc = b.tid & 3, rloc = b.tid >> 2;
+    GconvRows<T, PA> rows;
 #pragma unroll
-    for (int p = 0; p < PA; ++p) {
-        const int m = m0 + ((rloc + 64 * p) & (BM - 1));
-        if (m < a.M) {
-            const int n = m >> (a.lgHr + a.lgWr);
-            const int rh = (m >> a.lgWr) & (Hr - 1), rw = m & (Wr - 1);
-            a_base[p] = in + (size_t)n * a.Hi * a.Wi * a.Ci + kc * 8;
-            if (a.form == 0) { a_ih0[p] = 2 * rh - 1; a_iw0[p] = 2 * rw - 1; }
-            else             { a_ih0[p] = rh + ph;    a_iw0[p] = rw + pw; }
-        } else {
-            a_base[p] = in; a_ih0[p] = -(1 << 20); a_iw0[p] = -(1 << 20);
-        }
-    }
-    const T* wcur = wp + ((size_t)cls * a.Co + n0 + (rloc & (BN - 1))) * Ktot + kc * 8 + (size_t)k_lo * BK;
-    const T* const zeros = reinterpret_cast<const T*>(a.zeros);
-
-    const T* a_cur[PA];
-    int a_step[PA];
-    int l_tap = k_lo >> lgcpt, l_cc = k_lo & ((1 << lgcpt) - 1);
-    auto set_tap = [&]() __attribute__((always_inline)) {
-        int dh, dw;
-        if (a.form == 0) { dh = l_tap >> 2; dw = l_tap & 3; } else { dh = -(l_tap >> 1); dw = -(l_tap & 1); }
-#pragma unroll
-        for (int p = 0; p < PA; ++p) {
-            const int ih = a_ih0[p] + dh, iw = a_iw0[p] + dw;
-            const bool ok = (unsigned)ih < (unsigned)a.Hi && (unsigned)iw < (unsigned)a.Wi;
-            a_cur[p] = ok ? a_base[p] + ((size_t)(ih * a.Wi + iw) * a.Ci + l_cc * BK) : zeros;
-            a_step[p] = ok ? BK : 0;
-        }
-    };
+    for (int p = 0; p < PA; ++p) gconv_row(a, b, rows, p, b.m0 + ((rloc + 64 * p) & (BM - 1)), kc * 8);
+    const T* wcur = wp + ((size_t)b.cls * a.Co + b.n0 + (rloc & (BN - 1))) * b.Ktot + kc * 8 + (size_t)b.k_lo * BK;
+    int l_tap = b.k_lo >> b.lgcpt, l_cc = b.k_lo & ((1 << b.lgcpt) - 1);
+    auto set_tap = [&]() __attribute__((always_inline)) { gconv_set_tap(a, rows, l_tap, l_cc); };
     s16x8 ra[NSET][PA], rb[NSET][PB];    // register sets: tile t waits in set t % NSET
     auto load_tile = [&](int set = 0) __attribute__((always_inline)) {
 #pragma unroll
         for (int p = 0; p < PA; ++p) {
-            ra[set][p] = *reinterpret_cast<const s16x8*>(a_cur[p]);
-            a_cur[p] += a_step[p];
+            ra[set][p] = *reinterpret_cast<const s16x8*>(rows.cur[p]);
+            rows.cur[p] += rows.step[p];
         }
 #pragma unroll
-        for (int p = 0; p < PB; ++p) rb[set][p] = *reinterpret_cast<const s16x8*>(wcur + (size_t)(64 * p) * Ktot);
+        for (int p = 0; p < PB; ++p) rb[set][p] = *reinterpret_cast<const s16x8*>(wcur + (size_t)(64 * p) * b.Ktot);
         wcur += BK;
-        if (++l_cc == (1 << lgcpt)) { l_cc = 0; ++l_tap; set_tap(); }
+        if (++l_cc == (1 << b.lgcpt)) { l_cc = 0; ++l_tap; set_tap(); }
     };
     auto store_tile = [&](int buf, int set = 0) __attribute__((always_inline)) {
         T* dA = sA + buf * LD * BM + (rloc & (BM - 1)) * LD + kc * 8;
@@ -195,48 +151,22 @@ __global__ __launch_bounds__(256 * KQ) void k_gconv16(const GConvArgs a) {
     const bool to_slab = gridDim.y > 1;
     float* const slab = a.slab + (size_t)blockIdx.y * a.slab_stride;
     T* const outp = reinterpret_cast<T*>(a.out);
-    const T* const aref = reinterpret_cast<const T*>(a.aref);
     const int epi = to_slab ? (int)EPI_RAW : a.epi;
     constexpr int LDT = BN + 4, SR = BM < 64 ? BM : 64, NPASS = BM / SR;
     static_assert(SR * LDT * 4 <= 2 * LD * (BM + BN) * 2, "a 64-row slice of the output tile must fit the staging buffers");
     float* const sT = reinterpret_cast<float*>(smem_raw);
-    if (KQ > 1) {                                    // quad 1's accumulators -> LDS -> added to quad 0's (lane-for-lane)
-        float* const red = reinterpret_cast<float*>(smem_raw + QUAD_SHORTS);
-        if (quad == 1) {
-#pragma unroll
-            for (int i = 0; i < TM; ++i)
-#pragma unroll
-                for (int j = 0; j < TN; ++j)
-#pragma unroll
-                    for (int r = 0; r < 16; ++r) red[(((wave * TM + i) * TN + j) * 16 + r) * 64 + lane] = acc[i][j][r];
-        }
-        __syncthreads();
-        if (quad == 0) {
-#pragma unroll
-            for (int i = 0; i < TM; ++i)
-#pragma unroll
-                for (int j = 0; j < TN; ++j)
-#pragma unroll
-                    for (int r = 0; r < 16; ++r) acc[i][j][r] += red[(((wave * TM + i) * TN + j) * 16 + r) * 64 + lane];
-        }
-    }
+    if (KQ > 1) kq_handover(reinterpret_cast<float*>(smem_raw + QUAD_SHORTS), b.quad, wave, lane, acc);
     constexpr int C4 = BN / 4, RPP = 256 / C4;
-    const int c4 = tid % C4, r0 = tid / C4;
-    const int co = n0 + c4 * 4;
-    const f32x4 bias4 = epi == EPI_BIAS_LRELU_DROP ? *reinterpret_cast<const f32x4*>(a.bias + co) : f32x4{0.f, 0.f, 0.f, 0.f};
-    f32x4 sc4 = {1.f, 1.f, 1.f, 1.f}, sh4 = {0.f, 0.f, 0.f, 0.f};
-    if (epi == EPI_AFFINE_RELU) { sc4 = *reinterpret_cast<const f32x4*>(a.scale + co); sh4 = *reinterpret_cast<const f32x4*>(a.shift + co); }
-    const bool use_noise = (epi == EPI_BIAS_LRELU_DROP || epi == EPI_LRELU_BWD) && a.noise != nullptr;
-    BnBwdParams bq;
-    f32x4 st0 = {0.f, 0.f, 0.f, 0.f}, st1 = st0;
-    if (epi == EPI_BN_BWD_STATS) bq = bn_bwd_params(a.bnp, a.Co, co);
+    const int c4 = b.tid % C4, r0 = b.tid / C4;
+    const int co = b.n0 + c4 * 4;
+    EpiState e = epi_load(a, epi, co);
 #pragma unroll
     for (int q = 0; q < NPASS; ++q) {
         if (q) __syncthreads();
 #pragma unroll
         for (int i = 0; i < TM; ++i) {
             const int rb = wm * (32 * TM) + 32 * i - q * SR;              // this wave's 32-row block inside the slice?
-            if (rb < 0 || rb >= SR || quad != 0) continue;
+            if (rb < 0 || rb >= SR || b.quad != 0) continue;
 #pragma unroll
             for (int j = 0; j < TN; ++j)
 #pragma unroll
@@ -246,61 +176,24 @@ __global__ __launch_bounds__(256 * KQ) void k_gconv16(const GConvArgs a) {
         __syncthreads();
 #pragma unroll
         for (int p = 0; p < SR / RPP; ++p) {
-            const int row = r0 + RPP * p, m = m0 + q * SR + row;
-            if (m >= a.M || quad != 0) continue;
+            const int row = r0 + RPP * p, m = b.m0 + q * SR + row;
+            if (m >= a.M || b.quad != 0) continue;
             const int n = m >> (a.lgHr + a.lgWr);
             size_t opix;
             if (a.form == 0) {
                 opix = (size_t)m;
             } else {
-                const int rh = (m >> a.lgWr) & (Hr - 1), rw = m & (Wr - 1);
-                opix = ((size_t)n * a.Ho + 2 * rh + ph) * a.Wo + 2 * rw + pw;
+                const int rh = (m >> a.lgWr) & (b.Hr - 1), rw = m & (b.Wr - 1);
+                opix = ((size_t)n * a.Ho + 2 * rh + b.ph) * a.Wo + 2 * rw + b.pw;
             }
             const size_t o = opix * a.Co + co;
-            f32x4 v = *reinterpret_cast<const f32x4*>(sT + row * LDT + c4 * 4);
-            if (epi == EPI_BN_BWD_STATS) {
-                bn_bwd_stat_terms<T, LK>(v, ld4<T>(aref + o), bq, a.gslope, st0, st1);      // (v as it is stored: rounded to T)
-            } else if (epi == EPI_BIAS_LRELU_DROP) {
-#pragma unroll
-                for (int e = 0; e < 4; ++e) { float t = v[e] + bias4[e]; v[e] = t > 0.f ? t : t * a.slope; }
-                if (use_noise) {
-                    const f32x4 nz = *reinterpret_cast<const f32x4*>(a.noise + (size_t)n * a.Co + co);
-#pragma unroll
-                    for (int e = 0; e < 4; ++e) v[e] *= nz[e];
-                }
-            } else if (epi == EPI_AFFINE_RELU) {
-#pragma unroll
-                for (int e = 0; e < 4; ++e) v[e] = g_act<LK>(fmaf(v[e], sc4[e], sh4[e]), a.gslope);
-            } else if (epi == EPI_LRELU_BWD) {
-                const f32x4 ar = ld4<T>(aref + o);
-#pragma unroll
-                for (int e = 0; e < 4; ++e) v[e] *= ar[e] > 0.f ? 1.f : a.slope;
-                if (use_noise) {
-                    const f32x4 nz = *reinterpret_cast<const f32x4*>(a.noise + (size_t)n * a.Co + co);
-#pragma unroll
-                    for (int e = 0; e < 4; ++e) v[e] *= nz[e];
-                }
-            }
+            const f32x4 v = epi_apply<T, LK>(a, e, *reinterpret_cast<const f32x4*>(sT + row * LDT + c4 * 4), o, n, co);
             if (to_slab) *reinterpret_cast<f32x4*>(slab + o) = v; else st4<T>(outp + o, v);
         }
     }
-    if (epi == EPI_BN_BWD_STATS) {                   // the tile's column sums: see k_gconv
-        __syncthreads();
-        if (quad == 0) {
-            *reinterpret_cast<f32x4*>(sT + (size_t)tid * 8) = st0;
-            *reinterpret_cast<f32x4*>(sT + (size_t)tid * 8 + 4) = st1;
-        }
-        __syncthreads();
-        if (quad == 0 && r0 == 0) {
-#pragma unroll 4
-            for (int k = 1; k < RPP; ++k) {
-                st0 += *reinterpret_cast<const f32x4*>(sT + (size_t)(k * C4 + c4) * 8);
-                st1 += *reinterpret_cast<const f32x4*>(sT + (size_t)(k * C4 + c4) * 8 + 4);
-            }
-            const size_t prow = (size_t)cls * (gridDim.x / tiles_n) + bid / tiles_n;
-            *reinterpret_cast<f32x4*>(a.stat0 + prow * a.Co + co) = st0;
-            *reinterpret_cast<f32x4*>(a.stat1 + prow * a.Co + co) = st1;
-        }
+    if (e.stats) {
+        __syncthreads();                             // the tile is stored: sT is free
+        epi_stats_reduce(a, e, sT, b.tid, b.quad == 0, c4, r0, C4, RPP, (size_t)b.cls * (gridDim.x / b.tiles_n) + b.bid / b.tiles_n, co);
     }
 }
 
@@ -354,12 +247,11 @@ __global__ __launch_bounds__(256) void k_wgrad16(const WgradArgs a) {
     const T* const zeros = reinterpret_cast<const T*>(a.zeros);
 
     const int tid = threadIdx.x, lane = tid & 63, wave = tid >> 6;
-    const int li = lane & 31, lh = lane >> 5;
     const int wm = wave / WN, wn = wave % WN;
     const int N = 16 << a.lgCl;
     const int tiles_n = N / BN;
     // (XCD-aware order, as in k_wgrad: the tiles of one K split share an XCD's L2)
-    const int lid = xcd_remap16(blockIdx.z * gridDim.x + blockIdx.x, gridDim.x * gridDim.z);
+    const int lid = xcd_remap(blockIdx.z * gridDim.x + blockIdx.x, gridDim.x * gridDim.z);
     const int bx = lid % gridDim.x, bz = lid / gridDim.x;
     const int i0 = (bx / tiles_n) * BM, j0 = (bx % tiles_n) * BN;
     const int kbeg = bz * a.kchunk;
@@ -456,44 +348,7 @@ __global__ __launch_bounds__(256) void k_wgrad16(const WgradArgs a) {
     }
 #undef WG_LOAD_TILE
 #undef WG_STORE_TILE
-    (void)li; (void)lh;
-    float* const fsm = reinterpret_cast<float*>(smem);
-    if (bias_blk) {                                   // the main loop's last barrier has passed: LDS is free
-        fsm[kq * BM + bcol] = bsum;
-        __syncthreads();
-        if (tid < BM) {
-            float t = fsm[tid];
-#pragma unroll
-            for (int q = 1; q < NQ; ++q) t += fsm[q * BM + tid];
-            if (gridDim.z == 1) a.db[i0 + tid] = t;
-            else a.slab[(size_t)gridDim.z * a.Cs * N + (size_t)bz * a.Cs + i0 + tid] = t;
-        }
-    }
-    const int li2 = lane & 31, lh2 = lane >> 5;
-    if (gridDim.z == 1 && a.dw) {
-#pragma unroll
-        for (int i = 0; i < TM; ++i)
-#pragma unroll
-            for (int r = 0; r < 16; ++r) {
-                const int row = i0 + wm * (32 * TM) + 32 * i + (r & 3) + 8 * (r >> 2) + 4 * lh2;
-#pragma unroll
-                for (int j = 0; j < TN; ++j) {
-                    const int col = j0 + wn * (32 * TN) + 32 * j + li2;
-                    a.dw[((size_t)row * Cl + (col & (Cl - 1))) * 16 + (col >> a.lgCl)] = acc[i][j][r];
-                }
-            }
-        return;
-    }
-    float* const out = a.slab + (size_t)bz * a.Cs * N;
-#pragma unroll
-    for (int i = 0; i < TM; ++i)
-#pragma unroll
-        for (int r = 0; r < 16; ++r) {
-            const int row = i0 + wm * (32 * TM) + 32 * i + (r & 3) + 8 * (r >> 2) + 4 * lh2;
-#pragma unroll
-            for (int j = 0; j < TN; ++j)
-                out[(size_t)row * N + j0 + wn * (32 * TN) + 32 * j + li2] = acc[i][j][r];
-        }
+    wgrad_tail<BM, BN, WM, WN>(a, reinterpret_cast<float*>(smem), bias_blk, bsum, i0, j0, bz, acc);
 }
 
 void launch_wgrad16(bool small, const WgradArgs& a, dim3 grid, hipStream_t st, hipEvent_t e0, hipEvent_t e1) {

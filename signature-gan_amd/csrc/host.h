@@ -26,3 +26,5 @@ struct DevGuard {
 };
 
 static inline unsigned blocks(int64_t n) { return (unsigned)((n + 255) / 256); }
+// ceil(log2(v)); the extents it is used on are powers of two
+static inline int ilog2(int v) { int l = 0; while ((1 << l) < v) ++l; return l; }

@@ -58,7 +58,6 @@ static const int64_t PARTIAL_FLOATS = (int64_t)2 << 20;   // each of the three r
     DevGuard dg_((c)->cfg.device);                                    \
     HIPCHK(dg_.err)
 
-static int ilog2i(int v) { int l = 0; while ((1 << l) < v) ++l; return l; }
 
 // ------------------------------------------------------------------------------------------
 // RCCL (the collective of the data-parallel step).  The library does not link librccl: the
@@ -811,7 +810,7 @@ static GConvArgs gconv_args(const siggan_ctx* c, int form, int B, int h_in, int 
     const int h_small = form == 0 ? h_in / 2 : h_in;
     a.form = form; a.B = B; a.Hi = a.Wi = h_in; a.Ci = c_in; a.Co = c_out;
     a.Ho = a.Wo = form == 0 ? h_in / 2 : 2 * h_in;
-    a.lgHr = a.lgWr = ilog2i(h_small); a.M = B * h_small * h_small;
+    a.lgHr = a.lgWr = ilog2(h_small); a.M = B * h_small * h_small;
     return a;
 }
 // ... and of its weight gradient: small [B][h_small]^2[c_small] x large [B][2 h_small]^2[c_large] -> dw, split over the pixels
@@ -823,7 +822,7 @@ static WgradCall wgrad_args(const siggan_ctx* c, const void* small, const void* 
     WgradArgs& w = g.w;
     w.zeros = c->zeros; w.dt = c->dt;
     w.S = small; w.L = large; w.slab = slab; w.dw = dw; w.B = B; w.Cs = c_small; w.Cl = c_large;
-    w.lgHs = w.lgWs = ilog2i(h_small); w.lgCl = ilog2i(c_large); w.K = B * h_small * h_small;
+    w.lgHs = w.lgWs = ilog2(h_small); w.lgCl = ilog2(c_large); w.K = B * h_small * h_small;
     g.max_splits = (int)(c->slab_floats / ((int64_t)c_small * (16 * c_large + 1)));
     return g;
 }
