@@ -1,5 +1,5 @@
 """ctypes binding of the C ABI in include/siggan.h (and siggan_mlp.h, siggan_verifier.h, siggan_verifier_grad.h, siggan_verifier_pairs.h, siggan_verifier_topk.h,
-siggan_verifier_train.h, siggan_verifier_data.h, siggan_moments.h, siggan_select.h, siggan_neighbors.h, siggan_resize.h, siggan_components.h).
+siggan_verifier_train.h, siggan_verifier_data.h, siggan_moments.h, siggan_select.h, siggan_neighbors.h, siggan_resize.h, siggan_components.h, siggan_ssim.h).
 
 The shared library is built in-tree by ``__graft_entry__.build()`` / ``csrc/Makefile`` and must be
 present: there is no CPU or PyTorch fallback for this path -- a missing or stale library raises.
@@ -280,6 +280,17 @@ _COMPONENTS_SIGNATURES = {
 }
 COMPONENTS_EXPORTS = tuple(_COMPONENTS_SIGNATURES)
 
+# single-scale SSIM between byte images (include/siggan_ssim.h): context-free, new symbols again
+SSIM_TAPS, SSIM_SIGMA, SSIM_MIN_HEIGHT, SSIM_MIN_WIDTH, SSIM_MAX_SIZE = 11, 1.5, 11, 12, 128
+SSIM_ALL, SSIM_SAME_SET, SSIM_PAIRED = 0, 1, 2
+_SSIM_SIGNATURES = {
+    "siggan_ssim_window": (C.c_int, [C.POINTER(C.c_float)]),
+    "siggan_ssim_maps_bytes": (_I64, [_I32, _I32, _I32]),
+    "siggan_ssim_prepare_u8": (C.c_int, [_I32, _P, _I32, _I32, _I32, _P, _P]),
+    "siggan_ssim_pairs": (C.c_int, [_I32, _P, _P, _I32, _P, _P, _I32, _I32, _I32, _I32, _P, _P, _P, _P]),
+}
+SSIM_EXPORTS = tuple(_SSIM_SIGNATURES)
+
 _lib = None
 
 
@@ -296,7 +307,7 @@ def load():
     for name, (res, args) in {**_SIGNATURES, **_VERIFIER_SIGNATURES, **_VERIFIER_GRAD_SIGNATURES, **_VERIFIER_PAIRS_SIGNATURES,
                               **_VERIFIER_TOPK_SIGNATURES, **_VERIFIER_TRAIN_SIGNATURES,
                               **_VERIFIER_DATA_SIGNATURES, **_MOMENTS_SIGNATURES, **_SELECT_SIGNATURES,
-                              **_NEIGHBORS_SIGNATURES, **_RESIZE_SIGNATURES, **_COMPONENTS_SIGNATURES}.items():
+                              **_NEIGHBORS_SIGNATURES, **_RESIZE_SIGNATURES, **_COMPONENTS_SIGNATURES, **_SSIM_SIGNATURES}.items():
         fn = getattr(lib, name)          # AttributeError if the library does not export the symbol
         fn.restype, fn.argtypes = res, args
     if lib.siggan_abi_version() != ABI_VERSION:

@@ -37,8 +37,9 @@ from .resize import resize_f32, resize_u8
 from .train_vanilla_gan_signatures import save_sample_grid
 from .utils.inference import load_generator_and_config
 from .utils.frechet import FeatureMoments, embedding_spread, frechet_distance
-from .utils.metrics import (INCEPTION_AVAILABLE, LPIPS_AVAILABLE, calculate_fid, calculate_foreground_ratio,
-                            calculate_lpips_diversity, calculate_stroke_density, foreground_ratio_from_counts,
+from .utils.metrics import (INCEPTION_AVAILABLE, LPIPS_AVAILABLE, SSIM_DIVERSITY_IMAGES, calculate_fid, calculate_foreground_ratio,
+                            calculate_lpips_diversity, calculate_ssim_diversity, calculate_ssim_nearest_real,
+                            calculate_stroke_density, foreground_ratio_from_counts,
                             fragmentation_from_counters, stroke_density_from_counts, verifier_embedding_chunks)
 from .utils.neighbors import manifold_metrics
 
@@ -158,15 +159,29 @@ class ComponentSink:
         return torch.cat(self.parts).cpu().numpy() if self.parts else np.zeros((0, 9), np.int32)
 
 
+class SsimSink:
+    """Keeps the bytes of every uint8 batch it is shown, on the device (--ssim): the pixel-space comparisons need the whole set
+    at once.  ``images()``: all of them, uint8 (N, H, W)."""
+
+    def __init__(self) -> None:
+        self.parts = []
+
+    def update(self, u8: torch.Tensor) -> None:
+        self.parts.append(u8.reshape(u8.shape[0], u8.shape[-2], u8.shape[-1]).clone())
+
+    def images(self) -> Optional[torch.Tensor]:
+        return torch.cat(self.parts).contiguous() if self.parts else None
+
+
 @torch.no_grad()
 def generate_samples(generator: Generator, n_samples: int, latent_dim: int, device: torch.device, batch_size: int = 64,
                      keep_images: Optional[int] = None, threshold: float = THRESHOLD,
                      embedding_sink: Optional[EmbeddingSink] = None,
-                     component_sink: Optional[ComponentSink] = None) -> GeneratedSamples:
+                     component_sink: Optional[ComponentSink] = None, ssim_sink: Optional[SsimSink] = None) -> GeneratedSamples:
     """N samples, z = torch.randn per batch as the reference draws it (so a seed means the same).  ``keep_images``: how
     many leading samples to bring back as fp32 images (None: all, what the reference returns).  ``embedding_sink``: receives
     every batch's uint8 tensor while it is on the device; its finished statistics travel in the result.  ``component_sink``:
-    is shown the same bytes and keeps their component counters."""
+    is shown the same bytes and keeps their component counters; ``ssim_sink`` keeps the bytes themselves."""
     generator.eval()
     eng = generator._require_engine()
     keep = n_samples if keep_images is None else max(0, min(int(keep_images), n_samples))
@@ -187,6 +202,8 @@ def generate_samples(generator: Generator, n_samples: int, latent_dim: int, devi
             embedding_sink.update(u8)
         if component_sink is not None:
             component_sink.update(u8)
+        if ssim_sink is not None:
+            ssim_sink.update(u8)
         if (i + 1) % 10 == 0 or i == n_batches - 1:
             print(f"  Generated {min((i + 1) * batch_size, n_samples)}/{n_samples} samples")
     s = generator.output_size
@@ -203,12 +220,14 @@ def generate_samples(generator: Generator, n_samples: int, latent_dim: int, devi
 
 
 def load_real_images(real_dir: Path, n_images: int, image_size: int, device: torch.device,
-                     verifier_size: Optional[int] = None, component_sink: Optional[ComponentSink] = None):
+                     verifier_size: Optional[int] = None, component_sink: Optional[ComponentSink] = None,
+                     ssim_sink: Optional[SsimSink] = None):
     """Up to ``n_images`` files of ``real_dir`` as (N, 1, S, S) fp32 in [-1, 1] ON THE DEVICE: decoded and resized by the
     loader's helper (PIL -> 'L' -> bilinear), normalised by its byte table in the input-pipeline kernel.
     ``verifier_size``: -> (that tensor, the SAME files decoded at verifier_size as uint8 (N, V, V) on the device) -- what the
     reference's verifier sees of a real file, which it resizes from the file and not from a 128x128 copy.
-    ``component_sink``: is shown the decoded BYTES (the cache the normalisation reads), not a re-quantised fp32 copy."""
+    ``component_sink`` / ``ssim_sink``: are shown the decoded BYTES (the cache the normalisation reads), not a re-quantised
+    fp32 copy."""
     from . import _lib
     real_dir = Path(real_dir)
     if not real_dir.exists():
@@ -240,6 +259,8 @@ def load_real_images(real_dir: Path, n_images: int, image_size: int, device: tor
     cache = torch.from_numpy(np.stack(decoded)).to(dev)
     if component_sink is not None:
         component_sink.update(cache)
+    if ssim_sink is not None:
+        ssim_sink.update(cache)
     index = torch.arange(n, dtype=torch.int32, device=dev)
     lut = normalize_lut((-1.0, 1.0)).to(dev)
     out = torch.empty(n, 1, image_size, image_size, dtype=torch.float32, device=dev)
@@ -348,13 +369,15 @@ def _verifier_neighbors(metrics: Dict[str, Any], fake_images, real_embeddings: O
 
 def compute_metrics(fake_images, real_images: Optional[torch.Tensor], device: torch.device,
                     verifier: Optional[VerifierFeatures] = None, neighbors_k: Optional[int] = None,
-                    verifier_real: Optional[torch.Tensor] = None, fragmentation: Optional[Dict[str, Any]] = None) -> Dict[str, Any]:
+                    verifier_real: Optional[torch.Tensor] = None, fragmentation: Optional[Dict[str, Any]] = None,
+                    pixel_similarity: Optional[Dict[str, Any]] = None) -> Dict[str, Any]:
     """The report's ``metrics`` dictionary.  ``fake_images``: a GeneratedSamples (its counters are used) or a tensor.
     ``verifier``: add the Frechet distance over its embeddings (the ``verifier_*`` keys; none without it).
     ``verifier_real``: the real set as the verifier is to see it when that is not ``real_images`` (a 128x128 Generator: the
     files decoded at 64x64, load_real_images' second result); the pixel-space metrics keep ``real_images``.
     ``neighbors_k``: add precision / recall, density / coverage and the nearest-real distances at that k.
-    ``fragmentation``: the finished ``fragmentation`` block (fragmentation_block), added as it is; no key without it."""
+    ``fragmentation``: the finished ``fragmentation`` block (fragmentation_block), added as it is; no key without it.
+    ``pixel_similarity``: likewise the finished ``pixel_similarity`` block (pixel_similarity_block)."""
     metrics: Dict[str, Any] = {"n_samples": len(fake_images), "image_shape": list(fake_images.shape[1:]),
                                "metrics_computed_at": datetime.now().isoformat()}
     if real_images is not None and INCEPTION_AVAILABLE:
@@ -419,7 +442,31 @@ def compute_metrics(fake_images, real_images: Optional[torch.Tensor], device: to
         metrics["fragmentation"] = fragmentation
         g = fragmentation["generated"]
         print(f"  Ink components per image - Mean: {g['components_mean']:.2f}, speckle ink ratio: {g['speckle_ink_ratio']:.4f}")
+    if pixel_similarity is not None:
+        metrics["pixel_similarity"] = pixel_similarity
+        print(f"  SSIM diversity (1 - mean pairwise SSIM): {_fmt(pixel_similarity['generated_diversity']['all_pairs']['diversity'])}")
     return metrics
+
+
+def _fmt(v: Optional[float]) -> str:
+    return "n/a" if v is None else format(v, ".4f")
+
+
+def pixel_similarity_block(generated: SsimSink, real: Optional[SsimSink] = None) -> Dict[str, Any]:
+    """The report's ``pixel_similarity`` key (--ssim): {window, generated_diversity, and with a real set real_diversity and
+    nearest_real}.  Diversity: utils.metrics.calculate_ssim_diversity over at most the set's first 512 images; nearest_real:
+    calculate_ssim_nearest_real over every generated and every real image.  Each set is prepared once."""
+    from .ssim import WINDOW_SIGMA, WINDOW_TAPS, SsimSet, window
+    fake = SsimSet(generated.images())
+    block: Dict[str, Any] = {"window": {"taps": WINDOW_TAPS, "sigma": WINDOW_SIGMA, "weights": [float(v) for v in window()],
+                                        "dynamic_range": 255, "valid_positions_only": True},
+                             "diversity_images": SSIM_DIVERSITY_IMAGES,
+                             "generated_diversity": calculate_ssim_diversity(fake)}
+    if real is not None and real.parts:
+        true = SsimSet(real.images())
+        block["real_diversity"] = calculate_ssim_diversity(true)
+        block["nearest_real"] = calculate_ssim_nearest_real(fake, true)
+    return block
 
 
 def fragmentation_block(generated: ComponentSink, real: Optional[ComponentSink] = None) -> Dict[str, Any]:
@@ -466,6 +513,18 @@ def print_summary(metrics: Dict[str, Any]) -> None:
           else f"FID Score: Not computed - {metrics.get('fid_error', 'unknown reason')}")
     print(f"LPIPS Diversity: {lp:.4f} (higher = more diverse)" if lp is not None
           else f"LPIPS Diversity: Not computed - {metrics.get('lpips_error', 'unknown reason')}")
+    if "pixel_similarity" in metrics:
+        ps = metrics["pixel_similarity"]
+        g = ps["generated_diversity"]
+        line = (f"SSIM Diversity: {_fmt(g['all_pairs']['diversity'])} (1 - mean pairwise SSIM over {g['n']} images, higher = more "
+                f"diverse; {_fmt(g['lpips_pairs']['diversity'])} on the LPIPS pair set)")
+        if "real_diversity" in ps:
+            line += f"; real set: {_fmt(ps['real_diversity']['all_pairs']['diversity'])}"
+        print(line)
+        if "nearest_real" in ps:
+            nr = ps["nearest_real"]
+            print(f"SSIM to the nearest real image: median {nr['median']:.4f}, max {nr['max']:.4f} (real leave-one-out median "
+                  f"{_fmt(nr['real_loo_median'])}, excess {_fmt(nr['excess_median'])}; clearly positive = memorisation warning)")
     if "verifier_frechet_distance" in metrics:
         vfd = metrics["verifier_frechet_distance"]
         print(f"Verifier Frechet Distance: {vfd:.4f} (lower is better)" if vfd is not None
@@ -517,6 +576,7 @@ class _Args(argparse.Namespace):
     verifier_checkpoint = None
     verifier_neighbors = None
     components = None
+    ssim = False
 
 
 def parse_args(argv=None) -> argparse.Namespace:
@@ -540,6 +600,10 @@ def parse_args(argv=None) -> argparse.Namespace:
                    help="Label the ink components of every generated (and real) image on the device and add a 'fragmentation' "
                         "block to the report; a component of fewer than MIN_AREA pixels counts as a speck "
                         "(MIN_AREA omitted: max(2, round(0.001 * H * W)))")
+    p.add_argument("--ssim", action="store_true", default=argparse.SUPPRESS,
+                   help="Add a 'pixel_similarity' block to the report: mean pairwise SSIM of the generated set (and of the real set) as "
+                        "a diversity measure, and every generated image's highest SSIM to a real one against the real set's own "
+                        "leave-one-out values; computed on the device, needs no network weights")
     a = p.parse_args(argv, namespace=_Args())
     if a.components is not None and a.components != "auto" and a.components < 1:
         p.error("--components MIN_AREA must be >= 1")
@@ -564,9 +628,11 @@ def main(argv=None) -> int:
         if a.components is not None:
             min_area = None if a.components == "auto" else a.components
             frag_fake, frag_real = ComponentSink(min_area), ComponentSink(min_area)
+        ssim_fake, ssim_real = (SsimSink(), SsimSink()) if a.ssim else (None, None)
         fake = generate_samples(generator, a.n_samples, generator.latent_dim, device, a.batch_size,
                                 keep_images=max(0, a.n_grids) * a.grid_size,
-                                embedding_sink=verifier.sink() if verifier is not None else None, component_sink=frag_fake)
+                                embedding_sink=verifier.sink() if verifier is not None else None, component_sink=frag_fake,
+                                ssim_sink=ssim_fake)
         print("\nCreating sample grids...")
         grid_paths = create_sample_grids(fake, output_dir, a.n_grids, a.grid_size)
         real = verifier_real = None
@@ -574,14 +640,16 @@ def main(argv=None) -> int:
             try:
                 if verifier is not None and verifier.input_resize is not None:
                     real, verifier_real = load_real_images(real_dir, a.n_samples, generator.output_size, device, VERIFIER_IMAGE_SIZE,
-                                                           component_sink=frag_real)
+                                                           component_sink=frag_real, ssim_sink=ssim_real)
                 else:
-                    real = load_real_images(real_dir, a.n_samples, generator.output_size, device, component_sink=frag_real)
+                    real = load_real_images(real_dir, a.n_samples, generator.output_size, device, component_sink=frag_real,
+                                            ssim_sink=ssim_real)
             except Exception as e:                              # noqa: BLE001 -- the evaluation goes on without them
                 print(f"Warning: Could not load real images: {e}")
         print("\nComputing evaluation metrics...")
         metrics = compute_metrics(fake, real, device, verifier, a.verifier_neighbors, verifier_real,
-                                  fragmentation_block(frag_fake, frag_real) if frag_fake is not None else None)
+                                  fragmentation_block(frag_fake, frag_real) if frag_fake is not None else None,
+                                  pixel_similarity_block(ssim_fake, ssim_real) if a.ssim else None)
         report_path = save_evaluation_report(metrics, config, output_dir, checkpoint_path, grid_paths)
         print_summary(metrics)
         print("\nEvaluation complete!")

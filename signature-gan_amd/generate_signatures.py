@@ -143,13 +143,15 @@ def generate_refined(generator, discriminator, n_samples: int, output_dir: str, 
 def run_projection(generator, path: str, output_dir: str, prefix: str = "signature", steps: int = 200, lr: float = 0.05,
                    restarts: int = 1, seed: Optional[int] = None, discriminator=None, realism_weight: float = 0.0,
                    prior_weight: float = 0.0, verifier=None, identity_weight: float = 0.0,
-                   identity_score_weight: float = 0.0, verifier_resize: bool = False) -> None:
+                   identity_score_weight: float = 0.0, verifier_resize: bool = False, project_ssim: bool = False) -> None:
     """Reconstructions of the image file / the images of the directory ``path``: ``<prefix>_projection_%06d.png`` each, and
     ``<prefix>_projection.json``: [{file, reconstruction, loss, z}, ...] in the same order; with ``realism_weight`` > 0 every
     record also holds ``realism``, the Discriminator's score of the reconstruction.  With a ``verifier`` every record holds
     ``identity``: {embedding_distance, verifier_score} of G(z) against the target at the returned z, and
     ``identity_pixel_only``: the same two numbers for the projection without the identity term (what the term bought).
-    ``verifier_resize``: the verifier reads targets and reconstructions through the device resize to 64x64 (a 128x128 Generator)."""
+    ``verifier_resize``: the verifier reads targets and reconstructions through the device resize to 64x64 (a 128x128 Generator).
+    ``project_ssim``: every record also holds ``ssim``, the structural similarity (ssim.ssim_paired) of the target's bytes and
+    the reconstruction's bytes as written."""
     from PIL import Image
     os.makedirs(output_dir, exist_ok=True)
     files, targets = load_target_images(path, generator.output_size)
@@ -168,6 +170,11 @@ def run_projection(generator, path: str, output_dir: str, prefix: str = "signatu
     if realism_weight > 0:
         mb = generator._require_engine().max_batch
         realism = torch.cat([discriminator.score_u8(torch.from_numpy(recon[i:i + mb]).to(z.device)) for i in range(0, len(recon), mb)]).cpu()
+    similarity = None
+    if project_ssim:
+        from .ssim import ssim_paired
+        similarity = ssim_paired(torch.as_tensor(targets).to(z.device).contiguous(),
+                                 torch.from_numpy(recon).to(z.device).contiguous()).cpu()
     z, loss = z.cpu(), loss.cpu()
     records = []
     for i, name in enumerate(files):
@@ -179,6 +186,8 @@ def run_projection(generator, path: str, output_dir: str, prefix: str = "signatu
         if identity is not None:
             records[-1]["identity"] = identity[i]
             records[-1]["identity_pixel_only"] = pixel_only[i]
+        if similarity is not None:
+            records[-1]["ssim"] = float(similarity[i])
     with open(os.path.join(output_dir, f"{prefix}_projection.json"), "w") as f:
         json.dump(records, f, indent=2)
     print(f"Reconstruction loss (mean squared error in [-1, 1]): best {float(loss.min()):.3e}, worst {float(loss.max()):.3e}")
@@ -325,6 +334,14 @@ def despeckle_opt(a: argparse.Namespace) -> Optional[Despeckle]:
     return Despeckle(None if v == "auto" else v, 128 if a.threshold is None else a.threshold)
 
 
+# --project_ssim, kept out of the namespace the same way
+PROJECT_SSIM_DEFAULTS = dict(project_ssim=False)
+
+
+def project_ssim_opt(a: argparse.Namespace) -> bool:
+    return getattr(a, "project_ssim", PROJECT_SSIM_DEFAULTS["project_ssim"])
+
+
 def identity_opt(a: argparse.Namespace, name: str):
     """A flag of IDENTITY_DEFAULTS: its value on the command line, else its default."""
     return getattr(a, name, IDENTITY_DEFAULTS[name])
@@ -402,7 +419,12 @@ def parse_args(argv=None) -> argparse.Namespace:
                    help="Remove ink components of fewer than MIN_AREA pixels from every generated signature before it is scored and "
                         "written (MIN_AREA omitted: max(2, round(0.001 * H * W))); ink is byte < --threshold, 128 without it "
                         "(default: off)")
+    p.add_argument("--project_ssim", action="store_true", **later,
+                   help="With --project: record every reconstruction's structural similarity (SSIM, 11-tap Gaussian window, computed "
+                        "on the device) to its target in <prefix>_projection.json (default: off)")
     a = p.parse_args(argv)
+    if hasattr(a, "project_ssim") and a.project is None:
+        p.error("--project_ssim needs --project")
     if hasattr(a, "despeckle"):
         if a.project is not None or a.morph is not None:
             p.error("--despeckle cleans generated signatures; projections and morph strips are left alone")
@@ -502,7 +524,8 @@ def main(argv=None) -> None:
                 verifier = load_model(identity_opt(a, "verifier_checkpoint"), device)[0]
             run_projection(generator, a.project, a.output_dir, a.prefix, a.project_steps, a.project_lr, a.project_restarts, a.seed,
                            discriminator, w_d, w_p, verifier, identity_opt(a, "project_identity_weight"),
-                           identity_opt(a, "project_identity_score_weight"), identity_opt(a, "project_identity_resize"))
+                           identity_opt(a, "project_identity_score_weight"), identity_opt(a, "project_identity_resize"),
+                           project_ssim_opt(a))
         if a.morph is not None:
             run_morph(generator, a.morph, a.output_dir, device, a.prefix, a.morph_frames, a.seed, a.threshold, a.transparent,
                       a.project_steps, a.project_lr, a.project_restarts)

@@ -225,6 +225,49 @@ def calculate_fragmentation(images: torch.Tensor, threshold: int = 128, connecti
     return fragmentation_from_counters(component_stats(images.contiguous(), threshold, connectivity, min_area).cpu().numpy())
 
 
+# ---- pixel-space similarity: SSIM (ssim.py) ---------------------------------------------------------------------------------
+SSIM_DIVERSITY_IMAGES = 512           # a set's diversity is taken over at most its first 512 images (131 k pairs)
+
+
+def _ssim_set(images, what: str):
+    """An ssim.SsimSet of ``images``: one as it is; uint8 (N, S, S) / (N, 1, S, S) or fp32 in [-1, 1], quantised by the generation
+    rule first, moved to the device when it is not there."""
+    from ..ssim import SsimSet
+    if isinstance(images, SsimSet):
+        return images
+    if not isinstance(images, torch.Tensor):
+        raise ValueError(f"{what} must be a tensor, got {type(images).__name__}")
+    if images.device.type != "cuda":
+        if not torch.cuda.is_available():
+            raise RuntimeError("SSIM is computed on a ROCm device ('cuda:N'); there is no CPU path")
+        images = images.cuda()
+    if images.dtype != torch.uint8:
+        images = quantize_generated(images)
+    return SsimSet(images.contiguous())
+
+
+def calculate_ssim_diversity(images, max_images: int = SSIM_DIVERSITY_IMAGES) -> Dict[str, Any]:
+    """Mean pairwise SSIM of a set and 1 - mean (higher = more diverse, the direction of LPIPS), over at most its first
+    ``max_images`` images: ssim.ssim_diversity of the set's own matrix, which is formed on the device.  A pixel-space measure
+    that needs no network weights."""
+    from ..ssim import SsimSet, ssim_diversity, ssim_matrix
+    s = _ssim_set(images, "images")
+    if s.n > max_images:
+        s = SsimSet(s.u8[:max_images])
+    return ssim_diversity(ssim_matrix(s).cpu().numpy())
+
+
+def calculate_ssim_nearest_real(generated, real) -> Dict[str, Any]:
+    """Each generated image's highest SSIM to a real one against the real set's own leave-one-out values
+    (ssim.nearest_real_from_best): the memorisation check in pixel space.  Only one value and one index per image leave the
+    device; no matrix is formed."""
+    from ..ssim import nearest_real_from_best, ssim_best
+    g, r = _ssim_set(generated, "generated"), _ssim_set(real, "real")
+    best, index = ssim_best(g, r)
+    loo = ssim_best(r)[0].cpu().numpy() if r.n >= 2 else None
+    return nearest_real_from_best(best.cpu().numpy(), index.cpu().numpy(), loo)
+
+
 class MetricsTracker:
     """Per-epoch running values and the history of their epoch averages (utils/metrics.py:177-213)."""
 
