@@ -1,5 +1,5 @@
 """ctypes binding of the C ABI in include/siggan.h (and siggan_mlp.h, siggan_verifier.h, siggan_verifier_grad.h, siggan_verifier_pairs.h, siggan_verifier_topk.h,
-siggan_verifier_train.h, siggan_verifier_data.h, siggan_moments.h, siggan_select.h, siggan_neighbors.h, siggan_resize.h, siggan_components.h, siggan_ssim.h).
+siggan_verifier_train.h, siggan_verifier_data.h, siggan_moments.h, siggan_select.h, siggan_neighbors.h, siggan_resize.h, siggan_components.h, siggan_ssim.h, siggan_strokes.h).
 
 The shared library is built in-tree by ``__graft_entry__.build()`` / ``csrc/Makefile`` and must be
 present: there is no CPU or PyTorch fallback for this path -- a missing or stale library raises.
@@ -291,6 +291,13 @@ _SSIM_SIGNATURES = {
 }
 SSIM_EXPORTS = tuple(_SSIM_SIGNATURES)
 
+# stroke geometry of byte images (include/siggan_strokes.h): context-free, one more symbol
+SK_MAX_SIZE, SK_WIDTH_BINS, SK_MAX_RADIUS2, SK_COUNT = 128, 16, 36, 23
+_STROKES_SIGNATURES = {
+    "siggan_strokes_u8": (C.c_int, [_I32, _P, _I32, _I32, _I32, _I32, _I32, _I32, _I32, _P, _P, _P, _P, _P]),
+}
+STROKES_EXPORTS = tuple(_STROKES_SIGNATURES)
+
 _lib = None
 
 
@@ -307,7 +314,8 @@ def load():
     for name, (res, args) in {**_SIGNATURES, **_VERIFIER_SIGNATURES, **_VERIFIER_GRAD_SIGNATURES, **_VERIFIER_PAIRS_SIGNATURES,
                               **_VERIFIER_TOPK_SIGNATURES, **_VERIFIER_TRAIN_SIGNATURES,
                               **_VERIFIER_DATA_SIGNATURES, **_MOMENTS_SIGNATURES, **_SELECT_SIGNATURES,
-                              **_NEIGHBORS_SIGNATURES, **_RESIZE_SIGNATURES, **_COMPONENTS_SIGNATURES, **_SSIM_SIGNATURES}.items():
+                              **_NEIGHBORS_SIGNATURES, **_RESIZE_SIGNATURES, **_COMPONENTS_SIGNATURES, **_SSIM_SIGNATURES,
+                              **_STROKES_SIGNATURES}.items():
         fn = getattr(lib, name)          # AttributeError if the library does not export the symbol
         fn.restype, fn.argtypes = res, args
     if lib.siggan_abi_version() != ABI_VERSION:

@@ -20,6 +20,9 @@ device buffer, and exact fp64 k-nearest-neighbour queries run there (utils/neigh
 host.  A 128x128 Generator's bytes are shrunk to the verifier's 64x64 on the device first (resize.py: Pillow's antialiased
 bilinear filter, byte for byte what the reference's verifier transform makes of the written PNG), the real files are
 decoded at 64x64 for the verifier, and the report says so in ``verifier_input_resize``.
+``--strokes`` adds the report key ``stroke_geometry``: skeleton length, line ends, junction pixels and a histogram of local
+pen widths of the generated images (and of the real ones, under the same condition as ``fragmentation``), from a thinning and
+an exact distance map of the bytes already on the device (strokes.py); 23 counters per image reach the host.
 Without the flags nothing changes: stdout, report keys and exit codes are the reference's."""
 import argparse
 import json
@@ -40,7 +43,8 @@ from .utils.frechet import FeatureMoments, embedding_spread, frechet_distance
 from .utils.metrics import (INCEPTION_AVAILABLE, LPIPS_AVAILABLE, SSIM_DIVERSITY_IMAGES, calculate_fid, calculate_foreground_ratio,
                             calculate_lpips_diversity, calculate_ssim_diversity, calculate_ssim_nearest_real,
                             calculate_stroke_density, foreground_ratio_from_counts,
-                            fragmentation_from_counters, stroke_density_from_counts, verifier_embedding_chunks)
+                            fragmentation_from_counters, stroke_density_from_counts, stroke_geometry_from_counters,
+                            verifier_embedding_chunks)
 from .utils.neighbors import manifold_metrics
 
 THRESHOLD = 0.5          # the threshold compute_metrics passes to both statistics (evaluate_vanilla_gan_signatures.py:306,318)
@@ -159,6 +163,21 @@ class ComponentSink:
         return torch.cat(self.parts).cpu().numpy() if self.parts else np.zeros((0, 9), np.int32)
 
 
+class StrokeSink:
+    """Collects the stroke counters (strokes.stroke_stats, int32 (B, 23)) of every uint8 batch it is shown while the batch is on
+    the device (--strokes); ``counters()`` brings all of them to the host at once."""
+
+    def __init__(self, threshold: int = COMPONENT_THRESHOLD) -> None:
+        self.threshold, self.parts = threshold, []
+
+    def update(self, u8: torch.Tensor) -> None:
+        from .strokes import stroke_stats
+        self.parts.append(stroke_stats(u8.contiguous(), self.threshold))
+
+    def counters(self) -> np.ndarray:
+        return torch.cat(self.parts).cpu().numpy() if self.parts else np.zeros((0, 23), np.int32)
+
+
 class SsimSink:
     """Keeps the bytes of every uint8 batch it is shown, on the device (--ssim): the pixel-space comparisons need the whole set
     at once.  ``images()``: all of them, uint8 (N, H, W)."""
@@ -177,11 +196,13 @@ class SsimSink:
 def generate_samples(generator: Generator, n_samples: int, latent_dim: int, device: torch.device, batch_size: int = 64,
                      keep_images: Optional[int] = None, threshold: float = THRESHOLD,
                      embedding_sink: Optional[EmbeddingSink] = None,
-                     component_sink: Optional[ComponentSink] = None, ssim_sink: Optional[SsimSink] = None) -> GeneratedSamples:
+                     component_sink: Optional[ComponentSink] = None, ssim_sink: Optional[SsimSink] = None,
+                     stroke_sink: Optional[StrokeSink] = None) -> GeneratedSamples:
     """N samples, z = torch.randn per batch as the reference draws it (so a seed means the same).  ``keep_images``: how
     many leading samples to bring back as fp32 images (None: all, what the reference returns).  ``embedding_sink``: receives
     every batch's uint8 tensor while it is on the device; its finished statistics travel in the result.  ``component_sink``:
-    is shown the same bytes and keeps their component counters; ``ssim_sink`` keeps the bytes themselves."""
+    is shown the same bytes and keeps their component counters; ``ssim_sink`` keeps the bytes themselves; ``stroke_sink``
+    keeps their stroke counters."""
     generator.eval()
     eng = generator._require_engine()
     keep = n_samples if keep_images is None else max(0, min(int(keep_images), n_samples))
@@ -204,6 +225,8 @@ def generate_samples(generator: Generator, n_samples: int, latent_dim: int, devi
             component_sink.update(u8)
         if ssim_sink is not None:
             ssim_sink.update(u8)
+        if stroke_sink is not None:
+            stroke_sink.update(u8)
         if (i + 1) % 10 == 0 or i == n_batches - 1:
             print(f"  Generated {min((i + 1) * batch_size, n_samples)}/{n_samples} samples")
     s = generator.output_size
@@ -221,13 +244,13 @@ def generate_samples(generator: Generator, n_samples: int, latent_dim: int, devi
 
 def load_real_images(real_dir: Path, n_images: int, image_size: int, device: torch.device,
                      verifier_size: Optional[int] = None, component_sink: Optional[ComponentSink] = None,
-                     ssim_sink: Optional[SsimSink] = None):
+                     ssim_sink: Optional[SsimSink] = None, stroke_sink: Optional[StrokeSink] = None):
     """Up to ``n_images`` files of ``real_dir`` as (N, 1, S, S) fp32 in [-1, 1] ON THE DEVICE: decoded and resized by the
     loader's helper (PIL -> 'L' -> bilinear), normalised by its byte table in the input-pipeline kernel.
     ``verifier_size``: -> (that tensor, the SAME files decoded at verifier_size as uint8 (N, V, V) on the device) -- what the
     reference's verifier sees of a real file, which it resizes from the file and not from a 128x128 copy.
-    ``component_sink`` / ``ssim_sink``: are shown the decoded BYTES (the cache the normalisation reads), not a re-quantised
-    fp32 copy."""
+    ``component_sink`` / ``ssim_sink`` / ``stroke_sink``: are shown the decoded BYTES (the cache the normalisation reads), not
+    a re-quantised fp32 copy."""
     from . import _lib
     real_dir = Path(real_dir)
     if not real_dir.exists():
@@ -261,6 +284,8 @@ def load_real_images(real_dir: Path, n_images: int, image_size: int, device: tor
         component_sink.update(cache)
     if ssim_sink is not None:
         ssim_sink.update(cache)
+    if stroke_sink is not None:
+        stroke_sink.update(cache)
     index = torch.arange(n, dtype=torch.int32, device=dev)
     lut = normalize_lut((-1.0, 1.0)).to(dev)
     out = torch.empty(n, 1, image_size, image_size, dtype=torch.float32, device=dev)
@@ -370,14 +395,16 @@ def _verifier_neighbors(metrics: Dict[str, Any], fake_images, real_embeddings: O
 def compute_metrics(fake_images, real_images: Optional[torch.Tensor], device: torch.device,
                     verifier: Optional[VerifierFeatures] = None, neighbors_k: Optional[int] = None,
                     verifier_real: Optional[torch.Tensor] = None, fragmentation: Optional[Dict[str, Any]] = None,
-                    pixel_similarity: Optional[Dict[str, Any]] = None) -> Dict[str, Any]:
+                    pixel_similarity: Optional[Dict[str, Any]] = None,
+                    stroke_geometry: Optional[Dict[str, Any]] = None) -> Dict[str, Any]:
     """The report's ``metrics`` dictionary.  ``fake_images``: a GeneratedSamples (its counters are used) or a tensor.
     ``verifier``: add the Frechet distance over its embeddings (the ``verifier_*`` keys; none without it).
     ``verifier_real``: the real set as the verifier is to see it when that is not ``real_images`` (a 128x128 Generator: the
     files decoded at 64x64, load_real_images' second result); the pixel-space metrics keep ``real_images``.
     ``neighbors_k``: add precision / recall, density / coverage and the nearest-real distances at that k.
     ``fragmentation``: the finished ``fragmentation`` block (fragmentation_block), added as it is; no key without it.
-    ``pixel_similarity``: likewise the finished ``pixel_similarity`` block (pixel_similarity_block)."""
+    ``pixel_similarity``: likewise the finished ``pixel_similarity`` block (pixel_similarity_block); ``stroke_geometry``:
+    likewise the finished ``stroke_geometry`` block (stroke_geometry_block)."""
     metrics: Dict[str, Any] = {"n_samples": len(fake_images), "image_shape": list(fake_images.shape[1:]),
                                "metrics_computed_at": datetime.now().isoformat()}
     if real_images is not None and INCEPTION_AVAILABLE:
@@ -445,6 +472,10 @@ def compute_metrics(fake_images, real_images: Optional[torch.Tensor], device: to
     if pixel_similarity is not None:
         metrics["pixel_similarity"] = pixel_similarity
         print(f"  SSIM diversity (1 - mean pairwise SSIM): {_fmt(pixel_similarity['generated_diversity']['all_pairs']['diversity'])}")
+    if stroke_geometry is not None:
+        metrics["stroke_geometry"] = stroke_geometry
+        g = stroke_geometry["generated"]
+        print(f"  Pen width along the skeleton - Mean: {_fmt(g['mean_width'])}, skeleton length: {_fmt(g['skeleton_length']['mean'])}")
     return metrics
 
 
@@ -466,6 +497,15 @@ def pixel_similarity_block(generated: SsimSink, real: Optional[SsimSink] = None)
         true = SsimSet(real.images())
         block["real_diversity"] = calculate_ssim_diversity(true)
         block["nearest_real"] = calculate_ssim_nearest_real(fake, true)
+    return block
+
+
+def stroke_geometry_block(generated: StrokeSink, real: Optional[StrokeSink] = None) -> Dict[str, Any]:
+    """The report's ``stroke_geometry`` key (--strokes): {threshold, generated, real (only when a real set was measured)}, each
+    side a utils.metrics.stroke_geometry_from_counters dictionary."""
+    block: Dict[str, Any] = {"threshold": generated.threshold, "generated": stroke_geometry_from_counters(generated.counters())}
+    if real is not None and real.parts:
+        block["real"] = stroke_geometry_from_counters(real.counters())
     return block
 
 
@@ -567,6 +607,15 @@ def print_summary(metrics: Dict[str, Any]) -> None:
                 print(f"{side.capitalize()}: {d['components_mean']:.2f} components per image (median {d['components_median']:.1f}), "
                       f"{d['small_components_mean']:.2f} specks, speckle ink ratio {d['speckle_ink_ratio']:.4f}, largest component share "
                       f"{'n/a' if share is None else format(share, '.4f')}, {d['empty_images']} empty")
+    if "stroke_geometry" in metrics:
+        sg = metrics["stroke_geometry"]
+        print(f"\n--- Stroke geometry (skeleton and pen width, ink < {sg['threshold']}) ---")
+        for side in ("generated", "real"):
+            if side in sg:
+                d = sg[side]
+                print(f"{side.capitalize()}: pen width {_fmt(d['mean_width'])} px (thickest stroke {_fmt(d['thickest']['mean'])}), skeleton "
+                      f"{_fmt(d['skeleton_length']['mean'])} px, {_fmt(d['endpoints']['mean'])} line ends, "
+                      f"{_fmt(d['junction_pixels']['mean'])} junction pixels, {d['empty']} empty")
     print("\n" + bar)
 
 
@@ -577,6 +626,7 @@ class _Args(argparse.Namespace):
     verifier_neighbors = None
     components = None
     ssim = False
+    strokes = False
 
 
 def parse_args(argv=None) -> argparse.Namespace:
@@ -604,6 +654,10 @@ def parse_args(argv=None) -> argparse.Namespace:
                    help="Add a 'pixel_similarity' block to the report: mean pairwise SSIM of the generated set (and of the real set) as "
                         "a diversity measure, and every generated image's highest SSIM to a real one against the real set's own "
                         "leave-one-out values; computed on the device, needs no network weights")
+    p.add_argument("--strokes", action="store_true", default=argparse.SUPPRESS,
+                   help="Add a 'stroke_geometry' block to the report: skeleton length, line ends, junction pixels and a histogram of "
+                        "local pen widths of every generated (and real) image, from a thinning and an exact distance map computed on "
+                        "the device; needs no network weights")
     a = p.parse_args(argv, namespace=_Args())
     if a.components is not None and a.components != "auto" and a.components < 1:
         p.error("--components MIN_AREA must be >= 1")
@@ -629,10 +683,11 @@ def main(argv=None) -> int:
             min_area = None if a.components == "auto" else a.components
             frag_fake, frag_real = ComponentSink(min_area), ComponentSink(min_area)
         ssim_fake, ssim_real = (SsimSink(), SsimSink()) if a.ssim else (None, None)
+        stroke_fake, stroke_real = (StrokeSink(), StrokeSink()) if a.strokes else (None, None)
         fake = generate_samples(generator, a.n_samples, generator.latent_dim, device, a.batch_size,
                                 keep_images=max(0, a.n_grids) * a.grid_size,
                                 embedding_sink=verifier.sink() if verifier is not None else None, component_sink=frag_fake,
-                                ssim_sink=ssim_fake)
+                                ssim_sink=ssim_fake, stroke_sink=stroke_fake)
         print("\nCreating sample grids...")
         grid_paths = create_sample_grids(fake, output_dir, a.n_grids, a.grid_size)
         real = verifier_real = None
@@ -640,16 +695,18 @@ def main(argv=None) -> int:
             try:
                 if verifier is not None and verifier.input_resize is not None:
                     real, verifier_real = load_real_images(real_dir, a.n_samples, generator.output_size, device, VERIFIER_IMAGE_SIZE,
-                                                           component_sink=frag_real, ssim_sink=ssim_real)
+                                                           component_sink=frag_real, ssim_sink=ssim_real,
+                                                           stroke_sink=stroke_real)
                 else:
                     real = load_real_images(real_dir, a.n_samples, generator.output_size, device, component_sink=frag_real,
-                                            ssim_sink=ssim_real)
+                                            ssim_sink=ssim_real, stroke_sink=stroke_real)
             except Exception as e:                              # noqa: BLE001 -- the evaluation goes on without them
                 print(f"Warning: Could not load real images: {e}")
         print("\nComputing evaluation metrics...")
         metrics = compute_metrics(fake, real, device, verifier, a.verifier_neighbors, verifier_real,
                                   fragmentation_block(frag_fake, frag_real) if frag_fake is not None else None,
-                                  pixel_similarity_block(ssim_fake, ssim_real) if a.ssim else None)
+                                  pixel_similarity_block(ssim_fake, ssim_real) if a.ssim else None,
+                                  stroke_geometry_block(stroke_fake, stroke_real) if a.strokes else None)
         report_path = save_evaluation_report(metrics, config, output_dir, checkpoint_path, grid_paths)
         print_summary(metrics)
         print("\nEvaluation complete!")

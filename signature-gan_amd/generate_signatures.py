@@ -27,7 +27,13 @@ byte stays.  It applies to the plain run, ``--filter_by_realism`` (the pool is c
 to the file it stands beside), ``--refine_by_realism`` and ``--adapt``; projections and morph strips are left alone.  What
 was removed is recorded as ``despeckle: {min_area, threshold, connectivity, removed_components, removed_pixels}``: in
 ``<prefix>_despeckle.json`` for a plain run, as a key of ``<prefix>_adapt.json``, and in ``<prefix>_scores.json`` /
-``<prefix>_refine.json``, which then are ``{"despeckle": {...}, "records": [...]}`` instead of the bare list."""
+``<prefix>_refine.json``, which then are ``{"despeckle": {...}, "records": [...]}`` instead of the bare list.
+
+``--pen_width W`` (1..9; the plain run only) redraws every generated signature at one pen width on the device before it is
+written (strokes.restroke_u8): the image is thinned to its centre line (ink is byte < ``--threshold``, 128 without it) and the
+line is drawn again, ink 0 on paper 255, with a disc of squared radius (W - 1)^2 // 4.  ``--despeckle`` given as well runs
+first.  ``<prefix>_pen_width.json`` records W, the radius, the threshold and the mean pen width along the centre line before
+and after."""
 import argparse
 import json
 import os
@@ -37,7 +43,7 @@ from typing import Any, Dict, Optional
 import numpy as np
 import torch
 
-from .utils.inference import (Despeckle, generate_signatures_batch, generate_signatures_filtered, generate_signatures_refined,
+from .utils.inference import (Despeckle, PenWidth, generate_signatures_batch, generate_signatures_filtered, generate_signatures_refined,
                               load_discriminator, load_generator, load_target_images, morph_sequence, morph_strip, process_images,
                               project_signatures)
 
@@ -45,13 +51,14 @@ from .utils.inference import (Despeckle, generate_signatures_batch, generate_sig
 def generate_signatures(generator, n_samples: int, output_dir: str, batch_size: int = 64,
                         device: torch.device = torch.device("cuda"), seed: Optional[int] = None,
                         prefix: str = "signature", noise_scale: float = 1.0, threshold: Optional[int] = None,
-                        transparent: bool = False, despeckle: Optional[Despeckle] = None) -> None:
+                        transparent: bool = False, despeckle: Optional[Despeckle] = None,
+                        pen_width: Optional[PenWidth] = None) -> None:
     os.makedirs(output_dir, exist_ok=True)
     print(f"Output directory: {output_dir}")
     print(f"Generating {n_samples} signatures...")
     images = generate_signatures_batch(generator=generator, n_samples=n_samples, latent_dim=generator.latent_dim,
                                        device=device, seed=seed, batch_size=batch_size, noise_scale=noise_scale,
-                                       **with_despeckle(despeckle))
+                                       **with_despeckle(despeckle), **with_pen_width(pen_width))
     if threshold is not None:
         images = process_images(images, threshold=threshold, make_transparent=transparent)
     print(f"Saving {len(images)} images...")
@@ -61,6 +68,12 @@ def generate_signatures(generator, n_samples: int, output_dir: str, batch_size: 
         with open(os.path.join(output_dir, f"{prefix}_despeckle.json"), "w") as f:
             json.dump({"despeckle": despeckle.report()}, f, indent=2)
         print_despeckle(despeckle)
+    if pen_width is not None:
+        r = pen_width.report()
+        with open(os.path.join(output_dir, f"{prefix}_pen_width.json"), "w") as f:
+            json.dump(r, f, indent=2)
+        print(f"Pen width: redrawn at {r['pen_width']} px (radius^2 {r['radius2']}); mean width along the centre line "
+              f"{r['mean_width_before']} before, {r['mean_width_after']} after")
     print("\nGeneration complete!")
     print(f"Generated {len(images)} signatures saved to: {output_dir}")
 
@@ -68,6 +81,11 @@ def generate_signatures(generator, n_samples: int, output_dir: str, batch_size: 
 def with_despeckle(despeckle: Optional[Despeckle]) -> Dict[str, Any]:
     """The keyword a generation call gets: none at all without --despeckle, so such a call is what it was."""
     return {} if despeckle is None else {"despeckle": despeckle}
+
+
+def with_pen_width(pen_width: Optional[PenWidth]) -> Dict[str, Any]:
+    """Likewise for --pen_width."""
+    return {} if pen_width is None else {"pen_width": pen_width}
 
 
 def print_despeckle(despeckle: Despeckle) -> None:
@@ -334,6 +352,18 @@ def despeckle_opt(a: argparse.Namespace) -> Optional[Despeckle]:
     return Despeckle(None if v == "auto" else v, 128 if a.threshold is None else a.threshold)
 
 
+# --pen_width, kept out of the namespace the same way: absent = off
+PEN_WIDTH_DEFAULTS = dict(pen_width=None)
+
+
+def pen_width_opt(a: argparse.Namespace) -> Optional[PenWidth]:
+    """The PenWidth of a command line with --pen_width (its ink threshold is --threshold, 128 without it), else None."""
+    v = getattr(a, "pen_width", PEN_WIDTH_DEFAULTS["pen_width"])
+    if v is None:
+        return None
+    return PenWidth(v, 128 if a.threshold is None else a.threshold)
+
+
 # --project_ssim, kept out of the namespace the same way
 PROJECT_SSIM_DEFAULTS = dict(project_ssim=False)
 
@@ -422,7 +452,20 @@ def parse_args(argv=None) -> argparse.Namespace:
     p.add_argument("--project_ssim", action="store_true", **later,
                    help="With --project: record every reconstruction's structural similarity (SSIM, 11-tap Gaussian window, computed "
                         "on the device) to its target in <prefix>_projection.json (default: off)")
+    p.add_argument("--pen_width", type=int, metavar="W", **later,
+                   help="Redraw every generated signature at pen width W (1..9) before it is written: thinned to its centre line "
+                        "and drawn again with a disc of squared radius (W - 1)^2 // 4, on the device; ink is byte < --threshold, "
+                        "128 without it; after --despeckle when both are given; the plain run only (default: off)")
     a = p.parse_args(argv)
+    if hasattr(a, "pen_width"):
+        if not 1 <= a.pen_width <= 9:
+            p.error("--pen_width W must be in 1..9")
+        for flag, on in (("filter_by_realism", a.filter_by_realism), ("refine_by_realism", opt(a, "refine_by_realism")),
+                         ("adapt", adapt_opt(a, "adapt") is not None), ("project", a.project is not None), ("morph", a.morph is not None)):
+            if on:
+                p.error(f"--pen_width redraws the plain generation run only; it cannot be combined with --{flag}")
+        if a.threshold is not None and not 1 <= a.threshold <= 255:
+            p.error("--pen_width needs --threshold in 1..255")
     if hasattr(a, "project_ssim") and a.project is None:
         p.error("--project_ssim needs --project")
     if hasattr(a, "despeckle"):
@@ -540,7 +583,7 @@ def main(argv=None) -> None:
                           a.oversampling_ratio, a.threshold, a.transparent, a.noise_scale, **with_despeckle(despeckle_opt(a)))
     else:
         generate_signatures(generator, a.n_samples, a.output_dir, a.batch_size, device, a.seed, a.prefix, a.noise_scale,
-                            a.threshold, a.transparent, **with_despeckle(despeckle_opt(a)))
+                            a.threshold, a.transparent, **with_despeckle(despeckle_opt(a)), **with_pen_width(pen_width_opt(a)))
     print("\n" + "=" * 50 + "\nGeneration Summary:")
     print(f"  Checkpoint: {a.checkpoint}\n  Samples generated: {a.n_samples}\n  Output directory: {a.output_dir}")
     print(f"  Seed: {a.seed if a.seed is not None else 'Random'}\n  Device: {device}\n" + "=" * 50)

@@ -134,20 +134,65 @@ class Despeckle:
                 "removed_components": self.removed_components, "removed_pixels": self.removed_pixels}
 
 
-def generate_uint8(generator: Generator, z: torch.Tensor, despeckle: Optional[Despeckle] = None) -> np.ndarray:
+class PenWidth:
+    """The settings of ``generate_signatures --pen_width`` and what the redraw has measured so far: every image is thinned to
+    its centre line and drawn again with a disc of squared radius ``strokes.radius2_for_pen_width(width)`` -- ink (byte <
+    ``threshold``) becomes 0, paper 255 (strokes.restroke_u8, on the device).  ``redraw_device`` adds the width histograms of the
+    images before (from the redraw's own launch) and after (a second launch on the result) to the totals ``report`` hands
+    out as mean widths."""
+
+    def __init__(self, width: int, threshold: int = 128) -> None:
+        from ..strokes import WIDTH_BINS, radius2_for_pen_width
+        if not 1 <= int(threshold) <= 255:
+            raise ValueError(f"pen width needs an ink threshold in 1..255, got {threshold}")
+        self.width, self.radius2, self.threshold = int(width), radius2_for_pen_width(width), int(threshold)
+        self.before, self.after = np.zeros(WIDTH_BINS, np.int64), np.zeros(WIDTH_BINS, np.int64)
+
+    def redraw_device(self, u8: torch.Tensor) -> None:
+        """Redraw the contiguous uint8 (N, H, W) device tensor IN PLACE."""
+        from ..strokes import COUNT, WIDTH_HIST, restroke_u8, stroke_stats
+        stats = torch.empty(u8.shape[0], COUNT, dtype=torch.int32, device=u8.device)
+        restroke_u8(u8, self.radius2, self.threshold, 0, 255, out=u8, stats=stats)
+        after = stroke_stats(u8, self.threshold)
+        self.before += stats[:, WIDTH_HIST:].sum(dim=0, dtype=torch.int64).cpu().numpy()
+        self.after += after[:, WIDTH_HIST:].sum(dim=0, dtype=torch.int64).cpu().numpy()
+
+    def redraw_host(self, u8: np.ndarray, device: torch.device) -> np.ndarray:
+        """(N, H, W) uint8 on the host -> the redrawn copy, through the device."""
+        t = torch.from_numpy(np.ascontiguousarray(u8)).to(device)
+        self.redraw_device(t)
+        return _to_host_u8(t)
+
+    @staticmethod
+    def _mean(hist: np.ndarray) -> Optional[float]:
+        widths = 2 * np.arange(1, len(hist) + 1, dtype=np.int64) - 1
+        return float(int((hist * widths).sum()) / int(hist.sum())) if hist.sum() else None
+
+    def report(self) -> Dict[str, Any]:
+        return {"pen_width": self.width, "radius2": self.radius2, "threshold": self.threshold,
+                "mean_width_before": self._mean(self.before), "mean_width_after": self._mean(self.after)}
+
+
+def generate_uint8(generator: Generator, z: torch.Tensor, despeckle: Optional[Despeckle] = None,
+                   pen_width: Optional[PenWidth] = None) -> np.ndarray:
     """z (B, latent) -> (B, H, W) uint8, the bytes of ``tensor_to_uint8(generator(z))``.  In eval mode the Generator's last
     kernel writes them itself (Engine.g_generate_u8) and one byte per pixel crosses to the host; a Generator left in train()
     mode (BatchNorm batch statistics) has no such kernel and takes the fp32 route.  ``despeckle``: the bytes are cleaned
-    (and what was removed is counted) before they are returned -- on the device, before the copy, in eval mode."""
+    (and what was removed is counted) before they are returned -- on the device, before the copy, in eval mode.
+    ``pen_width``: the bytes are then redrawn at that pen width, on the device as well."""
     if generator.training:
         u8 = tensor_to_uint8(generator(z))
         if despeckle is not None:
             u8, stats = despeckle.clean_host(u8, z.device)
             despeckle.count(stats)
+        if pen_width is not None:
+            u8 = pen_width.redraw_host(u8, z.device)
         return u8
     u8 = generator._require_engine().g_generate_u8(z)
     if despeckle is not None:
         despeckle.count(despeckle.clean_device(u8))
+    if pen_width is not None:
+        pen_width.redraw_device(u8)
     return _to_host_u8(u8)
 
 
@@ -158,10 +203,12 @@ def tensor_to_pil_image(tensor: torch.Tensor):
 
 def generate_signatures_batch(generator: Generator, n_samples: int, latent_dim: int, device: torch.device,
                               seed: Optional[int] = None, batch_size: int = 32, progress_callback=None,
-                              noise_scale: float = 1.0, despeckle: Optional[Despeckle] = None) -> List[Any]:
+                              noise_scale: float = 1.0, despeckle: Optional[Despeckle] = None,
+                              pen_width: Optional[PenWidth] = None) -> List[Any]:
     """Reference semantics (utils/inference.py:136-194): optional torch.manual_seed, then per batch
     z = randn(b, latent, device=device) * noise_scale -> generator(z) -> one PIL image per sample.  ``despeckle``: every
-    batch's bytes are cleaned on the way (generate_uint8)."""
+    batch's bytes are cleaned on the way (generate_uint8); ``pen_width``: and then redrawn at that pen width."""
+    extra = {} if pen_width is None else {"pen_width": pen_width}
     from PIL import Image
     if seed is not None:
         torch.manual_seed(seed)
@@ -173,7 +220,7 @@ def generate_signatures_batch(generator: Generator, n_samples: int, latent_dim: 
     while done < n_samples:
         b = min(batch_size, n_samples - done)
         z = torch.randn(b, latent_dim, device=device) * noise_scale
-        for arr in generate_uint8(generator, z, despeckle):
+        for arr in generate_uint8(generator, z, despeckle, **extra):
             out.append(Image.fromarray(arr, mode="L"))
         done += b
         if progress_callback is not None:

@@ -225,6 +225,63 @@ def calculate_fragmentation(images: torch.Tensor, threshold: int = 128, connecti
     return fragmentation_from_counters(component_stats(images.contiguous(), threshold, connectivity, min_area).cpu().numpy())
 
 
+# ---- stroke geometry: skeleton and pen width (strokes.py) ---------------------------------------------------------------
+def _ceil_sqrt(values: np.ndarray) -> np.ndarray:
+    """The smallest integer k with k * k >= v, by integer comparison (v in 0..4096)."""
+    squares = np.arange(0, 66, dtype=np.int64) ** 2
+    return np.searchsorted(squares, np.asarray(values, dtype=np.int64), side="left")
+
+
+def stroke_geometry_from_counters(counters) -> Dict[str, Any]:
+    """The stroke-geometry dictionary from (N, 23) stroke counters (strokes.STAT_NAMES), pure numpy on integers.
+    images: N; bound_hit: images whose thinning reached the kernel's safety bound (PASSES = -1; they count in nothing below);
+    empty: images without ink; width_histogram: the sixteen width bins summed over the images; mean_width:
+    sum((2k - 1) * hist[k]) / sum(hist), the pooled local pen width (None without a skeleton); width_per_image {mean, std}: the
+    same per image, over the images that have a skeleton; thickest {mean, max}: 2 * ceil(sqrt(d2_max)) - 1 per image, over the
+    images that have ink; skeleton_length {mean, std}; endpoints {mean}; junction_pixels {mean}; ink_per_skeleton_pixel {mean}:
+    ink / skeleton per image, over the images that have a skeleton.  A bar of even width reads one pixel low (strokes.py)."""
+    from ..strokes import COUNT, D2_MAX, ENDPOINTS, INK, JUNCTION_PIXELS, PASSES, SKELETON, WIDTH_BINS, WIDTH_HIST
+    c = np.asarray(counters, dtype=np.int64).reshape(-1, COUNT)
+    if c.shape[0] == 0:
+        raise ValueError("no images")
+    n = int(c.shape[0])
+    hit = c[:, PASSES] < 0
+    c = c[~hit]
+    hist = c[:, WIDTH_HIST:WIDTH_HIST + WIDTH_BINS]
+    widths = 2 * np.arange(1, WIDTH_BINS + 1, dtype=np.int64) - 1
+    pooled = hist.sum(axis=0)
+    has_skel, has_ink = c[:, SKELETON] > 0, c[:, INK] > 0
+    per_image = (hist[has_skel] * widths).sum(axis=1) / np.maximum(hist[has_skel].sum(axis=1), 1)
+    thickest = 2 * _ceil_sqrt(c[has_ink, D2_MAX]) - 1
+    mean = lambda v: float(np.mean(v)) if len(v) else None                        # noqa: E731
+    std = lambda v: float(np.std(v)) if len(v) else None                          # noqa: E731
+    return {"images": n, "empty": int((~has_ink).sum()), "bound_hit": int(hit.sum()),
+            "width_histogram": [int(v) for v in pooled],
+            "mean_width": float(int((pooled * widths).sum()) / int(pooled.sum())) if pooled.sum() else None,
+            "width_per_image": {"mean": mean(per_image), "std": std(per_image)},
+            "thickest": {"mean": mean(thickest), "max": int(thickest.max()) if len(thickest) else None},
+            "skeleton_length": {"mean": mean(c[:, SKELETON]), "std": std(c[:, SKELETON])},
+            "endpoints": {"mean": mean(c[:, ENDPOINTS])}, "junction_pixels": {"mean": mean(c[:, JUNCTION_PIXELS])},
+            "ink_per_skeleton_pixel": {"mean": mean(c[has_skel, INK] / np.maximum(c[has_skel, SKELETON], 1))}}
+
+
+def calculate_stroke_geometry(images: torch.Tensor, threshold: int = 128) -> Dict[str, Any]:
+    """How thick and how long the strokes of ``images`` are: uint8 (B, S, S) / (B, 1, S, S), or fp32 in [-1, 1] quantised by the
+    generation rule first.  Ink is byte < ``threshold``.  Skeleton and distance map are computed on the device
+    (strokes.stroke_stats) and only the (B, 23) counters reach the host; a structural metric that needs no network weights.
+    Returns stroke_geometry_from_counters' dictionary."""
+    from ..strokes import stroke_stats
+    if not isinstance(images, torch.Tensor):
+        raise ValueError(f"images must be a tensor, got {type(images).__name__}")
+    if images.device.type != "cuda":
+        if not torch.cuda.is_available():
+            raise RuntimeError("the strokes are measured on a ROCm device ('cuda:N'); there is no CPU path")
+        images = images.cuda()
+    if images.dtype != torch.uint8:
+        images = quantize_generated(images)
+    return stroke_geometry_from_counters(stroke_stats(images.contiguous(), threshold).cpu().numpy())
+
+
 # ---- pixel-space similarity: SSIM (ssim.py) ---------------------------------------------------------------------------------
 SSIM_DIVERSITY_IMAGES = 512           # a set's diversity is taken over at most its first 512 images (131 k pairs)
 
