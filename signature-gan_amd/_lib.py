@@ -1,5 +1,5 @@
 """ctypes binding of the C ABI in include/siggan.h (and siggan_mlp.h, siggan_verifier.h, siggan_verifier_grad.h, siggan_verifier_pairs.h, siggan_verifier_topk.h,
-siggan_verifier_train.h, siggan_verifier_data.h, siggan_moments.h, siggan_select.h, siggan_neighbors.h, siggan_resize.h, siggan_components.h, siggan_ssim.h, siggan_strokes.h).
+siggan_verifier_train.h, siggan_verifier_data.h, siggan_moments.h, siggan_select.h, siggan_neighbors.h, siggan_resize.h, siggan_components.h, siggan_ssim.h, siggan_strokes.h, siggan_diverse.h).
 
 The shared library is built in-tree by ``__graft_entry__.build()`` / ``csrc/Makefile`` and must be
 present: there is no CPU or PyTorch fallback for this path -- a missing or stale library raises.
@@ -260,6 +260,14 @@ _NEIGHBORS_SIGNATURES = {
 }
 NEIGHBORS_EXPORTS = tuple(_NEIGHBORS_SIGNATURES)
 
+# greedy farthest-point selection among feature rows (include/siggan_diverse.h): context-free, new symbols again
+DIVERSE_MAX_N, DIVERSE_MAX_DIM, DIVERSE_ROW_TILE = 65536, 1024, 32
+_DIVERSE_SIGNATURES = {
+    "siggan_select_diverse_workspace": (C.c_size_t, [_I32]),
+    "siggan_select_diverse": (C.c_int, [_I32, _P, _I32, _I32, _P, _P, _I32, _I32, C.c_double, _P, _P, _P, _P, _P, C.c_size_t, _P]),
+}
+DIVERSE_EXPORTS = tuple(_DIVERSE_SIGNATURES)
+
 # Pillow's antialiased bilinear resize, bytes and fp32 with its transpose (include/siggan_resize.h): new symbols again
 RESIZE_MAX_IN, RESIZE_MAX_OUT = 1024, 128
 _RESIZE_SIGNATURES = {
@@ -315,7 +323,7 @@ def load():
                               **_VERIFIER_TOPK_SIGNATURES, **_VERIFIER_TRAIN_SIGNATURES,
                               **_VERIFIER_DATA_SIGNATURES, **_MOMENTS_SIGNATURES, **_SELECT_SIGNATURES,
                               **_NEIGHBORS_SIGNATURES, **_RESIZE_SIGNATURES, **_COMPONENTS_SIGNATURES, **_SSIM_SIGNATURES,
-                              **_STROKES_SIGNATURES}.items():
+                              **_STROKES_SIGNATURES, **_DIVERSE_SIGNATURES}.items():
         fn = getattr(lib, name)          # AttributeError if the library does not export the symbol
         fn.restype, fn.argtypes = res, args
     if lib.siggan_abi_version() != ABI_VERSION:

@@ -33,7 +33,17 @@ was removed is recorded as ``despeckle: {min_area, threshold, connectivity, remo
 written (strokes.restroke_u8): the image is thinned to its centre line (ink is byte < ``--threshold``, 128 without it) and the
 line is drawn again, ink 0 on paper 255, with a disc of squared radius (W - 1)^2 // 4.  ``--despeckle`` given as well runs
 first.  ``<prefix>_pen_width.json`` records W, the radius, the threshold and the mean pen width along the centre line before
-and after."""
+and after.
+
+``--filter_by_realism --diverse`` (with ``--verifier_checkpoint``) selects for diversity instead of taking the top of the
+ranking (utils.inference.generate_signatures_diverse): among the ``--diverse_keep_ratio`` most realistic signatures of the pool
+it picks, greedily, those that lie farthest apart in the Siamese verifier's embedding space (utils.diverse.select_diverse, on
+the device).  ``--diverse_real_dir DIR --diverse_memorisation_ratio R`` bars near copies of the real signatures in DIR,
+``--diverse_existing_dir DIR`` keeps the picks away from a synthetic set that exists already, ``--diverse_min_separation S``
+stops the run once nothing new is at least S away from what is kept -- fewer than ``--n_samples`` files may then be written.
+The files are in pick order, ``<prefix>_scores.json`` is the filter's, and ``<prefix>_diverse.json`` is the report: every pick's
+pool index, score and gain, and the nearest-neighbour distances inside this selection beside those of the plain top-n.  Whether
+a verifier trained on such a set is more accurate is not measured."""
 import argparse
 import json
 import os
@@ -43,7 +53,8 @@ from typing import Any, Dict, Optional
 import numpy as np
 import torch
 
-from .utils.inference import (Despeckle, PenWidth, generate_signatures_batch, generate_signatures_filtered, generate_signatures_refined,
+from .utils.inference import (Despeckle, PenWidth, generate_signatures_batch, generate_signatures_diverse, generate_signatures_filtered,
+                              generate_signatures_refined,
                               load_discriminator, load_generator, load_target_images, morph_sequence, morph_strip, process_images,
                               project_signatures)
 
@@ -126,6 +137,53 @@ def generate_filtered(generator, discriminator, n_samples: int, output_dir: str,
     print(f"Generated {len(images)} signatures saved to: {output_dir}")
     if scores:
         print(f"Realism scores: best {scores[0]:.4f}, worst kept {scores[-1]:.4f}")
+
+
+def generate_diverse(generator, discriminator, verifier, n_samples: int, output_dir: str, batch_size: int = 64,
+                     device: torch.device = torch.device("cuda"), seed: Optional[int] = None, prefix: str = "signature",
+                     oversampling_ratio: float = 2.0, threshold: Optional[int] = None, transparent: bool = False,
+                     noise_scale: float = 1.0, despeckle: Optional[Despeckle] = None, keep_ratio: float = 0.5,
+                     real_dir: Optional[str] = None, memorisation_ratio: Optional[float] = None, existing_dir: Optional[str] = None,
+                     min_separation: float = 0.0) -> None:
+    """Up to ``n_samples`` of int(n_samples * oversampling_ratio) generated signatures, chosen for diversity among the
+    ``keep_ratio`` most realistic (utils.inference.generate_signatures_diverse), written in pick order under the usual names,
+    plus ``<prefix>_scores.json`` as generate_filtered writes it and ``<prefix>_diverse.json``, the selection's report."""
+    os.makedirs(output_dir, exist_ok=True)
+    print(f"Output directory: {output_dir}")
+    print(f"Generating {int(n_samples * oversampling_ratio)} signatures, selecting up to {n_samples} for diversity...")
+    size = generator.output_size
+    real = load_target_images(real_dir, size)[1] if real_dir is not None else None
+    existing = load_target_images(existing_dir, size)[1] if existing_dir is not None else None
+    images, scores, report = generate_signatures_diverse(
+        generator, discriminator, verifier, n_samples, generator.latent_dim, device, seed=seed, batch_size=batch_size,
+        oversampling_ratio=oversampling_ratio, keep_ratio=keep_ratio, noise_scale=noise_scale, threshold=threshold, real_u8=real,
+        memorisation_ratio=memorisation_ratio, existing_u8=existing, min_separation=min_separation, verifier_resize=size != 64,
+        **with_despeckle(despeckle))
+    if threshold is not None:
+        images = process_images(images, threshold=threshold, make_transparent=transparent)
+    print(f"Saving {len(images)} images...")
+    records = []
+    for i, (img, score) in enumerate(zip(images, scores)):
+        name = f"{prefix}_{i + 1:06d}.png"
+        img.save(os.path.join(output_dir, name), "PNG")
+        records.append({"file": name, "score": score})
+        report["picks"][i]["file"] = name
+    with open(os.path.join(output_dir, f"{prefix}_scores.json"), "w") as f:
+        json.dump(records_json(records, despeckle), f, indent=2)
+    with open(os.path.join(output_dir, f"{prefix}_diverse.json"), "w") as f:
+        json.dump(report, f, indent=2)
+    if despeckle is not None:
+        print_despeckle(despeckle)
+    print("\nGeneration complete!")
+    print(f"Generated {len(images)} signatures saved to: {output_dir}")
+    if len(images) < n_samples:
+        print(f"Selected {len(images)} of the {n_samples} signatures asked for (stopped by: {report['stopped_by']})")
+    d, t = report["diverse"], report["top_n"]
+    if d["min_nn_distance"] is not None and t["min_nn_distance"] is not None:
+        print(f"Nearest-neighbour distance inside the selection: min {d['min_nn_distance']:.4f}, mean {d['mean_nn_distance']:.4f} "
+              f"(top-n by realism: min {t['min_nn_distance']:.4f}, mean {t['mean_nn_distance']:.4f})")
+    if d["mean_realism"] is not None and t["mean_realism"] is not None:
+        print(f"Mean realism: {d['mean_realism']:.4f} (top-n by realism: {t['mean_realism']:.4f})")
 
 
 def generate_refined(generator, discriminator, n_samples: int, output_dir: str, batch_size: int = 64,
@@ -372,6 +430,16 @@ def project_ssim_opt(a: argparse.Namespace) -> bool:
     return getattr(a, "project_ssim", PROJECT_SSIM_DEFAULTS["project_ssim"])
 
 
+# the --diverse flags, kept out of the namespace the same way
+DIVERSE_DEFAULTS = dict(diverse=False, diverse_keep_ratio=0.5, diverse_real_dir=None, diverse_memorisation_ratio=None,
+                        diverse_existing_dir=None, diverse_min_separation=0.0)
+
+
+def diverse_opt(a: argparse.Namespace, name: str):
+    """A flag of DIVERSE_DEFAULTS: its value on the command line, else its default."""
+    return getattr(a, name, DIVERSE_DEFAULTS[name])
+
+
 def identity_opt(a: argparse.Namespace, name: str):
     """A flag of IDENTITY_DEFAULTS: its value on the command line, else its default."""
     return getattr(a, name, IDENTITY_DEFAULTS[name])
@@ -456,7 +524,42 @@ def parse_args(argv=None) -> argparse.Namespace:
                    help="Redraw every generated signature at pen width W (1..9) before it is written: thinned to its centre line "
                         "and drawn again with a disc of squared radius (W - 1)^2 // 4, on the device; ink is byte < --threshold, "
                         "128 without it; after --despeckle when both are given; the plain run only (default: off)")
+    p.add_argument("--diverse", action="store_true", **later,
+                   help="With --filter_by_realism and --verifier_checkpoint: select for diversity -- greedily the signatures "
+                        "farthest apart in the verifier's embedding space, among the most realistic of the pool -- instead of "
+                        "keeping the top of the ranking; write <prefix>_diverse.json (default: off)")
+    p.add_argument("--diverse_keep_ratio", type=float, metavar="R", **later,
+                   help="With --diverse: the fraction of the pool, best realism first, that may be selected (default: 0.5)")
+    p.add_argument("--diverse_real_dir", type=str, metavar="DIR", **later,
+                   help="With --diverse and --diverse_memorisation_ratio: real signatures the selection must not copy")
+    p.add_argument("--diverse_memorisation_ratio", type=float, metavar="R", **later,
+                   help="With --diverse_real_dir: a candidate closer to a real signature than R times the real set's median "
+                        "nearest-neighbour distance is not selected")
+    p.add_argument("--diverse_existing_dir", type=str, metavar="DIR", **later,
+                   help="With --diverse: a synthetic set that exists already; the selection keeps away from it too")
+    p.add_argument("--diverse_min_separation", type=float, metavar="S", **later,
+                   help="With --diverse: stop once no candidate is at least S (embedding distance) from everything kept; fewer "
+                        "than n_samples may then be written (default: 0)")
     a = p.parse_args(argv)
+    if diverse_opt(a, "diverse"):
+        if not a.filter_by_realism:
+            p.error("--diverse needs --filter_by_realism")
+        if identity_opt(a, "verifier_checkpoint") is None:
+            p.error("--diverse needs --verifier_checkpoint")
+        for flag, on in (("refine_by_realism", opt(a, "refine_by_realism")), ("adapt", adapt_opt(a, "adapt") is not None),
+                         ("project", a.project is not None), ("morph", a.morph is not None), ("pen_width", hasattr(a, "pen_width"))):
+            if on:
+                p.error(f"--diverse cannot be combined with --{flag}")
+        if any(hasattr(a, k) for k in IDENTITY_DEFAULTS if k != "verifier_checkpoint"):
+            p.error("the --project_identity_* flags need --project")
+        if (diverse_opt(a, "diverse_real_dir") is None) != (diverse_opt(a, "diverse_memorisation_ratio") is None):
+            p.error("--diverse_real_dir and --diverse_memorisation_ratio need each other")
+        ratio = diverse_opt(a, "diverse_memorisation_ratio")
+        if not 0.0 < diverse_opt(a, "diverse_keep_ratio") <= 1.0 or not diverse_opt(a, "diverse_min_separation") >= 0 or (
+                ratio is not None and not ratio >= 0):
+            p.error("--diverse_keep_ratio must be in (0, 1], --diverse_min_separation and --diverse_memorisation_ratio >= 0")
+    elif any(hasattr(a, k) for k in DIVERSE_DEFAULTS):
+        p.error("the --diverse_* flags need --diverse")
     if hasattr(a, "pen_width"):
         if not 1 <= a.pen_width <= 9:
             p.error("--pen_width W must be in 1..9")
@@ -501,7 +604,7 @@ def parse_args(argv=None) -> argparse.Namespace:
         p.error("--project_realism_weight and --project_prior_weight must be >= 0")
     if a.project is None and (hasattr(a, "project_realism_weight") or hasattr(a, "project_prior_weight")):
         p.error("--project_realism_weight and --project_prior_weight need --project")
-    if a.project is None and any(hasattr(a, k) for k in IDENTITY_DEFAULTS):
+    if a.project is None and not diverse_opt(a, "diverse") and any(hasattr(a, k) for k in IDENTITY_DEFAULTS):
         p.error("--verifier_checkpoint, --project_identity_weight and --project_identity_score_weight need --project")
     w_i = (identity_opt(a, "project_identity_weight"), identity_opt(a, "project_identity_score_weight"))
     if not w_i[0] >= 0 or not w_i[1] >= 0:
@@ -577,6 +680,15 @@ def main(argv=None) -> None:
         generate_refined(generator, need_discriminator("--refine_by_realism"), a.n_samples, a.output_dir, a.batch_size, device, a.seed,
                          a.prefix, opt(a, "refine_steps"), opt(a, "refine_lr"), opt(a, "refine_prior"), a.threshold, a.transparent,
                          a.noise_scale, **with_despeckle(despeckle_opt(a)))
+    elif a.filter_by_realism and diverse_opt(a, "diverse"):
+        from .signature_verifier_eval import load_model
+        discriminator = need_discriminator("--diverse")
+        verifier = load_model(identity_opt(a, "verifier_checkpoint"), device)[0]
+        generate_diverse(generator, discriminator, verifier, a.n_samples, a.output_dir, a.batch_size, device, a.seed, a.prefix,
+                         a.oversampling_ratio, a.threshold, a.transparent, a.noise_scale, despeckle_opt(a),
+                         diverse_opt(a, "diverse_keep_ratio"), diverse_opt(a, "diverse_real_dir"),
+                         diverse_opt(a, "diverse_memorisation_ratio"), diverse_opt(a, "diverse_existing_dir"),
+                         diverse_opt(a, "diverse_min_separation"))
     elif a.filter_by_realism:
         discriminator = need_discriminator("--filter_by_realism")
         generate_filtered(generator, discriminator, a.n_samples, a.output_dir, a.batch_size, device, a.seed, a.prefix,

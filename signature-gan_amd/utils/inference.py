@@ -17,7 +17,10 @@ Engine.g_latent_objective_grad), and on top of it the app's second generation ta
 Realism-guided refinement joins the two: ``refine_latents`` moves latent vectors up the Discriminator's eval-mode score (an
 Adam loop on z around Engine.g_latent_objective_grad) instead of throwing low-scoring images away,
 ``generate_signatures_refined`` is generation on top of it, and ``project_signatures`` takes the same realism and prior terms
-beside its pixel error.  ``adopt_discriminator`` brings the Discriminator into the Generator's context for them."""
+beside its pixel error.  ``adopt_discriminator`` brings the Discriminator into the Generator's context for them.
+
+``generate_signatures_diverse`` takes the filter's pool and selects from it for diversity in the verifier's embedding space
+(utils/diverse.py) instead of keeping the top of the ranking."""
 import math
 from typing import Any, Dict, List, Optional, Tuple
 
@@ -301,6 +304,31 @@ def dequantize_uint8(u8: np.ndarray) -> torch.Tensor:
     return (torch.from_numpy(np.ascontiguousarray(u8)).float() / 127.5 - 1.0).unsqueeze(1)
 
 
+def _scored_pool(g_eng, d_eng, total, plan, latent_dim, device, noise_scale, binarize, despeckle=None, tick=None):
+    """The device route's pool: (pool uint8 (total, S, S), scores fp32 (total,), removed int32 (total, 9) or None), all on the
+    Generator's device.  Batch by batch (``plan``: filter_plan's), seeded, z = randn * noise_scale, the Generator's last kernel
+    writes the bytes into the pool, ``despeckle`` cleans them IN PLACE (``removed``: the counters of what they were) and the
+    Discriminator scores them where they lie, binarised on load when ``binarize`` is a byte value.  ``tick(b)`` after every batch.
+    generate_signatures_filtered and generate_signatures_diverse both build their pool here, so for equal arguments the two
+    hold the same bytes and scores."""
+    size = g_eng.image_size
+    pool = torch.empty(total, size, size, dtype=torch.uint8, device=g_eng.device)
+    scores = torch.empty(total, dtype=torch.float32, device=g_eng.device)
+    removed = torch.empty(total, 9, dtype=torch.int32, device=g_eng.device) if despeckle is not None else None
+    done = 0
+    for b, batch_seed in plan:
+        _seed_batch(batch_seed)
+        z = torch.randn(b, latent_dim, device=device) * noise_scale
+        g_eng.g_generate_u8(z, out=pool[done:done + b])
+        if despeckle is not None:
+            removed[done:done + b] = despeckle.clean_device(pool[done:done + b])
+        d_eng.d_score_u8(pool[done:done + b], binarize=binarize, out=scores[done:done + b])
+        done += b
+        if tick is not None:
+            tick(b)
+    return pool, scores, removed
+
+
 def generate_signatures_filtered(generator: Generator, discriminator: Discriminator, n_signatures: int, latent_dim: int,
                                  device: torch.device, seed: Optional[int] = None, batch_size: int = 32,
                                  oversampling_ratio: float = 2.0, noise_scale: float = 1.0, threshold: Optional[int] = None,
@@ -361,26 +389,150 @@ def generate_signatures_filtered(generator: Generator, discriminator: Discrimina
         records = [(arr, sc) for arr, sc, _ in records]
         return [Image.fromarray(arr, mode="L") for arr, _ in records], [sc for _, sc in records]
 
-    g_eng, d_eng = generator._require_engine(), discriminator._require_engine()
-    size = g_eng.image_size
-    pool = torch.empty(total, size, size, dtype=torch.uint8, device=g_eng.device)
-    scores = torch.empty(total, dtype=torch.float32, device=g_eng.device)
+    g_eng = generator._require_engine()
     binarize = None if threshold is None else int(threshold)
-    removed = torch.empty(total, 9, dtype=torch.int32, device=g_eng.device) if despeckle is not None else None
-    for b, batch_seed in plan:
-        _seed_batch(batch_seed)
-        z = torch.randn(b, latent_dim, device=device) * noise_scale
-        g_eng.g_generate_u8(z, out=pool[done:done + b])
-        if despeckle is not None:
-            removed[done:done + b] = despeckle.clean_device(pool[done:done + b])
-        d_eng.d_score_u8(pool[done:done + b], binarize=binarize, out=scores[done:done + b])
-        tick(b)
+    pool, scores, removed = _scored_pool(g_eng, discriminator._require_engine(), total, plan, latent_dim, device, noise_scale,
+                                         binarize, despeckle, tick)
     index = g_eng.select_topk(scores, keep)
     if despeckle is not None:
         despeckle.count(removed[index.long()])
     picked = _to_host_u8(g_eng.gather_u8(pool, index, binarize=binarize))
     best = _to_host_u8(scores[index.long()].view(torch.uint8)).view(np.float32)
     return [Image.fromarray(arr, mode="L") for arr in picked], [float(sc) for sc in best]
+
+
+# ---- diversity-aware selection from the filter's pool ----------------------------------------------------------------------
+def _as_u8_images(name: str, images, size: int, device: torch.device) -> torch.Tensor:
+    t = torch.as_tensor(np.ascontiguousarray(images) if isinstance(images, np.ndarray) else images)
+    if t.dtype != torch.uint8 or t.dim() != 3 or tuple(t.shape[1:]) != (size, size) or t.shape[0] < 1:
+        raise ValueError(f"{name} must be uint8 (N >= 1, {size}, {size}), got {t.dtype} {tuple(t.shape)}")
+    return t.to(device).contiguous()
+
+
+def _embed_u8(verifier, u8: torch.Tensor, resize: bool) -> torch.Tensor:
+    """The verifier's embeddings of uint8 (N, S, S) device images, max_images at a time: embed_u8, or embed_resized."""
+    embed = verifier.embed_resized if resize else verifier.embed_u8
+    step = int(verifier.max_images)
+    return torch.cat([embed(u8[i:i + step]) for i in range(0, u8.shape[0], step)]).contiguous()
+
+
+def _nn_d2(emb: torch.Tensor) -> Optional[np.ndarray]:
+    """Every row's squared distance to its nearest other row, on the host; None for fewer than two rows."""
+    from .neighbors import knn
+    if emb.shape[0] < 2:
+        return None
+    return knn(emb, emb, 1, exclude_self=True)[0][:, 0].cpu().numpy()
+
+
+def generate_signatures_diverse(generator: Generator, discriminator: Discriminator, verifier, n_signatures: int, latent_dim: int,
+                                device: torch.device, seed: Optional[int] = None, batch_size: int = 32,
+                                oversampling_ratio: float = 4.0, keep_ratio: float = 0.5, noise_scale: float = 1.0,
+                                threshold: Optional[int] = None, real_u8=None, memorisation_ratio: Optional[float] = None,
+                                existing_u8=None, min_separation: float = 0.0, despeckle: Optional[Despeckle] = None,
+                                verifier_resize: bool = False, return_pool: bool = False) -> Tuple[List[Any], List[float], Dict[str, Any]]:
+    """Diversity-aware selection from the realism filter's pool: generate int(n * ratio) signatures exactly as the device route
+    of generate_signatures_filtered does (the same filter_plan, batch seeds, in-place despeckle and d_score_u8, so pool bytes
+    and scores are the filter's bit for bit), embed the bytes that will be written (the binarised pool with ``threshold``)
+    with the Siamese ``verifier`` (embed_u8; ``verifier_resize``: embed_resized, for a 128x128 Generator), and pick up to
+    min(n, total) signatures that are mutually farthest apart in that space (utils.diverse.select_diverse), among the
+    eligible ones: the ceil(keep_ratio * total) most realistic (utils.diverse.eligibility).
+
+    ``real_u8`` (N, S, S) uint8 with ``memorisation_ratio`` (they come together; the ratio has no default): a candidate whose
+    nearest real embedding is closer than memorisation_ratio * the median of the real set's own leave-one-out nearest
+    distances is not eligible.  ``existing_u8``: a synthetic set grown in earlier runs; the picks keep away from it as they
+    do from each other (its nearest-member distances are the selection's anchors).  ``min_separation``: stop once the best
+    remaining candidate is closer than this to what is kept, so fewer than n may come back.  Without anchors the first pick is
+    the eligible signature with the highest realism score; with anchors it is the one farthest from them.
+
+    Returns (PIL 'L' images in pick order, their scores, report): utils.diverse.diversity_summary's dictionary -- what was
+    picked and why the run ended, each pick's gain, and the nearest-neighbour distances and mean realism inside this
+    selection beside those of the plain top-n-by-realism selection of the same pool: what was bought and what it cost.
+    ``return_pool``: report['_device'] holds the device tensors {pool, scores, embeddings, eligible}.  Of the pool only the
+    selected images, their scores and the pick lists cross to the host, beside the numbers the report is made of (the
+    nearest-neighbour and nearest-real distances of the two selections of n, one coverage figure).  The host waits for the
+    device three times on the way: for the number of eligible rows and the first pick (two scalars) before the selection is
+    enqueued, for the number of picks after it, and for the selected bytes.
+
+    There is no host route: a Generator, Discriminator or verifier in train() mode, or a pool larger than _lib.SELECT_MAX,
+    raises ValueError."""
+    from PIL import Image
+    from .. import _lib
+    from .diverse import diversity_summary, eligibility, select_diverse
+    from .neighbors import knn
+    if threshold is not None and not 0 <= int(threshold) <= 255:
+        raise ValueError(f"threshold must be a byte value, got {threshold}")
+    if (real_u8 is None) != (memorisation_ratio is None):
+        raise ValueError("real_u8 and memorisation_ratio come together: the memorisation floor is memorisation_ratio times the "
+                         "real set's median leave-one-out nearest distance, and the ratio has no default")
+    if memorisation_ratio is not None and not float(memorisation_ratio) >= 0.0:
+        raise ValueError(f"memorisation_ratio must be >= 0, got {memorisation_ratio}")
+    if not float(min_separation) >= 0.0:
+        raise ValueError(f"min_separation must be >= 0, got {min_separation}")
+    if not 0.0 < float(keep_ratio) <= 1.0:
+        raise ValueError(f"keep_ratio must be in (0, 1], got {keep_ratio}")
+    if generator.training or discriminator.training or verifier.training:
+        raise ValueError("diverse selection has no host route: call .eval() on the Generator, the Discriminator and the verifier")
+    if generator.output_size != 64 and not verifier_resize:
+        raise ValueError(f"the verifier reads 64x64 images: a {generator.output_size}x{generator.output_size} Generator needs "
+                         "verifier_resize=True")
+    total, plan = filter_plan(n_signatures, oversampling_ratio, batch_size, seed)
+    if total > _lib.SELECT_MAX:
+        raise ValueError(f"diverse selection has no host route: a pool of {total} signatures exceeds {_lib.SELECT_MAX}")
+    keep = min(int(n_signatures), total)
+    if keep < 1:
+        return [], [], diversity_summary(max(total, 0), 0, max(keep, 0), [], [], 0, [])
+    g_eng = generator._require_engine()
+    dev, size = g_eng.device, g_eng.image_size
+    real = existing = None
+    if real_u8 is not None:
+        real = _as_u8_images("real_u8", real_u8, size, dev)
+        if real.shape[0] < 2:
+            raise ValueError("the memorisation floor needs at least two real signatures")
+    if existing_u8 is not None:
+        existing = _as_u8_images("existing_u8", existing_u8, size, dev)
+    binarize = None if threshold is None else int(threshold)
+    pool, scores, removed = _scored_pool(g_eng, discriminator._require_engine(), total, plan, latent_dim, device, noise_scale,
+                                         binarize, despeckle)
+    everything = torch.arange(total, dtype=torch.int32, device=dev)
+    written = pool if binarize is None else g_eng.gather_u8(pool, everything, binarize=binarize)
+    emb = _embed_u8(verifier, written, verifier_resize)
+
+    near_d2 = floor2 = None
+    if real is not None:
+        real_emb = _embed_u8(verifier, real, verifier_resize)
+        near_d2 = knn(emb, real_emb, 1)[0][:, 0].contiguous()
+        loo = knn(real_emb, real_emb, 1, exclude_self=True)[0][:, 0].sqrt().sort().values
+        median = 0.5 * (loo[(loo.numel() - 1) // 2] + loo[loo.numel() // 2])                 # numpy's median, on the device
+        floor2 = (float(memorisation_ratio) * median) ** 2
+    mask = eligibility(scores, keep_ratio, near_d2, floor2)
+    anchor_d2 = None
+    if existing is not None:
+        existing_emb = _embed_u8(verifier, existing, verifier_resize)
+        anchor_d2 = knn(emb, existing_emb, 1)[0][:, 0].contiguous()
+    rank = g_eng.select_topk(scores, total)                                                 # the filter's order of the pool
+    eligible_in_rank = torch.nonzero(mask[rank.long()]).flatten()
+    n_eligible = int(eligible_in_rank.numel())
+    first = int(rank[eligible_in_rank[0]]) if anchor_d2 is None and n_eligible else None
+
+    order, gain2, count, min_d2 = select_diverse(emb, keep, mask, anchor_d2, first, min_separation)
+    count_h = int(count.cpu()[0])
+    picks = order[:count_h].contiguous()
+    top = rank[:keep].contiguous()
+    coverage = float(min_d2[mask.bool()].max().cpu()) if n_eligible else None
+    report = diversity_summary(total, n_eligible, keep, order.cpu().numpy(), gain2.cpu().numpy(), count_h,
+                               scores[picks.long()].cpu().numpy(),
+                               None if near_d2 is None else near_d2[picks.long()].cpu().numpy(), coverage,
+                               _nn_d2(emb[picks.long()].contiguous()), scores[top.long()].cpu().numpy(),
+                               _nn_d2(emb[top.long()].contiguous()))
+    if return_pool:
+        report["_device"] = {"pool": pool, "scores": scores, "embeddings": emb, "eligible": mask}
+    if count_h == 0:
+        return [], [], report
+    if despeckle is not None:
+        despeckle.count(removed[picks.long()])
+    picked = _to_host_u8(g_eng.gather_u8(pool, picks, binarize=binarize))
+    best = _to_host_u8(scores[picks.long()].view(torch.uint8)).view(np.float32)
+    return [Image.fromarray(arr, mode="L") for arr in picked], [float(sc) for sc in best], report
 
 
 # ---- projection into the latent space and morphing ---------------------------------------------------------------------
