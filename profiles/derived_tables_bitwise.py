@@ -1,13 +1,14 @@
 """Bit-for-bit comparison of two builds of the library over everything the derived-state tables feed.
 
     python profiles/derived_tables_bitwise.py --parent PARENT.so [--new NEW.so] [--also NAME=OTHER.so] [--set small|tiles|both]
-                                              [--out FILE.json]
+                                              [--brief] [--out FILE.json]
 
 Each build runs in a fresh process of its own (the library is loaded once per process, through SIGGAN_LIB_PATH).  For every
 seeded configuration below: three train_steps (clipping on the second, the next real batch staged, z and dropout from the
-library RNG), then an eval g_forward, a d_forward, one g_latent_objective_grad and one g_compute_grads.  Recorded: the sha256
-of every arena (params, grads, both moments, step counts), the BatchNorm running statistics and counters, the spectral-norm
-u / v, every step's metrics buffer and the four outputs.  A call a context refuses (the latent objective on a 16-bit one) is
+library RNG), then an eval g_forward, a d_forward, one g_latent_objective_grad, a g_generate_u8 with stroke counters, a
+d_score_u8, a seeded g_latent_objective_grad, two g_param_grads (first_layer 0 and a middle one) and one g_compute_grads.
+Recorded: the sha256 of every arena (params, grads, both moments, step counts), the BatchNorm running statistics and counters,
+the spectral-norm u / v, every step's metrics buffer and every call's outputs.  A call a context refuses (the latent objective on a 16-bit one) is
 recorded by its message, which must be equal too.  --also: further builds held to the same hashes; what they print to
 stderr behind the prefix TABLECMP is kept in the result (a scratch build that compares its job tables with the parent's
 builders reports there).
@@ -114,11 +115,19 @@ def child(out_path, which):
             one_step(eng, extra, reals[i], reals[i + 1], B, clip=1.0 if i == 1 else None)
             torch.cuda.synchronize()
             r[f"step{i}/metrics"] = sha(eng.metrics)
+        flat = lambda ts: torch.cat([t.reshape(-1).float() for t in ts])     # (bytes and stroke counters are exact in fp32)
+        u8 = (reals[2] * 127.5 + 127.5).clamp(0, 255).to(torch.uint8)[:, 0].contiguous()
         calls = {
             "g_forward": lambda: eng.g_forward(z, training=False),
             "d_forward": lambda: eng.d_forward(reals[3], training=False),
-            "g_latent_objective_grad": lambda: torch.cat([t.reshape(-1) for t in eng.g_latent_objective_grad(
-                z, target=reals[3], recon_weight=1.0, realism_weight=0.5, prior_weight=0.25, want_terms=True, want_probs=True)]),
+            "g_latent_objective_grad": lambda: flat(eng.g_latent_objective_grad(
+                z, target=reals[3], recon_weight=1.0, realism_weight=0.5, prior_weight=0.25, want_terms=True, want_probs=True)),
+            "g_generate_u8": lambda: flat(eng.g_generate_u8(z, threshold=0.0)),
+            "d_score_u8": lambda: eng.d_score_u8(u8),
+            "g_latent_objective_grad_seeded": lambda: flat(eng.g_latent_objective_grad(
+                z, target=reals[3], recon_weight=1.0, realism_weight=0.5, prior_weight=0.25, want_terms=True, image_grad=reals[1])),
+            "g_param_grad/0": lambda: flat(eng.g_param_grad(z, target=reals[3], realism_weight=0.5, want_terms=True, want_probs=True)),
+            "g_param_grad/mid": lambda: flat(eng.g_param_grad(z, target=reals[3], realism_weight=0.5, first_layer=(eng.g_layers + 1) // 2)),
         }
         for cname, fn in calls.items():
             try:
@@ -196,6 +205,8 @@ def main():
     ap.add_argument("--also", action="append", default=[])
     ap.add_argument("--out", default=os.path.join(ROOT, "profiles", "derived_tables_bitwise.json"))
     ap.add_argument("--set", default="small", choices=sorted(SETS))
+    ap.add_argument("--brief", action="store_true", help="write one sha256 per configuration (over its values in key order) and "
+                    "the refusals' messages instead of every hash, and leave the epilogue coverage out: for a change that touches no kernel")
     ap.add_argument("--child")
     a = ap.parse_args()
     if a.child:
@@ -233,14 +244,17 @@ def main():
     if a.set != "small":
         result["configuration_set"] = a.set
         result["launches_equal"] = all(launched[b] == launched["parent"] for b in launched)
-        result["epilogue_coverage"] = coverage(launched["new"], a.set)
+        result["epilogue_coverage"] = cov = coverage(launched["new"], a.set)
         different += [] if result["launches_equal"] else ["launches"]
         result["all_equal"] = not different
+    if a.brief and not different:
+        result.pop("epilogue_coverage", None)
+        result["sha256"] = {c: {"values": len(v), "sha256_of_values": hashlib.sha256(json.dumps(v, sort_keys=True).encode()).hexdigest(),
+                                "refused": {k: s for k, s in v.items() if s.startswith("refused")}} for c, v in got["parent"].items()}
     with open(a.out, "w") as f:
         json.dump(result, f, indent=1)
     print(json.dumps({k: result[k] for k in ("builds", "values_per_build", "all_equal", "different", "stderr_notes")}), flush=True)
     if a.set != "small":
-        cov = result["epilogue_coverage"]
         print(json.dumps({"launches_equal": result["launches_equal"], "unreachable": cov["unreachable_at_these_shapes"],
                           "kernels_seen": cov["kernels_seen"]}), flush=True)
     return 0 if not different else 1

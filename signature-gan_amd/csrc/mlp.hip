@@ -327,7 +327,7 @@ extern "C" int mlpgan_d_forward(mlpgan_ctx* c, const float* x, int32_t B, float*
     if (!x || !probs) return FAIL(SIGGAN_E_INVALID, "null tensor");
     hipStream_t s = (hipStream_t)stream;
     d_fwd(c, x, B, s);
-    launch_bce(c->logits, B, B, 0.f, 0.f, probs, nullptr, nullptr, 0, s);
+    launch_bce(LogitSrc{c->logits}, B, B, 0.f, 0.f, probs, nullptr, nullptr, 0, s);
     return hipGetLastError() == hipSuccess ? SIGGAN_OK : FAIL(SIGGAN_E_HIP, "kernel launch failed");
 }
 extern "C" int mlpgan_d_step(mlpgan_ctx* c, const float* real, int32_t B, const float* z, const siggan_hyper* hp, float* mt, void* stream) {
@@ -342,7 +342,7 @@ extern "C" int mlpgan_d_step(mlpgan_ctx* c, const float* real, int32_t B, const 
     HIPCHK(hipMemcpyAsync(c->x2, real, ib, hipMemcpyDeviceToDevice, s));             // rows [0, B): real
     g_fwd(c, c->z, B, false, c->x2 + (size_t)B * c->P, s);                          // rows [B, 2B): G.eval()(z), no grad
     d_fwd(c, c->x2, 2 * B, s);                                                      // no BatchNorm in D: one 2B-row pass
-    launch_bce(c->logits, 2 * B, B, hp->label_smoothing, 0.f, c->probs, c->dlogit, mt, 0, s);
+    launch_bce(LogitSrc{c->logits}, 2 * B, B, hp->label_smoothing, 0.f, c->probs, c->dlogit, mt, 0, s);
     d_bwd(c, c->x2, 2 * B, true, false, s);
     adam(c, 1, hp, mt, s);
     return hipGetLastError() == hipSuccess ? SIGGAN_OK : FAIL(SIGGAN_E_HIP, "kernel launch failed");
@@ -358,7 +358,7 @@ extern "C" int mlpgan_g_step(mlpgan_ctx* c, int32_t B, const float* z, const sig
     else launch_randn(c->z, (int64_t)B * c->gdim[0], c->dev, 2, s);
     g_fwd(c, c->z, B, true, c->img, s);                                             // G.train(): BatchNorm batch statistics
     d_fwd(c, c->img, B, s);
-    launch_bce(c->logits, B, B, 1.0f, 1.0f, c->probs, c->dlogit, mt, 1, s);
+    launch_bce(LogitSrc{c->logits}, B, B, 1.0f, 1.0f, c->probs, c->dlogit, mt, 1, s);
     d_bwd(c, c->img, B, false, true, s);                                            // through D into the image; no D weight grads
     hipLaunchKernelGGL(k_act_bwd, dim3(blocks((int64_t)B * c->P)), dim3(256), 0, s, c->dx, c->img, c->dimg, (int64_t)B * c->P, (int)ACT_TANH, 0.f);
     const int nh = c->nh;

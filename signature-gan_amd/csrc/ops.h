@@ -176,19 +176,21 @@ void launch_cls_features(int dt, const void* act, float* feat, int B, int C, hip
 // sigmoid + BCE (mean per segment) + d(logit); seg0 = first n0 rows with target y0, rest target y1
 // gscale: d(logit) is multiplied by it (the fp16 gradient scale; every gradient downstream then carries it and the optimiser
 // step divides it out again -- 1 for fp32 / bf16)
-void launch_bce(const float* logits, int B, int n0, float y0, float y1, float* probs, float* dlogit,
-                float* metrics, int is_g_step, hipStream_t s, float gscale = 1.0f, const float* parts = nullptr, int P = 0,
-                const float* bc = nullptr);
+// The logit of row n: stored (k_cls_fwd; P == 0, logits alone), or -- when the last block's split-K epilogue left P partial dot
+// products per image (GConvArgs::cls_part) -- their sum in order plus the bias bc[0]; `logits` then receives the sum (k_bce).
+struct LogitSrc { const float* logits; const float* parts; int P; const float* bc; };
+void launch_bce(const LogitSrc& src, int B, int n0, float y0, float y1, float* probs, float* dlogit, float* metrics, int is_g_step,
+                hipStream_t s, float gscale = 1.0f);
 // dv[n][hw][c] = dlogit[n] * wcp[hw*C+c] * leaky'(act) * noise[n][c]
 // from the logits (rows < n0: target y0, the rest y1; each segment's mean): d(logit) is recomputed with k_bce's expression
-void launch_cls_bwd(int dt, const float* logits, int n0, float y0, float y1, const float* wcp, const void* act, const float* noise,
-                    float slope, void* dv, int B, int C, hipStream_t s, float gscale = 1.0f, float* bce_probs = nullptr,
-                    float* bce_dlogit = nullptr, float* bce_metrics = nullptr, int bce_is_g = 0, bool with_bce = false,
-                    const float* parts = nullptr, int P = 0, const float* bc = nullptr);
+// bce != nullptr: launch_bce's work (same rows, targets and gscale) rides as one more block of this launch
+struct BceRider { float* probs; float* dlogit; float* metrics; int is_g; };
+void launch_cls_bwd(int dt, const LogitSrc& src, int n0, float y0, float y1, const float* wcp, const void* act, const float* noise,
+                    float slope, void* dv, int B, int C, hipStream_t s, float gscale = 1.0f, const BceRider* bce = nullptr);
 // the same in eval form, per image (siggan_g_latent_objective_grad; fp32): no dropout table, target 1 with a count of 1,
 // d(logit) times wd;  term[n] = -max(log p[n], -100) and (optional) probs[n] = p[n] are written by one more block
-void launch_cls_bwd_eval(const float* logits, const float* parts, int P, const float* bc, const float* wcp, const float* act, float slope,
-                         float* dv, int B, int C, float wd, float* term, float* probs, hipStream_t s);
+void launch_cls_bwd_eval(const LogitSrc& src, const float* wcp, const float* act, float slope, float* dv, int B, int C, float wd,
+                         float* term, float* probs, hipStream_t s);
 // dWc (torch order c*16+hw) and dbc
 void launch_cls_wgrad(int dt, const float* dlogit, const void* act, float* dWc, float* dbc, int B, int C, hipStream_t s);
 // dst[i] = (float)src[i] for a tensor of element type dt
@@ -254,7 +256,7 @@ void launch_adam(float* p, float* g, float* m, float* v, int64_t n, const DevSta
 // 16 x 16 x 16-tap tile of a convolution weight updates it and writes both MFMA packs from LDS (64-byte runs each way), the
 // classifier / one-channel weights and the BatchNorm eval tables likewise.  Same update arithmetic, same pack values as the
 // two launches it replaces (bitwise: tests/test_engine_gpu.py compares the execution modes).  Both job tables are built from
-// one list of records (siggan.hip, struct Derived: which fields mean what is said there, once); the destination layouts are
+// one list of records (ctx.h, struct Derived: which fields mean what is said there, once); the destination layouts are
 // the functions both kernels call (ops.hip, pack_down_idx / pack_up_idx / bn_eval_store).
 enum ApType : int { AP_FLAT = 0, AP_CONV, AP_T16, AP_TAPS, AP_BN };
 struct ApJob {

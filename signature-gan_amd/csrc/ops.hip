@@ -1342,8 +1342,8 @@ __device__ __forceinline__ float bce_dlogit(float x, float y, float inv_count);
 // nn.Sigmoid + nn.BCELoss(mean) per segment and its gradient w.r.t. the logit (torch formulas:
 // log clamped at -100; grad_p = (p - y) / max((1 - p) * p, 1e-12) / count; dlogit = grad_p * p * (1 - p))
 // The logit of row n: stored (k_cls_fwd), or -- when the last block's split-K epilogue left P partial dot products per image
-// (GConvArgs::cls_part) -- their sum in order plus the bias.  k_bce and k_cls_bwd use this one expression: they agree bit for bit.
-struct LogitSrc { const float* logits; const float* parts; int P; const float* bc; };
+// (GConvArgs::cls_part) -- their sum in order plus the bias (LogitSrc, ops.h).  k_bce and k_cls_bwd use this one expression: they
+// agree bit for bit.
 __device__ __forceinline__ float logit_of(const LogitSrc& q, int64_t n) {
     if (q.P == 0) return q.logits[n];
     float v[16];                                  // P <= 16: every load in flight before the first add (a run-time loop
@@ -1403,10 +1403,10 @@ __global__ __launch_bounds__(256) void k_bce(const BceArgs b) {
     __shared__ float sh[24];
     bce_block(b.src, b.logits_out, b.B, b.n0, b.y0, b.y1, b.probs, b.dlogit, b.metrics, b.is_g, b.gscale, sh);
 }
-void launch_bce(const float* logits, int B, int n0, float y0, float y1, float* probs, float* dlogit, float* metrics,
-                int is_g_step, hipStream_t s, float gscale, const float* parts, int P, const float* bc) {
+void launch_bce(const LogitSrc& src, int B, int n0, float y0, float y1, float* probs, float* dlogit, float* metrics, int is_g_step,
+                hipStream_t s, float gscale) {
     hipLaunchKernelGGL(k_bce, dim3(1), dim3(256), 0, s,
-                       BceArgs{LogitSrc{logits, parts, P, bc}, const_cast<float*>(logits), B, n0, y0, y1, probs, dlogit, metrics, is_g_step, gscale});
+                       BceArgs{src, const_cast<float*>(src.logits), B, n0, y0, y1, probs, dlogit, metrics, is_g_step, gscale});
 }
 
 // d(logit) of sigmoid + BCE(mean) for row n, k_bce's own expression (so both kernels agree bit for bit)
@@ -1449,14 +1449,13 @@ __global__ __launch_bounds__(256) void k_cls_bwd(const float* __restrict__ logit
     }
     st4<T>(dv + i, g);
 }
-void launch_cls_bwd(int dt, const float* logits, int n0, float y0, float y1, const float* wcp, const void* act, const float* noise,
-                    float slope, void* dv, int B, int C, hipStream_t s, float gscale, float* bce_probs, float* bce_dlogit,
-                    float* bce_metrics, int bce_is_g, bool with_bce, const float* parts, int P, const float* bc) {
+void launch_cls_bwd(int dt, const LogitSrc& src, int n0, float y0, float y1, const float* wcp, const void* act, const float* noise,
+                    float slope, void* dv, int B, int C, hipStream_t s, float gscale, const BceRider* bce) {
     const int64_t total = (int64_t)B * 16 * C;
-    const BceArgs b = BceArgs{LogitSrc{logits, parts, P, bc}, const_cast<float*>(logits), B, n0, y0, y1, bce_probs, bce_dlogit, bce_metrics,
-                              bce_is_g, gscale};
-    SIGGAN_DT_SWITCH(dt, T, hipLaunchKernelGGL(k_cls_bwd<T>, dim3(cdiv(total, 1024) + (with_bce ? 1 : 0)), dim3(256), 0, s, logits, B, n0, y0,
-                                                y1, wcp, (const T*)act, noise, slope, (T*)dv, total, C, gscale, b, with_bce ? 1 : 0));
+    const BceRider r = bce ? *bce : BceRider{nullptr, nullptr, nullptr, 0};
+    const BceArgs b = BceArgs{src, const_cast<float*>(src.logits), B, n0, y0, y1, r.probs, r.dlogit, r.metrics, r.is_g, gscale};
+    SIGGAN_DT_SWITCH(dt, T, hipLaunchKernelGGL(k_cls_bwd<T>, dim3(cdiv(total, 1024) + (bce ? 1 : 0)), dim3(256), 0, s, src.logits, B, n0, y0,
+                                                y1, wcp, (const T*)act, noise, slope, (T*)dv, total, C, gscale, b, bce ? 1 : 0));
 }
 // The classifier tail of siggan_g_latent_objective_grad: eval mode (no dropout multiplier), one loss PER IMAGE (target 1, a count
 // of 1 instead of the step's 1 / B), d(logit) times the realism weight wd once.  k_cls_bwd's element layout; the last block
@@ -1485,10 +1484,10 @@ __global__ __launch_bounds__(256) void k_cls_bwd_eval(const LogitSrc src, const 
     for (int e = 0; e < 4; ++e) g[e] = dl * w4[e] * (a4[e] > 0.f ? 1.f : slope);
     *reinterpret_cast<f32x4*>(dv + i) = g;
 }
-void launch_cls_bwd_eval(const float* logits, const float* parts, int P, const float* bc, const float* wcp, const float* act, float slope,
-                         float* dv, int B, int C, float wd, float* term, float* probs, hipStream_t s) {
+void launch_cls_bwd_eval(const LogitSrc& src, const float* wcp, const float* act, float slope, float* dv, int B, int C, float wd,
+                         float* term, float* probs, hipStream_t s) {
     const int64_t total = (int64_t)B * 16 * C;
-    hipLaunchKernelGGL(k_cls_bwd_eval, dim3(cdiv(total, 1024) + 1), dim3(256), 0, s, LogitSrc{logits, parts, P, bc}, wcp, act, slope, dv,
+    hipLaunchKernelGGL(k_cls_bwd_eval, dim3(cdiv(total, 1024) + 1), dim3(256), 0, s, src, wcp, act, slope, dv,
                        total, C, wd, B, term, probs);
 }
 // dWc[f] = sum_n dlogit[n] * act[n][f'], dbc = sum_n dlogit[n]: 64 features x 4 row lanes per block (rows n = lane, lane + 4,

@@ -347,7 +347,7 @@ int main() {
 
 def test_gconv_refuses_a_statistics_epilogue_without_a_carve(tmp_path):
     """launch_gconv refuses an EPI_BN_BWD_STATS launch whose caller did not set stat0 / stat_cap (-1, nothing enqueued)
-    instead of storing raw values that the caller's BatchNorm backward would then read as partial sums; siggan.hip turns
+    instead of storing raw values that the caller's BatchNorm backward would then read as partial sums; passes.hip turns
     the refusal into SIGGAN_E_STATE.  A host-only program calls the library's launcher on a box without a GPU."""
     import subprocess
     src, exe = tmp_path / "refuse.cpp", tmp_path / "refuse"

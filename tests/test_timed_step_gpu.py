@@ -134,7 +134,7 @@ def _timed_vs_oracle(dtype, size, latent, batch, steps):
     hp, real_c = dp.hp, real.cpu()
     assert eng._mode == 2 and dp.transport == "host"       # overlap on, no graph (pre_real is off under graph mode)
     # the riders run at fp32 only: the 16-bit contexts measured faster with the first block as a launch of its own, and
-    # fp16 has no one-launch update at all (its overflow guard) -- siggan.hip apply_common
+    # fp16 has no one-launch update at all (its overflow guard) -- step.hip apply_common
     ride = batch if dtype == "f32" else 0
     m = dict(rode=ride, riders=ride * (size // 4))
     m.update(dict(sign_flips=0, metric_frac=0.0, d_grad=0.0, g_grad=0.0, bn=0.0) if dtype == "f32" else dict(narrow=[]))
