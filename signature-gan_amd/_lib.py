@@ -1,5 +1,5 @@
 """ctypes binding of the C ABI in include/siggan.h (and siggan_mlp.h, siggan_verifier.h, siggan_verifier_grad.h, siggan_verifier_pairs.h, siggan_verifier_topk.h,
-siggan_verifier_train.h, siggan_verifier_data.h, siggan_moments.h, siggan_select.h, siggan_neighbors.h, siggan_resize.h, siggan_components.h, siggan_ssim.h, siggan_strokes.h, siggan_diverse.h).
+siggan_verifier_train.h, siggan_verifier_data.h, siggan_moments.h, siggan_select.h, siggan_neighbors.h, siggan_resize.h, siggan_components.h, siggan_ssim.h, siggan_strokes.h, siggan_diverse.h, siggan_shape.h).
 
 The shared library is built in-tree by ``__graft_entry__.build()`` / ``csrc/Makefile`` and must be
 present: there is no CPU or PyTorch fallback for this path -- a missing or stale library raises.
@@ -306,6 +306,14 @@ _STROKES_SIGNATURES = {
 }
 STROKES_EXPORTS = tuple(_STROKES_SIGNATURES)
 
+# ink moments of signature images and their pixel gradient (include/siggan_shape.h): context-free, new symbols again
+SHAPE_FEATURES, SHAPE_SUMS, SHAPE_SYY_MIN = 8, 6, 1e-12
+_SHAPE_SIGNATURES = {
+    "siggan_shape_f32": (C.c_int, [_I32, _P, _I32, _I32, _P, _P, _P, _P, _P, _P]),
+    "siggan_shape_u8": (C.c_int, [_I32, _P, _I32, _I32, _P, _P]),
+}
+SHAPE_EXPORTS = tuple(_SHAPE_SIGNATURES)
+
 _lib = None
 
 
@@ -323,7 +331,7 @@ def load():
                               **_VERIFIER_TOPK_SIGNATURES, **_VERIFIER_TRAIN_SIGNATURES,
                               **_VERIFIER_DATA_SIGNATURES, **_MOMENTS_SIGNATURES, **_SELECT_SIGNATURES,
                               **_NEIGHBORS_SIGNATURES, **_RESIZE_SIGNATURES, **_COMPONENTS_SIGNATURES, **_SSIM_SIGNATURES,
-                              **_STROKES_SIGNATURES, **_DIVERSE_SIGNATURES}.items():
+                              **_STROKES_SIGNATURES, **_DIVERSE_SIGNATURES, **_SHAPE_SIGNATURES}.items():
         fn = getattr(lib, name)          # AttributeError if the library does not export the symbol
         fn.restype, fn.argtypes = res, args
     if lib.siggan_abi_version() != ABI_VERSION:

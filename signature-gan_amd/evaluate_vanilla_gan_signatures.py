@@ -23,6 +23,9 @@ decoded at 64x64 for the verifier, and the report says so in ``verifier_input_re
 ``--strokes`` adds the report key ``stroke_geometry``: skeleton length, line ends, junction pixels and a histogram of local
 pen widths of the generated images (and of the real ones, under the same condition as ``fragmentation``), from a thinning and
 an exact distance map of the bytes already on the device (strokes.py); 23 counters per image reach the host.
+``--shape`` adds the report key ``shape_attributes``: the ink moments of the generated images (and of the real ones, under the
+same condition) -- mass, centre, second moments, slant, spread; mean, standard deviation and 5 / 50 / 95th percentiles of
+each --, from exact integer sums of the bytes already on the device (shape.py); six integers per image reach the host.
 Without the flags nothing changes: stdout, report keys and exit codes are the reference's."""
 import argparse
 import json
@@ -43,8 +46,8 @@ from .utils.frechet import FeatureMoments, embedding_spread, frechet_distance
 from .utils.metrics import (INCEPTION_AVAILABLE, LPIPS_AVAILABLE, SSIM_DIVERSITY_IMAGES, calculate_fid, calculate_foreground_ratio,
                             calculate_lpips_diversity, calculate_ssim_diversity, calculate_ssim_nearest_real,
                             calculate_stroke_density, foreground_ratio_from_counts,
-                            fragmentation_from_counters, stroke_density_from_counts, stroke_geometry_from_counters,
-                            verifier_embedding_chunks)
+                            fragmentation_from_counters, shape_attributes_from_features, stroke_density_from_counts,
+                            stroke_geometry_from_counters, verifier_embedding_chunks)
 from .utils.neighbors import manifold_metrics
 
 THRESHOLD = 0.5          # the threshold compute_metrics passes to both statistics (evaluate_vanilla_gan_signatures.py:306,318)
@@ -178,6 +181,23 @@ class StrokeSink:
         return torch.cat(self.parts).cpu().numpy() if self.parts else np.zeros((0, 23), np.int32)
 
 
+class ShapeSink:
+    """Collects the six integer moment sums (shape.shape_sums_u8, int64 (B, 6)) of every uint8 batch it is shown while the batch
+    is on the device (--shape); ``features()`` brings them to the host at once and makes the (N, 8) features of them."""
+
+    def __init__(self) -> None:
+        self.parts, self.size = [], None
+
+    def update(self, u8: torch.Tensor) -> None:
+        from .shape import shape_sums_u8
+        self.size = int(u8.shape[-1])
+        self.parts.append(shape_sums_u8(u8.contiguous()))
+
+    def features(self) -> np.ndarray:
+        from .shape import features_from_sums
+        return features_from_sums(torch.cat(self.parts).cpu().numpy(), self.size)
+
+
 class SsimSink:
     """Keeps the bytes of every uint8 batch it is shown, on the device (--ssim): the pixel-space comparisons need the whole set
     at once.  ``images()``: all of them, uint8 (N, H, W)."""
@@ -197,12 +217,12 @@ def generate_samples(generator: Generator, n_samples: int, latent_dim: int, devi
                      keep_images: Optional[int] = None, threshold: float = THRESHOLD,
                      embedding_sink: Optional[EmbeddingSink] = None,
                      component_sink: Optional[ComponentSink] = None, ssim_sink: Optional[SsimSink] = None,
-                     stroke_sink: Optional[StrokeSink] = None) -> GeneratedSamples:
+                     stroke_sink: Optional[StrokeSink] = None, shape_sink: Optional[ShapeSink] = None) -> GeneratedSamples:
     """N samples, z = torch.randn per batch as the reference draws it (so a seed means the same).  ``keep_images``: how
     many leading samples to bring back as fp32 images (None: all, what the reference returns).  ``embedding_sink``: receives
     every batch's uint8 tensor while it is on the device; its finished statistics travel in the result.  ``component_sink``:
     is shown the same bytes and keeps their component counters; ``ssim_sink`` keeps the bytes themselves; ``stroke_sink``
-    keeps their stroke counters."""
+    keeps their stroke counters, ``shape_sink`` their moment sums."""
     generator.eval()
     eng = generator._require_engine()
     keep = n_samples if keep_images is None else max(0, min(int(keep_images), n_samples))
@@ -227,6 +247,8 @@ def generate_samples(generator: Generator, n_samples: int, latent_dim: int, devi
             ssim_sink.update(u8)
         if stroke_sink is not None:
             stroke_sink.update(u8)
+        if shape_sink is not None:
+            shape_sink.update(u8)
         if (i + 1) % 10 == 0 or i == n_batches - 1:
             print(f"  Generated {min((i + 1) * batch_size, n_samples)}/{n_samples} samples")
     s = generator.output_size
@@ -244,12 +266,13 @@ def generate_samples(generator: Generator, n_samples: int, latent_dim: int, devi
 
 def load_real_images(real_dir: Path, n_images: int, image_size: int, device: torch.device,
                      verifier_size: Optional[int] = None, component_sink: Optional[ComponentSink] = None,
-                     ssim_sink: Optional[SsimSink] = None, stroke_sink: Optional[StrokeSink] = None):
+                     ssim_sink: Optional[SsimSink] = None, stroke_sink: Optional[StrokeSink] = None,
+                     shape_sink: Optional[ShapeSink] = None):
     """Up to ``n_images`` files of ``real_dir`` as (N, 1, S, S) fp32 in [-1, 1] ON THE DEVICE: decoded and resized by the
     loader's helper (PIL -> 'L' -> bilinear), normalised by its byte table in the input-pipeline kernel.
     ``verifier_size``: -> (that tensor, the SAME files decoded at verifier_size as uint8 (N, V, V) on the device) -- what the
     reference's verifier sees of a real file, which it resizes from the file and not from a 128x128 copy.
-    ``component_sink`` / ``ssim_sink`` / ``stroke_sink``: are shown the decoded BYTES (the cache the normalisation reads), not
+    ``component_sink`` / ``ssim_sink`` / ``stroke_sink`` / ``shape_sink``: are shown the decoded BYTES (the cache the normalisation reads), not
     a re-quantised fp32 copy."""
     from . import _lib
     real_dir = Path(real_dir)
@@ -286,6 +309,8 @@ def load_real_images(real_dir: Path, n_images: int, image_size: int, device: tor
         ssim_sink.update(cache)
     if stroke_sink is not None:
         stroke_sink.update(cache)
+    if shape_sink is not None:
+        shape_sink.update(cache)
     index = torch.arange(n, dtype=torch.int32, device=dev)
     lut = normalize_lut((-1.0, 1.0)).to(dev)
     out = torch.empty(n, 1, image_size, image_size, dtype=torch.float32, device=dev)
@@ -396,7 +421,8 @@ def compute_metrics(fake_images, real_images: Optional[torch.Tensor], device: to
                     verifier: Optional[VerifierFeatures] = None, neighbors_k: Optional[int] = None,
                     verifier_real: Optional[torch.Tensor] = None, fragmentation: Optional[Dict[str, Any]] = None,
                     pixel_similarity: Optional[Dict[str, Any]] = None,
-                    stroke_geometry: Optional[Dict[str, Any]] = None) -> Dict[str, Any]:
+                    stroke_geometry: Optional[Dict[str, Any]] = None,
+                    shape_attributes: Optional[Dict[str, Any]] = None) -> Dict[str, Any]:
     """The report's ``metrics`` dictionary.  ``fake_images``: a GeneratedSamples (its counters are used) or a tensor.
     ``verifier``: add the Frechet distance over its embeddings (the ``verifier_*`` keys; none without it).
     ``verifier_real``: the real set as the verifier is to see it when that is not ``real_images`` (a 128x128 Generator: the
@@ -404,7 +430,8 @@ def compute_metrics(fake_images, real_images: Optional[torch.Tensor], device: to
     ``neighbors_k``: add precision / recall, density / coverage and the nearest-real distances at that k.
     ``fragmentation``: the finished ``fragmentation`` block (fragmentation_block), added as it is; no key without it.
     ``pixel_similarity``: likewise the finished ``pixel_similarity`` block (pixel_similarity_block); ``stroke_geometry``:
-    likewise the finished ``stroke_geometry`` block (stroke_geometry_block)."""
+    likewise the finished ``stroke_geometry`` block (stroke_geometry_block); ``shape_attributes``: likewise the finished
+    ``shape_attributes`` block (shape_attributes_block)."""
     metrics: Dict[str, Any] = {"n_samples": len(fake_images), "image_shape": list(fake_images.shape[1:]),
                                "metrics_computed_at": datetime.now().isoformat()}
     if real_images is not None and INCEPTION_AVAILABLE:
@@ -476,6 +503,9 @@ def compute_metrics(fake_images, real_images: Optional[torch.Tensor], device: to
         metrics["stroke_geometry"] = stroke_geometry
         g = stroke_geometry["generated"]
         print(f"  Pen width along the skeleton - Mean: {_fmt(g['mean_width'])}, skeleton length: {_fmt(g['skeleton_length']['mean'])}")
+    if shape_attributes is not None:
+        metrics["shape_attributes"] = shape_attributes
+        print(f"  Shape attributes - {_shape_line(shape_attributes['generated'])}")
     return metrics
 
 
@@ -497,6 +527,22 @@ def pixel_similarity_block(generated: SsimSink, real: Optional[SsimSink] = None)
         true = SsimSet(real.images())
         block["real_diversity"] = calculate_ssim_diversity(true)
         block["nearest_real"] = calculate_ssim_nearest_real(fake, true)
+    return block
+
+
+def _shape_line(d: Dict[str, Any]) -> str:
+    mean = lambda name: _fmt(None if d[name] is None else d[name]["mean"])                  # noqa: E731
+    return (f"slant {mean('slant')} (negative leans right), spread {mean('spread')}, mass {mean('mass')}, centre "
+            f"({mean('cx')}, {mean('cy')}), {d['empty']} empty")
+
+
+def shape_attributes_block(generated: ShapeSink, real: Optional[ShapeSink] = None) -> Dict[str, Any]:
+    """The report's ``shape_attributes`` key (--shape): {generated, real (only when a real set was measured)}, each side a
+    utils.metrics.shape_attributes_from_features dictionary: per ink moment (shape.FEATURES) the mean, standard deviation
+    and 5th / 50th / 95th percentiles over the set, from the exact integer sums of the bytes."""
+    block: Dict[str, Any] = {"generated": shape_attributes_from_features(generated.features())}
+    if real is not None and real.parts:
+        block["real"] = shape_attributes_from_features(real.features())
     return block
 
 
@@ -616,6 +662,11 @@ def print_summary(metrics: Dict[str, Any]) -> None:
                 print(f"{side.capitalize()}: pen width {_fmt(d['mean_width'])} px (thickest stroke {_fmt(d['thickest']['mean'])}), skeleton "
                       f"{_fmt(d['skeleton_length']['mean'])} px, {_fmt(d['endpoints']['mean'])} line ends, "
                       f"{_fmt(d['junction_pixels']['mean'])} junction pixels, {d['empty']} empty")
+    if "shape_attributes" in metrics:
+        print("\n--- Shape attributes (ink moments; coordinates in units of the image side) ---")
+        for side in ("generated", "real"):
+            if side in metrics["shape_attributes"]:
+                print(f"{side.capitalize()}: {_shape_line(metrics['shape_attributes'][side])}")
     print("\n" + bar)
 
 
@@ -627,6 +678,7 @@ class _Args(argparse.Namespace):
     components = None
     ssim = False
     strokes = False
+    shape = False
 
 
 def parse_args(argv=None) -> argparse.Namespace:
@@ -658,6 +710,10 @@ def parse_args(argv=None) -> argparse.Namespace:
                    help="Add a 'stroke_geometry' block to the report: skeleton length, line ends, junction pixels and a histogram of "
                         "local pen widths of every generated (and real) image, from a thinning and an exact distance map computed on "
                         "the device; needs no network weights")
+    p.add_argument("--shape", action="store_true", default=argparse.SUPPRESS,
+                   help="Add a 'shape_attributes' block to the report: mass, centre, second moments, slant and spread of every "
+                        "generated (and real) image's ink -- mean, standard deviation and 5 / 50 / 95th percentiles --, from exact "
+                        "integer sums computed on the device; needs no network weights")
     a = p.parse_args(argv, namespace=_Args())
     if a.components is not None and a.components != "auto" and a.components < 1:
         p.error("--components MIN_AREA must be >= 1")
@@ -684,10 +740,11 @@ def main(argv=None) -> int:
             frag_fake, frag_real = ComponentSink(min_area), ComponentSink(min_area)
         ssim_fake, ssim_real = (SsimSink(), SsimSink()) if a.ssim else (None, None)
         stroke_fake, stroke_real = (StrokeSink(), StrokeSink()) if a.strokes else (None, None)
+        shape_fake, shape_real = (ShapeSink(), ShapeSink()) if a.shape else (None, None)
         fake = generate_samples(generator, a.n_samples, generator.latent_dim, device, a.batch_size,
                                 keep_images=max(0, a.n_grids) * a.grid_size,
                                 embedding_sink=verifier.sink() if verifier is not None else None, component_sink=frag_fake,
-                                ssim_sink=ssim_fake, stroke_sink=stroke_fake)
+                                ssim_sink=ssim_fake, stroke_sink=stroke_fake, shape_sink=shape_fake)
         print("\nCreating sample grids...")
         grid_paths = create_sample_grids(fake, output_dir, a.n_grids, a.grid_size)
         real = verifier_real = None
@@ -696,17 +753,18 @@ def main(argv=None) -> int:
                 if verifier is not None and verifier.input_resize is not None:
                     real, verifier_real = load_real_images(real_dir, a.n_samples, generator.output_size, device, VERIFIER_IMAGE_SIZE,
                                                            component_sink=frag_real, ssim_sink=ssim_real,
-                                                           stroke_sink=stroke_real)
+                                                           stroke_sink=stroke_real, shape_sink=shape_real)
                 else:
                     real = load_real_images(real_dir, a.n_samples, generator.output_size, device, component_sink=frag_real,
-                                            ssim_sink=ssim_real, stroke_sink=stroke_real)
+                                            ssim_sink=ssim_real, stroke_sink=stroke_real, shape_sink=shape_real)
             except Exception as e:                              # noqa: BLE001 -- the evaluation goes on without them
                 print(f"Warning: Could not load real images: {e}")
         print("\nComputing evaluation metrics...")
         metrics = compute_metrics(fake, real, device, verifier, a.verifier_neighbors, verifier_real,
                                   fragmentation_block(frag_fake, frag_real) if frag_fake is not None else None,
                                   pixel_similarity_block(ssim_fake, ssim_real) if a.ssim else None,
-                                  stroke_geometry_block(stroke_fake, stroke_real) if a.strokes else None)
+                                  stroke_geometry_block(stroke_fake, stroke_real) if a.strokes else None,
+                                  shape_attributes_block(shape_fake, shape_real) if a.shape else None)
         report_path = save_evaluation_report(metrics, config, output_dir, checkpoint_path, grid_paths)
         print_summary(metrics)
         print("\nEvaluation complete!")

@@ -43,7 +43,16 @@ the device).  ``--diverse_real_dir DIR --diverse_memorisation_ratio R`` bars nea
 stops the run once nothing new is at least S away from what is kept -- fewer than ``--n_samples`` files may then be written.
 The files are in pick order, ``<prefix>_scores.json`` is the filter's, and ``<prefix>_diverse.json`` is the report: every pick's
 pool index, score and gain, and the nearest-neighbour distances inside this selection beside those of the plain top-n.  Whether
-a verifier trained on such a set is more accurate is not measured."""
+a verifier trained on such a set is more accurate is not measured.
+
+``--edit`` changes the shape of every generated signature before it is written (utils.inference.generate_signatures_edited: Adam
+on z around the ink moments' gradient, shape.shape_grad, on the device): ``--edit_slant_delta D`` adds D to the slant (the shear
+coefficient; NEGATIVE leans to the right, because the image's v axis points down), ``--edit_size_scale R`` makes the signature R
+times as large in the frame, ``--edit_boldness_scale R`` multiplies its ink mass, ``--edit_shift DX DY`` moves its centre (in
+units of the image side, DY downwards); ``--edit_keep W`` weighs staying the same signature.  The latent vectors are the ones
+the plain run draws for the same ``--seed``, so the two runs' files pair up.  ``<prefix>_edit.json`` records, per file, the
+features before, the targets, the features after and the objective before and after.  Whether an edit reaches its target
+depends on the checkpoint, and whether edited signatures help a verifier's training is not measured."""
 import argparse
 import json
 import os
@@ -54,7 +63,7 @@ import numpy as np
 import torch
 
 from .utils.inference import (Despeckle, PenWidth, generate_signatures_batch, generate_signatures_diverse, generate_signatures_filtered,
-                              generate_signatures_refined,
+                              generate_signatures_edited, generate_signatures_refined,
                               load_discriminator, load_generator, load_target_images, morph_sequence, morph_strip, process_images,
                               project_signatures)
 
@@ -214,6 +223,34 @@ def generate_refined(generator, discriminator, n_samples: int, output_dir: str, 
     print(f"Generated {len(images)} signatures saved to: {output_dir}")
     if after:
         print(f"Realism scores: mean {sum(before) / len(before):.4f} before, {sum(after) / len(after):.4f} after")
+
+
+def generate_edited(generator, discriminator, n_samples: int, output_dir: str, batch_size: int = 64,
+                    device: torch.device = torch.device("cuda"), seed: Optional[int] = None, prefix: str = "signature",
+                    threshold: Optional[int] = None, transparent: bool = False, noise_scale: float = 1.0,
+                    edit: Optional[Dict[str, Any]] = None) -> None:
+    """``n_samples`` generated signatures whose latent vectors were edited (``edit``: utils.inference.edit_latents' keyword
+    arguments), written in generation order under the usual names, plus ``<prefix>_edit.json``: {edit: the settings, records:
+    [{file, before, targets, after, objective_before, objective_after}, ...]} in the same order."""
+    os.makedirs(output_dir, exist_ok=True)
+    print(f"Output directory: {output_dir}")
+    print(f"Generating {n_samples} signatures, editing each for {edit['steps']} steps...")
+    images, records = generate_signatures_edited(generator, n_samples, generator.latent_dim, device, seed=seed, batch_size=batch_size,
+                                                 noise_scale=noise_scale, threshold=threshold, discriminator=discriminator, **edit)
+    if threshold is not None:
+        images = process_images(images, threshold=threshold, make_transparent=transparent)
+    print(f"Saving {len(images)} images...")
+    for i, (img, rec) in enumerate(zip(images, records)):
+        name = f"{prefix}_{i + 1:06d}.png"
+        img.save(os.path.join(output_dir, name), "PNG")
+        records[i] = {"file": name, **rec}
+    with open(os.path.join(output_dir, f"{prefix}_edit.json"), "w") as f:
+        json.dump({"edit": {k: (list(v) if isinstance(v, tuple) else v) for k, v in edit.items()}, "records": records}, f, indent=2)
+    print("\nGeneration complete!")
+    print(f"Generated {len(images)} signatures saved to: {output_dir}")
+    for name in sorted({k for r in records for k in r["targets"]}):
+        mean = lambda key: sum(r[key][name] for r in records) / len(records)              # noqa: E731
+        print(f"  {name}: mean {mean('before'):.5f} before, {mean('after'):.5f} after (target {mean('targets'):.5f})")
 
 
 def run_projection(generator, path: str, output_dir: str, prefix: str = "signature", steps: int = 200, lr: float = 0.05,
@@ -440,6 +477,24 @@ def diverse_opt(a: argparse.Namespace, name: str):
     return getattr(a, name, DIVERSE_DEFAULTS[name])
 
 
+# the --edit flags, kept out of the namespace the same way
+EDIT_DEFAULTS = dict(edit=False, edit_slant_delta=0.0, edit_size_scale=1.0, edit_boldness_scale=1.0, edit_shift=(0.0, 0.0),
+                     edit_steps=30, edit_lr=0.02, edit_keep=1.0, edit_realism_weight=0.0)
+
+
+def edit_opt(a: argparse.Namespace, name: str):
+    """A flag of EDIT_DEFAULTS: its value on the command line, else its default."""
+    return getattr(a, name, EDIT_DEFAULTS[name])
+
+
+def edit_kwargs(a: argparse.Namespace) -> Dict[str, Any]:
+    """utils.inference.edit_latents' keyword arguments of a command line with --edit."""
+    return dict(slant_delta=edit_opt(a, "edit_slant_delta"), size_scale=edit_opt(a, "edit_size_scale"),
+                boldness_scale=edit_opt(a, "edit_boldness_scale"), shift=tuple(edit_opt(a, "edit_shift")),
+                steps=edit_opt(a, "edit_steps"), lr=edit_opt(a, "edit_lr"), keep_weight=edit_opt(a, "edit_keep"),
+                realism_weight=edit_opt(a, "edit_realism_weight"))
+
+
 def identity_opt(a: argparse.Namespace, name: str):
     """A flag of IDENTITY_DEFAULTS: its value on the command line, else its default."""
     return getattr(a, name, IDENTITY_DEFAULTS[name])
@@ -540,7 +595,38 @@ def parse_args(argv=None) -> argparse.Namespace:
     p.add_argument("--diverse_min_separation", type=float, metavar="S", **later,
                    help="With --diverse: stop once no candidate is at least S (embedding distance) from everything kept; fewer "
                         "than n_samples may then be written (default: 0)")
+    p.add_argument("--edit", action="store_true", **later,
+                   help="Edit the shape of every generated signature (Adam on z around the ink moments' gradient, on the device) "
+                        "before it is written; the latent vectors are the plain run's for the same --seed; write "
+                        "<prefix>_edit.json (default: off)")
+    p.add_argument("--edit_slant_delta", type=float, metavar="D", **later,
+                   help="With --edit: add D to the slant, the shear coefficient sxy / syy; NEGATIVE leans to the right (default: 0)")
+    p.add_argument("--edit_size_scale", type=float, metavar="R", **later,
+                   help="With --edit: make the signature R times as large in the frame (its spread R^2 times) (default: 1)")
+    p.add_argument("--edit_boldness_scale", type=float, metavar="R", **later,
+                   help="With --edit: multiply the signature's ink mass by R (default: 1)")
+    p.add_argument("--edit_shift", type=float, nargs=2, metavar=("DX", "DY"), **later,
+                   help="With --edit: move the ink's centre by (DX, DY) in units of the image side, DY downwards (default: 0 0)")
+    p.add_argument("--edit_steps", type=int, **later, help="Adam iterations of an edit (default: 30)")
+    p.add_argument("--edit_lr", type=float, **later, help="Adam learning rate of an edit (default: 0.02)")
+    p.add_argument("--edit_keep", type=float, metavar="W", **later,
+                   help="With --edit: weight of staying the same signature, mean((G(z) - G(z0))^2) (default: 1)")
+    p.add_argument("--edit_realism_weight", type=float, metavar="W", **later,
+                   help="With --edit: weight of -log D(G(z)); needs the checkpoint's Discriminator (default: 0)")
     a = p.parse_args(argv)
+    if edit_opt(a, "edit"):
+        for flag, on in (("filter_by_realism", a.filter_by_realism), ("refine_by_realism", opt(a, "refine_by_realism")),
+                         ("adapt", adapt_opt(a, "adapt") is not None), ("project", a.project is not None), ("morph", a.morph is not None),
+                         ("pen_width", hasattr(a, "pen_width")), ("despeckle", hasattr(a, "despeckle"))):
+            if on:
+                p.error(f"--edit edits the plain generation run only; it cannot be combined with --{flag}")
+        from .utils.inference import check_edit
+        try:
+            check_edit(**edit_kwargs(a), has_discriminator=True)
+        except ValueError as e:
+            p.error(f"--edit: {e}")
+    elif any(hasattr(a, k) for k in EDIT_DEFAULTS):
+        p.error("the --edit_* flags need --edit")
     if diverse_opt(a, "diverse"):
         if not a.filter_by_realism:
             p.error("--diverse needs --filter_by_realism")
@@ -676,7 +762,11 @@ def main(argv=None) -> None:
             run_morph(generator, a.morph, a.output_dir, device, a.prefix, a.morph_frames, a.seed, a.threshold, a.transparent,
                       a.project_steps, a.project_lr, a.project_restarts)
         return
-    if opt(a, "refine_by_realism"):
+    if edit_opt(a, "edit"):
+        kw = edit_kwargs(a)
+        generate_edited(generator, need_discriminator("--edit_realism_weight") if kw["realism_weight"] > 0 else None, a.n_samples,
+                        a.output_dir, a.batch_size, device, a.seed, a.prefix, a.threshold, a.transparent, a.noise_scale, kw)
+    elif opt(a, "refine_by_realism"):
         generate_refined(generator, need_discriminator("--refine_by_realism"), a.n_samples, a.output_dir, a.batch_size, device, a.seed,
                          a.prefix, opt(a, "refine_steps"), opt(a, "refine_lr"), opt(a, "refine_prior"), a.threshold, a.transparent,
                          a.noise_scale, **with_despeckle(despeckle_opt(a)))

@@ -20,7 +20,11 @@ Adam loop on z around Engine.g_latent_objective_grad) instead of throwing low-sc
 beside its pixel error.  ``adopt_discriminator`` brings the Discriminator into the Generator's context for them.
 
 ``generate_signatures_diverse`` takes the filter's pool and selects from it for diversity in the verifier's embedding space
-(utils/diverse.py) instead of keeping the top of the ranking."""
+(utils/diverse.py) instead of keeping the top of the ranking.
+
+``edit_latents`` changes a generated signature's shape attributes -- slant, size, boldness, position: the ink moments of
+shape.py -- while it stays the same signature: an Adam loop on z around shape.shape_grad, whose image-space gradient the seeded
+Engine.g_latent_objective_grad carries to z; ``generate_signatures_edited`` is generation on top of it."""
 import math
 from typing import Any, Dict, List, Optional, Tuple
 
@@ -718,6 +722,164 @@ def generate_signatures_refined(generator: Generator, discriminator: Discriminat
         before.append(p0); after.append(p1)
     host = lambda ts: [float(x) for x in torch.cat(ts).cpu()]
     return images, host(after), host(before)
+
+
+# ---- shape-attribute editing: slant, size, boldness, position ----------------------------------------------------------------
+def check_edit(slant_delta=0.0, size_scale=1.0, boldness_scale=1.0, shift=(0.0, 0.0), steps=30, lr=0.02, keep_weight=1.0,
+               realism_weight=0.0, prior_weight=0.0, shape_weight=1.0, has_discriminator=False):
+    """The host-side refusals of edit_latents, raised as ValueError before anything is allocated.  Returns the edit as floats:
+    (slant_delta, size_scale, boldness_scale, (dx, dy)).  Pure host code."""
+    try:
+        shift = tuple(float(v) for v in shift)
+    except TypeError:
+        shift = ()
+    if len(shift) != 2:
+        raise ValueError("shift must be two numbers (dx, dy)")
+    edit = (float(slant_delta), float(size_scale), float(boldness_scale), shift)
+    if not all(math.isfinite(v) for v in edit[:3] + shift):
+        raise ValueError(f"the edit must be finite, got {edit}")
+    if not edit[1] > 0 or not edit[2] > 0:
+        raise ValueError(f"size_scale and boldness_scale must be > 0, got {edit[1]}, {edit[2]}")
+    if edit == (0.0, 1.0, 1.0, (0.0, 0.0)):
+        raise ValueError("no edit was asked for: give slant_delta != 0, size_scale != 1, boldness_scale != 1 or shift != (0, 0)")
+    if steps < 1 or not lr > 0:
+        raise ValueError(f"steps must be >= 1 and lr > 0, got {steps}, {lr}")
+    w = (float(keep_weight), float(realism_weight), float(prior_weight), float(shape_weight))
+    if any(not math.isfinite(x) or x < 0.0 for x in w):
+        raise ValueError(f"keep_weight, realism_weight, prior_weight and shape_weight must be finite and >= 0, got {w}")
+    if not w[3] > 0:
+        raise ValueError("an edit follows the shape objective: shape_weight must be > 0")
+    if w[1] > 0 and not has_discriminator:
+        raise ValueError("realism_weight > 0 needs the Discriminator")
+    return edit
+
+
+def edit_targets(features0: torch.Tensor, slant_delta: float = 0.0, size_scale: float = 1.0, boldness_scale: float = 1.0,
+                 shift: Tuple[float, float] = (0.0, 0.0), shape_weight: float = 1.0) -> Tuple[torch.Tensor, torch.Tensor]:
+    """(weights, targets), both fp64 (N, 8) where ``features0`` (N, 8) fp64 lives: what an edit asks of shape.shape_grad, from
+    each start image's own features f0.  Targets: slant f0 + slant_delta; spread f0 * size_scale^2 (a signature R times as
+    large has R^2 times the spread; sxx, syy and sxy get no target of their own); mass f0 * boldness_scale; cx f0 + dx and
+    cy f0 + dy (``shift`` is one edit: both coordinates are held).  An edit left at its default gets weight 0 -- its target
+    column holds f0 and is not looked at.  Weights: shape_weight / scale_k, so that one knob serves all: scale 1 for slant
+    and the centre, max(f0_k^2, 1e-6) for mass and spread (their residuals are then relative).  Torch only, no
+    synchronisation; works on the CPU."""
+    from ..shape import CX, CY, MASS, SLANT, SPREAD
+    f0 = features0
+    if not isinstance(f0, torch.Tensor) or f0.dtype != torch.float64 or f0.dim() != 2 or f0.shape[1] != 8:
+        raise ValueError("features0 must be a float64 (N, 8) tensor")
+    w, t = torch.zeros_like(f0), f0.clone()
+    def relative(k):                                           # (tensor / tensor: a correctly rounded division)
+        scale = torch.clamp(f0[:, k] * f0[:, k], min=1e-6)
+        return torch.full_like(scale, float(shape_weight)) / scale
+
+    if slant_delta != 0.0:
+        t[:, SLANT] = f0[:, SLANT] + float(slant_delta)
+        w[:, SLANT] = float(shape_weight)
+    if size_scale != 1.0:
+        t[:, SPREAD] = f0[:, SPREAD] * (float(size_scale) * float(size_scale))
+        w[:, SPREAD] = relative(SPREAD)
+    if boldness_scale != 1.0:
+        t[:, MASS] = f0[:, MASS] * float(boldness_scale)
+        w[:, MASS] = relative(MASS)
+    if tuple(shift) != (0.0, 0.0):
+        t[:, CX], t[:, CY] = f0[:, CX] + float(shift[0]), f0[:, CY] + float(shift[1])
+        w[:, CX] = w[:, CY] = float(shape_weight)
+    return w.contiguous(), t.contiguous()
+
+
+def edit_latents(generator: Generator, z0: torch.Tensor, slant_delta: float = 0.0, size_scale: float = 1.0,
+                 boldness_scale: float = 1.0, shift: Tuple[float, float] = (0.0, 0.0), steps: int = 30, lr: float = 0.02,
+                 betas: Tuple[float, float] = (0.9, 0.999), keep_weight: float = 1.0, discriminator: Optional[Discriminator] = None,
+                 realism_weight: float = 0.0, prior_weight: float = 0.0, shape_weight: float = 1.0):
+    """Move the latent vectors ``z0`` (N, latent) so that their signatures lean more (``slant_delta`` is added to the slant; a
+    NEGATIVE delta leans to the right, because the image's v axis points down), sit larger in the frame (``size_scale`` R: the
+    spread becomes R^2 times what it is), carry more ink (``boldness_scale``: the mass is multiplied) or move (``shift``
+    (dx, dy) in units of the image side, dy downwards) -- while staying the same signature.  The shape objective is
+    shape.shape_grad's with edit_targets' weights and targets, from each start image's own features f0 = shape(G(z0));
+    staying the same is the reconstruction term keep_weight * mean((G(z) - t0)^2) against the bytes t0 generate_uint8 gives at
+    z0; ``realism_weight`` (needs ``discriminator``, brought in by adopt_discriminator) and ``prior_weight`` are refine_latents'.
+
+    ``steps`` iterations of Adam on z, every iteration Engine.g_forward(z) -> shape.shape_grad (the image-space gradient of the
+    shape objective at G(z)) -> the seeded Engine.g_latent_objective_grad (J_G^T of it joins dz) -> the shape objective added
+    in torch -> Engine.op_adam, in chunks of the engine's max_batch (refine_plan), all enqueued without a host
+    synchronisation.  The Generator must be in eval() mode; its weights and BatchNorm buffers do not move.
+
+    Returns (z (N, latent) fp32 device tensor, images (N, S, S) uint8 numpy -- generate_uint8 at z --, features_before (N, 8)
+    fp64 device tensor, features_after (N, 8): at the returned z, targets (N, 8): edit_targets' (a column without an edit holds
+    f0), history (steps + 1, N) fp32 device tensor: the full objective at the start of every iteration and, last, AT the
+    returned z).  A call that asks for no edit raises ValueError.  Whether an edit reaches its target depends on the
+    Generator; nothing here promises it."""
+    from ..shape import _shape_grad_checked, shape_features
+    edit = check_edit(slant_delta, size_scale, boldness_scale, shift, steps, lr, keep_weight, realism_weight, prior_weight,
+                      shape_weight, discriminator is not None)
+    if generator.training:
+        raise ValueError("edit_latents needs the Generator in eval() mode (running BatchNorm statistics)")
+    eng = adopt_discriminator(generator, discriminator) if realism_weight > 0 else generator._require_engine()
+    dev, latent, size = eng.device, eng.latent_dim, eng.image_size
+    z0 = torch.as_tensor(z0, dtype=torch.float32)
+    if z0.dim() != 2 or z0.shape[1] != latent:
+        raise ValueError(f"z0 must be (N, {latent}), got {tuple(z0.shape)}")
+    n = z0.shape[0]
+    z_all = z0.to(dev).contiguous().clone()
+    before, after, targets = (torch.empty(n, 8, dtype=torch.float64, device=dev) for _ in range(3))
+    hist = torch.empty(steps + 1, n, dtype=torch.float32, device=dev)
+    for t0, b in refine_plan(n, eng.max_batch):
+        z = z_all[t0:t0 + b]                                   # (a contiguous view: Adam updates the returned tensor in place)
+        f0 = shape_features(eng.g_forward(z, training=False))
+        w, t = edit_targets(f0, *edit, shape_weight=shape_weight)
+        before[t0:t0 + b], targets[t0:t0 + b] = f0, t
+        keep = eng.g_generate_u8(z) if keep_weight > 0 else None
+        dx = torch.empty(b, 1, size, size, dtype=torch.float32, device=dev)
+        shape_obj = torch.empty(b, dtype=torch.float32, device=dev)
+
+        def grad(k, z, dz, out):
+            img = eng.g_forward(z, training=False)
+            feats = _shape_grad_checked(img, b, size, dev, w, t, dx, shape_obj)[2]
+            eng.g_latent_objective_grad(z, keep, keep_weight, realism_weight, prior_weight, dz_out=dz, objective_out=out, image_grad=dx)
+            out += shape_obj
+            if k == steps:
+                after[t0:t0 + b] = feats
+
+        hist[:steps, t0:t0 + b] = _descend(eng, z, steps, lr, betas, grad, hist[steps, t0:t0 + b])
+    u8 = np.empty((n, size, size), dtype=np.uint8)
+    for t0, b in refine_plan(n, eng.max_batch):
+        u8[t0:t0 + b] = generate_uint8(generator, z_all[t0:t0 + b])
+    return z_all, u8, before, after, targets, hist
+
+
+def generate_signatures_edited(generator: Generator, n_signatures: int, latent_dim: int, device: torch.device,
+                               seed: Optional[int] = None, batch_size: int = 32, noise_scale: float = 1.0,
+                               threshold: Optional[int] = None, **edit) -> Tuple[List[Any], List[Dict[str, Any]]]:
+    """Generation with every latent vector edited (edit_latents; ``edit``: its keyword arguments) before its image is made.
+    The latent vectors are the ones generate_signatures_batch draws for the same ``seed``, ``batch_size`` and ``noise_scale``
+    (one seeding, then z = randn * noise_scale per batch; the edit draws nothing), so image i of this run is the edited
+    image i of the plain run.  Returns (PIL 'L' images in generation order -- binarised when ``threshold`` is given --,
+    records): per image {before, targets, after} -- the eight features by name, ``targets`` only those the edit weighs --
+    and {objective_before, objective_after}, the ends of the objective's history."""
+    from PIL import Image
+    from ..shape import CX, CY, FEATURES, MASS, SLANT, SPREAD
+    if threshold is not None and not 0 <= int(threshold) <= 255:
+        raise ValueError(f"threshold must be a byte value, got {threshold}")
+    asked = check_edit(**{k: v for k, v in edit.items() if k not in ("betas", "discriminator")},
+                       has_discriminator=edit.get("discriminator") is not None)
+    edited = sorted(([SLANT] if asked[0] != 0.0 else []) + ([SPREAD] if asked[1] != 1.0 else [])
+                    + ([MASS] if asked[2] != 1.0 else []) + ([CX, CY] if asked[3] != (0.0, 0.0) else []))
+    _seed_batch(seed)
+    images, records, done = [], [], 0
+    while done < n_signatures:
+        b = min(batch_size, n_signatures - done)
+        z = torch.randn(b, latent_dim, device=device) * noise_scale
+        _, u8, before, after, targets, hist = edit_latents(generator, z, **edit)
+        if threshold is not None:
+            u8 = binarize_uint8(u8, threshold)
+        images += [Image.fromarray(arr, mode="L") for arr in u8]
+        before, after, targets, hist = before.cpu().numpy(), after.cpu().numpy(), targets.cpu().numpy(), hist.cpu().numpy()
+        for i in range(b):
+            named = lambda row, ks=range(8): {FEATURES[k]: float(row[k]) for k in ks}          # noqa: E731
+            records.append({"before": named(before[i]), "targets": named(targets[i], edited), "after": named(after[i]),
+                            "objective_before": float(hist[0, i]), "objective_after": float(hist[-1, i])})
+        done += b
+    return images, records
 
 
 def check_identity_projection(generator, verifier, identity_weight, identity_score_weight, verifier_resize=False):

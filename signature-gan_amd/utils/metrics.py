@@ -282,6 +282,44 @@ def calculate_stroke_geometry(images: torch.Tensor, threshold: int = 128) -> Dic
     return stroke_geometry_from_counters(stroke_stats(images.contiguous(), threshold).cpu().numpy())
 
 
+# ---- shape attributes: ink moments (shape.py) --------------------------------------------------------------------------------
+def shape_attributes_from_features(features) -> Dict[str, Any]:
+    """The shape-attribute dictionary from (N, 8) features (shape.FEATURES), pure numpy: {images, empty, and per feature name
+    {mean, std, p5, p50, p95}}.  mass is summarised over every image, the other seven over the images that have ink (None where
+    there is none): an empty image has no centre, size or slant.  A signature leaning to the right has a NEGATIVE slant."""
+    from ..shape import FEATURES, MASS
+    f = np.asarray(features, dtype=np.float64).reshape(-1, len(FEATURES))
+    if f.shape[0] == 0:
+        raise ValueError("no images")
+    has = f[:, MASS] > 0.0
+    out: Dict[str, Any] = {"images": int(f.shape[0]), "empty": int((~has).sum())}
+    for k, name in enumerate(FEATURES):
+        v = f[:, k] if k == MASS else f[has, k]
+        if len(v) == 0:
+            out[name] = None
+            continue
+        p5, p50, p95 = np.percentile(v, [5, 50, 95])
+        out[name] = {"mean": float(np.mean(v)), "std": float(np.std(v)), "p5": float(p5), "p50": float(p50), "p95": float(p95)}
+    return out
+
+
+def calculate_shape_attributes(images: torch.Tensor) -> Dict[str, Any]:
+    """Where the ink of ``images`` sits, how far it spreads and how it leans: uint8 (B, S, S) / (B, 1, S, S) -- exact integer sums
+    on the device (shape.shape_sums_u8), turned into features on the host (shape.features_from_sums) -- or fp32 in [-1, 1]
+    (shape.shape_features, fp64 on the device), S = 64 or 128.  Only (B, 6) or (B, 8) numbers reach the host; a structural
+    metric that needs no network weights.  Returns shape_attributes_from_features' dictionary."""
+    from ..shape import features_from_sums, shape_features, shape_sums_u8
+    if not isinstance(images, torch.Tensor):
+        raise ValueError(f"images must be a tensor, got {type(images).__name__}")
+    if images.device.type != "cuda":
+        if not torch.cuda.is_available():
+            raise RuntimeError("the moments are summed on a ROCm device ('cuda:N'); there is no CPU path")
+        images = images.cuda()
+    if images.dtype == torch.uint8:
+        return shape_attributes_from_features(features_from_sums(shape_sums_u8(images.contiguous()).cpu().numpy(), images.shape[-1]))
+    return shape_attributes_from_features(shape_features(images.detach().to(torch.float32).contiguous()).cpu().numpy())
+
+
 # ---- pixel-space similarity: SSIM (ssim.py) ---------------------------------------------------------------------------------
 SSIM_DIVERSITY_IMAGES = 512           # a set's diversity is taken over at most its first 512 images (131 k pairs)
 
