@@ -1,5 +1,5 @@
 """ctypes binding of the C ABI in include/siggan.h (and siggan_mlp.h, siggan_verifier.h, siggan_verifier_grad.h, siggan_verifier_pairs.h, siggan_verifier_topk.h,
-siggan_verifier_train.h, siggan_verifier_data.h, siggan_moments.h, siggan_select.h, siggan_neighbors.h, siggan_resize.h, siggan_components.h, siggan_ssim.h, siggan_strokes.h, siggan_diverse.h, siggan_shape.h).
+siggan_verifier_train.h, siggan_verifier_data.h, siggan_moments.h, siggan_select.h, siggan_neighbors.h, siggan_resize.h, siggan_components.h, siggan_ssim.h, siggan_strokes.h, siggan_diverse.h, siggan_shape.h, siggan_twosample.h).
 
 The shared library is built in-tree by ``__graft_entry__.build()`` / ``csrc/Makefile`` and must be
 present: there is no CPU or PyTorch fallback for this path -- a missing or stale library raises.
@@ -314,6 +314,21 @@ _SHAPE_SIGNATURES = {
 }
 SHAPE_EXPORTS = tuple(_SHAPE_SIGNATURES)
 
+# quadratic forms of an implicit kernel matrix with 0/1 group indicators (include/siggan_twosample.h): context-free, new symbols again
+KERNEL_POLY, KERNEL_RBF = 0, 1
+TWOSAMPLE_MAX_N, TWOSAMPLE_MAX_COLS, TWOSAMPLE_MAX_DIM, TWOSAMPLE_ROW_BLOCK = 16384, 4096, 1024, 32
+
+
+class KernelSpec(C.Structure):            # siggan_kernel_spec
+    _fields_ = [("kind", C.c_int32), ("degree", C.c_int32), ("gamma", C.c_double), ("coef0", C.c_double)]
+
+
+_TWOSAMPLE_SIGNATURES = {
+    "siggan_kernel_forms_workspace": (C.c_size_t, [_I32, _I32]),
+    "siggan_kernel_forms": (C.c_int, [_I32, _P, _I32, _I32, C.POINTER(KernelSpec), _P, _I32, _P, _P, _P, C.c_size_t, _P]),
+}
+TWOSAMPLE_EXPORTS = tuple(_TWOSAMPLE_SIGNATURES)
+
 _lib = None
 
 
@@ -331,7 +346,7 @@ def load():
                               **_VERIFIER_TOPK_SIGNATURES, **_VERIFIER_TRAIN_SIGNATURES,
                               **_VERIFIER_DATA_SIGNATURES, **_MOMENTS_SIGNATURES, **_SELECT_SIGNATURES,
                               **_NEIGHBORS_SIGNATURES, **_RESIZE_SIGNATURES, **_COMPONENTS_SIGNATURES, **_SSIM_SIGNATURES,
-                              **_STROKES_SIGNATURES, **_DIVERSE_SIGNATURES, **_SHAPE_SIGNATURES}.items():
+                              **_STROKES_SIGNATURES, **_DIVERSE_SIGNATURES, **_SHAPE_SIGNATURES, **_TWOSAMPLE_SIGNATURES}.items():
         fn = getattr(lib, name)          # AttributeError if the library does not export the symbol
         fn.restype, fn.argtypes = res, args
     if lib.siggan_abi_version() != ABI_VERSION:

@@ -17,7 +17,12 @@ Every generated batch's bytes go through ``embed_u8`` into an fp64 accumulator w
 precision / recall, density / coverage and the distance from every generated sample to its nearest real one, against the
 real set's own leave-one-out distances -- the memorisation check.  The embeddings of both sets are then also kept in a
 device buffer, and exact fp64 k-nearest-neighbour queries run there (utils/neighbors.py); k-lists and counts reach the
-host.  A 128x128 Generator's bytes are shrunk to the verifier's 64x64 on the device first (resize.py: Pillow's antialiased
+host.  ``--verifier_kid [PERMUTATIONS]`` (with ``--verifier_checkpoint`` and ``--real_dir``) adds the report key
+``verifier_two_sample``: the Kernel Inception Distance (unbiased MMD^2 under the cubic polynomial kernel, mean and standard
+deviation over 100 subsets) and a permutation test of the RBF-kernel MMD^2 with its p-value -- can the generated set be told
+from the real one, and by more than chance at this sample size?  The embeddings are kept as for ``--verifier_neighbors``;
+fp64 quadratic forms of the implicit kernel matrix run on the device (utils/twosample.py), three numbers per subset or
+permutation reach the host.  A 128x128 Generator's bytes are shrunk to the verifier's 64x64 on the device first (resize.py: Pillow's antialiased
 bilinear filter, byte for byte what the reference's verifier transform makes of the written PNG), the real files are
 decoded at 64x64 for the verifier, and the report says so in ``verifier_input_resize``.
 ``--strokes`` adds the report key ``stroke_geometry``: skeleton length, line ends, junction pixels and a histogram of local
@@ -47,7 +52,7 @@ from .utils.metrics import (INCEPTION_AVAILABLE, LPIPS_AVAILABLE, SSIM_DIVERSITY
                             calculate_lpips_diversity, calculate_ssim_diversity, calculate_ssim_nearest_real,
                             calculate_stroke_density, foreground_ratio_from_counts,
                             fragmentation_from_counters, shape_attributes_from_features, stroke_density_from_counts,
-                            stroke_geometry_from_counters, verifier_embedding_chunks)
+                            stroke_geometry_from_counters, two_sample_metrics, verifier_embedding_chunks)
 from .utils.neighbors import manifold_metrics
 
 THRESHOLD = 0.5          # the threshold compute_metrics passes to both statistics (evaluate_vanilla_gan_signatures.py:306,318)
@@ -130,9 +135,11 @@ class VerifierFeatures:
     ``input_resize``: None for a 64x64 Generator; for another size the name of the resize the generated bytes take on the
     device before the verifier sees them (``verifier_input_resize`` in the report)."""
 
-    def __init__(self, checkpoint: Path, device: torch.device, image_size: int, neighbors_k: Optional[int] = None) -> None:
+    def __init__(self, checkpoint: Path, device: torch.device, image_size: int, neighbors_k: Optional[int] = None,
+                 keep_embeddings: bool = False) -> None:
         self.checkpoint, self.model, self.error = str(checkpoint), None, None
         self.neighbors_k = neighbors_k                          # --verifier_neighbors: the sinks keep their embeddings
+        self.keep_embeddings = bool(keep_embeddings)            # --verifier_kid: likewise
         self.input_resize = (None if image_size == VERIFIER_IMAGE_SIZE
                              else f"pillow_bilinear_{image_size}_to_{VERIFIER_IMAGE_SIZE}")
         try:
@@ -144,7 +151,8 @@ class VerifierFeatures:
     def sink(self) -> Optional[EmbeddingSink]:
         if self.model is None:
             return None
-        return EmbeddingSink(self.model, keep=self.neighbors_k is not None, resize=self.input_resize is not None)
+        return EmbeddingSink(self.model, keep=self.neighbors_k is not None or self.keep_embeddings,
+                             resize=self.input_resize is not None)
 
 
 class ComponentSink:
@@ -358,7 +366,7 @@ def _verifier_frechet(metrics: Dict[str, Any], fake_images, real_images: Optiona
                       verifier: VerifierFeatures) -> Optional[torch.Tensor]:
     """The ``verifier_*`` keys of the report; any failure is recorded as ``verifier_frechet_error``, like ``fid_error``.
     ``real_images``: what the verifier is to see of the real set -- fp32 (N, 1, 64, 64) or uint8 (N, 64, 64).
-    -> the real images' embeddings when the sink kept them (``--verifier_neighbors``), else None."""
+    -> the real images' embeddings when the sink kept them (``--verifier_neighbors``, ``--verifier_kid``), else None."""
     metrics["verifier_checkpoint"] = verifier.checkpoint
     metrics["verifier_input_resize"] = verifier.input_resize
     real_embeddings = None
@@ -417,12 +425,39 @@ def _verifier_neighbors(metrics: Dict[str, Any], fake_images, real_embeddings: O
         metrics["verifier_neighbors_error"] = str(e)
 
 
+TWO_SAMPLE_SEED = 0      # the subsets and permutations of --verifier_kid do not move with --seed: a p-value is comparable across runs
+
+
+def _verifier_two_sample(metrics: Dict[str, Any], fake_images, real_embeddings: Optional[torch.Tensor],
+                         verifier: Optional[VerifierFeatures], permutations: int) -> None:
+    """The key ``--verifier_kid`` adds, ``verifier_two_sample`` = {kid, mmd_test, n_real, n_generated}, from the embeddings
+    both sinks kept; any failure is recorded as ``verifier_two_sample_error`` and the key is None."""
+    print("Computing verifier KID and the MMD permutation test...")
+    try:
+        if verifier is None:
+            raise ValueError("--verifier_kid needs --verifier_checkpoint")
+        if verifier.error:
+            raise ValueError(verifier.error)
+        fake_embeddings = getattr(fake_images, "embeddings", None)
+        if fake_embeddings is None:
+            raise ValueError("the generated samples were not embedded")
+        if real_embeddings is None:
+            raise ValueError(metrics.get("verifier_frechet_error") or "no real images provided")
+        m = metrics["verifier_two_sample"] = two_sample_metrics(real_embeddings, fake_embeddings, permutations, seed=TWO_SAMPLE_SEED)
+        print(f"  Verifier KID: {m['kid']['kid_mean']:.6f} +- {m['kid']['kid_std']:.6f}, "
+              f"MMD^2: {m['mmd_test']['mmd2']:.6f} (p = {m['mmd_test']['p_value']:.4f})")
+    except Exception as e:                                      # noqa: BLE001 -- the report records any failure
+        print(f"  Skipping verifier KID / MMD test: {e}")
+        metrics["verifier_two_sample"], metrics["verifier_two_sample_error"] = None, str(e)
+
+
 def compute_metrics(fake_images, real_images: Optional[torch.Tensor], device: torch.device,
                     verifier: Optional[VerifierFeatures] = None, neighbors_k: Optional[int] = None,
                     verifier_real: Optional[torch.Tensor] = None, fragmentation: Optional[Dict[str, Any]] = None,
                     pixel_similarity: Optional[Dict[str, Any]] = None,
                     stroke_geometry: Optional[Dict[str, Any]] = None,
-                    shape_attributes: Optional[Dict[str, Any]] = None) -> Dict[str, Any]:
+                    shape_attributes: Optional[Dict[str, Any]] = None,
+                    kid_permutations: Optional[int] = None) -> Dict[str, Any]:
     """The report's ``metrics`` dictionary.  ``fake_images``: a GeneratedSamples (its counters are used) or a tensor.
     ``verifier``: add the Frechet distance over its embeddings (the ``verifier_*`` keys; none without it).
     ``verifier_real``: the real set as the verifier is to see it when that is not ``real_images`` (a 128x128 Generator: the
@@ -431,7 +466,8 @@ def compute_metrics(fake_images, real_images: Optional[torch.Tensor], device: to
     ``fragmentation``: the finished ``fragmentation`` block (fragmentation_block), added as it is; no key without it.
     ``pixel_similarity``: likewise the finished ``pixel_similarity`` block (pixel_similarity_block); ``stroke_geometry``:
     likewise the finished ``stroke_geometry`` block (stroke_geometry_block); ``shape_attributes``: likewise the finished
-    ``shape_attributes`` block (shape_attributes_block)."""
+    ``shape_attributes`` block (shape_attributes_block).  ``kid_permutations``: add ``verifier_two_sample``, the KID and
+    the MMD permutation test with that many permutations."""
     metrics: Dict[str, Any] = {"n_samples": len(fake_images), "image_shape": list(fake_images.shape[1:]),
                                "metrics_computed_at": datetime.now().isoformat()}
     if real_images is not None and INCEPTION_AVAILABLE:
@@ -467,6 +503,8 @@ def compute_metrics(fake_images, real_images: Optional[torch.Tensor], device: to
         real_embeddings = _verifier_frechet(metrics, fake_images, real_images if verifier_real is None else verifier_real, verifier)
     if neighbors_k is not None:
         _verifier_neighbors(metrics, fake_images, real_embeddings, verifier, neighbors_k)
+    if kid_permutations is not None:
+        _verifier_two_sample(metrics, fake_images, real_embeddings, verifier, kid_permutations)
 
     print("Computing stroke density distribution...")
     try:
@@ -621,6 +659,18 @@ def print_summary(metrics: Dict[str, Any]) -> None:
             v = metrics[key]
             print(f"Verifier {label}: {v:.4f} ({hint}, k = {metrics.get('verifier_neighbors_k')})" if v is not None
                   else f"Verifier {label}: Not computed - {metrics.get('verifier_neighbors_error', 'unknown reason')}")
+    if "verifier_two_sample" in metrics:
+        ts = metrics["verifier_two_sample"]
+        if ts is None:
+            why = metrics.get("verifier_two_sample_error", "unknown reason")
+            print(f"Verifier KID: Not computed - {why}")
+            print(f"Verifier MMD test: Not computed - {why}")
+        else:
+            k, t = ts["kid"], ts["mmd_test"]
+            print(f"Verifier KID: {k['kid_mean']:.6f} +- {k['kid_std']:.6f} ({k['subsets']} subsets of {k['subset_size']}, lower is "
+                  f"better; full sets {k['kid_full']:.6f})")
+            print(f"Verifier MMD^2 ({t['kind']}, gamma {t['gamma']:.4g}): {t['mmd2']:.6f}, p = {t['p_value']:.4f} over "
+                  f"{t['permutations']} permutations (null 95% quantile {t['null_q95']:.6f}; small p = the sets can be told apart)")
     print("\n--- Stroke Analysis ---")
     stroke = metrics.get("stroke_density")
     if stroke:
@@ -675,6 +725,7 @@ class _Args(argparse.Namespace):
     without them parses to the reference's attributes and nothing else."""
     verifier_checkpoint = None
     verifier_neighbors = None
+    verifier_kid = None
     components = None
     ssim = False
     strokes = False
@@ -698,6 +749,10 @@ def parse_args(argv=None) -> argparse.Namespace:
     p.add_argument("--verifier_neighbors", type=int, default=None, metavar="K",
                    help="With --verifier_checkpoint and --real_dir: adds precision / recall, density / coverage and "
                         "nearest-real distances over the verifier's embeddings, from K nearest neighbours")
+    p.add_argument("--verifier_kid", nargs="?", type=int, const=1000, default=argparse.SUPPRESS, metavar="PERMUTATIONS",
+                   help="With --verifier_checkpoint and --real_dir: adds the Kernel Inception Distance (mean and standard deviation "
+                        "over 100 subsets) and a permutation test of the RBF-kernel MMD with PERMUTATIONS label permutations over "
+                        "the verifier's embeddings")
     p.add_argument("--components", nargs="?", type=lambda v: v if v == "auto" else int(v), const="auto", default=None, metavar="MIN_AREA",
                    help="Label the ink components of every generated (and real) image on the device and add a 'fragmentation' "
                         "block to the report; a component of fewer than MIN_AREA pixels counts as a speck "
@@ -715,6 +770,8 @@ def parse_args(argv=None) -> argparse.Namespace:
                         "generated (and real) image's ink -- mean, standard deviation and 5 / 50 / 95th percentiles --, from exact "
                         "integer sums computed on the device; needs no network weights")
     a = p.parse_args(argv, namespace=_Args())
+    if a.verifier_kid is not None and a.verifier_kid < 1:
+        p.error("--verifier_kid PERMUTATIONS must be >= 1")
     if a.components is not None and a.components != "auto" and a.components < 1:
         p.error("--components MIN_AREA must be >= 1")
     return a
@@ -732,7 +789,8 @@ def main(argv=None) -> int:
     real_dir = Path(a.real_dir) if a.real_dir else None
     try:
         generator, config = load_generator_from_checkpoint(checkpoint_path, device)
-        verifier = (VerifierFeatures(Path(a.verifier_checkpoint), device, generator.output_size, a.verifier_neighbors)
+        verifier = (VerifierFeatures(Path(a.verifier_checkpoint), device, generator.output_size, a.verifier_neighbors,
+                                     keep_embeddings=a.verifier_kid is not None)
                     if a.verifier_checkpoint else None)
         frag_fake = frag_real = None
         if a.components is not None:
@@ -764,7 +822,8 @@ def main(argv=None) -> int:
                                   fragmentation_block(frag_fake, frag_real) if frag_fake is not None else None,
                                   pixel_similarity_block(ssim_fake, ssim_real) if a.ssim else None,
                                   stroke_geometry_block(stroke_fake, stroke_real) if a.strokes else None,
-                                  shape_attributes_block(shape_fake, shape_real) if a.shape else None)
+                                  shape_attributes_block(shape_fake, shape_real) if a.shape else None,
+                                  kid_permutations=a.verifier_kid)
         report_path = save_evaluation_report(metrics, config, output_dir, checkpoint_path, grid_paths)
         print_summary(metrics)
         print("\nEvaluation complete!")

@@ -12,7 +12,9 @@ texts are the reference's, so callers (the evaluation CLI) report them the same 
 construction over a network the user trains here: ``calculate_verifier_frechet_distance``, a Frechet distance between two
 image sets in the Siamese verifier's embedding space (utils/frechet.py; the statistics are accumulated on the device),
 and ``calculate_verifier_manifold_metrics``: precision / recall, density / coverage and nearest-real distances in that space
-(utils/neighbors.py; exact fp64 nearest-neighbour queries on the device)."""
+(utils/neighbors.py; exact fp64 nearest-neighbour queries on the device), and ``calculate_verifier_two_sample``: the Kernel
+Inception Distance and a permutation test of the kernel MMD in that space (utils/twosample.py; fp64 quadratic forms of the
+implicit kernel matrix on the device)."""
 from collections import defaultdict
 from typing import Any, Dict, List, Optional, Union
 
@@ -22,6 +24,7 @@ import torch
 from .._lib import IS_INK_SIGNED, IS_INK_UNIT, IS_NEG
 from .frechet import FeatureMoments, embedding_spread, frechet_distance
 from .neighbors import manifold_metrics
+from .twosample import kid, mmd_permutation_test
 
 try:
     from torchvision.models import inception_v3  # noqa: F401
@@ -114,6 +117,32 @@ def calculate_verifier_manifold_metrics(real_images: torch.Tensor, fake_images: 
     real_emb = verifier_embeddings(real_images.to(dev), verifier, max_batch)
     fake_emb = verifier_embeddings(fake_images.to(dev), verifier, max_batch)
     out = manifold_metrics(real_emb, fake_emb, k)
+    out["embedding_dim"] = int(verifier.embedding_dim)
+    return out
+
+
+# ---- KID and the MMD permutation test over verifier embeddings (device quadratic forms, host statistics) ---------------
+def two_sample_metrics(real_emb: torch.Tensor, fake_emb: torch.Tensor, permutations: int = 1000, subsets: int = 100,
+                       seed: int = 0) -> Dict[str, Any]:
+    """{'kid': utils.twosample.kid's dictionary, 'mmd_test': utils.twosample.mmd_permutation_test's (RBF, median
+    heuristic), 'n_real', 'n_generated'} of two (n, dim) fp32 embedding sets on one ROCm device."""
+    return {"kid": kid(real_emb, fake_emb, subsets=subsets, seed=seed),
+            "mmd_test": mmd_permutation_test(real_emb, fake_emb, permutations=permutations, seed=seed),
+            "n_real": int(real_emb.shape[0]), "n_generated": int(fake_emb.shape[0])}
+
+
+def calculate_verifier_two_sample(real_images: torch.Tensor, fake_images: torch.Tensor, verifier, permutations: int = 1000,
+                                  subsets: int = 100, seed: int = 0, max_batch: Optional[int] = None) -> Dict[str, Any]:
+    """The Kernel Inception Distance and the RBF MMD permutation test of two image sets in the embedding space of ``verifier``
+    (as for ``calculate_verifier_frechet_distance``: the same image formats, the same chunks).  At least 2 images per set,
+    else ValueError.  -> ``two_sample_metrics``' dictionary plus 'embedding_dim'."""
+    dev = next(verifier.parameters()).device
+    if real_images.shape[0] < 2 or fake_images.shape[0] < 2:
+        raise ValueError(f"a two-sample statistic needs at least 2 images per set, got {real_images.shape[0]} and "
+                         f"{fake_images.shape[0]}")
+    real_emb = verifier_embeddings(real_images.to(dev), verifier, max_batch)
+    fake_emb = verifier_embeddings(fake_images.to(dev), verifier, max_batch)
+    out = two_sample_metrics(real_emb, fake_emb, permutations, subsets, seed)
     out["embedding_dim"] = int(verifier.embedding_dim)
     return out
 
