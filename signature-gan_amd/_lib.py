@@ -1,5 +1,5 @@
-"""ctypes binding of the C ABI in include/siggan.h (and siggan_mlp.h, siggan_verifier.h, siggan_verifier_grad.h, siggan_verifier_pairs.h, siggan_verifier_topk.h,
-siggan_verifier_train.h, siggan_verifier_data.h, siggan_moments.h, siggan_select.h, siggan_neighbors.h, siggan_resize.h, siggan_components.h, siggan_ssim.h, siggan_strokes.h, siggan_diverse.h, siggan_shape.h, siggan_twosample.h).
+"""ctypes binding of the C ABI in include/siggan.h and the siggan_*.h headers beside it: one table of signatures per header,
+all of them in ``GROUPS``.
 
 The shared library is built in-tree by ``__graft_entry__.build()`` / ``csrc/Makefile`` and must be
 present: there is no CPU or PyTorch fallback for this path -- a missing or stale library raises.
@@ -329,6 +329,14 @@ _TWOSAMPLE_SIGNATURES = {
 }
 TWOSAMPLE_EXPORTS = tuple(_TWOSAMPLE_SIGNATURES)
 
+# every table above, in the order the symbols joined the ABI: load() binds them, build() checks the library exports them.
+# A new header adds its table here and nowhere else.
+GROUPS = (_SIGNATURES, _VERIFIER_SIGNATURES, _VERIFIER_GRAD_SIGNATURES, _VERIFIER_PAIRS_SIGNATURES, _VERIFIER_TOPK_SIGNATURES,
+          _VERIFIER_TRAIN_SIGNATURES, _VERIFIER_DATA_SIGNATURES, _MOMENTS_SIGNATURES, _SELECT_SIGNATURES, _NEIGHBORS_SIGNATURES,
+          _RESIZE_SIGNATURES, _COMPONENTS_SIGNATURES, _SSIM_SIGNATURES, _STROKES_SIGNATURES, _DIVERSE_SIGNATURES, _SHAPE_SIGNATURES,
+          _TWOSAMPLE_SIGNATURES)
+ALL_EXPORTS = tuple(name for group in GROUPS for name in group)
+
 _lib = None
 
 
@@ -342,13 +350,10 @@ def load():
             f"{LIB_PATH} is missing: build it with `python -c 'import __graft_entry__ as g; g.build()'` "
             "(or `make -C signature-gan_amd/csrc`). This path has no CPU/PyTorch fallback.")
     lib = C.CDLL(LIB_PATH)
-    for name, (res, args) in {**_SIGNATURES, **_VERIFIER_SIGNATURES, **_VERIFIER_GRAD_SIGNATURES, **_VERIFIER_PAIRS_SIGNATURES,
-                              **_VERIFIER_TOPK_SIGNATURES, **_VERIFIER_TRAIN_SIGNATURES,
-                              **_VERIFIER_DATA_SIGNATURES, **_MOMENTS_SIGNATURES, **_SELECT_SIGNATURES,
-                              **_NEIGHBORS_SIGNATURES, **_RESIZE_SIGNATURES, **_COMPONENTS_SIGNATURES, **_SSIM_SIGNATURES,
-                              **_STROKES_SIGNATURES, **_DIVERSE_SIGNATURES, **_SHAPE_SIGNATURES, **_TWOSAMPLE_SIGNATURES}.items():
-        fn = getattr(lib, name)          # AttributeError if the library does not export the symbol
-        fn.restype, fn.argtypes = res, args
+    for group in GROUPS:
+        for name, (res, args) in group.items():
+            fn = getattr(lib, name)      # AttributeError if the library does not export the symbol
+            fn.restype, fn.argtypes = res, args
     if lib.siggan_abi_version() != ABI_VERSION:
         raise RuntimeError(f"libsiggan_hip.so ABI {lib.siggan_abi_version()} != expected {ABI_VERSION}; rebuild")
     _lib = lib

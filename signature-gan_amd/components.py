@@ -9,13 +9,12 @@ is untouched.  Ink is ``byte < threshold``, the rule of ``gather_u8``'s binarize
 All three take a contiguous uint8 device tensor (N, H, W) or (N, 1, H, W) with 1 <= H <= 128 and W a multiple of 4 in
 4..128, run one kernel on the current stream and never synchronise the host.  Arguments are validated before the library is
 touched; there is no CPU path.  Everything is integer arithmetic: equal input gives bit-equal output."""
-import ctypes as C
 from typing import Optional
 
-import numpy as np
 import torch
 
-from . import _lib
+from . import _call, _lib
+from ._call import as_int, ptr
 
 # columns of component_stats (SIGGAN_CC_*)
 INK, COMPONENTS, LARGEST, SMALL_COMPONENTS, SMALL_INK, X0, Y0, X1, Y1 = range(9)
@@ -30,28 +29,12 @@ def default_min_area(height: int, width: int) -> int:
     return max(2, int(round(0.001 * int(height) * int(width))))
 
 
-def _int(value, what: str) -> int:
-    if isinstance(value, bool) or not isinstance(value, (int, np.integer)):
-        raise ValueError(f"{what} must be an integer, got {value!r}")
-    return int(value)
-
-
 def check_arguments(u8, threshold, connectivity, min_area, fill=255):
     """The refusals that need no device, in a fixed order: type, dtype, rank, sizes, parameters, device, layout.
     Returns (n, h, w, threshold, connectivity, min_area, fill) with min_area resolved."""
-    if not isinstance(u8, torch.Tensor):
-        raise ValueError(f"images must be a tensor, got {type(u8).__name__}")
-    if u8.dtype != torch.uint8:
-        raise ValueError(f"images must be torch.uint8, got {u8.dtype}")
-    if not (u8.dim() == 3 or (u8.dim() == 4 and u8.shape[1] == 1)):
-        raise ValueError(f"images must be (N, H, W) or (N, 1, H, W), got {tuple(u8.shape)}")
-    n, h, w = u8.shape[0], u8.shape[-2], u8.shape[-1]
-    if not 1 <= h <= _lib.CC_MAX_SIZE:
-        raise ValueError(f"height = {h} outside [1, {_lib.CC_MAX_SIZE}]")
-    if not 4 <= w <= _lib.CC_MAX_SIZE or w % 4:
-        raise ValueError(f"width = {w} must be a multiple of 4 in [4, {_lib.CC_MAX_SIZE}]")
-    threshold, connectivity, fill = _int(threshold, "threshold"), _int(connectivity, "connectivity"), _int(fill, "fill")
-    min_area = default_min_area(h, w) if min_area is None else _int(min_area, "min_area")
+    n, h, w = _call.check_u8_images(u8, "images", 1, 4, _lib.CC_MAX_SIZE, True)
+    threshold, connectivity, fill = as_int(threshold, "threshold"), as_int(connectivity, "connectivity"), as_int(fill, "fill")
+    min_area = default_min_area(h, w) if min_area is None else as_int(min_area, "min_area")
     if not 1 <= threshold <= 255:
         raise ValueError(f"threshold = {threshold} outside [1, 255]")
     if connectivity not in (4, 8):
@@ -60,21 +43,15 @@ def check_arguments(u8, threshold, connectivity, min_area, fill=255):
         raise ValueError(f"min_area = {min_area} < 1")
     if not threshold <= fill <= 255:
         raise ValueError(f"fill = {fill} outside [threshold = {threshold}, 255]: a cleaned pixel must not be ink")
-    if u8.device.type != "cuda":
-        raise ValueError("images must live on a ROCm device ('cuda:N'); there is no CPU path")
-    if not u8.is_contiguous():
-        raise ValueError("images must be contiguous")
+    _call.check_resident(u8, "images")
     return n, h, w, threshold, connectivity, min_area, fill
 
 
 def _run(u8, n, h, w, threshold, connectivity, min_area, fill, stats=None, root=None, clean=None):
     if n == 0:
         return
-    device = u8.device.index if u8.device.index is not None else torch.cuda.current_device()
-    stream = C.c_void_p(torch.cuda.current_stream(u8.device).cuda_stream)
-    ptr = lambda t: C.c_void_p(t.data_ptr() if t is not None else None)          # noqa: E731
-    _lib.check(_lib.load().siggan_components_u8(device, ptr(u8), n, h, w, threshold, connectivity, min_area, fill, ptr(stats),
-                                                ptr(root), ptr(clean), stream))
+    _lib.check(_lib.load().siggan_components_u8(_call.device_of(u8).index, ptr(u8), n, h, w, threshold, connectivity, min_area, fill,
+                                                ptr(stats), ptr(root), ptr(clean), _call.stream(u8.device)))
 
 
 def component_stats(u8: torch.Tensor, threshold: int = 128, connectivity: int = 8, min_area: Optional[int] = None) -> torch.Tensor:
@@ -101,15 +78,7 @@ def despeckle_u8(u8: torch.Tensor, threshold: int = 128, connectivity: int = 8, 
     does not overlap it; ``stats``, a contiguous int32 (N, 9) device tensor, receives component_stats' counters of the INPUT
     from the same launch (small_components / small_ink are what the cleaning removes)."""
     n, h, w, threshold, connectivity, min_area, fill = check_arguments(u8, threshold, connectivity, min_area, fill)
-    if out is None:
-        out = torch.empty_like(u8)
-    elif (not isinstance(out, torch.Tensor) or out.dtype != torch.uint8 or out.device != u8.device or not out.is_contiguous()
-          or out.numel() != u8.numel()):
-        raise ValueError(f"out must be a contiguous torch.uint8 tensor of {u8.numel()} elements on {u8.device}")
-    elif out.data_ptr() != u8.data_ptr() and (out.data_ptr() < u8.data_ptr() + u8.numel() and u8.data_ptr() < out.data_ptr() + out.numel()):
-        raise ValueError("out overlaps the input without being the input")
-    if stats is not None and (not isinstance(stats, torch.Tensor) or stats.dtype != torch.int32 or stats.device != u8.device
-                              or not stats.is_contiguous() or tuple(stats.shape) != (n, 9)):
-        raise ValueError(f"stats must be a contiguous torch.int32 tensor ({n}, 9) on {u8.device}")
+    out = _call.check_out_u8(out, u8)
+    _call.check_stats(stats, n, 9, u8.device)
     _run(u8, n, h, w, threshold, connectivity, min_area, fill, stats=stats, clean=out)
     return out

@@ -28,6 +28,7 @@
 
 #include "../../include/siggan_components.h"
 #include "host.h"
+#include "ink_rows.h"
 
 namespace {
 
@@ -59,13 +60,6 @@ template <typename M> __device__ __forceinline__ int start_in_pair(M starts, int
     const int two = (int)(starts >> (2 * k)) & 3;
     return two ? 2 * k + ((two & 1) ? 0 : 1) : -1;
 }
-
-// Slot tid, tid + THREADS, ... as (row, column pair) without a division per slot.
-struct SlotWalk {
-    int slot, y, k, dy, dk, wh;
-    __device__ SlotWalk(int first, int wh_) : slot(first), y(first / wh_), k(first % wh_), dy(THREADS / wh_), dk(THREADS % wh_), wh(wh_) {}
-    __device__ void next() { slot += THREADS; y += dy; k += dk; if (k >= wh) { k -= wh; ++y; } }
-};
 
 __device__ __forceinline__ int load_lab(const int* lab, int x) { return __atomic_load_n(lab + x, __ATOMIC_RELAXED); }
 
@@ -119,18 +113,17 @@ __global__ __launch_bounds__(THREADS) void k_components(const uint8_t* u8, int h
     __syncthreads();
     const int nseg = (w + 63) >> 6;
     for (int item = wave; item < h * nseg; item += THREADS / 64) {
-        const int y = item / nseg, seg = item - y * nseg, x = seg * 64 + lane;
-        const bool ink = x < w && (int)simg[y * w + x] < thr;
-        const uint64_t m = __ballot(ink);
+        const int y = item / nseg, seg = item - y * nseg;
+        const uint64_t m = ink_word(simg, w, y, seg, lane, thr);
         if (lane == 0) smask[2 * y + seg] = m;
     }
     __syncthreads();
 
     // 3. join every run with the runs it touches in the row above
     int bad = 0;
-    for (SlotWalk t(wh + tid, wh); t.slot < nodes && !bad; t.next()) {
+    for (RowWalk t(wh + tid, THREADS, wh); t.i < nodes && !bad; t.next()) {       // slot t.i = (row t.y, column pair t.x)
         const M m = row_mask<M>(smask, t.y);
-        const int s = start_in_pair(run_starts(m), t.k);
+        const int s = start_in_pair(run_starts(m), t.x);
         if (s < 0) continue;
         const int e = run_end(m, s, w);                                  // the run is [s, e)
         const M up = row_mask<M>(smask, t.y - 1), ups = run_starts(up);
@@ -138,7 +131,7 @@ __global__ __launch_bounds__(THREADS) void k_components(const uint8_t* u8, int h
         while (touch && !bad) {
             const int b = ctz(touch);
             const int us = top((M)(ups & below<M>(b + 1))), ue = run_end(up, b, w);   // the run above holding b is [us, ue)
-            join(lab, t.slot, (t.y - 1) * wh + (us >> 1), nodes, bad);
+            join(lab, t.i, (t.y - 1) * wh + (us >> 1), nodes, bad);
             touch &= ~below<M>(ue);
         }
     }
@@ -150,13 +143,13 @@ __global__ __launch_bounds__(THREADS) void k_components(const uint8_t* u8, int h
     //    of a run that is no root only ever holds its link.
     bad = 0;
     int ink = 0;
-    for (SlotWalk t(tid, wh); t.slot < nodes && !bad; t.next()) {
+    for (RowWalk t(tid, THREADS, wh); t.i < nodes && !bad; t.next()) {
         const M m = row_mask<M>(smask, t.y);
-        const int s = start_in_pair(run_starts(m), t.k);
+        const int s = start_in_pair(run_starts(m), t.x);
         if (s < 0) continue;
         const int len = run_end(m, s, w) - s;
-        const int r = find_root(lab, t.slot, nodes, bad);
-        if (r != t.slot) __atomic_store_n(lab + t.slot, r, __ATOMIC_RELAXED);
+        const int r = find_root(lab, t.i, nodes, bad);
+        if (r != t.i) __atomic_store_n(lab + t.i, r, __ATOMIC_RELAXED);
         ink += len;
         atomicAdd(lab + r, len << 16);
     }
@@ -170,10 +163,10 @@ __global__ __launch_bounds__(THREADS) void k_components(const uint8_t* u8, int h
     // 5. counters
     if (stats) {
         int comps = 0, largest = 0, small = 0, small_ink = 0, x0 = INT_MAX, y0 = INT_MAX, x1 = -1, y1 = -1;
-        for (SlotWalk t(tid, wh); t.slot < nodes; t.next()) {
-            const int slot = t.slot, y = t.y;
+        for (RowWalk t(tid, THREADS, wh); t.i < nodes; t.next()) {
+            const int slot = t.i, y = t.y;
             const M m = row_mask<M>(smask, y);
-            const int s = start_in_pair(run_starts(m), t.k);
+            const int s = start_in_pair(run_starts(m), t.x);
             if (s < 0) continue;
             const int e = run_end(m, s, w);
             const int r = lab[slot] & 0xffff, area = lab[r] >> 16;
@@ -249,20 +242,12 @@ __global__ __launch_bounds__(THREADS) void k_components(const uint8_t* u8, int h
 extern "C" int siggan_components_u8(int32_t device, const uint8_t* u8_dev, int32_t batch, int32_t height, int32_t width,
                                     int32_t threshold, int32_t connectivity, int32_t min_area, int32_t fill,
                                     int32_t* stats_dev, int32_t* root_dev, uint8_t* clean_dev, void* stream) {
-    if (!u8_dev) return FAIL(SIGGAN_E_INVALID, "null image tensor");
-    if (!stats_dev && !root_dev && !clean_dev) return FAIL(SIGGAN_E_INVALID, "no output: give stats_dev, root_dev or clean_dev");
-    if (batch < 1) return FAIL(SIGGAN_E_INVALID, "batch = %d < 1", batch);
-    if (height < 1 || height > SIGGAN_CC_MAX_SIZE) return FAIL(SIGGAN_E_INVALID, "height = %d outside [1, %d]", height, SIGGAN_CC_MAX_SIZE);
-    if (width < 4 || width > SIGGAN_CC_MAX_SIZE || (width & 3))
-        return FAIL(SIGGAN_E_INVALID, "width = %d must be a multiple of 4 in [4, %d]", width, SIGGAN_CC_MAX_SIZE);
-    if (threshold < 1 || threshold > 255) return FAIL(SIGGAN_E_INVALID, "threshold = %d outside [1, 255]", threshold);
+    const char* no_output = !stats_dev && !root_dev && !clean_dev ? "no output: give stats_dev, root_dev or clean_dev" : nullptr;
+    if (int rc = ink_refuse_images(u8_dev, no_output, batch, height, width, SIGGAN_CC_MAX_SIZE, threshold)) return rc;
     if (connectivity != 4 && connectivity != 8) return FAIL(SIGGAN_E_INVALID, "connectivity must be 4 or 8, got %d", connectivity);
     if (min_area < 1) return FAIL(SIGGAN_E_INVALID, "min_area = %d < 1", min_area);
-    if (fill < threshold || fill > 255)
-        return FAIL(SIGGAN_E_INVALID, "fill = %d outside [threshold = %d, 255]: a cleaned pixel must not be ink", fill, threshold);
-    if ((reinterpret_cast<uintptr_t>(u8_dev) | reinterpret_cast<uintptr_t>(stats_dev) | reinterpret_cast<uintptr_t>(root_dev) |
-         reinterpret_cast<uintptr_t>(clean_dev)) & 3)
-        return FAIL(SIGGAN_E_INVALID, "u8_dev, stats_dev, root_dev and clean_dev must be 4-byte aligned");
+    if (int rc = ink_refuse_fill(fill, threshold, "a cleaned pixel must not be ink")) return rc;
+    if (int rc = ink_refuse_unaligned({u8_dev, stats_dev, root_dev, clean_dev}, "u8_dev, stats_dev, root_dev and clean_dev")) return rc;
     const size_t lds = (size_t)16 * height + (size_t)3 * height * width;     // masks + labels (2 B per pixel) + image
     DevGuard dg(device); HIPCHK(dg.err);
     void (*kernel)(const uint8_t*, int, int, int, int, int, int32_t*, int32_t*, uint8_t*) =

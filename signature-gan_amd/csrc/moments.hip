@@ -15,6 +15,7 @@
 
 #include "../../include/siggan_moments.h"
 #include "host.h"
+#include "rows_f64.h"                                    // double4_t, nothing else: the operand layout here differs
 
 struct siggan_moments {
     int device, dim;
@@ -25,7 +26,6 @@ struct siggan_moments {
 
 namespace {
 
-typedef double double4_t __attribute__((ext_vector_type(4)));
 constexpr int MT = 16;                                   // tile edge
 
 // grid: T * (T + 1) / 2 blocks of one wave, T = ceil(dim / 16); block t is the t-th tile of the upper triangle, row-major

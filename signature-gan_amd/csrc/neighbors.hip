@@ -2,14 +2,10 @@
 // (include/siggan_neighbors.h), on v_mfma_f64_16x16x4_f64.  gfx950 only.
 //
 // One tile kernel, k_neighbors, with two epilogues.  A workgroup of four waves owns 16 query rows; wave w walks the
-// reference tiles w, w + 4, ... of 16 rows each.  The MFMA takes the reference rows as A and the query rows as B, so by
-// the f64 C/D map (col = l & 15, row = (l >> 4) + 4 * reg -- NOT the f32 16x16 map) lane l holds query i0 + (l & 15)
-// against the references j0 + (l >> 4) + 4 * reg: one query per lane, hence ONE sorted k-list (distance, row number) per
-// lane, touched only when a candidate beats its last entry.
-//
-// Operands: lane l loads features kb .. kb + 3, kb = 16 c + 4 (l >> 4), of row (l & 15) per 16-feature chunk c (one 16-byte
-// load when the rows allow it) and feeds element e to the chunk's MFMA step e.  Which feature sits in which k slot of a
-// step does not matter as long as A and B agree, and they do.  Features past dim and rows past the set load as 0.0.
+// reference tiles w, w + 4, ... of 16 rows each.  Operands, accumulator map and the order of summation are rows_f64.h's:
+// the MFMA takes the reference rows as A and the query rows as B, so lane l holds query i0 + (l & 15) against the
+// references j0 + (l >> 4) + 4 * reg: one query per lane, hence ONE sorted k-list (distance, row number) per lane, touched
+// only when a candidate beats its last entry.
 //
 // d2 = max(0, (|q|^2 + |r|^2) - 2 q.r).  The norms are the diagonals of the MFMA products R R^T (per reference tile) and
 // Q Q^T (once per wave) over the SAME chunk and step order as the dot products: a row against a bit-identical row
@@ -26,29 +22,11 @@
 
 #include "../../include/siggan_neighbors.h"
 #include "host.h"
+#include "rows_f64.h"
 
 namespace {
 
-typedef double double4_t __attribute__((ext_vector_type(4)));
-constexpr int NT = 16;                                   // tile edge: query rows per workgroup, reference rows per tile
 constexpr int WAVES = 4;
-constexpr int CHUNK = 16;                                // features per K chunk: four MFMA steps of four
-
-// features kb .. kb + 3 of one row; VEC: dim % 4 == 0 and 16-byte aligned bases, so kb < dim covers all four
-template <bool VEC>
-__device__ __forceinline__ float4 load4(const float* __restrict__ row, bool row_ok, int kb, int dim) {
-    float4 v = {0.f, 0.f, 0.f, 0.f};
-    if (!row_ok) return v;
-    if (VEC) {
-        if (kb < dim) v = *reinterpret_cast<const float4*>(row + kb);
-    } else {
-        if (kb < dim) v.x = row[kb];
-        if (kb + 1 < dim) v.y = row[kb + 1];
-        if (kb + 2 < dim) v.z = row[kb + 2];
-        if (kb + 3 < dim) v.w = row[kb + 3];
-    }
-    return v;
-}
 
 __device__ __forceinline__ bool before(double d, int j, double ld, int lj) { return (d < ld) | ((d == ld) & (j < lj)); }
 
@@ -86,22 +64,13 @@ __global__ __launch_bounds__(64 * WAVES) void k_neighbors(const float* __restric
     const bool q_ok = i < nq;
     const float* qrow = q + (size_t)(q_ok ? i : 0) * (size_t)dim;
 
-    // |q_i|^2: the diagonal of Q Q^T, element (x, x) in lane ((x & 3) << 4 | x), register x >> 2
-    double qn;
-    {
-        double4_t acc = {0.0, 0.0, 0.0, 0.0};
-        for (int c0 = 0; c0 < dim; c0 += CHUNK) {
-            const float4 b = load4<VEC>(qrow, q_ok, c0 + 4 * g, dim);
-            acc = __builtin_amdgcn_mfma_f64_16x16x4f64((double)b.x, (double)b.x, acc, 0, 0, 0);
-            acc = __builtin_amdgcn_mfma_f64_16x16x4f64((double)b.y, (double)b.y, acc, 0, 0, 0);
-            acc = __builtin_amdgcn_mfma_f64_16x16x4f64((double)b.z, (double)b.z, acc, 0, 0, 0);
-            acc = __builtin_amdgcn_mfma_f64_16x16x4f64((double)b.w, (double)b.w, acc, 0, 0, 0);
-        }
-        const int src = ((x & 3) << 4) | x;
-        const double d0 = __shfl(acc[0], src), d1 = __shfl(acc[1], src), d2 = __shfl(acc[2], src), d3 = __shfl(acc[3], src);
-        const int reg = x >> 2;
-        qn = reg == 0 ? d0 : reg == 1 ? d1 : reg == 2 ? d2 : d3;
+    // |q_i|^2: the diagonal of Q Q^T
+    double4_t qq = {0.0, 0.0, 0.0, 0.0};
+    for (int c0 = 0; c0 < dim; c0 += CHUNK) {
+        const float4 b = load4<VEC>(qrow, q_ok, c0 + 4 * g, dim);
+        chunk_mfma(qq, b, b);
     }
+    const double qn = diagonal_of(qq, x);
 
     double ld[KC];
     int lj[KC];
@@ -119,14 +88,7 @@ __global__ __launch_bounds__(64 * WAVES) void k_neighbors(const float* __restric
             const int kb = c0 + 4 * g;
             const float4 a = load4<VEC>(rrow, r_ok, kb, dim);
             const float4 b = load4<VEC>(qrow, q_ok, kb, dim);
-            dot = __builtin_amdgcn_mfma_f64_16x16x4f64((double)a.x, (double)b.x, dot, 0, 0, 0);
-            nrm = __builtin_amdgcn_mfma_f64_16x16x4f64((double)a.x, (double)a.x, nrm, 0, 0, 0);
-            dot = __builtin_amdgcn_mfma_f64_16x16x4f64((double)a.y, (double)b.y, dot, 0, 0, 0);
-            nrm = __builtin_amdgcn_mfma_f64_16x16x4f64((double)a.y, (double)a.y, nrm, 0, 0, 0);
-            dot = __builtin_amdgcn_mfma_f64_16x16x4f64((double)a.z, (double)b.z, dot, 0, 0, 0);
-            nrm = __builtin_amdgcn_mfma_f64_16x16x4f64((double)a.z, (double)a.z, nrm, 0, 0, 0);
-            dot = __builtin_amdgcn_mfma_f64_16x16x4f64((double)a.w, (double)b.w, dot, 0, 0, 0);
-            nrm = __builtin_amdgcn_mfma_f64_16x16x4f64((double)a.w, (double)a.w, nrm, 0, 0, 0);
+            chunk_mfma_with_norm(dot, nrm, a, b);
         }
 #pragma unroll
         for (int reg = 0; reg < 4; ++reg) {
@@ -208,10 +170,6 @@ int check_sets(const char* who, const float* q, int nq, const float* r, int nr, 
     return SIGGAN_OK;
 }
 
-bool rows_allow_16_byte_loads(const float* q, const float* r, int dim) {
-    return (dim & 3) == 0 && ((reinterpret_cast<uintptr_t>(q) | reinterpret_cast<uintptr_t>(r)) & 15) == 0;
-}
-
 }  // namespace
 
 extern "C" int siggan_knn(int32_t device, const float* q_dev, int32_t nq, const float* r_dev, int32_t nr, int32_t dim, int32_t k,
@@ -222,7 +180,7 @@ extern "C" int siggan_knn(int32_t device, const float* q_dev, int32_t nq, const 
     const int avail = nr - (exclude_diagonal ? 1 : 0);
     if (k > avail) return FAIL(SIGGAN_E_INVALID, "siggan_knn: k = %d exceeds the %d reference rows a query may take", k, avail);
     DevGuard dg(device); HIPCHK(dg.err);
-    const bool vec = rows_allow_16_byte_loads(q_dev, r_dev, dim);
+    const bool vec = rows_allow_16_byte_loads(dim, q_dev, r_dev);
     const hipStream_t st = (hipStream_t)stream;
     const int excl = exclude_diagonal ? 1 : 0;
     if (k == 1)      launch<1, false>(vec, st, q_dev, nq, r_dev, nr, dim, k, excl, dist2_dev, index_dev, nullptr, nullptr);
@@ -238,7 +196,7 @@ extern "C" int siggan_ball_count(int32_t device, const float* q_dev, int32_t nq,
     if (int rc = check_sets("siggan_ball_count", q_dev, nq, r_dev, nr, dim)) return rc;
     if (!radius2_dev || !count_dev) return FAIL(SIGGAN_E_INVALID, "siggan_ball_count: null tensor");
     DevGuard dg(device); HIPCHK(dg.err);
-    launch<1, true>(rows_allow_16_byte_loads(q_dev, r_dev, dim), (hipStream_t)stream, q_dev, nq, r_dev, nr, dim, 0, 0, nullptr,
+    launch<1, true>(rows_allow_16_byte_loads(dim, q_dev, r_dev), (hipStream_t)stream, q_dev, nq, r_dev, nr, dim, 0, 0, nullptr,
                     nullptr, radius2_dev, count_dev);
     HIPCHK(hipGetLastError());
     return SIGGAN_OK;

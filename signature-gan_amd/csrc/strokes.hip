@@ -25,6 +25,7 @@
 
 #include "../../include/siggan_strokes.h"
 #include "host.h"
+#include "ink_rows.h"
 #include "strokes_word.h"
 
 namespace {
@@ -38,7 +39,6 @@ __host__ __device__ constexpr size_t lds_bytes(int h, int w, bool distance) {
     return (size_t)48 * h + 4 * (FLAGS + STATS) + (distance ? (size_t)h * w : 0);
 }
 
-__device__ __forceinline__ int bit_at(const uint64_t* m, int y, int x) { return (int)(m[2 * y + (x >> 6)] >> (x & 63)) & 1; }
 // Four bits (0/1 bytes of one word) times v: bit j -> byte j.
 __device__ __forceinline__ unsigned spread4(int four) { return (four & 1) | ((four & 2) << 7) | ((four & 4) << 14) | ((four & 8) << 21); }
 
@@ -60,9 +60,7 @@ __global__ __launch_bounds__(THREADS) void k_strokes(const uint8_t* u8, int h, i
     // 1. row masks
     const uint8_t* src = u8 + img * hw;
     for (int item = wave; item < 2 * h; item += THREADS / 64) {          // wave-uniform
-        const int y = item >> 1, x = (item & 1) * 64 + lane;
-        const bool is_ink = x < w && (int)src[y * w + x] < thr;
-        const uint64_t m = __ballot(is_ink);
+        const uint64_t m = ink_word(src, w, item >> 1, item & 1, lane, thr);
         if (lane == 0) { smask[item] = m; bufa[item] = m; bufb[item] = 0; }
     }
     for (int i = tid; i < FLAGS + STATS; i += THREADS) sflag[i] = 0;     // (sstat follows sflag)
@@ -172,22 +170,13 @@ __global__ __launch_bounds__(THREADS) void k_strokes(const uint8_t* u8, int h, i
 extern "C" int siggan_strokes_u8(int32_t device, const uint8_t* u8_dev, int32_t batch, int32_t height, int32_t width,
                                  int32_t threshold, int32_t radius2, int32_t ink, int32_t fill,
                                  int32_t* stats_dev, int16_t* d2_dev, uint8_t* skel_dev, uint8_t* redraw_dev, void* stream) {
-    if (!u8_dev) return FAIL(SIGGAN_E_INVALID, "null image tensor");
-    if (!stats_dev && !d2_dev && !skel_dev && !redraw_dev)
-        return FAIL(SIGGAN_E_INVALID, "no output: give stats_dev, d2_dev, skel_dev or redraw_dev");
-    if (batch < 1) return FAIL(SIGGAN_E_INVALID, "batch = %d < 1", batch);
-    if (height < 1 || height > SIGGAN_SK_MAX_SIZE) return FAIL(SIGGAN_E_INVALID, "height = %d outside [1, %d]", height, SIGGAN_SK_MAX_SIZE);
-    if (width < 4 || width > SIGGAN_SK_MAX_SIZE || (width & 3))
-        return FAIL(SIGGAN_E_INVALID, "width = %d must be a multiple of 4 in [4, %d]", width, SIGGAN_SK_MAX_SIZE);
-    if (threshold < 1 || threshold > 255) return FAIL(SIGGAN_E_INVALID, "threshold = %d outside [1, 255]", threshold);
+    const char* no_output = !stats_dev && !d2_dev && !skel_dev && !redraw_dev ? "no output: give stats_dev, d2_dev, skel_dev or redraw_dev" : nullptr;
+    if (int rc = ink_refuse_images(u8_dev, no_output, batch, height, width, SIGGAN_SK_MAX_SIZE, threshold)) return rc;
     if (radius2 < 0 || radius2 > SIGGAN_SK_MAX_RADIUS2) return FAIL(SIGGAN_E_INVALID, "radius2 = %d outside [0, %d]", radius2, SIGGAN_SK_MAX_RADIUS2);
     if (ink < 0 || ink >= threshold)
         return FAIL(SIGGAN_E_INVALID, "ink = %d outside [0, threshold - 1 = %d]: a redrawn stroke must be ink", ink, threshold - 1);
-    if (fill < threshold || fill > 255)
-        return FAIL(SIGGAN_E_INVALID, "fill = %d outside [threshold = %d, 255]: the paper must not be ink", fill, threshold);
-    if ((reinterpret_cast<uintptr_t>(u8_dev) | reinterpret_cast<uintptr_t>(stats_dev) | reinterpret_cast<uintptr_t>(skel_dev) |
-         reinterpret_cast<uintptr_t>(redraw_dev)) & 3)
-        return FAIL(SIGGAN_E_INVALID, "u8_dev, stats_dev, skel_dev and redraw_dev must be 4-byte aligned");
+    if (int rc = ink_refuse_fill(fill, threshold, "the paper must not be ink")) return rc;
+    if (int rc = ink_refuse_unaligned({u8_dev, stats_dev, skel_dev, redraw_dev}, "u8_dev, stats_dev, skel_dev and redraw_dev")) return rc;
     if (reinterpret_cast<uintptr_t>(d2_dev) & 1) return FAIL(SIGGAN_E_INVALID, "d2_dev must be 2-byte aligned");
     DevGuard dg(device); HIPCHK(dg.err);
     hipLaunchKernelGGL(k_strokes, dim3((unsigned)batch), dim3(THREADS), lds_bytes(height, width, stats_dev || d2_dev), (hipStream_t)stream,

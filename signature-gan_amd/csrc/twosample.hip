@@ -11,8 +11,7 @@
 // wave reaches only after its reads of b.
 //
 // The chaining needs no layout shuffle.  The K MFMA takes the j-rows as A and the i-rows as B, so by the f64 C/D map
-// (col = l & 15, row = (l >> 4) + 4 * reg -- NOT the f32 16x16 map) lane l holds k(x_j, x_i) for i = i0 + (l & 15) and
-// j = j0 + (l >> 4) + 4 * reg.  The A operand of an MFMA step is A[m = l & 15][k = l >> 4]: accumulator register v IS the
+// (rows_f64.h) lane l holds k(x_j, x_i) for i = i0 + (l & 15) and j = j0 + (l >> 4) + 4 * reg.  The A operand of an MFMA step is A[m = l & 15][k = l >> 4]: accumulator register v IS the
 // A operand of the k-slice j = j0 + 4 v .. j0 + 4 v + 3 of Z[i][c] += sum_j K[i][j] L[j][c].  The B operand of that step is
 // L[j0 + 4 v + (l >> 4)][column of lane l & 15].  Which column a lane's slot stands for is free as long as the epilogue
 // agrees: slot x of sub-tile s is column c0 + 4 x + s, so one 4-byte load gives a lane the labels of all four sub-tiles.
@@ -20,8 +19,7 @@
 // and sums over reg, the two i-tiles, then the four lane groups (xor 16, 32).  Partial forms per (row block, column) go to
 // the workspace; k_forms_reduce adds them in ascending row-block order.  No atomics; every word has one writer.
 //
-// Dot products and norms: neighbors.hip's scheme.  Lane l loads features kb .. kb + 3, kb = 16 c + 4 (l >> 4), of row
-// (l & 15) per 16-feature chunk c and feeds element e to the chunk's MFMA step e.  The RBF norms are the diagonals of the
+// Dot products and norms: rows_f64.h's scheme, the one neighbors.hip is built from.  The RBF norms are the diagonals of the
 // MFMA products X X^T of every 16-row tile against itself over the same chunk and step order, so a row against a
 // bit-identical row gives d2 = 0.0 and k = 1.0 exactly; k_norms forms them once per call into the workspace (behind the
 // partial forms) instead of once per workgroup and tile.  k(x_i, x_i) for diag[] is the diagonal tile's value before it is
@@ -32,35 +30,17 @@
 
 #include "../../include/siggan_twosample.h"
 #include "host.h"
+#include "rows_f64.h"
 
 namespace {
 
-typedef double double4_t __attribute__((ext_vector_type(4)));
-constexpr int NT = 16;                                   // tile edge
 constexpr int WAVES = 4;
-constexpr int CHUNK = 16;                                // features per K chunk: four MFMA steps of four
 constexpr int ROWS = SIGGAN_TWOSAMPLE_ROW_BLOCK;         // rows i per workgroup
 constexpr int ITILES = ROWS / NT;
 constexpr int SUB = 4;                                   // column sub-tiles of 16 per wave
 constexpr int WAVE_COLS = NT * SUB;                      // 64
 constexpr int WG_COLS = WAVE_COLS * WAVES;               // 256
 static_assert(ROWS % NT == 0, "a row block is whole tiles");
-
-// features kb .. kb + 3 of one row; VEC: dim % 4 == 0 and a 16-byte aligned base, so kb < dim covers all four
-template <bool VEC>
-__device__ __forceinline__ float4 load4(const float* __restrict__ row, bool row_ok, int kb, int dim) {
-    float4 v = {0.f, 0.f, 0.f, 0.f};
-    if (!row_ok) return v;
-    if (VEC) {
-        if (kb < dim) v = *reinterpret_cast<const float4*>(row + kb);
-    } else {
-        if (kb < dim) v.x = row[kb];
-        if (kb + 1 < dim) v.y = row[kb + 1];
-        if (kb + 2 < dim) v.z = row[kb + 2];
-        if (kb + 3 < dim) v.w = row[kb + 3];
-    }
-    return v;
-}
 
 // the label bytes of row `row`, columns c .. c + 3, byte s in bits 8 s ..; rows past n and columns past cols read as 0.
 // vec: cols % 4 == 0 and a 4-byte aligned base (c is a multiple of 4, so c < cols covers all four)
@@ -79,15 +59,6 @@ __device__ __forceinline__ double is_label(uint32_t word, int s, uint32_t which)
     return ((word >> (8 * s)) & 0xffu) == which ? 1.0 : 0.0;
 }
 
-// the diagonal element (x, x) of a 16 x 16 product sits in lane ((x & 3) << 4 | x), register x >> 2; -> to every lane of
-// column slot x
-__device__ __forceinline__ double diagonal_of(const double4_t& acc, int x) {
-    const int src = ((x & 3) << 4) | x;
-    const double d0 = __shfl(acc[0], src), d1 = __shfl(acc[1], src), d2 = __shfl(acc[2], src), d3 = __shfl(acc[3], src);
-    const int reg = x >> 2;
-    return reg == 0 ? d0 : reg == 1 ? d1 : reg == 2 ? d2 : d3;
-}
-
 // |x_i|^2 of every row as the diagonal of its tile's X X^T; grid: ceil(n / 16) workgroups of one wave
 template <bool VEC>
 __global__ __launch_bounds__(64) void k_norms(const float* __restrict__ xs, int n, int dim, double* __restrict__ norms) {
@@ -98,10 +69,7 @@ __global__ __launch_bounds__(64) void k_norms(const float* __restrict__ xs, int 
     double4_t acc = {0.0, 0.0, 0.0, 0.0};
     for (int f0 = 0; f0 < dim; f0 += CHUNK) {
         const float4 b = load4<VEC>(irow, i_ok, f0 + 4 * g, dim);
-        acc = __builtin_amdgcn_mfma_f64_16x16x4f64((double)b.x, (double)b.x, acc, 0, 0, 0);
-        acc = __builtin_amdgcn_mfma_f64_16x16x4f64((double)b.y, (double)b.y, acc, 0, 0, 0);
-        acc = __builtin_amdgcn_mfma_f64_16x16x4f64((double)b.z, (double)b.z, acc, 0, 0, 0);
-        acc = __builtin_amdgcn_mfma_f64_16x16x4f64((double)b.w, (double)b.w, acc, 0, 0, 0);
+        chunk_mfma(acc, b, b);
     }
     const double d = diagonal_of(acc, x);
     if (g == 0 && i_ok) norms[i] = d;
@@ -156,10 +124,7 @@ __global__ __launch_bounds__(64 * WAVES) void k_forms(const float* __restrict__ 
                     const int kb = f0 + 4 * g;
                     const float4 a = load4<VEC>(jrow, j_ok, kb, dim);
                     const float4 b = load4<VEC>(irow, i_ok, kb, dim);
-                    dot = __builtin_amdgcn_mfma_f64_16x16x4f64((double)a.x, (double)b.x, dot, 0, 0, 0);
-                    dot = __builtin_amdgcn_mfma_f64_16x16x4f64((double)a.y, (double)b.y, dot, 0, 0, 0);
-                    dot = __builtin_amdgcn_mfma_f64_16x16x4f64((double)a.z, (double)b.z, dot, 0, 0, 0);
-                    dot = __builtin_amdgcn_mfma_f64_16x16x4f64((double)a.w, (double)b.w, dot, 0, 0, 0);
+                    chunk_mfma(dot, a, b);
                 }
 #pragma unroll
                 for (int reg = 0; reg < 4; ++reg) {
@@ -281,7 +246,7 @@ extern "C" int siggan_kernel_forms(int32_t device, const float* x_dev, int32_t n
         return FAIL(SIGGAN_E_INVALID, "%s: workspace of %zu bytes, n = %d and cols = %d need %zu", who, workspace_bytes, n, cols, need);
     DevGuard dg(device); HIPCHK(dg.err);
     const hipStream_t st = (hipStream_t)stream;
-    const bool vec = (dim & 3) == 0 && (reinterpret_cast<uintptr_t>(x_dev) & 15) == 0;
+    const bool vec = rows_allow_16_byte_loads(dim, x_dev);
     const int labels_vec = (cols & 3) == 0 && (reinterpret_cast<uintptr_t>(labels_dev) & 3) == 0;
     double* partial = static_cast<double*>(workspace_dev);
     const int row_blocks = row_blocks_of(n);

@@ -5,7 +5,7 @@ import math
 
 import torch
 
-from . import _lib, layout
+from . import _call, _lib, layout
 
 
 def _ptr(t):
@@ -472,8 +472,8 @@ class Engine:
             raise ValueError("image_stats needs a contiguous float32 (B, ...) tensor")
         b = x.shape[0]
         stats = torch.empty(b, _lib.IS_COUNT, dtype=torch.int32, device=x.device)
-        _lib.check(_lib.load().siggan_image_stats(x.device.index, _ptr(x), b, x.numel() // b if b else 0, float(threshold),
-                                                  _ptr(stats), C.c_void_p(torch.cuda.current_stream(x.device).cuda_stream)))
+        _lib.check(_lib.load().siggan_image_stats(x.device.index, _call.ptr(x), b, x.numel() // b if b else 0, float(threshold),
+                                                  _call.ptr(stats), _call.stream(x.device)))
         return stats
 
     def _masks(self, masks, b, passes):
@@ -537,8 +537,8 @@ class Engine:
         if scores.dtype != torch.float32 or scores.dim() != 1 or not scores.is_contiguous():
             raise ValueError("select_topk needs a contiguous float32 (m,) tensor")
         index = torch.empty(max(int(k), 0), dtype=torch.int32, device=scores.device)
-        _lib.check(_lib.load().siggan_select_topk(scores.device.index, _ptr(scores), scores.numel(), int(k), _ptr(index),
-                                                  C.c_void_p(torch.cuda.current_stream(scores.device).cuda_stream)))
+        _lib.check(_lib.load().siggan_select_topk(scores.device.index, _call.ptr(scores), scores.numel(), int(k), _call.ptr(index),
+                                                  _call.stream(scores.device)))
         return index
 
     @staticmethod
@@ -557,9 +557,9 @@ class Engine:
         m, k = pool.shape[0], index.numel()
         pixels = pool.numel() // m if m else 0
         out = torch.empty((k,) + tuple(pool.shape[1:]), dtype=torch.uint8, device=pool.device)
-        _lib.check(_lib.load().siggan_gather_u8(pool.device.index, _ptr(pool), m, pixels, _ptr(index), k,
-                                                -1 if binarize is None else int(binarize), _ptr(out),
-                                                C.c_void_p(torch.cuda.current_stream(pool.device).cuda_stream)))
+        _lib.check(_lib.load().siggan_gather_u8(pool.device.index, _call.ptr(pool), m, pixels, _call.ptr(index), k,
+                                                -1 if binarize is None else int(binarize), _call.ptr(out),
+                                                _call.stream(pool.device)))
         return out
 
     # ---- training steps --------------------------------------------------------------------------

@@ -17,7 +17,7 @@ from typing import Dict, Optional, Tuple, Union
 import numpy as np
 import torch
 
-from . import _lib
+from . import _call, _lib
 
 Size = Union[int, Tuple[int, int]]
 _CONTEXTS: Dict[int, "_ResizeContext"] = {}
@@ -44,8 +44,8 @@ class _ResizeContext:
             pass
 
 
-def _context(device: torch.device) -> _ResizeContext:
-    index = device.index if device.index is not None else torch.cuda.current_device()
+def _context(src: torch.Tensor) -> _ResizeContext:
+    index = _call.device_of(src).index
     ctx = _CONTEXTS.get(index)
     if ctx is None:
         ctx = _CONTEXTS[index] = _ResizeContext(index)
@@ -75,10 +75,7 @@ def check_images(images, dtype: torch.dtype, what: str, limit: int) -> Tuple[int
     n, h, w = images.shape[0], images.shape[-2], images.shape[-1]
     if not (1 <= h <= limit and 1 <= w <= limit):
         raise ValueError(f"{what} is {h} x {w}: sizes outside [1, {limit}]")
-    if images.device.type != "cuda":
-        raise ValueError(f"{what} must live on a ROCm device ('cuda:N'); there is no CPU path")
-    if not images.is_contiguous():
-        raise ValueError(f"{what} must be contiguous")
+    _call.check_resident(images, what)
     return n, h, w
 
 
@@ -92,10 +89,8 @@ def _run(name: str, src: torch.Tensor, n: int, hs: int, ws: int, hd: int, wd: in
         dst = out
     if n == 0:
         return dst
-    ctx = _context(src.device)
-    stream = C.c_void_p(torch.cuda.current_stream(src.device).cuda_stream)
-    fn = getattr(ctx.lib, name)
-    _lib.check(fn(ctx._h, C.c_void_p(src.data_ptr()), n, hs, ws, C.c_void_p(dst.data_ptr()), hd, wd, stream))
+    ctx = _context(src)
+    _lib.check(getattr(ctx.lib, name)(ctx._h, _call.ptr(src), n, hs, ws, _call.ptr(dst), hd, wd, _call.stream(src.device)))
     return dst
 
 

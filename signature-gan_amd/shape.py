@@ -17,13 +17,13 @@ term contributes nothing when syy <= 1e-12.  ``shape_sums_u8`` gives the six exa
 255 - b, coordinates p = 2c + 1 - s, q = 2r + 1 - s) and ``features_from_sums`` turns them into the eight features on the
 host, for ink (255 - b) / 255.  ``reference_features`` / ``reference_grad`` restate the definitions in numpy fp64; they need
 no device.  Arguments are validated before the library is touched; there is no CPU path for the device calls."""
-import ctypes as C
 from typing import Optional, Tuple
 
 import numpy as np
 import torch
 
-from . import _lib
+from . import _call, _lib
+from ._call import device_of, ptr, stream
 
 FEATURES = ("mass", "cx", "cy", "sxx", "syy", "sxy", "slant", "spread")
 MASS, CX, CY, SXX, SYY, SXY, SLANT, SPREAD = range(8)
@@ -171,10 +171,7 @@ def _check_images(images, dtype: torch.dtype, what: str) -> Tuple[int, int]:
         raise ValueError(f"{what} must be square with a side in {SIZES}, got {h} x {w}")
     if b < 1:
         raise ValueError(f"{what} holds no image")
-    if images.device.type != "cuda":
-        raise ValueError(f"{what} must live on a ROCm device ('cuda:N'); there is no CPU path")
-    if not images.is_contiguous():
-        raise ValueError(f"{what} must be contiguous")
+    _call.check_resident(images, what)
     return b, h
 
 
@@ -205,25 +202,12 @@ def _out(name: str, t: Optional[torch.Tensor], shape, dtype: torch.dtype, dev: t
     return t
 
 
-def _stream(dev: torch.device):
-    return C.c_void_p(torch.cuda.current_stream(dev).cuda_stream)
-
-
-def _ptr(t: Optional[torch.Tensor]):
-    return C.c_void_p(t.data_ptr()) if t is not None else None
-
-
-def _device(images: torch.Tensor) -> torch.device:
-    dev = images.device
-    return dev if dev.index is not None else torch.device("cuda", torch.cuda.current_device())
-
-
 def shape_features(images: torch.Tensor) -> torch.Tensor:
     """(B, 8) fp64 on the device: the features (FEATURES) of contiguous fp32 device images (B, 1, s, s) or (B, s, s)."""
     b, s = _check_images(images, torch.float32, "images")
-    dev = _device(images)
+    dev = device_of(images)
     feats = torch.empty(b, 8, dtype=torch.float64, device=dev)
-    _lib.check(_lib.load().siggan_shape_f32(dev.index, _ptr(images), b, s, None, None, _ptr(feats), None, None, _stream(dev)))
+    _lib.check(_lib.load().siggan_shape_f32(dev.index, ptr(images), b, s, None, None, ptr(feats), None, None, stream(dev)))
     return feats
 
 
@@ -235,7 +219,7 @@ def shape_grad(images: torch.Tensor, weights, targets, dx_out: Optional[torch.Te
     one small synchronising check -- pass a host array, or call the library directly, inside a loop that must not wait).
     ``dx_out`` / ``objective_out``: caller-owned contiguous fp32 device tensors the results are written into."""
     b, s = _check_images(images, torch.float32, "images")
-    dev = _device(images)
+    dev = device_of(images)
     w = _check_rows("weights", weights, b, dev, True)
     t = _check_rows("targets", targets, b, dev, False)
     return _shape_grad_checked(images, b, s, dev, w, t, dx_out, objective_out)
@@ -246,8 +230,8 @@ def _shape_grad_checked(images, b, s, dev, w, t, dx_out=None, objective_out=None
     dx = _out("dx_out", dx_out, (b, 1, s, s), torch.float32, dev)
     obj = _out("objective_out", objective_out, (b,), torch.float32, dev)
     feats = torch.empty(b, 8, dtype=torch.float64, device=dev)
-    _lib.check(_lib.load().siggan_shape_f32(dev.index, _ptr(images), b, s, _ptr(w), _ptr(t), _ptr(feats), _ptr(dx), _ptr(obj),
-                                            _stream(dev)))
+    _lib.check(_lib.load().siggan_shape_f32(dev.index, ptr(images), b, s, ptr(w), ptr(t), ptr(feats), ptr(dx), ptr(obj),
+                                            stream(dev)))
     return dx, obj, feats
 
 
@@ -255,7 +239,7 @@ def shape_sums_u8(u8: torch.Tensor) -> torch.Tensor:
     """(B, 6) int64 on the device: sum ink, ink p, ink q, ink p^2, ink q^2, ink p q of contiguous uint8 device images
     (B, s, s) or (B, 1, s, s), exact (ink = 255 - b, p = 2c + 1 - s, q = 2r + 1 - s).  features_from_sums makes features of them."""
     b, s = _check_images(u8, torch.uint8, "byte images")
-    dev = _device(u8)
+    dev = device_of(u8)
     sums = torch.empty(b, N_SUMS, dtype=torch.int64, device=dev)
-    _lib.check(_lib.load().siggan_shape_u8(dev.index, _ptr(u8), b, s, _ptr(sums), _stream(dev)))
+    _lib.check(_lib.load().siggan_shape_u8(dev.index, ptr(u8), b, s, ptr(sums), stream(dev)))
     return sums

@@ -17,7 +17,8 @@ from typing import Any, Dict, Optional, Tuple, Union
 import numpy as np
 import torch
 
-from . import _lib
+from . import _call, _lib
+from ._call import ptr, stream
 
 WINDOW_TAPS, WINDOW_SIGMA = _lib.SSIM_TAPS, _lib.SSIM_SIGMA
 LPIPS_IMAGES, LPIPS_REACH = 100, 10        # the reference's LPIPS pair set: i < j < i + 10 over the first 100 images
@@ -33,32 +34,10 @@ def window() -> np.ndarray:
 
 def check_images(u8, what: str = "images") -> Tuple[int, int, int]:
     """The refusals that need no device, in a fixed order: type, dtype, rank, sizes, device, layout.  Returns (n, h, w)."""
-    if not isinstance(u8, torch.Tensor):
-        raise ValueError(f"{what} must be a tensor or an SsimSet, got {type(u8).__name__}")
-    if u8.dtype != torch.uint8:
-        raise ValueError(f"{what} must be torch.uint8, got {u8.dtype}")
-    if not (u8.dim() == 3 or (u8.dim() == 4 and u8.shape[1] == 1)):
-        raise ValueError(f"{what} must be (N, H, W) or (N, 1, H, W), got {tuple(u8.shape)}")
-    n, h, w = u8.shape[0], u8.shape[-2], u8.shape[-1]
-    if n < 1:
-        raise ValueError(f"{what} holds no image")
-    if not _lib.SSIM_MIN_HEIGHT <= h <= _lib.SSIM_MAX_SIZE:
-        raise ValueError(f"height = {h} outside [{_lib.SSIM_MIN_HEIGHT}, {_lib.SSIM_MAX_SIZE}]")
-    if not _lib.SSIM_MIN_WIDTH <= w <= _lib.SSIM_MAX_SIZE or w % 4:
-        raise ValueError(f"width = {w} must be a multiple of 4 in [{_lib.SSIM_MIN_WIDTH}, {_lib.SSIM_MAX_SIZE}]")
-    if u8.device.type != "cuda":
-        raise ValueError(f"{what} must live on a ROCm device ('cuda:N'); there is no CPU path")
-    if not u8.is_contiguous():
-        raise ValueError(f"{what} must be contiguous")
+    n, h, w = _call.check_u8_images(u8, what, _lib.SSIM_MIN_HEIGHT, _lib.SSIM_MIN_WIDTH, _lib.SSIM_MAX_SIZE, False,
+                                    kinds="a tensor or an SsimSet")
+    _call.check_resident(u8, what)
     return n, h, w
-
-
-def _ptr(t: Optional[torch.Tensor]) -> C.c_void_p:
-    return C.c_void_p(t.data_ptr() if t is not None else None)
-
-
-def _stream(device: torch.device) -> C.c_void_p:
-    return C.c_void_p(torch.cuda.current_stream(device).cuda_stream)
 
 
 class SsimSet:
@@ -68,10 +47,10 @@ class SsimSet:
     def __init__(self, u8: torch.Tensor) -> None:
         self.n, self.h, self.w = check_images(u8)
         self.u8 = u8
-        self.device = u8.device if u8.device.index is not None else torch.device("cuda", torch.cuda.current_device())
+        self.device = _call.device_of(u8)
         self.maps = torch.empty((self.n, 2, self.h - 10, self.w - 10), dtype=torch.float32, device=u8.device)
-        _lib.check(_lib.load().siggan_ssim_prepare_u8(self.device.index, _ptr(u8), self.n, self.h, self.w, _ptr(self.maps),
-                                                      _stream(u8.device)))
+        _lib.check(_lib.load().siggan_ssim_prepare_u8(self.device.index, ptr(u8), self.n, self.h, self.w, ptr(self.maps),
+                                                      stream(u8.device)))
 
     def __len__(self) -> int:
         return self.n
@@ -106,8 +85,8 @@ def _two(a: Images, b: Optional[Images]) -> Tuple[SsimSet, Optional[SsimSet]]:
 
 def _pairs(a: SsimSet, b: Optional[SsimSet], mode: int, matrix=None, best=None, index=None) -> None:
     b_u8, b_maps, nb = (b.u8, b.maps, b.n) if b is not None else (None, None, a.n)     # SAME_SET: b is a
-    _lib.check(_lib.load().siggan_ssim_pairs(a.device.index, _ptr(a.u8), _ptr(a.maps), a.n, _ptr(b_u8), _ptr(b_maps), nb, a.h, a.w,
-                                             mode, _ptr(matrix), _ptr(best), _ptr(index), _stream(a.device)))
+    _lib.check(_lib.load().siggan_ssim_pairs(a.device.index, ptr(a.u8), ptr(a.maps), a.n, ptr(b_u8), ptr(b_maps), nb, a.h, a.w,
+                                             mode, ptr(matrix), ptr(best), ptr(index), stream(a.device)))
 
 
 def ssim_matrix(a: Images, b: Optional[Images] = None) -> torch.Tensor:

@@ -13,13 +13,12 @@ axis-aligned bar of width W lands in bin ceil(W / 2): even widths read one pixel
 All four take a contiguous uint8 device tensor (N, H, W) or (N, 1, H, W) with 1 <= H <= 128 and W a multiple of 4 in
 4..128, run one kernel on the current stream and never synchronise the host.  Arguments are validated before the library is
 touched; there is no CPU path.  Everything is integer arithmetic: equal input gives bit-equal output."""
-import ctypes as C
 from typing import Optional
 
-import numpy as np
 import torch
 
-from . import _lib
+from . import _call, _lib
+from ._call import as_int, ptr
 
 # columns of stroke_stats (SIGGAN_SK_*)
 INK, SKELETON, ENDPOINTS, JUNCTION_PIXELS, PASSES, D2_MAX, D2_SKEL_SUM, WIDTH_HIST = range(8)
@@ -33,33 +32,17 @@ MAX_PEN_WIDTH = 9
 def radius2_for_pen_width(w: int) -> int:
     """The squared disc radius that redraws a centre line at pen width ``w`` in 1..9: (w - 1)^2 // 4, that is
     0, 0, 1, 2, 4, 6, 9, 12, 16.  (Widths 1 and 2 both give the skeleton itself: it is one pixel wide.)"""
-    w = _int(w, "pen width")
+    w = as_int(w, "pen width")
     if not 1 <= w <= MAX_PEN_WIDTH:
         raise ValueError(f"pen width = {w} outside [1, {MAX_PEN_WIDTH}]")
     return (w - 1) ** 2 // 4
 
 
-def _int(value, what: str) -> int:
-    if isinstance(value, bool) or not isinstance(value, (int, np.integer)):
-        raise ValueError(f"{what} must be an integer, got {value!r}")
-    return int(value)
-
-
 def check_arguments(u8, threshold, radius2=0, ink=0, fill=255):
     """The refusals that need no device, in a fixed order: type, dtype, rank, sizes, parameters, device, layout.
     Returns (n, h, w, threshold, radius2, ink, fill)."""
-    if not isinstance(u8, torch.Tensor):
-        raise ValueError(f"images must be a tensor, got {type(u8).__name__}")
-    if u8.dtype != torch.uint8:
-        raise ValueError(f"images must be torch.uint8, got {u8.dtype}")
-    if not (u8.dim() == 3 or (u8.dim() == 4 and u8.shape[1] == 1)):
-        raise ValueError(f"images must be (N, H, W) or (N, 1, H, W), got {tuple(u8.shape)}")
-    n, h, w = u8.shape[0], u8.shape[-2], u8.shape[-1]
-    if not 1 <= h <= _lib.SK_MAX_SIZE:
-        raise ValueError(f"height = {h} outside [1, {_lib.SK_MAX_SIZE}]")
-    if not 4 <= w <= _lib.SK_MAX_SIZE or w % 4:
-        raise ValueError(f"width = {w} must be a multiple of 4 in [4, {_lib.SK_MAX_SIZE}]")
-    threshold, radius2, ink, fill = _int(threshold, "threshold"), _int(radius2, "radius2"), _int(ink, "ink"), _int(fill, "fill")
+    n, h, w = _call.check_u8_images(u8, "images", 1, 4, _lib.SK_MAX_SIZE, True)
+    threshold, radius2, ink, fill = as_int(threshold, "threshold"), as_int(radius2, "radius2"), as_int(ink, "ink"), as_int(fill, "fill")
     if not 1 <= threshold <= 255:
         raise ValueError(f"threshold = {threshold} outside [1, 255]")
     if not 0 <= radius2 <= _lib.SK_MAX_RADIUS2:
@@ -68,21 +51,15 @@ def check_arguments(u8, threshold, radius2=0, ink=0, fill=255):
         raise ValueError(f"ink = {ink} outside [0, threshold - 1 = {threshold - 1}]: a redrawn stroke must be ink")
     if not threshold <= fill <= 255:
         raise ValueError(f"fill = {fill} outside [threshold = {threshold}, 255]: the paper must not be ink")
-    if u8.device.type != "cuda":
-        raise ValueError("images must live on a ROCm device ('cuda:N'); there is no CPU path")
-    if not u8.is_contiguous():
-        raise ValueError("images must be contiguous")
+    _call.check_resident(u8, "images")
     return n, h, w, threshold, radius2, ink, fill
 
 
 def _run(u8, n, h, w, threshold, radius2=0, ink=0, fill=255, stats=None, d2=None, skel=None, redraw=None):
     if n == 0:
         return
-    device = u8.device.index if u8.device.index is not None else torch.cuda.current_device()
-    stream = C.c_void_p(torch.cuda.current_stream(u8.device).cuda_stream)
-    ptr = lambda t: C.c_void_p(t.data_ptr() if t is not None else None)          # noqa: E731
-    _lib.check(_lib.load().siggan_strokes_u8(device, ptr(u8), n, h, w, threshold, radius2, ink, fill, ptr(stats), ptr(d2), ptr(skel),
-                                             ptr(redraw), stream))
+    _lib.check(_lib.load().siggan_strokes_u8(_call.device_of(u8).index, ptr(u8), n, h, w, threshold, radius2, ink, fill, ptr(stats),
+                                             ptr(d2), ptr(skel), ptr(redraw), _call.stream(u8.device)))
 
 
 def stroke_stats(u8: torch.Tensor, threshold: int = 128) -> torch.Tensor:
@@ -118,15 +95,7 @@ def restroke_u8(u8: torch.Tensor, radius2: int, threshold: int = 128, ink: int =
     ``u8`` itself (in place) or a contiguous uint8 tensor of the same element count that does not overlap it; ``stats``, a
     contiguous int32 (N, 23) device tensor, receives stroke_stats' counters of the INPUT from the same launch."""
     n, h, w, threshold, radius2, ink, fill = check_arguments(u8, threshold, radius2, ink, fill)
-    if out is None:
-        out = torch.empty_like(u8)
-    elif (not isinstance(out, torch.Tensor) or out.dtype != torch.uint8 or out.device != u8.device or not out.is_contiguous()
-          or out.numel() != u8.numel()):
-        raise ValueError(f"out must be a contiguous torch.uint8 tensor of {u8.numel()} elements on {u8.device}")
-    elif out.data_ptr() != u8.data_ptr() and (out.data_ptr() < u8.data_ptr() + u8.numel() and u8.data_ptr() < out.data_ptr() + out.numel()):
-        raise ValueError("out overlaps the input without being the input")
-    if stats is not None and (not isinstance(stats, torch.Tensor) or stats.dtype != torch.int32 or stats.device != u8.device
-                              or not stats.is_contiguous() or tuple(stats.shape) != (n, COUNT)):
-        raise ValueError(f"stats must be a contiguous torch.int32 tensor ({n}, {COUNT}) on {u8.device}")
+    out = _call.check_out_u8(out, u8)
+    _call.check_stats(stats, n, COUNT, u8.device)
     _run(u8, n, h, w, threshold, radius2, ink, fill, stats=stats, redraw=out)
     return out

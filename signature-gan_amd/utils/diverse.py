@@ -11,7 +11,6 @@ definitions in one place -- turns what a run fetched into its report.
 
 Whether a verifier trained on a set selected this way is more accurate than one trained on the top of the ranking is not
 measured here."""
-import ctypes as C
 import math
 from typing import Any, Dict, Optional, Tuple
 
@@ -19,13 +18,8 @@ import numpy as np
 import torch
 
 from .. import _lib
-from .neighbors import _check_sets, _stream
-
-
-def _check_vector(name: str, t: Any, dtype: torch.dtype, n: int, dev: torch.device) -> None:
-    if (not isinstance(t, torch.Tensor) or t.device != dev or t.dtype != dtype or tuple(t.shape) != (n,)
-            or not t.is_contiguous()):
-        raise ValueError(f"{name} must be a contiguous {str(dtype).replace('torch.', '')} ({n},) tensor on {dev}")
+from .._call import check_rows, check_vector, ptr, stream
+from .neighbors import _check_sets
 
 
 def select_diverse(x: torch.Tensor, n_select: int, eligible: Optional[torch.Tensor] = None,
@@ -43,9 +37,9 @@ def select_diverse(x: torch.Tensor, n_select: int, eligible: Optional[torch.Tens
     n, dim = x.shape
     n_select = int(n_select)
     if eligible is not None:
-        _check_vector("eligible", eligible, torch.uint8, n, dev)
+        check_vector("eligible", eligible, torch.uint8, n, dev)
     if anchor_d2 is not None:
-        _check_vector("anchor_d2", anchor_d2, torch.float64, n, dev)
+        check_vector("anchor_d2", anchor_d2, torch.float64, n, dev)
     min_separation = float(min_separation)
     if not min_separation >= 0.0:
         raise ValueError(f"min_separation must be >= 0, got {min_separation}")
@@ -57,10 +51,9 @@ def select_diverse(x: torch.Tensor, n_select: int, eligible: Optional[torch.Tens
     gain2 = torch.empty(k, dtype=torch.float64, device=dev)
     count = torch.empty(1, dtype=torch.int32, device=dev)
     min_d2 = torch.empty(n, dtype=torch.float64, device=dev)
-    ptr = lambda t: C.c_void_p(t.data_ptr()) if t is not None else None          # noqa: E731
     _lib.check(lib.siggan_select_diverse(dev.index, ptr(x), n, dim, ptr(eligible), ptr(anchor_d2), -1 if first is None else int(first),
                                          n_select, min_separation * min_separation, ptr(order), ptr(gain2), ptr(count), ptr(min_d2),
-                                         ptr(workspace), size, _stream(dev)))
+                                         ptr(workspace), size, stream(dev)))
     return order, gain2, count, min_d2
 
 
@@ -70,12 +63,7 @@ def eligibility(scores: torch.Tensor, keep_ratio: float, nearest_real_d2: Option
     -- when both are given -- only rows with ``nearest_real_d2`` (fp64 (n,) device: squared distance to the nearest real
     sample) >= ``floor2`` (a number or a 0-d device tensor).  Nothing synchronises the host."""
     from ..engine import Engine
-    if not isinstance(scores, torch.Tensor) or scores.device.type != "cuda":
-        raise ValueError("scores must be a tensor on a ROCm device ('cuda:N'); there is no CPU path")
-    if scores.dtype != torch.float32 or scores.dim() != 1 or scores.numel() < 1:
-        raise ValueError(f"scores must be float32 (n >= 1,), got {scores.dtype} {tuple(scores.shape)}")
-    if not scores.is_contiguous():
-        raise ValueError("scores must be contiguous")
+    check_rows("scores", scores, torch.float32, "(n >= 1,)", shape=(None,), min_rows=1)
     n = scores.numel()
     keep_ratio = float(keep_ratio)
     if not 0.0 < keep_ratio <= 1.0:
@@ -87,7 +75,7 @@ def eligibility(scores: torch.Tensor, keep_ratio: float, nearest_real_d2: Option
     mask = torch.zeros(n, dtype=torch.uint8, device=scores.device)
     mask[index.long()] = 1
     if nearest_real_d2 is not None:
-        _check_vector("nearest_real_d2", nearest_real_d2, torch.float64, n, scores.device)
+        check_vector("nearest_real_d2", nearest_real_d2, torch.float64, n, scores.device)
         mask = mask * (nearest_real_d2 >= floor2).to(torch.uint8)
     return mask.contiguous()
 

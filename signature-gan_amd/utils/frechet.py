@@ -13,6 +13,7 @@ import numpy as np
 import torch
 
 from .. import _lib
+from .._call import check_rows, ptr, stream
 
 
 def stats_from_moments(n: int, s: np.ndarray, gram: np.ndarray) -> Tuple[int, np.ndarray, np.ndarray]:
@@ -46,17 +47,13 @@ class FeatureMoments:
         self._h = h
 
     def _stream(self):
-        return C.c_void_p(torch.cuda.current_stream(self.device).cuda_stream)
+        return stream(self.device)
 
     def update(self, features: torch.Tensor) -> None:
         """features: (n, dim) fp32 contiguous tensor on this accumulator's device, n >= 1."""
-        if not isinstance(features, torch.Tensor) or features.device != self.device:
-            raise ValueError(f"features must be a tensor on {self.device}")
-        if features.dtype != torch.float32 or features.dim() != 2 or features.shape[1] != self.dim:
-            raise ValueError(f"features must be float32 (n, {self.dim}), got {features.dtype} {tuple(features.shape)}")
-        if not features.is_contiguous():
-            raise ValueError("features must be contiguous")
-        _lib.check(self.lib.siggan_moments_update(self._h, C.c_void_p(features.data_ptr()), features.shape[0], self._stream()))
+        check_rows("features", features, torch.float32, f"(n, {self.dim})", shape=(None, self.dim), device=self.device,
+                   where=str(self.device))
+        _lib.check(self.lib.siggan_moments_update(self._h, ptr(features), features.shape[0], self._stream()))
 
     def reset(self) -> None:
         _lib.check(self.lib.siggan_moments_reset(self._h, self._stream()))
@@ -72,8 +69,7 @@ class FeatureMoments:
         s = torch.empty(self.dim, dtype=torch.float64, device=self.device)
         g = torch.empty(self.dim, self.dim, dtype=torch.float64, device=self.device)
         n = C.c_int64()
-        _lib.check(self.lib.siggan_moments_read(self._h, C.c_void_p(s.data_ptr()), C.c_void_p(g.data_ptr()), C.byref(n),
-                                                self._stream()))
+        _lib.check(self.lib.siggan_moments_read(self._h, ptr(s), ptr(g), C.byref(n), self._stream()))
         return int(n.value), s.cpu().numpy(), g.cpu().numpy()
 
     def finish(self) -> Tuple[int, np.ndarray, np.ndarray]:

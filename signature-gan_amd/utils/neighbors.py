@@ -15,32 +15,23 @@ do are k-nearest-neighbour queries between the two sets of embeddings:
 ``knn`` and ``ball_count`` (include/siggan_neighbors.h, csrc/neighbors.hip) answer the queries in fp64 on the device
 without forming the distance matrix; ``manifold_metrics`` makes six launches and brings only k-lists and counts to the
 host, where ``manifold_from_neighbors`` -- pure numpy, the definitions in one place -- reduces them."""
-import ctypes as C
 from typing import Any, Dict, Tuple
 
 import numpy as np
 import torch
 
-from .. import _lib
+from .. import _call, _lib
+from .._call import ptr, stream
 
 CLOSEST = 5                                                 # how many generated -> real pairs ``nearest_real`` lists
 
 
 def _check_sets(q: torch.Tensor, r: torch.Tensor) -> torch.device:
     for name, t in (("q", q), ("r", r)):
-        if not isinstance(t, torch.Tensor) or t.device.type != "cuda":
-            raise ValueError(f"{name} must be a tensor on a ROCm device ('cuda:N'); there is no CPU path")
-        if t.dtype != torch.float32 or t.dim() != 2:
-            raise ValueError(f"{name} must be float32 (n, dim), got {t.dtype} {tuple(t.shape)}")
-        if not t.is_contiguous():
-            raise ValueError(f"{name} must be contiguous")
+        _call.check_rows(name, t, torch.float32, "(n, dim)")
     if r.device != q.device or r.shape[1] != q.shape[1]:
         raise ValueError(f"q {tuple(q.shape)} on {q.device} and r {tuple(r.shape)} on {r.device} must share device and dim")
     return q.device
-
-
-def _stream(device: torch.device) -> C.c_void_p:
-    return C.c_void_p(torch.cuda.current_stream(device).cuda_stream)
 
 
 def knn(q: torch.Tensor, r: torch.Tensor, k: int, exclude_self: bool = False) -> Tuple[torch.Tensor, torch.Tensor]:
@@ -53,9 +44,8 @@ def knn(q: torch.Tensor, r: torch.Tensor, k: int, exclude_self: bool = False) ->
         raise ValueError(f"k = {k} outside [1, {_lib.KNN_MAX_K}]")
     dist2 = torch.empty(q.shape[0], k, dtype=torch.float64, device=dev)
     index = torch.empty(q.shape[0], k, dtype=torch.int32, device=dev)
-    _lib.check(_lib.load().siggan_knn(dev.index, C.c_void_p(q.data_ptr()), q.shape[0], C.c_void_p(r.data_ptr()), r.shape[0],
-                                      q.shape[1], k, 1 if exclude_self else 0, C.c_void_p(dist2.data_ptr()),
-                                      C.c_void_p(index.data_ptr()), _stream(dev)))
+    _lib.check(_lib.load().siggan_knn(dev.index, ptr(q), q.shape[0], ptr(r), r.shape[0], q.shape[1], k, 1 if exclude_self else 0,
+                                      ptr(dist2), ptr(index), stream(dev)))
     return dist2, index
 
 
@@ -63,13 +53,10 @@ def ball_count(q: torch.Tensor, r: torch.Tensor, radius2: torch.Tensor) -> torch
     """int32 (nq): in how many of the balls around the rows of r -- squared radii ``radius2``, fp64 (nr) -- each row of q
     lies (d2 <= radius2, the distances ``knn`` gives)."""
     dev = _check_sets(q, r)
-    if (not isinstance(radius2, torch.Tensor) or radius2.device != dev or radius2.dtype != torch.float64
-            or tuple(radius2.shape) != (r.shape[0],) or not radius2.is_contiguous()):
-        raise ValueError(f"radius2 must be a contiguous float64 ({r.shape[0]},) tensor on {dev}")
+    _call.check_vector("radius2", radius2, torch.float64, r.shape[0], dev)
     count = torch.empty(q.shape[0], dtype=torch.int32, device=dev)
-    _lib.check(_lib.load().siggan_ball_count(dev.index, C.c_void_p(q.data_ptr()), q.shape[0], C.c_void_p(r.data_ptr()),
-                                             r.shape[0], q.shape[1], C.c_void_p(radius2.data_ptr()),
-                                             C.c_void_p(count.data_ptr()), _stream(dev)))
+    _lib.check(_lib.load().siggan_ball_count(dev.index, ptr(q), q.shape[0], ptr(r), r.shape[0], q.shape[1], ptr(radius2), ptr(count),
+                                             stream(dev)))
     return count
 
 

@@ -27,6 +27,7 @@ import numpy as np
 import torch
 
 from .. import _lib
+from .._call import check_rows, ptr, stream
 
 KINDS = {"poly": _lib.KERNEL_POLY, "rbf": _lib.KERNEL_RBF}
 MEDIAN_ROWS = 512                                          # the median heuristic looks at no more pooled rows than this
@@ -35,18 +36,9 @@ KID_MAX_SUBSET = 1000
 
 # ---- the device call ---------------------------------------------------------------------------------------------------
 def _check_inputs(x: torch.Tensor, labels: torch.Tensor) -> torch.device:
-    if not isinstance(x, torch.Tensor) or x.device.type != "cuda":
-        raise ValueError("x must be a tensor on a ROCm device ('cuda:N'); there is no CPU path")
-    if x.dtype != torch.float32 or x.dim() != 2:
-        raise ValueError(f"x must be float32 (n, dim), got {x.dtype} {tuple(x.shape)}")
-    if not x.is_contiguous():
-        raise ValueError("x must be contiguous")
-    if not isinstance(labels, torch.Tensor) or labels.device != x.device:
-        raise ValueError(f"labels must be a tensor on x's device {x.device}")
-    if labels.dtype != torch.uint8 or labels.dim() != 2 or labels.shape[0] != x.shape[0]:
-        raise ValueError(f"labels must be uint8 ({x.shape[0]}, cols), got {labels.dtype} {tuple(labels.shape)}")
-    if not labels.is_contiguous():
-        raise ValueError("labels must be contiguous")
+    check_rows("x", x, torch.float32, "(n, dim)")
+    check_rows("labels", labels, torch.uint8, f"({x.shape[0]}, cols)", shape=(x.shape[0], None), device=x.device,
+               where=f"x's device {x.device}")
     if x.shape[0] > _lib.TWOSAMPLE_MAX_N:
         raise ValueError(f"n = {x.shape[0]} rows exceed SIGGAN_TWOSAMPLE_MAX_N = {_lib.TWOSAMPLE_MAX_N}")
     return x.device
@@ -71,16 +63,13 @@ def kernel_forms(x: torch.Tensor, labels: torch.Tensor, kind: str = "rbf", gamma
     n, dim, cols = x.shape[0], x.shape[1], labels.shape[1]
     forms = torch.empty(cols, 3, dtype=torch.float64, device=dev)
     diag = torch.empty(n, dtype=torch.float64, device=dev) if want_diag else None
-    stream = C.c_void_p(torch.cuda.current_stream(dev).cuda_stream)
     for lo in range(0, max(cols, 1), _lib.TWOSAMPLE_MAX_COLS):
         part = labels if cols <= _lib.TWOSAMPLE_MAX_COLS else labels[:, lo:lo + _lib.TWOSAMPLE_MAX_COLS].contiguous()
         pc = part.shape[1]
         size = lib.siggan_kernel_forms_workspace(n, pc)
         ws = torch.empty(max(size, 8) // 8, dtype=torch.float64, device=dev)
-        _lib.check(lib.siggan_kernel_forms(dev.index, C.c_void_p(x.data_ptr()), n, dim, C.byref(spec), C.c_void_p(part.data_ptr()), pc,
-                                           C.c_void_p(forms[lo:lo + pc].data_ptr()),
-                                           C.c_void_p(diag.data_ptr()) if diag is not None and lo == 0 else None,
-                                           C.c_void_p(ws.data_ptr()), size, stream))
+        _lib.check(lib.siggan_kernel_forms(dev.index, ptr(x), n, dim, C.byref(spec), ptr(part), pc, ptr(forms[lo:lo + pc]),
+                                           ptr(diag if lo == 0 else None), ptr(ws), size, stream(dev)))
     return (forms, diag) if want_diag else forms
 
 
@@ -159,10 +148,7 @@ def median_heuristic_gamma(rows: np.ndarray) -> float:
 # ---- the statistics ----------------------------------------------------------------------------------------------------------
 def _pool(real_emb: torch.Tensor, fake_emb: torch.Tensor) -> torch.Tensor:
     for name, t in (("real_emb", real_emb), ("fake_emb", fake_emb)):
-        if not isinstance(t, torch.Tensor) or t.device.type != "cuda":
-            raise ValueError(f"{name} must be a tensor on a ROCm device ('cuda:N'); there is no CPU path")
-        if t.dtype != torch.float32 or t.dim() != 2:
-            raise ValueError(f"{name} must be float32 (n, dim), got {t.dtype} {tuple(t.shape)}")
+        check_rows(name, t, torch.float32, "(n, dim)", contiguous=False)            # torch.cat below copies anyway
     if real_emb.device != fake_emb.device or real_emb.shape[1] != fake_emb.shape[1]:
         raise ValueError(f"real_emb {tuple(real_emb.shape)} on {real_emb.device} and fake_emb {tuple(fake_emb.shape)} on "
                          f"{fake_emb.device} must share device and dim")

@@ -175,4 +175,8 @@ def test_entry_points_are_declared_listed_and_exported():
         assert decl and len(decl.group(1).split(",")) == len(fn.argtypes), name
     assert f"#define SIGGAN_RESIZE_MAX_IN  {_lib.RESIZE_MAX_IN}" in h and f"#define SIGGAN_RESIZE_MAX_OUT {_lib.RESIZE_MAX_OUT}" in h
     mk = open(os.path.join(ROOT, "signature-gan_amd", "csrc", "Makefile")).read()
-    assert "resize.hip" in mk and "siggan_resize.h" in mk
+    # the source is listed; its headers, siggan_resize.h among them, are tracked through the compiler's dependency files
+    assert "resize.hip" in mk and "-MMD" in mk and "-include $(OBJ:.o=.d)" in mk
+    dep = os.path.join(ROOT, "signature-gan_amd", "csrc", "resize.d")       # written beside the object by the build that made the library
+    assert os.path.exists(dep), "resize.d is missing: the library was not built by csrc/Makefile"
+    assert "siggan_resize.h" in open(dep).read()
