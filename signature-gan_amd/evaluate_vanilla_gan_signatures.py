@@ -48,7 +48,8 @@ from .resize import resize_f32, resize_u8
 from .train_vanilla_gan_signatures import save_sample_grid
 from .utils.inference import load_generator_and_config
 from .utils.frechet import FeatureMoments, embedding_spread, frechet_distance
-from .utils.metrics import (INCEPTION_AVAILABLE, LPIPS_AVAILABLE, SSIM_DIVERSITY_IMAGES, calculate_fid, calculate_foreground_ratio,
+from .utils.metrics import (DTW_DIVERSITY_IMAGES, INCEPTION_AVAILABLE, LPIPS_AVAILABLE, SSIM_DIVERSITY_IMAGES,
+                            calculate_dtw_diversity, calculate_dtw_nearest_real, calculate_fid, calculate_foreground_ratio,
                             calculate_lpips_diversity, calculate_ssim_diversity, calculate_ssim_nearest_real,
                             calculate_stroke_density, foreground_ratio_from_counts,
                             fragmentation_from_counters, shape_attributes_from_features, stroke_density_from_counts,
@@ -207,8 +208,8 @@ class ShapeSink:
 
 
 class SsimSink:
-    """Keeps the bytes of every uint8 batch it is shown, on the device (--ssim): the pixel-space comparisons need the whole set
-    at once.  ``images()``: all of them, uint8 (N, H, W)."""
+    """Keeps the bytes of every uint8 batch it is shown, on the device (--ssim, --dtw): the comparisons between images need the
+    whole set at once.  ``images()``: all of them, uint8 (N, H, W)."""
 
     def __init__(self) -> None:
         self.parts = []
@@ -457,7 +458,8 @@ def compute_metrics(fake_images, real_images: Optional[torch.Tensor], device: to
                     pixel_similarity: Optional[Dict[str, Any]] = None,
                     stroke_geometry: Optional[Dict[str, Any]] = None,
                     shape_attributes: Optional[Dict[str, Any]] = None,
-                    kid_permutations: Optional[int] = None) -> Dict[str, Any]:
+                    kid_permutations: Optional[int] = None,
+                    elastic_similarity: Optional[Dict[str, Any]] = None) -> Dict[str, Any]:
     """The report's ``metrics`` dictionary.  ``fake_images``: a GeneratedSamples (its counters are used) or a tensor.
     ``verifier``: add the Frechet distance over its embeddings (the ``verifier_*`` keys; none without it).
     ``verifier_real``: the real set as the verifier is to see it when that is not ``real_images`` (a 128x128 Generator: the
@@ -467,7 +469,8 @@ def compute_metrics(fake_images, real_images: Optional[torch.Tensor], device: to
     ``pixel_similarity``: likewise the finished ``pixel_similarity`` block (pixel_similarity_block); ``stroke_geometry``:
     likewise the finished ``stroke_geometry`` block (stroke_geometry_block); ``shape_attributes``: likewise the finished
     ``shape_attributes`` block (shape_attributes_block).  ``kid_permutations``: add ``verifier_two_sample``, the KID and
-    the MMD permutation test with that many permutations."""
+    the MMD permutation test with that many permutations.  ``elastic_similarity``: the finished ``elastic_similarity`` block
+    (elastic_similarity_block), added as it is; no key without it."""
     metrics: Dict[str, Any] = {"n_samples": len(fake_images), "image_shape": list(fake_images.shape[1:]),
                                "metrics_computed_at": datetime.now().isoformat()}
     if real_images is not None and INCEPTION_AVAILABLE:
@@ -537,6 +540,9 @@ def compute_metrics(fake_images, real_images: Optional[torch.Tensor], device: to
     if pixel_similarity is not None:
         metrics["pixel_similarity"] = pixel_similarity
         print(f"  SSIM diversity (1 - mean pairwise SSIM): {_fmt(pixel_similarity['generated_diversity']['all_pairs']['diversity'])}")
+    if elastic_similarity is not None:
+        metrics["elastic_similarity"] = elastic_similarity
+        print(f"  DTW diversity (mean pairwise distance per column): {_fmt(elastic_similarity['generated_diversity']['all_pairs']['diversity'])}")
     if stroke_geometry is not None:
         metrics["stroke_geometry"] = stroke_geometry
         g = stroke_geometry["generated"]
@@ -565,6 +571,24 @@ def pixel_similarity_block(generated: SsimSink, real: Optional[SsimSink] = None)
         true = SsimSet(real.images())
         block["real_diversity"] = calculate_ssim_diversity(true)
         block["nearest_real"] = calculate_ssim_nearest_real(fake, true)
+    return block
+
+
+def elastic_similarity_block(generated: SsimSink, real: Optional[SsimSink] = None, band: Optional[int] = None,
+                             threshold: int = 128) -> Dict[str, Any]:
+    """The report's ``elastic_similarity`` key (--dtw): {band, threshold, generated_diversity, and with a real set real_diversity
+    and nearest_real}, banded DTW distances between column profiles, per column.  Diversity:
+    utils.metrics.calculate_dtw_diversity over at most the set's first 512 images; nearest_real: calculate_dtw_nearest_real over
+    every generated and every real image.  ``band`` None: dtw.default_band of the width.  Each set is profiled once."""
+    from .dtw import DtwSet, check_band
+    fake = DtwSet(generated.images(), threshold)
+    band = check_band(band, fake.w)
+    block: Dict[str, Any] = {"band": band, "threshold": threshold, "diversity_images": DTW_DIVERSITY_IMAGES,
+                             "generated_diversity": calculate_dtw_diversity(fake, band)}
+    if real is not None and real.parts:
+        true = DtwSet(real.images(), threshold)
+        block["real_diversity"] = calculate_dtw_diversity(true, band)
+        block["nearest_real"] = calculate_dtw_nearest_real(fake, true, band)
     return block
 
 
@@ -649,6 +673,18 @@ def print_summary(metrics: Dict[str, Any]) -> None:
             nr = ps["nearest_real"]
             print(f"SSIM to the nearest real image: median {nr['median']:.4f}, max {nr['max']:.4f} (real leave-one-out median "
                   f"{_fmt(nr['real_loo_median'])}, excess {_fmt(nr['excess_median'])}; clearly positive = memorisation warning)")
+    if "elastic_similarity" in metrics:
+        es = metrics["elastic_similarity"]
+        g = es["generated_diversity"]
+        line = (f"DTW Diversity: {_fmt(g['all_pairs']['diversity'])} (mean pairwise column-profile DTW distance per column over {g['n']} "
+                f"images, band {es['band']}, higher = more diverse; {_fmt(g['lpips_pairs']['diversity'])} on the LPIPS pair set)")
+        if "real_diversity" in es:
+            line += f"; real set: {_fmt(es['real_diversity']['all_pairs']['diversity'])}"
+        print(line)
+        if "nearest_real" in es:
+            nr = es["nearest_real"]
+            print(f"DTW to the nearest real image: median {nr['median']:.4f}, min {nr['min']:.4f} per column (real leave-one-out median "
+                  f"{_fmt(nr['real_loo_median'])}, excess {_fmt(nr['excess_median'])}; clearly positive = memorisation warning)")
     if "verifier_frechet_distance" in metrics:
         vfd = metrics["verifier_frechet_distance"]
         print(f"Verifier Frechet Distance: {vfd:.4f} (lower is better)" if vfd is not None
@@ -730,6 +766,7 @@ class _Args(argparse.Namespace):
     ssim = False
     strokes = False
     shape = False
+    dtw = None
 
 
 def parse_args(argv=None) -> argparse.Namespace:
@@ -769,7 +806,15 @@ def parse_args(argv=None) -> argparse.Namespace:
                    help="Add a 'shape_attributes' block to the report: mass, centre, second moments, slant and spread of every "
                         "generated (and real) image's ink -- mean, standard deviation and 5 / 50 / 95th percentiles --, from exact "
                         "integer sums computed on the device; needs no network weights")
+    p.add_argument("--dtw", nargs="?", type=lambda v: v if v == "auto" else int(v), const="auto", default=argparse.SUPPRESS, metavar="BAND",
+                   help="Add an 'elastic_similarity' block to the report: banded dynamic time warping between the column profiles "
+                        "(ink count, first and last ink row, vertical runs) of the images -- mean pairwise distance of the generated "
+                        "set (and of the real set) as a diversity measure, and every generated image's lowest distance to a real one "
+                        "against the real set's own leave-one-out values; tolerates shifts of up to BAND columns (BAND omitted: "
+                        "max(1, width // 8)); computed on the device, needs no network weights")
     a = p.parse_args(argv, namespace=_Args())
+    if a.dtw is not None and a.dtw != "auto" and a.dtw < 0:
+        p.error("--dtw BAND must be >= 0")
     if a.verifier_kid is not None and a.verifier_kid < 1:
         p.error("--verifier_kid PERMUTATIONS must be >= 1")
     if a.components is not None and a.components != "auto" and a.components < 1:
@@ -796,7 +841,7 @@ def main(argv=None) -> int:
         if a.components is not None:
             min_area = None if a.components == "auto" else a.components
             frag_fake, frag_real = ComponentSink(min_area), ComponentSink(min_area)
-        ssim_fake, ssim_real = (SsimSink(), SsimSink()) if a.ssim else (None, None)
+        ssim_fake, ssim_real = (SsimSink(), SsimSink()) if a.ssim or a.dtw is not None else (None, None)
         stroke_fake, stroke_real = (StrokeSink(), StrokeSink()) if a.strokes else (None, None)
         shape_fake, shape_real = (ShapeSink(), ShapeSink()) if a.shape else (None, None)
         fake = generate_samples(generator, a.n_samples, generator.latent_dim, device, a.batch_size,
@@ -823,7 +868,9 @@ def main(argv=None) -> int:
                                   pixel_similarity_block(ssim_fake, ssim_real) if a.ssim else None,
                                   stroke_geometry_block(stroke_fake, stroke_real) if a.strokes else None,
                                   shape_attributes_block(shape_fake, shape_real) if a.shape else None,
-                                  kid_permutations=a.verifier_kid)
+                                  kid_permutations=a.verifier_kid,
+                                  elastic_similarity=(elastic_similarity_block(ssim_fake, ssim_real, None if a.dtw == "auto" else a.dtw)
+                                                      if a.dtw is not None else None))
         report_path = save_evaluation_report(metrics, config, output_dir, checkpoint_path, grid_paths)
         print_summary(metrics)
         print("\nEvaluation complete!")

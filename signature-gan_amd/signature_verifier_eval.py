@@ -1035,6 +1035,20 @@ def evaluate_model(model: SiameseNetwork, dataloader: DataLoader, device: torch.
     return metrics, y_true, y_scores, y_pred
 
 
+def list_signatures(test_dir: str) -> Tuple[List[str], List[Path], np.ndarray]:
+    """(writers, paths, writer_of int32 (N,)): the files SignatureTestDataset lists, writer by writer, and each file's index
+    into ``writers``.  The listing alone: no sampled pairs, no np.random."""
+    ds = SignatureTestDataset.__new__(SignatureTestDataset)
+    ds.test_dir, ds.user_signatures = Path(test_dir), {}
+    ds._load_signatures()
+    writers = list(ds.user_signatures.keys())
+    paths = [p for w in writers for p in ds.user_signatures[w]]
+    writer_of = np.array([wi for wi, w in enumerate(writers) for _ in ds.user_signatures[w]], dtype=np.int32)
+    if len(paths) < 2:
+        raise ValueError(f"No test pairs in: {test_dir}")
+    return writers, paths, writer_of
+
+
 def evaluate_all_pairs(model: SiameseNetwork, test_dir: Union[str, Path], threshold: float = 0.5, batch_size: int = 256,
                        thresholds=None) -> Dict[str, Any]:
     """Evaluate on EVERY pair of the test directory's signatures instead of a sample: N signatures give N (N - 1) / 2 pairs,
@@ -1047,14 +1061,7 @@ def evaluate_all_pairs(model: SiameseNetwork, test_dir: Union[str, Path], thresh
     'impostor_pairs', 'rank1_identification_rate': the share of signatures that have a genuine candidate and whose best genuine
     score exceeds their best impostor score, 'hardest_impostors': per writer the highest-scoring pair with another writer}."""
     model.eval()
-    ds = SignatureTestDataset.__new__(SignatureTestDataset)          # the listing alone: no sampled pairs, no np.random
-    ds.test_dir, ds.user_signatures = Path(test_dir), {}
-    ds._load_signatures()
-    writers = list(ds.user_signatures.keys())
-    paths = [p for w in writers for p in ds.user_signatures[w]]
-    writer_of = np.array([wi for wi, w in enumerate(writers) for _ in ds.user_signatures[w]], dtype=np.int32)
-    if len(paths) < 2:
-        raise ValueError(f"No test pairs in: {test_dir}")
+    writers, paths, writer_of = list_signatures(test_dir)
     device = next(model.parameters()).device
     chunks = []
     with torch.no_grad():
@@ -1081,6 +1088,53 @@ def evaluate_all_pairs(model: SiameseNetwork, test_dir: Union[str, Path], thresh
     return {'metrics': metrics, 'num_signatures': n, 'num_writers': len(writers), 'total_pairs': n * (n - 1) // 2,
             'genuine_pairs': metrics['total_genuine'], 'impostor_pairs': metrics['total_forgeries'],
             'num_thresholds': int(host["thresholds"].size), 'rank1_identification_rate': rank1, 'hardest_impostors': hardest}
+
+
+def dtw_scores(y_true: np.ndarray, distance: np.ndarray) -> Dict[str, float]:
+    """{auc, eer, eer_distance} of a distance used as a verifier: -distance goes through roc_curve / auc /
+    compute_eer_from_scores (labels 1 = genuine), and eer_distance is the distance at the EER point."""
+    y_true, score = np.asarray(y_true), -np.asarray(distance, dtype=np.float64)
+    fpr, tpr, _ = roc_curve(y_true, score)
+    eer, eer_threshold = compute_eer_from_scores(y_true, score)
+    return {'auc': auc(fpr, tpr), 'eer': eer, 'eer_distance': -eer_threshold}
+
+
+def evaluate_dtw_baseline(test_dataset: "SignatureTestDataset", device: torch.device, band: Optional[int] = None,
+                          all_pairs_dir: Optional[str] = None) -> Dict[str, Any]:
+    """A training-free baseline verifier on the pairs the Siamese network is evaluated on: every pair of ``test_dataset`` (its
+    resized bytes, get_uint8) is scored by the banded DTW distance between the two images' column profiles (dtw.dtw_paired,
+    one HIP call), a low distance meaning genuine.  Returns {band, pairs, genuine, forgery, auc, eer, eer_distance};
+    ``all_pairs_dir``: adds 'all_pairs', the same three numbers (and counts) over all N (N - 1) / 2 pairs of that directory's
+    signatures, from one dtw.dtw_matrix call.  ``band`` None: dtw.default_band(64).  It needs no checkpoint; whether it tracks
+    a trained verifier's accuracy is not measured."""
+    from .dtw import DtwSet, check_band, dtw_matrix, dtw_paired
+    band = check_band(band, IMAGE_SIZE)
+    pairs = [test_dataset.get_uint8(i) for i in range(len(test_dataset))]
+    first = torch.stack([p[0] for p in pairs]).to(device)
+    second = torch.stack([p[1] for p in pairs]).to(device)
+    y_true = np.array([int(p[2]) for p in pairs], dtype=np.int64)
+    distance = dtw_paired(first, second, band).cpu().numpy()
+    block: Dict[str, Any] = {'band': band, 'pairs': int(y_true.size), 'genuine': int(np.sum(y_true == 1)),
+                             'forgery': int(np.sum(y_true == 0)), **dtw_scores(y_true, distance)}
+    if all_pairs_dir is not None:
+        _, paths, writer_of = list_signatures(all_pairs_dir)
+        every = DtwSet(torch.from_numpy(np.stack([load_uint8(p) for p in paths])).to(device))
+        matrix = dtw_matrix(every, band=band).cpu().numpy()
+        i, j = np.triu_indices(len(paths), 1)
+        same = (writer_of[i] == writer_of[j]).astype(np.int64)
+        block['all_pairs'] = {'pairs': int(same.size), 'genuine': int(same.sum()), 'forgery': int(same.size - same.sum()),
+                              **dtw_scores(same, matrix[i, j])}
+    return block
+
+
+def print_dtw_baseline_summary(block: Dict[str, Any]) -> None:
+    """The --dtw_baseline line: the classical method beside the trained models."""
+    line = (f"DTW BASELINE (no training, band {block['band']}): ROC-AUC {block['auc']:.4f}, EER {block['eer']:.4f} at distance "
+            f"{block['eer_distance']:.0f} on {block['pairs']} pairs")
+    if 'all_pairs' in block:
+        ap = block['all_pairs']
+        line += f"; all {ap['pairs']} pairs: ROC-AUC {ap['auc']:.4f}, EER {ap['eer']:.4f}"
+    print(line)
 
 
 def print_all_pairs_summary(results: Dict[str, Dict[str, Any]]) -> None:
@@ -1240,8 +1294,10 @@ def plot_comparison_bar_chart(results: Dict[str, Dict[str, Any]], save_path: Uni
 # =============================================================================
 
 
-def generate_evaluation_report(results: Dict[str, Dict[str, Any]], output_path: Union[str, Path]) -> Dict[str, Any]:
-    """Write the evaluation report (JSON) and return it."""
+def generate_evaluation_report(results: Dict[str, Dict[str, Any]], output_path: Union[str, Path],
+                               dtw_baseline: Optional[Dict[str, Any]] = None) -> Dict[str, Any]:
+    """Write the evaluation report (JSON) and return it.  ``dtw_baseline``: evaluate_dtw_baseline's block, added as the
+    report's 'dtw_baseline' key; no key without it."""
     report = {
         'evaluation_timestamp': datetime.now().isoformat(),
         'num_models_evaluated': len(results),
@@ -1274,6 +1330,8 @@ def generate_evaluation_report(results: Dict[str, Dict[str, Any]], output_path: 
                     improvement = ((baseline_val - augmented_val) / baseline_val * 100) if baseline_val != 0 else 0
                 comparison[metric]['improvement'] = f"{improvement:+.2f}%"
         report['comparison_summary'] = comparison
+    if dtw_baseline is not None:
+        report['dtw_baseline'] = dtw_baseline
 
     output_path = Path(output_path)
     output_path.parent.mkdir(parents=True, exist_ok=True)
@@ -1346,10 +1404,13 @@ def evaluate_signature_verifier(
     pairs_per_user: int = 20,
     threshold: float = 0.5,
     device: Optional[str] = None,
-    all_pairs: bool = False
+    all_pairs: bool = False,
+    dtw_baseline: Optional[Union[int, str]] = None
 ) -> Dict[str, Any]:
     """Run the complete signature verification evaluation pipeline; returns the report dictionary.  ``all_pairs`` adds
-    evaluate_all_pairs' result per model (report key 'all_pairs') and a block to the printed summary."""
+    evaluate_all_pairs' result per model (report key 'all_pairs') and a block to the printed summary.  ``dtw_baseline``: a
+    band in columns, or 'auto' for dtw.default_band(64): adds evaluate_dtw_baseline's block on the same test pairs (report key
+    'dtw_baseline', with ``all_pairs`` also over every pair) and one line to the printed summary; it is not a model row."""
     if device is None:
         device = 'cuda' if torch.cuda.is_available() else 'cpu'
     device = torch.device(device)
@@ -1385,6 +1446,11 @@ def evaluate_signature_verifier(
     print_evaluation_summary(results)
     if all_pairs:
         print_all_pairs_summary(results)
+    baseline_block = None
+    if dtw_baseline is not None:
+        baseline_block = evaluate_dtw_baseline(test_dataset, device, None if dtw_baseline == 'auto' else dtw_baseline,
+                                               test_dir if all_pairs else None)
+        print_dtw_baseline_summary(baseline_block)
 
     print("\n[Plots] Generating visualizations...")
     plotted = plot_roc_curve(results, output_path / 'roc_curve.png')
@@ -1396,7 +1462,7 @@ def evaluate_signature_verifier(
     else:
         print("[Plot] skipped (matplotlib not available)")
 
-    report = generate_evaluation_report(results, output_path / 'evaluation_report.json')
+    report = generate_evaluation_report(results, output_path / 'evaluation_report.json', baseline_block)
 
     print("\n" + "=" * 50)
     print("EVALUATION COMPLETE")
@@ -1412,8 +1478,7 @@ def evaluate_signature_verifier(
     return report
 
 
-def main() -> None:
-    """Main entry point with CLI argument parsing."""
+def parse_args(argv=None) -> argparse.Namespace:
     parser = argparse.ArgumentParser(
         description='Evaluate trained Siamese network models for signature verification',
         formatter_class=argparse.ArgumentDefaultsHelpFormatter
@@ -1434,12 +1499,24 @@ def main() -> None:
                         help='Also evaluate on every pair of the test directory (N (N - 1) / 2 pairs) in one HIP pass')
     parser.add_argument('--device', type=str, default=None, choices=['cuda', 'cpu'],
                         help='Device to run evaluation on (default: auto-detect)')
-    args = parser.parse_args()
+    parser.add_argument('--dtw_baseline', nargs='?', type=lambda v: v if v == 'auto' else int(v), const='auto', default=None, metavar='BAND',
+                        help='Also score the test pairs with a training-free baseline: banded dynamic time warping between the '
+                             'column profiles of the two signatures, BAND columns of slack (BAND omitted: 8); adds a '
+                             "'dtw_baseline' block (ROC-AUC, EER) to the report")
+    args = parser.parse_args(argv)
 
     if not args.baseline_model and not args.augmented_model:
         parser.error("At least one of --baseline_model or --augmented_model must be provided")
     if args.device == 'cpu':
         parser.error(f"--device cpu: the verifier {_NO_CPU}")
+    if args.dtw_baseline is not None and args.dtw_baseline != 'auto' and args.dtw_baseline < 0:
+        parser.error("--dtw_baseline BAND must be >= 0")
+    return args
+
+
+def main(argv=None) -> None:
+    """Main entry point with CLI argument parsing."""
+    args = parse_args(argv)
 
     print("=" * 70)
     print("SIGNATURE VERIFICATION MODEL EVALUATION")
@@ -1462,7 +1539,8 @@ def main() -> None:
         pairs_per_user=args.pairs_per_user,
         threshold=args.threshold,
         device=args.device,
-        all_pairs=args.all_pairs
+        all_pairs=args.all_pairs,
+        dtw_baseline=args.dtw_baseline
     )
 
 

@@ -392,6 +392,49 @@ def calculate_ssim_nearest_real(generated, real) -> Dict[str, Any]:
     return nearest_real_from_best(best.cpu().numpy(), index.cpu().numpy(), loo)
 
 
+# ---- elastic similarity: banded DTW on column profiles (dtw.py) ---------------------------------------------------------------
+DTW_DIVERSITY_IMAGES = 512            # as for SSIM: a set's diversity is taken over at most its first 512 images
+
+
+def _dtw_set(images, what: str, threshold: int = 128):
+    """A dtw.DtwSet of ``images``: one as it is; uint8 (N, H, W) / (N, 1, H, W) or fp32 in [-1, 1], quantised by the generation
+    rule first, moved to the device when it is not there."""
+    from ..dtw import DtwSet
+    if isinstance(images, DtwSet):
+        return images
+    if not isinstance(images, torch.Tensor):
+        raise ValueError(f"{what} must be a tensor, got {type(images).__name__}")
+    if images.device.type != "cuda":
+        if not torch.cuda.is_available():
+            raise RuntimeError("DTW is computed on a ROCm device ('cuda:N'); there is no CPU path")
+        images = images.cuda()
+    if images.dtype != torch.uint8:
+        images = quantize_generated(images)
+    return DtwSet(images.contiguous(), threshold)
+
+
+def calculate_dtw_diversity(images, band: Optional[int] = None, max_images: int = DTW_DIVERSITY_IMAGES) -> Dict[str, Any]:
+    """Mean pairwise DTW distance of a set per column (higher = more diverse, the direction of LPIPS), over at most its first
+    ``max_images`` images: dtw.dtw_diversity of the set's own matrix, which is formed on the device.  The same signature
+    nudged sideways counts as the same, genuinely different shapes as different; it needs no network weights."""
+    from ..dtw import dtw_diversity, dtw_matrix
+    s = _dtw_set(images, "images")
+    if s.n > max_images:
+        s = s.first(max_images)
+    return dtw_diversity(dtw_matrix(s, band=band).cpu().numpy(), s.w)
+
+
+def calculate_dtw_nearest_real(generated, real, band: Optional[int] = None) -> Dict[str, Any]:
+    """Each generated image's lowest DTW distance to a real one against the real set's own leave-one-out values
+    (dtw.nearest_real_from_best): the memorisation check of --ssim made tolerant of small shifts.  Only one value and one
+    index per image leave the device; no matrix is formed."""
+    from ..dtw import dtw_best, nearest_real_from_best
+    g, r = _dtw_set(generated, "generated"), _dtw_set(real, "real")
+    best, index = dtw_best(g, r, band)
+    loo = dtw_best(r, band=band)[0].cpu().numpy() if r.n >= 2 else None
+    return nearest_real_from_best(best.cpu().numpy(), index.cpu().numpy(), loo, g.w)
+
+
 class MetricsTracker:
     """Per-epoch running values and the history of their epoch averages (utils/metrics.py:177-213)."""
 
