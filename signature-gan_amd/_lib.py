@@ -336,18 +336,15 @@ _DTW_SIGNATURES = {
     "siggan_dtw_profiles_u8": (C.c_int, [_I32, _P, _I32, _I32, _I32, _I32, _P, _P]),
     "siggan_dtw_pairs": (C.c_int, [_I32, _P, _I32, _P, _I32, _I32, _I32, _I32, _P, _P, _P, _P]),
 }
-DTW_SYMBOLS = tuple(_DTW_SIGNATURES)
+DTW_EXPORTS = tuple(_DTW_SIGNATURES)
 
-# every table above but the last, in the order the symbols joined the ABI: load() binds them, build() checks the library exports them.
+# every table above, in the order the symbols joined the ABI: load() binds them, build() checks the library exports them.
 # A new header adds its table here and nowhere else.
 GROUPS = (_SIGNATURES, _VERIFIER_SIGNATURES, _VERIFIER_GRAD_SIGNATURES, _VERIFIER_PAIRS_SIGNATURES, _VERIFIER_TOPK_SIGNATURES,
           _VERIFIER_TRAIN_SIGNATURES, _VERIFIER_DATA_SIGNATURES, _MOMENTS_SIGNATURES, _SELECT_SIGNATURES, _NEIGHBORS_SIGNATURES,
           _RESIZE_SIGNATURES, _COMPONENTS_SIGNATURES, _SSIM_SIGNATURES, _STROKES_SIGNATURES, _DIVERSE_SIGNATURES, _SHAPE_SIGNATURES,
-          _TWOSAMPLE_SIGNATURES)
+          _TWOSAMPLE_SIGNATURES, _DTW_SIGNATURES)
 ALL_EXPORTS = tuple(name for group in GROUPS for name in group)
-# GROUPS, ALL_EXPORTS and the *_EXPORTS names are held to the list above by tests/test_call_cpu.py.  Tables that joined after
-# it stand here under another name (DTW_SYMBOLS); load() binds them the same way, so a library without them does not load.
-LATER_GROUPS = (_DTW_SIGNATURES,)
 
 _lib = None
 
@@ -362,7 +359,7 @@ def load():
             f"{LIB_PATH} is missing: build it with `python -c 'import __graft_entry__ as g; g.build()'` "
             "(or `make -C signature-gan_amd/csrc`). This path has no CPU/PyTorch fallback.")
     lib = C.CDLL(LIB_PATH)
-    for group in GROUPS + LATER_GROUPS:
+    for group in GROUPS:
         for name, (res, args) in group.items():
             fn = getattr(lib, name)      # AttributeError if the library does not export the symbol
             fn.restype, fn.argtypes = res, args

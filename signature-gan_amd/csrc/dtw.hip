@@ -10,20 +10,19 @@
 //   lane 0's first diagonal, which makes D(0, 0) = d(0, 0).  Beyond 64 columns the rows go in two strips: lane 63 of the
 //   first strip drops D(63, j) into lane j & 63 of one of two `edge` registers (a readlane, then a select on the lane
 //   number), and lane 0 of the second strip reads them back as its `up`.  No LDS, no barrier, every lane active throughout.
-//   A workgroup of four waves holds four rows of a; a wave walks its slice of b's rows.  `best`: the wave keeps the smallest
-//   (distance << 32 | column) key of its row and writes it to slot (row, split); k_dtw_best takes the splits in order.
+//   A workgroup of four waves holds four rows of a; a wave walks its slice of b's rows.  The splits of b's rows and a row's
+//   `best` as a key (LowestI32) are image_pairs.h's.
 #include <hip/hip_runtime.h>
 #include <stdint.h>
 
 #include "../../include/siggan_dtw.h"
+#include "image_pairs.h"
 #include "ink_rows.h"
 
 namespace {
 
 constexpr int INF = 0x3fffffff;          // + a cost (<= 1020) stays far below INT32_MAX
-constexpr int MAX_SPLITS = 32;
 constexpr int WAVES = 4;                 // rows of a per workgroup
-constexpr unsigned long long NO_KEY = ~0ull;
 
 __global__ __launch_bounds__(256) void k_dtw_profiles(const uint8_t* __restrict__ u8, int n, int h, int w, int thr,
                                                       uint32_t* __restrict__ prof) {
@@ -110,8 +109,7 @@ __device__ __forceinline__ int dtw_pair(const int (&pa)[NS], const int (&pb)[NS]
     return result;
 }
 
-// grid (ceil(na / WAVES), splits), WAVES waves = a-rows per workgroup.  Split s owns columns [s * per, min(nb, (s + 1) * per));
-// in PAIRED mode there is one split and a wave's only column is its own row.
+// grid (ceil(na / WAVES), splits), WAVES waves = a-rows per workgroup.  In PAIRED mode a wave's only column is its own row.
 template <int NS>
 __global__ __launch_bounds__(64 * WAVES) void k_dtw_pairs(const uint32_t* __restrict__ a_prof, int na, const uint32_t* __restrict__ b_prof,
                                                           int nb, int w, int band, int mode, int per, int32_t* __restrict__ matrix,
@@ -125,32 +123,16 @@ __global__ __launch_bounds__(64 * WAVES) void k_dtw_pairs(const uint32_t* __rest
     int pa[NS], pb[NS];
 #pragma unroll
     for (int q = 0; q < NS; ++q) pa[q] = 64 * q + lane < w ? (int)a_prof[(size_t)i * w + 64 * q + lane] : 0;
-    unsigned long long best = NO_KEY;
+    unsigned long long best = LowestI32::NONE;
     for (int j = j_begin; j < j_end; ++j) {
         if (same && j == i && !matrix) continue;
 #pragma unroll
         for (int q = 0; q < NS; ++q) pb[q] = 64 * q + lane < w ? (int)b_prof[(size_t)j * w + 64 * q + lane] : 0;
         const int value = dtw_pair<NS>(pa, pb, w, band, lane);
-        if (matrix && lane == 0) matrix[paired ? (size_t)i : (size_t)i * nb + j] = value;
-        if (!(same && j == i)) {
-            const unsigned long long key = ((unsigned long long)(uint32_t)value << 32) | (unsigned long long)(uint32_t)j;
-            best = key < best ? key : best;
-        }
+        if (matrix && lane == 0) matrix[matrix_slot(paired, i, j, nb)] = value;
+        if (!(same && j == i)) keep_better<LowestI32>(best, value, j);
     }
     if (keys && lane == 0) keys[(size_t)i * S + split] = best;
-}
-
-__global__ void k_dtw_best(const unsigned long long* __restrict__ keys, int na, int S, int32_t* __restrict__ best,
-                           int32_t* __restrict__ best_index) {
-    const int i = blockIdx.x * blockDim.x + threadIdx.x;
-    if (i >= na) return;
-    unsigned long long m = NO_KEY;
-    for (int s = 0; s < S; ++s) {
-        const unsigned long long k = keys[(size_t)i * S + s];
-        m = k < m ? k : m;
-    }
-    if (best) best[i] = m != NO_KEY ? (int32_t)(m >> 32) : -1;
-    if (best_index) best_index[i] = m != NO_KEY ? (int32_t)(uint32_t)m : -1;
 }
 
 int check_width(int32_t w) {
@@ -174,57 +156,27 @@ extern "C" int siggan_dtw_profiles_u8(int32_t device, const uint8_t* u8_dev, int
 
 extern "C" int siggan_dtw_pairs(int32_t device, const uint32_t* a_prof, int32_t na, const uint32_t* b_prof, int32_t nb, int32_t w,
                                 int32_t band, int32_t mode, int32_t* matrix, int32_t* best, int32_t* best_index, void* stream) {
-    if (na < 1 || nb < 1) return FAIL(SIGGAN_E_INVALID, "na = %d, nb = %d: both must be >= 1", na, nb);
+    const bool want_best = best || best_index;
+    if (int rc = pairs_refuse_counts(na, nb)) return rc;
     if (int rc = check_width(w)) return rc;
     if (band < 0 || band > w - 1) return FAIL(SIGGAN_E_INVALID, "band = %d outside [0, %d]", band, w - 1);
-    if (mode != SIGGAN_DTW_ALL && mode != SIGGAN_DTW_SAME_SET && mode != SIGGAN_DTW_PAIRED)
-        return FAIL(SIGGAN_E_INVALID, "mode = %d is none of SIGGAN_DTW_ALL, SIGGAN_DTW_SAME_SET, SIGGAN_DTW_PAIRED", mode);
-    if (!matrix && !best && !best_index) return FAIL(SIGGAN_E_INVALID, "no output: give matrix, best or best_index");
+    if (int rc = pairs_refuse_mode_or_no_output("SIGGAN_DTW", mode, matrix || want_best)) return rc;
     if (!a_prof) return FAIL(SIGGAN_E_INVALID, "null a_prof");
-    if (mode == SIGGAN_DTW_SAME_SET) {
-        if ((b_prof && b_prof != a_prof) || nb != na)
-            return FAIL(SIGGAN_E_INVALID, "SIGGAN_DTW_SAME_SET: b must be a (null or a's pointer, nb == na)");
-        b_prof = a_prof;
-    }
+    if (int rc = pairs_refuse_same_set("SIGGAN_DTW", mode, !b_prof || b_prof == a_prof, na, nb, "a's pointer")) return rc;
+    if (mode == SIGGAN_DTW_SAME_SET) b_prof = a_prof;
     if (!b_prof) return FAIL(SIGGAN_E_INVALID, "null b_prof");
-    if (mode == SIGGAN_DTW_PAIRED) {
-        if (nb != na) return FAIL(SIGGAN_E_INVALID, "SIGGAN_DTW_PAIRED: na = %d != nb = %d", na, nb);
-        if (best || best_index) return FAIL(SIGGAN_E_INVALID, "SIGGAN_DTW_PAIRED has no best / best_index");
-    }
+    if (int rc = pairs_refuse_paired("SIGGAN_DTW", mode, na, nb, want_best)) return rc;
     if (int rc = ink_refuse_unaligned({a_prof, b_prof, matrix, best, best_index}, "every pointer")) return rc;
 
     const int row_tiles = (na + WAVES - 1) / WAVES;
-    int S = 1, per = nb;
-    const bool want_best = best || best_index;
-    if (mode != SIGGAN_DTW_PAIRED) {
-        // enough workgroups for every CU a few times over, no empty split
-        int want = (1024 + row_tiles - 1) / row_tiles;
-        want = want < 1 ? 1 : (want > MAX_SPLITS ? MAX_SPLITS : want);
-        want = want > nb ? nb : want;
-        per = (nb + want - 1) / want;
-        S = (nb + per - 1) / per;
-    }
+    const PairPlan plan = mode == SIGGAN_DTW_PAIRED ? PairPlan{1, nb} : pair_plan(nb, row_tiles, 1);
 
     DevGuard dg(device); HIPCHK(dg.err);
     hipStream_t st = (hipStream_t)stream;
-    unsigned long long* keys = nullptr;
-    if (want_best) {
-        const size_t bytes = (size_t)na * S * sizeof(unsigned long long);
-        hipError_t e = hipMallocAsync((void**)&keys, bytes, st);
-        if (e != hipSuccess) return FAIL(SIGGAN_E_NOMEM, "hipMallocAsync(%zu) -> %s", bytes, hipGetErrorString(e));
-    }
     void (*kernel)(const uint32_t*, int, const uint32_t*, int, int, int, int, int, int32_t*, unsigned long long*) =
         w <= 64 ? k_dtw_pairs<1> : k_dtw_pairs<2>;
-    hipLaunchKernelGGL(kernel, dim3((unsigned)row_tiles, (unsigned)S), dim3(64 * WAVES), 0, st, a_prof, na, b_prof, nb, w, band, mode, per,
-                       matrix, keys);
-    hipError_t launched = hipGetLastError();
-    if (want_best) {
-        if (launched == hipSuccess) {
-            hipLaunchKernelGGL(k_dtw_best, dim3(blocks(na)), dim3(256), 0, st, keys, na, S, best, best_index);
-            launched = hipGetLastError();
-        }
-        (void)hipFreeAsync(keys, st);
-    }
-    HIPCHK(launched);
-    return SIGGAN_OK;
+    return pairs_launch<LowestI32>(st, na, plan.S, best, best_index, [&](unsigned long long* keys) {
+        hipLaunchKernelGGL(kernel, dim3((unsigned)row_tiles, (unsigned)plan.S), dim3(64 * WAVES), 0, st, a_prof, na, b_prof, nb, w, band, mode,
+                           plan.per, matrix, keys);
+    });
 }

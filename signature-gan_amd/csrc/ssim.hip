@@ -12,20 +12,19 @@
 // k_ssim_pairs:   a workgroup of up to four waves keeps one a-image per wave as bytes in LDS and walks its slice of the
 //   columns in chunks of b-images staged as bytes in LDS for all its waves.  Per pair only G * (x y) is filtered; the sink
 //   reads the two images' prepared map rows, forms s with one division and keeps one partial sum per lane, which a fixed
-//   butterfly in the wave ends.  `best`: the wave keeps the largest (ordered value bits << 32 | ~column) key of its row and
-//   writes it to slot (row, split); k_ssim_best takes the splits in order.  No atomics anywhere.
+//   butterfly in the wave ends.  The splits of the columns and a row's `best` as a key (HighestF32) are image_pairs.h's.
 #include <hip/hip_runtime.h>
 #include <math.h>
 #include <stdint.h>
 
 #include "../../include/siggan_ssim.h"
-#include "host.h"
+#include "image_pairs.h"
+#include "ink_rows.h"
 
 namespace {
 
 constexpr int TAPS = SIGGAN_SSIM_TAPS;
 constexpr int HALO = TAPS - 1;
-constexpr int MAX_SPLITS = 32;
 constexpr int STAGE_BYTES = 16384;       // of b-images per chunk
 constexpr int MAX_CHUNK = 8;             // b-images per chunk at most
 constexpr float SSIM_C1 = (float)((0.01 * 255.0) * (0.01 * 255.0));
@@ -121,17 +120,6 @@ __global__ __launch_bounds__(256) void k_ssim_prepare(Taps t, const uint8_t* __r
     filter_rows<NC>(t, srow[wave], h, w, lane, [&](int r, int c) { const float f = (float)x[r * w + c]; return f * f; }, s1);
 }
 
-// An fp32 bit pattern as an unsigned integer of the same order (SSIM lies in [-1, 1]).
-__device__ __forceinline__ uint32_t ordered_bits(float f) {
-    const uint32_t u = __float_as_uint(f);
-    return (u & 0x80000000u) ? ~u : (u | 0x80000000u);
-}
-__device__ __forceinline__ float unordered_bits(uint32_t u) { return __uint_as_float((u & 0x80000000u) ? (u ^ 0x80000000u) : ~u); }
-// "higher value, then lower column"; 0 = no candidate (no finite value maps to 0)
-__device__ __forceinline__ unsigned long long best_key(float value, int j) {
-    return ((unsigned long long)ordered_bits(value) << 32) | (unsigned long long)(~(uint32_t)j);
-}
-
 template <int NC> struct PairSink {
     const float* amu; const float* avar; const float* bmu; const float* bvar; int ow;
     float mx[NC], vx[NC], my[NC], vy[NC], sum;
@@ -149,8 +137,7 @@ template <int NC> struct PairSink {
 };
 
 // grid (ceil(na / RW), splits), RW = blockDim.x / 64 waves = a-images per workgroup.  Dynamic LDS: RW * 2 * w floats, then
-// RW a-images, then `chunk` b-images, h * w bytes each.  Split s owns columns [s * per, min(nb, (s + 1) * per)); in PAIRED
-// mode there is one split and a workgroup's columns are its own rows.
+// RW a-images, then `chunk` b-images, h * w bytes each.  In PAIRED mode a workgroup's columns are its own rows.
 template <int NC>
 __global__ __launch_bounds__(256) void k_ssim_pairs(Taps t, const uint8_t* __restrict__ a_u8, const float* __restrict__ a_maps, int na,
                                                     const uint8_t* __restrict__ b_u8, const float* __restrict__ b_maps, int nb, int h,
@@ -174,7 +161,7 @@ __global__ __launch_bounds__(256) void k_ssim_pairs(Taps t, const uint8_t* __res
     for (int e = tid; e < na_here * words; e += threads)
         sa32[e] = reinterpret_cast<const unsigned*>(a_u8 + (size_t)i0 * hw)[e];
     const float count = (float)(oh * ow);
-    unsigned long long best = 0ull;
+    unsigned long long best = HighestF32::NONE;
     for (int jc = j_begin; jc < j_end; jc += chunk) {
         const int cnt = min(chunk, j_end - jc);
         __syncthreads();                                                 // the previous chunk is consumed
@@ -194,28 +181,12 @@ __global__ __launch_bounds__(256) void k_ssim_pairs(Taps t, const uint8_t* __res
 #pragma unroll
             for (int o = 32; o > 0; o >>= 1) total += __shfl_xor(total, o, 64);
             const float value = total / count;
-            if (matrix && lane == 0) matrix[paired ? (size_t)i : (size_t)i * nb + j] = value;
-            if (!(same && j == i)) {
-                const unsigned long long key = best_key(value, j);
-                best = key > best ? key : best;
-            }
+            if (matrix && lane == 0) matrix[matrix_slot(paired, i, j, nb)] = value;
+            if (!(same && j == i)) keep_better<HighestF32>(best, value, j);
             wave_sync();                                                 // the last row's readers before the next pair writes
         }
     }
     if (keys && i < na && lane == 0) keys[(size_t)i * S + split] = best;
-}
-
-__global__ void k_ssim_best(const unsigned long long* __restrict__ keys, int na, int S, float* __restrict__ best,
-                            int32_t* __restrict__ best_index) {
-    const int i = blockIdx.x * blockDim.x + threadIdx.x;
-    if (i >= na) return;
-    unsigned long long m = 0ull;
-    for (int s = 0; s < S; ++s) {
-        const unsigned long long k = keys[(size_t)i * S + s];
-        m = k > m ? k : m;
-    }
-    if (best) best[i] = m ? unordered_bits((uint32_t)(m >> 32)) : -1.0f;
-    if (best_index) best_index[i] = m ? (int32_t)(~(uint32_t)m) : -1;
 }
 
 int check_size(int32_t h, int32_t w) {
@@ -225,8 +196,6 @@ int check_size(int32_t h, int32_t w) {
         return FAIL(SIGGAN_E_INVALID, "width = %d must be a multiple of 4 in [%d, %d]", w, SIGGAN_SSIM_MIN_WIDTH, SIGGAN_SSIM_MAX_SIZE);
     return SIGGAN_OK;
 }
-
-inline bool misaligned(const void* p) { return (reinterpret_cast<uintptr_t>(p) & 3) != 0; }
 
 }  // namespace
 
@@ -248,7 +217,7 @@ extern "C" int siggan_ssim_prepare_u8(int32_t device, const uint8_t* u8_dev, int
     if (n < 1) return FAIL(SIGGAN_E_INVALID, "n = %d < 1", n);
     if (int rc = check_size(h, w)) return rc;
     if (!u8_dev || !maps_dev) return FAIL(SIGGAN_E_INVALID, "null image or map tensor");
-    if (misaligned(u8_dev) || misaligned(maps_dev)) return FAIL(SIGGAN_E_INVALID, "u8_dev and maps_dev must be 4-byte aligned");
+    if (int rc = ink_refuse_unaligned({u8_dev, maps_dev}, "u8_dev and maps_dev")) return rc;
     DevGuard dg(device); HIPCHK(dg.err);
     void (*kernel)(Taps, const uint8_t*, int, int, int, float*) = w <= 64 ? k_ssim_prepare<1> : k_ssim_prepare<2>;
     hipLaunchKernelGGL(kernel, dim3((unsigned)((n + 3) / 4)), dim3(256), 0, (hipStream_t)stream, host_taps(), u8_dev, n, h, w, maps_dev);
@@ -259,66 +228,33 @@ extern "C" int siggan_ssim_prepare_u8(int32_t device, const uint8_t* u8_dev, int
 extern "C" int siggan_ssim_pairs(int32_t device, const uint8_t* a_u8, const float* a_maps, int32_t na, const uint8_t* b_u8,
                                  const float* b_maps, int32_t nb, int32_t h, int32_t w, int32_t mode, float* matrix, float* best,
                                  int32_t* best_index, void* stream) {
-    if (na < 1 || nb < 1) return FAIL(SIGGAN_E_INVALID, "na = %d, nb = %d: both must be >= 1", na, nb);
+    const bool want_best = best || best_index;
+    if (int rc = pairs_refuse_counts(na, nb)) return rc;
     if (int rc = check_size(h, w)) return rc;
-    if (mode != SIGGAN_SSIM_ALL && mode != SIGGAN_SSIM_SAME_SET && mode != SIGGAN_SSIM_PAIRED)
-        return FAIL(SIGGAN_E_INVALID, "mode = %d is none of SIGGAN_SSIM_ALL, SIGGAN_SSIM_SAME_SET, SIGGAN_SSIM_PAIRED", mode);
-    if (!matrix && !best && !best_index) return FAIL(SIGGAN_E_INVALID, "no output: give matrix, best or best_index");
+    if (int rc = pairs_refuse_mode_or_no_output("SIGGAN_SSIM", mode, matrix || want_best)) return rc;
     if (!a_u8 || !a_maps) return FAIL(SIGGAN_E_INVALID, "null a_u8 or a_maps");
-    if (mode == SIGGAN_SSIM_SAME_SET) {
-        if ((b_u8 && b_u8 != a_u8) || (b_maps && b_maps != a_maps) || nb != na)
-            return FAIL(SIGGAN_E_INVALID, "SIGGAN_SSIM_SAME_SET: b must be a (null or a's pointers, nb == na)");
-        b_u8 = a_u8; b_maps = a_maps;
-    }
+    if (int rc = pairs_refuse_same_set("SIGGAN_SSIM", mode, (!b_u8 || b_u8 == a_u8) && (!b_maps || b_maps == a_maps), na, nb, "a's pointers")) return rc;
+    if (mode == SIGGAN_SSIM_SAME_SET) { b_u8 = a_u8; b_maps = a_maps; }
     if (!b_u8 || !b_maps) return FAIL(SIGGAN_E_INVALID, "null b_u8 or b_maps");
-    if (mode == SIGGAN_SSIM_PAIRED) {
-        if (nb != na) return FAIL(SIGGAN_E_INVALID, "SIGGAN_SSIM_PAIRED: na = %d != nb = %d", na, nb);
-        if (best || best_index) return FAIL(SIGGAN_E_INVALID, "SIGGAN_SSIM_PAIRED has no best / best_index");
-    }
-    if (misaligned(a_u8) || misaligned(a_maps) || misaligned(b_u8) || misaligned(b_maps) || misaligned(matrix) || misaligned(best) ||
-        misaligned(best_index))
-        return FAIL(SIGGAN_E_INVALID, "every pointer must be 4-byte aligned");
+    if (int rc = pairs_refuse_paired("SIGGAN_SSIM", mode, na, nb, want_best)) return rc;
+    if (int rc = ink_refuse_unaligned({a_u8, a_maps, b_u8, b_maps, matrix, best, best_index}, "every pointer")) return rc;
 
     const int hw = h * w;
     const int RW = hw <= 8192 ? 4 : 2;                                   // a-images (waves) per workgroup: LDS stays under 64 KiB
     int chunk = STAGE_BYTES / hw;
     chunk = chunk < 1 ? 1 : (chunk > MAX_CHUNK ? MAX_CHUNK : chunk);
     const int row_tiles = (na + RW - 1) / RW;
-    int S = 1, per = nb;
-    const bool want_best = best || best_index;
-    if (mode == SIGGAN_SSIM_PAIRED) {
-        chunk = chunk < RW ? chunk : RW;
-    } else {
-        // enough workgroups for every CU a few times over, whole chunks per split, no empty split
-        const int chunks = (nb + chunk - 1) / chunk;
-        int want = (1024 + row_tiles - 1) / row_tiles;
-        want = want < 1 ? 1 : (want > MAX_SPLITS ? MAX_SPLITS : want);
-        want = want > chunks ? chunks : want;
-        per = ((chunks + want - 1) / want) * chunk;
-        S = (nb + per - 1) / per;
-    }
+    PairPlan plan{1, nb};
+    if (mode == SIGGAN_SSIM_PAIRED) chunk = chunk < RW ? chunk : RW;
+    else plan = pair_plan(nb, row_tiles, chunk);                          // whole chunks per split
     const size_t lds = (size_t)RW * 2 * w * sizeof(float) + (size_t)(RW + chunk) * hw;
 
     DevGuard dg(device); HIPCHK(dg.err);
     hipStream_t st = (hipStream_t)stream;
-    unsigned long long* keys = nullptr;
-    if (want_best) {
-        const size_t bytes = (size_t)na * S * sizeof(unsigned long long);
-        hipError_t e = hipMallocAsync((void**)&keys, bytes, st);
-        if (e != hipSuccess) return FAIL(SIGGAN_E_NOMEM, "hipMallocAsync(%zu) -> %s", bytes, hipGetErrorString(e));
-    }
     void (*kernel)(Taps, const uint8_t*, const float*, int, const uint8_t*, const float*, int, int, int, int, int, int, float*,
                    unsigned long long*) = w <= 64 ? k_ssim_pairs<1> : k_ssim_pairs<2>;
-    hipLaunchKernelGGL(kernel, dim3((unsigned)row_tiles, (unsigned)S), dim3(64 * RW), lds, st, host_taps(), a_u8, a_maps, na, b_u8,
-                       b_maps, nb, h, w, mode, chunk, per, matrix, keys);
-    hipError_t launched = hipGetLastError();
-    if (want_best) {
-        if (launched == hipSuccess) {
-            hipLaunchKernelGGL(k_ssim_best, dim3(blocks(na)), dim3(256), 0, st, keys, na, S, best, best_index);
-            launched = hipGetLastError();
-        }
-        (void)hipFreeAsync(keys, st);
-    }
-    HIPCHK(launched);
-    return SIGGAN_OK;
+    return pairs_launch<HighestF32>(st, na, plan.S, best, best_index, [&](unsigned long long* keys) {
+        hipLaunchKernelGGL(kernel, dim3((unsigned)row_tiles, (unsigned)plan.S), dim3(64 * RW), lds, st, host_taps(), a_u8, a_maps, na, b_u8,
+                           b_maps, nb, h, w, mode, chunk, plan.per, matrix, keys);
+    });
 }

@@ -24,9 +24,7 @@ import torch
 
 from . import _call, _lib
 from ._call import as_int, ptr, stream
-
-LPIPS_IMAGES, LPIPS_REACH = 100, 10        # the reference's LPIPS pair set: i < j < i + 10 over the first 100 images
-CLOSEST = 5
+from ._image_pairs import CLOSEST, LPIPS_IMAGES, LPIPS_REACH, PAIRED, host, mode, nearest_real, outputs, pair_sets  # noqa: F401
 
 
 def default_band(w: int) -> int:
@@ -127,17 +125,17 @@ def _pairs(a: DtwSet, b: Optional[DtwSet], band: int, mode: int, matrix=None, be
                                             ptr(best), ptr(index), stream(a.device)))
 
 
-def _mode(b: Optional[DtwSet]) -> int:
-    return _lib.DTW_ALL if b is not None else _lib.DTW_SAME_SET
+def _scored(a: Images, b: Optional[Images], band, matrix: bool, best: bool):
+    a, b, band = _two(a, b, band)
+    out = outputs(a, b, torch.int32, matrix, best)
+    _pairs(a, b, band, mode(b), *out)
+    return out
 
 
 def dtw_matrix(a: Images, b: Optional[Images] = None, band: Optional[int] = None) -> torch.Tensor:
     """int32 (len(a), len(b)) on the device: the DTW distance of every a_i to every b_j within ``band`` columns (None:
     default_band(W)).  ``b`` None: a against itself, (n, n), symmetric with a diagonal of 0."""
-    a, b, band = _two(a, b, band)
-    out = torch.empty((a.n, b.n if b is not None else a.n), dtype=torch.int32, device=a.device)
-    _pairs(a, b, band, _mode(b), matrix=out)
-    return out
+    return _scored(a, b, band, True, False)[0]
 
 
 def dtw_paired(a: Images, b: Images, band: Optional[int] = None) -> torch.Tensor:
@@ -146,7 +144,7 @@ def dtw_paired(a: Images, b: Images, band: Optional[int] = None) -> torch.Tensor
         raise ValueError("b must be a tensor or a DtwSet, got NoneType")
     a, b, band = _two(a, b, band, paired=True)
     out = torch.empty((a.n,), dtype=torch.int32, device=a.device)
-    _pairs(a, b, band, _lib.DTW_PAIRED, matrix=out)
+    _pairs(a, b, band, PAIRED, matrix=out)
     return out
 
 
@@ -154,30 +152,15 @@ def dtw_best(a: Images, b: Optional[Images] = None, band: Optional[int] = None) 
     """(int32 (len(a),), int32 (len(a),)) on the device: each a_i's lowest distance to an image of ``b`` and that image's
     index, equal values resolved to the lower index.  ``b`` None: to another image of ``a`` itself (j = i is left out; a
     single image gives -1 / -1).  No matrix is formed."""
-    a, b, band = _two(a, b, band)
-    best = torch.empty((a.n,), dtype=torch.int32, device=a.device)
-    index = torch.empty((a.n,), dtype=torch.int32, device=a.device)
-    _pairs(a, b, band, _mode(b), best=best, index=index)
-    return best, index
+    return _scored(a, b, band, False, True)[1:]
 
 
 def dtw_matrix_and_best(a: Images, b: Optional[Images] = None, band: Optional[int] = None) -> Tuple[torch.Tensor, torch.Tensor, torch.Tensor]:
     """(dtw_matrix, *dtw_best) of the same arguments out of one launch; the integers are those of the separate calls."""
-    a, b, band = _two(a, b, band)
-    out = torch.empty((a.n, b.n if b is not None else a.n), dtype=torch.int32, device=a.device)
-    best = torch.empty((a.n,), dtype=torch.int32, device=a.device)
-    index = torch.empty((a.n,), dtype=torch.int32, device=a.device)
-    _pairs(a, b, band, _mode(b), matrix=out, best=best, index=index)
-    return out, best, index
+    return _scored(a, b, band, True, True)
 
 
 # ---- numpy reductions of ready results ----------------------------------------------------------------------------------
-def _host(x, dtype) -> np.ndarray:
-    if isinstance(x, torch.Tensor):
-        x = x.detach().cpu().numpy()
-    return np.asarray(x, dtype=dtype)
-
-
 def _width(w) -> int:
     w = as_int(w, "w")
     if w < 1:
@@ -197,14 +180,9 @@ def dtw_diversity(matrix, w: int) -> Dict[str, Any]:
     the width ``w``): higher means more diverse, the direction of LPIPS.  Two pair sets: ``lpips_pairs``, the reference's
     LPIPS pair set (i < j < i + 10 over the first min(100, n) images), and ``all_pairs``, the full upper triangle.  A set of
     one image has no pair: means are None."""
-    m, w = _host(matrix, np.float64), _width(w)
-    if m.ndim != 2 or m.shape[0] != m.shape[1] or m.shape[0] < 1:
-        raise ValueError(f"matrix must be (n, n) with n >= 1, got {m.shape}")
-    n = m.shape[0]
-    first = min(LPIPS_IMAGES, n)
-    near = [m[i, j] for i in range(first) for j in range(i + 1, min(i + LPIPS_REACH, first))]
-    return {"n": n, "w": w, "lpips_pairs": _pair_set(np.asarray(near, dtype=np.float64), w),
-            "all_pairs": _pair_set(m[np.triu_indices(n, 1)], w)}
+    w = _width(w)
+    n, near, every = pair_sets(matrix)
+    return {"n": n, "w": w, "lpips_pairs": _pair_set(near, w), "all_pairs": _pair_set(every, w)}
 
 
 def nearest_real_from_best(best, index, real_loo_best, w: int) -> Dict[str, Any]:
@@ -214,15 +192,7 @@ def nearest_real_from_best(best, index, real_loo_best, w: int) -> Dict[str, Any]
     real_loo_median - median, where a clearly positive value says the generated images sit closer to a real one than the
     real ones sit to each other: the memorisation warning; closest: the five (generated index, real index, distance per
     column) of lowest distance, equal values by generated index."""
-    raw, index, w = _host(best, np.int64).reshape(-1), _host(index, np.int64).reshape(-1), _width(w)
-    if raw.size < 1 or raw.size != index.size:
-        raise ValueError(f"best has {raw.size} entries and index {index.size}: need equally many, at least one")
-    best = raw.astype(np.float64) / w
-    loo = _host(real_loo_best, np.float64).reshape(-1) / w if real_loo_best is not None else np.zeros(0)
-    median = float(np.median(best))
-    loo_median = float(np.median(loo)) if loo.size else None
-    order = np.lexsort((np.arange(raw.size), raw))[:CLOSEST]
-    return {"n_generated": int(best.size), "n_real_loo": int(loo.size), "mean": float(np.mean(best)), "median": median,
-            "min": float(np.min(best)), "real_loo_median": loo_median,
-            "excess_median": loo_median - median if loo_median is not None else None,
-            "closest": [(int(i), int(index[i]), float(best[i])) for i in order]}
+    w = _width(w)
+    loo = host(real_loo_best, np.float64).reshape(-1) / w if real_loo_best is not None else np.zeros(0)
+    return nearest_real(host(best, np.int64).reshape(-1).astype(np.float64) / w, host(index, np.int64).reshape(-1), loo,
+                        higher_is_closer=False)

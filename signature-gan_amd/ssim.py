@@ -19,10 +19,9 @@ import torch
 
 from . import _call, _lib
 from ._call import ptr, stream
+from ._image_pairs import CLOSEST, LPIPS_IMAGES, LPIPS_REACH, PAIRED, host, mode, nearest_real, outputs, pair_sets  # noqa: F401
 
 WINDOW_TAPS, WINDOW_SIGMA = _lib.SSIM_TAPS, _lib.SSIM_SIGMA
-LPIPS_IMAGES, LPIPS_REACH = 100, 10        # the reference's LPIPS pair set: i < j < i + 10 over the first 100 images
-CLOSEST = 5
 
 
 def window() -> np.ndarray:
@@ -89,13 +88,17 @@ def _pairs(a: SsimSet, b: Optional[SsimSet], mode: int, matrix=None, best=None, 
                                              mode, ptr(matrix), ptr(best), ptr(index), stream(a.device)))
 
 
+def _scored(a: Images, b: Optional[Images], matrix: bool, best: bool):
+    a, b = _two(a, b)
+    out = outputs(a, b, torch.float32, matrix, best)
+    _pairs(a, b, mode(b), *out)
+    return out
+
+
 def ssim_matrix(a: Images, b: Optional[Images] = None) -> torch.Tensor:
     """fp32 (len(a), len(b)) on the device: SSIM of every a_i with every b_j.  ``b`` None: a against itself, (n, n) with a
     diagonal of exactly 1.0."""
-    a, b = _two(a, b)
-    out = torch.empty((a.n, b.n if b is not None else a.n), dtype=torch.float32, device=a.device)
-    _pairs(a, b, _lib.SSIM_ALL if b is not None else _lib.SSIM_SAME_SET, matrix=out)
-    return out
+    return _scored(a, b, True, False)[0]
 
 
 def ssim_paired(a: Images, b: Images) -> torch.Tensor:
@@ -106,7 +109,7 @@ def ssim_paired(a: Images, b: Images) -> torch.Tensor:
     if a.n != b.n:
         raise ValueError(f"a holds {a.n} images and b {b.n}: paired SSIM needs equally many")
     out = torch.empty((a.n,), dtype=torch.float32, device=a.device)
-    _pairs(a, b, _lib.SSIM_PAIRED, matrix=out)
+    _pairs(a, b, PAIRED, matrix=out)
     return out
 
 
@@ -114,30 +117,15 @@ def ssim_best(a: Images, b: Optional[Images] = None) -> Tuple[torch.Tensor, torc
     """(fp32 (len(a),), int32 (len(a),)) on the device: each a_i's highest SSIM to an image of ``b`` and that image's index,
     equal values resolved to the lower index.  ``b`` None: to another image of ``a`` itself (j = i is left out; a single image
     gives -1.0 / -1).  No matrix is formed."""
-    a, b = _two(a, b)
-    best = torch.empty((a.n,), dtype=torch.float32, device=a.device)
-    index = torch.empty((a.n,), dtype=torch.int32, device=a.device)
-    _pairs(a, b, _lib.SSIM_ALL if b is not None else _lib.SSIM_SAME_SET, best=best, index=index)
-    return best, index
+    return _scored(a, b, False, True)[1:]
 
 
 def ssim_matrix_and_best(a: Images, b: Optional[Images] = None) -> Tuple[torch.Tensor, torch.Tensor, torch.Tensor]:
     """(ssim_matrix, *ssim_best) of the same arguments out of one launch; the bits are those of the separate calls."""
-    a, b = _two(a, b)
-    out = torch.empty((a.n, b.n if b is not None else a.n), dtype=torch.float32, device=a.device)
-    best = torch.empty((a.n,), dtype=torch.float32, device=a.device)
-    index = torch.empty((a.n,), dtype=torch.int32, device=a.device)
-    _pairs(a, b, _lib.SSIM_ALL if b is not None else _lib.SSIM_SAME_SET, matrix=out, best=best, index=index)
-    return out, best, index
+    return _scored(a, b, True, True)
 
 
 # ---- numpy reductions of ready results ----------------------------------------------------------------------------------
-def _host(x, dtype) -> np.ndarray:
-    if isinstance(x, torch.Tensor):
-        x = x.detach().cpu().numpy()
-    return np.asarray(x, dtype=dtype)
-
-
 def _pair_set(values: np.ndarray) -> Dict[str, Any]:
     if values.size == 0:
         return {"pairs": 0, "mean_ssim": None, "diversity": None}
@@ -149,13 +137,8 @@ def ssim_diversity(matrix) -> Dict[str, Any]:
     """Mean pairwise SSIM of a set from its own (n, n) matrix, and ``diversity`` = 1 - mean: higher means more diverse, the
     direction of LPIPS.  Two pair sets: ``lpips_pairs``, the reference's LPIPS pair set (i < j < i + 10 over the first
     min(100, n) images), and ``all_pairs``, the full upper triangle.  A set of one image has no pair: means are None."""
-    m = _host(matrix, np.float64)
-    if m.ndim != 2 or m.shape[0] != m.shape[1] or m.shape[0] < 1:
-        raise ValueError(f"matrix must be (n, n) with n >= 1, got {m.shape}")
-    n = m.shape[0]
-    first = min(LPIPS_IMAGES, n)
-    near = [m[i, j] for i in range(first) for j in range(i + 1, min(i + LPIPS_REACH, first))]
-    return {"n": n, "lpips_pairs": _pair_set(np.asarray(near, dtype=np.float64)), "all_pairs": _pair_set(m[np.triu_indices(n, 1)])}
+    n, near, every = pair_sets(matrix)
+    return {"n": n, "lpips_pairs": _pair_set(near), "all_pairs": _pair_set(every)}
 
 
 def nearest_real_from_best(best, index, real_loo_best=None) -> Dict[str, Any]:
@@ -164,14 +147,5 @@ def nearest_real_from_best(best, index, real_loo_best=None) -> Dict[str, Any]:
     mean / median / max; real_loo_median; excess_median = median - real_loo_median, where a clearly positive value says the
     generated images sit closer to a real one than the real ones sit to each other: the memorisation warning; closest: the
     five (generated index, real index, SSIM) of highest SSIM, equal values by generated index."""
-    best, index = _host(best, np.float64).reshape(-1), _host(index, np.int64).reshape(-1)
-    if best.size < 1 or best.size != index.size:
-        raise ValueError(f"best has {best.size} entries and index {index.size}: need equally many, at least one")
-    loo = _host(real_loo_best, np.float64).reshape(-1) if real_loo_best is not None else np.zeros(0)
-    median = float(np.median(best))
-    loo_median = float(np.median(loo)) if loo.size else None
-    order = np.lexsort((np.arange(best.size), -best))[:CLOSEST]
-    return {"n_generated": int(best.size), "n_real_loo": int(loo.size), "mean": float(np.mean(best)), "median": median,
-            "max": float(np.max(best)), "real_loo_median": loo_median,
-            "excess_median": median - loo_median if loo_median is not None else None,
-            "closest": [(int(i), int(index[i]), float(best[i])) for i in order]}
+    loo = host(real_loo_best, np.float64).reshape(-1) if real_loo_best is not None else np.zeros(0)
+    return nearest_real(host(best, np.float64).reshape(-1), host(index, np.int64).reshape(-1), loo, higher_is_closer=True)

@@ -353,21 +353,20 @@ def calculate_shape_attributes(images: torch.Tensor) -> Dict[str, Any]:
 SSIM_DIVERSITY_IMAGES = 512           # a set's diversity is taken over at most its first 512 images (131 k pairs)
 
 
-def _ssim_set(images, what: str):
-    """An ssim.SsimSet of ``images``: one as it is; uint8 (N, S, S) / (N, 1, S, S) or fp32 in [-1, 1], quantised by the generation
-    rule first, moved to the device when it is not there."""
-    from ..ssim import SsimSet
-    if isinstance(images, SsimSet):
+def _image_set(images, what: str, set_class, op: str):
+    """A ``set_class`` (ssim.SsimSet, dtw.DtwSet) of ``images``: one as it is; uint8 (N, H, W) / (N, 1, H, W) or fp32 in [-1, 1], quantised
+    by the generation rule first, moved to the device when it is not there.  ``op``: the measure, as the refusal names it."""
+    if isinstance(images, set_class):
         return images
     if not isinstance(images, torch.Tensor):
         raise ValueError(f"{what} must be a tensor, got {type(images).__name__}")
     if images.device.type != "cuda":
         if not torch.cuda.is_available():
-            raise RuntimeError("SSIM is computed on a ROCm device ('cuda:N'); there is no CPU path")
+            raise RuntimeError(f"{op} is computed on a ROCm device ('cuda:N'); there is no CPU path")
         images = images.cuda()
     if images.dtype != torch.uint8:
         images = quantize_generated(images)
-    return SsimSet(images.contiguous())
+    return set_class(images.contiguous())
 
 
 def calculate_ssim_diversity(images, max_images: int = SSIM_DIVERSITY_IMAGES) -> Dict[str, Any]:
@@ -375,7 +374,7 @@ def calculate_ssim_diversity(images, max_images: int = SSIM_DIVERSITY_IMAGES) ->
     ``max_images`` images: ssim.ssim_diversity of the set's own matrix, which is formed on the device.  A pixel-space measure
     that needs no network weights."""
     from ..ssim import SsimSet, ssim_diversity, ssim_matrix
-    s = _ssim_set(images, "images")
+    s = _image_set(images, "images", SsimSet, "SSIM")
     if s.n > max_images:
         s = SsimSet(s.u8[:max_images])
     return ssim_diversity(ssim_matrix(s).cpu().numpy())
@@ -385,8 +384,8 @@ def calculate_ssim_nearest_real(generated, real) -> Dict[str, Any]:
     """Each generated image's highest SSIM to a real one against the real set's own leave-one-out values
     (ssim.nearest_real_from_best): the memorisation check in pixel space.  Only one value and one index per image leave the
     device; no matrix is formed."""
-    from ..ssim import nearest_real_from_best, ssim_best
-    g, r = _ssim_set(generated, "generated"), _ssim_set(real, "real")
+    from ..ssim import SsimSet, nearest_real_from_best, ssim_best
+    g, r = _image_set(generated, "generated", SsimSet, "SSIM"), _image_set(real, "real", SsimSet, "SSIM")
     best, index = ssim_best(g, r)
     loo = ssim_best(r)[0].cpu().numpy() if r.n >= 2 else None
     return nearest_real_from_best(best.cpu().numpy(), index.cpu().numpy(), loo)
@@ -396,29 +395,12 @@ def calculate_ssim_nearest_real(generated, real) -> Dict[str, Any]:
 DTW_DIVERSITY_IMAGES = 512            # as for SSIM: a set's diversity is taken over at most its first 512 images
 
 
-def _dtw_set(images, what: str, threshold: int = 128):
-    """A dtw.DtwSet of ``images``: one as it is; uint8 (N, H, W) / (N, 1, H, W) or fp32 in [-1, 1], quantised by the generation
-    rule first, moved to the device when it is not there."""
-    from ..dtw import DtwSet
-    if isinstance(images, DtwSet):
-        return images
-    if not isinstance(images, torch.Tensor):
-        raise ValueError(f"{what} must be a tensor, got {type(images).__name__}")
-    if images.device.type != "cuda":
-        if not torch.cuda.is_available():
-            raise RuntimeError("DTW is computed on a ROCm device ('cuda:N'); there is no CPU path")
-        images = images.cuda()
-    if images.dtype != torch.uint8:
-        images = quantize_generated(images)
-    return DtwSet(images.contiguous(), threshold)
-
-
 def calculate_dtw_diversity(images, band: Optional[int] = None, max_images: int = DTW_DIVERSITY_IMAGES) -> Dict[str, Any]:
     """Mean pairwise DTW distance of a set per column (higher = more diverse, the direction of LPIPS), over at most its first
     ``max_images`` images: dtw.dtw_diversity of the set's own matrix, which is formed on the device.  The same signature
     nudged sideways counts as the same, genuinely different shapes as different; it needs no network weights."""
-    from ..dtw import dtw_diversity, dtw_matrix
-    s = _dtw_set(images, "images")
+    from ..dtw import DtwSet, dtw_diversity, dtw_matrix
+    s = _image_set(images, "images", DtwSet, "DTW")
     if s.n > max_images:
         s = s.first(max_images)
     return dtw_diversity(dtw_matrix(s, band=band).cpu().numpy(), s.w)
@@ -428,8 +410,8 @@ def calculate_dtw_nearest_real(generated, real, band: Optional[int] = None) -> D
     """Each generated image's lowest DTW distance to a real one against the real set's own leave-one-out values
     (dtw.nearest_real_from_best): the memorisation check of --ssim made tolerant of small shifts.  Only one value and one
     index per image leave the device; no matrix is formed."""
-    from ..dtw import dtw_best, nearest_real_from_best
-    g, r = _dtw_set(generated, "generated"), _dtw_set(real, "real")
+    from ..dtw import DtwSet, dtw_best, nearest_real_from_best
+    g, r = _image_set(generated, "generated", DtwSet, "DTW"), _image_set(real, "real", DtwSet, "DTW")
     best, index = dtw_best(g, r, band)
     loo = dtw_best(r, band=band)[0].cpu().numpy() if r.n >= 2 else None
     return nearest_real_from_best(best.cpu().numpy(), index.cpu().numpy(), loo, g.w)

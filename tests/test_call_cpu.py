@@ -158,11 +158,11 @@ def test_all_exports_is_the_groups_in_order_without_duplicates():
     by_name = [_lib.EXPORTS, _lib.VERIFIER_EXPORTS, _lib.VERIFIER_GRAD_EXPORTS, _lib.VERIFIER_PAIRS_EXPORTS, _lib.VERIFIER_TOPK_EXPORTS,
                _lib.VERIFIER_TRAIN_EXPORTS, _lib.VERIFIER_DATA_EXPORTS, _lib.MOMENTS_EXPORTS, _lib.SELECT_EXPORTS, _lib.NEIGHBORS_EXPORTS,
                _lib.RESIZE_EXPORTS, _lib.COMPONENTS_EXPORTS, _lib.SSIM_EXPORTS, _lib.STROKES_EXPORTS, _lib.DIVERSE_EXPORTS, _lib.SHAPE_EXPORTS,
-               _lib.TWOSAMPLE_EXPORTS]
+               _lib.TWOSAMPLE_EXPORTS, _lib.DTW_EXPORTS]
     assert [tuple(g) for g in _lib.GROUPS] == [tuple(e) for e in by_name]
     assert _lib.ALL_EXPORTS == tuple(name for e in by_name for name in e)
     assert len(set(_lib.ALL_EXPORTS)) == len(_lib.ALL_EXPORTS) == sum(len(e) for e in by_name)
-    assert len(_lib.EXPORTS) == 64 and _lib.ALL_EXPORTS[0] == "siggan_abi_version" and _lib.ALL_EXPORTS[-1] == "siggan_kernel_forms"
+    assert len(_lib.EXPORTS) == 64 and _lib.ALL_EXPORTS[0] == "siggan_abi_version" and _lib.ALL_EXPORTS[-1] == "siggan_dtw_pairs"
     # every *_EXPORTS tuple the module defines is a group: none can be forgotten
     named = {n for n in vars(_lib) if re.fullmatch(r"[A-Z_]*EXPORTS", n) and n != "ALL_EXPORTS"}
     assert len(named) == len(_lib.GROUPS) and {id(getattr(_lib, n)) for n in named} == {id(e) for e in by_name}

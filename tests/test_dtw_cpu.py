@@ -23,11 +23,11 @@ ROOT = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
 def test_exports_match_the_header_and_the_makefile_lists_the_source():
     header = open(os.path.join(ROOT, "include", "siggan_dtw.h")).read()
     declared = re.findall(r"^int (siggan_\w+)\(", header, flags=re.M)
-    assert tuple(declared) == _lib.DTW_SYMBOLS == ("siggan_dtw_profiles_u8", "siggan_dtw_pairs")
+    assert tuple(declared) == _lib.DTW_EXPORTS == ("siggan_dtw_profiles_u8", "siggan_dtw_pairs")
     lib = _lib.load()
-    assert all(hasattr(lib, name) for name in _lib.DTW_SYMBOLS)
-    assert not set(_lib.DTW_SYMBOLS) & set(_lib.EXPORTS) and len(_lib.EXPORTS) == 64
-    assert _lib._DTW_SIGNATURES in _lib.LATER_GROUPS and all(getattr(lib, name).argtypes is not None for name in _lib.DTW_SYMBOLS)   # load() bound them
+    assert all(hasattr(lib, name) for name in _lib.DTW_EXPORTS)
+    assert not set(_lib.DTW_EXPORTS) & set(_lib.EXPORTS) and len(_lib.EXPORTS) == 64
+    assert _lib._DTW_SIGNATURES in _lib.GROUPS and all(getattr(lib, name).argtypes is not None for name in _lib.DTW_EXPORTS)   # load() bound them
     assert _lib.ABI_VERSION == 4 and lib.siggan_abi_version() == 4
     assert int(re.search(r"#define SIGGAN_DTW_MAX_SIZE (\S+)", header).group(1)) == _lib.DTW_MAX_SIZE == 128
     enum = re.search(r"enum \{([^}]*)\}", header).group(1)

@@ -170,6 +170,23 @@ def test_the_library_refuses_before_it_touches_a_device():
     assert lib.siggan_ssim_maps_bytes(0, 64, 64) == _lib.E_ARG and lib.siggan_ssim_maps_bytes(1, 64, 130) == _lib.E_ARG
 
 
+def test_the_split_planner_is_the_two_planners_it_replaced(tmp_path):
+    """csrc/pair_plan.h -- how siggan_ssim_pairs and siggan_dtw_pairs split b's columns over the grid -- against the two
+    formulas it replaced and against what the kernels need of a plan (1 <= S <= 32, whole units per split, no empty split,
+    every column owned), for every nb in 1..4096, 44 values of row_tiles and unit in 1..8, by the stand-alone
+    csrc/pair_plan_check.cpp under AddressSanitizer and UBSan: this is what the test is about, so it starts the compiler and
+    the program."""
+    import subprocess
+    csrc = os.path.join(os.path.dirname(os.path.dirname(os.path.abspath(__file__))), "signature-gan_amd", "csrc")
+    exe = str(tmp_path / "pair_plan_check")
+    subprocess.run([os.environ.get("HIPCC", "/opt/rocm/bin/hipcc"), "-x", "c++", "-O1", "-g", "-std=c++17", "-Wall",
+                    "-fsanitize=address,undefined", "-fno-sanitize-recover=all", "-o", exe, os.path.join(csrc, "pair_plan_check.cpp")],
+                   check=True, cwd=str(tmp_path))
+    run = subprocess.run([exe], capture_output=True, text=True, timeout=120)
+    assert run.returncode == 0, run.stdout + run.stderr
+    assert run.stdout.strip() == f"OK {4096 * 44 * 8}", run.stdout + run.stderr
+
+
 def test_exports_match_the_header():
     header = open(os.path.join(os.path.dirname(os.path.dirname(os.path.abspath(__file__))), "include", "siggan_ssim.h")).read()
     declared = re.findall(r"^(?:int|int64_t) (siggan_\w+)\(", header, flags=re.M)

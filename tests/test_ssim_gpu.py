@@ -132,6 +132,18 @@ def test_best_is_numpys_first_maximum_of_the_calls_own_matrix(shape):
         assert best[0].item() == 1.0 and index[0].item() == 1
         best, index = ssim.ssim_best(sa)
         assert (best[0].item(), index[0].item(), best[9].item(), index[9].item()) == (1.0, 9, 1.0, 0)
+    if shape == (11, 12):
+        # a tie ACROSS splits: one row against nine columns is the smallest case of two splits (columns 0..7 and 8), and above
+        # B[1] and B[7] share a split.  Columns of B that are no copy of A[0], then A[0] at 3 and 8: the lower column wins
+        # although the later split holds the same key value; at 8 alone: the later split's key is the only 1.0
+        others = [j for j in range(world.nb) if not np.array_equal(world.b[j], world.a[0])][:9]
+        for placed in ((3, 8), (8,)):
+            columns = world.b[others].copy()
+            columns[list(placed)] = world.a[0]
+            a, b = ssim.SsimSet(dev(world.a[:1])), ssim.SsimSet(dev(columns))
+            best, index = ssim.ssim_best(a, b)
+            _, both, both_index = ssim.ssim_matrix_and_best(a, b)
+            assert (best.item(), index.item(), both.item(), both_index.item()) == (1.0, placed[0], 1.0, placed[0]), placed
 
 
 @pytest.mark.parametrize("shape", [(11, 12), (40, 52), (64, 128)], ids=["11x12", "40x52", "64x128"])
