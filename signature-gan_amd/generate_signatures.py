@@ -52,7 +52,12 @@ times as large in the frame, ``--edit_boldness_scale R`` multiplies its ink mass
 units of the image side, DY downwards); ``--edit_keep W`` weighs staying the same signature.  The latent vectors are the ones
 the plain run draws for the same ``--seed``, so the two runs' files pair up.  ``<prefix>_edit.json`` records, per file, the
 features before, the targets, the features after and the objective before and after.  Whether an edit reaches its target
-depends on the checkpoint, and whether edited signatures help a verifier's training is not measured."""
+depends on the checkpoint, and whether edited signatures help a verifier's training is not measured.
+
+``--adapt PATH --adapt_preprocess`` and ``--project PATH --project_preprocess`` take raw scans: every file goes through
+preprocess_signatures.preprocess_single_image at the checkpoint's size (denoise, validate, crop, area resize, centre, CLAHE on
+the device) instead of the plain decode-and-resize, the preprocessed targets are written as ``<prefix>_target_%06d.png`` and
+named in the JSON report; a scan that preprocessing rejects ends the run with an error."""
 import argparse
 import json
 import os
@@ -256,7 +261,8 @@ def generate_edited(generator, discriminator, n_samples: int, output_dir: str, b
 def run_projection(generator, path: str, output_dir: str, prefix: str = "signature", steps: int = 200, lr: float = 0.05,
                    restarts: int = 1, seed: Optional[int] = None, discriminator=None, realism_weight: float = 0.0,
                    prior_weight: float = 0.0, verifier=None, identity_weight: float = 0.0,
-                   identity_score_weight: float = 0.0, verifier_resize: bool = False, project_ssim: bool = False) -> None:
+                   identity_score_weight: float = 0.0, verifier_resize: bool = False, project_ssim: bool = False,
+                   preprocess: bool = False) -> None:
     """Reconstructions of the image file / the images of the directory ``path``: ``<prefix>_projection_%06d.png`` each, and
     ``<prefix>_projection.json``: [{file, reconstruction, loss, z}, ...] in the same order; with ``realism_weight`` > 0 every
     record also holds ``realism``, the Discriminator's score of the reconstruction.  With a ``verifier`` every record holds
@@ -264,10 +270,13 @@ def run_projection(generator, path: str, output_dir: str, prefix: str = "signatu
     ``identity_pixel_only``: the same two numbers for the projection without the identity term (what the term bought).
     ``verifier_resize``: the verifier reads targets and reconstructions through the device resize to 64x64 (a 128x128 Generator).
     ``project_ssim``: every record also holds ``ssim``, the structural similarity (ssim.ssim_paired) of the target's bytes and
-    the reconstruction's bytes as written."""
+    the reconstruction's bytes as written.  ``preprocess``: the files are raw scans; every target goes through
+    load_preprocessed_targets instead of the plain load, is written as ``<prefix>_target_%06d.png`` and named in its record
+    under ``preprocessed_target``."""
     from PIL import Image
     os.makedirs(output_dir, exist_ok=True)
-    files, targets = load_target_images(path, generator.output_size)
+    files, targets = load_preprocessed_targets(path, generator.output_size) if preprocess else load_target_images(path, generator.output_size)
+    target_names = save_preprocessed_targets(targets, output_dir, prefix) if preprocess else None
     print(f"Projecting {len(files)} images into the latent space ({steps} steps, {restarts} restart(s))...")
     kw = dict(steps=steps, lr=lr, seed=seed, restarts=restarts, discriminator=discriminator, realism_weight=realism_weight,
               prior_weight=prior_weight)
@@ -301,6 +310,8 @@ def run_projection(generator, path: str, output_dir: str, prefix: str = "signatu
             records[-1]["identity_pixel_only"] = pixel_only[i]
         if similarity is not None:
             records[-1]["ssim"] = float(similarity[i])
+        if target_names is not None:
+            records[-1]["preprocessed_target"] = target_names[i]
     with open(os.path.join(output_dir, f"{prefix}_projection.json"), "w") as f:
         json.dump(records, f, indent=2)
     print(f"Reconstruction loss (mean squared error in [-1, 1]): best {float(loss.min()):.3e}, worst {float(loss.max()):.3e}")
@@ -358,17 +369,21 @@ def run_adapt(generator, path: str, output_dir: str, device: torch.device, n_sam
               steps: int = 100, lr: float = 1e-4, first_layer: int = 0, anchor_weight: float = 0.0, discriminator=None,
               realism_weight: float = 0.0, sigma: float = 0.25, save: Optional[str] = None, seed: Optional[int] = None,
               project_steps: int = 200, project_lr: float = 0.05, project_restarts: int = 1, threshold: Optional[int] = None,
-              transparent: bool = False, config: Optional[Dict[str, Any]] = None, despeckle: Optional[Despeckle] = None) -> None:
+              transparent: bool = False, config: Optional[Dict[str, Any]] = None, despeckle: Optional[Despeckle] = None,
+              preprocess: bool = False) -> None:
     """Adapt the Generator to the image file / the images of the directory ``path`` (utils.inference.adapt_generator: project
     them to pivots, then Adam on the weights of layers >= ``first_layer``), then write ``n_samples`` signatures
     ``<prefix>_%06d.png`` generated at z = pivot[i mod N] + sigma * randn (seeded by ``seed``) and ``<prefix>_adapt.json``:
     {steps, lr, first_layer, anchor_weight, realism_weight, sigma, trainable: [keys], targets: [{file, loss_before,
     loss_after}, ...]}.  ``save``: also a checkpoint {generator_state_dict, config} of the adapted weights that
-    load_generator reads back."""
+    load_generator reads back.  ``preprocess``: the files are raw scans; every target goes through load_preprocessed_targets
+    instead of the plain load, is written as ``<prefix>_target_%06d.png`` and named in its entry of ``targets`` under
+    ``preprocessed_target``, and the report says ``preprocess: true``."""
     from PIL import Image
     from .utils.inference import adapt_generator, generate_uint8
     os.makedirs(output_dir, exist_ok=True)
-    files, targets = load_target_images(path, generator.output_size)
+    files, targets = load_preprocessed_targets(path, generator.output_size) if preprocess else load_target_images(path, generator.output_size)
+    target_names = save_preprocessed_targets(targets, output_dir, prefix) if preprocess else None
     print(f"Adapting the Generator to {len(files)} signatures ({steps} steps, lr {lr:g}, layers >= {first_layer})...")
     res = adapt_generator(generator, targets, steps=steps, lr=lr, first_layer=first_layer, anchor_weight=anchor_weight,
                           discriminator=discriminator, realism_weight=realism_weight, seed=seed,
@@ -392,6 +407,10 @@ def run_adapt(generator, path: str, output_dir: str, device: torch.device, n_sam
     if despeckle is not None:
         report["despeckle"] = despeckle.report()
         print_despeckle(despeckle)
+    if target_names is not None:
+        report["preprocess"] = True
+        for entry, name in zip(report["targets"], target_names):
+            entry["preprocessed_target"] = name
     with open(os.path.join(output_dir, f"{prefix}_adapt.json"), "w") as f:
         json.dump(report, f, indent=2)
     if save:
@@ -465,6 +484,50 @@ PROJECT_SSIM_DEFAULTS = dict(project_ssim=False)
 
 def project_ssim_opt(a: argparse.Namespace) -> bool:
     return getattr(a, "project_ssim", PROJECT_SSIM_DEFAULTS["project_ssim"])
+
+
+# --adapt_preprocess / --project_preprocess, kept out of the namespace the same way
+PREPROCESS_DEFAULTS = dict(adapt_preprocess=False, project_preprocess=False)
+
+
+def preprocess_opt(a: argparse.Namespace, name: str) -> bool:
+    """A flag of PREPROCESS_DEFAULTS: its value on the command line, else its default."""
+    return getattr(a, name, PREPROCESS_DEFAULTS[name])
+
+
+def load_preprocessed_targets(path: str, image_size: int, device=None):
+    """load_target_images for raw scans: the same files in the same order, each through
+    preprocess_signatures.preprocess_single_image at the checkpoint's size (denoise, validate, crop, resize, centre, CLAHE on
+    the device) instead of the plain decode-and-resize.  A scan that preprocessing rejects raises: a target cannot be dropped
+    silently."""
+    from pathlib import Path
+    from .data_loader_signatures import SignatureDataset
+    from .preprocess_signatures import preprocess_single_image
+    p = Path(path)
+    if not p.exists():
+        raise FileNotFoundError(f"no such image file or directory: {path}")
+    ds = SignatureDataset(p if p.is_dir() else p.parent)
+    if not p.is_dir():
+        ds.image_paths = [p]
+    if len(ds) == 0:
+        raise ValueError(f"No images found in {path}")
+    names, out = [], []
+    for i in range(len(ds)):
+        f = ds.get_image_path(i)
+        arr = preprocess_single_image(f, (image_size, image_size), normalize=False, device=device)
+        if arr is None:
+            raise ValueError(f"preprocessing rejected {f}: unreadable, outside 16..1024 pixels a side, blank, or degenerate")
+        names.append(os.path.basename(str(f))); out.append(arr)
+    return names, np.stack(out)
+
+
+def save_preprocessed_targets(targets, output_dir: str, prefix: str):
+    """``<prefix>_target_%06d.png`` per preprocessed target; returns the names."""
+    from PIL import Image
+    names = [f"{prefix}_target_{i + 1:06d}.png" for i in range(len(targets))]
+    for name, t in zip(names, targets):
+        Image.fromarray(t, mode="L").save(os.path.join(output_dir, name), "PNG")
+    return names
 
 
 # the --diverse flags, kept out of the namespace the same way
@@ -575,6 +638,11 @@ def parse_args(argv=None) -> argparse.Namespace:
     p.add_argument("--project_ssim", action="store_true", **later,
                    help="With --project: record every reconstruction's structural similarity (SSIM, 11-tap Gaussian window, computed "
                         "on the device) to its target in <prefix>_projection.json (default: off)")
+    p.add_argument("--adapt_preprocess", action="store_true", **later,
+                   help="With --adapt: the files are raw scans; send each through the device preprocessing (denoise, validate, crop, "
+                        "resize, centre, CLAHE) at the checkpoint's size instead of the plain load (default: off)")
+    p.add_argument("--project_preprocess", action="store_true", **later,
+                   help="With --project: the same for the images to project (default: off)")
     p.add_argument("--pen_width", type=int, metavar="W", **later,
                    help="Redraw every generated signature at pen width W (1..9) before it is written: thinned to its centre line "
                         "and drawn again with a disc of squared radius (W - 1)^2 // 4, on the device; ink is byte < --threshold, "
@@ -657,6 +725,10 @@ def parse_args(argv=None) -> argparse.Namespace:
             p.error("--pen_width needs --threshold in 1..255")
     if hasattr(a, "project_ssim") and a.project is None:
         p.error("--project_ssim needs --project")
+    if hasattr(a, "project_preprocess") and a.project is None:
+        p.error("--project_preprocess needs --project")
+    if hasattr(a, "adapt_preprocess") and adapt_opt(a, "adapt") is None:
+        p.error("--adapt_preprocess needs --adapt")
     if hasattr(a, "despeckle"):
         if a.project is not None or a.morph is not None:
             p.error("--despeckle cleans generated signatures; projections and morph strips are left alone")
@@ -744,7 +816,8 @@ def main(argv=None) -> None:
                   adapt_opt(a, "adapt_lr"), adapt_opt(a, "adapt_first_layer"), adapt_opt(a, "adapt_anchor"),
                   need_discriminator("--adapt_realism_weight") if w_d > 0 else None, w_d,
                   0.25 * a.noise_scale if sigma is None else sigma, adapt_opt(a, "adapt_save"), a.seed, a.project_steps,
-                  a.project_lr, a.project_restarts, a.threshold, a.transparent, config, **with_despeckle(despeckle_opt(a)))
+                  a.project_lr, a.project_restarts, a.threshold, a.transparent, config, **with_despeckle(despeckle_opt(a)),
+                  **({"preprocess": True} if preprocess_opt(a, "adapt_preprocess") else {}))
         return
     if a.project is not None or a.morph is not None:
         if a.project is not None:
@@ -757,7 +830,7 @@ def main(argv=None) -> None:
             run_projection(generator, a.project, a.output_dir, a.prefix, a.project_steps, a.project_lr, a.project_restarts, a.seed,
                            discriminator, w_d, w_p, verifier, identity_opt(a, "project_identity_weight"),
                            identity_opt(a, "project_identity_score_weight"), identity_opt(a, "project_identity_resize"),
-                           project_ssim_opt(a))
+                           project_ssim_opt(a), **({"preprocess": True} if preprocess_opt(a, "project_preprocess") else {}))
         if a.morph is not None:
             run_morph(generator, a.morph, a.output_dir, device, a.prefix, a.morph_frames, a.seed, a.threshold, a.transparent,
                       a.project_steps, a.project_lr, a.project_restarts)
