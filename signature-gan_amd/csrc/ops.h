@@ -10,7 +10,7 @@ namespace siggan {
 // device-resident per-call state: nothing a captured launch needs lives in kernel arguments
 struct DevState {
     unsigned long long seed;
-    unsigned long long rng_ctr;      // bumped once per step phase
+    unsigned long long rng_ctr;      // + 1 per optimiser update, siggan_op_randn and mask-less training siggan_d_forward
     // scalars of the pending Adam apply (written by k_adam_prepare)
     float step_size;                 // lr / (1 - beta1^t)
     float bc2_sqrt;                  // sqrt(1 - beta2^t)

@@ -3,7 +3,10 @@
 // values.  The normal transform is Box-Muller on the hardware transcendental units (v_log / v_sin / v_cos / v_sqrt): the
 // latent batch is drawn inside the fc kernel by every workgroup that needs it, so a draw has to cost tens of cycles, not the
 // hundreds of the range-reduced libm routines.  Every kernel that draws goes through these functions, so the value of
-// element e of stream s at call counter c is the same whichever kernel produces it.
+// element e of stream s at call counter c is the same whichever kernel produces it (element e = word e & 3 of group e >> 2;
+// who draws which stream, element and counter: DESIGN.md 3, "Random streams"; restated in tests/rngcommon.py).
+// u01 maps a word to [2^-25, 1.0], both ends included: from x >> 8 = 2^23 on the sum below needs 25 bits and rounds to even,
+// so 0x800000 gives exactly 0.5 and 0xFFFFFF exactly 1.0 -- where log is 0 and the pair of normals +-0, not NaN.
 #pragma once
 #include <hip/hip_runtime.h>
 #include <stdint.h>

@@ -621,7 +621,8 @@ class Engine:
 
     def train_step(self, real, z_d=None, masks=None, z_g=None, lr_d=2e-4, lr_g=2e-4, beta1=0.5, beta2=0.999, eps=1e-8,
                    label_smoothing=0.9, clip=None, sync=True, next_real=None):
-        """One pipelined G+D step (n_critic = 1): same results as d_step followed by g_step.  next_real: the
+        """One pipelined G+D step (n_critic = 1): same results as d_step followed by g_step on the same latents (a drawn
+        z_g comes from the D phase's call counter here, from the G phase's -- one later -- there).  next_real: the
         following step's real batch, if the loop already has it (see stage_real)."""
         self.step_begin(real, z_d, masks, z_g, label_smoothing)
         dm = self.d_apply(lr_d, beta1, beta2, eps, clip, 1.0, sync)
