@@ -447,8 +447,9 @@ int32_t siggan_prof_slots(void);
 int siggan_prof_read(siggan_ctx *ctx, int32_t idx, char *name, int32_t name_cap, int64_t *launches,
                      double *ms, double *flops, double *bytes);
 /* test hook: *count = the launches recorded since siggan_prof_enable; for launch idx (in launch order) the first n of
- * {kernel slot, form (0 down / 1 up), epilogue asked for, epilogue run, rows per class M, Ci, Co} (gconv.h: GConvArgs,
- * enum Epilogue; -1 where a launch is no implicit GEMM).  Does not synchronise. */
+ * {kernel slot, form (0 down / 1 up), epilogue asked for, epilogue run, rows per class M, Ci, Co, K slabs (> 1: summed and
+ * finished by the split-K epilogue kernel), in-workgroup K split (1 or 2)} (gconv.h: GConvArgs, enum Epilogue; -1 where a
+ * launch is no implicit GEMM).  Does not synchronise. */
 int siggan_prof_launch(siggan_ctx *ctx, int64_t idx, int32_t *fields, int32_t n, int64_t *count);
 
 /* test hook: copy the first n elements of a library-owned workspace tensor (NHWC), converted to fp32, into out_dev:

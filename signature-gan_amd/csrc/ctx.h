@@ -20,6 +20,7 @@ using namespace siggan;
 
 static const float BN_MOMENTUM = 0.1f, BN_EPS = 1e-5f;   // nn.BatchNorm defaults (generator_vanilla_gan.py:58,126)
 static const int MAXL = 6;
+// (restated in tests/evalpaths.py, matched as text by tests/test_eval_paths_cpu.py)
 static const int64_t PARTIAL_FLOATS = (int64_t)2 << 20;   // each of the three reduction-partial regions (partial, partial_b, partial_c)
 static const float SN_EPS = 1e-12f;        // torch.nn.utils.spectral_norm's eps
 // Events that order the library's own lanes against each other on ONE device carry no system-scope fence: with the default

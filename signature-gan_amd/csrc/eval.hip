@@ -113,7 +113,7 @@ static int latent_objective_grad(siggan_ctx* c, const float* z_dev, int B, const
             if (l >= 2) { a.epi = EPI_LRELU_BWD; a.aref = c->g_a[l - 1]; a.noise = tab[l - 1]; a.slope = gs; }
             launch_gconv(a, s);
         }
-        // (the last 64 floats of `partial` are siggan_op_adam's scratch slot)
+        // (the last 64 floats of `partial` are siggan_op_adam's scratch slot; the cap is restated in tests/evalpaths.py)
         launch_fc_dz((const float*)c->g_da[0], (const float*)c->g_a[0], c->g_bne[0], GP(c, gi_fc_w()), dz_dev, c->partial,
                      PARTIAL_FLOATS - 64, B, c->latent, c->gC[0], gs, s, wp > 0.f ? z_dev : nullptr, wp / (float)c->latent);
     } else {

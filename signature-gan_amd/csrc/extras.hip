@@ -171,8 +171,8 @@ extern "C" int siggan_prof_launch(siggan_ctx* c, int64_t idx, int32_t* fields, i
     if (n <= 0) return SIGGAN_OK;
     if (idx < 0 || idx >= *count) return FAIL(SIGGAN_E_INVALID, "launch %lld of %lld", (long long)idx, (long long)*count);
     const Prof::Rec& r = g_prof_store.recs[(size_t)idx];
-    const int32_t v[7] = {r.id, r.form, r.epi_req, r.epi, r.M, r.Ci, r.Co};
-    for (int i = 0; i < n && i < 7; ++i) fields[i] = v[i];
+    const int32_t v[9] = {r.id, r.form, r.epi_req, r.epi, r.M, r.Ci, r.Co, r.slabs, r.kq};
+    for (int i = 0; i < n && i < 9; ++i) fields[i] = v[i];
     return SIGGAN_OK;
 }
 

@@ -104,14 +104,15 @@ struct Prof {
     struct Rec {
         int id; double flops, bytes; hipEvent_t e0, e1;   // algorithmic FLOPs and HBM bytes (operands read once + result written once)
         // implicit-GEMM launches (else -1): form, the epilogue the caller asked for and the one that ran (they differ where
-        // EPI_BN_BWD_STATS fell back to EPI_RAW: the stat_cap carve was too small), rows per class, Ci, Co
-        int form, epi_req, epi, M, Ci, Co;
+        // EPI_BN_BWD_STATS fell back to EPI_RAW: the stat_cap carve was too small), rows per class, Ci, Co; how K was split:
+        // slabs (> 1: that many, summed and finished by k_splitk_epilogue) and kq (2: the in-workgroup two-way split)
+        int form, epi_req, epi, M, Ci, Co, slabs, kq;
     };
     static constexpr int NID = 8;
     std::vector<Rec> recs;
     static const char* name(int id);
     void begin(int id, double flops, double bytes, hipStream_t st);
-    void shape(const GConvArgs& a, int epi_req);      // tags the last record with the GEMM it launched
+    void shape(const GConvArgs& a, int epi_req, int slabs = 1, int kq = 1);      // tags the last record with the GEMM it launched
     void clear();
 };
 extern Prof* g_prof;

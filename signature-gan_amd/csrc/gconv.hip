@@ -411,13 +411,13 @@ const char* Prof::name(int id) {
 // hipEventRecord pair would include.
 void Prof::begin(int id, double flops, double bytes, hipStream_t) {
     Rec r; r.id = id; r.flops = flops; r.bytes = bytes;
-    r.form = r.epi_req = r.epi = r.M = r.Ci = r.Co = -1;
+    r.form = r.epi_req = r.epi = r.M = r.Ci = r.Co = r.slabs = r.kq = -1;
     (void)hipEventCreate(&r.e0); (void)hipEventCreate(&r.e1);
     recs.push_back(r);
 }
-void Prof::shape(const GConvArgs& a, int epi_req) {
+void Prof::shape(const GConvArgs& a, int epi_req, int slabs, int kq) {
     Rec& r = recs.back();
-    r.form = a.form; r.epi_req = epi_req; r.epi = a.epi; r.M = a.M; r.Ci = a.Ci; r.Co = a.Co;
+    r.form = a.form; r.epi_req = epi_req; r.epi = a.epi; r.M = a.M; r.Ci = a.Ci; r.Co = a.Co; r.slabs = slabs; r.kq = kq;
 }
 void Prof::clear() {
     for (auto& r : recs) { (void)hipEventDestroy(r.e0); (void)hipEventDestroy(r.e1); }
@@ -459,7 +459,7 @@ static int launch_cfg(const GConvArgs& a_in, hipStream_t st, int id, int nsplit)
     // algorithmic FLOPs = 2 * M * Co * (taps * Ci) per class (== 2 * conv MACs, padding taps included)
     if (g_prof) {
         g_prof->begin(id, 2.0 * a.M * a.Co * (double)((a.form == 0 ? 16 : 4) * a.Ci) * ncls, gconv_bytes(a), st);
-        g_prof->shape(a, a_in.epi);
+        g_prof->shape(a, a_in.epi, nsplit, KQ);
     }
     hipEvent_t e0 = g_prof ? g_prof->recs.back().e0 : nullptr, e1 = g_prof ? g_prof->recs.back().e1 : nullptr;
     if (a.dt != DT_F32) {
@@ -491,6 +491,7 @@ int launch_gconv(const GConvArgs& a_in, hipStream_t st) {
     const int ncls = a.form == 0 ? 1 : 4;
     auto blocks = [&](int bm, int bn) { return ((a.M + bm - 1) / bm) * (a.Co / bn) * ncls; };
     const int nk = (a.form == 0 ? 16 : 4) * (a.Ci / BK);
+    // (the tile and split rules from here to the end of the function are restated in tests/evalpaths.py, matched as text by tests/test_eval_paths_cpu.py)
     auto splits = [&](int nblk) {
         int ns = 1;
         if (a.slab && nblk < 384) {

@@ -8,7 +8,7 @@
 
 namespace siggan {
 
-static constexpr int BK = 32;    // K-tile (elements)
+static constexpr int BK = 32;    // K-tile (elements; restated in tests/evalpaths.py)
 
 // XCD-aware bijective remap (8 XCDs, blocks b and b+8 share an L2): consecutive logical tiles,
 // which share an A row-panel, land on one XCD.

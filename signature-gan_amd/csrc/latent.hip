@@ -212,7 +212,8 @@ void launch_final_dgrad_eval(const float* dpre, const float* Wt, const float* a,
 // K padded to the 32-wide tile (latent 100, 50); at ~50 MFLOP the kernel is bound by launch and load latency, not by FLOPs.
 // The four waves meet in LDS (wave order), the splits of F in k_fc_dz_sum (split order).
 // =========================================================================================
-constexpr int DZ_BT = 8, DZ_SUB = 64;
+constexpr int DZ_BT = 8, DZ_SUB = 64;        // (restated in tests/evalpaths.py, matched as text by tests/test_eval_paths_cpu.py, as are nsplit's rule in launch_fc_dz and the
+                                             //  workgroup counts of launch_obj_fin_tiles / k_obj_fin_tiles)
 
 template <bool LK>
 __global__ __launch_bounds__(256) void k_fc_dz(const float* __restrict__ dh, const float* __restrict__ a0,

@@ -82,7 +82,7 @@ __global__ __launch_bounds__(256) void k_bn_eval_bwd(float* g, const float* __re
 bool launch_bn_eval_bwd(float* g, const float* y, int64_t R, int C, const float* bne, float* part, int64_t part_cap,
                         float* dgamma, float* dbeta, hipStream_t s) {
     if (C < 32 || C > 512 || (C & (C - 1)) != 0) return false;        // (the blocks' channel counts: 32 .. 256; 2 * C / 4 <= 256 threads combine)
-    int64_t rows = 512;
+    int64_t rows = 512;                                                // (restated in tests/evalpaths.py)
     while (cdiv(R, rows) * 2 * (int64_t)C > part_cap) rows *= 2;
     const int nch = cdiv(R, rows);
     hipLaunchKernelGGL(k_bn_eval_bwd, dim3((unsigned)nch), dim3(256), 0, s, g, y, R, C, (int)rows, bne, part);

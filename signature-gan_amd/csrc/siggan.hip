@@ -21,6 +21,7 @@ extern "C" int siggan_abi_version(void) { return SIGGAN_ABI_VERSION; }
 extern "C" const char* siggan_last_error(void) { return g_err; }
 
 static void build_layout(siggan_ctx* c) {
+    // (the chains, and slab_k_floats below: restated in tests/evalpaths.py, matched as text by tests/test_eval_paths_cpu.py)
     static const int g64[] = {256, 128, 64, 32, 32}, g128[] = {512, 256, 128, 64, 32, 32};
     static const int d64[] = {1, 64, 128, 256, 512}, d128[] = {1, 64, 128, 256, 512, 512};
     if (c->S == 64) { c->Lg = 4; c->Ld = 4; memcpy(c->gC, g64, sizeof g64); memcpy(c->dC, d64, sizeof d64); }

@@ -721,8 +721,9 @@ class Engine:
         return out
 
     def prof_launches(self):
-        """[{kernel, form, epi_req, epi, M, Ci, Co}] for every launch recorded since prof_enable, in launch order (test hook:
-        which GEMM ran on which tile; epilogue names as _lib.EPILOGUES, None where a launch is no implicit GEMM)."""
+        """[{kernel, form, epi_req, epi, M, Ci, Co, slabs, kq}] for every launch recorded since prof_enable, in launch order
+        (test hook: which GEMM ran on which tile and how it split K -- slabs > 1: that many, finished by k_splitk_epilogue; kq 2:
+        the in-workgroup two-way split; epilogue names as _lib.EPILOGUES, None / -1 where a launch is no implicit GEMM)."""
         names = {}
         for i in range(self.lib.siggan_prof_slots()):
             buf = C.create_string_buffer(64)
@@ -731,13 +732,13 @@ class Engine:
             names[i] = buf.value.decode()
         count = C.c_int64()
         _lib.check(self.lib.siggan_prof_launch(self._h, 0, None, 0, C.byref(count)))
-        f = (C.c_int32 * 7)()
+        f = (C.c_int32 * 9)()
         out = []
         for i in range(count.value):
-            _lib.check(self.lib.siggan_prof_launch(self._h, i, f, 7, C.byref(count)))
+            _lib.check(self.lib.siggan_prof_launch(self._h, i, f, 9, C.byref(count)))
             epi = lambda e: _lib.EPILOGUES[e] if 0 <= e < len(_lib.EPILOGUES) else None
             out.append({"kernel": names.get(f[0], "?"), "form": f[1], "epi_req": epi(f[2]), "epi": epi(f[3]), "M": f[4],
-                        "Ci": f[5], "Co": f[6]})
+                        "Ci": f[5], "Co": f[6], "slabs": f[7], "kq": f[8]})
         return out
 
     def debug_tensor(self, name, index, shape):

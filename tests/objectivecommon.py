@@ -19,6 +19,32 @@ CASES = [(64, 100, 3, 0.0, False),       # ragged GEMM rows in both networks
 # realism alone; all three (16 brings the reconstruction gradient to the realism gradient's order at 64x64, so an error in
 # either is visible); reconstruction alone
 WEIGHTS = [(0.0, 1.0, 0.0), (16.0, 1.0, 0.5), (1.0, 0.0, 0.0)]
+# The batches the callers run (project_signatures, refine_latents, edit_latents, adapt_generator work in chunks of the engine's
+# max_batch, 64 by default), each the smallest that reaches its launcher paths: (case, z seed).  What each reaches is
+# evalpaths.describe(size, latent, batch), held to the sources by test_eval_paths_cpu.py and to the library's launch profile by
+# test_eval_grad_batches_gpu.py.  The Generator's chains are 256-128-64-32-32 and 512-256-128-64-32-32 (siggan.hip).
+BATCH_CASES = [
+    # k_fc_dz's second image tile with one live row; three objective workgroups, the last a single wave; the first scale table
+    # copied by two workgroups; k_bn_eval_bwd on block 1 in two chunks, the second 64 rows; every GEMM still slab-split
+    ((64, 100, 9, 0.0, False), SEED["z"]),
+    # generic fc kernels (latent % 4 != 0), one k pass in k_fc_dz, a second tile with 5 live rows, the LeakyReLU variants; the
+    # Discriminator chain's five- and three-way slab splits
+    ((64, 50, 13, 0.2, False), SEED["z"]),
+    # the default chunk: l = 4 as unsplit k_gconv<128,32> (512 workgroups) and l = 3 as the two-quad k_gconv<64,64>, both with
+    # EPI_LRELU_BWD and the scale table in the kernel; l = 2 as a 4-slab split; the Discriminator's chain without slabs (l = 4
+    # two-quad)
+    ((64, 100, 64, 0.0, False), SEED["z"]),
+    # l = 5 as unsplit k_gconv<128,32> at exactly 384 workgroups; l = 4 as a three-way, l = 3 as a six-way slab split; k_fc_dz's
+    # second tile with 4 live rows.  (At SEED["z"], +3, +7, +8 the fp64 oracle's logits reach 6.5 .. 10.8: this z keeps them < 6)
+    ((128, 128, 12, 0.0, False), SEED["z"] + 2),
+    # l = 3 and l = 2 as unsplit one-quad k_gconv<64,64> with the table in the kernel, l = 1 two-quad; the Discriminator's l = 3
+    # as k_gconv<128,128>; 32 image tiles in k_fc_dz, 64 objective workgroups, table copies of 32 / 16 / 8 workgroups
+    ((64, 100, 256, 0.0, False), SEED["z"]),
+    # launch_fc_dz halves nsplit once B * latent exceeds 32767 at 64x64 (64 * B * latent > PARTIAL_FLOATS - 64): 64 images at
+    # latent 512 are the smallest batch of whole tiles that does -- nsplit 32, so every k_fc_dz workgroup walks TWO 64-feature
+    # chunks (the f0 loop with its barriers), in eight passes over k and eight image tiles; the GEMMs are those of B = 64
+    ((64, 512, 64, 0.0, False), SEED["z"]),
+]
 
 R_STEPS, R_LR = 20, 0.02           # the refinement loop of test_refine_gpu
 
@@ -33,11 +59,14 @@ def oracle_d_sd64(size, uv=None):
     return O.sn_weights(d64, {k: v.double().cpu() for k, v in uv.items()}, size, training=False)
 
 
-def oracle_objective(g_sd64, d_sd64, z, t64, size, signs_g=None, signs_d=None, slope=0.0, rec_g=None, rec_d=None):
+def oracle_objective(g_sd64, d_sd64, z, t64, size, signs_g=None, signs_d=None, slope=0.0, rec_g=None, rec_d=None,
+                     dtype=torch.float64):
     """The three unweighted terms (3, B), their gradients with respect to z (3, B, latent) and the logits (B,) in fp64.
     ``signs_*``: another implementation's activation decisions in the two networks (None: the run's own); ``t64`` None: no
-    reconstruction term (zeros).  The objective is linear in the terms, so one run serves every weight set."""
-    z64 = z.double().clone().requires_grad_()
+    reconstruction term (zeros).  The objective is linear in the terms, so one run serves every weight set.  ``dtype``: the
+    type z is run in -- torch.float32 with states and target cast alike is torch's own fp32 arithmetic, the yardstick for how
+    well conditioned a z is."""
+    z64 = z.to(dtype).clone().requires_grad_()
     img = O.g_forward(g_sd64, z64, False, size, signs=signs_g, record=rec_g, slope=slope)
     feat = O.d_features(d_sd64, img, size, None, signs=signs_d, record=rec_d)
     logit = F.linear(feat, d_sd64["classifier.0.weight"], d_sd64["classifier.0.bias"])[:, 0]

@@ -10,6 +10,7 @@ gain, where no prediction saturates (the test asserts |logit| < 6 on the device)
 power iterations (objectivecommon.objective_engine says why), read back from the context for the oracle."""
 import ctypes as C
 import math
+import time
 
 import numpy as np
 import pytest
@@ -24,13 +25,15 @@ pytestmark = pytest.mark.gpu
 ALL3 = WEIGHTS[1]
 
 
-def compute_case(case):
+def compute_case(case, z_seed=None, extra=None):
     """Everything the tests of one case compare, computed once and brought to the CPU (also what
-    profiles/latent_objective_parity_margins.py records)."""
+    profiles/latent_objective_parity_margins.py records).  ``z_seed``: the seed of z (default SEED["z"]; the targets are the
+    bytes of G at SEED["z"] + 1 either way).  ``extra(eng, out, zc, t_u8)``: further calls on the same engine, after the ones
+    here, adding to ``out`` (test_eval_grad_batches_gpu.py)."""
     from hipcommon import hip_signs_g
     size, latent, batch, slope, sn = case
     eng = objective_engine(size, latent, batch, slope, sn)
-    z = torch.from_numpy(I.gen_z(batch, latent, SEED["z"]))
+    z = torch.from_numpy(I.gen_z(batch, latent, SEED["z"] if z_seed is None else z_seed))
     zc = z.cuda()
     t_u8 = eng.g_generate_u8(torch.from_numpy(I.gen_z(batch, latent, SEED["z"] + 1)).cuda())
     t_f32 = lut_f32(t_u8)
@@ -50,11 +53,15 @@ def compute_case(case):
     after = frozen()
     out["frozen"] = [(k, torch.equal(before[k], after[k])) for k in before]
     out["d_forward"] = eng.d_forward(out[ALL3][4].cuda(), training=False).cpu().reshape(-1)
+    if extra is not None:
+        extra(eng, out, zc, t_u8)
     eng.close()
     rec_g, rec_d = [], []
+    t0 = time.perf_counter()
     out["terms_ref"], out["grads_ref"], out["logit_ref"] = oracle_objective(
         oracle_sd64(size, latent, GAIN[size]), oracle_d_sd64(size, uv), z, out["t64"], size, out["signs_g"], out["signs_d"], slope,
         rec_g, rec_d)
+    out["oracle_seconds"] = time.perf_counter() - t0
     out["rec_g"], out["rec_d"] = rec_g, rec_d
     return out
 

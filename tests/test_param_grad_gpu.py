@@ -7,7 +7,8 @@ max|d - ref| <= 1e-4 * max|ref| -- the project's gradient bound, applied per ten
 against fp64 on shared decisions and targets deviates at most 3.9e-6 of a tensor's max over these cases, and no tensor's max|ref|
 is below 3e-4, so the bound is neither vacuous nor within rounding).  Cases, final-conv gain and targets: those of
 test_latent_grad_gpu / test_latent_objective_gpu -- the smallest shapes that reach ragged GEMM rows, one sample, five blocks, the
-generic fc path and LeakyReLU -- plus the spectral-norm Discriminator for the realism term alone."""
+generic fc path and LeakyReLU -- plus the spectral-norm Discriminator for the realism term alone, plus the batches adapt_generator
+runs, 9 and 64 images (PARAM_BATCH_CASES; worst tensor there 7.5e-6 and 5.5e-6, no tensor's max|ref| below 1.5e-3)."""
 import ctypes as C
 import math
 
@@ -18,7 +19,7 @@ import torch
 from adaptcommon import BOUND, PARAM_WEIGHTS, combine, n_blocks, oracle_param_grads, param_keys, split_arena, tensor_margins
 from common import I, SEED
 from latentcommon import oracle_sd64
-from objectivecommon import CASES, GAIN, hip_signs_d_rows, lut_f32, objective_engine, oracle_d_sd64
+from objectivecommon import BATCH_CASES, CASES, GAIN, hip_signs_d_rows, lut_f32, objective_engine, oracle_d_sd64
 
 pytestmark = pytest.mark.gpu
 BOTH = PARAM_WEIGHTS[2]
@@ -103,7 +104,16 @@ def check_bound(run):
     return worst
 
 
-@pytest.fixture(scope="module", params=CASES, ids=lambda c: f"s{c[0]}-z{c[1]}-b{c[2]}-slope{c[3]:g}{'-sn' if c[4] else ''}")
+# ... and the batches adapt_generator runs (chunks of max_batch, 64 by default): 9 images -- k_bn_eval_bwd on block 1 in two
+# chunks, the second 64 rows, every input-gradient GEMM still slab-split with other counts than at 3 -- and 64, where the
+# table-free EPI_LRELU_BWD runs inside k_gconv<128,32> (l = 4, 512 workgroups) and the two-quad k_gconv<64,64> (l = 3), and
+# k_part_sum's lanes add up to 16 chunks each (512 chunks in block 4).  evalpaths restates the launchers; the GEMMs are pinned
+# through the profile by test_the_batch_cases_make_their_launches.
+PARAM_BATCH_CASES = [c for c, _ in BATCH_CASES if c[:3] in ((64, 100, 9), (64, 100, 64))]
+
+
+@pytest.fixture(scope="module", params=CASES + PARAM_BATCH_CASES,
+                ids=lambda c: f"s{c[0]}-z{c[1]}-b{c[2]}-slope{c[3]:g}{'-sn' if c[4] else ''}")
 def run(request):
     return compute_case(request.param)
 
@@ -225,6 +235,30 @@ def test_first_layer_freezes_a_prefix_and_shortens_the_chain():
     assert len(eng.prof_launches()) == expected_gemms(size, 0, True)
     eng.prof_enable(False)
     eng.close()
+
+
+@pytest.mark.parametrize("case", PARAM_BATCH_CASES, ids=lambda c: f"b{c[2]}")
+def test_the_batch_cases_make_their_launches(case):
+    """One g_param_grad with both weights on an engine of its own makes the input-gradient GEMMs evalpaths restates for the
+    batch -- tile, rows, channels, slab count, in-workgroup split; test_eval_paths_cpu.py writes them out per case -- in both
+    chains, and as many GEMM and weight-gradient launches as expected_gemms counts."""
+    import evalpaths
+    size, latent, batch, slope, sn = case
+    eng = objective_engine(size, latent, batch, slope, sn)
+    zc = torch.from_numpy(I.gen_z(batch, latent, SEED["z"])).cuda()
+    t_u8 = eng.g_generate_u8(torch.from_numpy(I.gen_z(batch, latent, SEED["z"] + 1)).cuda())
+    eng.prof_enable(True)
+    try:
+        eng.g_param_grad(zc, t_u8, *BOTH)
+        torch.cuda.synchronize()
+        launches = eng.prof_launches()
+    finally:
+        eng.prof_enable(False)
+        eng.close()
+    keys = ("kernel", "form", "epi", "M", "Ci", "Co", "slabs", "kq")
+    for want in evalpaths.g_chain(size, batch) + evalpaths.d_chain(size, batch):
+        assert [l for l in launches if all(l[k] == want[k] for k in keys)], (want, [{k: l[k] for k in keys} for l in launches if l["M"] >= 0])
+    assert len(launches) == expected_gemms(size, 0, True)
 
 
 @pytest.mark.parametrize("graph", [False, True], ids=["eager", "graph"])
