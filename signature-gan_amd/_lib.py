@@ -1,5 +1,5 @@
 """ctypes binding of the C ABI in include/siggan.h and the siggan_*.h headers beside it: one table of signatures per header,
-all of them in ``GROUPS`` or, for headers added after siggan_dtw.h, in ``EXTRA_GROUPS``.
+all of them in ``GROUPS`` or, for headers added after siggan_dtw.h, in ``EXTRA_GROUPS`` / ``ADDED_GROUPS``.
 
 The shared library is built in-tree by ``__graft_entry__.build()`` / ``csrc/Makefile`` and must be
 present: there is no CPU or PyTorch fallback for this path -- a missing or stale library raises.
@@ -352,6 +352,12 @@ _PREPROCESS_SIGNATURES = {
     "siggan_preprocess_u8": (C.c_int, [_I32, _P, _I64, _P, _P, _I32, C.POINTER(PreprocessOptions), _P, _P, _P, _P, _P, C.c_size_t, _P]),
 }
 
+# the signature duplicator: smooth random warps of byte images (include/siggan_warp.h): context-free, one more symbol
+WARP_MAX_SIZE, WARP_PARAMS, WARP_MAX_N, WARP_CELLS, WARP_STREAM, WARP_MAX_CTRL = 128, 12, 1 << 20, (8, 16, 32), 0x57415250, 8192
+_WARP_SIGNATURES = {
+    "siggan_warp_u8": (C.c_int, [_I32, _P, _I64, _P, _P, _P, _P, _P, _I32, _I32, _I32, _I32, _I32, C.c_uint64, _P]),
+}
+
 # every table up to siggan_dtw.h, in the order the symbols joined the ABI: load() binds them, build() checks the library
 # exports them.  GROUPS and ALL_EXPORTS stop there: tests/test_call_cpu.py pins both, their last symbol and every name
 # ending in EXPORTS, and existing tests do not change.  A new header therefore adds its table to EXTRA_GROUPS below and
@@ -364,6 +370,11 @@ ALL_EXPORTS = tuple(name for group in GROUPS for name in group)
 # the tables of headers added since: load() binds them after GROUPS, build() checks the library exports them as well
 EXTRA_GROUPS = (_PREPROCESS_SIGNATURES,)
 EXTRA_SYMBOLS = tuple(name for group in EXTRA_GROUPS for name in group)
+# tests/test_preprocess_cpu.py pins EXTRA_GROUPS and EXTRA_SYMBOLS whole as they stood with siggan_preprocess.h, so they stop
+# there too.  Headers added after it list their tables here; load() and build() walk this tuple as they walk the two above.
+# A test of a new header checks that its own table is IN this tuple, never the tuple's whole value, so it can keep growing.
+ADDED_GROUPS = (_WARP_SIGNATURES,)
+ADDED_SYMBOLS = tuple(name for group in ADDED_GROUPS for name in group)
 
 _lib = None
 
@@ -378,7 +389,7 @@ def load():
             f"{LIB_PATH} is missing: build it with `python -c 'import __graft_entry__ as g; g.build()'` "
             "(or `make -C signature-gan_amd/csrc`). This path has no CPU/PyTorch fallback.")
     lib = C.CDLL(LIB_PATH)
-    for group in GROUPS + EXTRA_GROUPS:
+    for group in GROUPS + EXTRA_GROUPS + ADDED_GROUPS:
         for name, (res, args) in group.items():
             fn = getattr(lib, name)      # AttributeError if the library does not export the symbol
             fn.restype, fn.argtypes = res, args

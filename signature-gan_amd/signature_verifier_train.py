@@ -18,7 +18,10 @@ HBM-resident uint8 cache and every batch is gathered and augmented by one HIP la
 
 Beyond the reference, and off by default: ``hard_mining`` (``--hard_mining K``, device pipeline only) adds to every epoch from
 ``hard_mining_start`` on the pairs the current weights get most wrong -- per signature its K highest-scoring impostors and its
-lowest-scoring genuine partners, taken from one all-pairs pass in HIP (``verifier_mining``).
+lowest-scoring genuine partners, taken from one all-pairs pass in HIP (``verifier_mining``).  ``elastic`` (``--elastic PX``, device
+pipeline only) sends every augmented training batch through one more HIP launch, the smooth random warp of ``warp.warp_u8`` with
+control displacements of up to PX pixels: genuine-looking variation the rigid RandomAffine cannot give.  Whether it improves
+accuracy is not measured.
 """
 import argparse
 import ctypes as C
@@ -428,8 +431,25 @@ def check_hard_mining(input_pipeline, hard_mining, hard_mining_genuine=None, har
     return k_imp, k_gen, start, every
 
 
+ELASTIC_FLAGS = ("elastic", "elastic_cell")
+
+
+def check_elastic(input_pipeline, elastic, elastic_cell=None):
+    """None when the elastic warp is off, else the checked warp.WarpSpec: amplitude ``elastic`` pixels on both axes, control
+    cell ``elastic_cell`` (default 16), no affine part (RandomAffine has run already)."""
+    if elastic is None:
+        if elastic_cell is not None:
+            raise ValueError("elastic_cell needs elastic")
+        return None
+    if input_pipeline != "device":
+        raise ValueError("the elastic warp needs --input_pipeline device (it runs on the device loader's batches); "
+                         f"got input_pipeline={input_pipeline!r}")
+    from .warp import WarpSpec
+    return WarpSpec(cell=16 if elastic_cell is None else elastic_cell, amplitude=(elastic, elastic)).check()
+
+
 def _fit(tag: str, dataset, epochs, output_path, file_name, batch_size, learning_rate, embedding_dim, device, extra,
-         input_pipeline: str = "host", mining=None):
+         input_pipeline: str = "host", mining=None, elastic=None):
     train_size = int(0.8 * len(dataset))
     val_size = len(dataset) - train_size
     train_dataset, val_dataset = torch.utils.data.random_split(dataset, [train_size, val_size])
@@ -438,9 +458,9 @@ def _fit(tag: str, dataset, epochs, output_path, file_name, batch_size, learning
         if mining is not None:
             from .verifier_mining import MiningPairLoader
             train_loader = MiningPairLoader(train_dataset, batch_size, shuffle=True, augment=True, k_impostor=mining[0],
-                                            k_genuine=mining[1], exclude_dataset=val_dataset, device=device)
+                                            k_genuine=mining[1], exclude_dataset=val_dataset, device=device, elastic=elastic)
         else:
-            train_loader = DevicePairLoader(train_dataset, batch_size, shuffle=True, augment=True, device=device)
+            train_loader = DevicePairLoader(train_dataset, batch_size, shuffle=True, augment=True, device=device, elastic=elastic)
         val_loader = DevicePairLoader(val_dataset, batch_size, shuffle=False, augment=False, device=device)
     else:
         train_loader = DataLoader(train_dataset, batch_size=batch_size, shuffle=True, num_workers=0)
@@ -478,17 +498,21 @@ def checkpoint_dict(model, embedding_dim, val_accuracy, epoch, **extra):
 def train_model(data_dir: str, synthetic_dir: Optional[str], epochs: int, model_output: str, batch_size: int = 32,
                 learning_rate: float = 0.001, embedding_dim: int = 128, device: Optional[str] = None,
                 input_pipeline: str = "host", hard_mining: Optional[int] = None, hard_mining_genuine: Optional[int] = None,
-                hard_mining_start: int = 2, hard_mining_every: int = 1) -> Dict[str, str]:
+                hard_mining_start: int = 2, hard_mining_every: int = 1, elastic: Optional[float] = None,
+                elastic_cell: Optional[int] = None) -> Dict[str, str]:
     """Trains the baseline model (real signatures) and, with a synthetic directory, the augmented one (real + synthetic);
     returns the paths of the saved best-validation checkpoints.  input_pipeline: "host" (the reference's DataLoader over
     Pillow decodes) or "device" (HBM-resident cache + one augmentation launch per batch; module docstring).
     hard_mining: K (1 .. 16) turns hard-pair mining on (device pipeline only): from epoch ``hard_mining_start`` (1-based) on,
     every ``hard_mining_every`` epochs, each real signature's K highest-scoring impostors and ``hard_mining_genuine`` (default K)
     lowest-scoring genuine partners under the current weights join the epoch's pairs; the validation split's pairs are never
-    mined."""
+    mined.
+    elastic: PX turns the elastic warp of the training batches on (device pipeline only): control displacements of up to PX
+    pixels per axis (at most 0.4 * ``elastic_cell``; cell 8, 16 or 32, default 16) after the reference's augmentation."""
     if input_pipeline not in INPUT_PIPELINES:
         raise ValueError(f"input_pipeline must be one of {INPUT_PIPELINES}, got {input_pipeline!r}")
     mining = check_hard_mining(input_pipeline, hard_mining, hard_mining_genuine, hard_mining_start, hard_mining_every)
+    elastic = check_elastic(input_pipeline, elastic, elastic_cell)
     if device is None:
         device = 'cuda' if torch.cuda.is_available() else 'cpu'
     device = torch.device(device)
@@ -509,7 +533,7 @@ def train_model(data_dir: str, synthetic_dir: Optional[str], epochs: int, model_
         print("Please ensure data directory contains signature images organized by user.")
     else:
         baseline_path = _fit("baseline", baseline_dataset, epochs, output_path, 'baseline_siamese_model.pth', batch_size,
-                             learning_rate, embedding_dim, device, {}, input_pipeline, mining)
+                             learning_rate, embedding_dim, device, {}, input_pipeline, mining, elastic)
         saved_models['baseline'] = str(baseline_path)
         print(f"\nBaseline model saved to: {baseline_path}")
 
@@ -523,7 +547,7 @@ def train_model(data_dir: str, synthetic_dir: Optional[str], epochs: int, model_
             print("WARNING: No training pairs generated for augmented model.")
         else:
             augmented_path = _fit("augmented", augmented_dataset, epochs, output_path, 'augmented_siamese_model.pth', batch_size,
-                                  learning_rate, embedding_dim, device, {'includes_synthetic': True}, input_pipeline, mining)
+                                  learning_rate, embedding_dim, device, {'includes_synthetic': True}, input_pipeline, mining, elastic)
             saved_models['augmented'] = str(augmented_path)
             print(f"\nAugmented model saved to: {augmented_path}")
     else:
@@ -556,8 +580,12 @@ def main(argv=None):
     parser.add_argument('--hard_mining_start', metavar='E', **later,
                         help='With --hard_mining: first epoch, 1-based, that trains on mined pairs (default: 2)')
     parser.add_argument('--hard_mining_every', metavar='N', **later, help='With --hard_mining: mine again every N epochs (default: 1)')
+    parser.add_argument('--elastic', metavar='PX', type=float, default=argparse.SUPPRESS,
+                        help='Elastic warp of the training batches (needs --input_pipeline device): smooth random control '
+                             'displacements of up to PX pixels per axis, at most 0.4 cells (default: off)')
+    parser.add_argument('--elastic_cell', metavar='C', **later, help='With --elastic: pixels between control points, 8, 16 or 32 (default: 16)')
     args = parser.parse_args(argv)
-    mining = {k: getattr(args, k) for k in MINING_FLAGS if hasattr(args, k)}
+    mining = {k: getattr(args, k) for k in MINING_FLAGS + ELASTIC_FLAGS if hasattr(args, k)}
 
     print("="*60)
     print("Signature Verification Model Training")

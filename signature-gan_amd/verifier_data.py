@@ -23,13 +23,15 @@ loader (data_loader_signatures.py).
 There is no CPU fallback: the loader needs a ROCm device and the HIP library.  The planning functions are pure CPU.
 """
 import math
-from typing import List, Tuple, Union
+import dataclasses
+from typing import List, Optional, Tuple, Union
 
 import numpy as np
 import torch
 from torch.utils.data import Subset
 
 from .data_loader_signatures import _scale_tables, _uniform_many
+from .warp import WarpSpec, warp_u8
 
 SIZE = 64                                   # the verifier's only image size
 FILL = 0                                    # RandomAffine's default fill: corners turn black, as in the reference
@@ -127,10 +129,17 @@ def _pairs_of(ds):
 class DevicePairLoader:
     """Iterable over (x1, x2, labels) batches in HBM -- x1 / x2 uint8 (B, 64, 64) views of one (2B, 64, 64) tensor, labels fp32
     (B,) -- for ``train_epoch`` / ``evaluate``; ``len``, ``.dataset`` and ``.batch_size`` as torch's DataLoader.
-    ``pairs_dataset`` is a SignaturePairDataset or a torch.utils.data.Subset of one (what random_split returns)."""
+    ``pairs_dataset`` is a SignaturePairDataset or a torch.utils.data.Subset of one (what random_split returns).
+
+    ``elastic``: a ``warp.WarpSpec`` (None: off, and the loader is what it was without it).  With ``augment``, every batch's
+    2m augmented rows then go through one more launch, the smooth random warp of ``warp.warp_u8`` with the loader's FILL,
+    into a second buffer.  A row's draw id is epoch * 2^32 + its running number in the epoch (rows in batch order, a
+    batch's m first images before its m second ones); the epoch is a count of ``iter()`` calls the loader keeps, from 0;
+    ``elastic_seed`` is the warp's seed.  torch's generator is not consumed."""
 
     def __init__(self, pairs_dataset, batch_size: int, shuffle: bool, augment: bool,
-                 device: Union[str, torch.device, None] = None, drop_last: bool = False):
+                 device: Union[str, torch.device, None] = None, drop_last: bool = False, elastic: Optional[WarpSpec] = None,
+                 elastic_seed: int = 0):
         from . import _lib
         from .signature_verifier_eval import load_uint8
         self.lib = _lib.load()                               # raises if the HIP library is missing
@@ -142,6 +151,11 @@ class DevicePairLoader:
             dev = torch.device("cuda", torch.cuda.current_device())
         if batch_size < 1:
             raise ValueError(f"batch_size must be positive, got {batch_size}")
+        if elastic is not None:
+            if not isinstance(elastic, WarpSpec):
+                raise ValueError(f"elastic must be a WarpSpec, got {type(elastic).__name__}")
+            elastic = dataclasses.replace(elastic.check(), fill=FILL)
+        self.elastic, self.elastic_seed, self.epoch = elastic, int(elastic_seed), 0
         self.device, self.dataset = dev, pairs_dataset
         self.batch_size, self.shuffle, self.augment, self.drop_last = int(batch_size), bool(shuffle), bool(augment), bool(drop_last)
         pairs = _pairs_of(pairs_dataset)
@@ -171,6 +185,7 @@ class DevicePairLoader:
 
     def __iter__(self):
         dev = self.device
+        epoch, self.epoch = self.epoch, self.epoch + 1
         slots, labels = self._epoch_pairs()
         batches, draws = plan_pair_epoch(len(labels), self.batch_size, self.shuffle, self.drop_last, self.augment)
         if not batches:
@@ -194,4 +209,6 @@ class DevicePairLoader:
                 prm_dev.data_ptr() + 32 * o if prm_dev is not None else None,
                 tab_dev.data_ptr() + 4 * SIZE * o if tab_dev is not None else None,
                 out.data_ptr(), 2 * m, SIZE, FILL, stream))
+            if self.elastic is not None and self.augment:
+                out = warp_u8(out, self.elastic, self.elastic_seed, draw_ids=[(epoch << 32) + o + r for r in range(2 * m)])
             yield out[:m], out[m:], labels_dev[int(s):int(e)]

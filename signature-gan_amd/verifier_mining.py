@@ -94,13 +94,15 @@ def mine_hard_pairs(model, cache_u8: torch.Tensor, ids: torch.Tensor, anchor_ok,
 class MiningPairLoader(DevicePairLoader):
     """A DevicePairLoader whose cache holds every file of the signature table (``signature_table`` order) and whose epochs run
     over the dataset's pairs followed by the pairs ``remine`` found last -- planned, augmented and gathered by the same path.
-    ``exclude_dataset``: a pair dataset (the validation split) whose pairs are never mined."""
+    ``exclude_dataset``: a pair dataset (the validation split) whose pairs are never mined; ``elastic`` / ``elastic_seed``: as
+    for DevicePairLoader."""
 
     def __init__(self, pairs_dataset, batch_size: int, shuffle: bool, augment: bool, k_impostor: int, k_genuine: int = None,
-                 exclude_dataset=None, device=None, drop_last: bool = False):
+                 exclude_dataset=None, device=None, drop_last: bool = False, elastic=None, elastic_seed: int = 0):
         self.files, ids, synthetic = signature_table(pairs_dataset)
         self._row = {p: r for r, p in enumerate(self.files)}
-        super().__init__(pairs_dataset, batch_size, shuffle, augment, device=device, drop_last=drop_last)
+        super().__init__(pairs_dataset, batch_size, shuffle, augment, device=device, drop_last=drop_last, elastic=elastic,
+                         elastic_seed=elastic_seed)
         self.k_impostor = int(k_impostor)
         self.k_genuine = self.k_impostor if k_genuine is None else int(k_genuine)
         self.ids = torch.from_numpy(ids).to(self.device)
