@@ -358,6 +358,17 @@ _WARP_SIGNATURES = {
     "siggan_warp_u8": (C.c_int, [_I32, _P, _I64, _P, _P, _P, _P, _P, _I32, _I32, _I32, _I32, _I32, C.c_uint64, _P]),
 }
 
+# k-means++ seeding and Lloyd passes on feature rows (include/siggan_kmeans.h): context-free, new symbols again.  The tuple
+# of names is KMEANS_SYMBOLS, not ..._EXPORTS: tests/test_call_cpu.py counts every name ending in EXPORTS against GROUPS.
+KMEANS_MAX_N, KMEANS_MAX_DIM, KMEANS_MAX_K, KMEANS_MAX_ITERATIONS, KMEANS_STREAM = 65536, 1024, 256, 1000, 0x4B4D5050
+KMEANS_SUM_BLOCK, KMEANS_FEATURE_SLAB = 64, 256
+_KMEANS_SIGNATURES = {
+    "siggan_kmeans_workspace": (C.c_size_t, [_I32, _I32, _I32]),
+    "siggan_kmeans_seed": (C.c_int, [_I32, _P, _I32, _I32, _I32, C.c_uint64, _P, _P, _P, C.c_size_t, _P]),
+    "siggan_kmeans_lloyd": (C.c_int, [_I32, _P, _I32, _I32, _P, _I32, _I32, _P, _P, _P, _P, _P, _P, C.c_size_t, _P]),
+}
+KMEANS_SYMBOLS = tuple(_KMEANS_SIGNATURES)
+
 # every table up to siggan_dtw.h, in the order the symbols joined the ABI: load() binds them, build() checks the library
 # exports them.  GROUPS and ALL_EXPORTS stop there: tests/test_call_cpu.py pins both, their last symbol and every name
 # ending in EXPORTS, and existing tests do not change.  A new header therefore adds its table to EXTRA_GROUPS below and
@@ -373,7 +384,7 @@ EXTRA_SYMBOLS = tuple(name for group in EXTRA_GROUPS for name in group)
 # tests/test_preprocess_cpu.py pins EXTRA_GROUPS and EXTRA_SYMBOLS whole as they stood with siggan_preprocess.h, so they stop
 # there too.  Headers added after it list their tables here; load() and build() walk this tuple as they walk the two above.
 # A test of a new header checks that its own table is IN this tuple, never the tuple's whole value, so it can keep growing.
-ADDED_GROUPS = (_WARP_SIGNATURES,)
+ADDED_GROUPS = (_WARP_SIGNATURES, _KMEANS_SIGNATURES)
 ADDED_SYMBOLS = tuple(name for group in ADDED_GROUPS for name in group)
 
 _lib = None

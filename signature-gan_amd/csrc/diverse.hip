@@ -18,6 +18,7 @@
 
 #include "../../include/siggan_diverse.h"
 #include "host.h"
+#include "row_d2.h"
 
 namespace {
 
@@ -132,13 +133,7 @@ __global__ __launch_bounds__(256) void k_diverse_pick(const float* __restrict__ 
         const int i = base + j;                                           // wave-uniform
         if (i >= n) break;
         const float* xi = x + (size_t)i * dim;
-        double acc = 0.0;
-        for (int k = lane; k < dim; k += 64) {
-            const double d = (double)xi[k] - (double)xp[k];
-            acc = acc + d * d;
-        }
-#pragma unroll
-        for (int o = 32; o; o >>= 1) acc = acc + __shfl_xor(acc, o);      // a + b == b + a: every lane holds the same bits
+        const double acc = wave_row_d2(xi, xp, dim, lane);                // row_d2.h: every lane holds the same bits
         double mi = m[i];
         mi = acc < mi ? acc : mi;
         const bool gone = i == p || taken[i] != 0;

@@ -452,6 +452,41 @@ def _verifier_two_sample(metrics: Dict[str, Any], fake_images, real_embeddings: 
         metrics["verifier_two_sample"], metrics["verifier_two_sample_error"] = None, str(e)
 
 
+MODES_SEED = 0           # like TWO_SAMPLE_SEED: the split, the seeding and so the bins of --modes do not move with --seed
+
+
+def _mode_coverage(metrics: Dict[str, Any], fake_images, real_embeddings: Optional[torch.Tensor],
+                   verifier: Optional[VerifierFeatures], request: Dict[str, Any]) -> None:
+    """The key ``--modes`` adds, ``mode_coverage`` = utils.modes.mode_coverage's dictionary plus feature_space and feature_dim.
+    ``request``: {k (None: utils.modes.default_k), generated, real (the SsimSinks that kept the bytes; unused with a verifier)}.
+    With a verifier the rows are the embeddings both sinks kept ('verifier'), else utils.modes.pixel_features of the bytes
+    ('pixels/4').  Any failure is recorded as ``mode_coverage_error`` and the key is None."""
+    from .utils.modes import mode_coverage, pixel_features
+    print("Computing mode coverage (k-means bins, NDB and JS divergence)...")
+    try:
+        if verifier is not None:
+            if verifier.error:
+                raise ValueError(verifier.error)
+            fake, real, space = getattr(fake_images, "embeddings", None), real_embeddings, "verifier"
+            if fake is None:
+                raise ValueError("the generated samples were not embedded")
+            if real is None:
+                raise ValueError(metrics.get("verifier_frechet_error") or "no real images provided")
+        else:
+            real_u8 = request["real"].images()
+            if real_u8 is None:
+                raise ValueError("no real images provided")
+            fake, real, space = pixel_features(request["generated"].images()), pixel_features(real_u8), "pixels/4"
+        m = mode_coverage(real, fake, k=request["k"], seed=MODES_SEED)
+        m["feature_space"], m["feature_dim"] = space, int(real.shape[1])
+        metrics["mode_coverage"] = m
+        print(f"  NDB / K: {m['generated_vs_real']['ndb_over_k']:.4f} over {m['k']} bins ({space}), JS divergence: "
+              f"{m['generated_vs_real']['js_divergence']:.4f}")
+    except Exception as e:                                      # noqa: BLE001 -- the report records any failure
+        print(f"  Skipping mode coverage: {e}")
+        metrics["mode_coverage"], metrics["mode_coverage_error"] = None, str(e)
+
+
 def compute_metrics(fake_images, real_images: Optional[torch.Tensor], device: torch.device,
                     verifier: Optional[VerifierFeatures] = None, neighbors_k: Optional[int] = None,
                     verifier_real: Optional[torch.Tensor] = None, fragmentation: Optional[Dict[str, Any]] = None,
@@ -459,7 +494,8 @@ def compute_metrics(fake_images, real_images: Optional[torch.Tensor], device: to
                     stroke_geometry: Optional[Dict[str, Any]] = None,
                     shape_attributes: Optional[Dict[str, Any]] = None,
                     kid_permutations: Optional[int] = None,
-                    elastic_similarity: Optional[Dict[str, Any]] = None) -> Dict[str, Any]:
+                    elastic_similarity: Optional[Dict[str, Any]] = None,
+                    modes: Optional[Dict[str, Any]] = None) -> Dict[str, Any]:
     """The report's ``metrics`` dictionary.  ``fake_images``: a GeneratedSamples (its counters are used) or a tensor.
     ``verifier``: add the Frechet distance over its embeddings (the ``verifier_*`` keys; none without it).
     ``verifier_real``: the real set as the verifier is to see it when that is not ``real_images`` (a 128x128 Generator: the
@@ -470,7 +506,7 @@ def compute_metrics(fake_images, real_images: Optional[torch.Tensor], device: to
     likewise the finished ``stroke_geometry`` block (stroke_geometry_block); ``shape_attributes``: likewise the finished
     ``shape_attributes`` block (shape_attributes_block).  ``kid_permutations``: add ``verifier_two_sample``, the KID and
     the MMD permutation test with that many permutations.  ``elastic_similarity``: the finished ``elastic_similarity`` block
-    (elastic_similarity_block), added as it is; no key without it."""
+    (elastic_similarity_block), added as it is; no key without it.  ``modes``: add ``mode_coverage`` (_mode_coverage's request)."""
     metrics: Dict[str, Any] = {"n_samples": len(fake_images), "image_shape": list(fake_images.shape[1:]),
                                "metrics_computed_at": datetime.now().isoformat()}
     if real_images is not None and INCEPTION_AVAILABLE:
@@ -508,6 +544,8 @@ def compute_metrics(fake_images, real_images: Optional[torch.Tensor], device: to
         _verifier_neighbors(metrics, fake_images, real_embeddings, verifier, neighbors_k)
     if kid_permutations is not None:
         _verifier_two_sample(metrics, fake_images, real_embeddings, verifier, kid_permutations)
+    if modes is not None:
+        _mode_coverage(metrics, fake_images, real_embeddings, verifier, modes)
 
     print("Computing stroke density distribution...")
     try:
@@ -707,6 +745,20 @@ def print_summary(metrics: Dict[str, Any]) -> None:
                   f"better; full sets {k['kid_full']:.6f})")
             print(f"Verifier MMD^2 ({t['kind']}, gamma {t['gamma']:.4g}): {t['mmd2']:.6f}, p = {t['p_value']:.4f} over "
                   f"{t['permutations']} permutations (null 95% quantile {t['null_q95']:.6f}; small p = the sets can be told apart)")
+    if "mode_coverage" in metrics:
+        mc = metrics["mode_coverage"]
+        if mc is None:
+            why = metrics.get("mode_coverage_error", "unknown reason")
+            print(f"Mode coverage (NDB): Not computed - {why}")
+            print(f"Missing modes: Not computed - {why}")
+        else:
+            g, floor = mc["generated_vs_real"], mc["real_holdout_vs_real"]
+            print(f"Mode coverage (NDB): {g['ndb']} of {mc['k']} bins differ, NDB / K {g['ndb_over_k']:.4f}, JS divergence "
+                  f"{g['js_divergence']:.4f} ({mc['feature_space']}; real hold-out floor: "
+                  + (f"NDB / K {floor['ndb_over_k']:.4f}, JS {floor['js_divergence']:.4f}" if floor is not None
+                     else f"none - {mc['real_holdout_reason']}") + "; lower is better)")
+            print(f"Missing modes: {len(g['missing_bins'])} bins hold no generated sample; most under-represented: "
+                  + (", ".join(f"bin {e['bin']} (nearest real row {e['real_row']})" for e in mc["under_represented_examples"]) or "none"))
     print("\n--- Stroke Analysis ---")
     stroke = metrics.get("stroke_density")
     if stroke:
@@ -767,6 +819,7 @@ class _Args(argparse.Namespace):
     strokes = False
     shape = False
     dtw = None
+    modes = None
 
 
 def parse_args(argv=None) -> argparse.Namespace:
@@ -812,7 +865,18 @@ def parse_args(argv=None) -> argparse.Namespace:
                         "set (and of the real set) as a diversity measure, and every generated image's lowest distance to a real one "
                         "against the real set's own leave-one-out values; tolerates shifts of up to BAND columns (BAND omitted: "
                         "max(1, width // 8)); computed on the device, needs no network weights")
+    p.add_argument("--modes", nargs="?", type=lambda v: v if v == "auto" else int(v), const="auto", default=argparse.SUPPRESS, metavar="K",
+                   help="With --real_dir: add a 'mode_coverage' block to the report: k-means bins of half the real set, computed on "
+                        "the device, the number of statistically different bins (NDB) and the Jensen-Shannon divergence between the "
+                        "real and the generated bin histograms, the real set's own hold-out floor, and the bins the Generator "
+                        "produces too rarely or not at all.  Over the verifier's embeddings with --verifier_checkpoint, else over "
+                        "4 x 4 box means of the pixels, which needs no network weights (K omitted: about 20 real images per bin, "
+                        "between 2 and 100)")
     a = p.parse_args(argv, namespace=_Args())
+    if a.modes is not None and a.modes != "auto" and not 2 <= a.modes <= 256:
+        p.error("--modes K must be in [2, 256]")
+    if a.modes is not None and not a.real_dir:
+        p.error("--modes needs --real_dir")
     if a.dtw is not None and a.dtw != "auto" and a.dtw < 0:
         p.error("--dtw BAND must be >= 0")
     if a.verifier_kid is not None and a.verifier_kid < 1:
@@ -835,13 +899,14 @@ def main(argv=None) -> int:
     try:
         generator, config = load_generator_from_checkpoint(checkpoint_path, device)
         verifier = (VerifierFeatures(Path(a.verifier_checkpoint), device, generator.output_size, a.verifier_neighbors,
-                                     keep_embeddings=a.verifier_kid is not None)
+                                     keep_embeddings=a.verifier_kid is not None or a.modes is not None)
                     if a.verifier_checkpoint else None)
         frag_fake = frag_real = None
         if a.components is not None:
             min_area = None if a.components == "auto" else a.components
             frag_fake, frag_real = ComponentSink(min_area), ComponentSink(min_area)
-        ssim_fake, ssim_real = (SsimSink(), SsimSink()) if a.ssim or a.dtw is not None else (None, None)
+        ssim_fake, ssim_real = ((SsimSink(), SsimSink()) if a.ssim or a.dtw is not None or (a.modes is not None and verifier is None)
+                                else (None, None))
         stroke_fake, stroke_real = (StrokeSink(), StrokeSink()) if a.strokes else (None, None)
         shape_fake, shape_real = (ShapeSink(), ShapeSink()) if a.shape else (None, None)
         fake = generate_samples(generator, a.n_samples, generator.latent_dim, device, a.batch_size,
@@ -870,7 +935,9 @@ def main(argv=None) -> int:
                                   shape_attributes_block(shape_fake, shape_real) if a.shape else None,
                                   kid_permutations=a.verifier_kid,
                                   elastic_similarity=(elastic_similarity_block(ssim_fake, ssim_real, None if a.dtw == "auto" else a.dtw)
-                                                      if a.dtw is not None else None))
+                                                      if a.dtw is not None else None),
+                                  modes=(dict(k=None if a.modes == "auto" else a.modes, generated=ssim_fake, real=ssim_real)
+                                         if a.modes is not None else None))
         report_path = save_evaluation_report(metrics, config, output_dir, checkpoint_path, grid_paths)
         print_summary(metrics)
         print("\nEvaluation complete!")

@@ -417,6 +417,37 @@ def calculate_dtw_nearest_real(generated, real, band: Optional[int] = None) -> D
     return nearest_real_from_best(best.cpu().numpy(), index.cpu().numpy(), loo, g.w)
 
 
+# ---- mode coverage: k-means bins, NDB and JS divergence (utils/modes.py) -------------------------------------------------------
+def mode_features(images: torch.Tensor, verifier=None, max_batch: Optional[int] = None) -> torch.Tensor:
+    """The fp32 rows mode counting works on.  With a ``verifier``: its embeddings (``verifier_embeddings``: the same image
+    formats and chunks as the other verifier metrics).  Without one: modes.pixel_features of the bytes -- uint8 (N, S, S) /
+    (N, 1, S, S) as they are, fp32 in [-1, 1] quantised by the generation rule first --, which needs no network weights."""
+    from .modes import pixel_features
+    if not isinstance(images, torch.Tensor):
+        raise ValueError(f"images must be a tensor, got {type(images).__name__}")
+    dev = next(verifier.parameters()).device if verifier is not None else images.device
+    if dev.type != "cuda":
+        if not torch.cuda.is_available():
+            raise RuntimeError("the modes are counted on a ROCm device ('cuda:N'); there is no CPU path")
+        dev = torch.device("cuda")
+    images = images.to(dev)
+    if verifier is not None:
+        return verifier_embeddings(images, verifier, max_batch)
+    return pixel_features(images if images.dtype == torch.uint8 else quantize_generated(images))
+
+
+def calculate_mode_coverage(real_images: torch.Tensor, fake_images: torch.Tensor, verifier=None, **kw) -> Dict[str, Any]:
+    """Which groups of the real set the generated set produces too rarely or not at all: the number of statistically
+    different bins and the JS divergence of the bin histograms over k-means bins of the real set, beside the real set's own
+    hold-out floor (modes.mode_coverage; ``kw``: its k, seed, alpha, iterations, restarts).  Features: ``mode_features``.
+    -> mode_coverage's dictionary plus 'feature_space' ('verifier' or 'pixels/4') and 'feature_dim'."""
+    from .modes import mode_coverage
+    real, fake = mode_features(real_images, verifier), mode_features(fake_images, verifier)
+    out = mode_coverage(real, fake, **kw)
+    out["feature_space"], out["feature_dim"] = ("verifier" if verifier is not None else "pixels/4"), int(real.shape[1])
+    return out
+
+
 class MetricsTracker:
     """Per-epoch running values and the history of their epoch averages (utils/metrics.py:177-213)."""
 
